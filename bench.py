@@ -1,7 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on BASELINE.json's config.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+plain   : set-up, W untimed + K timed steps of the headline configuration,
+          the result line (`metric`, `value`, `unit`, `ms_per_step`, `dtype`,
+          the configuration); no kernel instrumentation in the timed region.
+--full  : everything below besides: the kernel table and roofline, the
+          stopping-test and time-to-tolerance figures, the other precisions,
+          preconditioners and regions, the SpMV half of the metric, the
+          Kershaw mesh, the collectives, the CPU baseline.
+--dump-outputs DIR: after the timed steps, what they computed -- the solution
+          iterate (float64; a fixed seeded sample of 2^22 points over all
+          ranks when there are more) and the last residual norm -- as
+          DIR/*.npy.
 
 metric : "PCG DOF-updates/sec + SpMV GB/s (%HBM peak), 3D Poisson N=7"
 workload: config C2 per GPU -- 3-D Poisson, 32^3 spectral elements of degree
@@ -99,7 +111,12 @@ def parse():
     ap.add_argument("--flag", action="append", default=[], metavar="NAME=VALUE", help="launch-sequence switch of the host layer (fddh_problem_set_flag) applied to every problem of the run, for A/B runs on one box: e.g. --flag fused_arnoldi_step=0")
     ap.add_argument("--cpu-sample-elements", type=int, default=None, help="elements per direction and rank of the CPU baseline's sample (default: the workload itself up to degree 7 -- 32 = config C2 --, 16 beyond: as many points)")
     ap.add_argument("--cpu-sample-steps", type=int, default=3, help="outer PCG iterations of the sample (one rank at C2: about 6 s each on the box's host)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="besides the headline: kernel table / roofline, time to tolerance, the other legs, the SpMV figures, collectives and the CPU baseline (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed steps computed (solution iterate, last residual norm) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.kernel_table and not args.full:
+        ap.error("--kernel-table is a --full measurement")
+    return args
 
 
 def cpu_baseline(args, world, P):
@@ -267,6 +284,25 @@ class _ThreadRanks:
         return m
 
 
+DUMP_SAMPLE = 1 << 22  # float64 solution entries written at most, over all ranks (32 MiB)
+
+
+def dump_outputs(directory, prob, last_res, rank, world):
+    """What the timed steps computed, as a caller of the stepwise solve receives it: the solution iterate on the rank's
+    points (a fixed seeded sample, in index order, when there are more than DUMP_SAMPLE / ranks) and the last residual
+    norm.  More than one rank: one file per rank."""
+    import numpy as np
+
+    u = prob.pcg_solution()
+    keep = DUMP_SAMPLE // world
+    if u.size > keep:
+        u = u[np.sort(np.random.default_rng(0).choice(u.size, keep, replace=False))]
+    tag = "" if world == 1 else "_rank%d" % rank
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "solution%s.npy" % tag), np.ascontiguousarray(u, dtype=np.float64))
+    np.save(os.path.join(directory, "residual_norm%s.npy" % tag), np.array([last_res], dtype=np.float64))
+
+
 def main():
     args = parse()
     if args.cpu_sample_elements is None:
@@ -381,12 +417,15 @@ def run(args, rank, world, max_over_ranks, comm_label):
     #   composite    the full-domain-decomposition region of every rank: carried in `composite` (no V-cycle, flagged)
     #                and in `reference_default` (V-cycle inside: the configuration the reference runs, BASELINE C5).
     # --composite-headline makes the composite without the V-cycle the headline, as in rounds 1-2.
+    # A plain run builds the headline's region only; --full builds both.
     comp = blk = None
     if world > 1 and not args.no_precond:
-        blk = create(True)
-        if not args.block_local:
+        composite_headline = args.composite_headline and not args.block_local
+        if args.full or not composite_headline:
+            blk = create(True)
+        if composite_headline or (args.full and not args.block_local):
             comp = create(False)
-        prob = comp if (args.composite_headline and comp is not None) else blk
+        prob = comp if composite_headline else blk
     else:
         prob = create(args.block_local)
     progress("problem%s set up" % ("s (block-local and composite)" if comp is not None else ""))
@@ -490,9 +529,68 @@ def run(args, rank, world, max_over_ranks, comm_label):
     # ---------------- headline configuration ----------------
     configure(args.amg, args.amg_precision)
     headline_steps = timed_gmres_steps if args.outer == "gmres" else timed_steps
-    dt, last_res, kernels = headline_steps(args.steps, args.warmup, not args.no_kernel_timing)
+    dt, last_res, kernels = headline_steps(args.steps, args.warmup, args.full and not args.no_kernel_timing)
     value = nodes * args.steps / dt
     progress("headline steps timed: %.3f ms per step" % (dt / args.steps * 1e3))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, prob, last_res, rank, world)
+
+    info = prob.refresh()
+    if args.no_precond:
+        pre_name, pre_text = "none", "no preconditioner"
+    else:
+        pre_name = "fdd_gmres4+amg_vcycle(%d levels, f%d)" % (amg_states[id(prob)]["levels"], args.amg_precision) if args.amg else ("fdd_gmres4" if (composite or world == 1) else "fdd_gmres4 (block-local)")
+        if composite:
+            pre_text = "full-domain-decomposition preconditioner (per rank: %d own + %d ring/extended elements, %d superdomain dofs of %d coarse; inner GMRES(4), polynomial reduction %d)" % (
+                info["num_local_elements"], sub["num_ext_elems"] - info["num_local_elements"], sub["sup_dofs"], sub["coarse_dofs"], args.reduction)
+        elif world > 1:
+            pre_text = "BLOCK-LOCAL FDD preconditioner (own elements only: no neighbour rings / superdomain; inner GMRES(4), polynomial reduction %d)" % args.reduction
+        else:
+            pre_text = "FDD preconditioner (single subdomain = whole domain, inner GMRES(4), polynomial reduction %d)" % args.reduction
+
+    out = {
+        "metric": "PCG DOF-updates/sec + SpMV GB/s (%HBM peak), 3D Poisson N=7",
+        "value": value,
+        "unit": "DOF-updates/s",
+        # a rehearsal's ranks share ONE device: the structured fields say so (ADVICE r3), never an N-GPU weak-scaling point
+        "n_gpus": 1 if rehearsal else world,
+        "ranks": world,
+        "rehearsal": rehearsal,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": None if rehearsal else "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {
+            "workload": f"3D Poisson, {E[0]}x{E[1]}x{E[2]} elements ({e}^3 per GPU), N={N}, " + ("flexible PCG" if args.outer == "fcg" else "flexible GMRES(20)") + " + " + pre_text
+                        + ("" if args.mesh == "box" else f", Kershaw mesh eps = {args.eps}"),
+            "outer": args.outer,
+            "mesh": args.mesh,
+            "elements": list(E),
+            "rank_grid": list(P),
+            "poly_degree": N,
+            "points_per_gpu": info["num_local_points"],
+            "unique_nodes": nodes,
+            "preconditioner": pre_name,
+            "comm": comm_label,
+        },
+        "points_updates_per_s": info["num_local_points"] * world * args.steps / dt,
+        "last_residual_norm": last_res,
+        "setup_s": t_setup,
+    }
+    if comp is not None:
+        out["config"]["composite"] = {k: comp_sub[k] for k in ("num_elems", "num_ext_elems", "num_points", "sub_dofs", "sub_ext_dofs", "interface_dofs", "sup_dofs", "sup_ext_dofs", "unique_dofs", "coarse_dofs", "num_peers")}
+        out["config"]["composite"]["superdomain_levels"] = comp.sub_composite_levels()
+    if not args.full:
+        if world > 1:
+            H.barrier()
+        if rank == 0:
+            print(json.dumps(out))
+        prob.close()
+        return
 
     # the same K steps with a stopping test (one host synchronisation) per step, as a real solve runs them
     if args.outer == "fcg":
@@ -700,50 +798,7 @@ def run(args, rank, world, max_over_ranks, comm_label):
             progress("Kershaw leg: reference default done")
             kp.close()
 
-    info = prob.refresh()
-    if args.no_precond:
-        pre_name, pre_text = "none", "no preconditioner"
-    else:
-        pre_name = "fdd_gmres4+amg_vcycle(%d levels, f%d)" % (amg_states[id(prob)]["levels"], args.amg_precision) if args.amg else ("fdd_gmres4" if (composite or world == 1) else "fdd_gmres4 (block-local)")
-        if composite:
-            pre_text = "full-domain-decomposition preconditioner (per rank: %d own + %d ring/extended elements, %d superdomain dofs of %d coarse; inner GMRES(4), polynomial reduction %d)" % (
-                info["num_local_elements"], sub["num_ext_elems"] - info["num_local_elements"], sub["sup_dofs"], sub["coarse_dofs"], args.reduction)
-        elif world > 1:
-            pre_text = "BLOCK-LOCAL FDD preconditioner (own elements only: no neighbour rings / superdomain; inner GMRES(4), polynomial reduction %d)" % args.reduction
-        else:
-            pre_text = "FDD preconditioner (single subdomain = whole domain, inner GMRES(4), polynomial reduction %d)" % args.reduction
-
-    out = {
-        "metric": "PCG DOF-updates/sec + SpMV GB/s (%HBM peak), 3D Poisson N=7",
-        "value": value,
-        "unit": "DOF-updates/s",
-        # a rehearsal's ranks share ONE device: the structured fields say so (ADVICE r3), never an N-GPU weak-scaling point
-        "n_gpus": 1 if rehearsal else world,
-        "ranks": world,
-        "rehearsal": rehearsal,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": None if rehearsal else "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {
-            "workload": f"3D Poisson, {E[0]}x{E[1]}x{E[2]} elements ({e}^3 per GPU), N={N}, " + ("flexible PCG" if args.outer == "fcg" else "flexible GMRES(20)") + " + " + pre_text
-                        + ("" if args.mesh == "box" else f", Kershaw mesh eps = {args.eps}"),
-            "outer": args.outer,
-            "mesh": args.mesh,
-            "elements": list(E),
-            "rank_grid": list(P),
-            "poly_degree": N,
-            "points_per_gpu": info["num_local_points"],
-            "unique_nodes": nodes,
-            "preconditioner": pre_name,
-            "comm": comm_label,
-        },
-        "points_updates_per_s": info["num_local_points"] * world * args.steps / dt,
-        "last_residual_norm": last_res,
+    out.update({
         "ms_per_step_with_stopping_tests": dt_tests / args.steps * 1e3,
         "to_1e-7": headline_tol,
         "preconditioner_in_f32": headline_f32,
@@ -751,21 +806,17 @@ def run(args, rank, world, max_over_ranks, comm_label):
         "affine_geometry": affine_leg,
         "block_local": block_local_leg,
         "composite": composite_leg,
-        "setup_s": t_setup,
         "roofline": roofline,
         "spmv": spmv,
         "reference_default": reference_default,
         "reference_default_gmres": reference_default_gmres,
         "kershaw": kershaw_leg,
         "kernels": table,
-    }
+    })
     if world > 1:
         # the solve path's collectives alone, with the solve's own sizes and buffers (max over ranks)
         comm = (comp if comp is not None else prob).comm_time(20)
         out["comm_us"] = {k: {"avg_us": max_over_ranks(v["avg_us"]), "bytes": v["bytes"]} for k, v in comm.items()}
-    if comp is not None:
-        out["config"]["composite"] = {k: comp_sub[k] for k in ("num_elems", "num_ext_elems", "num_points", "sub_dofs", "sub_ext_dofs", "interface_dofs", "sup_dofs", "sup_ext_dofs", "unique_dofs", "coarse_dofs", "num_peers")}
-        out["config"]["composite"]["superdomain_levels"] = comp.sub_composite_levels()
 
     progress("device legs done; CPU baseline")
     # rank 0 times the oracle on its host cores while the other ranks wait at the barrier below

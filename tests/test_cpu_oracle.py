@@ -18,12 +18,43 @@ vp = ctypes.c_void_p
 
 
 # ------------------------------------------------------------------ GLL tables
+def _gll_tables_closed_form():
+    """The golden tables against closed-form statements independent of any
+    speclib: nodes -1, the roots of P_N', 1; weights 2 / (N (N+1) P_N(z)^2);
+    D[i, j] = P_N(z_i) / (P_N(z_j) (z_i - z_j)), -+N (N+1) / 4 in the corners;
+    the interpolators as Lagrange products.  To rounding (the roots come from
+    numpy's companion-matrix solver)."""
+    from numpy.polynomial import legendre
+
+    for N in range(1, 16):
+        n = N + 1
+        z, w, D = S.gll(N)
+        PN = legendre.Legendre.basis(N)
+        zz = np.concatenate(([-1.0], np.sort(PN.deriv().roots().real) if N > 1 else [], [1.0]))
+        p = PN(zz)
+        DD = np.zeros((n, n))
+        for i in range(n):
+            for j in range(n):
+                if i != j:
+                    DD[i, j] = p[i] / (p[j] * (zz[i] - zz[j]))
+        DD[0, 0], DD[-1, -1] = -N * (N + 1) / 4.0, N * (N + 1) / 4.0
+        assert np.abs(z - zz).max() < 1e-14 and np.abs(w - 2.0 / (N * (N + 1) * p**2)).max() < 1e-14
+        assert np.abs(D.reshape(n, n) - DD).max() < 1e-11
+    for Nc, Nf in [(3, 7), (1, 7), (5, 7), (1, 3), (9, 15), (14, 15)]:
+        zc, zf = S.gll(Nc)[0], S.gll(Nf)[0]
+        JJ = np.array([[np.prod([(x - zc[m]) / (zc[j] - zc[m]) for m in range(Nc + 1) if m != j]) for j in range(Nc + 1)] for x in zf])
+        assert np.abs(S.J_cf(Nc, Nf).reshape(Nf + 1, Nc + 1) - JJ).max() < 1e-13
+
+
 def test_golden_gll_tables_match_reference_speclib():
     """tests/golden/gll_tables.json is what the reference's own
-    special_functions.f returns (compiled by oracle/Makefile `ref`).  Runs where
-    oracle/_ref exists (build container; the .so also travels to the GPU box)."""
+    special_functions.f returns (compiled by oracle/Makefile `ref`): against
+    their closed forms to rounding everywhere, and bit for bit against that
+    library where oracle/_ref is built (where the reference's source is
+    readable; the .so also travels to the GPU box)."""
+    _gll_tables_closed_form()
     if not os.path.exists(S.SPECLIB_REF_SO):
-        pytest.skip("oracle/_ref/libspeclib_ref.so not built (needs /root/reference)")
+        return
     L = ctypes.CDLL(S.SPECLIB_REF_SO)
     L.hgll_.restype = ctypes.c_double
     for N in range(1, 16):

@@ -294,6 +294,38 @@ def test_stepwise_pcg_equals_the_solver(setup):
         p.close()
 
 
+def test_bench_plain_run_and_its_outputs(setup, tmp_path):
+    """A plain `bench.py` run times the headline steps and nothing else (no --full object in its line); --dump-outputs
+    writes what those steps computed, which is what the stepwise solve run here on the same seeded problem returns."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    out = subprocess.run([sys.executable, os.path.join(S.ROOT, "bench.py"), "--gpus", "1", "--elements", "4", "--degree", "3", "--reduction", "2", "--steps", "3", "--warmup", "2",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "DOF-updates/s" and line["higher_is_better"] is True and line["dtype"] == "f64" and line["metric"].startswith("PCG DOF-updates/sec")
+    assert not set(line) & {"to_1e-7", "ms_per_step_with_stopping_tests", "reference_default", "kershaw", "spmv", "roofline", "kernels", "cpu_baseline", "comm_us"}
+    u, r = np.load(tmp_path / "solution.npy"), np.load(tmp_path / "residual_norm.npy")
+    assert u.dtype == np.float64 and r.dtype == np.float64 and r.tolist() == [line["last_residual_norm"]]
+    p = H.Problem.box((4, 4, 4), (1, 1, 1), 3, 2, True)
+    try:
+        p.set_flag("sub_use_preconditioner", 0)
+        p.set_flag("preconditioner_precision", 64)
+        _, f = p.make_rhs(function_id=4, seed=1234)
+        p.pcg_begin(f)
+        p.pcg_steps(2)
+        last = p.pcg_steps(3)
+        mine = p.pcg_solution()
+        assert u.shape == mine.shape == (line["config"]["points_per_gpu"],)
+        assert abs(last - r[0]) <= 1e-12 * r[0] and np.abs(mine - u).max() <= 1e-12 * np.abs(u).max()
+    finally:
+        p.close()
+
+
 def test_mesh_file_roundtrip(setup, tmp_path):
     """The reference's on-disk input (domain.tpp:45-224): write the box mesh as
     a Nek5000-style file set, read it back through Domain::initialize(dir, N)."""

@@ -6,7 +6,7 @@ root=$(pwd)
 out=$root/gpurun_out/r04_headline_gaps
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $out/trace -o run -- python3 $root/bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-reference-default --no-time-to-tolerance --no-stencil --no-kershaw --no-kernel-timing > $out/run.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $out/trace -o run -- python3 $root/bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-reference-default --no-time-to-tolerance --no-stencil --no-kershaw --no-kernel-timing > $out/run.log 2>&1
 cd $root
 csv=$(find $out/trace -name '*kernel_trace.csv' | head -n 1)
 python3 tools/kernel_gaps.py $csv > $out/kernel_gaps_headline.md

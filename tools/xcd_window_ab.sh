@@ -5,7 +5,7 @@
 what=${1:-both}
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
-common="--steps 6 --warmup 2 --no-reference-default --no-time-to-tolerance --no-stencil --no-cpu-baseline --no-kershaw --kernel-table"
+common="--full --steps 6 --warmup 2 --no-reference-default --no-time-to-tolerance --no-stencil --no-cpu-baseline --no-kershaw --kernel-table"
 show() { python3 - "$1" "$2" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
