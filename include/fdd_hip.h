@@ -398,6 +398,56 @@ int fdd_interface_unpack(double *prefix, const double *slots, const int *slot_of
 int fdd_interface_gather(double *buf, const int *index, int n, const double *a, const double *b, void *stream);
 int fdd_interface_sum(double *a, double *b, const int *ptr, const int *col, int rows, const double *buf, void *stream);
 
+/* ------------------------------------------------------------------ */
+/* AMG setup on the device (csrc/fdd_amg_setup.hip): the leading levels */
+/* of the low-order hierarchy, bit-identical to host/low_order.hpp      */
+/* ------------------------------------------------------------------ */
+/* Every sparse result is built count -> row pointers -> fill.  Matrices are CSR with int indices in device memory.
+ * row_pointers: ptr_host[0] = 0, ptr_host[i + 1] = ptr_host[i] + row_len[i], scanned on the host in 64-bit arithmetic
+ * (FDD_ERR_INVALID_ARGUMENT when the total leaves the int range; nothing wraps), and copied to ptr (device, rows + 1).
+ * Blocking. */
+int fdd_amg_setup_row_pointers(int *ptr, int *ptr_host, const int *row_len, int rows, void *stream);
+/* C = A B in the order of low_order::multiply (Gustavson: acc[j] starts at 0.0 and takes a_ik * b_kj in the order of A's
+ * row, then of B's row); output columns ascending.  B's rows must be sorted by column.  cursor_ws: nnz(A) ints.  The col /
+ * val arrays of a matrix without entries may be NULL. */
+int fdd_amg_setup_spgemm_count(int *row_len, int *cursor_ws, const int *A_ptr, const int *A_col, const int *B_ptr, const int *B_col, int a_rows, int b_rows, void *stream);
+int fdd_amg_setup_spgemm_fill(int *C_col, double *C_val, int *cursor_ws, const int *C_ptr, const int *A_ptr, const int *A_col, const double *A_val, const int *B_ptr, const int *B_col, const double *B_val, int a_rows, int b_rows, void *stream);
+/* T = A^T, the stable counting sort of low_order::transpose: every row of T in A's row order, values only move.
+ * drop_tol >= 0 keeps the entries with |a| > drop_tol only (CSR_Matrix::transpose); < 0 keeps all.  A_val / T_val may be
+ * NULL (pattern only).  row_len: a_cols ints (zeroed here); cursor_ws: a_cols ints; src_ws: nnz_t ints. */
+int fdd_amg_setup_transpose_count(int *row_len, const int *A_ptr, const int *A_col, const double *A_val, int a_rows, int a_cols, double drop_tol, void *stream);
+int fdd_amg_setup_transpose_fill(int *T_col, double *T_val, int *cursor_ws, int *src_ws, const int *T_ptr, const int *A_ptr, const int *A_col, const double *A_val, int a_rows, int a_cols, int nnz_t, double drop_tol, void *stream);
+/* low_order::assemble_fem: the P1 stiffness of the 6 tetrahedra of every GLL sub-cell.  stencils: per element point
+ * (element-major, x fastest) its row's 27 neighbour slots K[27 * point + s] and their `touched` bits mask[point], summed in
+ * the host's order (sz, sy, sx, t).  count / fill: the rows of the dofs from the stencils of their points (dof_ptr /
+ * dof_points: the ascending points of every dof, the transpose of point_dof), as from_triplets merges them. */
+int fdd_amg_setup_fem_stencils(double *K, unsigned int *mask, const double *x, const double *y, const double *z, const int *point_dof, int poly_degree, int num_elements, double epsilon, void *stream);
+int fdd_amg_setup_fem_count(int *row_len, const int *dof_ptr, const int *dof_points, const unsigned int *mask, const int *point_dof, int poly_degree, int num_dofs, void *stream);
+int fdd_amg_setup_fem_fill(int *A_col, double *A_val, const int *A_ptr, const int *dof_ptr, const int *dof_points, const unsigned int *mask, const double *K, const int *point_dof, int poly_degree, int num_dofs, void *stream);
+/* D[i] = 1 / sqrt(a_ii) (a_ii = 0.0 where row i has no diagonal entry), as low_order::build computes it */
+int fdd_amg_setup_inv_sqrt_diagonal(double *D, const int *A_ptr, const int *A_col, const double *A_val, int rows, void *stream);
+/* flag (device int) = 1 if every one of the nnz values is exactly 1.0, else 0 */
+int fdd_amg_setup_unit_values(int *flag, const double *val, long long nnz, void *stream);
+/* One geometric level (low_order::geometric_level) of a conforming 3-D lattice given as its point -> dof array point_dof
+ * (num_elements * n^3 points, -1: no dof).  keep (m), lo, hi, wl (n each) are HOST arrays: the nodes the coarser lattice
+ * keeps and the 1-D interpolation of every node (n <= 32).  In order:
+ *   lattice_dofs          first[d] = the first point of dof d (INT_MAX: none), kept[d] = 1 where a point of d is kept in
+ *                         every direction; num_points < 2^31
+ *   lattice_coarse_flags  flag[d] = 1 for the dofs that stay (no point, or kept) -> fdd_amg_setup_row_pointers -> cstart
+ *   lattice_cmap          cmap[d] = cstart[d] for those, -1 otherwise; owner_dof[first[d]] = d (-1 elsewhere, num_points
+ *                         entries); *unplaced (device int) = 1 if some dof has no point
+ *   lattice_interp_count / _fill   the rows of P (num_dofs x coarse dofs): row lengths (-1 where a kept node's dof is not
+ *                         kept, refused by row_pointers), then columns and values
+ *   lattice_coarse_points the coarser lattice's point -> coarse dof array (num_elements * m^3 points) */
+int fdd_amg_setup_lattice_dofs(int *first, int *kept, const int *point_dof, long long num_elements, int num_dofs, int n, int m, const int *keep, const int *lo, const int *hi, const double *wl, void *stream);
+int fdd_amg_setup_lattice_coarse_flags(int *flag, const int *first, const int *kept, int num_dofs, void *stream);
+int fdd_amg_setup_lattice_cmap(int *cmap, int *owner_dof, int *unplaced, const int *cstart, const int *first, const int *kept, long long num_points, int num_dofs, void *stream);
+int fdd_amg_setup_lattice_interp_count(int *row_len, const int *cmap, const int *first, const int *point_dof, int num_dofs, int n, int m, const int *keep, const int *lo, const int *hi, const double *wl, void *stream);
+int fdd_amg_setup_lattice_interp_fill(int *P_col, double *P_val, const int *P_ptr, const int *cmap, const int *first, const int *point_dof, int num_dofs, int n, int m, const int *keep, const int *lo, const int *hi, const double *wl, void *stream);
+int fdd_amg_setup_lattice_coarse_points(int *coarse_point_dof, const int *point_dof, const int *cmap, long long num_elements, int n, int m, const int *keep, const int *lo, const int *hi, const double *wl, void *stream);
+/* free and total device memory (hipMemGetInfo): the setup's peak HBM under FDD_SETUP_TIMING */
+int fdd_amg_setup_memory_info(size_t *free_bytes, size_t *total_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -180,7 +180,12 @@ int fddh_problem_set_options(fddh_problem *p, int max_iterations, double toleran
  *                              this build, not in the reference (host/subdomain.hpp)
  *   "amg_graph"                1: the V-cycle is replayed as one hipGraph when the stream allows capture (default)
  *   "amg_fused_smoother"       1: the smoother's element-wise kernels run as SpMV epilogues, bit-identical (default); 0: the reference's launch sequence 
- *   "amg_precision"            64 (default) or 32: the reference's `Float` (AMG/config.hpp:4): the V-cycle in double or in float */
+ *   "amg_precision"            64 (default) or 32: the reference's `Float` (AMG/config.hpp:4): the V-cycle in double or in float
+ *   "amg_device_setup"         0 (default): the low-order AMG hierarchy is built on the host threads; 1: the FEM matrix and
+ *                              every level coarsened on the lattice are built on the device and stay in HBM (the first level
+ *                              that is not comes back to the host loop), bit-identical to the host build.  Applies to
+ *                              fddh_problem_amg_build and to the build on first use; a composite region builds on the host
+ *                              and says so.  Fails, naming the entry, when the kernel library lacks an fdd_amg_setup_* entry. */
 /* Flag "affine_geometry" (an option of this build, off by default; the reference always streams the six factor
  * arrays): after fddh_problem_set_flag(p, "affine_geometry", 1), which of the operators run on the kernel that forms the
  * factors from six numbers per element (fdd_hip.h: fdd_stiffness_matrix_affine) -- the fine Domain's node-space operator,
@@ -205,6 +210,10 @@ int fddh_problem_amg_apply(fddh_problem *p, const double *r, double *z);
  * subdomain.tpp:3383-3549), and attach it.  coarsest_size / strength <= 0 take the defaults (400 rows, 0.08). */
 int fddh_problem_amg_build(fddh_problem *p, int coarsest_size, double strength, int smooth_prolongator, int verbose, int *num_levels);
 int fddh_problem_amg_level_info(const fddh_problem *p, int level, int *n, int *nnz_A, int *n_coarse, int *nnz_P);
+/* the last hierarchy build (explicit or on first use): on how many of its levels the matrix A was computed on the device
+ * ("amg_device_setup": the FEM matrix, the Galerkin products of the lattice levels, the hand-off level's included; 0 for a
+ * host build) and its wall time in seconds (0 and 0 before any build).  Either argument may be NULL. */
+int fddh_problem_amg_setup_info(const fddh_problem *p, int *levels_built_on_device, double *setup_seconds);
 /* 1 where the interpolator of `level` (to level + 1) is applied matrix-free: a geometric level of fddh_problem_amg_build's own
  * hierarchy on a conforming 3-D region with 8 or 16 lattice nodes per direction (fdd_lattice_prolong / _restrict,
  * include/fdd_hip.h), and the flag "amg_matrix_free_transfer" (default 1) on; 0: two SpMVs with the CSR interpolator */

@@ -179,6 +179,15 @@ class Hierarchy
     fdd::memory coarse_inverse_val32;
     fdd_csr_plan *coarse_plan32 = nullptr;
 
+    // f32 copy of n doubles in HBM (the levels built on the device have no host values): the same round-to-nearest cast
+    static fdd::memory to_f32_device(const fdd::memory &v, size_t n)
+    {
+        fdd::memory m = fdd::dev().malloc<float>(std::max<size_t>(n, 1));
+        if (n > 0) FDD_CALL(fdd_sub_copy_f32_f64(m.as<float>(), v.as<double>(), (int)n, fdd::dev().stream));
+        return m;
+    }
+    static fdd::memory to_f32(const CSR_Matrix<double> &M) { return M.host_mirrors() ? to_f32(M.val_hst) : to_f32_device(M.val, (size_t)M.num_nnz); }
+
     template <typename Vec>
     static fdd::memory to_f32(const Vec &v)
     {
@@ -202,12 +211,12 @@ class Hierarchy
         if (ready32) return;
         for (Level &L : levels)
         {
-            L.A_val32 = to_f32(L.A.val_hst);
+            L.A_val32 = to_f32(L.A);
             blocked_plan(&L.A_plan32, L.A, L.A_val32);
             if (L.P.num_rows > 0 and not L.P.ptr_hst.empty())
             {
-                L.P_val32 = to_f32(L.P.val_hst);
-                L.R_val32 = to_f32(L.R.val_hst);
+                L.P_val32 = to_f32(L.P);
+                L.R_val32 = to_f32(L.R);
                 blocked_plan(&L.P_plan32, L.P, L.P_val32);
                 blocked_plan(&L.R_plan32, L.R, L.R_val32);
             }
@@ -217,7 +226,7 @@ class Hierarchy
                 L.T.gather_val32 = to_f32(L.T.gather.val_hst);
                 blocked_plan(&L.T.gather_plan32, L.T.gather, L.T.gather_val32);
             }
-            L.D_val32 = to_f32(L.D_hst);
+            L.D_val32 = L.D_hst.empty() ? to_f32_device(L.D_val, (size_t)L.n) : to_f32(L.D_hst);
             for (fdd::memory *m : {&L.f32, &L.u32, &L.r32, &L.v32, &L.work32}) *m = fdd::dev().malloc<float>(L.n);
         }
         coarse_inverse_val32 = to_f32(coarse_inverse.val_hst);
@@ -406,6 +415,20 @@ class Hierarchy
         L.A.adopt_csr(n, n, std::move(A_ptr), std::move(A_col), std::move(A_val));
         if (has_P) L.P.adopt_csr(n, n_coarse, std::move(P_ptr), std::move(P_col), std::move(P_val));
         finish_level(L, D_val, coefs_, has_P);
+    }
+
+    // a level built in HBM (Subdomain::amg_build with "amg_device_setup"): A, D, the interpolator P and R = P^T (as
+    // CSR_Matrix::transpose makes it) are adopted as they are; the host keeps their row pointers only
+    void add_level_device(int n, std::vector<int> &&A_ptr_hst, fdd::memory A_ptr, fdd::memory A_col, fdd::memory A_val, fdd::memory D_val, const double *coefs_, int n_coarse, std::vector<int> &&P_ptr_hst,
+                          fdd::memory P_ptr, fdd::memory P_col, fdd::memory P_val, std::vector<int> &&R_ptr_hst, fdd::memory R_ptr, fdd::memory R_col, fdd::memory R_val)
+    {
+        Level &L = new_level(n);
+        L.A.adopt_device(n, n, std::move(A_ptr_hst), A_ptr, A_col, A_val);
+        L.P.adopt_device(n, n_coarse, std::move(P_ptr_hst), P_ptr, P_col, P_val);
+        L.R.adopt_device(n_coarse, n, std::move(R_ptr_hst), R_ptr, R_col, R_val);
+        L.D_val = D_val;
+        L.coefs.assign(coefs_, coefs_ + cheby_order);
+        for (fdd::memory *m : {&L.f, &L.u, &L.r, &L.v, &L.w, &L.work}) *m = fdd::dev().malloc<double>(n);
     }
 
   private:

@@ -188,6 +188,43 @@ class CSR_Matrix
         upload();
     }
 
+    // the same for arrays that were built in HBM (the device AMG setup): col / val stay device-only (col_hst / val_hst
+    // empty; download_host() fetches them), the host keeps the row pointers the SpMV plans are made from
+    void adopt_device(int num_rows_, int num_cols_, std::vector<int> &&ptr_, fdd::memory ptr_dev, fdd::memory col_dev, fdd::memory val_dev)
+    {
+        initialize(num_rows_, num_cols_);
+        if ((num_rows == 0) or (num_cols == 0) or (ptr_[num_rows] == 0))
+        {
+            for (fdd::memory *m : {&ptr_dev, &col_dev, &val_dev}) m->free();
+            return;
+        }
+        ptr_hst = std::move(ptr_);
+        col_hst.clear();
+        val_hst.clear();
+        num_nnz = ptr_hst[num_rows];
+        ptr = ptr_dev;
+        col = col_dev;
+        val = val_dev;
+        {
+            fdd::memory flag = fdd::dev().malloc<int>(1);
+            int unit = 0;
+            FDD_CALL(fdd_amg_setup_unit_values(flag.as<int>(), val.as<double>(), (long long)num_nnz, fdd::dev().stream));
+            flag.copyTo(&unit, sizeof(int));
+            flag.free();
+            unit_values = unit != 0;
+        }
+        is_identity = unit_values and (num_rows == num_cols) and (num_nnz == num_rows);
+        if (is_identity)
+        {
+            std::vector<int> c((size_t)num_nnz);
+            col.copyTo(c.data(), (size_t)num_nnz * sizeof(int));
+            for (int i = 0; is_identity and i < num_rows; i++)
+                if (c[(size_t)i] != i) is_identity = false;
+        }
+        make_plan();
+    }
+    bool host_mirrors() const { return (int)col_hst.size() == num_nnz; }
+
     // y = alpha*A*x + beta*y (AMG::CSR_Matrix::matvec, AMG/csr_matrix.cpp:129-131); beta == 0 never reads y
     void matvec(fdd::memory &y, fdd::memory &x, double alpha, double beta)
     {
@@ -269,7 +306,12 @@ class CSR_Matrix
         ptr.copyFrom(ptr_hst.data(), (num_rows + 1) * sizeof(int));
         col.copyFrom(col_hst.data(), num_nnz * sizeof(int));
         val.copyFrom(val_hst.data(), num_nnz * sizeof(DType));
+        make_plan();
+    }
 
+    // the SpMV plan of the device arrays (from the host row pointers)
+    void make_plan()
+    {
         if (plan) FDD_CALL(fdd_csr_plan_destroy(plan));
         FDD_CALL(fdd_csr_plan_create(&plan, ptr_hst.data(), num_rows, num_cols, num_nnz));
         FDD_CALL(fdd_csr_plan_kind(plan, &plan_kind));

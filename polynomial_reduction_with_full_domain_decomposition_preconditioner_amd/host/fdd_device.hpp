@@ -20,8 +20,47 @@
 
 #include "fdd_hip.h"
 
+// The AMG setup entries (fdd_hip.h, "AMG setup on the device") are referenced weakly: a kernel library without them
+// (an older libfdd_hip, a CPU stand-in of its C-ABI) still loads, and the switch that needs them ("amg_device_setup")
+// refuses to turn on, naming the missing entry (missing_amg_setup_entry).
+#pragma weak fdd_amg_setup_row_pointers
+#pragma weak fdd_amg_setup_spgemm_count
+#pragma weak fdd_amg_setup_spgemm_fill
+#pragma weak fdd_amg_setup_transpose_count
+#pragma weak fdd_amg_setup_transpose_fill
+#pragma weak fdd_amg_setup_fem_stencils
+#pragma weak fdd_amg_setup_fem_count
+#pragma weak fdd_amg_setup_fem_fill
+#pragma weak fdd_amg_setup_inv_sqrt_diagonal
+#pragma weak fdd_amg_setup_unit_values
+#pragma weak fdd_amg_setup_lattice_dofs
+#pragma weak fdd_amg_setup_lattice_coarse_flags
+#pragma weak fdd_amg_setup_lattice_cmap
+#pragma weak fdd_amg_setup_lattice_interp_count
+#pragma weak fdd_amg_setup_lattice_interp_fill
+#pragma weak fdd_amg_setup_lattice_coarse_points
+#pragma weak fdd_amg_setup_memory_info
+
 namespace fdd
 {
+
+// the first AMG setup entry the loaded kernel library does not export, or nullptr
+inline const char *missing_amg_setup_entry()
+{
+#define FDD_SETUP_ENTRY(name) {(const void *)&name, #name}
+    const struct
+    {
+        const void *fn;
+        const char *name;
+    } entries[] = {FDD_SETUP_ENTRY(fdd_amg_setup_row_pointers), FDD_SETUP_ENTRY(fdd_amg_setup_spgemm_count),    FDD_SETUP_ENTRY(fdd_amg_setup_spgemm_fill),
+                   FDD_SETUP_ENTRY(fdd_amg_setup_transpose_count), FDD_SETUP_ENTRY(fdd_amg_setup_transpose_fill), FDD_SETUP_ENTRY(fdd_amg_setup_fem_stencils),
+                   FDD_SETUP_ENTRY(fdd_amg_setup_fem_count),    FDD_SETUP_ENTRY(fdd_amg_setup_fem_fill),        FDD_SETUP_ENTRY(fdd_amg_setup_inv_sqrt_diagonal),
+                   FDD_SETUP_ENTRY(fdd_amg_setup_unit_values), FDD_SETUP_ENTRY(fdd_amg_setup_lattice_dofs), FDD_SETUP_ENTRY(fdd_amg_setup_lattice_coarse_flags), FDD_SETUP_ENTRY(fdd_amg_setup_lattice_cmap), FDD_SETUP_ENTRY(fdd_amg_setup_lattice_interp_count), FDD_SETUP_ENTRY(fdd_amg_setup_lattice_interp_fill), FDD_SETUP_ENTRY(fdd_amg_setup_lattice_coarse_points), FDD_SETUP_ENTRY(fdd_amg_setup_memory_info)};
+#undef FDD_SETUP_ENTRY
+    for (const auto &e : entries)
+        if (e.fn == nullptr) return e.name;
+    return nullptr;
+}
 
 inline void check(int rc, const char *what)
 {

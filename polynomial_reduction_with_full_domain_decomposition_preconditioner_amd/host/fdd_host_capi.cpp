@@ -995,6 +995,15 @@ int fddh_problem_set_flag(fddh_problem *p, const char *name, int value)
             for (auto &kv : p->domains) kv.second.mfma_stiffness = value != 0;
             if (p->subdomain) p->subdomain->mfma_stiffness = value != 0;
         }
+        else if (s == "amg_device_setup")
+        {
+            // build the FEM matrix and the lattice levels of the AMG hierarchy in HBM (Subdomain::amg_build); needs the
+            // fdd_amg_setup_* entries of the kernel library
+            if (!p->subdomain) return fail("problem was created without a Subdomain");
+            if (value != 0)
+                if (const char *missing = fdd::missing_amg_setup_entry()) return fail("amg_device_setup needs %s, which the loaded kernel library does not export", missing);
+            p->subdomain->amg_device_setup = value != 0;
+        }
         else if (s == "sub_use_preconditioner")
         {
             if (!p->subdomain) return fail("problem was created without a Subdomain");
@@ -1163,6 +1172,23 @@ int fddh_problem_amg_level_info(const fddh_problem *p, int level, int *n, int *n
     }
 }
 
+int fddh_problem_amg_setup_info(const fddh_problem *p, int *levels_built_on_device, double *setup_seconds)
+{
+    try
+    {
+        if (int rc = rank_check(p)) return rc;
+        if (!p) return fail("null argument");
+        if (!p->subdomain) return fail("problem was created without a Subdomain");
+        if (levels_built_on_device) *levels_built_on_device = p->subdomain->amg_levels_on_device;
+        if (setup_seconds) *setup_seconds = p->subdomain->amg_setup_seconds;
+        return 0;
+    }
+    catch (const std::exception &e)
+    {
+        return fail("%s", e.what());
+    }
+}
+
 int fddh_problem_amg_level_transfer(const fddh_problem *p, int level, int *matrix_free)
 {
     try
@@ -1189,16 +1215,27 @@ int fddh_problem_amg_level_arrays(const fddh_problem *cp, int level, int *A_ptr,
         auto &lv = p->subdomain->amg_hierarchy.levels;
         if (level < 0 || level >= (int)lv.size()) return fail("the hierarchy has %d levels", (int)lv.size());
         amg::Level &L = lv[level];
+        // col / val of a level built in HBM have no host copy: read from the device arrays
+        auto fetch = [](CSR_Matrix<double> &M, int *col, double *val) {
+            if (M.host_mirrors())
+            {
+                if (col) memcpy(col, M.col_hst.data(), M.col_hst.size() * sizeof(int));
+                if (val) memcpy(val, M.val_hst.data(), M.val_hst.size() * sizeof(double));
+            }
+            else if (M.num_nnz > 0)
+            {
+                if (col) M.col.copyTo(col, (size_t)M.num_nnz * sizeof(int));
+                if (val) M.val.copyTo(val, (size_t)M.num_nnz * sizeof(double));
+            }
+        };
         if (A_ptr) memcpy(A_ptr, L.A.ptr_hst.data(), L.A.ptr_hst.size() * sizeof(int));
-        if (A_col) memcpy(A_col, L.A.col_hst.data(), L.A.col_hst.size() * sizeof(int));
-        if (A_val) memcpy(A_val, L.A.val_hst.data(), L.A.val_hst.size() * sizeof(double));
+        fetch(L.A, A_col, A_val);
         if (D_val) L.D_val.copyTo(D_val, (size_t)L.n * sizeof(double));
         if (coefs) memcpy(coefs, L.coefs.data(), L.coefs.size() * sizeof(double));
         if (L.P.num_rows > 0)
         {
             if (P_ptr) memcpy(P_ptr, L.P.ptr_hst.data(), L.P.ptr_hst.size() * sizeof(int));
-            if (P_col) memcpy(P_col, L.P.col_hst.data(), L.P.col_hst.size() * sizeof(int));
-            if (P_val) memcpy(P_val, L.P.val_hst.data(), L.P.val_hst.size() * sizeof(double));
+            fetch(L.P, P_col, P_val);
         }
         return 0;
     }

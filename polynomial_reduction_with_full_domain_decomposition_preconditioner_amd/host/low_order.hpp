@@ -923,13 +923,45 @@ inline HostCSR geometric_level(const Lattice &fine, int num_dofs, Lattice &coars
     return P;
 }
 
-inline std::vector<Level> build(HostCSR A0, const Options &o, bool verbose = false, Lattice lattice = Lattice())
+// What a level of the hierarchy does, decided from its size, its index and the lattice left: shared by build() below and
+// by the device loop of Subdomain::amg_build, so that both make the same decisions (the FDD_TUNE_AMG_* overrides included)
+struct LevelPlan
+{
+    double eig_ratio = 0.3; // lower end of the Chebyshev smoother's interval (the level's coefs)
+    bool last = false;      // the coarsest level: no interpolator
+    bool geometric = false; // coarsened on the lattice (geometric_level); otherwise, unless last, by aggregation
+};
+
+inline bool geometric_levels_enabled(const Options &o)
+{
+    static const int geometric_env = getenv("FDD_TUNE_AMG_GEOMETRIC") ? atoi(getenv("FDD_TUNE_AMG_GEOMETRIC")) : -1; // development override
+    return geometric_env >= 0 ? geometric_env != 0 : o.geometric_levels;
+}
+
+inline LevelPlan plan_level(const Options &o, int l, int n, const Lattice &lattice, int geometric_done)
+{
+    LevelPlan plan;
+    const bool geometric = geometric_levels_enabled(o);
+    // the levels that are coarsened on the lattice lose 2.33 nodes per direction in one step (N = 7), more than an
+    // aggregation level: the smoother in front of such a step has to reach further down the spectrum
+    static const double geo_ratio_env = getenv("FDD_TUNE_AMG_GEOMETRIC_EIG_RATIO") ? atof(getenv("FDD_TUNE_AMG_GEOMETRIC_EIG_RATIO")) : 0.0; // development override
+    const bool lattice_next = geometric and lattice.active(geometric_done > 0 ? 3 : o.geometric_min_nodes) and lattice.rows.cols == n and n > o.coarsest_size;
+    plan.eig_ratio = lattice_next ? (geo_ratio_env > 0.0 ? geo_ratio_env : o.geometric_eig_ratio) : o.eig_ratio;
+    plan.last = (n <= o.coarsest_size) or (l == o.max_levels - 1);
+    static const int min_nodes_env = getenv("FDD_TUNE_AMG_GEOMETRIC_MIN_NODES") ? atoi(getenv("FDD_TUNE_AMG_GEOMETRIC_MIN_NODES")) : 0; // development override
+    // a lattice of fewer than geometric_min_nodes nodes is coarsened geometrically only as the continuation of a
+    // geometric level above it (N = 7: 8 -> 4 -> 2 nodes); on its own (degrees 2 and 3) the one factor-3 step is weaker
+    // than the aggregation (the rod of DESIGN 5.3, N = 2: 23 against 19 iterations)
+    plan.geometric = not plan.last and geometric and lattice.active(geometric_done > 0 ? 3 : (min_nodes_env > 0 ? min_nodes_env : o.geometric_min_nodes)) and lattice.rows.cols == n;
+    return plan;
+}
+
+// first_level / geometric_done: where a hierarchy whose leading levels were built elsewhere (on the device) continues --
+// A0 is level first_level's matrix, `lattice` what is left of the lattice after geometric_done geometric levels
+inline std::vector<Level> build(HostCSR A0, const Options &o, bool verbose = false, Lattice lattice = Lattice(), int first_level = 0, int geometric_done = 0)
 {
     std::vector<Level> levels;
     HostCSR A = std::move(A0);
-    static const int geometric_env = getenv("FDD_TUNE_AMG_GEOMETRIC") ? atoi(getenv("FDD_TUNE_AMG_GEOMETRIC")) : -1; // development override
-    const bool geometric = geometric_env >= 0 ? geometric_env != 0 : o.geometric_levels;
-    int geometric_done = 0;
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t_mark = now();
     auto lap = [&](const char *what, int l) {
@@ -937,7 +969,7 @@ inline std::vector<Level> build(HostCSR A0, const Options &o, bool verbose = fal
         if (verbose) printf("low_order:   level %d %-24s %7.3f s\n", l, what, t - t_mark);
         t_mark = t;
     };
-    for (int l = 0; l < o.max_levels; l++)
+    for (int l = first_level; l < o.max_levels; l++)
     {
         Level L;
         const int n = A.rows;
@@ -947,25 +979,18 @@ inline std::vector<Level> build(HostCSR A0, const Options &o, bool verbose = fal
             for (long long i = i0; i < i1; i++) L.D[i] = 1.0 / std::sqrt(d[i]);
         });
         const double lmax = o.lambda_max ? o.lambda_max(A, L.D, o.power_iterations) : max_eigenvalue_scaled(A, L.D, o.power_iterations);
+        const LevelPlan plan = plan_level(o, l, n, lattice, geometric_done);
         {
-            // the levels that are coarsened on the lattice lose 2.33 nodes per direction in one step (N = 7), more than an
-            // aggregation level: the smoother in front of such a step has to reach further down the spectrum
-            static const double geo_ratio_env = getenv("FDD_TUNE_AMG_GEOMETRIC_EIG_RATIO") ? atof(getenv("FDD_TUNE_AMG_GEOMETRIC_EIG_RATIO")) : 0.0; // development override
             Options ol = o;
-            const bool lattice_next = geometric and lattice.active(geometric_done > 0 ? 3 : o.geometric_min_nodes) and lattice.rows.cols == n and n > o.coarsest_size;
-            if (lattice_next) ol.eig_ratio = geo_ratio_env > 0.0 ? geo_ratio_env : o.geometric_eig_ratio;
+            ol.eig_ratio = plan.eig_ratio;
             L.coefs = chebyshev_coefficients(lmax, ol);
         }
         if (verbose) printf("low_order: level %d rows %d nnz %lld lambda_max(DAD) %.4f\n", l, n, A.nnz(), lmax);
         lap("diagonal + lambda_max", l);
 
-        bool last = (n <= o.coarsest_size) or (l == o.max_levels - 1);
+        bool last = plan.last;
         HostCSR P;
-        static const int min_nodes_env = getenv("FDD_TUNE_AMG_GEOMETRIC_MIN_NODES") ? atoi(getenv("FDD_TUNE_AMG_GEOMETRIC_MIN_NODES")) : 0; // development override
-        // a lattice of fewer than geometric_min_nodes nodes is coarsened geometrically only as the continuation of a
-        // geometric level above it (N = 7: 8 -> 4 -> 2 nodes); on its own (degrees 2 and 3) the one factor-3 step is weaker
-        // than the aggregation (the rod of DESIGN 5.3, N = 2: 23 against 19 iterations)
-        if (not last and geometric and lattice.active(geometric_done > 0 ? 3 : (min_nodes_env > 0 ? min_nodes_env : o.geometric_min_nodes)) and lattice.rows.cols == n)
+        if (plan.geometric)
         {
             geometric_done++;
             Lattice next;

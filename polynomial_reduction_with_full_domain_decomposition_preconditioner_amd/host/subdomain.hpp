@@ -49,6 +49,7 @@
 #include <vector>
 
 #include "amg.hpp"
+#include "amg_device_setup.hpp"
 #include "composite.hpp"
 #include "config.hpp"
 #include "csr_matrix.hpp"
@@ -1266,20 +1267,34 @@ class Subdomain
         static const bool timing = getenv("FDD_SETUP_TIMING") != nullptr;
         const auto clock = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         const double t0 = clock();
-        fdd::memory ptr = dv.malloc<int>((size_t)n + 1), col = dv.malloc<int>(nnz), val = dv.malloc<double>(nnz);
+        fdd::memory ptr = dv.malloc<int>((size_t)n + 1), col = dv.malloc<int>(nnz), val = dv.malloc<double>(nnz), Dd = dv.malloc<double>(n);
         ptr.copyFrom(M.ptr.data(), ((size_t)n + 1) * sizeof(int));
         col.copyFrom(M.col.data(), nnz * sizeof(int));
         val.copyFrom(M.val.data(), nnz * sizeof(double));
+        Dd.copyFrom(D.data(), (size_t)n * sizeof(double));
+        if (timing and n > 100000) printf("low_order:   lambda_max on the device: matrix up %.3f s\n", clock() - t0);
+        const double lambda = device_lambda_max(n, M.ptr, ptr, col, val, Dd, iterations);
+        for (fdd::memory *m : {&ptr, &col, &val, &Dd}) m->free();
+        return lambda;
+    }
+    // the same on a matrix and a D that are in HBM already (ptr_hst: the host's copy of the row pointers)
+    double device_lambda_max(int n, const std::vector<int> &ptr_hst, const fdd::memory &ptr, const fdd::memory &col, const fdd::memory &val, const fdd::memory &Dd, int iterations)
+    {
+        const size_t nnz = (size_t)ptr_hst[(size_t)n];
+        if (n == 0 or nnz == 0 or iterations <= 0) return 1.0;
+        fdd::device_t &dv = fdd::dev();
+        void *stream = dv.stream;
+        static const bool timing = getenv("FDD_SETUP_TIMING") != nullptr;
+        const auto clock = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         const double t1 = clock();
         fdd_csr_plan *plan = nullptr;
-        FDD_CALL(fdd_csr_plan_create(&plan, M.ptr.data(), n, n, (int)nnz));
+        FDD_CALL(fdd_csr_plan_create(&plan, ptr_hst.data(), n, n, (int)nnz));
         const double t2 = clock();
-        fdd::memory v = dv.malloc<double>(n), vn = dv.malloc<double>(n), t = dv.malloc<double>(n), w = dv.malloc<double>(n), Dd = dv.malloc<double>(n);
+        fdd::memory v = dv.malloc<double>(n), vn = dv.malloc<double>(n), t = dv.malloc<double>(n), w = dv.malloc<double>(n);
         fdd::memory ws = dv.malloc<double>(fdd_reduce_workspace_doubles()), sc = dv.malloc<double>(2);
         {
             const std::vector<double> start = fdd::low_order::power_iteration_start(n);
             v.copyFrom(start.data(), (size_t)n * sizeof(double));
-            Dd.copyFrom(D.data(), (size_t)n * sizeof(double));
         }
         double *scp = sc.as<double>();
         const double t3 = clock();
@@ -1294,14 +1309,17 @@ class Subdomain
         }
         double lambda = 1.0;
         sc.slice(1, 1).copyTo(&lambda, sizeof(double));
-        if (timing and n > 100000) printf("low_order:   lambda_max on the device: matrix up %.3f s, plan %.3f s, vectors %.3f s, %d iterations %.3f s\n", t1 - t0, t2 - t1, t3 - t2, iterations, clock() - t3);
+        if (timing and n > 100000) printf("low_order:   lambda_max on the device: plan %.3f s, vectors %.3f s, %d iterations %.3f s\n", t2 - t1, t3 - t2, iterations, clock() - t3);
         FDD_CALL(fdd_csr_plan_destroy(plan));
-        for (fdd::memory *m : {&ptr, &col, &val, &v, &vn, &t, &w, &Dd, &ws, &sc}) m->free();
+        for (fdd::memory *m : {&v, &vn, &t, &w, &ws, &sc}) m->free();
         return lambda;
     }
 
     // Build the low-order FEM matrix of the region and an AMG hierarchy for it on the host and attach it
     // (stands in for subdomain.tpp:2749-3549, see low_order.hpp).  Returns the number of levels.
+    // With amg_device_setup (conforming regions): the FEM matrix and every level coarsened on the lattice are built in
+    // HBM (amg_device_setup.hpp) and stay there; the first level that is not is downloaded and the host loop
+    // (low_order::build) continues from it, level index and lattice state kept.  Bit-identical either way.
     int amg_build(fdd::low_order::Options options, bool verbose = false)
     {
         if (dim != 3 or fine_mesh == nullptr or (poly_degree[0] < 2 and not is_composite))
@@ -1310,30 +1328,15 @@ class Subdomain
             exit(EXIT_FAILURE);
         }
         options.cheby_order = cheby_order;
+        static const bool timing = getenv("FDD_SETUP_TIMING") != nullptr;
         const auto clock = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         const double t0 = clock();
-        fdd::low_order::HostCSR A;
-        if (is_composite)
-        {
-            // the composite's low-order operator: mixed-degree region with its hanging edges / faces, plus the
-            // superdomain rows (subdomain.tpp:2749-3472, composite.hpp)
-            std::vector<std::vector<double>> nodes(num_levels);
-            for (int l = 0; l < num_levels; l++)
-            {
-                const int n = poly_degree[l] + 1;
-                std::vector<double> w(n);
-                nodes[l].resize(n);
-                fdd::gll::zwgll(nodes[l].data(), w.data(), n);
-            }
-            A = fdd::composite::assemble_low_order(comp, nodes, D_hat[num_levels - 1].first, (double)epsilon);
-        }
-        else
-            A = fdd::low_order::assemble_fem(fine_mesh->x.data(), fine_mesh->y.data(), fine_mesh->z.data(), point_dof.data(), num_dofs, poly_degree[0], fine_mesh->num_local_elements, epsilon);
-        const double t1 = clock();
+        const bool on_device = amg_device_setup and not is_composite;
+        if (amg_device_setup and is_composite) rstdout("amg_device_setup: a composite region builds its low-order hierarchy on the host\n");
         // the lattice the level-0 dofs sit on (the GLL points of the degree-N elements): the leading levels of the
-        // hierarchy coarsen it geometrically (low_order.hpp)
+        // hierarchy coarsen it geometrically (low_order.hpp); the device build also takes its point -> dof rows
         fdd::low_order::Lattice lattice;
-        if (options.geometric_levels and poly_degree[0] >= 2)
+        if ((options.geometric_levels or on_device) and poly_degree[0] >= 2)
         {
             const int n = poly_degree[0] + 1;
             lattice.dim = dim;
@@ -1361,25 +1364,131 @@ class Subdomain
             }
         }
         options.lambda_max = [this](const fdd::low_order::HostCSR &M, const std::vector<double> &D, int iterations) { return device_lambda_max(M, D, iterations); };
-        std::vector<fdd::low_order::Level> lv = fdd::low_order::build(std::move(A), options, verbose, std::move(lattice));
-        const double t2 = clock();
         amg_hierarchy = amg::Hierarchy();
+        amg_hierarchy.cheby_order = cheby_order;
+        amg_hierarchy.num_vcycles = num_vcycles;
+        amg_levels_on_device = 0;
+        fdd::low_order::HostCSR A;
+        int first_host_level = 0, geometric_done = 0;
+        double t1 = 0.0;
+        if (on_device)
+        {
+            namespace S = fdd::amg_setup;
+            double t_mark = clock();
+            auto lap = [&](const char *what, int l) {
+                if (not(timing or verbose)) return;
+                FDD_CALL(fdd_stream_sync(fdd::dev().stream));
+                const double t = clock();
+                if (timing or verbose) printf("low_order: device setup: level %d %-22s %7.3f s\n", l, what, t - t_mark);
+                t_mark = t;
+            };
+            S::least_free() = (size_t)-1;
+            S::note_memory();
+            // the level-0 lattice in HBM: its point -> dof array (every later lattice is made from it on the device)
+            S::DeviceLattice DL;
+            DL.n = poly_degree[0] + 1;
+            DL.cols = num_dofs;
+            DL.ref = lattice.ref;
+            DL.num_elements = fine_mesh->num_local_elements;
+            DL.point_dof = fdd::dev().malloc<int>(std::max<size_t>(point_dof.size(), 1));
+            DL.point_dof.copyFrom(point_dof.data(), point_dof.size() * sizeof(int));
+            S::DeviceCSR Ad = S::assemble_fem(fine_mesh->x.data(), fine_mesh->y.data(), fine_mesh->z.data(), DL.point_dof, lattice.rows, num_dofs, poly_degree[0], fine_mesh->num_local_elements, epsilon);
+            lap("FEM matrix", 0);
+            t1 = clock();
+            const bool use_lattice = options.geometric_levels;
+            lattice = fdd::low_order::Lattice(); // the host's copy is not needed any more
+            int l = 0;
+            for (;; l++)
+            {
+                const int n = Ad.rows;
+                const fdd::low_order::LevelPlan plan = fdd::low_order::plan_level(options, l, n, use_lattice ? DL.host(false) : fdd::low_order::Lattice(), geometric_done);
+                if (not plan.geometric) break; // hand-off: this level and the ones below it are built on the host
+                fdd::memory D = S::inv_sqrt_diag(Ad);
+                const double lmax = device_lambda_max(n, Ad.ptr_hst, Ad.ptr, Ad.col, Ad.val, D, options.power_iterations);
+                fdd::low_order::Options ol = options;
+                ol.eig_ratio = plan.eig_ratio;
+                const std::vector<double> coefs = fdd::low_order::chebyshev_coefficients(lmax, ol);
+                if (verbose) printf("low_order: level %d rows %d nnz %lld lambda_max(DAD) %.4f\n", l, n, Ad.nnz(), lmax);
+                lap("diagonal + lambda_max", l);
+                geometric_done++;
+                S::DeviceLattice next;
+                fdd::low_order::Transfer transfer;
+                S::DeviceCSR Pd = S::geometric_level(DL, n, next, transfer);
+                DL.point_dof.free();
+                DL = std::move(next);
+                if (verbose) printf("low_order: level %d coarsened on the lattice: %d -> %d rows, %d nodes per direction and element left\n", l, n, Pd.cols, DL.n);
+                lap("interpolator", l);
+                S::DeviceCSR Rd = S::transpose(Pd);                   // low_order::transpose, for the Galerkin product
+                S::DeviceCSR Rv = S::transpose(Pd, 1.0e-12);          // CSR_Matrix::transpose, the V-cycle's R
+                lap("transpose", l);
+                S::DeviceCSR AP = S::multiply(Ad, Pd);
+                lap("A P", l);
+                S::DeviceCSR Ac = S::multiply(Rd, AP);
+                lap("R (A P)", l);
+                AP.free();
+                Rd.free();
+                const int nc = Pd.cols;
+                amg_hierarchy.add_level_device(n, std::move(Ad.ptr_hst), Ad.ptr, Ad.col, Ad.val, D, coefs.data(), nc, std::move(Pd.ptr_hst), Pd.ptr, Pd.col, Pd.val, std::move(Rv.ptr_hst), Rv.ptr, Rv.col, Rv.val);
+                amg_hierarchy.set_lattice_transfer((size_t)l, std::move(transfer));
+                lap("level attached", l);
+                Ad = Ac;
+            }
+            A = S::download(Ad);
+            Ad.free();
+            if (use_lattice) lattice = DL.host(true); // small by now (C2 / C3: the degree-1 lattice)
+            DL.point_dof.free();
+            lap("hand-off download", l);
+            S::note_memory();
+            if (timing)
+            {
+                size_t free_b = 0, total_b = 0;
+                FDD_CALL(fdd_amg_setup_memory_info(&free_b, &total_b));
+                printf("low_order: device setup: peak device memory in use %.2f GB of %.2f GB (sampled after each allocation step)\n", (double)(total_b - S::least_free()) / 1e9, (double)total_b / 1e9);
+            }
+            first_host_level = l;
+            amg_levels_on_device = l + 1; // the matrices of levels 0 .. l (level l's is the device loop's last Galerkin product)
+        }
+        else
+        {
+            if (is_composite)
+            {
+                // the composite's low-order operator: mixed-degree region with its hanging edges / faces, plus the
+                // superdomain rows (subdomain.tpp:2749-3472, composite.hpp)
+                std::vector<std::vector<double>> nodes(num_levels);
+                for (int l = 0; l < num_levels; l++)
+                {
+                    const int n = poly_degree[l] + 1;
+                    std::vector<double> w(n);
+                    nodes[l].resize(n);
+                    fdd::gll::zwgll(nodes[l].data(), w.data(), n);
+                }
+                A = fdd::composite::assemble_low_order(comp, nodes, D_hat[num_levels - 1].first, (double)epsilon);
+            }
+            else
+                A = fdd::low_order::assemble_fem(fine_mesh->x.data(), fine_mesh->y.data(), fine_mesh->z.data(), point_dof.data(), num_dofs, poly_degree[0], fine_mesh->num_local_elements, epsilon);
+            t1 = clock();
+        }
+        std::vector<fdd::low_order::Level> lv = fdd::low_order::build(std::move(A), options, verbose, std::move(lattice), first_host_level, geometric_done);
+        const double t2 = clock();
         for (size_t l = 0; l < lv.size(); l++)
         {
             const bool coarsest = (l + 1 == lv.size());
-            amg_hierarchy.cheby_order = cheby_order;
-            amg_hierarchy.num_vcycles = num_vcycles;
             fdd::low_order::Level &L = lv[l];
             if (coarsest) L.P = fdd::low_order::HostCSR();
             const int n = L.A.rows, nc = L.P.cols;
             amg_hierarchy.add_level_adopt(n, std::move(L.A.ptr), std::move(L.A.col), std::move(L.A.val), L.D.data(), L.coefs.data(), nc, std::move(L.P.ptr), std::move(L.P.col), std::move(L.P.val));
-            amg_hierarchy.set_lattice_transfer(l, std::move(L.transfer)); // a geometric level: its interpolator is applied matrix-free
+            amg_hierarchy.set_lattice_transfer((size_t)first_host_level + l, std::move(L.transfer)); // a geometric level: its interpolator is applied matrix-free
             lv[l] = fdd::low_order::Level(); // free the host copy as we go
         }
         if (verbose) printf("low_order: FEM matrix %.2f s, hierarchy %.2f s, levels to the device %.2f s (%d host threads)\n", t1 - t0, t2 - t1, clock() - t2, fdd::low_order::host_threads());
         amg_finalize();
+        amg_setup_seconds = clock() - t0;
+        if (timing) printf("low_order: AMG setup %.3f s, %d of %d levels built on the device\n", amg_setup_seconds, amg_levels_on_device, (int)amg_hierarchy.levels.size());
         return (int)amg_hierarchy.levels.size();
     }
+    bool amg_device_setup = false; // "amg_device_setup": amg_build makes the FEM matrix and the lattice levels in HBM (conforming regions)
+    int amg_levels_on_device = 0;  // of the last amg_build: the levels whose matrix A was computed on the device
+    double amg_setup_seconds = 0.0;
     void apply_low_order_preconditioner(fdd::memory &z, fdd::memory &r) { low_order_preconditioner(z, r); }
 
     bool block_local = false;             // more than one rank: keep the rank's own elements only (no rings, no superdomain): block-Jacobi, the comparison point

@@ -522,11 +522,20 @@ class Problem:
             _H().call("fddh_problem_amg_add_level", self.h, A.shape[0], a[0].ctypes.data_as(ip), a[1].ctypes.data_as(ip), _dp(a[2]), _dp(D), _dp(coefs), len(coefs), *pargs)
         _H().call("fddh_problem_amg_finalize", self.h)
 
-    def amg_build(self, coarsest_size=0, strength=0.0, smooth_prolongator=True, verbose=False):
-        """Low-order FEM matrix + smoothed-aggregation hierarchy built by the host layer; returns the level count."""
+    def amg_build(self, coarsest_size=0, strength=0.0, smooth_prolongator=True, verbose=False, device=None):
+        """Low-order FEM matrix + smoothed-aggregation hierarchy built by the host layer; returns the level count.
+        device: None leaves the flag "amg_device_setup" as it is, True / False sets it first (the leading levels on the GPU)."""
+        if device is not None:
+            self.set_flag("amg_device_setup", 1 if device else 0)
         nl = ctypes.c_int()
         _H().call("fddh_problem_amg_build", self.h, int(coarsest_size), float(strength), int(smooth_prolongator), int(verbose), ctypes.byref(nl))
         return nl.value
+
+    def amg_setup_info(self):
+        """The last hierarchy build: {"levels_built_on_device": int, "setup_seconds": float} (0 levels: a host build)."""
+        lv, sec = ctypes.c_int(0), ctypes.c_double(0.0)
+        _H().call("fddh_problem_amg_setup_info", self.h, ctypes.byref(lv), ctypes.byref(sec))
+        return {"levels_built_on_device": lv.value, "setup_seconds": sec.value}
 
     def amg_level_transfer(self, level):
         """True where the interpolator of `level` is applied matrix-free (fdd_lattice_prolong / _restrict)."""
