@@ -185,7 +185,30 @@ int fddh_problem_set_options(fddh_problem *p, int max_iterations, double toleran
  *                              every level coarsened on the lattice are built on the device and stay in HBM (the first level
  *                              that is not comes back to the host loop), bit-identical to the host build.  Applies to
  *                              fddh_problem_amg_build and to the build on first use; a composite region builds on the host
- *                              and says so.  Fails, naming the entry, when the kernel library lacks an fdd_amg_setup_* entry. */
+ *                              and says so.  Fails, naming the entry, when the kernel library lacks an fdd_amg_setup_* entry.
+ *   "amg_num_vcycles" 1..16, "amg_cheby_order" 1..4 (subdomain.hpp:236-237), "amg_matrix_free_transfer",
+ *   "preconditioner_precision" 64 / 32 (the whole inner solve)
+ *
+ * Changing options and flags on a live problem.  The settings above may be changed between two calls of a problem that
+ * has already solved something; tests/reconfigure_walks.py walks one-rank problems (box, Kershaw, forced composite)
+ * through lists of them, setting the flags in the order of that file, and requires at every step the bits of a problem
+ * built anew with the same settings.  That, not more, is what is covered: several ranks are not, nor is every order of
+ * setting the flags.  Buffers follow the sizes, captured graphs are dropped with the setting they were captured under,
+ * and the V-cycle's switches outlive a (re)build of the hierarchy.  "amg_cheby_order" on a hierarchy of
+ * fddh_problem_amg_build's own (explicit or on first use) builds it again with the options of that build and the current
+ * "amg_device_setup" -- the whole setup is paid again (one line on stdout says how long it took).
+ * Where the order of setting matters:
+ *   "preconditioner_precision" 32 is checked against "device_bookkeeping" / "assembled_inner_solve" when it is set (both
+ *                              must be on); switching one of them off afterwards is accepted, while a problem built anew
+ *                              that sets them in that other order is refused: not covered by the walks
+ *   "preconditioner_precision" sets the V-cycle's precision too once a hierarchy exists: set "amg_precision" after it
+ *   "amg_precision" / "preconditioner_precision" 32 need a Chebyshev order of at least 2 at the time they are set
+ * Refused on a live problem, with an error that names the option, the option keeping its value (the closed list of
+ * refused transitions; tests/reconfigure_walks.py REFUSED matches it line for line):
+ *   "amg_cheby_order"          a new value once a hierarchy has been handed in (fddh_problem_amg_add_level): its
+ *                              coefficients are the caller's
+ *   "amg_cheby_order"          a value below 2 while "amg_precision" or "preconditioner_precision" is 32
+ */
 /* Flag "affine_geometry" (an option of this build, off by default; the reference always streams the six factor
  * arrays): after fddh_problem_set_flag(p, "affine_geometry", 1), which of the operators run on the kernel that forms the
  * factors from six numbers per element (fdd_hip.h: fdd_stiffness_matrix_affine) -- the fine Domain's node-space operator,

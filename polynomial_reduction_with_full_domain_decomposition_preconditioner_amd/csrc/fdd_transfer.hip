@@ -139,6 +139,9 @@ __global__ __launch_bounds__(kBlock) void lattice_restrict_kernel(T *__restrict_
         }
 }
 
+// the sizes the kernels are built for (fdd_lattice_supported)
+static bool lattice_supported(int n, int m) { return (n == 8 || n == 16) && m >= 2 && m <= n / 2 + 1; }
+
 static bool fill(LatticeInterp &I, int n, int m, const int *lo, const int *hi, const double *wl)
 {
     if (n > kMaxN || m > n / 2 + 1 || m < 2) return false;
@@ -170,7 +173,8 @@ static void launch_restrict(T *partial, const T *fine, const int *owner_dof, con
 template <typename T>
 static int prolong(T *u, const T *ec, const int *owner_dof, const int *coarse_dof, int n, int m, const int *lo, const int *hi, const double *wl, long long E, void *stream)
 {
-    FDD_REQUIRE(E >= 0 && E < (1LL << 31) / (n * n * n));
+    FDD_REQUIRE(lattice_supported(n, m)); // before n divides anything
+    FDD_REQUIRE(E >= 0 && E < (1LL << 31) / ((long long)n * n * n));
     if (E == 0) return 0;
     FDD_REQUIRE(u != nullptr && ec != nullptr && owner_dof != nullptr && coarse_dof != nullptr && lo != nullptr && hi != nullptr && wl != nullptr);
     LatticeInterp I;
@@ -191,7 +195,8 @@ static int prolong(T *u, const T *ec, const int *owner_dof, const int *coarse_do
 template <typename T>
 static int restrict_(T *partial, const T *fine, const int *owner_dof, int n, int m, const int *lo, const int *hi, const double *wl, long long E, void *stream)
 {
-    FDD_REQUIRE(E >= 0 && E < (1LL << 31) / (n * n * n));
+    FDD_REQUIRE(lattice_supported(n, m)); // before n divides anything
+    FDD_REQUIRE(E >= 0 && E < (1LL << 31) / ((long long)n * n * n));
     if (E == 0) return 0;
     FDD_REQUIRE(partial != nullptr && fine != nullptr && owner_dof != nullptr && lo != nullptr && hi != nullptr && wl != nullptr);
     LatticeInterp I;
@@ -215,7 +220,7 @@ extern "C" {
 int fdd_lattice_supported(int n, int m, int *supported)
 {
     FDD_REQUIRE(supported != nullptr);
-    *supported = ((n == 8 || n == 16) && m >= 2 && m <= n / 2 + 1) ? 1 : 0;
+    *supported = lattice_supported(n, m) ? 1 : 0;
     return 0;
 }
 

@@ -376,6 +376,15 @@ class Hierarchy
         destroy_graphs();
     }
 
+    void release_graphs() { destroy_graphs(); } // before the hierarchy is replaced (Subdomain::amg_build)
+
+    // a captured graph holds one launch sequence
+    void set_fused_smoother(bool on)
+    {
+        if (on != fused_smoother) destroy_graphs();
+        fused_smoother = on;
+    }
+
     // subdomain.hpp:236 (swept by run.py:154): a captured graph belongs to one cycle count
     void set_num_vcycles(int v)
     {

@@ -114,6 +114,7 @@ class Domain
     std::vector<DType> s_gmres;
     std::vector<DType> gamma;
     bool gmres_allocated = false;
+    int gmres_point_vectors = 0; // num_vectors the point-space basis V, Z was allocated for
 
     // state of a running flexible CG (fcg_begin / fcg_step)
     fdd::memory fcg_u;
@@ -371,18 +372,35 @@ class Domain
         va_valid = std::max(va_valid, upto + 1);
     }
 
+    // The basis follows num_vectors, which fddh_problem_set_options may change between two solves; the Hessenberg matrix
+    // and the rotations are shared with gmres_nodes and sized by whichever path ran last (gmres_host_arrays).
     void allocate_gmres()
     {
-        if (gmres_allocated) return;
+        gmres_host_arrays(num_vectors);
+        if (gmres_allocated and gmres_point_vectors == num_vectors) return;
+        for (auto *set : {&V, &Z})
+        {
+            for (auto &v : *set) v.free();
+            set->clear();
+        }
         V.resize(num_vectors + 1);
         for (int i = 0; i < num_vectors + 1; i++) V[i] = fdd::dev().malloc<DType>(num_local_points);
         Z.resize(num_vectors);
         for (int i = 0; i < num_vectors; i++) Z[i] = fdd::dev().malloc<DType>(num_local_points);
-        H.assign(num_vectors, std::vector<DType>(num_vectors, 0.0));
-        c_gmres.assign(num_vectors, 0.0);
-        s_gmres.assign(num_vectors, 0.0);
-        gamma.assign(num_vectors + 1, 0.0);
+        va_valid = 0;
+        gmres_point_vectors = num_vectors;
         gmres_allocated = true;
+    }
+
+    // H, c, s, gamma of GMRES(m): one set for the point-space and the node-space solve, re-made whenever the other path
+    // (or another num_vectors) left them at a different size
+    void gmres_host_arrays(int m)
+    {
+        if ((int)H.size() == m and (int)c_gmres.size() == m and (int)s_gmres.size() == m and (int)gamma.size() == m + 1) return;
+        H.assign(m, std::vector<DType>(m, 0.0));
+        c_gmres.assign(m, 0.0);
+        s_gmres.assign(m, 0.0);
+        gamma.assign(m + 1, 0.0);
     }
 
   public:
@@ -1018,7 +1036,9 @@ class Domain
             return nullptr;
         }
         const double *known = nullptr;
-        if (norm_on_dof_slice and shared_residual_norm)
+        // (only with the inner solve to share it with: without a preconditioner the norm keeps its masked form, whether or not
+        // an earlier solve of this problem set the dof maps up)
+        if (norm_on_dof_slice and shared_residual_norm and use_preconditioner)
         {
             // One rank, mask = 1 on the dof slice and 0 elsewhere: the masked sum over the nodes IS the plain sum over the
             // slice -- the sum the inner solve forms first (its right-hand side is this slice, read in place).  Formed once,
@@ -1520,12 +1540,9 @@ class Domain
                 VP.resize(m + 1);
                 for (auto &v : VP) v = fdd::dev().malloc<DType>(std::max(num_local_points, 1));
             }
-            H.assign(m, std::vector<DType>(m, 0.0));
-            c_gmres.assign(m, 0.0);
-            s_gmres.assign(m, 0.0);
-            gamma.assign(m + 1, 0.0);
             gmres_nodes_vectors = m;
         }
+        gmres_host_arrays(m); // shared with the point-space solve, which may have run with another num_vectors since
         residual_history.clear();
 
         // the assembled copy <., .> reads: gs over the ranks on the interface prefix, nothing to do on one rank

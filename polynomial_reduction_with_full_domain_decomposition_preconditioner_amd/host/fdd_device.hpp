@@ -78,6 +78,10 @@ struct device_t
     void *stream = nullptr; // hipStream_t all kernels of this rank run on
     bool owns_stream = false; // created by fddh_init(own_stream): released by fddh_rank_finalize
     bool initialised = false; // fddh_init ran on this thread (a null stream alone cannot tell: it is also the legacy default stream)
+    // which rank this is: a process-wide counter's next value, taken by the first fddh_init of the thread (and by the first
+    // after an fddh_rank_finalize), 0 while the thread is no rank.  The address of this thread_local cannot serve: a thread
+    // started after a rank thread has exited may get the same one.
+    unsigned long long rank_instance = 0;
 
     template <typename T>
     class memory malloc(size_t n);

@@ -4,6 +4,7 @@
 // in and out of device memory.
 #include "fdd_host.h"
 
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -47,7 +48,7 @@ struct fddh_problem
     // The rank (= host thread) that built the problem: its device stream, communicator and globals are thread_local, so a
     // call from any other thread would silently run on the legacy default stream with a one-rank communicator (every
     // collective skipped: wrong sums, or peers hanging in RCCL).  Every fddh_problem_* entry checks it (rank_check).
-    const void *owner = nullptr;
+    unsigned long long owner = 0; // device_t::rank_instance of that rank; never 0 for a finished problem
 
     // device staging vectors
     fdd::memory a, b, c;
@@ -57,14 +58,15 @@ struct fddh_problem
     const Domain<SType> &fine() const { return domains.at(poly_degree); }
 };
 
-// identity of the calling rank's per-thread state
-static const void *this_rank() { return &fdd::dev(); }
+// identity of the calling rank: unique over the life of the process, 0 on a thread that is not (or no longer) a rank
+static unsigned long long this_rank() { return fdd::dev().rank_instance; }
+static std::atomic<unsigned long long> rank_instances{0};
 
 // 0 when the calling thread is an initialised rank (fddh_init) and, for a problem, the one that built it
 static int rank_check(const fddh_problem *p = nullptr)
 {
     if (!fdd::dev().initialised) return fail("fddh_init has not been called on this thread: the host layer's device stream and communicator are per rank = per host thread");
-    if (p && p->owner != this_rank()) return fail("this problem was built by another rank (host thread); its stream and communicator are not the calling thread's");
+    if (p && (p->owner == 0 || p->owner != this_rank())) return fail("this problem was built by another rank (host thread); its stream and communicator are not the calling thread's");
     return 0;
 }
 
@@ -134,6 +136,7 @@ int fddh_init(int device, void *stream, int own_stream)
         }
         fdd::dev().owns_stream = own_stream != 0;
         fdd::dev().stream = stream;
+        if (!fdd::dev().initialised) fdd::dev().rank_instance = ++rank_instances; // a further fddh_init of a live rank changes its stream, not who it is
         fdd::dev().initialised = true;
         return 0;
     }
@@ -260,6 +263,7 @@ int fddh_rank_finalize(void)
         d.stream = nullptr;
         d.owns_stream = false;
         d.initialised = false;
+        d.rank_instance = 0; // the problems this rank built are nobody's now: every entry refuses them
         return 0;
     }
     catch (const std::exception &e)
@@ -1023,7 +1027,7 @@ int fddh_problem_set_flag(fddh_problem *p, const char *name, int value)
         }
         else if (s == "amg_fused_smoother")
         {
-            if (p->subdomain) p->subdomain->amg_hierarchy.fused_smoother = value != 0;
+            if (p->subdomain) p->subdomain->amg_hierarchy.set_fused_smoother(value != 0);
         }
         else if (s == "amg_matrix_free_transfer")
         {
@@ -1051,8 +1055,14 @@ int fddh_problem_set_flag(fddh_problem *p, const char *name, int value)
             // coefficients are computed when the hierarchy is built: set it before (fddh_problem_amg_build / first solve)
             if (!p->subdomain) return fail("problem was created without a Subdomain");
             if (value < 1 || value > 4) return fail("amg_cheby_order must lie in 1..4 (subdomain.tpp:3477-3478)");
-            if (p->subdomain->amg_hierarchy.ready() && value != p->subdomain->cheby_order) return fail("amg_cheby_order must be set before the hierarchy is built");
-            p->subdomain->cheby_order = value;
+            // -- or afterwards where the hierarchy is fddh_problem_amg_build's own: it is built again with the options of that
+            // build.  One that was handed in level by level carries the caller's coefficients and cannot follow.
+            Subdomain<PType> &sub = *p->subdomain;
+            if (value == sub.cheby_order) return 0;
+            if (value < 2 && (sub.amg_hierarchy.precision == 32 || sub.precision == 32)) return fail("amg_cheby_order %d: the 32-bit V-cycle (amg_precision / preconditioner_precision 32) needs a Chebyshev order of at least 2", value);
+            if (sub.amg_hierarchy.ready() && !sub.amg_built_here) return fail("amg_cheby_order cannot change once a hierarchy has been handed in (fddh_problem_amg_add_level): its coefficients are the caller's");
+            sub.cheby_order = value;
+            if (sub.amg_hierarchy.ready()) sub.amg_rebuild();
         }
         else if (s == "amg_precision")
         {

@@ -424,6 +424,8 @@ class Subdomain
     void low_order_preconditioner(fdd::memory &z, fdd::memory &r)
     {
         amg::Level &fine = amg_checked();
+        // this entry gives and takes double vectors; the float inner solve may have left the cycle reading f32 and writing u32
+        if (amg_hierarchy.f32_io) amg_hierarchy.set_f32_io(false);
         fdd::memory r_sub_l = r.slice(0, subdomain_operator.num_points);
         fdd::memory z_sub_l = z.slice(0, subdomain_operator.num_points);
         subdomain_operator.Qt.multiply(work_dev[0], r_sub_l); // :3996
@@ -1327,6 +1329,7 @@ class Subdomain
             fprintf(stderr, "ERROR: Subdomain::amg_build handles 3-D regions of degree >= 2\n");
             exit(EXIT_FAILURE);
         }
+        amg_build_options = options; // kept: a later change of "amg_cheby_order" rebuilds with them (amg_rebuild)
         options.cheby_order = cheby_order;
         static const bool timing = getenv("FDD_SETUP_TIMING") != nullptr;
         const auto clock = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -1364,10 +1367,22 @@ class Subdomain
             }
         }
         options.lambda_max = [this](const fdd::low_order::HostCSR &M, const std::vector<double> &D, int iterations) { return device_lambda_max(M, D, iterations); };
-        amg_hierarchy = amg::Hierarchy();
+        {
+            // the run-time switches of the cycle belong to the problem, not to one hierarchy: a build (explicit, on first
+            // use, or again) keeps what fddh_problem_set_flag stored
+            const bool graph = amg_hierarchy.use_graph, fused = amg_hierarchy.fused_smoother, matrix_free = amg_hierarchy.matrix_free_transfer;
+            const int bits = amg_hierarchy.precision;
+            amg_hierarchy.release_graphs();
+            amg_hierarchy = amg::Hierarchy();
+            amg_hierarchy.use_graph = graph;
+            amg_hierarchy.fused_smoother = fused;
+            amg_hierarchy.matrix_free_transfer = matrix_free;
+            amg_hierarchy.precision = (bits == 32 and cheby_order >= 2) ? 32 : 64;
+        }
         amg_hierarchy.cheby_order = cheby_order;
         amg_hierarchy.num_vcycles = num_vcycles;
         amg_levels_on_device = 0;
+        amg_built_here = false;
         fdd::low_order::HostCSR A;
         int first_host_level = 0, geometric_done = 0;
         double t1 = 0.0;
@@ -1482,9 +1497,19 @@ class Subdomain
         }
         if (verbose) printf("low_order: FEM matrix %.2f s, hierarchy %.2f s, levels to the device %.2f s (%d host threads)\n", t1 - t0, t2 - t1, clock() - t2, fdd::low_order::host_threads());
         amg_finalize();
+        amg_built_here = true;
         amg_setup_seconds = clock() - t0;
         if (timing) printf("low_order: AMG setup %.3f s, %d of %d levels built on the device\n", amg_setup_seconds, amg_levels_on_device, (int)amg_hierarchy.levels.size());
         return (int)amg_hierarchy.levels.size();
+    }
+    // the hierarchy in place is amg_build's own (not handed in through amg_add_level): it can be made again
+    bool amg_built_here = false;
+    fdd::low_order::Options amg_build_options;
+    int amg_rebuild()
+    {
+        const int nl = amg_build(amg_build_options);
+        rstdout("Low-order preconditioner assembled again (amg_cheby_order %d): %d levels, %.3f s\n", cheby_order, nl, amg_setup_seconds); // a sweep's reader sees what a change of the order costs
+        return nl;
     }
     bool amg_device_setup = false; // "amg_device_setup": amg_build makes the FEM matrix and the lattice levels in HBM (conforming regions)
     int amg_levels_on_device = 0;  // of the last amg_build: the levels whose matrix A was computed on the device
@@ -2085,6 +2110,7 @@ class Subdomain
     void flexible_conjugate_gradient(fdd::memory &u_l, fdd::memory &f_l, bool print_history = true, bool use_relative = false)
     {
         residual_history.clear();
+        history_pending = false; // a lazy solve before this one (pcg_steps) may have left its history on the device: it is not this solve's
         tree_operator(r_k, f_l);
 
         fdd_timer().start("subdomain.vector_operations");
@@ -2220,6 +2246,7 @@ class Subdomain
             qa = fdd::dev().malloc<DType>(std::max(nd, 1));
         }
         residual_history.clear();
+        history_pending = false; // a lazy solve before this one (pcg_steps) may have left its history on the device: it is not this solve's
 
         tree_operator(f, f_l);
         initialize_arrays(u_k, r_k, f);
@@ -2703,6 +2730,7 @@ class Subdomain
         }
         if ((int)H.size() != m) allocate_krylov_scalars();
         residual_history.clear();
+        history_pending = false; // a lazy solve before this one (pcg_steps) may have left its history on the device: it is not this solve's
         double *sc = scalars.as<double>();
         double *ws = reduce_ws.as<double>();
         const double *nw = norm_weight_is_one ? nullptr : norm_weight.as<double>(); // NULL: unit weights, not read
@@ -2870,6 +2898,7 @@ class Subdomain
 
         if ((int)Z.size() != num_vectors) allocate_krylov();
         residual_history.clear();
+        history_pending = false; // a lazy solve before this one (pcg_steps) may have left its history on the device: it is not this solve's
 
         tree_operator(f, f_l);
 

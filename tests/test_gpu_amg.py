@@ -123,14 +123,29 @@ def test_reference_sweep_parameters_as_run_time_switches(own_stream, cheby_order
     """The parameters the reference's harness sweeps by rewriting header lines and rebuilding (run.py:150-156: subdomain.hpp:236
     `num_vcycles`, :237 `cheby_order`, clamped to 1..4 by subdomain.tpp:3477-3478) as run-time switches of the host layer
     (`amg_num_vcycles`, `amg_cheby_order`; `poisson --vcycles / --cheby`): the V-cycle with them against the oracle's with the
-    same hierarchy, the inner solves and the outer solve iteration for iteration; the order cannot change under a built
-    hierarchy (its coefficients are the hierarchy's)."""
+    same hierarchy, the inner solves and the outer solve iteration for iteration; a new order under a hierarchy of the host
+    layer's own rebuilds it (bit for bit the hierarchy of a problem that had the order from the start)."""
     p = make_problem((4, 4, 4), 3, 2)
     try:
         its = amg_checks.check_amg(p, 3, 2, builder="product", cheby_order=cheby_order, num_vcycles=num_vcycles)
         assert its is not None and its <= 10
+        # the order under a hierarchy the host layer built itself: built again with the options of that build, and the
+        # bits of a problem that had the order from the start (a handed-in hierarchy refuses: reconfigure_walks.py)
+        other = 1 if cheby_order != 1 else 2
+        r = S.seeded_uniform(p.n, 21) - 0.5
+        p.set_flag("amg_cheby_order", other)
+        q = make_problem((4, 4, 4), 3, 2)
+        try:
+            q.set_flag("amg_cheby_order", other)
+            q.set_flag("amg_num_vcycles", num_vcycles)
+            assert q.amg_build(coarsest_size=40) >= 2
+            want = q.amg_apply(r)
+        finally:
+            q.close()
+        assert np.array_equal(p.amg_apply(r).view(np.uint64), want.view(np.uint64))
+        assert len(p.amg_levels(other)[0]["coefs"]) == other
         with pytest.raises(lib.FddError):
-            p.set_flag("amg_cheby_order", 1 if cheby_order != 1 else 2)
+            p.set_flag("amg_cheby_order", 5)
         p.set_flag("amg_num_vcycles", 1)  # any time: the captured graph is dropped
         with pytest.raises(lib.FddError):
             p.set_flag("amg_num_vcycles", 0)

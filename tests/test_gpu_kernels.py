@@ -621,6 +621,44 @@ def test_lattice_transfer_equals_the_csr_interpolator(gpu, n, keep, E, precision
         k("fdd_lattice_prolong" + suffix, du, t(ec), t(owner), t(coarse), 6, 3, vpi(lo), vpi(hi), vpi(wl), ctypes.c_longlong(1))
 
 
+@pytest.mark.parametrize("suffix", ["", "_f32"])
+def test_lattice_transfer_refuses_bad_sizes_before_any_launch(gpu, suffix):
+    """fdd_lattice_prolong / fdd_lattice_restrict and their _f32 forms check the lattice (n, m: exactly what
+    fdd_lattice_supported accepts) and then the element count, before n divides anything and before any launch: n = 0 was a
+    host integer division by zero.  Every refused call raises and leaves the output buffer, pre-filled with a sentinel, alone."""
+    tt = torch.float64 if suffix == "" else torch.float32
+    sentinel = -12345.5
+    vpi = lambda arr: vp(arr.ctypes.data)
+    lo, hi, wl = np.zeros(17, np.int32), np.zeros(17, np.int32), np.ones(17)
+    size = 2 * 17**3
+    src = torch.zeros(size, dtype=tt, device=gpu)
+    owner = torch.full((size,), -1, dtype=torch.int32, device=gpu)
+    coarse = torch.full((size,), -1, dtype=torch.int32, device=gpu)
+    cases = [(n, 2, 1) for n in (0, -1, 1, 7, 9, 17)]                                  # lattices that are not built
+    cases += [(n, m, 1) for n in (0, -1, 1, 7, 9, 17, 8, 16) for m in (0, n + 1)]      # kept counts out of range
+    cases += [(8, 6, 1), (16, 10, 1)]                                                  # one more than n / 2 + 1
+    cases += [(n, 2, E) for n in (8, 16) for E in (-1, -(2**40), 2**31 // n**3, 2**31, 2**40)]  # E < 0 and E at and past the 2^31 bound
+    for n, m, E in cases:
+        supported = ctypes.c_int(-1)
+        lib.hip().call("fdd_lattice_supported", n, m, ctypes.byref(supported))
+        assert supported.value == (1 if (n in (8, 16) and 2 <= m <= n // 2 + 1) else 0), (n, m)
+        if E == 1:
+            assert supported.value == 0, (n, m)
+        for name, args in (("fdd_lattice_prolong", (src, owner, coarse)), ("fdd_lattice_restrict", (src, owner))):
+            out = torch.full((size,), sentinel, dtype=tt, device=gpu)
+            with pytest.raises(lib.FddError):
+                k(name + suffix, out, *args, n, m, vpi(lo), vpi(hi), vpi(wl), ctypes.c_longlong(E))
+            torch.cuda.synchronize()
+            assert bool((out == sentinel).all()), (name, n, m, E)
+    # accepted sizes with no element launch nothing and succeed
+    for n in (8, 16):
+        out = torch.full((size,), sentinel, dtype=tt, device=gpu)
+        k("fdd_lattice_prolong" + suffix, out, src, owner, coarse, n, 2, vpi(lo), vpi(hi), vpi(wl), ctypes.c_longlong(0))
+        k("fdd_lattice_restrict" + suffix, out, src, owner, n, 2, vpi(lo), vpi(hi), vpi(wl), ctypes.c_longlong(0))
+        torch.cuda.synchronize()
+        assert bool((out == sentinel).all())
+
+
 def test_csr_empty_matrix(gpu):
     ptr = np.zeros(11, np.int32)
     run_csr_case(gpu, ptr, np.zeros(0, np.int32), np.zeros(0), 7, expect_kind=0)
