@@ -21,15 +21,25 @@
 
 #include <chrono>
 #include <map>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
 #include "config.hpp"
 #include "csr_matrix.hpp"
 #include "low_order.hpp"
+#include "precision_ops.hpp"
 
 namespace amg
 {
+
+// Float = float (AMG/config.hpp:4): the f32 copy of a matrix's values and the row-block plan of the f32 SpMV on them
+// (the index arrays are the matrix's own)
+struct Csr32
+{
+    fdd::memory val;
+    fdd_csr_plan *plan = nullptr;
+};
 
 // matrix-free form of a geometric level's interpolator (fdd_lattice_prolong / _restrict, csrc/fdd_transfer.hip): the maps
 // of low_order::Transfer on the device, the element-local partial sums of the restriction and the boolean gather that adds
@@ -43,8 +53,7 @@ struct LatticeTransfer
     long long num_elements = 0;
     fdd::memory owner_dof, coarse_dof, partial, partial32;
     CSR_Matrix<double> gather; // coarse dofs x kept nodes of all elements
-    fdd::memory gather_val32;
-    fdd_csr_plan *gather_plan32 = nullptr;
+    Csr32 gather32;
     double prolong_bytes(int n_fine, int n_coarse, int vb) const { return 4.0 * (double)num_elements * n * n * n + 2.0 * vb * n_fine + (4.0 + vb) * (double)num_elements * m * m * m + 0.0 * n_coarse; }
     double restrict_bytes(int n_fine, int vb) const { return 4.0 * (double)num_elements * n * n * n + 1.0 * vb * n_fine + 1.0 * vb * (double)num_elements * m * m * m; }
 };
@@ -59,11 +68,54 @@ struct Level
     fdd::memory D_val;
     std::vector<double> coefs; // Chebyshev coefficients, coefs[p] multiplies (DAD)^p
     fdd::memory f, u, r, v, w, work;
-    // Float = float (AMG/config.hpp:4): f32 copies of the values and vectors, row-block plans for the f32 SpMV
     std::vector<double> D_hst;
-    fdd::memory A_val32, P_val32, R_val32, D_val32;
-    fdd::memory f32, u32, r32, v32, work32;
-    fdd_csr_plan *A_plan32 = nullptr, *P_plan32 = nullptr, *R_plan32 = nullptr;
+    // Float = float: f32 copies of the values and vectors; nothing of it exists before the float cycle first runs
+    // (Hierarchy::prepare32)
+    struct Float32
+    {
+        Csr32 A, P, R;
+        fdd::memory D_val, f, u, r, v, work;
+    } s;
+};
+
+// What the one body of the cycle sees of a level in one precision: the vectors and the diagonal, and for the level's
+// matrices (and the coarse inverse) y = alpha*M*x + beta*y (matvec), y = alpha*M*x + beta*y_in (matvec_to) and the three
+// smoother epilogues of the SpMV with A.  Double: the members of CSR_Matrix; float: the f32 plan entries.
+template <typename Real>
+struct View;
+
+template <>
+struct View<double>
+{
+    Level &L;
+    fdd::memory &f = L.f, &u = L.u, &r = L.r, &v = L.v, &work = L.work, &D = L.D_val, &partial = L.T.partial;
+    static void matvec(CSR_Matrix<double> &M, Csr32 &, fdd::memory &y, fdd::memory &x, double alpha, double beta) { M.matvec(y, x, alpha, beta); }
+    static void matvec_to(CSR_Matrix<double> &M, Csr32 &, fdd::memory &y, fdd::memory &y_in, fdd::memory &x, double alpha, double beta) { M.matvec_to(y, y_in, x, alpha, beta); }
+    void smooth_residual(fdd::memory &out, double coef) { L.A.smooth_residual(out, r, u, f, D, coef); }
+    void smooth_polynomial(fdd::memory &out, fdd::memory &in, double coef) { L.A.smooth_polynomial(out, in, r, D, coef); }
+    void smooth_update(fdd::memory &in, double coef) { L.A.smooth_update(u, in, r, D, coef); }
+    void smooth_update_from_zero(fdd::memory &in, double coef) { L.A.smooth_update_from_zero(u, in, r, D, coef); } // u = 0 + D w: u is not read
+};
+
+template <>
+struct View<float>
+{
+    Level &L;
+    fdd::memory &f = L.s.f, &u = L.s.u, &r = L.s.r, &v = L.s.v, &work = L.s.work, &D = L.s.D_val, &partial = L.T.partial32;
+    static void spmv(CSR_Matrix<double> &M, Csr32 &M32, fdd::memory &y, const float *y_in, fdd::memory &x, float alpha, float beta)
+    {
+        fdd::ProfileScope prof("csr_block_kernel<f32>", 8.0 * M.num_nnz + 8.0 * M.num_rows + 4.0 * M.num_cols + (beta != 0.0f ? 4.0 * M.num_rows : 0.0));
+        FDD_CALL(fdd_csr_plan_matvec_to_f32(M32.plan, y.as<float>(), y_in, M.ptr.as<int>(), M.col.as<int>(), M32.val.as<float>(), x.as<float>(), alpha, beta, fdd::dev().stream));
+    }
+    static void matvec(CSR_Matrix<double> &M, Csr32 &M32, fdd::memory &y, fdd::memory &x, float alpha, float beta) { spmv(M, M32, y, beta != 0.0f ? y.as<float>() : nullptr, x, alpha, beta); }
+    static void matvec_to(CSR_Matrix<double> &M, Csr32 &M32, fdd::memory &y, fdd::memory &y_in, fdd::memory &x, float alpha, float beta) { spmv(M, M32, y, y_in.as<float>(), x, alpha, beta); }
+    const int *ptr() const { return L.A.ptr.as<int>(); }
+    const int *col() const { return L.A.col.as<int>(); }
+    const float *val() const { return L.s.A.val.as<float>(); }
+    void smooth_residual(fdd::memory &out, float coef) { FDD_CALL(fdd_amg_smooth_residual_matvec_f32(L.s.A.plan, out.as<float>(), r.as<float>(), ptr(), col(), val(), u.as<float>(), f.as<float>(), D.as<float>(), coef, fdd::dev().stream)); }
+    void smooth_polynomial(fdd::memory &out, fdd::memory &in, float coef) { FDD_CALL(fdd_amg_smooth_polynomial_matvec_f32(L.s.A.plan, out.as<float>(), ptr(), col(), val(), in.as<float>(), r.as<float>(), D.as<float>(), coef, fdd::dev().stream)); }
+    void smooth_update(fdd::memory &in, float coef) { FDD_CALL(fdd_amg_smooth_update_matvec_f32(L.s.A.plan, u.as<float>(), ptr(), col(), val(), in.as<float>(), r.as<float>(), D.as<float>(), coef, fdd::dev().stream)); }
+    void smooth_update_from_zero(fdd::memory &in, float coef) { FDD_CALL(fdd_amg_smooth_update_matvec_from_zero_f32(L.s.A.plan, u.as<float>(), ptr(), col(), val(), in.as<float>(), r.as<float>(), D.as<float>(), coef, fdd::dev().stream)); }
 };
 
 class Hierarchy
@@ -83,101 +135,112 @@ class Hierarchy
     }
     CSR_Matrix<double> coarse_inverse;
 
+
     // Chebyshev smoother, device branches of subdomain.tpp:19-83
     // u_is_zero: the level's u was just set to 0 (every pre-smoothing), so f - A u is f itself
     // bit for bit and the SpMV of scaled_residual is skipped (the reference multiplies by the zero vector)
+    template <typename Real>
     void smooth(int l, bool u_is_zero = false)
     {
+        constexpr bool f32 = std::is_same<Real, float>::value;
         Level &L = levels[l];
+        View<Real> V{L};
         void *s = fdd::dev().stream;
-        if (fused_smoother and cheby_order >= 2)
+        const auto coef = [&L](int p) { return (Real)L.coefs[p]; };
+        if (f32 or (fused_smoother and cheby_order >= 2)) // the float cycle has the fused sequence only, whatever fused_smoother says
         {
             // the same statements as below, with the element-wise kernels running as epilogues of the SpMV in front
             // of them (bit-identical): cheby_order SpMV launches (one fewer, plus one element-wise, from u = 0) and
             // no vector in between goes through HBM.  work and v alternate as the SpMV operand.
-            fdd::memory *in = &L.work, *out = &L.v;
+            fdd::memory *in = &V.work, *out = &V.v;
             if (u_is_zero)
-                FDD_CALL(fdd_amg_smooth_start(in->as<double>(), L.r.as<double>(), L.f.as<double>(), L.D_val.as<double>(), L.coefs[cheby_order - 1], L.n, s));
+                fdd::ops::amg_smooth_start(in->as<Real>(), V.r.template as<Real>(), V.f.template as<Real>(), V.D.template as<Real>(), coef(cheby_order - 1), L.n, s);
             else
-                L.A.smooth_residual(*in, L.r, L.u, L.f, L.D_val, L.coefs[cheby_order - 1]);
+                V.smooth_residual(*in, coef(cheby_order - 1));
             for (int p = cheby_order - 2; p >= 1; p--)
             {
-                L.A.smooth_polynomial(*out, *in, L.r, L.D_val, L.coefs[p]);
+                V.smooth_polynomial(*out, *in, coef(p));
                 std::swap(in, out);
             }
             if (u_is_zero)
-                L.A.smooth_update_from_zero(L.u, *in, L.r, L.D_val, L.coefs[0]); // u = 0 + D w: u is not read, and was not zeroed (vcycle_launches)
+                V.smooth_update_from_zero(*in, coef(0)); // u was not zeroed (vcycle_launches)
             else
-                L.A.smooth_update(L.u, *in, L.r, L.D_val, L.coefs[0]);
+                V.smooth_update(*in, coef(0));
             return;
         }
-        // scaled_residual (:34-39): work = f - A u without the copy "work = f" in front of the SpMV; from u = 0 it is f
-        if (not u_is_zero) L.A.matvec_to(L.work, L.f, L.u, -1.0, 1.0);
-        FDD_CALL(fdd_amg_main_scaled_residual(L.r.as<double>(), L.w.as<double>(), (u_is_zero ? L.f : L.work).as<double>(), L.D_val.as<double>(), L.coefs[cheby_order - 1], L.n, s));
-        // polynomial_evaluation (:62-67)
-        for (int p = cheby_order - 2; p >= 0; p--)
+        if constexpr (not f32)
         {
-            FDD_CALL(fdd_amg_vector_multiplication(L.work.as<double>(), L.D_val.as<double>(), L.w.as<double>(), L.n, s));
-            L.A.matvec(L.v, L.work, 1.0, 0.0);
-            FDD_CALL(fdd_amg_main_polynomial_evaluation(L.w.as<double>(), L.v.as<double>(), L.r.as<double>(), L.D_val.as<double>(), L.coefs[p], L.n, s));
+            // scaled_residual (:34-39): work = f - A u without the copy "work = f" in front of the SpMV; from u = 0 it is f
+            if (not u_is_zero) L.A.matvec_to(L.work, L.f, L.u, -1.0, 1.0);
+            FDD_CALL(fdd_amg_main_scaled_residual(L.r.as<double>(), L.w.as<double>(), (u_is_zero ? L.f : L.work).as<double>(), L.D_val.as<double>(), L.coefs[cheby_order - 1], L.n, s));
+            // polynomial_evaluation (:62-67)
+            for (int p = cheby_order - 2; p >= 0; p--)
+            {
+                FDD_CALL(fdd_amg_vector_multiplication(L.work.as<double>(), L.D_val.as<double>(), L.w.as<double>(), L.n, s));
+                L.A.matvec(L.v, L.work, 1.0, 0.0);
+                FDD_CALL(fdd_amg_main_polynomial_evaluation(L.w.as<double>(), L.v.as<double>(), L.r.as<double>(), L.D_val.as<double>(), L.coefs[p], L.n, s));
+            }
+            // update_field (:79-82)
+            FDD_CALL(fdd_amg_main_update_field(L.u.as<double>(), L.w.as<double>(), L.D_val.as<double>(), L.n, s));
         }
-        // update_field (:79-82)
-        FDD_CALL(fdd_amg_main_update_field(L.u.as<double>(), L.w.as<double>(), L.D_val.as<double>(), L.n, s));
     }
 
-    // subdomain.tpp:4015-4139, every level on the device
+    // subdomain.tpp:4015-4139, every level on the device.  Float = float (AMG/config.hpp:4, swept by run.py:157) is the
+    // same cycle on f32 values and vectors: the residual is cast down on entry and the correction cast up on exit (the
+    // reference copies Float data at subdomain.tpp:4008,4142) unless the caller works in float itself (f32_io).
+    template <typename Real>
     void vcycle_launches()
     {
+        constexpr bool f32 = std::is_same<Real, float>::value;
         const int nl = (int)levels.size();
         void *s = fdd::dev().stream;
+        if (f32 and not f32_io) FDD_CALL(fdd_sub_copy_f32_f64(levels[0].s.f.as<float>(), levels[0].f.as<double>(), levels[0].n, s));
         // the fused pre-smoother writes u = 0 + D w without reading u: the reference's zeroing of u (:4012, :4026, :4058)
-        // would be 8 B per row written and read back for nothing
-        const bool smoother_writes_u = fused_smoother and cheby_order >= 2;
-        if (not smoother_writes_u or nl == 1) FDD_CALL(fdd_amg_vector_set_to_value(levels[0].u.as<double>(), 0.0, levels[0].n, s)); // :4012
+        // would be a write and a read back per row for nothing
+        const bool smoother_writes_u = f32 or (fused_smoother and cheby_order >= 2);
+        if (not smoother_writes_u or nl == 1) fdd::ops::amg_set_to_value(View<Real>{levels[0]}.u.template as<Real>(), (Real)0, levels[0].n, s); // :4012
         for (int iter = 0; iter < num_vcycles; iter++)
         {
             for (int l = 0; l < nl - 1; l++)
             {
                 Level &L = levels[l];
-                if (l > 0 and not smoother_writes_u) FDD_CALL(fdd_amg_vector_set_to_value(L.u.as<double>(), 0.0, L.n, s));
-                smooth(l, l > 0 or iter == 0);
-                L.A.matvec_to(L.v, L.f, L.u, -1.0, 1.0); // v = f - A u
+                View<Real> V{L}, C{levels[l + 1]};
+                if (l > 0 and not smoother_writes_u) fdd::ops::amg_set_to_value(V.u.template as<Real>(), (Real)0, L.n, s);
+                smooth<Real>(l, l > 0 or iter == 0);
+                V.matvec_to(L.A, L.s.A, V.v, V.f, V.u, -1, 1); // v = f - A u
                 if (L.T.active and matrix_free_transfer)
                 {
                     {
-                        fdd::ProfileScope prof("lattice_restrict_kernel", L.T.restrict_bytes(L.n, 8));
-                        FDD_CALL(fdd_lattice_restrict(L.T.partial.as<double>(), L.v.as<double>(), L.T.owner_dof.as<int>(), L.T.n, L.T.m, L.T.lo.data(), L.T.hi.data(), L.T.wl.data(), L.T.num_elements, s));
+                        fdd::ProfileScope prof(f32 ? "lattice_restrict_kernel<f32>" : "lattice_restrict_kernel", L.T.restrict_bytes(L.n, sizeof(Real)));
+                        fdd::ops::lattice_restrict(V.partial.template as<Real>(), V.v.template as<Real>(), L.T.owner_dof.as<int>(), L.T.n, L.T.m, L.T.lo.data(), L.T.hi.data(), L.T.wl.data(), L.T.num_elements, s);
                     }
-                    L.T.gather.matvec(levels[l + 1].f, L.T.partial, 1.0, 0.0);
+                    V.matvec(L.T.gather, L.T.gather32, C.f, V.partial, 1, 0);
                 }
                 else
-                    L.R.matvec(levels[l + 1].f, L.v, 1.0, 0.0);
+                    V.matvec(L.R, L.s.R, C.f, V.v, 1, 0);
             }
-            Level &C = levels[nl - 1];
-            coarse_inverse.matvec(C.u, C.f, 1.0, 0.0); // hypre_GaussElimSolve's role (:4084)
+            View<Real> B{levels[nl - 1]};
+            B.matvec(coarse_inverse, coarse_inverse32, B.u, B.f, 1, 0); // hypre_GaussElimSolve's role (:4084)
             for (int l = nl - 1; l > 0; l--)
             {
                 Level &F = levels[l - 1];
+                View<Real> V{F}, C{levels[l]};
                 if (F.T.active and matrix_free_transfer)
                 {
-                    fdd::ProfileScope prof("lattice_prolong_kernel", F.T.prolong_bytes(F.n, levels[l].n, 8));
-                    FDD_CALL(fdd_lattice_prolong(F.u.as<double>(), levels[l].u.as<double>(), F.T.owner_dof.as<int>(), F.T.coarse_dof.as<int>(), F.T.n, F.T.m, F.T.lo.data(), F.T.hi.data(), F.T.wl.data(), F.T.num_elements, s));
+                    fdd::ProfileScope prof(f32 ? "lattice_prolong_kernel<f32>" : "lattice_prolong_kernel", F.T.prolong_bytes(F.n, levels[l].n, sizeof(Real)));
+                    fdd::ops::lattice_prolong(V.u.template as<Real>(), C.u.template as<Real>(), F.T.owner_dof.as<int>(), F.T.coarse_dof.as<int>(), F.T.n, F.T.m, F.T.lo.data(), F.T.hi.data(), F.T.wl.data(), F.T.num_elements, s);
                 }
                 else
-                    F.P.matvec(F.u, levels[l].u, 1.0, 1.0); // u_{l-1} += P u_l
-                smooth(l - 1);
+                    V.matvec(F.P, F.s.P, V.u, C.u, 1, 1); // u_{l-1} += P u_l
+                smooth<Real>(l - 1);
             }
         }
+        if (f32 and not f32_io) FDD_CALL(fdd_sub_copy_f64_f32(levels[0].u.as<double>(), levels[0].s.u.as<float>(), levels[0].n, s));
     }
+    void vcycle_launches() { precision == 32 ? vcycle_launches<float>() : vcycle_launches<double>(); }
 
-    // ---------------------------------------------------------------------------------------------
-    // Float = float (AMG/config.hpp:4, swept by run.py:157): the same cycle on f32 values and vectors.
-    // The residual is cast down on entry and the correction cast up on exit (the reference copies Float
-    // data at subdomain.tpp:4008,4142); fused smoother sequence only.
-    // ---------------------------------------------------------------------------------------------
     bool ready32 = false;
-    fdd::memory coarse_inverse_val32;
-    fdd_csr_plan *coarse_plan32 = nullptr;
+    Csr32 coarse_inverse32;
 
     // f32 copy of n doubles in HBM (the levels built on the device have no host values): the same round-to-nearest cast
     static fdd::memory to_f32_device(const fdd::memory &v, size_t n)
@@ -186,8 +249,6 @@ class Hierarchy
         if (n > 0) FDD_CALL(fdd_sub_copy_f32_f64(m.as<float>(), v.as<double>(), (int)n, fdd::dev().stream));
         return m;
     }
-    static fdd::memory to_f32(const CSR_Matrix<double> &M) { return M.host_mirrors() ? to_f32(M.val_hst) : to_f32_device(M.val, (size_t)M.num_nnz); }
-
     template <typename Vec>
     static fdd::memory to_f32(const Vec &v)
     {
@@ -197,13 +258,14 @@ class Hierarchy
         return m;
     }
 
-    // plan of the f32 entries; with short even rows it gets the sliced-ELL copy like the fp64 plans (csr_matrix.hpp)
-    static void blocked_plan(fdd_csr_plan **plan, CSR_Matrix<double> &M, fdd::memory &val32)
+    // the f32 values of M and their plan; with short even rows it gets the sliced-ELL copy like the fp64 plans (csr_matrix.hpp)
+    static void make32(Csr32 &M32, CSR_Matrix<double> &M)
     {
+        M32.val = M.host_mirrors() ? to_f32(M.val_hst) : to_f32_device(M.val, (size_t)M.num_nnz);
         if (M.num_rows == 0 or M.num_cols == 0 or M.ptr_hst.empty()) return;
-        FDD_CALL(fdd_csr_plan_create_f32(plan, M.ptr_hst.data(), M.num_rows, M.num_cols, M.num_nnz));
+        FDD_CALL(fdd_csr_plan_create_f32(&M32.plan, M.ptr_hst.data(), M.num_rows, M.num_cols, M.num_nnz));
         int attached = 0;
-        if (M.num_nnz > M.num_rows) FDD_CALL(fdd_csr_plan_attach_sell(*plan, M.ptr_hst.data(), M.ptr.as<int>(), M.col.as<int>(), val32.ptr(), 1.3, &attached, fdd::dev().stream));
+        if (M.num_nnz > M.num_rows) FDD_CALL(fdd_csr_plan_attach_sell(M32.plan, M.ptr_hst.data(), M.ptr.as<int>(), M.col.as<int>(), M32.val.ptr(), 1.3, &attached, fdd::dev().stream));
     }
 
     void prepare32()
@@ -211,99 +273,22 @@ class Hierarchy
         if (ready32) return;
         for (Level &L : levels)
         {
-            L.A_val32 = to_f32(L.A);
-            blocked_plan(&L.A_plan32, L.A, L.A_val32);
+            make32(L.s.A, L.A);
             if (L.P.num_rows > 0 and not L.P.ptr_hst.empty())
             {
-                L.P_val32 = to_f32(L.P);
-                L.R_val32 = to_f32(L.R);
-                blocked_plan(&L.P_plan32, L.P, L.P_val32);
-                blocked_plan(&L.R_plan32, L.R, L.R_val32);
+                make32(L.s.P, L.P);
+                make32(L.s.R, L.R);
             }
             if (L.T.active)
             {
                 L.T.partial32 = fdd::dev().malloc<float>((size_t)L.T.gather.num_cols);
-                L.T.gather_val32 = to_f32(L.T.gather.val_hst);
-                blocked_plan(&L.T.gather_plan32, L.T.gather, L.T.gather_val32);
+                make32(L.T.gather32, L.T.gather);
             }
-            L.D_val32 = L.D_hst.empty() ? to_f32_device(L.D_val, (size_t)L.n) : to_f32(L.D_hst);
-            for (fdd::memory *m : {&L.f32, &L.u32, &L.r32, &L.v32, &L.work32}) *m = fdd::dev().malloc<float>(L.n);
+            L.s.D_val = L.D_hst.empty() ? to_f32_device(L.D_val, (size_t)L.n) : to_f32(L.D_hst);
+            for (fdd::memory *m : {&L.s.f, &L.s.u, &L.s.r, &L.s.v, &L.s.work}) *m = fdd::dev().malloc<float>(L.n);
         }
-        coarse_inverse_val32 = to_f32(coarse_inverse.val_hst);
-        blocked_plan(&coarse_plan32, coarse_inverse, coarse_inverse_val32);
+        make32(coarse_inverse32, coarse_inverse);
         ready32 = true;
-    }
-
-    // y = alpha*A*x + beta*y_in on f32 data
-    static void matvec32(fdd_csr_plan *plan, CSR_Matrix<double> &M, fdd::memory &val32, fdd::memory &y, fdd::memory *y_in, fdd::memory &x, float alpha, float beta)
-    {
-        fdd::ProfileScope prof("csr_block_kernel<f32>", 8.0 * M.num_nnz + 8.0 * M.num_rows + 4.0 * M.num_cols + (beta != 0.0f ? 4.0 * M.num_rows : 0.0));
-        FDD_CALL(fdd_csr_plan_matvec_to_f32(plan, y.as<float>(), y_in ? y_in->as<float>() : nullptr, M.ptr.as<int>(), M.col.as<int>(), val32.as<float>(), x.as<float>(), alpha, beta, fdd::dev().stream));
-    }
-
-    void smooth32(int l, bool u_is_zero)
-    {
-        Level &L = levels[l];
-        void *s = fdd::dev().stream;
-        const int *ptr = L.A.ptr.as<int>(), *col = L.A.col.as<int>();
-        const float *val = L.A_val32.as<float>(), *D = L.D_val32.as<float>();
-        fdd::memory *in = &L.work32, *out = &L.v32;
-        if (u_is_zero)
-            FDD_CALL(fdd_amg_smooth_start_f32(in->as<float>(), L.r32.as<float>(), L.f32.as<float>(), D, (float)L.coefs[cheby_order - 1], L.n, s));
-        else
-            FDD_CALL(fdd_amg_smooth_residual_matvec_f32(L.A_plan32, in->as<float>(), L.r32.as<float>(), ptr, col, val, L.u32.as<float>(), L.f32.as<float>(), D, (float)L.coefs[cheby_order - 1], s));
-        for (int p = cheby_order - 2; p >= 1; p--)
-        {
-            FDD_CALL(fdd_amg_smooth_polynomial_matvec_f32(L.A_plan32, out->as<float>(), ptr, col, val, in->as<float>(), L.r32.as<float>(), D, (float)L.coefs[p], s));
-            std::swap(in, out);
-        }
-        if (u_is_zero)
-            FDD_CALL(fdd_amg_smooth_update_matvec_from_zero_f32(L.A_plan32, L.u32.as<float>(), ptr, col, val, in->as<float>(), L.r32.as<float>(), D, (float)L.coefs[0], s));
-        else
-            FDD_CALL(fdd_amg_smooth_update_matvec_f32(L.A_plan32, L.u32.as<float>(), ptr, col, val, in->as<float>(), L.r32.as<float>(), D, (float)L.coefs[0], s));
-    }
-
-    void vcycle_launches32()
-    {
-        const int nl = (int)levels.size();
-        void *s = fdd::dev().stream;
-        if (not f32_io) FDD_CALL(fdd_sub_copy_f32_f64(levels[0].f32.as<float>(), levels[0].f.as<double>(), levels[0].n, s));
-        // the pre-smoother writes u = 0 + D w without reading u (smooth32): no zeroing of u
-        if (nl == 1) FDD_CALL(fdd_amg_vector_set_to_value_f32(levels[0].u32.as<float>(), 0.0f, levels[0].n, s));
-        for (int iter = 0; iter < num_vcycles; iter++)
-        {
-            for (int l = 0; l < nl - 1; l++)
-            {
-                Level &L = levels[l];
-                smooth32(l, l > 0 or iter == 0);
-                matvec32(L.A_plan32, L.A, L.A_val32, L.v32, &L.f32, L.u32, -1.0f, 1.0f);
-                if (L.T.active and matrix_free_transfer)
-                {
-                    {
-                        fdd::ProfileScope prof("lattice_restrict_kernel<f32>", L.T.restrict_bytes(L.n, 4));
-                        FDD_CALL(fdd_lattice_restrict_f32(L.T.partial32.as<float>(), L.v32.as<float>(), L.T.owner_dof.as<int>(), L.T.n, L.T.m, L.T.lo.data(), L.T.hi.data(), L.T.wl.data(), L.T.num_elements, s));
-                    }
-                    matvec32(L.T.gather_plan32, L.T.gather, L.T.gather_val32, levels[l + 1].f32, nullptr, L.T.partial32, 1.0f, 0.0f);
-                }
-                else
-                    matvec32(L.R_plan32, L.R, L.R_val32, levels[l + 1].f32, nullptr, L.v32, 1.0f, 0.0f);
-            }
-            Level &C = levels[nl - 1];
-            matvec32(coarse_plan32, coarse_inverse, coarse_inverse_val32, C.u32, nullptr, C.f32, 1.0f, 0.0f);
-            for (int l = nl - 1; l > 0; l--)
-            {
-                Level &F = levels[l - 1];
-                if (F.T.active and matrix_free_transfer)
-                {
-                    fdd::ProfileScope prof("lattice_prolong_kernel<f32>", F.T.prolong_bytes(F.n, levels[l].n, 4));
-                    FDD_CALL(fdd_lattice_prolong_f32(F.u32.as<float>(), levels[l].u32.as<float>(), F.T.owner_dof.as<int>(), F.T.coarse_dof.as<int>(), F.T.n, F.T.m, F.T.lo.data(), F.T.hi.data(), F.T.wl.data(), F.T.num_elements, s));
-                }
-                else
-                    matvec32(F.P_plan32, F.P, F.P_val32, F.u32, &F.u32, levels[l].u32, 1.0f, 1.0f);
-                smooth32(l - 1, false);
-            }
-        }
-        if (not f32_io) FDD_CALL(fdd_sub_copy_f64_f32(levels[0].u.as<double>(), levels[0].u32.as<float>(), levels[0].n, s));
     }
 
   public:
@@ -313,7 +298,7 @@ class Hierarchy
     bool fused_smoother = true; // element-wise smoother kernels as SpMV epilogues (false: the reference's launch sequence)
     int precision = 64;         // AMG/config.hpp:4 `Float`: 64 = double, 32 = float (set_precision)
     bool f32_io = false;        // precision 32 with a caller that works in float itself (the single-precision inner solve): the right-hand
-                                // side is given in levels[0].f32, the correction is read from levels[0].u32, no casts at the two ends
+                                // side is given in levels[0].s.f, the correction is read from levels[0].s.u, no casts at the two ends
 
     void set_f32_io(bool on)
     {
@@ -323,9 +308,9 @@ class Hierarchy
     fdd::memory &rhs32()
     {
         prepare32();
-        return levels[0].f32;
+        return levels[0].s.f;
     }
-    fdd::memory &solution32() { return levels[0].u32; }
+    fdd::memory &solution32() { return levels[0].s.u; }
 
     // the interpolator of a geometric level applied matrix-free where the hierarchy's builder handed its maps over
     // (set_lattice_transfer); false: the CSR interpolator and its transpose, as on every other level.  The same operator
@@ -518,7 +503,7 @@ class Hierarchy
         if (f32) prepare32();
         if (use_graph and not graph_failed)
         {
-            void *&graph = graphs[(f32 and f32_io) ? levels[0].u32.ptr() : levels[0].u.ptr()];
+            void *&graph = graphs[(f32 and f32_io) ? levels[0].s.u.ptr() : levels[0].u.ptr()];
             if (graph == nullptr)
             {
                 // captured once on a private stream (the caller's may be the default stream, which
@@ -531,10 +516,7 @@ class Hierarchy
                         const bool profiling = fdd::profiler().enabled; // no event records inside a capture
                         fdd::profiler().enabled = false;
                         fdd::dev().stream = cs;
-                        if (f32)
-                            vcycle_launches32();
-                        else
-                            vcycle_launches();
+                        vcycle_launches();
                         fdd::dev().stream = s;
                         fdd::profiler().enabled = profiling;
                         if (fdd_graph_end_capture(cs, &graph) != 0) graph = nullptr;
@@ -550,18 +532,15 @@ class Hierarchy
                 return;
             }
         }
-        if (f32)
-            vcycle_launches32();
-        else
-            vcycle_launches();
+        vcycle_launches();
     }
 
     // The same cycle with its correction written into `out` (at least fine_size() entries of the cycle's output
-    // type: double, or float under f32_io) instead of levels[0].u / u32: the caller's vector stands in for the level's
+    // type: double, or float under f32_io) instead of levels[0].u / s.u: the caller's vector stands in for the level's
     // for the duration of the call.  The first call with a given vector captures a graph of its own.
     void vcycle_into(fdd::memory &out)
     {
-        fdd::memory &slot = (precision == 32 and f32_io) ? levels[0].u32 : levels[0].u;
+        fdd::memory &slot = (precision == 32 and f32_io) ? levels[0].s.u : levels[0].u;
         if (precision == 32) prepare32();
         const fdd::memory saved = slot;
         slot = fdd::memory(out.ptr(), (size_t)levels[0].n, (precision == 32 and f32_io) ? sizeof(float) : sizeof(double), false);

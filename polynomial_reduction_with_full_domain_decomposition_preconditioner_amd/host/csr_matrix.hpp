@@ -430,8 +430,10 @@ class CSR_Matrix
         FDD_CALL(fdd_csr_plan_dssum(plan, out, t, ptr.as<int>(), col.as<int>(), u, node_weight, point_mask, row_lo, row_hi, mode, fdd::dev().stream));
     }
 
-    // t[row] = sum of u over the row's entries on float vectors (the gather of a boolean matrix in the single-precision preconditioner)
-    void gather_f32(float *t, const float *u, int row_lo, int row_hi)
+    // t[row] = (sum of u over the row's entries) * node_weight[row]: the gather half alone, on double or on float vectors
+    // (the single-precision preconditioner, which has no weight)
+    void gather(double *t, const double *u, int row_lo, int row_hi, const double *node_weight = nullptr) { gather_scatter(nullptr, t, u, node_weight, nullptr, row_lo, row_hi, 1); }
+    void gather(float *t, const float *u, int row_lo, int row_hi)
     {
         if (row_hi <= row_lo or num_nnz == 0) return;
         fdd::ProfileScope prof((plan_pipelined ? "csr_short_pipelined_kernel<gather, f32>" : "gather_block_f32_kernel"), 8.0 * (row_hi - row_lo) + 8.0 * num_nnz * ((double)(row_hi - row_lo) / std::max(num_rows, 1)));
@@ -445,18 +447,19 @@ class CSR_Matrix
         FDD_CALL(fdd_csr_plan_gather_weighted_norm2(plan, out_dev, ws, ptr.as<int>(), col.as<int>(), u, node_weight, fdd::dev().stream));
     }
 
-    void multiply(fdd::memory &Au, fdd::memory &u)
+    void multiply(fdd::memory &Au, fdd::memory &u) { multiply(Au.as<double>(), u.as<double>()); }
+    void multiply(double *Au, const double *u)
     {
         materialize();
         if ((num_rows == 0) or (num_cols == 0)) return;
         initialization_check();
         if (num_nnz == 0) // never assembled (csr_matrix.tpp:96 leaves no device arrays): A = 0
         {
-            FDD_CALL(fdd_set_to_value(Au.as<double>(), 0.0, num_rows, 0, fdd::dev().stream));
+            FDD_CALL(fdd_set_to_value(Au, 0.0, num_rows, 0, fdd::dev().stream));
             return;
         }
         fdd::ProfileScope prof(plan_kind == 0 ? "csr_row_kernel<EpiPlain>" : "csr_block_kernel<EpiPlain>", algorithmic_bytes(false));
-        FDD_CALL(fdd_csr_plan_multiply(plan, Au.as<double>(), ptr.as<int>(), col.as<int>(), val.as<double>(), u.as<double>(), nullptr, fdd::dev().stream));
+        FDD_CALL(fdd_csr_plan_multiply(plan, Au, ptr.as<int>(), col.as<int>(), val.as<double>(), u, nullptr, fdd::dev().stream));
     }
 
     void multiply_range(fdd::memory &Au, fdd::memory &u, int row_start, int row_end)

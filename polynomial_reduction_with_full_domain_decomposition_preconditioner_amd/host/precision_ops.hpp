@@ -1,0 +1,84 @@
+/*
+ * precision_ops.hpp -- the kernel entries that exist once per precision (fdd_x on double, fdd_x_f32 on float vectors),
+ * named once: inline overloads on the pointer type, so that the inner GMRES (subdomain.hpp) and the V-cycle (amg.hpp)
+ * are written once over `Real`.  Where the two precisions differ in more than the suffix the difference is spelled
+ * out here and nowhere else.  Scalars on the device (scales, coefficients, reduction results) are double in both.
+ * The profile labels are the ones bench.py's kernel table keys on.
+ */
+#ifndef FDD_PRECISION_OPS_HPP
+#define FDD_PRECISION_OPS_HPP
+
+#include "config.hpp"
+
+namespace fdd
+{
+namespace ops
+{
+
+// ---- element-wise ----
+inline void scaling_dev(double *au, const double *scale_dev, const double *u, int n, void *s) { FDD_CALL(fdd_vector_scaling_dev(au, scale_dev, u, n, s)); }
+inline void scaling_dev(float *au, const double *scale_dev, const float *u, int n, void *s) { FDD_CALL(fdd_vector_scaling_dev_f32(au, scale_dev, u, n, s)); }
+inline void diagonal_scaling_dev(double *z, const double *d, const double *scale_dev, const double *u, int n, void *s) { FDD_CALL(fdd_vector_diagonal_scaling_dev(z, d, scale_dev, u, n, s)); }
+inline void diagonal_scaling_dev(float *z, const float *d, const double *scale_dev, const float *u, int n, void *s) { FDD_CALL(fdd_vector_diagonal_scaling_dev_f32(z, d, scale_dev, u, n, s)); }
+inline void vector_vector_addition(double *uv, double a, const double *u, double b, const double *v, int n, void *s) { FDD_CALL(fdd_vector_vector_addition(uv, a, u, b, v, n, s)); }
+inline void vector_vector_addition(float *uv, float a, const float *u, float b, const float *v, int n, void *s) { FDD_CALL(fdd_vector_vector_addition_f32(uv, a, u, b, v, n, s)); }
+inline void set_to_zero(double *u, int n, void *s) { FDD_CALL(fdd_set_to_value(u, 0.0, n, 0, s)); }
+inline void set_to_zero(float *u, int n, void *s) { FDD_CALL(fdd_amg_vector_set_to_value_f32(u, 0.0f, n, s)); }
+inline void gather_indexed(double *out, const double *in, const int *index, int n, void *s) { FDD_CALL(fdd_gather_indexed(out, in, index, nullptr, n, s)); }
+inline void gather_indexed(float *out, const float *in, const int *index, int n, void *s) { FDD_CALL(fdd_gather_indexed_f32(out, in, index, n, s)); }
+inline void scatter_add_indexed(double *y, const int *index, const double *t, int n, void *s) { FDD_CALL(fdd_scatter_add_indexed(y, index, t, n, s)); }
+inline void scatter_add_indexed(float *y, const int *index, const float *t, int n, void *s) { FDD_CALL(fdd_scatter_add_indexed_f32(y, index, t, n, s)); }
+
+// ---- the Arnoldi step's reductions: out[k] = <a, s_k b_k>, and dst = y + sign sum c_k (s_k x_k) with |dst|^2 ----
+// w: the norm weight of the dofs (null: 1 everywhere, not read).  The float entries take none.
+inline void multi_dot(double *out, double *ws, const double *a, const double *const *b, const double *b_scale, int m, const double *w, int n, void *s)
+{
+    ProfileScope prof("reduce_vec2_kernel<MultiDotW>", 8.0 * n * (m + 1 + (w ? 1 : 0)));
+    FDD_CALL(fdd_multi_weighted_inner_product_scaled(out, ws, a, b, b_scale, m, w, n, s));
+}
+inline void multi_dot(double *out, double *ws, const float *a, const float *const *b, const double *b_scale, int m, const double *, int n, void *s)
+{
+    ProfileScope prof("reduce_vec2_kernel<MultiDotF32>", 4.0 * n * (m + 1));
+    FDD_CALL(fdd_multi_inner_product_scaled_f32(out, ws, a, b, b_scale, m, n, s));
+}
+inline void multi_axpy_norm2(double *out, double *ws, double *dst, const double *y, const double *coeffs_dev, double sign, const double *const *x, const double *x_scale, int m, const double *w, int n, void *s)
+{
+    ProfileScope prof("reduce_vec2_kernel<MultiAxpyNorm>", 8.0 * n * (m + 2 + (w ? 1 : 0)));
+    FDD_CALL(fdd_multi_axpy_norm2_scaled_dev(out, ws, dst, y, coeffs_dev, sign, x, x_scale, m, w, n, s));
+}
+inline void multi_axpy_norm2(double *out, double *ws, float *dst, const float *y, const double *coeffs_dev, double sign, const float *const *x, const double *x_scale, int m, const double *, int n, void *s)
+{
+    ProfileScope prof("reduce_vec2_kernel<MultiAxpyNormF32>", 4.0 * n * (m + 2));
+    FDD_CALL(fdd_multi_axpy_norm2_scaled_dev_f32(out, ws, dst, y, coeffs_dev, sign, x, x_scale, m, n, s));
+}
+
+// ---- the solution update q (+)= sum_k c_k (s_k v_k); q_is_zero: q is not read ----
+// all m vectors (the host knows the column count).  Float has the limited entry only and runs it without a limit.
+inline void lincomb(double *q, int q_is_zero, const double *coeffs_dev, const double *const *v, const double *v_scale, int m, int n, void *s)
+{
+    ProfileScope prof("ew_vec2_kernel<MultiAxpy>", 8.0 * n * (m + (q_is_zero ? 1 : 2)));
+    FDD_CALL(fdd_multi_lincomb_scaled_dev(q, q_is_zero, coeffs_dev, v, v_scale, m, n, s));
+}
+inline void lincomb(float *q, int q_is_zero, const double *coeffs_dev, const float *const *v, const double *v_scale, int m, int n, void *s) { FDD_CALL(fdd_multi_lincomb_limited_dev_f32(q, q_is_zero, coeffs_dev, v, v_scale, nullptr, m, n, s)); }
+// vectors 0 .. (int)*last_dev only (the column count stays on the device: the lazy history)
+inline void lincomb_limited(double *q, int q_is_zero, const double *coeffs_dev, const double *const *v, const double *v_scale, const double *last_dev, int m, int n, void *s)
+{
+    ProfileScope prof("ew_vec2_kernel<MultiAxpy>", 8.0 * n * (m + 2));
+    FDD_CALL(fdd_multi_lincomb_limited_dev(q, q_is_zero, coeffs_dev, v, v_scale, last_dev, m, n, s));
+}
+inline void lincomb_limited(float *q, int q_is_zero, const double *coeffs_dev, const float *const *v, const double *v_scale, const double *last_dev, int m, int n, void *s) { FDD_CALL(fdd_multi_lincomb_limited_dev_f32(q, q_is_zero, coeffs_dev, v, v_scale, last_dev, m, n, s)); }
+
+// ---- V-cycle (amg.hpp) ----
+inline void amg_set_to_value(double *u, double value, int n, void *s) { FDD_CALL(fdd_amg_vector_set_to_value(u, value, n, s)); }
+inline void amg_set_to_value(float *u, float value, int n, void *s) { FDD_CALL(fdd_amg_vector_set_to_value_f32(u, value, n, s)); }
+inline void amg_smooth_start(double *work, double *Sr, const double *f, const double *D, double coef, int n, void *s) { FDD_CALL(fdd_amg_smooth_start(work, Sr, f, D, coef, n, s)); }
+inline void amg_smooth_start(float *work, float *Sr, const float *f, const float *D, float coef, int n, void *s) { FDD_CALL(fdd_amg_smooth_start_f32(work, Sr, f, D, coef, n, s)); }
+inline void lattice_restrict(double *partial, const double *fine, const int *owner_dof, int n, int m, const int *lo, const int *hi, const double *wl, long long ne, void *s) { FDD_CALL(fdd_lattice_restrict(partial, fine, owner_dof, n, m, lo, hi, wl, ne, s)); }
+inline void lattice_restrict(float *partial, const float *fine, const int *owner_dof, int n, int m, const int *lo, const int *hi, const double *wl, long long ne, void *s) { FDD_CALL(fdd_lattice_restrict_f32(partial, fine, owner_dof, n, m, lo, hi, wl, ne, s)); }
+inline void lattice_prolong(double *u, const double *coarse, const int *owner_dof, const int *coarse_dof, int n, int m, const int *lo, const int *hi, const double *wl, long long ne, void *s) { FDD_CALL(fdd_lattice_prolong(u, coarse, owner_dof, coarse_dof, n, m, lo, hi, wl, ne, s)); }
+inline void lattice_prolong(float *u, const float *coarse, const int *owner_dof, const int *coarse_dof, int n, int m, const int *lo, const int *hi, const double *wl, long long ne, void *s) { FDD_CALL(fdd_lattice_prolong_f32(u, coarse, owner_dof, coarse_dof, n, m, lo, hi, wl, ne, s)); }
+
+} // namespace ops
+} // namespace fdd
+
+#endif

@@ -84,10 +84,8 @@ struct Stiffness_Operator // subdomain.hpp:46-70
         int level = 0;
         int poly_degree = 1;
         int num_elements = 0;
-        bool contiguous = true;  // elements e*(N+1)^3 apart from `first_offset`
-        int first_offset = 0;
-        fdd::memory elem_offset; // int[num_elements] when not contiguous
-        const double *G[NUM_GEOM_FACTS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // geometric factors of the list's first point (contiguous lists)
+        int first_offset = 0;    // the list is one run of elements, (N+1)^dim points apart from here
+        const double *G[NUM_GEOM_FACTS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // geometric factors of the list's first point
         // affine elements (an option, Subdomain::set_affine_geometry): six numbers per element + the GLL weights stand for the factor arrays
         bool affine = false;
         double affine_deviation = -1.0;
@@ -143,10 +141,36 @@ class Subdomain
     fdd::memory reduce_ws;
     fdd::memory scalars;
 
-    std::vector<fdd::memory> VA; // assembled (dof-space) copies Qt_w V[i] of the Krylov basis
-    fdd::memory qa;              // Qt_w q
-    std::vector<fdd::memory> ZA;  // assembled-space inner solve: preconditioned basis (only with the AMG preconditioner)
-    fdd::memory ua, fa;          // assembled-space inner solve from point vectors: solution and right-hand side over the dofs
+    // the dof-space vectors of the inner solve, one set per precision of the preconditioner
+    template <typename Real>
+    struct DofKrylov
+    {
+        std::vector<fdd::memory> VA; // assembled (dof-space) copies Qt_w V[i] of the Krylov basis
+        fdd::memory qa;              // Qt_w q
+        std::vector<fdd::memory> ZA; // preconditioned basis (only with the V-cycle or point-Jacobi in the slot)
+        fdd::memory ua, fa;          // solution and right-hand side over the dofs (allocated by the solves that do not work on the caller's)
+        // m + 1 basis vectors and qa of na entries, and with keep_Z the m preconditioned ones: storage made for another
+        // num_vectors is replaced
+        void ensure(int m, int na, bool keep_Z)
+        {
+            if ((int)VA.size() != m + 1)
+            {
+                for (auto &v : VA) v.free();
+                VA.resize(m + 1);
+                for (auto &v : VA) v = fdd::dev().malloc<Real>(na);
+                qa.free();
+                qa = fdd::dev().malloc<Real>(na);
+            }
+            if (keep_Z and (int)ZA.size() != m)
+            {
+                for (auto &v : ZA) v.free();
+                ZA.resize(m);
+                for (auto &v : ZA) v = fdd::dev().malloc<Real>(na);
+            }
+        }
+    };
+    DofKrylov<double> krylov64;
+    DofKrylov<float> krylov32;
     fdd::memory point_dof_dev;   // dof of every level-0 point (-1: none): Q as an index array
     fdd::memory gmres_state;     // device-side GMRES bookkeeping (fdd_gmres_*_dev)
     bool norm_weight_is_one = false; // norm_weight == 1 everywhere (subdomain.tpp:2731-2747 without interface dofs)
@@ -815,40 +839,6 @@ class Subdomain
     int dof_space_size() const { return is_composite ? num_dofs : subdomain_operator.num_extended_dofs; }
     int dof_alloc_size() const { return is_composite ? W_len : subdomain_operator.num_extended_dofs; }
 
-    // qa (dofs) = [Qt A_L Q | A_sup] (s x~): the operator of the inner iteration on a dof vector.  x~ is one of the
-    // Krylov vectors; in a composite its allocation carries the copies and hanging values behind the dofs (W).
-    void operator_dofs(fdd::memory &qa_out, fdd::memory &xa, const double *scale_dev = nullptr)
-    {
-        if (not is_composite)
-        {
-            stiffness_from_dofs(q_k, xa, scale_dev);
-            gather_weighted(qa_out, q_k);
-            return;
-        }
-        void *stream = fdd::dev().stream;
-        const int nse = subdomain_operator.num_extended_dofs, ns = subdomain_operator.num_dofs, nI = num_interface_dofs, n_reg = superdomain_operator.num_dofs - nI;
-        if (n_sup_copies > 0) FDD_CALL(fdd_gather_indexed(xa.as<double>() + num_dofs, xa.as<double>(), copy_src.template as<int>(), nullptr, n_sup_copies, stream));
-        if (n_slaves > 0)
-        {
-            fdd::memory slaves = xa.slice(slave_base, n_slaves);
-            S_slave.multiply(slaves, xa);
-        }
-        stiffness_from_dofs(q_k, xa, scale_dev);
-        G_unit.gather_scatter(nullptr, qa_out.as<double>(), q_k.as<double>(), nullptr, nullptr, 0, nse, 1);
-        if (n_slaves > 0)
-        {
-            G_unit.gather_scatter(nullptr, slave_vals.as<double>() - nse, q_k.as<double>(), nullptr, nullptr, nse, nse + n_slaves, 1);
-            St_slave.multiply(st_tmp, slave_vals);
-            FDD_CALL(fdd_scatter_add_indexed(qa_out.as<double>(), st_rows.template as<int>(), st_tmp.as<double>(), St_slave.num_rows, stream));
-        }
-        if (n_reg > 0)
-        {
-            fdd::memory out = qa_out.slice(ns, n_reg), in = xa.slice(ns - nI, superdomain_operator.num_extended_dofs);
-            A_sup_reg.multiply(out, in);
-            if (scale_dev) FDD_CALL(fdd_vector_scaling_dev(out.as<double>(), scale_dev, out.as<double>(), n_reg, stream));
-        }
-    }
-
     // the right-hand side of the composite in dof space from the tree-exchanged composite vector T r (subdomain.tpp:4566-4646)
     // own_assembled: the sums over the rank's OWN points of every own dof, already formed by the caller (the outer
     // solve's node residual, which it keeps assembled): then only the ring points are gathered here
@@ -907,10 +897,8 @@ class Subdomain
         bool ready = false;
         std::vector<std::array<fdd::memory, NUM_GEOM_FACTS>> G; // per level list
         std::vector<fdd::memory> D_hat;                          // per level
-        fdd::memory S_val, St_val, Asup_val;
-        fdd_csr_plan *S_plan = nullptr, *St_plan = nullptr, *Asup_plan = nullptr;
-        std::vector<fdd::memory> VA, ZA;
-        fdd::memory qa, ua, fa, q_pts, slaves, st_tmp;
+        amg::Csr32 S, St, Asup;                                  // S_slave, St_slave, A_sup_reg
+        fdd::memory q_pts, slaves, st_tmp;
     } sp;
 
     template <typename Vec>
@@ -939,218 +927,109 @@ class Subdomain
         }
         sp.D_hat.resize(num_levels);
         for (int l = 0; l < num_levels; l++) sp.D_hat[l] = to_float(D_hat[l].first);
-        auto plan32 = [](fdd_csr_plan **plan, CSR_Matrix<DType> &M, fdd::memory &val32) {
+        auto plan32 = [](amg::Csr32 &M32, CSR_Matrix<DType> &M) {
             if (M.num_rows == 0 or M.num_nnz == 0) return;
-            val32 = to_float(M.val_hst);
-            FDD_CALL(fdd_csr_plan_create_f32(plan, M.ptr_hst.data(), M.num_rows, M.num_cols, M.num_nnz));
+            M32.val = to_float(M.val_hst);
+            FDD_CALL(fdd_csr_plan_create_f32(&M32.plan, M.ptr_hst.data(), M.num_rows, M.num_cols, M.num_nnz));
         };
         if (is_composite)
         {
-            plan32(&sp.S_plan, S_slave, sp.S_val);
-            plan32(&sp.St_plan, St_slave, sp.St_val);
-            plan32(&sp.Asup_plan, A_sup_reg, sp.Asup_val);
+            plan32(sp.S, S_slave);
+            plan32(sp.St, St_slave);
+            plan32(sp.Asup, A_sup_reg);
         }
-        const int na = std::max(dof_alloc_size(), 1);
-        sp.qa = fdd::dev().malloc<float>(na);
-        sp.ua = fdd::dev().malloc<float>(na);
-        sp.fa = fdd::dev().malloc<float>(na);
         sp.q_pts = fdd::dev().malloc<float>(std::max(subdomain_operator.num_points, 1));
         sp.slaves = fdd::dev().malloc<float>(std::max(n_slaves, 1));
         sp.st_tmp = fdd::dev().malloc<float>(std::max(St_slave.num_rows, 1));
         sp.ready = true;
     }
 
-    static void matvec32(fdd_csr_plan *plan, CSR_Matrix<DType> &M, fdd::memory &val32, float *y, const float *y_in, const float *x, float alpha, float beta)
+    // y = M x with one of the composite's small matrices; a matrix without entries leaves the float y alone
+    static void multiply(CSR_Matrix<DType> &M, amg::Csr32 &, double *y, const double *x) { M.multiply(y, x); }
+    static void multiply(CSR_Matrix<DType> &M, amg::Csr32 &M32, float *y, const float *x)
     {
-        if (plan == nullptr) return;
-        FDD_CALL(fdd_csr_plan_matvec_to_f32(plan, y, y_in, M.ptr.template as<int>(), M.col.template as<int>(), val32.template as<float>(), x, alpha, beta, fdd::dev().stream));
+        if (M32.plan) FDD_CALL(fdd_csr_plan_matvec_to_f32(M32.plan, y, nullptr, M.ptr.template as<int>(), M.col.template as<int>(), M32.val.template as<float>(), x, 1.0f, 0.0f, fdd::dev().stream));
     }
 
-    // operator_dofs on float vectors
-    void operator_dofs_f32(fdd::memory &qa_out, fdd::memory &xa, const double *scale_dev = nullptr)
+    // q (points) = A_local (Q (s z~)), s = *scale_dev when given (a basis vector kept unnormalised): one launch per level list
+    void stiffness_from_dofs(double *q, const double *za, const double *scale_dev = nullptr)
     {
         void *stream = fdd::dev().stream;
-        float *x = xa.as<float>(), *q = sp.q_pts.template as<float>(), *y = qa_out.as<float>();
-        if (is_composite)
+        const int *point_dof = point_dof_dev.template as<int>();
+        for (auto &ll : subdomain_operator.level_lists)
         {
-            if (n_sup_copies > 0) FDD_CALL(fdd_gather_indexed_f32(x + num_dofs, x, copy_src.template as<int>(), n_sup_copies, stream));
-            if (n_slaves > 0) matvec32(sp.S_plan, S_slave, sp.S_val, x + slave_base, nullptr, x, 1.0f, 0.0f);
+            const double n3 = (double)(ll.poly_degree + 1) * (ll.poly_degree + 1) * (ll.poly_degree + 1);
+            const double *D = subdomain_operator.D_hat[ll.level].template as<double>();
+            const bool mfma = ll.poly_degree >= 11 and mfma_stiffness;
+            if (ll.affine)
+            {
+                fdd::ProfileScope prof(mfma ? "mfma_stiffness_kernel<gather,affine>" : "fused_stiffness_kernel<gather,affine>", (12.0 * n3) * ll.num_elements + 8.0 * subdomain_operator.num_extended_dofs);
+                FDD_CALL((mfma ? fdd_stiffness_matrix_mfma_affine : fdd_stiffness_matrix_affine)(q + ll.first_offset, za, scale_dev, point_dof + ll.first_offset, D, ll.affine_c.template as<double>(), ll.affine_w.template as<double>(), nullptr, ll.num_elements, ll.poly_degree, stream));
+                continue;
+            }
+            fdd::ProfileScope prof(mfma ? "mfma_stiffness_kernel<gather>" : "fused_stiffness_kernel<gather>", (60.0 * n3) * ll.num_elements + 8.0 * subdomain_operator.num_extended_dofs);
+            FDD_CALL((mfma ? fdd_stiffness_matrix_mfma_gather : fdd_sub_stiffness_matrix_gather_scaled)(q + ll.first_offset, za, scale_dev, point_dof + ll.first_offset, D, ll.G, nullptr, ll.num_elements, ll.poly_degree, stream));
         }
+    }
+    // the same on float data (prepare_single_precision): no MFMA form
+    void stiffness_from_dofs(float *q, const float *za, const double *scale_dev = nullptr)
+    {
+        void *stream = fdd::dev().stream;
+        const int *point_dof = point_dof_dev.template as<int>();
         for (size_t k = 0; k < subdomain_operator.level_lists.size(); k++)
         {
             auto &ll = subdomain_operator.level_lists[k];
             const double n3 = (double)(ll.poly_degree + 1) * (ll.poly_degree + 1) * (ll.poly_degree + 1);
+            const float *D = sp.D_hat[ll.level].template as<float>();
             if (ll.affine)
             {
                 fdd::ProfileScope prof("fused_stiffness_kernel<gather,f32,affine>", (8.0 * n3) * ll.num_elements + 4.0 * subdomain_operator.num_extended_dofs);
-                FDD_CALL(fdd_stiffness_matrix_affine_f32(q + ll.first_offset, x, scale_dev, point_dof_dev.template as<int>() + ll.first_offset, sp.D_hat[ll.level].template as<float>(), ll.affine_c32.template as<float>(), ll.affine_w32.template as<float>(), nullptr, ll.num_elements, ll.poly_degree, stream));
+                FDD_CALL(fdd_stiffness_matrix_affine_f32(q + ll.first_offset, za, scale_dev, point_dof + ll.first_offset, D, ll.affine_c32.template as<float>(), ll.affine_w32.template as<float>(), nullptr, ll.num_elements, ll.poly_degree, stream));
                 continue;
             }
             fdd::ProfileScope prof("fused_stiffness_kernel<gather,f32>", (32.0 * n3) * ll.num_elements + 4.0 * subdomain_operator.num_extended_dofs);
             const float *Gs[NUM_GEOM_FACTS];
             for (int g = 0; g < NUM_GEOM_FACTS; g++) Gs[g] = sp.G[k][g].template as<float>();
-            FDD_CALL(fdd_sub_stiffness_matrix_gather_scaled_f32(q + ll.first_offset, x, scale_dev, point_dof_dev.template as<int>() + ll.first_offset, sp.D_hat[ll.level].template as<float>(), Gs, nullptr, ll.num_elements, ll.poly_degree, stream));
-        }
-        if (not is_composite)
-        {
-            CSR_Matrix<DType> &Qt = subdomain_operator.Qt;
-            Qt.gather_f32(y, q, 0, subdomain_operator.num_extended_dofs);
-            return;
-        }
-        const int nse = subdomain_operator.num_extended_dofs, ns = subdomain_operator.num_dofs, nI = num_interface_dofs, n_reg = superdomain_operator.num_dofs - nI;
-        G_unit.gather_f32(y, q, 0, nse);
-        if (n_slaves > 0)
-        {
-            float *sl = sp.slaves.template as<float>();
-            G_unit.gather_f32(sl - nse, q, nse, nse + n_slaves);
-            matvec32(sp.St_plan, St_slave, sp.St_val, sp.st_tmp.template as<float>(), nullptr, sl, 1.0f, 0.0f);
-            FDD_CALL(fdd_scatter_add_indexed_f32(y, st_rows.template as<int>(), sp.st_tmp.template as<float>(), St_slave.num_rows, stream));
-        }
-        if (n_reg > 0)
-        {
-            matvec32(sp.Asup_plan, A_sup_reg, sp.Asup_val, y + ns, nullptr, x + (ns - nI), 1.0f, 0.0f);
-            if (scale_dev) FDD_CALL(fdd_vector_scaling_dev_f32(y + ns, scale_dev, y + ns, n_reg, stream));
+            FDD_CALL(fdd_sub_stiffness_matrix_gather_scaled_f32(q + ll.first_offset, za, scale_dev, point_dof + ll.first_offset, D, Gs, nullptr, ll.num_elements, ll.poly_degree, stream));
         }
     }
 
-    // gmres_dofs_device on float vectors (same recurrences, same device bookkeeping); fa / ua stay double at the interface
-    void gmres_dofs_device_f32(fdd::memory &ua_out, fdd::memory &fa_in, bool print_history, bool use_relative)
+    // y (dofs) = [Qt A_L Q | A_sup] (s x~): the operator of the inner iteration on a dof vector.  x~ is one of the
+    // Krylov vectors; in a composite its allocation carries the copies and hanging values behind the dofs (W), which
+    // are written here.
+    template <typename Real>
+    void operator_dofs(Real *y, Real *x, const double *scale_dev = nullptr)
     {
-        prepare_single_precision();
-        const int nd = dof_space_size();
-        const int na = std::max(dof_alloc_size(), 1);
-        const int m = num_vectors;
+        constexpr bool f32 = std::is_same<Real, float>::value;
         void *stream = fdd::dev().stream;
-        if ((int)sp.VA.size() != m + 1)
+        Real *q = (f32 ? sp.q_pts : q_k).template as<Real>();
+        const int nse = subdomain_operator.num_extended_dofs;
+        if (not is_composite)
         {
-            for (auto &v : sp.VA) v.free();
-            sp.VA.resize(m + 1);
-            for (auto &v : sp.VA) v = fdd::dev().malloc<float>(na);
-        }
-        const bool jacobi = use_jacobi and not use_preconditioner;
-        const bool pre = use_preconditioner or jacobi;
-        if (jacobi) ensure_jacobi();
-        if (pre and (int)sp.ZA.size() != m)
-        {
-            for (auto &v : sp.ZA) v.free();
-            sp.ZA.resize(m);
-            for (auto &v : sp.ZA) v = fdd::dev().malloc<float>(na);
-        }
-        if (not gmres_state.ptr()) gmres_state = fdd::dev().malloc<char>(fdd_gmres_state_bytes());
-        residual_history.clear();
-        double *sc = scalars.as<double>();
-        double *ws = reduce_ws.as<double>();
-        void *st = gmres_state.ptr();
-        const double *y_dev = nullptr, *inv_dev = nullptr;
-        FDD_CALL(fdd_gmres_coefficients(st, &y_dev));
-        FDD_CALL(fdd_gmres_scales(st, &inv_dev));
-
-        FDD_CALL(fdd_sub_copy_f32_f64(sp.fa.template as<float>(), fa_in.as<double>(), nd, stream)); // copy_from_domain_data, subdomain.okl:268-274
-
-        auto dot = [&](double *out_dev, fdd::memory &a, const float *const *b, const double *b_scale, int count) {
-            fdd::ProfileScope prof("reduce_vec2_kernel<MultiDotF32>", 4.0 * nd * (count + 1));
-            FDD_CALL(fdd_multi_inner_product_scaled_f32(out_dev, ws, a.template as<float>(), b, b_scale, count, nd, stream));
-        };
-
-        if (use_preconditioner)
-        {
-            amg_checked();
-            if (amg_hierarchy.precision != 32 and not amg_hierarchy.set_precision(32))
-            {
-                fprintf(stderr, "ERROR: the single-precision preconditioner needs a Chebyshev order of at least 2\n");
-                exit(EXIT_FAILURE);
-            }
-            amg_hierarchy.set_f32_io(true);
-        }
-
-        int iter = 0;
-        bool first_cycle = true;
-        history_pending = false;
-        const bool lazy = lazy_history and max_iterations <= m and fdd::globals().pstdout_file == nullptr;
-        std::vector<const float *> W(m + 1), ptrs(m + 1);
-        std::vector<fdd::memory *> Wm(m + 1);
-        std::vector<double> hist(FDD_MULTI_MAX + 1);
-
-        while (iter < max_iterations)
-        {
-            if (first_cycle)
-                Wm[0] = &sp.fa;
+            stiffness_from_dofs(q, x, scale_dev);
+            if constexpr (f32)
+                subdomain_operator.Qt.gather(y, q, 0, nse); // the float gather takes no norm weight
             else
-            {
-                operator_dofs_f32(sp.qa, sp.ua);
-                FDD_CALL(fdd_vector_vector_addition_f32(sp.VA[0].template as<float>(), 1.0f, sp.fa.template as<float>(), -1.0f, sp.qa.template as<float>(), nd, stream));
-                Wm[0] = &sp.VA[0];
-            }
-            W[0] = Wm[0]->template as<float>();
-            {
-                const float *self[1] = {W[0]};
-                dot(sc, *Wm[0], self, nullptr, 1);
-            }
-            FDD_CALL(fdd_gmres_begin_dev(st, sc, first_cycle ? 1 : 0, stream));
-
-            for (int j = 0; j < m; j++)
-            {
-                if (use_preconditioner)
-                {
-                    fdd::memory &rhs = amg_hierarchy.rhs32();
-                    FDD_CALL(fdd_vector_scaling_dev_f32(rhs.template as<float>(), inv_dev + j, W[j], nd, stream));
-                    amg_hierarchy.vcycle_into(sp.ZA[j]);
-                    operator_dofs_f32(sp.qa, sp.ZA[j]);
-                }
-                else if (jacobi)
-                {
-                    FDD_CALL(fdd_vector_diagonal_scaling_dev_f32(sp.ZA[j].template as<float>(), jacobi_dinv_f32.template as<float>(), inv_dev + j, W[j], nd, stream));
-                    operator_dofs_f32(sp.qa, sp.ZA[j]);
-                }
-                else
-                    operator_dofs_f32(sp.qa, *Wm[j], inv_dev + j);
-
-                double *slot = sc + (j & 1) * FDD_GMRES_SLOT;
-                dot(slot, sp.qa, W.data(), inv_dev, j + 1);
-                {
-                    fdd::ProfileScope prof("reduce_vec2_kernel<MultiAxpyNormF32>", 4.0 * nd * (j + 3));
-                    FDD_CALL(fdd_multi_axpy_norm2_scaled_dev_f32(slot + (j + 1), ws, (j + 1 < m or not skip_last_basis_store) ? sp.VA[j + 1].template as<float>() : nullptr, sp.qa.template as<float>(), slot, -1.0, W.data(), inv_dev, j + 1, nd, stream)); // the cycle's last basis vector is never read: only its norm is formed
-                }
-                Wm[j + 1] = &sp.VA[j + 1];
-                W[j + 1] = sp.VA[j + 1].template as<float>();
-                FDD_CALL(fdd_gmres_step_dev(st, slot, j, iter, max_iterations, tolerance, use_relative ? 1 : 0, stream));
-            }
-            FDD_CALL(fdd_gmres_finish_dev(st, m, stream));
-
-            for (int i = 0; i < m; i++) ptrs[i] = pre ? sp.ZA[i].template as<float>() : W[i];
-            const double *scales = pre ? nullptr : inv_dev;
-            if (lazy)
-            {
-                const double *last_dev = nullptr;
-                FDD_CALL(fdd_gmres_last_column(st, &last_dev));
-                FDD_CALL(fdd_multi_lincomb_limited_dev_f32(sp.ua.template as<float>(), 1, y_dev, ptrs.data(), scales, last_dev, m, nd, stream));
-                history_pending = true;
-                iter = std::min(m, max_iterations);
-                break;
-            }
-
-            int nh = 0, j_last = -1, steps = 0, converged = 0;
-            FDD_CALL(fdd_gmres_fetch(st, nullptr, hist.data(), &nh, &j_last, &steps, &converged, stream));
-            if (first_cycle)
-            {
-                residual_history.push_back(hist[0]);
-                if (print_history) pstdout("- Iter %3d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", 0, hist[0], 1.0);
-            }
-            for (int k = 1; k < nh; k++)
-            {
-                residual_history.push_back(hist[k]);
-                if (print_history) pstdout("- Iter %3d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", iter + k, hist[k], hist[k] / residual_history[0]);
-            }
-            iter += steps;
-            if (j_last >= 0)
-                FDD_CALL(fdd_multi_lincomb_limited_dev_f32(sp.ua.template as<float>(), first_cycle ? 1 : 0, y_dev, ptrs.data(), scales, nullptr, j_last + 1, nd, stream));
-            else if (first_cycle)
-                FDD_CALL(fdd_amg_vector_set_to_value_f32(sp.ua.template as<float>(), 0.0f, nd, stream));
-            first_cycle = false;
-            if (converged) break;
+                subdomain_operator.Qt.gather(y, q, 0, nse, norm_weight_is_one ? nullptr : norm_weight.as<double>());
+            return;
         }
-        FDD_CALL(fdd_sub_copy_f64_f32(ua_out.as<double>(), sp.ua.template as<float>(), nd, stream)); // copy_to_domain_data, subdomain.okl:276-282
-        num_iterations += iter;
+        const int ns = subdomain_operator.num_dofs, nI = num_interface_dofs, n_reg = superdomain_operator.num_dofs - nI;
+        if (n_sup_copies > 0) fdd::ops::gather_indexed(x + num_dofs, x, copy_src.template as<int>(), n_sup_copies, stream);
+        if (n_slaves > 0) multiply(S_slave, sp.S, x + slave_base, x);
+        stiffness_from_dofs(q, x, scale_dev);
+        G_unit.gather(y, q, 0, nse);
+        if (n_slaves > 0)
+        {
+            Real *sl = (f32 ? sp.slaves : slave_vals).template as<Real>(), *st = (f32 ? sp.st_tmp : st_tmp).template as<Real>();
+            G_unit.gather(sl - nse, q, nse, nse + n_slaves);
+            multiply(St_slave, sp.St, st, sl);
+            fdd::ops::scatter_add_indexed(y, st_rows.template as<int>(), st, St_slave.num_rows, stream);
+        }
+        if (n_reg > 0)
+        {
+            multiply(A_sup_reg, sp.Asup, y + ns, x + (ns - nI));
+            if (scale_dev) fdd::ops::scaling_dev(y + ns, scale_dev, y + ns, n_reg, stream);
+        }
     }
 
   public:
@@ -1182,6 +1061,7 @@ class Subdomain
     // entries follow the Domain's node order)
     void gmres_composite_dofs(fdd::memory &ua_out, fdd::memory &r_pts, bool print_history = true, bool use_relative = false, const double *own_assembled = nullptr)
     {
+        fdd::memory &fa = krylov64.fa;
         if (not fa.ptr()) fa = fdd::dev().malloc<DType>(std::max(dof_alloc_size(), 1));
         tree_operator(f, r_pts);
         composite_rhs_dofs(fa, f, own_assembled);
@@ -1743,7 +1623,6 @@ class Subdomain
             ll.level = 0;
             ll.poly_degree = poly_degree[0];
             ll.num_elements = domain.num_local_elements;
-            ll.contiguous = true;
             ll.first_offset = 0;
             for (int g = 0; g < NUM_GEOM_FACTS; g++) ll.G[g] = subdomain_operator.G_ptrs[g];
             subdomain_operator.level_lists.push_back(ll);
@@ -2052,55 +1931,26 @@ class Subdomain
             {
                 const double n3 = (double)(ll.poly_degree + 1) * (ll.poly_degree + 1) * (ll.poly_degree + 1);
                 fdd::ProfileScope prof("mfma_stiffness_kernel", 64.0 * n3 * ll.num_elements);
-                if (ll.contiguous)
-                {
-                    const double *Gs[NUM_GEOM_FACTS];
-                    for (int g = 0; g < NUM_GEOM_FACTS; g++) Gs[g] = ll.G[g];
-                    FDD_CALL(fdd_stiffness_matrix_mfma(Au_sub_l.as<double>() + ll.first_offset, u_sub_l.as<double>() + ll.first_offset, subdomain_operator.D_hat[ll.level].template as<double>(), Gs, nullptr, ll.num_elements, ll.poly_degree, fdd::dev().stream));
-                }
-                else
-                {
-                    FDD_CALL(fdd_stiffness_matrix_mfma(Au_sub_l.as<double>(), u_sub_l.as<double>(), subdomain_operator.D_hat[ll.level].template as<double>(), subdomain_operator.G_ptrs, ll.elem_offset.template as<int>(), ll.num_elements, ll.poly_degree, fdd::dev().stream));
-                }
+                FDD_CALL(fdd_stiffness_matrix_mfma(Au_sub_l.as<double>() + ll.first_offset, u_sub_l.as<double>() + ll.first_offset, subdomain_operator.D_hat[ll.level].template as<double>(), ll.G, nullptr, ll.num_elements, ll.poly_degree, fdd::dev().stream));
             }
             else if (dim == 3 and ll.poly_degree <= 15)
             {
                 const double n3 = (double)(ll.poly_degree + 1) * (ll.poly_degree + 1) * (ll.poly_degree + 1);
                 fdd::ProfileScope prof("fused_stiffness_kernel", 64.0 * n3 * ll.num_elements);
-                if (ll.contiguous)
-                {
-                    const double *Gs[NUM_GEOM_FACTS];
-                    for (int g = 0; g < NUM_GEOM_FACTS; g++) Gs[g] = ll.G[g];
-                    FDD_CALL(fdd_sub_stiffness_matrix(Au_sub_l.as<double>() + ll.first_offset, u_sub_l.as<double>() + ll.first_offset, subdomain_operator.D_hat[ll.level].template as<double>(), Gs, nullptr, ll.num_elements, ll.poly_degree, fdd::dev().stream));
-                }
-                else
-                {
-                    FDD_CALL(fdd_sub_stiffness_matrix(Au_sub_l.as<double>(), u_sub_l.as<double>(), subdomain_operator.D_hat[ll.level].template as<double>(), subdomain_operator.G_ptrs, ll.elem_offset.template as<int>(), ll.num_elements, ll.poly_degree, fdd::dev().stream));
-                }
+                FDD_CALL(fdd_sub_stiffness_matrix(Au_sub_l.as<double>() + ll.first_offset, u_sub_l.as<double>() + ll.first_offset, subdomain_operator.D_hat[ll.level].template as<double>(), ll.G, nullptr, ll.num_elements, ll.poly_degree, fdd::dev().stream));
             }
             else if (dim == 2 and ll.poly_degree <= 15)
             {
                 const double n2 = (double)(ll.poly_degree + 1) * (ll.poly_degree + 1);
                 fdd::ProfileScope prof("fused_stiffness_2d_kernel", 40.0 * n2 * ll.num_elements);
-                if (ll.contiguous)
-                {
-                    const double *Gs[NUM_GEOM_FACTS];
-                    for (int g = 0; g < NUM_GEOM_FACTS; g++) Gs[g] = ll.G[g];
-                    FDD_CALL(fdd_stiffness_matrix_2d(Au_sub_l.as<double>() + ll.first_offset, u_sub_l.as<double>() + ll.first_offset, subdomain_operator.D_hat[ll.level].template as<double>(), Gs, nullptr, ll.num_elements, ll.poly_degree, fdd::dev().stream));
-                }
-                else
-                {
-                    FDD_CALL(fdd_stiffness_matrix_2d(Au_sub_l.as<double>(), u_sub_l.as<double>(), subdomain_operator.D_hat[ll.level].template as<double>(), subdomain_operator.G_ptrs, ll.elem_offset.template as<int>(), ll.num_elements, ll.poly_degree, fdd::dev().stream));
-                }
+                FDD_CALL(fdd_stiffness_matrix_2d(Au_sub_l.as<double>() + ll.first_offset, u_sub_l.as<double>() + ll.first_offset, subdomain_operator.D_hat[ll.level].template as<double>(), ll.G, nullptr, ll.num_elements, ll.poly_degree, fdd::dev().stream));
             }
             else
             {
-                // degree above 15: reference two-launch form on the contiguous list
+                // degree above 15: reference two-launch form on the list
                 const int npts = ll.num_elements * (int)std::lround(std::pow(ll.poly_degree + 1, dim));
                 double *GDu[3] = {work_dev[0].as<double>(), work_dev[1].as<double>(), work_dev[2].as<double>()};
-                const double *Gs[NUM_GEOM_FACTS];
-                for (int g = 0; g < NUM_GEOM_FACTS; g++) Gs[g] = ll.G[g];
-                FDD_CALL(fdd_dom_stiffness_matrix_1(GDu, u_sub_l.as<double>() + ll.first_offset, subdomain_operator.D_hat[ll.level].template as<double>(), Gs, npts, ll.poly_degree, dim, fdd::dev().stream));
+                FDD_CALL(fdd_dom_stiffness_matrix_1(GDu, u_sub_l.as<double>() + ll.first_offset, subdomain_operator.D_hat[ll.level].template as<double>(), ll.G, npts, ll.poly_degree, dim, fdd::dev().stream));
                 FDD_CALL(fdd_dom_stiffness_matrix_2(Au_sub_l.as<double>() + ll.first_offset, GDu, subdomain_operator.D_hat[ll.level].template as<double>(), npts, ll.poly_degree, dim, fdd::dev().stream));
             }
         }
@@ -2237,14 +2087,9 @@ class Subdomain
     {
         const int nd = subdomain_operator.num_extended_dofs;
         if ((int)Z.size() != num_vectors) allocate_krylov();
-        if ((int)VA.size() != num_vectors + 1)
-        {
-            for (auto &m : VA) m.free();
-            VA.resize(num_vectors + 1);
-            for (auto &m : VA) m = fdd::dev().malloc<DType>(std::max(nd, 1));
-            qa.free();
-            qa = fdd::dev().malloc<DType>(std::max(nd, 1));
-        }
+        krylov64.ensure(num_vectors, std::max(nd, 1), false);
+        std::vector<fdd::memory> &VA = krylov64.VA;
+        fdd::memory &qa = krylov64.qa;
         residual_history.clear();
         history_pending = false; // a lazy solve before this one (pcg_steps) may have left its history on the device: it is not this solve's
 
@@ -2427,14 +2272,7 @@ class Subdomain
                 ll.affine_w.copyFrom(w.data(), (size_t)n * sizeof(double));
                 ll.affine_c = fdd::dev().malloc<double>((size_t)ll.num_elements * NUM_GEOM_FACTS);
                 fdd::memory dev_dev = fdd::dev().malloc<double>(ll.num_elements);
-                if (ll.contiguous)
-                {
-                    const double *Gs[NUM_GEOM_FACTS];
-                    for (int g = 0; g < NUM_GEOM_FACTS; g++) Gs[g] = ll.G[g];
-                    FDD_CALL(fdd_stiffness_affine_detect(ll.affine_c.template as<double>(), dev_dev.template as<double>(), Gs, nullptr, ll.affine_w.template as<double>(), ll.num_elements, ll.poly_degree, fdd::dev().stream));
-                }
-                else
-                    FDD_CALL(fdd_stiffness_affine_detect(ll.affine_c.template as<double>(), dev_dev.template as<double>(), subdomain_operator.G_ptrs, ll.elem_offset.template as<int>(), ll.affine_w.template as<double>(), ll.num_elements, ll.poly_degree, fdd::dev().stream));
+                FDD_CALL(fdd_stiffness_affine_detect(ll.affine_c.template as<double>(), dev_dev.template as<double>(), ll.G, nullptr, ll.affine_w.template as<double>(), ll.num_elements, ll.poly_degree, fdd::dev().stream));
                 dev_dev.copyTo(dev_hst.data(), dev_hst.size() * sizeof(double));
                 dev_dev.free();
                 ll.affine_deviation = 0.0;
@@ -2453,58 +2291,10 @@ class Subdomain
     }
     static constexpr double PType_affine_tolerance() { return 64.0 * 2.220446049250313e-16; }
 
-    // q (points) = A_local (Q (s z~)), s = *scale_dev when given (a basis vector kept unnormalised)
-    void stiffness_from_dofs(fdd::memory &q, fdd::memory &za, const double *scale_dev = nullptr)
-    {
-        for (auto &ll : subdomain_operator.level_lists)
-        {
-            const double n3 = (double)(ll.poly_degree + 1) * (ll.poly_degree + 1) * (ll.poly_degree + 1);
-            if (ll.affine and ll.poly_degree >= 11 and mfma_stiffness)
-            {
-                fdd::ProfileScope prof("mfma_stiffness_kernel<gather,affine>", (12.0 * n3) * ll.num_elements + 8.0 * subdomain_operator.num_extended_dofs);
-                if (ll.contiguous)
-                    FDD_CALL(fdd_stiffness_matrix_mfma_affine(q.as<double>() + ll.first_offset, za.as<double>(), scale_dev, point_dof_dev.template as<int>() + ll.first_offset, subdomain_operator.D_hat[ll.level].template as<double>(), ll.affine_c.template as<double>(), ll.affine_w.template as<double>(), nullptr, ll.num_elements, ll.poly_degree, fdd::dev().stream));
-                else
-                    FDD_CALL(fdd_stiffness_matrix_mfma_affine(q.as<double>(), za.as<double>(), scale_dev, point_dof_dev.template as<int>(), subdomain_operator.D_hat[ll.level].template as<double>(), ll.affine_c.template as<double>(), ll.affine_w.template as<double>(), ll.elem_offset.template as<int>(), ll.num_elements, ll.poly_degree, fdd::dev().stream));
-                continue;
-            }
-            if (ll.affine)
-            {
-                fdd::ProfileScope prof("fused_stiffness_kernel<gather,affine>", (12.0 * n3) * ll.num_elements + 8.0 * subdomain_operator.num_extended_dofs);
-                if (ll.contiguous)
-                    FDD_CALL(fdd_stiffness_matrix_affine(q.as<double>() + ll.first_offset, za.as<double>(), scale_dev, point_dof_dev.template as<int>() + ll.first_offset, subdomain_operator.D_hat[ll.level].template as<double>(), ll.affine_c.template as<double>(), ll.affine_w.template as<double>(), nullptr, ll.num_elements, ll.poly_degree, fdd::dev().stream));
-                else
-                    FDD_CALL(fdd_stiffness_matrix_affine(q.as<double>(), za.as<double>(), scale_dev, point_dof_dev.template as<int>(), subdomain_operator.D_hat[ll.level].template as<double>(), ll.affine_c.template as<double>(), ll.affine_w.template as<double>(), ll.elem_offset.template as<int>(), ll.num_elements, ll.poly_degree, fdd::dev().stream));
-                continue;
-            }
-            if (ll.poly_degree >= 11 and mfma_stiffness)
-            {
-                fdd::ProfileScope prof("mfma_stiffness_kernel<gather>", (60.0 * n3) * ll.num_elements + 8.0 * subdomain_operator.num_extended_dofs);
-                if (ll.contiguous)
-                {
-                    const double *Gs[NUM_GEOM_FACTS];
-                    for (int g = 0; g < NUM_GEOM_FACTS; g++) Gs[g] = ll.G[g];
-                    FDD_CALL(fdd_stiffness_matrix_mfma_gather(q.as<double>() + ll.first_offset, za.as<double>(), scale_dev, point_dof_dev.template as<int>() + ll.first_offset, subdomain_operator.D_hat[ll.level].template as<double>(), Gs, nullptr, ll.num_elements, ll.poly_degree, fdd::dev().stream));
-                }
-                else
-                    FDD_CALL(fdd_stiffness_matrix_mfma_gather(q.as<double>(), za.as<double>(), scale_dev, point_dof_dev.template as<int>(), subdomain_operator.D_hat[ll.level].template as<double>(), subdomain_operator.G_ptrs, ll.elem_offset.template as<int>(), ll.num_elements, ll.poly_degree, fdd::dev().stream));
-                continue;
-            }
-            fdd::ProfileScope prof("fused_stiffness_kernel<gather>", (60.0 * n3) * ll.num_elements + 8.0 * subdomain_operator.num_extended_dofs);
-            if (ll.contiguous)
-            {
-                const double *Gs[NUM_GEOM_FACTS];
-                for (int g = 0; g < NUM_GEOM_FACTS; g++) Gs[g] = ll.G[g];
-                FDD_CALL(fdd_sub_stiffness_matrix_gather_scaled(q.as<double>() + ll.first_offset, za.as<double>(), scale_dev, point_dof_dev.template as<int>() + ll.first_offset, subdomain_operator.D_hat[ll.level].template as<double>(), Gs, nullptr, ll.num_elements, ll.poly_degree, fdd::dev().stream));
-            }
-            else
-                FDD_CALL(fdd_sub_stiffness_matrix_gather_scaled(q.as<double>(), za.as<double>(), scale_dev, point_dof_dev.template as<int>(), subdomain_operator.D_hat[ll.level].template as<double>(), subdomain_operator.G_ptrs, ll.elem_offset.template as<int>(), ll.num_elements, ll.poly_degree, fdd::dev().stream));
-        }
-    }
-
     void gmres_assembled(fdd::memory &u_l, fdd::memory &f_l, bool print_history, bool use_relative)
     {
         const int nd = std::max(dof_alloc_size(), 1);
+        fdd::memory &ua = krylov64.ua, &fa = krylov64.fa;
         if (not ua.ptr()) ua = fdd::dev().malloc<DType>(nd);
         if (not fa.ptr()) fa = fdd::dev().malloc<DType>(nd);
         if (is_composite)
@@ -2539,128 +2329,130 @@ class Subdomain
     void gmres_dofs_device(fdd::memory &ua, fdd::memory &fa, bool print_history, bool use_relative)
     {
         if (precision == 32)
-        {
-            gmres_dofs_device_f32(ua, fa, print_history, use_relative);
-            return;
-        }
-        if (use_preconditioner and amg_hierarchy.f32_io) amg_hierarchy.set_f32_io(false);
+            gmres_dofs_device_t(krylov32, ua, fa, print_history, use_relative);
+        else
+            gmres_dofs_device_t(krylov64, ua, fa, print_history, use_relative);
+    }
+
+    // Real = float is the reference's PTYPE = Float: the same recurrences and the same device bookkeeping on float vectors
+    // (prepare_single_precision), with the casts of subdomain.okl:268-282 at the two ends; ua_io / fa_io are double either way.
+    template <typename Real>
+    void gmres_dofs_device_t(DofKrylov<Real> &K, fdd::memory &ua_io, fdd::memory &fa_io, bool print_history, bool use_relative)
+    {
+        constexpr bool f32 = std::is_same<Real, float>::value;
+        namespace ops = fdd::ops;
         const int nd = dof_space_size();         // the unique dofs the iteration runs on
         const int na = std::max(dof_alloc_size(), 1); // composite: room for the copies / hanging values behind them
         const int m = num_vectors;
         void *stream = fdd::dev().stream;
-        if ((int)VA.size() != m + 1)
-        {
-            for (auto &v : VA) v.free();
-            VA.resize(m + 1);
-            for (auto &v : VA) v = fdd::dev().malloc<DType>(na);
-            qa.free();
-            qa = fdd::dev().malloc<DType>(na);
-        }
+        if constexpr (f32) prepare_single_precision();
         const bool jacobi = use_jacobi and not use_preconditioner;
         const bool pre = use_preconditioner or jacobi; // the preconditioned basis Z is kept
         if (jacobi) ensure_jacobi();
-        if (pre and (int)ZA.size() != m)
+        K.ensure(m, na, pre);
+        if constexpr (f32)
         {
-            for (auto &v : ZA) v.free();
-            ZA.resize(m);
-            for (auto &v : ZA) v = fdd::dev().malloc<DType>(na);
+            if (not K.ua.ptr()) K.ua = fdd::dev().malloc<float>(na);
+            if (not K.fa.ptr()) K.fa = fdd::dev().malloc<float>(na);
+            FDD_CALL(fdd_sub_copy_f32_f64(K.fa.template as<float>(), fa_io.as<double>(), nd, stream)); // copy_from_domain_data, subdomain.okl:268-274
         }
+        Real *ua = (f32 ? K.ua : ua_io).template as<Real>(), *fa = (f32 ? K.fa : fa_io).template as<Real>(), *qa = K.qa.template as<Real>();
         if (not gmres_state.ptr()) gmres_state = fdd::dev().malloc<char>(fdd_gmres_state_bytes());
         residual_history.clear();
         double *sc = scalars.as<double>();
         double *ws = reduce_ws.as<double>();
-        const double *nw = (norm_weight_is_one or is_composite) ? nullptr : norm_weight.as<double>(); // NULL: unit weights, not read (the composite iterates on its unique dofs: all weights 1)
+        // NULL: unit weights, not read (the composite iterates on its unique dofs: all weights 1; the float reductions take none)
+        const double *nw = (f32 or norm_weight_is_one or is_composite) ? nullptr : norm_weight.as<double>();
         void *st = gmres_state.ptr();
         const double *y_dev = nullptr, *inv_dev = nullptr;
         FDD_CALL(fdd_gmres_coefficients(st, &y_dev));
         FDD_CALL(fdd_gmres_scales(st, &inv_dev));
 
+        // the float solve runs the float V-cycle and gives and takes float vectors (f32_io); the double one gives and
+        // takes double vectors whatever the cycle's own precision
+        if (use_preconditioner)
+        {
+            if constexpr (f32)
+            {
+                amg_checked();
+                if (amg_hierarchy.precision != 32 and not amg_hierarchy.set_precision(32))
+                {
+                    fprintf(stderr, "ERROR: the single-precision preconditioner needs a Chebyshev order of at least 2\n");
+                    exit(EXIT_FAILURE);
+                }
+                amg_hierarchy.set_f32_io(true);
+            }
+            else if (amg_hierarchy.f32_io)
+                amg_hierarchy.set_f32_io(false);
+        }
+
         // The basis is kept UNNORMALISED: W_j = r (j = 0) or the orthogonalised q (j > 0), with
         // inv[j] = 1/gamma_0 or 1/||q|| in the device state.  Every reader forms inv[j] * W_j[d] on load
         // -- the value vector_scaling would have stored (subdomain.tpp:4358, 4457), bit for bit -- so the
         // normalisation pass per step disappears.
-        auto dot_dofs = [&](double *out_dev, fdd::memory &a, const double *const *b, const double *b_scale, int count) {
-            fdd::ProfileScope prof("reduce_vec2_kernel<MultiDotW>", 8.0 * nd * (count + 1 + (nw ? 1 : 0)));
-            FDD_CALL(fdd_multi_weighted_inner_product_scaled(out_dev, ws, a.as<double>(), b, b_scale, count, nw, nd, stream));
-        };
-
         // u~ starts at 0 (subdomain.tpp:4270-4275); the first update writes it without reading it
         int iter = 0;
         bool first_cycle = true;
         history_pending = false;
         const bool lazy = lazy_history and max_iterations <= m and fdd::globals().pstdout_file == nullptr;
-        std::vector<const double *> W(m + 1), ptrs(m + 1);
-        std::vector<fdd::memory *> Wm(m + 1);
+        std::vector<Real *> W(m + 1), ptrs(m + 1);
         std::vector<double> hist(FDD_MULTI_MAX + 1);
 
         while (iter < max_iterations)
         {
             if (first_cycle)
-            {
-                Wm[0] = &fa; // read only
-            }
+                W[0] = fa; // read only
             else
             {
                 // r~ = f~ - Qt A Q u~
                 operator_dofs(qa, ua);
-                FDD_CALL(fdd_vector_vector_addition(VA[0].template as<double>(), 1.0, fa.as<double>(), -1.0, qa.as<double>(), nd, stream));
-                Wm[0] = &VA[0];
+                W[0] = K.VA[0].template as<Real>();
+                ops::vector_vector_addition(W[0], 1, fa, -1, qa, nd, stream);
             }
-            W[0] = Wm[0]->template as<double>();
-            if (first_cycle and known_rhs_norm2_dev and nw == nullptr)
+            if (not f32 and first_cycle and known_rhs_norm2_dev and nw == nullptr)
                 FDD_CALL(fdd_gmres_begin_dev(st, known_rhs_norm2_dev, 1, stream)); // the caller has just formed |f~|^2 with this very call (Domain::node_norm_enqueue)
             else
             {
-                const double *self[1] = {W[0]};
-                dot_dofs(sc, *Wm[0], self, nullptr, 1);
+                ops::multi_dot(sc, ws, W[0], W.data(), nullptr, 1, nw, nd, stream);
                 FDD_CALL(fdd_gmres_begin_dev(st, sc, first_cycle ? 1 : 0, stream));
             }
 
             for (int j = 0; j < m; j++)
             {
+                Real *za = pre ? K.ZA[j].template as<Real>() : W[j];
                 if (use_preconditioner)
                 {
                     // z~_j = V(inv_j W_j): the V-cycle wants the normalised vector in its own buffer anyway
-                    amg::Level &fine = amg_checked();
-                    FDD_CALL(fdd_vector_scaling_dev(fine.f.as<double>(), inv_dev + j, W[j], nd, stream));
-                    amg_hierarchy.vcycle_into(ZA[j]); // the correction lands in the preconditioned basis vector itself
-                    operator_dofs(qa, ZA[j]);
+                    Real *rhs;
+                    if constexpr (f32)
+                        rhs = amg_hierarchy.rhs32().template as<float>();
+                    else
+                        rhs = amg_checked().f.template as<double>();
+                    ops::scaling_dev(rhs, inv_dev + j, W[j], nd, stream);
+                    amg_hierarchy.vcycle_into(K.ZA[j]); // the correction lands in the preconditioned basis vector itself
                 }
-                else if (jacobi)
-                {
-                    // z~_j = D^-1 (inv_j W_j)
-                    FDD_CALL(fdd_vector_diagonal_scaling_dev(ZA[j].template as<double>(), jacobi_dinv.as<double>(), inv_dev + j, W[j], nd, stream));
-                    operator_dofs(qa, ZA[j]);
-                }
-                else
-                    operator_dofs(qa, *Wm[j], inv_dev + j);
+                else if (jacobi) // z~_j = D^-1 (inv_j W_j)
+                    ops::diagonal_scaling_dev(za, (f32 ? jacobi_dinv_f32 : jacobi_dinv).template as<Real>(), inv_dev + j, W[j], nd, stream);
+                operator_dofs(qa, za, pre ? nullptr : inv_dev + j);
 
                 double *slot = sc + (j & 1) * FDD_GMRES_SLOT;
-                dot_dofs(slot, qa, W.data(), inv_dev, j + 1);
-                {
-                    fdd::ProfileScope prof("reduce_vec2_kernel<MultiAxpyNorm>", 8.0 * nd * (j + 3 + (nw ? 1 : 0)));
-                    FDD_CALL(fdd_multi_axpy_norm2_scaled_dev(slot + (j + 1), ws, (j + 1 < m or not skip_last_basis_store) ? VA[j + 1].template as<double>() : nullptr, qa.as<double>(), slot, -1.0, W.data(), inv_dev, j + 1, nw, nd, stream)); // the cycle's last basis vector is never read: only its norm is formed
-                }
-                Wm[j + 1] = &VA[j + 1];
-                W[j + 1] = VA[j + 1].template as<double>();
+                W[j + 1] = K.VA[j + 1].template as<Real>();
+                ops::multi_dot(slot, ws, qa, W.data(), inv_dev, j + 1, nw, nd, stream);
+                // the cycle's last basis vector is never read: only its norm is formed
+                ops::multi_axpy_norm2(slot + (j + 1), ws, (j + 1 < m or not skip_last_basis_store) ? W[j + 1] : nullptr, qa, slot, -1.0, W.data(), inv_dev, j + 1, nw, nd, stream);
                 FDD_CALL(fdd_gmres_step_dev(st, slot, j, iter, max_iterations, tolerance, use_relative ? 1 : 0, stream));
             }
             FDD_CALL(fdd_gmres_finish_dev(st, m, stream));
 
+            for (int i = 0; i < m; i++) ptrs[i] = pre ? K.ZA[i].template as<Real>() : W[i];
+            const double *scales = pre ? nullptr : inv_dev;
             if (lazy)
             {
                 // single cycle, nobody is waiting for the history: the update takes its column count from the
                 // device state and the host does not synchronise at all (finish_history() reads the state later)
                 const double *last_dev = nullptr;
                 FDD_CALL(fdd_gmres_last_column(st, &last_dev));
-                fdd::ProfileScope prof("ew_vec2_kernel<MultiAxpy>", 8.0 * nd * (m + 2));
-                if (pre)
-                {
-                    for (int i = 0; i < m; i++) ptrs[i] = ZA[i].template as<double>();
-                    FDD_CALL(fdd_multi_lincomb_limited_dev(ua.as<double>(), 1, y_dev, ptrs.data(), nullptr, last_dev, m, nd, stream));
-                }
-                else
-                    FDD_CALL(fdd_multi_lincomb_limited_dev(ua.as<double>(), 1, y_dev, W.data(), inv_dev, last_dev, m, nd, stream));
+                ops::lincomb_limited(ua, 1, y_dev, ptrs.data(), scales, last_dev, m, nd, stream);
                 history_pending = true;
                 iter = std::min(m, max_iterations); // the steps enqueued; an early stop is only known to the device
                 break;
@@ -2682,21 +2474,13 @@ class Subdomain
             iter += steps;
 
             if (j_last >= 0)
-            {
-                fdd::ProfileScope prof("ew_vec2_kernel<MultiAxpy>", 8.0 * nd * (j_last + (first_cycle ? 2 : 3)));
-                if (pre)
-                {
-                    for (int i = 0; i < j_last + 1; i++) ptrs[i] = ZA[i].template as<double>();
-                    FDD_CALL(fdd_multi_lincomb_scaled_dev(ua.as<double>(), first_cycle ? 1 : 0, y_dev, ptrs.data(), nullptr, j_last + 1, nd, stream));
-                }
-                else
-                    FDD_CALL(fdd_multi_lincomb_scaled_dev(ua.as<double>(), first_cycle ? 1 : 0, y_dev, W.data(), inv_dev, j_last + 1, nd, stream));
-            }
+                ops::lincomb(ua, first_cycle ? 1 : 0, y_dev, ptrs.data(), scales, j_last + 1, nd, stream);
             else if (first_cycle)
-                FDD_CALL(fdd_set_to_value(ua.as<double>(), 0.0, nd, 0, stream));
+                ops::set_to_zero(ua, nd, stream);
             first_cycle = false;
             if (converged) break;
         }
+        if constexpr (f32) FDD_CALL(fdd_sub_copy_f64_f32(ua_io.as<double>(), ua, nd, stream)); // copy_to_domain_data, subdomain.okl:276-282
         num_iterations += iter;
     }
 
@@ -2711,23 +2495,12 @@ class Subdomain
         const int nd = subdomain_operator.num_extended_dofs;
         const int m = num_vectors;
         void *stream = fdd::dev().stream;
-        if ((int)VA.size() != m + 1)
-        {
-            for (auto &v : VA) v.free();
-            VA.resize(m + 1);
-            for (auto &v : VA) v = fdd::dev().malloc<DType>(std::max(nd, 1));
-            qa.free();
-            qa = fdd::dev().malloc<DType>(std::max(nd, 1));
-        }
         const bool jacobi = use_jacobi and not use_preconditioner;
         const bool pre = use_preconditioner or jacobi;
         if (jacobi) ensure_jacobi();
-        if (pre and (int)ZA.size() != m)
-        {
-            for (auto &v : ZA) v.free();
-            ZA.resize(m);
-            for (auto &v : ZA) v = fdd::dev().malloc<DType>(std::max(nd, 1));
-        }
+        krylov64.ensure(m, std::max(nd, 1), pre);
+        std::vector<fdd::memory> &VA = krylov64.VA, &ZA = krylov64.ZA;
+        fdd::memory &qa = krylov64.qa;
         if ((int)H.size() != m) allocate_krylov_scalars();
         residual_history.clear();
         history_pending = false; // a lazy solve before this one (pcg_steps) may have left its history on the device: it is not this solve's
@@ -2765,7 +2538,7 @@ class Subdomain
             if (iter > 0)
             {
                 // r~ = f~ - Qt A Q u~
-                stiffness_from_dofs(q_k, ua);
+                stiffness_from_dofs(q_k.as<double>(), ua.as<double>());
                 gather_weighted(qa, q_k);
                 FDD_CALL(fdd_vector_vector_addition(qa.as<double>(), 1.0, fa.as<double>(), -1.0, qa.as<double>(), nd, stream));
                 const double *self[1] = {qa.as<double>()};
@@ -2802,7 +2575,7 @@ class Subdomain
                     za = &ZA[j];
                 }
 
-                stiffness_from_dofs(q_k, *za);
+                stiffness_from_dofs(q_k.as<double>(), za->template as<double>());
                 gather_weighted(qa, q_k);
 
                 // H[0..j][j] = <q~, v~_i>, q~ -= sum H v~_i, ||q~||^2: coefficients never leave the device in between
@@ -3079,7 +2852,7 @@ class Subdomain
         fdd::memory xa = fdd::dev().malloc<DType>(na), ya = fdd::dev().malloc<DType>(na);
         FDD_CALL(fdd_set_to_value(xa.as<double>(), 0.0, na, 0, fdd::dev().stream));
         xa.copyFrom(x, (size_t)nd * sizeof(DType));
-        operator_dofs(ya, xa);
+        operator_dofs(ya.as<double>(), xa.as<double>());
         ya.copyTo(y, (size_t)nd * sizeof(DType));
         xa.free();
         ya.free();
