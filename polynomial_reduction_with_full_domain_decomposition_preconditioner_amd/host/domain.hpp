@@ -32,6 +32,7 @@
 #include "csr_matrix.hpp"
 #include "element.hpp"
 #include "gll.hpp"
+#include "gmres.hpp"
 #include "math.hpp"
 #include "timer.hpp"
 
@@ -109,11 +110,7 @@ class Domain
     std::vector<fdd::memory> Z;
     std::vector<fdd::memory> VA; // assembled copies of the outer GMRES basis
     int va_valid = 0;            // VA[0..va_valid) match V of the current cycle
-    std::vector<std::vector<DType>> H;
-    std::vector<DType> c_gmres;
-    std::vector<DType> s_gmres;
-    std::vector<DType> gamma;
-    bool gmres_allocated = false;
+    fdd::GmresScalars<DType> gmres_scalars; // H, rotations, gamma of the outer GMRES: sized per solve, shared by the point-space and the node-space form
     int gmres_point_vectors = 0; // num_vectors the point-space basis V, Z was allocated for
 
     // state of a running flexible CG (fcg_begin / fcg_step)
@@ -372,12 +369,10 @@ class Domain
         va_valid = std::max(va_valid, upto + 1);
     }
 
-    // The basis follows num_vectors, which fddh_problem_set_options may change between two solves; the Hessenberg matrix
-    // and the rotations are shared with gmres_nodes and sized by whichever path ran last (gmres_host_arrays).
+    // The basis follows num_vectors, which fddh_problem_set_options may change between two solves.
     void allocate_gmres()
     {
-        gmres_host_arrays(num_vectors);
-        if (gmres_allocated and gmres_point_vectors == num_vectors) return;
+        if (gmres_point_vectors == num_vectors) return;
         for (auto *set : {&V, &Z})
         {
             for (auto &v : *set) v.free();
@@ -389,18 +384,35 @@ class Domain
         for (int i = 0; i < num_vectors; i++) Z[i] = fdd::dev().malloc<DType>(num_local_points);
         va_valid = 0;
         gmres_point_vectors = num_vectors;
-        gmres_allocated = true;
     }
 
-    // H, c, s, gamma of GMRES(m): one set for the point-space and the node-space solve, re-made whenever the other path
-    // (or another num_vectors) left them at a different size
-    void gmres_host_arrays(int m)
+    // The outer iteration is the reference's Domain loop: gmres.hpp says what the two switches stand for.
+    fdd::GmresControl<DType> outer_gmres_control(bool use_relative) const { return {max_iterations, tolerance, use_relative, /* count_at_step_start */ false, /* stop_on_nan */ true}; }
+    static void print_outer_step(int step, DType r_norm, DType relative) { rstdout("Iter %2d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", step, r_norm, relative); }
+
+    // H[i][col] = sum q * b[i] * mask for i < count: q is read once per group of FDD_MULTI_MAX vectors
+    void grouped_inner_products(std::vector<std::vector<DType>> &H, int col, fdd::memory &q, const double *const *b, int count, fdd::memory &mask, int n)
     {
-        if ((int)H.size() == m and (int)c_gmres.size() == m and (int)s_gmres.size() == m and (int)gamma.size() == m + 1) return;
-        H.assign(m, std::vector<DType>(m, 0.0));
-        c_gmres.assign(m, 0.0);
-        s_gmres.assign(m, 0.0);
-        gamma.assign(m + 1, 0.0);
+        double h[FDD_MULTI_MAX];
+        for (int g0 = 0; g0 < count; g0 += FDD_MULTI_MAX)
+        {
+            const int cnt = std::min(FDD_MULTI_MAX, count - g0);
+            FDD_CALL(fdd_multi_weighted_inner_product(scalars.as<double>(), reduce_ws.as<double>(), q.as<double>(), b + g0, cnt, mask.as<double>(), n, fdd::dev().stream));
+            fetch_scalars(h, cnt);
+            for (int i = 0; i < cnt; i++) H[g0 + i][col] = h[i];
+        }
+    }
+
+    // y += sum_{i < count} coeffs[i] * x[i], one pass over y per group of FDD_MULTI_MAX vectors
+    void grouped_axpy(fdd::memory &y, const DType *coeffs, std::vector<fdd::memory> &x, int count, int n)
+    {
+        for (int g0 = 0; g0 < count; g0 += FDD_MULTI_MAX)
+        {
+            const int cnt = std::min(FDD_MULTI_MAX, count - g0);
+            const double *ptrs[FDD_MULTI_MAX];
+            for (int i = 0; i < cnt; i++) ptrs[i] = x[g0 + i].template as<double>();
+            FDD_CALL(fdd_multi_axpy(y.as<double>(), coeffs + g0, ptrs, cnt, n, fdd::dev().stream));
+        }
     }
 
   public:
@@ -1542,7 +1554,6 @@ class Domain
             }
             gmres_nodes_vectors = m;
         }
-        gmres_host_arrays(m); // shared with the point-space solve, which may have run with another num_vectors since
         residual_history.clear();
 
         // the assembled copy <., .> reads: gs over the ranks on the interface prefix, nothing to do on one rank
@@ -1552,6 +1563,13 @@ class Domain
             gs_add_boundary(VNA[i]);
             return VNA[i];
         };
+        auto norm_of = [&](fdd::memory &v) {
+            DType norm;
+            fdd_timer().start("domain.residual_norm");
+            node_norm(norm, v);
+            fdd_timer().stop("domain.residual_norm");
+            return norm;
+        };
 
         fdd_timer().start("domain.vector_operations");
         gather_nodes(nf, f); // f^ = Qt f
@@ -1560,157 +1578,64 @@ class Domain
         if (points_too) VP[0].copyFrom(f, (size_t)num_local_points * sizeof(DType));
         fdd_timer().stop("domain.vector_operations");
 
-        DType r_norm, r_0_norm;
-        fdd_timer().start("domain.residual_norm");
-        node_norm(r_0_norm, nr);
-        fdd_timer().stop("domain.residual_norm");
-        residual_history.push_back(r_0_norm);
-        rstdout("Iter %2d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", 0, r_0_norm, 1.0);
-
-        bool converged = false;
-        int iter = 0, j;
-        DType alpha_j, beta_j, gamma_j, gamma_k;
-
-        while (iter < max_iterations)
-        {
-            if (iter > 0)
-            {
-                fdd_timer().start("domain.operator_application");
-                stiffness_from_nodes(q_k, nu);
-                gather_nodes(nq, q_k);
-                fdd_timer().stop("domain.operator_application");
-                fdd_timer().start("domain.vector_operations");
-                FDD_CALL(fdd_vector_vector_addition(nr.as<double>(), 1.0, nf.as<double>(), -1.0, nq.as<double>(), nn, stream));
-                if (points_too) FDD_CALL(fdd_vector_vector_addition(VP[0].as<double>(), 1.0, f.as<double>(), -1.0, q_k.as<double>(), num_local_points, stream));
-                fdd_timer().stop("domain.vector_operations");
-                fdd_timer().start("domain.residual_norm");
-                node_norm(r_norm, nr);
-                fdd_timer().stop("domain.residual_norm");
-                gamma[0] = r_norm;
-            }
-            else
-                gamma[0] = r_0_norm;
-
+        std::vector<const double *> va(m + 1, nullptr); // assembled basis of the current cycle
+        std::vector<DType> minus_h(m);
+        fdd::GmresSpace<DType> space;
+        space.initial_norm = [&] { return norm_of(nr); };
+        space.restart_norm = [&] {
+            fdd_timer().start("domain.operator_application");
+            stiffness_from_nodes(q_k, nu);
+            gather_nodes(nq, q_k);
+            fdd_timer().stop("domain.operator_application");
             fdd_timer().start("domain.vector_operations");
-            FDD_CALL(fdd_vector_scaling(VN[0].as<double>(), 1.0 / gamma[0], nr.as<double>(), nn, stream));
-            if (points_too) FDD_CALL(fdd_vector_scaling(VP[0].as<double>(), 1.0 / gamma[0], VP[0].as<double>(), num_local_points, stream));
+            FDD_CALL(fdd_vector_vector_addition(nr.as<double>(), 1.0, nf.as<double>(), -1.0, nq.as<double>(), nn, stream));
+            if (points_too) FDD_CALL(fdd_vector_vector_addition(VP[0].as<double>(), 1.0, f.as<double>(), -1.0, q_k.as<double>(), num_local_points, stream));
             fdd_timer().stop("domain.vector_operations");
-            std::vector<const double *> va(m + 1, nullptr); // assembled basis of this cycle
+            return norm_of(nr);
+        };
+        space.start_cycle = [&](DType gamma_0) {
+            fdd_timer().start("domain.vector_operations");
+            FDD_CALL(fdd_vector_scaling(VN[0].as<double>(), 1.0 / gamma_0, nr.as<double>(), nn, stream));
+            if (points_too) FDD_CALL(fdd_vector_scaling(VP[0].as<double>(), 1.0 / gamma_0, VP[0].as<double>(), num_local_points, stream));
+            fdd_timer().stop("domain.vector_operations");
             va[0] = assembled(0).template as<double>();
+        };
+        space.arnoldi_step = [&](int j, std::vector<std::vector<DType>> &H) {
+            if (points_too) rp.copyFrom(VP[j], (size_t)num_local_points * sizeof(DType)); // the tree restricts V_j on the points
+            precondition_nodes(ZN[j], VN[j], subdomain);
 
-            for (j = 0; j < m; j++)
-            {
-                if (points_too) rp.copyFrom(VP[j], (size_t)num_local_points * sizeof(DType)); // the tree restricts V_j on the points
-                precondition_nodes(ZN[j], VN[j], subdomain);
+            fdd_timer().start("domain.operator_application");
+            stiffness_from_nodes(q_k, ZN[j]);
+            gather_nodes(nq, q_k);
+            fdd_timer().stop("domain.operator_application");
 
-                fdd_timer().start("domain.operator_application");
-                stiffness_from_nodes(q_k, ZN[j]);
-                gather_nodes(nq, q_k);
-                fdd_timer().stop("domain.operator_application");
-
-                // classical Gram-Schmidt: every H[i][j] from the same q (domain.tpp:810-815), then the updates
-                fdd_timer().start("domain.inner_products");
-                std::vector<double> h(j + 1);
-                for (int g0 = 0; g0 < j + 1; g0 += FDD_MULTI_MAX)
-                {
-                    const int cnt = std::min(FDD_MULTI_MAX, j + 1 - g0);
-                    FDD_CALL(fdd_multi_weighted_inner_product(scalars.as<double>(), reduce_ws.as<double>(), nq.as<double>(), va.data() + g0, cnt, node_mask.as<double>(), nn, stream));
-                    fetch_scalars(h.data() + g0, cnt);
-                }
-                for (int i = 0; i < j + 1; i++) H[i][j] = h[i];
-                fdd_timer().stop("domain.inner_products");
-
-                fdd_timer().start("domain.vector_operations");
-                for (int g0 = 0; g0 < j + 1; g0 += FDD_MULTI_MAX)
-                {
-                    const int cnt = std::min(FDD_MULTI_MAX, j + 1 - g0);
-                    const double *ptrs[FDD_MULTI_MAX], *pptrs[FDD_MULTI_MAX];
-                    double coeffs[FDD_MULTI_MAX];
-                    for (int i = 0; i < cnt; i++)
-                    {
-                        ptrs[i] = VN[g0 + i].template as<double>();
-                        if (points_too) pptrs[i] = VP[g0 + i].template as<double>();
-                        coeffs[i] = -H[g0 + i][j];
-                    }
-                    FDD_CALL(fdd_multi_axpy(nq.as<double>(), coeffs, ptrs, cnt, nn, stream));
-                    if (points_too) FDD_CALL(fdd_multi_axpy(q_k.as<double>(), coeffs, pptrs, cnt, num_local_points, stream));
-                }
-                fdd_timer().stop("domain.vector_operations");
-
-                for (int i = 0; i < j; i++)
-                {
-                    DType h_ij = H[i][j];
-                    H[i][j] = c_gmres[i] * h_ij + s_gmres[i] * H[i + 1][j];
-                    H[i + 1][j] = -s_gmres[i] * h_ij + c_gmres[i] * H[i + 1][j];
-                }
-
-                fdd_timer().start("domain.residual_norm");
-                node_norm(alpha_j, nq);
-                fdd_timer().stop("domain.residual_norm");
-
-                if (std::abs(alpha_j) == 0.0)
-                {
-                    converged = true;
-                    break;
-                }
-
-                beta_j = std::sqrt(H[j][j] * H[j][j] + alpha_j * alpha_j);
-                gamma_j = 1.0 / beta_j;
-                c_gmres[j] = H[j][j] * gamma_j;
-                s_gmres[j] = alpha_j * gamma_j;
-                H[j][j] = beta_j;
-                gamma[j + 1] = -s_gmres[j] * gamma[j];
-                gamma[j] = c_gmres[j] * gamma[j];
-
-                r_norm = std::abs(gamma[j + 1]);
-                residual_history.push_back(r_norm);
-                rstdout("Iter %2d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", iter + 1, r_norm, r_norm / r_0_norm);
-
-                if (use_relative ? (r_norm / r_0_norm < tolerance) : (r_norm < tolerance))
-                {
-                    converged = true;
-                    break;
-                }
-                if (iter >= max_iterations or std::isnan(r_norm))
-                {
-                    converged = true;
-                    break;
-                }
-
-                fdd_timer().start("domain.vector_operations");
-                FDD_CALL(fdd_vector_scaling(VN[j + 1].as<double>(), 1.0 / alpha_j, nq.as<double>(), nn, stream));
-                if (points_too) FDD_CALL(fdd_vector_scaling(VP[j + 1].as<double>(), 1.0 / alpha_j, q_k.as<double>(), num_local_points, stream));
-                fdd_timer().stop("domain.vector_operations");
-                if (j + 1 < m) va[j + 1] = assembled(j + 1).template as<double>(); // the last vector of a cycle is never projected on
-
-                iter++;
-            }
-
-            if (j == m) j--;
-
-            // back substitution stored into c_gmres (domain.tpp:891-899)
-            for (int k = j; k >= 0; k--)
-            {
-                gamma_k = gamma[k];
-                for (int i = j; i > k; i--) gamma_k -= H[k][i] * c_gmres[i];
-                c_gmres[k] = gamma_k / H[k][k];
-            }
+            // classical Gram-Schmidt: every H[i][j] from the same q (domain.tpp:810-815), then the updates
+            fdd_timer().start("domain.inner_products");
+            grouped_inner_products(H, j, nq, va.data(), j + 1, node_mask, nn);
+            fdd_timer().stop("domain.inner_products");
 
             fdd_timer().start("domain.vector_operations");
-            for (int g0 = 0; g0 < j + 1; g0 += FDD_MULTI_MAX)
-            {
-                const int cnt = std::min(FDD_MULTI_MAX, j + 1 - g0);
-                const double *ptrs[FDD_MULTI_MAX];
-                for (int i = 0; i < cnt; i++) ptrs[i] = ZN[g0 + i].template as<double>();
-                FDD_CALL(fdd_multi_axpy(nu.as<double>(), c_gmres.data() + g0, ptrs, cnt, nn, stream));
-            }
+            for (int i = 0; i < j + 1; i++) minus_h[i] = -H[i][j];
+            grouped_axpy(nq, minus_h.data(), VN, j + 1, nn);
+            if (points_too) grouped_axpy(q_k, minus_h.data(), VP, j + 1, num_local_points);
             fdd_timer().stop("domain.vector_operations");
-
-            if (converged) break;
-        }
+            return norm_of(nq);
+        };
+        space.next_vector = [&](int j, DType alpha_j) {
+            fdd_timer().start("domain.vector_operations");
+            FDD_CALL(fdd_vector_scaling(VN[j + 1].as<double>(), 1.0 / alpha_j, nq.as<double>(), nn, stream));
+            if (points_too) FDD_CALL(fdd_vector_scaling(VP[j + 1].as<double>(), 1.0 / alpha_j, q_k.as<double>(), num_local_points, stream));
+            fdd_timer().stop("domain.vector_operations");
+            if (j + 1 < m) va[j + 1] = assembled(j + 1).template as<double>(); // the last vector of a cycle is never projected on
+        };
+        space.add_update = [&](int j, const std::vector<DType> &c) {
+            fdd_timer().start("domain.vector_operations");
+            grouped_axpy(nu, c.data(), ZN, j + 1, nn);
+            fdd_timer().stop("domain.vector_operations");
+        };
+        num_iterations = fdd::gmres_solve(gmres_scalars, m, outer_gmres_control(use_relative), space, residual_history, print_outer_step);
 
         Q.multiply(u, nu); // the solution back on the element-local points
-        num_iterations = iter;
     }
 
     // domain.tpp:727-914
@@ -1730,211 +1655,96 @@ class Domain
         FDD_CALL(fdd_dom_initialize_arrays(u_k.as<double>(), r_k.as<double>(), f.as<double>(), num_local_points, fdd::dev().stream));
         fdd_timer().stop("domain.vector_operations");
 
-        DType r_norm;
-        DType r_0_norm;
-
-        fdd_timer().start("domain.residual_norm");
-        residual_norm(r_0_norm, r_k);
-        fdd_timer().stop("domain.residual_norm");
-
-        residual_history.push_back(r_0_norm);
-        rstdout("Iter %2d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", 0, r_0_norm, 1.0);
-
-        bool converged = false;
-        int iter = 0;
-        int j;
-
-        DType alpha_j, beta_j, gamma_j, gamma_k;
-
-        while (iter < max_iterations)
-        {
-            if (iter > 0)
-            {
-                fdd_timer().start("domain.operator_application");
-                stiffness_matrix(r_k, u_k);
-                fdd_timer().stop("domain.operator_application");
-
-                fdd_timer().start("domain.vector_operations");
-                math.vector_vector_addition(r_k, 1.0, f, -1.0, r_k, num_local_points);
-                fdd_timer().stop("domain.vector_operations");
-
-                fdd_timer().start("domain.residual_norm");
-                residual_norm(r_norm, r_k);
-                fdd_timer().stop("domain.residual_norm");
-
-                gamma[0] = r_norm;
-            }
-            else
-            {
-                gamma[0] = r_0_norm;
-            }
+        auto norm_of = [&](fdd::memory &v) {
+            DType norm;
+            fdd_timer().start("domain.residual_norm");
+            residual_norm(norm, v);
+            fdd_timer().stop("domain.residual_norm");
+            return norm;
+        };
+        std::vector<const double *> va(num_vectors);
+        std::vector<DType> minus_h(num_vectors);
+        fdd::GmresSpace<DType> space;
+        space.initial_norm = [&] { return norm_of(r_k); };
+        space.restart_norm = [&] {
+            fdd_timer().start("domain.operator_application");
+            stiffness_matrix(r_k, u_k);
+            fdd_timer().stop("domain.operator_application");
 
             fdd_timer().start("domain.vector_operations");
-            math.vector_scaling(V[0], 1.0 / gamma[0], r_k, num_local_points);
+            math.vector_vector_addition(r_k, 1.0, f, -1.0, r_k, num_local_points);
+            fdd_timer().stop("domain.vector_operations");
+            return norm_of(r_k);
+        };
+        space.start_cycle = [&](DType gamma_0) {
+            fdd_timer().start("domain.vector_operations");
+            math.vector_scaling(V[0], 1.0 / gamma_0, r_k, num_local_points);
             fdd_timer().stop("domain.vector_operations");
             va_valid = 0; // a new basis
+        };
+        space.arnoldi_step = [&](int j, std::vector<std::vector<DType>> &H) {
+            apply_preconditioner(Z[j], V[j], subdomain);
 
-            for (j = 0; j < num_vectors; j++)
-            {
-                apply_preconditioner(Z[j], V[j], subdomain);
+            fdd_timer().start("domain.operator_application");
+            stiffness_matrix(q_k, Z[j]);
+            fdd_timer().stop("domain.operator_application");
 
-                fdd_timer().start("domain.operator_application");
-                stiffness_matrix(q_k, Z[j]);
-                fdd_timer().stop("domain.operator_application");
-
-                // classical Gram-Schmidt: every H[i][j] from the same q_k (domain.tpp:810-815)
-                if (restructured_outer)
-                {
-                    // <q, V_i> = sum q * (QQt V_i) * mask with the assembled copy VA[i] = mask * QQt V_i cached when
-                    // V_i was made (the reference redoes the dssum inside each of the (j+1)(j+2)/2 products);
-                    // the (j+1) dots read q once per group of FDD_MULTI_MAX, the (j+1) updates are one pass per group
-                    fdd_timer().start("domain.inner_products");
-                    gmres_cache_assembled(j);
-                    std::vector<double> h(j + 1);
-                    for (int g0 = 0; g0 < j + 1; g0 += FDD_MULTI_MAX)
-                    {
-                        const int cnt = std::min(FDD_MULTI_MAX, j + 1 - g0);
-                        const double *ptrs[FDD_MULTI_MAX];
-                        for (int i = 0; i < cnt; i++) ptrs[i] = VA[g0 + i].template as<double>();
-                        FDD_CALL(fdd_multi_weighted_inner_product(scalars.as<double>(), reduce_ws.as<double>(), q_k.as<double>(), ptrs, cnt, dirichlet_mask.as<double>(), num_local_points, fdd::dev().stream));
-                        fetch_scalars(h.data() + g0, cnt);
-                    }
-                    for (int i = 0; i < j + 1; i++) H[i][j] = h[i];
-                    fdd_timer().stop("domain.inner_products");
-
-                    fdd_timer().start("domain.vector_operations");
-                    for (int g0 = 0; g0 < j + 1; g0 += FDD_MULTI_MAX)
-                    {
-                        const int cnt = std::min(FDD_MULTI_MAX, j + 1 - g0);
-                        const double *ptrs[FDD_MULTI_MAX];
-                        double coeffs[FDD_MULTI_MAX];
-                        for (int i = 0; i < cnt; i++)
-                        {
-                            ptrs[i] = V[g0 + i].template as<double>();
-                            coeffs[i] = -H[g0 + i][j];
-                        }
-                        FDD_CALL(fdd_multi_axpy(q_k.as<double>(), coeffs, ptrs, cnt, num_local_points, fdd::dev().stream));
-                    }
-                    fdd_timer().stop("domain.vector_operations");
-                }
-                else
-                {
-                    for (int i = 0; i < j + 1; i++)
-                    {
-                        fdd_timer().start("domain.inner_products");
-                        assembled_inner_product(H[i][j], q_k, V[i]);
-                        fdd_timer().stop("domain.inner_products");
-                    }
-
-                    for (int i = 0; i < j + 1; i++)
-                    {
-                        fdd_timer().start("domain.vector_operations");
-                        math.vector_vector_addition(q_k, 1.0, q_k, -H[i][j], V[i], num_local_points);
-                        fdd_timer().stop("domain.vector_operations");
-                    }
-                }
-
-                for (int i = 0; i < j; i++)
-                {
-                    DType h_ij = H[i][j];
-                    H[i][j] = c_gmres[i] * h_ij + s_gmres[i] * H[i + 1][j];
-                    H[i + 1][j] = -s_gmres[i] * h_ij + c_gmres[i] * H[i + 1][j];
-                }
-
-                fdd_timer().start("domain.residual_norm");
-                residual_norm(alpha_j, q_k);
-                fdd_timer().stop("domain.residual_norm");
-
-                if (std::abs(alpha_j) == 0.0)
-                {
-                    converged = true;
-                    break;
-                }
-
-                beta_j = std::sqrt(H[j][j] * H[j][j] + alpha_j * alpha_j);
-                gamma_j = 1.0 / beta_j;
-                c_gmres[j] = H[j][j] * gamma_j;
-                s_gmres[j] = alpha_j * gamma_j;
-                H[j][j] = beta_j;
-                gamma[j + 1] = -s_gmres[j] * gamma[j];
-                gamma[j] = c_gmres[j] * gamma[j];
-
-                r_norm = std::abs(gamma[j + 1]);
-                residual_history.push_back(r_norm);
-                rstdout("Iter %2d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", iter + 1, r_norm, r_norm / r_0_norm);
-
-                if (use_relative)
-                {
-                    if (r_norm / r_0_norm < tolerance)
-                    {
-                        converged = true;
-                        break;
-                    }
-                }
-                else
-                {
-                    if (r_norm < tolerance)
-                    {
-                        converged = true;
-                        break;
-                    }
-                }
-
-                if (iter >= max_iterations)
-                {
-                    converged = true;
-                    break;
-                }
-
-                if (std::isnan(r_norm))
-                {
-                    converged = true;
-                    break;
-                }
-
-                fdd_timer().start("domain.vector_operations");
-                math.vector_scaling(V[j + 1], 1.0 / alpha_j, q_k, num_local_points);
-                fdd_timer().stop("domain.vector_operations");
-
-                iter++;
-            }
-
-            if (j == num_vectors) j--;
-
-            // back substitution stored into c_gmres (domain.tpp:891-899)
-            for (int k = j; k >= 0; k--)
-            {
-                gamma_k = gamma[k];
-                for (int i = j; i > k; i--) gamma_k -= H[k][i] * c_gmres[i];
-                c_gmres[k] = gamma_k / H[k][k];
-            }
-
+            // classical Gram-Schmidt: every H[i][j] from the same q_k (domain.tpp:810-815)
             if (restructured_outer)
             {
+                // <q, V_i> = sum q * (QQt V_i) * mask with the assembled copy VA[i] = mask * QQt V_i cached when
+                // V_i was made (the reference redoes the dssum inside each of the (j+1)(j+2)/2 products);
+                // the (j+1) dots read q once per group of FDD_MULTI_MAX, the (j+1) updates are one pass per group
+                fdd_timer().start("domain.inner_products");
+                gmres_cache_assembled(j);
+                for (int i = 0; i < j + 1; i++) va[i] = VA[i].template as<double>();
+                grouped_inner_products(H, j, q_k, va.data(), j + 1, dirichlet_mask, num_local_points);
+                fdd_timer().stop("domain.inner_products");
+
                 fdd_timer().start("domain.vector_operations");
-                for (int g0 = 0; g0 < j + 1; g0 += FDD_MULTI_MAX)
-                {
-                    const int cnt = std::min(FDD_MULTI_MAX, j + 1 - g0);
-                    const double *ptrs[FDD_MULTI_MAX];
-                    for (int i = 0; i < cnt; i++) ptrs[i] = Z[g0 + i].template as<double>();
-                    FDD_CALL(fdd_multi_axpy(u_k.as<double>(), c_gmres.data() + g0, ptrs, cnt, num_local_points, fdd::dev().stream));
-                }
+                for (int i = 0; i < j + 1; i++) minus_h[i] = -H[i][j];
+                grouped_axpy(q_k, minus_h.data(), V, j + 1, num_local_points);
                 fdd_timer().stop("domain.vector_operations");
             }
             else
             {
                 for (int i = 0; i < j + 1; i++)
                 {
+                    fdd_timer().start("domain.inner_products");
+                    assembled_inner_product(H[i][j], q_k, V[i]);
+                    fdd_timer().stop("domain.inner_products");
+                }
+
+                for (int i = 0; i < j + 1; i++)
+                {
                     fdd_timer().start("domain.vector_operations");
-                    math.vector_vector_addition(u_k, 1.0, u_k, c_gmres[i], Z[i], num_local_points);
+                    math.vector_vector_addition(q_k, 1.0, q_k, -H[i][j], V[i], num_local_points);
                     fdd_timer().stop("domain.vector_operations");
                 }
             }
-
-            if (converged) break;
-        }
-
-        num_iterations = iter;
+            return norm_of(q_k);
+        };
+        space.next_vector = [&](int j, DType alpha_j) {
+            fdd_timer().start("domain.vector_operations");
+            math.vector_scaling(V[j + 1], 1.0 / alpha_j, q_k, num_local_points);
+            fdd_timer().stop("domain.vector_operations");
+        };
+        space.add_update = [&](int j, const std::vector<DType> &c) {
+            if (restructured_outer)
+            {
+                fdd_timer().start("domain.vector_operations");
+                grouped_axpy(u_k, c.data(), Z, j + 1, num_local_points);
+                fdd_timer().stop("domain.vector_operations");
+                return;
+            }
+            for (int i = 0; i < j + 1; i++)
+            {
+                fdd_timer().start("domain.vector_operations");
+                math.vector_vector_addition(u_k, 1.0, u_k, c[i], Z[i], num_local_points);
+                fdd_timer().stop("domain.vector_operations");
+            }
+        };
+        num_iterations = fdd::gmres_solve(gmres_scalars, num_vectors, outer_gmres_control(use_relative), space, residual_history, print_outer_step);
     }
 };
 

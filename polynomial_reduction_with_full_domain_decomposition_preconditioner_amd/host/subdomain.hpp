@@ -55,6 +55,7 @@
 #include "csr_matrix.hpp"
 #include "domain.hpp"
 #include "gll.hpp"
+#include "gmres.hpp"
 #include "low_order.hpp"
 #include "math.hpp"
 #include "timer.hpp"
@@ -135,8 +136,7 @@ class Subdomain
 
     fdd::memory f, u_k, r_k, r_kp1, q_k, z_k, p_k;
     std::vector<fdd::memory> V, Z;
-    std::vector<std::vector<DType>> H;
-    std::vector<DType> c_gmres, s_gmres, gamma;
+    fdd::GmresScalars<DType> gmres_scalars; // H, rotations, gamma of the host-bookkeeping inner GMRES, sized per solve
 
     fdd::memory reduce_ws;
     fdd::memory scalars;
@@ -1527,7 +1527,7 @@ class Subdomain
         q_k = fdd::dev().malloc<DType>(num_values);
         z_k = fdd::dev().malloc<DType>(num_values);
         p_k = fdd::dev().malloc<DType>(num_values);
-        allocate_krylov_scalars(); // the point-space Krylov basis is allocated by the solvers that use it
+        // (the point-space Krylov basis is allocated by the solvers that use it)
 
         reduce_ws = fdd::dev().malloc<double>(fdd_reduce_workspace_doubles());
         scalars = fdd::dev().malloc<double>(2 * FDD_GMRES_SLOT);
@@ -1883,15 +1883,15 @@ class Subdomain
         for (int i = 0; i < num_vectors + 1; i++) V[i] = fdd::dev().malloc<DType>(num_values);
         Z.resize(num_vectors);
         for (int i = 0; i < num_vectors; i++) Z[i] = fdd::dev().malloc<DType>(num_values);
-        allocate_krylov_scalars();
     }
 
-    void allocate_krylov_scalars()
+    // The inner iteration is the reference's Subdomain loop: gmres.hpp says what the two switches stand for.
+    fdd::GmresControl<DType> inner_gmres_control(bool use_relative) const { return {max_iterations, tolerance, use_relative, /* count_at_step_start */ true, /* stop_on_nan */ false}; }
+    static auto print_inner_step(bool print_history)
     {
-        H.assign(num_vectors, std::vector<DType>(num_vectors, 0.0));
-        c_gmres.assign(num_vectors, 0.0);
-        s_gmres.assign(num_vectors, 0.0);
-        gamma.assign(num_vectors + 1, 0.0);
+        return [print_history](int step, DType r_norm, DType relative) {
+            if (print_history) pstdout("- Iter %3d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", step, r_norm, relative);
+        };
     }
 
     // subdomain.tpp:3969-3985
@@ -2096,129 +2096,60 @@ class Subdomain
         tree_operator(f, f_l);
         initialize_arrays(u_k, r_k, f);
 
-        DType r_norm;
-        DType r_0_norm;
-        gather_norm(r_0_norm, r_k);
-        residual_history.push_back(r_0_norm);
-        if (print_history) pstdout("- Iter %3d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", 0, r_0_norm, 1.0);
-
-        bool converged = false;
-        int iter = 0;
-        int j;
-        DType alpha_j, beta_j, gamma_j, gamma_k;
+        auto norm_of = [&](fdd::memory &v) {
+            DType norm;
+            gather_norm(norm, v);
+            return norm;
+        };
         std::vector<double> coeffs(num_vectors + 1);
         std::vector<const double *> ptrs(num_vectors + 1);
-
-        while (iter < max_iterations)
-        {
-            if (iter > 0)
-            {
-                stiffness_matrix(r_k, u_k);
-                math.vector_vector_addition(r_k, 1.0, f, -1.0, r_k, num_values);
-                gather_norm(r_norm, r_k);
-                gamma[0] = r_norm;
-            }
-            else
-            {
-                gamma[0] = r_0_norm;
-            }
-
-            math.vector_scaling(V[0], 1.0 / gamma[0], r_k, num_values);
+        fdd::GmresSpace<DType> space;
+        space.initial_norm = [&] { return norm_of(r_k); };
+        space.restart_norm = [&] {
+            stiffness_matrix(r_k, u_k);
+            math.vector_vector_addition(r_k, 1.0, f, -1.0, r_k, num_values);
+            return norm_of(r_k);
+        };
+        space.start_cycle = [&](DType gamma_0) {
+            math.vector_scaling(V[0], 1.0 / gamma_0, r_k, num_values);
             gather_weighted(VA[0], V[0]);
+        };
+        space.arnoldi_step = [&](int j, std::vector<std::vector<DType>> &H) {
+            direct_stiffness_summation(Z[j], V[j]);
+            stiffness_matrix(q_k, Z[j]);
 
-            for (j = 0; j < num_vectors; j++)
+            // H[0..j][j] = <q, V[i]> for all i from the same q (classical Gram-Schmidt)
+            gather_weighted(qa, q_k);
+            for (int i = 0; i < j + 1; i++) ptrs[i] = VA[i].template as<double>();
             {
-                iter++;
-
-                direct_stiffness_summation(Z[j], V[j]);
-                stiffness_matrix(q_k, Z[j]);
-
-                // H[0..j][j] = <q, V[i]> for all i from the same q (classical Gram-Schmidt)
-                gather_weighted(qa, q_k);
-                for (int i = 0; i < j + 1; i++) ptrs[i] = VA[i].template as<double>();
-                {
-                    fdd::ProfileScope prof("reduce_vec2_kernel<MultiDotW>", 8.0 * nd * (j + 3));
-                    FDD_CALL(fdd_multi_weighted_inner_product(scalars.as<double>(), reduce_ws.as<double>(), qa.as<double>(), ptrs.data(), j + 1, norm_weight.as<double>(), nd, fdd::dev().stream));
-                }
-                fetch_scalars(coeffs.data(), j + 1);
-                for (int i = 0; i < j + 1; i++)
-                {
-                    H[i][j] = coeffs[i];
-                    coeffs[i] = -H[i][j];
-                    ptrs[i] = V[i].template as<double>();
-                }
-                {
-                    fdd::ProfileScope prof("ew_vec2_kernel<MultiAxpy>", 8.0 * num_values * (j + 3));
-                    FDD_CALL(fdd_multi_axpy(q_k.as<double>(), coeffs.data(), ptrs.data(), j + 1, num_values, fdd::dev().stream));
-                }
-
-                for (int i = 0; i < j; i++)
-                {
-                    DType h_ij = H[i][j];
-                    H[i][j] = c_gmres[i] * h_ij + s_gmres[i] * H[i + 1][j];
-                    H[i + 1][j] = -s_gmres[i] * h_ij + c_gmres[i] * H[i + 1][j];
-                }
-
-                gather_norm(alpha_j, q_k);
-
-                if (std::abs(alpha_j) == 0.0)
-                {
-                    converged = true;
-                    break;
-                }
-
-                beta_j = std::sqrt(H[j][j] * H[j][j] + alpha_j * alpha_j);
-                gamma_j = 1.0 / beta_j;
-                c_gmres[j] = H[j][j] * gamma_j;
-                s_gmres[j] = alpha_j * gamma_j;
-                H[j][j] = beta_j;
-                gamma[j + 1] = -s_gmres[j] * gamma[j];
-                gamma[j] = c_gmres[j] * gamma[j];
-
-                r_norm = std::abs(gamma[j + 1]);
-                residual_history.push_back(r_norm);
-                if (print_history) pstdout("- Iter %3d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", iter, r_norm, r_norm / r_0_norm);
-
-                if (use_relative ? (r_norm / r_0_norm < tolerance) : (r_norm < tolerance))
-                {
-                    converged = true;
-                    break;
-                }
-
-                if (iter >= max_iterations)
-                {
-                    converged = true;
-                    break;
-                }
-
-                math.vector_scaling(V[j + 1], 1.0 / alpha_j, q_k, num_values);
-                gather_weighted(VA[j + 1], V[j + 1]);
+                fdd::ProfileScope prof("reduce_vec2_kernel<MultiDotW>", 8.0 * nd * (j + 3));
+                FDD_CALL(fdd_multi_weighted_inner_product(scalars.as<double>(), reduce_ws.as<double>(), qa.as<double>(), ptrs.data(), j + 1, norm_weight.as<double>(), nd, fdd::dev().stream));
             }
-
-            if (j == num_vectors) j--;
-
-            for (int k = j; k >= 0; k--)
-            {
-                gamma_k = gamma[k];
-                for (int i = j; i > k; i--) gamma_k -= H[k][i] * c_gmres[i];
-                c_gmres[k] = gamma_k / H[k][k];
-            }
-
+            fetch_scalars(coeffs.data(), j + 1);
             for (int i = 0; i < j + 1; i++)
             {
-                coeffs[i] = c_gmres[i];
-                ptrs[i] = Z[i].template as<double>();
+                H[i][j] = coeffs[i];
+                coeffs[i] = -H[i][j];
+                ptrs[i] = V[i].template as<double>();
             }
             {
                 fdd::ProfileScope prof("ew_vec2_kernel<MultiAxpy>", 8.0 * num_values * (j + 3));
-                FDD_CALL(fdd_multi_axpy(u_k.as<double>(), coeffs.data(), ptrs.data(), j + 1, num_values, fdd::dev().stream));
+                FDD_CALL(fdd_multi_axpy(q_k.as<double>(), coeffs.data(), ptrs.data(), j + 1, num_values, fdd::dev().stream));
             }
-
-            if (converged) break;
-        }
+            return norm_of(q_k);
+        };
+        space.next_vector = [&](int j, DType alpha_j) {
+            math.vector_scaling(V[j + 1], 1.0 / alpha_j, q_k, num_values);
+            gather_weighted(VA[j + 1], V[j + 1]);
+        };
+        space.add_update = [&](int j, const std::vector<DType> &c) {
+            for (int i = 0; i < j + 1; i++) ptrs[i] = Z[i].template as<double>();
+            fdd::ProfileScope prof("ew_vec2_kernel<MultiAxpy>", 8.0 * num_values * (j + 3));
+            FDD_CALL(fdd_multi_axpy(u_k.as<double>(), c.data(), ptrs.data(), j + 1, num_values, fdd::dev().stream));
+        };
+        num_iterations += fdd::gmres_solve(gmres_scalars, num_vectors, inner_gmres_control(use_relative), space, residual_history, print_inner_step(print_history));
 
         FDD_CALL(fdd_sub_copy_f64_f64(u_l.as<double>(), u_k.as<double>(), levels[0].num_points, fdd::dev().stream));
-        num_iterations += iter;
     }
 
     // ------------------------------------------------------------------
@@ -2501,7 +2432,6 @@ class Subdomain
         krylov64.ensure(m, std::max(nd, 1), pre);
         std::vector<fdd::memory> &VA = krylov64.VA, &ZA = krylov64.ZA;
         fdd::memory &qa = krylov64.qa;
-        if ((int)H.size() != m) allocate_krylov_scalars();
         residual_history.clear();
         history_pending = false; // a lazy solve before this one (pcg_steps) may have left its history on the device: it is not this solve's
         double *sc = scalars.as<double>();
@@ -2515,144 +2445,69 @@ class Subdomain
 
         FDD_CALL(fdd_set_to_value(ua.as<double>(), 0.0, nd, 0, stream));
 
-        DType r_norm, r_0_norm;
-        {
-            const double *self[1] = {fa.as<double>()};
-            dot_dofs(sc, fa, self, 1);
-            fetch_scalars(&r_0_norm, 1);
-            r_0_norm = std::sqrt(r_0_norm);
-        }
-        residual_history.push_back(r_0_norm);
-        if (print_history) pstdout("- Iter %3d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", 0, r_0_norm, 1.0);
-
-        bool converged = false;
-        int iter = 0;
-        int j;
-        DType alpha_j, beta_j, gamma_j, gamma_k;
+        auto norm_of = [&](fdd::memory &v) {
+            const double *self[1] = {v.as<double>()};
+            DType norm;
+            dot_dofs(sc, v, self, 1);
+            fetch_scalars(&norm, 1);
+            return std::sqrt(norm);
+        };
         std::vector<double> coeffs(m + 2);
         std::vector<const double *> ptrs(m + 1);
         fdd::memory *ra = &fa; // assembled residual of the current cycle
-
-        while (iter < max_iterations)
-        {
-            if (iter > 0)
+        fdd::GmresSpace<DType> space;
+        space.initial_norm = [&] { return norm_of(fa); };
+        // r~ = f~ - Qt A Q u~
+        space.restart_norm = [&] {
+            stiffness_from_dofs(q_k.as<double>(), ua.as<double>());
+            gather_weighted(qa, q_k);
+            FDD_CALL(fdd_vector_vector_addition(qa.as<double>(), 1.0, fa.as<double>(), -1.0, qa.as<double>(), nd, stream));
+            ra = &qa;
+            return norm_of(qa);
+        };
+        space.start_cycle = [&](DType gamma_0) { FDD_CALL(fdd_vector_scaling(VA[0].template as<double>(), 1.0 / gamma_0, ra->template as<double>(), nd, stream)); };
+        space.arnoldi_step = [&](int j, std::vector<std::vector<DType>> &H) {
+            // z~_j = M^-1 v~_j: the identity on assembled data (dssum), or the AMG V-cycle over the dofs
+            fdd::memory *za = &VA[j];
+            if (use_preconditioner)
             {
-                // r~ = f~ - Qt A Q u~
-                stiffness_from_dofs(q_k.as<double>(), ua.as<double>());
-                gather_weighted(qa, q_k);
-                FDD_CALL(fdd_vector_vector_addition(qa.as<double>(), 1.0, fa.as<double>(), -1.0, qa.as<double>(), nd, stream));
-                const double *self[1] = {qa.as<double>()};
-                dot_dofs(sc, qa, self, 1);
-                fetch_scalars(&r_norm, 1);
-                r_norm = std::sqrt(r_norm);
-                gamma[0] = r_norm;
-                ra = &qa;
+                amg::Level &fine = amg_checked();
+                fine.f.copyFrom(VA[j], (size_t)nd * sizeof(DType));
+                amg_hierarchy.vcycle();
+                ZA[j].copyFrom(fine.u, (size_t)nd * sizeof(DType));
+                za = &ZA[j];
             }
-            else
+            else if (jacobi)
             {
-                gamma[0] = r_0_norm;
-            }
-
-            FDD_CALL(fdd_vector_scaling(VA[0].template as<double>(), 1.0 / gamma[0], ra->template as<double>(), nd, stream));
-
-            for (j = 0; j < m; j++)
-            {
-                iter++;
-
-                // z~_j = M^-1 v~_j: the identity on assembled data (dssum), or the AMG V-cycle over the dofs
-                fdd::memory *za = &VA[j];
-                if (use_preconditioner)
-                {
-                    amg::Level &fine = amg_checked();
-                    fine.f.copyFrom(VA[j], (size_t)nd * sizeof(DType));
-                    amg_hierarchy.vcycle();
-                    ZA[j].copyFrom(fine.u, (size_t)nd * sizeof(DType));
-                    za = &ZA[j];
-                }
-                else if (jacobi)
-                {
-                    FDD_CALL(fdd_vector_diagonal_scaling_dev(ZA[j].template as<double>(), jacobi_dinv.as<double>(), nullptr, VA[j].template as<double>(), nd, stream));
-                    za = &ZA[j];
-                }
-
-                stiffness_from_dofs(q_k.as<double>(), za->template as<double>());
-                gather_weighted(qa, q_k);
-
-                // H[0..j][j] = <q~, v~_i>, q~ -= sum H v~_i, ||q~||^2: coefficients never leave the device in between
-                for (int i = 0; i < j + 1; i++) ptrs[i] = VA[i].template as<double>();
-                dot_dofs(sc, qa, ptrs.data(), j + 1);
-                {
-                    fdd::ProfileScope prof("reduce_vec2_kernel<MultiAxpyNorm>", 8.0 * nd * (j + 3 + (nw ? 1 : 0)));
-                    FDD_CALL(fdd_multi_axpy_norm2_dev(sc + (j + 1), ws, qa.as<double>(), sc, -1.0, ptrs.data(), j + 1, nw, nd, stream));
-                }
-                // v~_{j+1} = q~ / ||q~||, launched before the host looks at the numbers (unused if this was the last step)
-                if (j + 1 <= m) FDD_CALL(fdd_vector_scaling_rsqrt_dev(VA[j + 1].template as<double>(), sc + (j + 1), qa.as<double>(), nd, stream));
-
-                fetch_scalars(coeffs.data(), j + 2);
-                for (int i = 0; i < j + 1; i++) H[i][j] = coeffs[i];
-                alpha_j = std::sqrt(coeffs[j + 1]);
-
-                for (int i = 0; i < j; i++)
-                {
-                    DType h_ij = H[i][j];
-                    H[i][j] = c_gmres[i] * h_ij + s_gmres[i] * H[i + 1][j];
-                    H[i + 1][j] = -s_gmres[i] * h_ij + c_gmres[i] * H[i + 1][j];
-                }
-
-                if (std::abs(alpha_j) == 0.0)
-                {
-                    converged = true;
-                    break;
-                }
-
-                beta_j = std::sqrt(H[j][j] * H[j][j] + alpha_j * alpha_j);
-                gamma_j = 1.0 / beta_j;
-                c_gmres[j] = H[j][j] * gamma_j;
-                s_gmres[j] = alpha_j * gamma_j;
-                H[j][j] = beta_j;
-                gamma[j + 1] = -s_gmres[j] * gamma[j];
-                gamma[j] = c_gmres[j] * gamma[j];
-
-                r_norm = std::abs(gamma[j + 1]);
-                residual_history.push_back(r_norm);
-                if (print_history) pstdout("- Iter %3d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", iter, r_norm, r_norm / r_0_norm);
-
-                if (use_relative ? (r_norm / r_0_norm < tolerance) : (r_norm < tolerance))
-                {
-                    converged = true;
-                    break;
-                }
-
-                if (iter >= max_iterations)
-                {
-                    converged = true;
-                    break;
-                }
+                FDD_CALL(fdd_vector_diagonal_scaling_dev(ZA[j].template as<double>(), jacobi_dinv.as<double>(), nullptr, VA[j].template as<double>(), nd, stream));
+                za = &ZA[j];
             }
 
-            if (j == m) j--;
+            stiffness_from_dofs(q_k.as<double>(), za->template as<double>());
+            gather_weighted(qa, q_k);
 
-            for (int k = j; k >= 0; k--)
+            // H[0..j][j] = <q~, v~_i>, q~ -= sum H v~_i, ||q~||^2: coefficients never leave the device in between
+            for (int i = 0; i < j + 1; i++) ptrs[i] = VA[i].template as<double>();
+            dot_dofs(sc, qa, ptrs.data(), j + 1);
             {
-                gamma_k = gamma[k];
-                for (int i = j; i > k; i--) gamma_k -= H[k][i] * c_gmres[i];
-                c_gmres[k] = gamma_k / H[k][k];
+                fdd::ProfileScope prof("reduce_vec2_kernel<MultiAxpyNorm>", 8.0 * nd * (j + 3 + (nw ? 1 : 0)));
+                FDD_CALL(fdd_multi_axpy_norm2_dev(sc + (j + 1), ws, qa.as<double>(), sc, -1.0, ptrs.data(), j + 1, nw, nd, stream));
             }
+            // v~_{j+1} = q~ / ||q~||, launched before the host looks at the numbers (unused if this was the last step)
+            FDD_CALL(fdd_vector_scaling_rsqrt_dev(VA[j + 1].template as<double>(), sc + (j + 1), qa.as<double>(), nd, stream));
 
-            for (int i = 0; i < j + 1; i++)
-            {
-                coeffs[i] = c_gmres[i];
-                ptrs[i] = pre ? ZA[i].template as<double>() : VA[i].template as<double>();
-            }
-            {
-                fdd::ProfileScope prof("ew_vec2_kernel<MultiAxpy>", 8.0 * nd * (j + 3));
-                FDD_CALL(fdd_multi_axpy(ua.as<double>(), coeffs.data(), ptrs.data(), j + 1, nd, stream));
-            }
-
-            if (converged) break;
-        }
-
-        num_iterations += iter;
+            fetch_scalars(coeffs.data(), j + 2); // the one synchronisation of the step
+            for (int i = 0; i < j + 1; i++) H[i][j] = coeffs[i];
+            return std::sqrt(coeffs[j + 1]);
+        };
+        // already enqueued
+        space.next_vector = [](int, DType) {};
+        space.add_update = [&](int j, const std::vector<DType> &c) {
+            for (int i = 0; i < j + 1; i++) ptrs[i] = pre ? ZA[i].template as<double>() : VA[i].template as<double>();
+            fdd::ProfileScope prof("ew_vec2_kernel<MultiAxpy>", 8.0 * nd * (j + 3));
+            FDD_CALL(fdd_multi_axpy(ua.as<double>(), c.data(), ptrs.data(), j + 1, nd, stream));
+        };
+        num_iterations += fdd::gmres_solve(gmres_scalars, m, inner_gmres_control(use_relative), space, residual_history, print_inner_step(print_history));
     }
 
     // subdomain.tpp:4309-4489
@@ -2679,167 +2534,83 @@ class Subdomain
         initialize_arrays(u_k, r_k, f);
         fdd_timer().stop("subdomain.vector_operations");
 
-        DType r_norm;
-        DType r_0_norm;
+        auto norm_of = [&](fdd::memory &v) {
+            DType norm;
+            fdd_timer().start("subdomain.residual_norm");
+            residual_norm(norm, v);
+            fdd_timer().stop("subdomain.residual_norm");
+            return norm;
+        };
+        fdd::GmresSpace<DType> space;
+        space.initial_norm = [&] { return norm_of(r_k); };
+        space.restart_norm = [&] {
+            fdd_timer().start("subdomain.operator_application");
+            stiffness_matrix(r_k, u_k);
+            fdd_timer().stop("subdomain.operator_application");
 
-        fdd_timer().start("subdomain.residual_norm");
-        residual_norm(r_0_norm, r_k);
-        fdd_timer().stop("subdomain.residual_norm");
-        residual_history.push_back(r_0_norm);
-        if (print_history) pstdout("- Iter %3d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", 0, r_0_norm, 1.0);
-
-        bool converged = false;
-        int iter = 0;
-        int j;
-
-        DType alpha_j, beta_j, gamma_j, gamma_k;
-
-        while (iter < max_iterations)
-        {
-            if (iter > 0)
+            fdd_timer().start("subdomain.vector_operations");
+            math.vector_vector_addition(r_k, 1.0, f, -1.0, r_k, num_values);
+            fdd_timer().stop("subdomain.vector_operations");
+            return norm_of(r_k);
+        };
+        space.start_cycle = [&](DType gamma_0) {
+            fdd_timer().start("subdomain.vector_operations");
+            math.vector_scaling(V[0], 1.0 / gamma_0, r_k, num_values);
+            fdd_timer().stop("subdomain.vector_operations");
+        };
+        space.arnoldi_step = [&](int j, std::vector<std::vector<DType>> &H) {
+            if (use_preconditioner)
             {
-                fdd_timer().start("subdomain.operator_application");
-                stiffness_matrix(r_k, u_k);
-                fdd_timer().stop("subdomain.operator_application");
-
-                fdd_timer().start("subdomain.vector_operations");
-                math.vector_vector_addition(r_k, 1.0, f, -1.0, r_k, num_values);
-                fdd_timer().stop("subdomain.vector_operations");
-
-                fdd_timer().start("subdomain.residual_norm");
-                residual_norm(r_norm, r_k);
-                fdd_timer().stop("subdomain.residual_norm");
-
-                gamma[0] = r_norm;
+                low_order_preconditioner(Z[j], V[j]);
+            }
+            else if (use_jacobi)
+            {
+                jacobi_preconditioner(Z[j], V[j]);
             }
             else
             {
-                gamma[0] = r_0_norm;
+                fdd_timer().start("subdomain.preconditioner.identity");
+                direct_stiffness_summation(Z[j], V[j]);
+                fdd_timer().stop("subdomain.preconditioner.identity");
             }
 
-            fdd_timer().start("subdomain.vector_operations");
-            math.vector_scaling(V[0], 1.0 / gamma[0], r_k, num_values);
-            fdd_timer().stop("subdomain.vector_operations");
+            fdd_timer().start("subdomain.operator_application");
+            stiffness_matrix(q_k, Z[j]);
+            fdd_timer().stop("subdomain.operator_application");
 
-            for (j = 0; j < num_vectors; j++)
+            for (int i = 0; i < j + 1; i++)
             {
-                iter++; // incremented at the START of a step here (subdomain.tpp:4370)
-
-                if (use_preconditioner)
-                {
-                    low_order_preconditioner(Z[j], V[j]);
-                }
-                else if (use_jacobi)
-                {
-                    jacobi_preconditioner(Z[j], V[j]);
-                }
-                else
-                {
-                    fdd_timer().start("subdomain.preconditioner.identity");
-                    direct_stiffness_summation(Z[j], V[j]);
-                    fdd_timer().stop("subdomain.preconditioner.identity");
-                }
-
-                fdd_timer().start("subdomain.operator_application");
-                stiffness_matrix(q_k, Z[j]);
-                fdd_timer().stop("subdomain.operator_application");
-
-                for (int i = 0; i < j + 1; i++)
-                {
-                    fdd_timer().start("subdomain.inner_products");
-                    assembled_inner_product(H[i][j], q_k, V[i]);
-                    fdd_timer().stop("subdomain.inner_products");
-                }
-
-                for (int i = 0; i < j + 1; i++)
-                {
-                    fdd_timer().start("subdomain.vector_operations");
-                    math.vector_vector_addition(q_k, 1.0, q_k, -H[i][j], V[i], num_values);
-                    fdd_timer().stop("subdomain.vector_operations");
-                }
-
-                for (int i = 0; i < j; i++)
-                {
-                    DType h_ij = H[i][j];
-                    H[i][j] = c_gmres[i] * h_ij + s_gmres[i] * H[i + 1][j];
-                    H[i + 1][j] = -s_gmres[i] * h_ij + c_gmres[i] * H[i + 1][j];
-                }
-
-                fdd_timer().start("subdomain.residual_norm");
-                residual_norm(alpha_j, q_k);
-                fdd_timer().stop("subdomain.residual_norm");
-
-                if (std::abs(alpha_j) == 0.0)
-                {
-                    converged = true;
-                    break;
-                }
-
-                beta_j = std::sqrt(H[j][j] * H[j][j] + alpha_j * alpha_j);
-                gamma_j = 1.0 / beta_j;
-                c_gmres[j] = H[j][j] * gamma_j;
-                s_gmres[j] = alpha_j * gamma_j;
-                H[j][j] = beta_j;
-                gamma[j + 1] = -s_gmres[j] * gamma[j];
-                gamma[j] = c_gmres[j] * gamma[j];
-
-                r_norm = std::abs(gamma[j + 1]);
-                residual_history.push_back(r_norm);
-                if (print_history) pstdout("- Iter %3d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", iter, r_norm, r_norm / r_0_norm);
-
-                if (use_relative)
-                {
-                    if (r_norm / r_0_norm < tolerance)
-                    {
-                        converged = true;
-                        break;
-                    }
-                }
-                else
-                {
-                    if (r_norm < tolerance)
-                    {
-                        converged = true;
-                        break;
-                    }
-                }
-
-                // hitting max_iterations counts as converged (subdomain.tpp:4449-4453)
-                if (iter >= max_iterations)
-                {
-                    converged = true;
-                    break;
-                }
-
-                fdd_timer().start("subdomain.vector_operations");
-                math.vector_scaling(V[j + 1], 1.0 / alpha_j, q_k, num_values);
-                fdd_timer().stop("subdomain.vector_operations");
-            }
-
-            if (j == num_vectors) j--;
-
-            for (int k = j; k >= 0; k--)
-            {
-                gamma_k = gamma[k];
-                for (int i = j; i > k; i--) gamma_k -= H[k][i] * c_gmres[i];
-                c_gmres[k] = gamma_k / H[k][k];
+                fdd_timer().start("subdomain.inner_products");
+                assembled_inner_product(H[i][j], q_k, V[i]);
+                fdd_timer().stop("subdomain.inner_products");
             }
 
             for (int i = 0; i < j + 1; i++)
             {
                 fdd_timer().start("subdomain.vector_operations");
-                math.vector_vector_addition(u_k, 1.0, u_k, c_gmres[i], Z[i], num_values);
+                math.vector_vector_addition(q_k, 1.0, q_k, -H[i][j], V[i], num_values);
                 fdd_timer().stop("subdomain.vector_operations");
             }
-
-            if (converged) break;
-        }
+            return norm_of(q_k);
+        };
+        space.next_vector = [&](int j, DType alpha_j) {
+            fdd_timer().start("subdomain.vector_operations");
+            math.vector_scaling(V[j + 1], 1.0 / alpha_j, q_k, num_values);
+            fdd_timer().stop("subdomain.vector_operations");
+        };
+        space.add_update = [&](int j, const std::vector<DType> &c) {
+            for (int i = 0; i < j + 1; i++)
+            {
+                fdd_timer().start("subdomain.vector_operations");
+                math.vector_vector_addition(u_k, 1.0, u_k, c[i], Z[i], num_values);
+                fdd_timer().stop("subdomain.vector_operations");
+            }
+        };
+        num_iterations += fdd::gmres_solve(gmres_scalars, num_vectors, inner_gmres_control(use_relative), space, residual_history, print_inner_step(print_history));
 
         fdd_timer().start("subdomain.vector_operations");
         FDD_CALL(fdd_sub_copy_f64_f64(u_l.as<double>(), u_k.as<double>(), levels[0].num_points, fdd::dev().stream));
         fdd_timer().stop("subdomain.vector_operations");
-
-        num_iterations += iter;
     }
 
     // test / analysis hooks on the dof-space form of the inner iteration: y = (Qt A_L Q | A_sup) x on host vectors of
