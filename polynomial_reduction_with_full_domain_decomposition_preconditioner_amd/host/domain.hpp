@@ -6,7 +6,7 @@
  * the gfx950 kernels through the C-ABI instead of OCCA.
  *
  * What changed underneath (MI355X-first, same arithmetic):
- *   - stiffness_matrix is one fused launch (fdd_dom_stiffness_matrix) instead
+ *   - stiffness_matrix is one fused launch (element_operator.hpp) instead
  *     of two with a global scratch (domain.tpp:605-606);
  *   - every dot product finishes on the device; only the final scalar(s)
  *     cross PCIe (the reference copies one partial per 128 points and sums on
@@ -31,6 +31,7 @@
 #include "config.hpp"
 #include "csr_matrix.hpp"
 #include "element.hpp"
+#include "element_operator.hpp"
 #include "gll.hpp"
 #include "gmres.hpp"
 #include "math.hpp"
@@ -155,7 +156,7 @@ class Domain
 
     Math<DType> math;
 
-    const double *G_ptrs[NUM_GEOM_FACTS];
+    fdd::LevelList list; // the rank's elements as one run of one degree: what the element operator works on (element_operator.hpp)
 
     // From the all-gathered boundary ids (rank order, counts[r] per rank; every rank holds the same lists, so no further
     // communication): who shares which of this rank's boundary nodes.  Peer parts are ordered by global id on both sides.
@@ -586,6 +587,7 @@ class Domain
     {
         mesh = std::move(mesh_);
         poly_degree = mesh.poly_degree;
+        list = fdd::LevelList();
         fdd::SetupTimer timing("Domain::initialize", fdd::comm().rank == 0);
         fdd::globals().dim = mesh.dim; // `dim` is a global set by the last mesh read (config.hpp:48)
         const int dim = mesh.dim;
@@ -622,7 +624,7 @@ class Domain
         {
             geom_fact[g] = fdd::dev().malloc<DType>(num_local_points);
             geom_fact[g].copyFrom(mesh.g[g].data(), (size_t)num_local_points * sizeof(DType));
-            G_ptrs[g] = geom_fact[g].as<double>();
+            list.G[g] = geom_fact[g].as<double>();
         }
 
         timing.lap("elements, mask and factors to the device");
@@ -734,6 +736,10 @@ class Domain
         fdd::gll::dgll(D_hat_hst.data(), r_gll.data(), n);
         D_hat = fdd::dev().malloc<DType>((size_t)n * n);
         D_hat.copyFrom(D_hat_hst.data(), (size_t)n * n * sizeof(DType));
+        list.poly_degree = poly_degree;
+        list.dim = dim;
+        list.num_elements = num_local_elements;
+        list.D_hat = D_hat.as<double>(); // set_D_hat rewrites this buffer in place
 
         // Solver vectors (GMRES bases are allocated on first use)
         r_k = fdd::dev().malloc<DType>(num_local_points);
@@ -822,29 +828,7 @@ class Domain
     // domain.tpp:602-609
     void stiffness_matrix(fdd::memory &Au, fdd::memory &u, bool apply_dssum = false)
     {
-        if (mesh.dim == 3 and poly_degree >= 11 and poly_degree <= 15 and mfma_stiffness and Au.ptr() != u.ptr())
-        {
-            // high order: the six contractions on the fp64 matrix cores (tolerance-level parity, fdd_hip.h)
-            fdd::ProfileScope prof("mfma_stiffness_kernel", 64.0 * num_local_points);
-            FDD_CALL(fdd_stiffness_matrix_mfma(Au.as<double>(), u.as<double>(), D_hat.as<double>(), G_ptrs, nullptr, num_local_elements, poly_degree, fdd::dev().stream));
-        }
-        else if (mesh.dim == 3 and poly_degree <= 15)
-        {
-            fdd::ProfileScope prof("fused_stiffness_kernel", 64.0 * num_local_points);
-            FDD_CALL(fdd_dom_stiffness_matrix(Au.as<double>(), u.as<double>(), D_hat.as<double>(), G_ptrs, num_local_elements, poly_degree, fdd::dev().stream));
-        }
-        else if (mesh.dim == 2 and poly_degree <= 15)
-        {
-            fdd::ProfileScope prof("fused_stiffness_2d_kernel", 40.0 * num_local_points);
-            FDD_CALL(fdd_stiffness_matrix_2d(Au.as<double>(), u.as<double>(), D_hat.as<double>(), G_ptrs, nullptr, num_local_elements, poly_degree, fdd::dev().stream));
-        }
-        else
-        {
-            double *GDu[3] = {work_dev[0].as<double>(), work_dev[1].as<double>(), work_dev[2].as<double>()};
-            FDD_CALL(fdd_dom_stiffness_matrix_1(GDu, u.as<double>(), D_hat.as<double>(), G_ptrs, num_local_points, poly_degree, mesh.dim, fdd::dev().stream));
-            FDD_CALL(fdd_dom_stiffness_matrix_2(Au.as<double>(), GDu, D_hat.as<double>(), num_local_points, poly_degree, mesh.dim, fdd::dev().stream));
-        }
-
+        fdd::apply_local(list, Au.as<double>(), u.as<double>(), work_dev, mfma_stiffness);
         if (apply_dssum) direct_stiffness_summation(Au, Au, true, false);
     }
 
@@ -955,64 +939,20 @@ class Domain
         Qt.gather_scatter(nullptr, t.as<double>(), v.as<double>(), nullptr, nullptr, 0, num_local_nodes, 1);
     }
 
-    // ---- affine elements (an option of this build; the reference always streams the six factor arrays) ----
-    // Where every element of the mesh is an affine image of the reference cube (a box mesh), the factors of a point are
-    // c_f(e) (w_i w_j) w_k: the kernel forms them from six numbers per element and does not read 48 of its 64 bytes per
-    // point.  set_affine_geometry(true) checks the mesh's OWN factor arrays against that form on the device
-    // (fdd_stiffness_affine_detect) and switches the node-space operator over only if every element passes.
-    static constexpr double affine_tolerance = 64.0 * 2.220446049250313e-16;
-    bool affine_geometry = false; // in use
-    bool affine_checked = false;
-    double affine_deviation = -1.0; // largest relative deviation found (-1: not checked)
-    fdd::memory affine_c, affine_w;
+    // ---- affine elements (an option of this build, element_operator.hpp) ----
+    // set_affine_geometry(true) switches the node-space operator over only if every element of the mesh passes the check
+    // (a box mesh); false: it did not, or the mesh cannot run that kernel.
+    const fdd::LevelList &operator_list() const { return list; }
     bool set_affine_geometry(bool on)
     {
-        affine_geometry = false;
-        if (not on) return true;
-        if (mesh.dim != 3 or poly_degree > 15 or num_local_elements == 0) return false;
-        if (not affine_checked)
-        {
-            const int n = poly_degree + 1;
-            std::vector<double> z(n), w(n), dev_hst(num_local_elements);
-            fdd::gll::zwgll(z.data(), w.data(), n);
-            affine_w = fdd::dev().malloc<double>(n);
-            affine_w.copyFrom(w.data(), (size_t)n * sizeof(double));
-            affine_c = fdd::dev().malloc<double>((size_t)num_local_elements * NUM_GEOM_FACTS);
-            fdd::memory dev_dev = fdd::dev().malloc<double>(num_local_elements);
-            FDD_CALL(fdd_stiffness_affine_detect(affine_c.as<double>(), dev_dev.as<double>(), G_ptrs, nullptr, affine_w.as<double>(), num_local_elements, poly_degree, fdd::dev().stream));
-            dev_dev.copyTo(dev_hst.data(), dev_hst.size() * sizeof(double));
-            dev_dev.free();
-            affine_deviation = 0.0;
-            for (double x : dev_hst) affine_deviation = (x == x) ? std::max(affine_deviation, x) : 1.0;
-            affine_checked = true;
-        }
-        affine_geometry = affine_deviation <= affine_tolerance;
-        return affine_geometry;
+        list.affine = on and fdd::detect_affine(list);
+        return list.affine or not on;
     }
 
     // q (points) = A_local (Q p~)
     void stiffness_from_nodes(fdd::memory &q, fdd::memory &pn)
     {
-        if (affine_geometry)
-        {
-            if (poly_degree >= 11 and mfma_stiffness)
-            {
-                fdd::ProfileScope prof("mfma_stiffness_kernel<gather,affine>", 12.0 * num_local_points + 8.0 * num_local_nodes);
-                FDD_CALL(fdd_stiffness_matrix_mfma_affine(q.as<double>(), pn.as<double>(), nullptr, point_node_dev.as<int>(), D_hat.as<double>(), affine_c.as<double>(), affine_w.as<double>(), nullptr, num_local_elements, poly_degree, fdd::dev().stream));
-                return;
-            }
-            fdd::ProfileScope prof("fused_stiffness_kernel<gather,affine>", 12.0 * num_local_points + 8.0 * num_local_nodes);
-            FDD_CALL(fdd_stiffness_matrix_affine(q.as<double>(), pn.as<double>(), nullptr, point_node_dev.as<int>(), D_hat.as<double>(), affine_c.as<double>(), affine_w.as<double>(), nullptr, num_local_elements, poly_degree, fdd::dev().stream));
-            return;
-        }
-        if (poly_degree >= 11 and mfma_stiffness)
-        {
-            fdd::ProfileScope prof("mfma_stiffness_kernel<gather>", 60.0 * num_local_points + 8.0 * num_local_nodes);
-            FDD_CALL(fdd_stiffness_matrix_mfma_gather(q.as<double>(), pn.as<double>(), nullptr, point_node_dev.as<int>(), D_hat.as<double>(), G_ptrs, nullptr, num_local_elements, poly_degree, fdd::dev().stream));
-            return;
-        }
-        fdd::ProfileScope prof("fused_stiffness_kernel<gather>", 60.0 * num_local_points + 8.0 * num_local_nodes);
-        FDD_CALL(fdd_sub_stiffness_matrix_gather(q.as<double>(), pn.as<double>(), point_node_dev.as<int>(), D_hat.as<double>(), G_ptrs, nullptr, num_local_elements, poly_degree, fdd::dev().stream));
+        fdd::apply_gather(list, q.as<double>(), pn.as<double>(), point_node_dev.as<int>(), nullptr, num_local_nodes, mfma_stiffness);
     }
 
     // sqrt(<r, QQt r>) (domain.tpp:916-931) from r^ = Qt r: sum_n r^_n * gs(r^)_n * mask_n.

@@ -1,0 +1,175 @@
+/*
+ * element_operator.hpp -- the element stiffness operator on one run of elements of one degree, stated once for the
+ * Domain (which is exactly one such run) and the Subdomain (one run per polynomial level of its region): the list type,
+ * the choice of kernel for the local form (Au = A_L u on element-local points) and for the gather form
+ * (q = A_L (Q (s v)), Q read through an index array), and the check for affine elements.  This is the only host file that
+ * names a stiffness entry of fdd_hip.h.  The profile labels and byte counts are the ones bench.py's kernel table keys on.
+ */
+#ifndef FDD_ELEMENT_OPERATOR_HPP
+#define FDD_ELEMENT_OPERATOR_HPP
+
+#include <algorithm>
+#include <type_traits>
+#include <vector>
+
+#include "config.hpp"
+#include "gll.hpp"
+
+namespace fdd
+{
+
+template <typename Vec>
+inline memory to_float(const Vec &v)
+{
+    std::vector<float> t(v.begin(), v.end());
+    memory m = dev().malloc<float>(std::max<size_t>(t.size(), 1));
+    if (not t.empty()) m.copyFrom(t.data(), t.size() * sizeof(float));
+    return m;
+}
+
+// level-sorted element lists replace the per-point element / vertex / level / offset arrays of the reference
+// (subdomain.tpp:1603-1630)
+struct LevelList
+{
+    int level = 0;
+    int poly_degree = 1;
+    int dim = 3;
+    int num_elements = 0;
+    int first_offset = 0;                                                                      // the list is one run of elements, (N+1)^dim points apart from here
+    const double *G[NUM_GEOM_FACTS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // geometric factors of the list's first point
+    const double *D_hat = nullptr;                                                             // the degree's derivative table (its owner rewrites it in place: Domain::set_D_hat)
+    // float copies for the single-precision inner solve (Subdomain::prepare_single_precision); not allocated before
+    memory G32[NUM_GEOM_FACTS], D_hat32;
+    // affine elements (an option, set_affine_geometry): six numbers per element + the GLL weights stand for the factor arrays
+    bool affine = false;            // in use
+    double affine_deviation = -1.0; // largest relative deviation found (-1: not checked)
+    memory affine_c, affine_w, affine_c32, affine_w32;
+
+    size_t num_points() const { return (size_t)num_elements * (poly_degree + 1) * (poly_degree + 1) * (dim == 3 ? poly_degree + 1 : 1); }
+};
+
+// the matrix-core kernels exist in double only, for 3-D elements of degree 11..15
+template <typename Real>
+inline bool on_matrix_cores(const LevelList &ll, bool mfma_enabled)
+{
+    return std::is_same<Real, double>::value and mfma_enabled and ll.dim == 3 and ll.poly_degree >= 11 and ll.poly_degree <= 15;
+}
+
+// Au = A_L u on the points of the list (Au, u: the vectors the list's first_offset counts in).  workspace: three vectors
+// of the list's points for the two-launch form above degree 15.
+inline void apply_local(const LevelList &ll, double *Au, const double *u, const std::vector<memory> &workspace, bool mfma_enabled)
+{
+    void *stream = dev().stream;
+    const double points = (double)ll.num_points();
+    Au += ll.first_offset, u += ll.first_offset;
+    if (on_matrix_cores<double>(ll, mfma_enabled) and Au != u)
+    {
+        // high order: the six contractions on the fp64 matrix cores (tolerance-level parity, fdd_hip.h)
+        ProfileScope prof("mfma_stiffness_kernel", 64.0 * points);
+        FDD_CALL(fdd_stiffness_matrix_mfma(Au, u, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, stream));
+    }
+    else if (ll.dim == 3 and ll.poly_degree <= 15)
+    {
+        ProfileScope prof("fused_stiffness_kernel", 64.0 * points);
+        FDD_CALL(fdd_sub_stiffness_matrix(Au, u, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, stream));
+    }
+    else if (ll.dim == 2 and ll.poly_degree <= 15)
+    {
+        ProfileScope prof("fused_stiffness_2d_kernel", 40.0 * points);
+        FDD_CALL(fdd_stiffness_matrix_2d(Au, u, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, stream));
+    }
+    else
+    {
+        // degree above 15: the reference's two-launch form (domain.tpp:605-606) on the list
+        double *GDu[3] = {workspace[0].as<double>(), workspace[1].as<double>(), workspace[2].as<double>()};
+        FDD_CALL(fdd_dom_stiffness_matrix_1(GDu, u, ll.D_hat, ll.G, (int)ll.num_points(), ll.poly_degree, ll.dim, stream));
+        FDD_CALL(fdd_dom_stiffness_matrix_2(Au, GDu, ll.D_hat, (int)ll.num_points(), ll.poly_degree, ll.dim, stream));
+    }
+}
+
+namespace ops
+{
+// the gather entries per precision, as in precision_ops.hpp; q, point_index: at the list's first point
+inline void stiffness_gather(const LevelList &ll, double *q, const double *v, const double *scale_dev, const int *point_index, bool mfma, void *s)
+{
+    FDD_CALL((mfma ? fdd_stiffness_matrix_mfma_gather : fdd_sub_stiffness_matrix_gather_scaled)(q, v, scale_dev, point_index, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, s));
+}
+inline void stiffness_gather(const LevelList &ll, float *q, const float *v, const double *scale_dev, const int *point_index, bool, void *s)
+{
+    const float *G[NUM_GEOM_FACTS];
+    for (int g = 0; g < NUM_GEOM_FACTS; g++) G[g] = ll.G32[g].as<float>();
+    FDD_CALL(fdd_sub_stiffness_matrix_gather_scaled_f32(q, v, scale_dev, point_index, ll.D_hat32.as<float>(), G, nullptr, ll.num_elements, ll.poly_degree, s));
+}
+inline void stiffness_affine(const LevelList &ll, double *q, const double *v, const double *scale_dev, const int *point_index, bool mfma, void *s)
+{
+    FDD_CALL((mfma ? fdd_stiffness_matrix_mfma_affine : fdd_stiffness_matrix_affine)(q, v, scale_dev, point_index, ll.D_hat, ll.affine_c.as<double>(), ll.affine_w.as<double>(), nullptr, ll.num_elements, ll.poly_degree, s));
+}
+inline void stiffness_affine(const LevelList &ll, float *q, const float *v, const double *scale_dev, const int *point_index, bool, void *s)
+{
+    FDD_CALL(fdd_stiffness_matrix_affine_f32(q, v, scale_dev, point_index, ll.D_hat32.as<float>(), ll.affine_c32.as<float>(), ll.affine_w32.as<float>(), nullptr, ll.num_elements, ll.poly_degree, s));
+}
+}
+
+// q (points of the list) = A_L (Q (s v)): u[p] = s v[point_index[p]] on load (0 where the index is negative), s = *scale_dev
+// (null: 1).  q, point_index: the arrays the list's first_offset counts in; gathered_values: the length of v (the bytes it
+// adds to the count).  3-D lists of degree <= 15.
+template <typename Real>
+inline void apply_gather(const LevelList &ll, Real *q, const Real *v, const int *point_index, const double *scale_dev, int gathered_values, bool mfma_enabled)
+{
+    constexpr bool f32 = std::is_same<Real, float>::value;
+    const bool mfma = on_matrix_cores<Real>(ll, mfma_enabled);
+    const double points = (double)ll.num_points(), gathered = (double)sizeof(Real) * gathered_values;
+    q += ll.first_offset, point_index += ll.first_offset;
+    if (ll.affine)
+    {
+        ProfileScope prof(f32 ? "fused_stiffness_kernel<gather,f32,affine>" : mfma ? "mfma_stiffness_kernel<gather,affine>" : "fused_stiffness_kernel<gather,affine>", (f32 ? 8.0 : 12.0) * points + gathered);
+        ops::stiffness_affine(ll, q, v, scale_dev, point_index, mfma, dev().stream);
+        return;
+    }
+    ProfileScope prof(f32 ? "fused_stiffness_kernel<gather,f32>" : mfma ? "mfma_stiffness_kernel<gather>" : "fused_stiffness_kernel<gather>", (f32 ? 32.0 : 60.0) * points + gathered);
+    ops::stiffness_gather(ll, q, v, scale_dev, point_index, mfma, dev().stream);
+}
+
+// ---- affine elements (an option of this build; the reference always streams the six factor arrays) ----
+// Where an element is an affine image of the reference cube, the factors of a point are c_f(e) (w_i w_j) w_k: the kernel
+// forms them from six numbers per element and does not read 48 of its 64 bytes per point.  detect_affine checks the list's
+// OWN factor arrays against that form on the device, once (the deviation is kept), and says whether every element passes.
+// A list that cannot run the affine kernel (not 3-D, degree above 15, no elements) is not checked.
+constexpr double affine_tolerance = 64.0 * 2.220446049250313e-16;
+inline bool detect_affine(LevelList &ll)
+{
+    if (ll.dim != 3 or ll.poly_degree > 15 or ll.num_elements == 0) return false;
+    if (ll.affine_deviation < 0.0)
+    {
+        const int n = ll.poly_degree + 1;
+        std::vector<double> z(n), w(n), dev_hst(ll.num_elements);
+        gll::zwgll(z.data(), w.data(), n);
+        ll.affine_w = dev().malloc<double>(n);
+        ll.affine_w.copyFrom(w.data(), (size_t)n * sizeof(double));
+        ll.affine_c = dev().malloc<double>((size_t)ll.num_elements * NUM_GEOM_FACTS);
+        memory dev_dev = dev().malloc<double>(ll.num_elements);
+        FDD_CALL(fdd_stiffness_affine_detect(ll.affine_c.as<double>(), dev_dev.as<double>(), ll.G, nullptr, ll.affine_w.as<double>(), ll.num_elements, ll.poly_degree, dev().stream));
+        dev_dev.copyTo(dev_hst.data(), dev_hst.size() * sizeof(double));
+        dev_dev.free();
+        ll.affine_deviation = 0.0;
+        for (double x : dev_hst) ll.affine_deviation = (x == x) ? std::max(ll.affine_deviation, x) : 1.0;
+    }
+    return ll.affine_deviation <= affine_tolerance;
+}
+
+// the float copies of a checked list's element factors and weights, made when first asked for (the single-precision
+// inner solve reads them; a Domain never asks)
+inline void affine_float_copies(LevelList &ll)
+{
+    if (ll.affine_deviation < 0.0 or ll.affine_c32.ptr()) return;
+    const int n = ll.poly_degree + 1;
+    std::vector<double> z(n), w(n), c_hst((size_t)ll.num_elements * NUM_GEOM_FACTS);
+    gll::zwgll(z.data(), w.data(), n);
+    ll.affine_c.copyTo(c_hst.data(), c_hst.size() * sizeof(double));
+    ll.affine_c32 = to_float(c_hst);
+    ll.affine_w32 = to_float(w);
+}
+
+} // namespace fdd
+
+#endif

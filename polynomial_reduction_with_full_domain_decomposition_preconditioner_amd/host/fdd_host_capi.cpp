@@ -912,7 +912,7 @@ int fddh_problem_affine_info(fddh_problem *p, int *fine_domain_affine, int *sub_
         if (int rc = rank_check(p)) return rc;
         if (!p) return fail("null argument");
         Domain<SType> &dom = p->fine();
-        double worst = dom.affine_deviation;
+        double worst = dom.operator_list().affine_deviation;
         int lists = 0, affine = 0;
         if (p->subdomain)
             for (auto &ll : p->subdomain->operator_lists())
@@ -921,7 +921,7 @@ int fddh_problem_affine_info(fddh_problem *p, int *fine_domain_affine, int *sub_
                 if (ll.affine) affine++;
                 worst = std::max(worst, ll.affine_deviation);
             }
-        if (fine_domain_affine) *fine_domain_affine = dom.affine_geometry ? 1 : 0;
+        if (fine_domain_affine) *fine_domain_affine = dom.operator_list().affine ? 1 : 0;
         if (sub_lists_affine) *sub_lists_affine = affine;
         if (sub_lists) *sub_lists = lists;
         if (max_deviation) *max_deviation = worst;
@@ -1017,7 +1017,7 @@ int fddh_problem_set_flag(fddh_problem *p, const char *name, int value)
         else if (s == "affine_geometry")
         {
             // an option of this build: elements that are affine images of the reference cube do not stream their factor
-            // arrays (fdd_stiffness_matrix_affine); only where the mesh's own arrays have that form (fddh_problem_affine_info)
+            // arrays (element_operator.hpp); only where the mesh's own arrays have that form (fddh_problem_affine_info)
             for (auto &kv : p->domains) kv.second.set_affine_geometry(value != 0);
             if (p->subdomain) p->subdomain->set_affine_geometry(value != 0);
         }

@@ -41,7 +41,6 @@
 #define FDD_SUBDOMAIN_HPP
 
 #include <algorithm>
-#include <array>
 #include <cmath>
 #include <map>
 #include <unordered_map>
@@ -54,6 +53,7 @@
 #include "config.hpp"
 #include "csr_matrix.hpp"
 #include "domain.hpp"
+#include "element_operator.hpp"
 #include "gll.hpp"
 #include "gmres.hpp"
 #include "low_order.hpp"
@@ -74,25 +74,9 @@ struct Stiffness_Operator // subdomain.hpp:46-70
     CSR_Matrix<DType> P;
     CSR_Matrix<DType> Pt;
 
-    std::vector<fdd::memory> D_hat; // per level
     fdd::memory geom_fact[NUM_GEOM_FACTS];
-    const double *G_ptrs[NUM_GEOM_FACTS];
 
-    // level-sorted element lists replace the per-point element / vertex /
-    // level / offset arrays of the reference (subdomain.tpp:1603-1630)
-    struct LevelList
-    {
-        int level = 0;
-        int poly_degree = 1;
-        int num_elements = 0;
-        int first_offset = 0;    // the list is one run of elements, (N+1)^dim points apart from here
-        const double *G[NUM_GEOM_FACTS] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // geometric factors of the list's first point
-        // affine elements (an option, Subdomain::set_affine_geometry): six numbers per element + the GLL weights stand for the factor arrays
-        bool affine = false;
-        double affine_deviation = -1.0;
-        fdd::memory affine_c, affine_w, affine_c32, affine_w32;
-    };
-    std::vector<LevelList> level_lists;
+    std::vector<fdd::LevelList> level_lists; // one per polynomial level present (element_operator.hpp)
 };
 
 template <typename DType>
@@ -660,7 +644,7 @@ class Subdomain
         }
         jacobi_dinv = fdd::dev().malloc<DType>(inv.size());
         jacobi_dinv.copyFrom(inv.data(), inv.size() * sizeof(DType));
-        jacobi_dinv_f32 = to_float(inv);
+        jacobi_dinv_f32 = fdd::to_float(inv);
     }
 
     // the preconditioner slot of the reference-shaped loops with point-Jacobi in it: low_order_preconditioner
@@ -895,41 +879,27 @@ class Subdomain
     struct SinglePrecision
     {
         bool ready = false;
-        std::vector<std::array<fdd::memory, NUM_GEOM_FACTS>> G; // per level list
-        std::vector<fdd::memory> D_hat;                          // per level
         amg::Csr32 S, St, Asup;                                  // S_slave, St_slave, A_sup_reg
         fdd::memory q_pts, slaves, st_tmp;
     } sp;
-
-    template <typename Vec>
-    static fdd::memory to_float(const Vec &v)
-    {
-        std::vector<float> t(v.begin(), v.end());
-        fdd::memory m = fdd::dev().malloc<float>(std::max<size_t>(t.size(), 1));
-        if (not t.empty()) m.copyFrom(t.data(), t.size() * sizeof(float));
-        return m;
-    }
 
     void prepare_single_precision()
     {
         if (sp.ready) return;
         void *stream = fdd::dev().stream;
-        sp.G.resize(subdomain_operator.level_lists.size());
-        for (size_t k = 0; k < subdomain_operator.level_lists.size(); k++)
+        for (auto &ll : subdomain_operator.level_lists)
         {
-            auto &ll = subdomain_operator.level_lists[k];
-            const size_t np = (size_t)ll.num_elements * (size_t)std::lround(std::pow(ll.poly_degree + 1, dim));
+            const size_t np = ll.num_points();
             for (int g = 0; g < NUM_GEOM_FACTS; g++)
             {
-                sp.G[k][g] = fdd::dev().malloc<float>(std::max<size_t>(np, 1));
-                FDD_CALL(fdd_sub_copy_f32_f64(sp.G[k][g].template as<float>(), ll.G[g], (int)np, stream));
+                ll.G32[g] = fdd::dev().malloc<float>(std::max<size_t>(np, 1));
+                FDD_CALL(fdd_sub_copy_f32_f64(ll.G32[g].template as<float>(), ll.G[g], (int)np, stream));
             }
         }
-        sp.D_hat.resize(num_levels);
-        for (int l = 0; l < num_levels; l++) sp.D_hat[l] = to_float(D_hat[l].first);
+        for (auto &ll : subdomain_operator.level_lists) ll.D_hat32 = fdd::to_float(D_hat[ll.level].first);
         auto plan32 = [](amg::Csr32 &M32, CSR_Matrix<DType> &M) {
             if (M.num_rows == 0 or M.num_nnz == 0) return;
-            M32.val = to_float(M.val_hst);
+            M32.val = fdd::to_float(M.val_hst);
             FDD_CALL(fdd_csr_plan_create_f32(&M32.plan, M.ptr_hst.data(), M.num_rows, M.num_cols, M.num_nnz));
         };
         if (is_composite)
@@ -951,47 +921,12 @@ class Subdomain
         if (M32.plan) FDD_CALL(fdd_csr_plan_matvec_to_f32(M32.plan, y, nullptr, M.ptr.template as<int>(), M.col.template as<int>(), M32.val.template as<float>(), x, 1.0f, 0.0f, fdd::dev().stream));
     }
 
-    // q (points) = A_local (Q (s z~)), s = *scale_dev when given (a basis vector kept unnormalised): one launch per level list
-    void stiffness_from_dofs(double *q, const double *za, const double *scale_dev = nullptr)
+    // q (points) = A_local (Q (s z~)), s = *scale_dev when given (a basis vector kept unnormalised): one launch per level
+    // list, in double or on the float data of prepare_single_precision
+    template <typename Real>
+    void stiffness_from_dofs(Real *q, const Real *za, const double *scale_dev = nullptr)
     {
-        void *stream = fdd::dev().stream;
-        const int *point_dof = point_dof_dev.template as<int>();
-        for (auto &ll : subdomain_operator.level_lists)
-        {
-            const double n3 = (double)(ll.poly_degree + 1) * (ll.poly_degree + 1) * (ll.poly_degree + 1);
-            const double *D = subdomain_operator.D_hat[ll.level].template as<double>();
-            const bool mfma = ll.poly_degree >= 11 and mfma_stiffness;
-            if (ll.affine)
-            {
-                fdd::ProfileScope prof(mfma ? "mfma_stiffness_kernel<gather,affine>" : "fused_stiffness_kernel<gather,affine>", (12.0 * n3) * ll.num_elements + 8.0 * subdomain_operator.num_extended_dofs);
-                FDD_CALL((mfma ? fdd_stiffness_matrix_mfma_affine : fdd_stiffness_matrix_affine)(q + ll.first_offset, za, scale_dev, point_dof + ll.first_offset, D, ll.affine_c.template as<double>(), ll.affine_w.template as<double>(), nullptr, ll.num_elements, ll.poly_degree, stream));
-                continue;
-            }
-            fdd::ProfileScope prof(mfma ? "mfma_stiffness_kernel<gather>" : "fused_stiffness_kernel<gather>", (60.0 * n3) * ll.num_elements + 8.0 * subdomain_operator.num_extended_dofs);
-            FDD_CALL((mfma ? fdd_stiffness_matrix_mfma_gather : fdd_sub_stiffness_matrix_gather_scaled)(q + ll.first_offset, za, scale_dev, point_dof + ll.first_offset, D, ll.G, nullptr, ll.num_elements, ll.poly_degree, stream));
-        }
-    }
-    // the same on float data (prepare_single_precision): no MFMA form
-    void stiffness_from_dofs(float *q, const float *za, const double *scale_dev = nullptr)
-    {
-        void *stream = fdd::dev().stream;
-        const int *point_dof = point_dof_dev.template as<int>();
-        for (size_t k = 0; k < subdomain_operator.level_lists.size(); k++)
-        {
-            auto &ll = subdomain_operator.level_lists[k];
-            const double n3 = (double)(ll.poly_degree + 1) * (ll.poly_degree + 1) * (ll.poly_degree + 1);
-            const float *D = sp.D_hat[ll.level].template as<float>();
-            if (ll.affine)
-            {
-                fdd::ProfileScope prof("fused_stiffness_kernel<gather,f32,affine>", (8.0 * n3) * ll.num_elements + 4.0 * subdomain_operator.num_extended_dofs);
-                FDD_CALL(fdd_stiffness_matrix_affine_f32(q + ll.first_offset, za, scale_dev, point_dof + ll.first_offset, D, ll.affine_c32.template as<float>(), ll.affine_w32.template as<float>(), nullptr, ll.num_elements, ll.poly_degree, stream));
-                continue;
-            }
-            fdd::ProfileScope prof("fused_stiffness_kernel<gather,f32>", (32.0 * n3) * ll.num_elements + 4.0 * subdomain_operator.num_extended_dofs);
-            const float *Gs[NUM_GEOM_FACTS];
-            for (int g = 0; g < NUM_GEOM_FACTS; g++) Gs[g] = sp.G[k][g].template as<float>();
-            FDD_CALL(fdd_sub_stiffness_matrix_gather_scaled_f32(q + ll.first_offset, za, scale_dev, point_dof + ll.first_offset, D, Gs, nullptr, ll.num_elements, ll.poly_degree, stream));
-        }
+        for (auto &ll : subdomain_operator.level_lists) fdd::apply_gather(ll, q, za, point_dof_dev.template as<int>(), scale_dev, subdomain_operator.num_extended_dofs, mfma_stiffness);
     }
 
     // y (dofs) = [Qt A_L Q | A_sup] (s x~): the operator of the inner iteration on a dof vector.  x~ is one of the
@@ -1494,8 +1429,6 @@ class Subdomain
             PType &dl = domains[poly_degree[l]];
             D_hat[l].first = dl.D_hat_hst;
             D_hat[l].second = dl.D_hat;
-            subdomain_operator.D_hat.push_back(D_hat[l].second);
-            superdomain_operator.D_hat.push_back(D_hat[l].second);
         }
 
         is_composite = (fdd::comm().size > 1 and not block_local) or force_composite;
@@ -1549,11 +1482,7 @@ class Subdomain
         for (int w = 0; w < 3; w++) work_dev[w] = fdd::dev().malloc<DType>((size_t)total_level_points + (size_t)P + 16);
 
         // region geometry = own fine-level data (subdomain.tpp:667-699)
-        for (int g = 0; g < NUM_GEOM_FACTS; g++)
-        {
-            subdomain_operator.geom_fact[g] = domain.geom_fact[g];
-            subdomain_operator.G_ptrs[g] = domain.geom_fact[g].template as<double>();
-        }
+        for (int g = 0; g < NUM_GEOM_FACTS; g++) subdomain_operator.geom_fact[g] = domain.geom_fact[g];
 
         // dof numbering.  The reference ranks the global ids of the unmasked points
         // (subdomain.tpp:1151-1176); every numbering of those nodes gives the same
@@ -1619,12 +1548,14 @@ class Subdomain
 
         // one contiguous level-0 element list (subdomain.tpp:1603-1630 sorted by level)
         {
-            typename Stiffness_Operator<DType>::LevelList ll;
+            fdd::LevelList ll;
             ll.level = 0;
             ll.poly_degree = poly_degree[0];
+            ll.dim = dim;
+            ll.D_hat = D_hat[0].second.template as<double>();
             ll.num_elements = domain.num_local_elements;
             ll.first_offset = 0;
-            for (int g = 0; g < NUM_GEOM_FACTS; g++) ll.G[g] = subdomain_operator.G_ptrs[g];
+            for (int g = 0; g < NUM_GEOM_FACTS; g++) ll.G[g] = subdomain_operator.geom_fact[g].template as<double>();
             subdomain_operator.level_lists.push_back(ll);
         }
 
@@ -1725,7 +1656,6 @@ class Subdomain
             }
             else
                 subdomain_operator.geom_fact[g] = domain.geom_fact[g];
-            subdomain_operator.G_ptrs[g] = subdomain_operator.geom_fact[g].template as<double>();
         }
 
         setup_timing.lap("region geometry to the device");
@@ -1736,12 +1666,14 @@ class Subdomain
         {
             const int first = c.level_first_elem[l], count = c.level_num_elems[l];
             if (count == 0) continue;
-            typename Stiffness_Operator<DType>::LevelList ll;
+            fdd::LevelList ll;
             ll.level = l;
             ll.poly_degree = poly_degree[l];
+            ll.dim = dim;
+            ll.D_hat = D_hat[l].second.template as<double>();
             ll.num_elements = count;
             ll.first_offset = c.sub[first].offset;
-            for (int g = 0; g < NUM_GEOM_FACTS; g++) ll.G[g] = subdomain_operator.G_ptrs[g] + ll.first_offset;
+            for (int g = 0; g < NUM_GEOM_FACTS; g++) ll.G[g] = subdomain_operator.geom_fact[g].template as<double>() + ll.first_offset;
             subdomain_operator.level_lists.push_back(ll);
         }
 
@@ -1925,35 +1857,7 @@ class Subdomain
 
         superdomain_operator.A.multiply(Au_sup, u_sup); // empty: no-op
 
-        for (auto &ll : subdomain_operator.level_lists)
-        {
-            if (dim == 3 and ll.poly_degree >= 11 and ll.poly_degree <= 15 and mfma_stiffness and Au.ptr() != u.ptr())
-            {
-                const double n3 = (double)(ll.poly_degree + 1) * (ll.poly_degree + 1) * (ll.poly_degree + 1);
-                fdd::ProfileScope prof("mfma_stiffness_kernel", 64.0 * n3 * ll.num_elements);
-                FDD_CALL(fdd_stiffness_matrix_mfma(Au_sub_l.as<double>() + ll.first_offset, u_sub_l.as<double>() + ll.first_offset, subdomain_operator.D_hat[ll.level].template as<double>(), ll.G, nullptr, ll.num_elements, ll.poly_degree, fdd::dev().stream));
-            }
-            else if (dim == 3 and ll.poly_degree <= 15)
-            {
-                const double n3 = (double)(ll.poly_degree + 1) * (ll.poly_degree + 1) * (ll.poly_degree + 1);
-                fdd::ProfileScope prof("fused_stiffness_kernel", 64.0 * n3 * ll.num_elements);
-                FDD_CALL(fdd_sub_stiffness_matrix(Au_sub_l.as<double>() + ll.first_offset, u_sub_l.as<double>() + ll.first_offset, subdomain_operator.D_hat[ll.level].template as<double>(), ll.G, nullptr, ll.num_elements, ll.poly_degree, fdd::dev().stream));
-            }
-            else if (dim == 2 and ll.poly_degree <= 15)
-            {
-                const double n2 = (double)(ll.poly_degree + 1) * (ll.poly_degree + 1);
-                fdd::ProfileScope prof("fused_stiffness_2d_kernel", 40.0 * n2 * ll.num_elements);
-                FDD_CALL(fdd_stiffness_matrix_2d(Au_sub_l.as<double>() + ll.first_offset, u_sub_l.as<double>() + ll.first_offset, subdomain_operator.D_hat[ll.level].template as<double>(), ll.G, nullptr, ll.num_elements, ll.poly_degree, fdd::dev().stream));
-            }
-            else
-            {
-                // degree above 15: reference two-launch form on the list
-                const int npts = ll.num_elements * (int)std::lround(std::pow(ll.poly_degree + 1, dim));
-                double *GDu[3] = {work_dev[0].as<double>(), work_dev[1].as<double>(), work_dev[2].as<double>()};
-                FDD_CALL(fdd_dom_stiffness_matrix_1(GDu, u_sub_l.as<double>() + ll.first_offset, subdomain_operator.D_hat[ll.level].template as<double>(), ll.G, npts, ll.poly_degree, dim, fdd::dev().stream));
-                FDD_CALL(fdd_dom_stiffness_matrix_2(Au_sub_l.as<double>() + ll.first_offset, GDu, subdomain_operator.D_hat[ll.level].template as<double>(), npts, ll.poly_degree, dim, fdd::dev().stream));
-            }
-        }
+        for (auto &ll : subdomain_operator.level_lists) fdd::apply_local(ll, Au_sub_l.as<double>(), u_sub_l.as<double>(), work_dev, mfma_stiffness);
     }
 
     // subdomain.tpp:4161-4268
@@ -2181,46 +2085,18 @@ class Subdomain
     // Every level list of the region (own elements, rings at their reduced degrees) is checked on its own: a list whose
     // factor arrays all have the form c_f(e) (w_i w_j) w_k to rounding runs on the kernel that does not stream them.
     // Returns the number of lists switched over.
-    bool affine_geometry = false;
-    const std::vector<typename Stiffness_Operator<DType>::LevelList> &operator_lists() const { return subdomain_operator.level_lists; }
+    const std::vector<fdd::LevelList> &operator_lists() const { return subdomain_operator.level_lists; }
     int set_affine_geometry(bool on)
     {
         int count = 0;
-        affine_geometry = false;
         for (auto &ll : subdomain_operator.level_lists)
         {
-            if (not on or dim != 3 or ll.poly_degree > 15 or ll.num_elements == 0)
-            {
-                ll.affine = false;
-                continue;
-            }
-            if (ll.affine_deviation < 0.0)
-            {
-                const int n = ll.poly_degree + 1;
-                std::vector<double> z(n), w(n), dev_hst(ll.num_elements);
-                fdd::gll::zwgll(z.data(), w.data(), n);
-                ll.affine_w = fdd::dev().malloc<double>(n);
-                ll.affine_w.copyFrom(w.data(), (size_t)n * sizeof(double));
-                ll.affine_c = fdd::dev().malloc<double>((size_t)ll.num_elements * NUM_GEOM_FACTS);
-                fdd::memory dev_dev = fdd::dev().malloc<double>(ll.num_elements);
-                FDD_CALL(fdd_stiffness_affine_detect(ll.affine_c.template as<double>(), dev_dev.template as<double>(), ll.G, nullptr, ll.affine_w.template as<double>(), ll.num_elements, ll.poly_degree, fdd::dev().stream));
-                dev_dev.copyTo(dev_hst.data(), dev_hst.size() * sizeof(double));
-                dev_dev.free();
-                ll.affine_deviation = 0.0;
-                for (double x : dev_hst) ll.affine_deviation = (x == x) ? std::max(ll.affine_deviation, x) : 1.0;
-                // float copies for the single-precision inner solve
-                std::vector<double> c_hst((size_t)ll.num_elements * NUM_GEOM_FACTS);
-                ll.affine_c.copyTo(c_hst.data(), c_hst.size() * sizeof(double));
-                ll.affine_c32 = to_float(c_hst);
-                ll.affine_w32 = to_float(w);
-            }
-            ll.affine = ll.affine_deviation <= PType_affine_tolerance();
+            ll.affine = on and fdd::detect_affine(ll);
+            fdd::affine_float_copies(ll); // of a checked list, for the single-precision inner solve
             if (ll.affine) count++;
         }
-        affine_geometry = count > 0;
         return count;
     }
-    static constexpr double PType_affine_tolerance() { return 64.0 * 2.220446049250313e-16; }
 
     void gmres_assembled(fdd::memory &u_l, fdd::memory &f_l, bool print_history, bool use_relative)
     {
