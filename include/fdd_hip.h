@@ -157,6 +157,11 @@ int fdd_dom_inner_product_flexible(double *out, double *ws, const double *r_k, c
  * domain.okl:140-184 one iteration early; fdd_sub_inner_product(p, q) is what is left of that kernel):
  * out2 = {gamma_next, theta}.  Same bits as the two separate entries. */
 int fdd_dom_inner_product_flexible_gamma(double *out2, double *ws, const double *r_k, const double *r_kp1, const double *z_k, int num_points, void *stream);
+/* fdd_multi_lincomb_limited_dev on z_k's slice [slice_begin, slice_begin + slice_size) (v[k][d] belongs to node slice_begin + d;
+ * z_is_zero: the slice is not read) and fdd_dom_inner_product_flexible_gamma over all num_points, in ONE pass: the slice of
+ * z_k is formed, stored and entered into the two sums without being read back, and a v[0] that is r_kp1's own slice is read
+ * once.  z_k and out2 have the bits of the two separate entries. */
+int fdd_dom_lincomb_flexible_gamma(double *out2, double *ws, const double *r_k, const double *r_kp1, double *z_k, int num_points, int slice_begin, int slice_size, int z_is_zero, const double *coeffs_dev, const double *const *v, const double *v_scale_dev, const double *last_dev, int m, void *stream);
 int fdd_dom_inner_product(double *out, double *ws, const double *u_k, const double *v_k, const double *dirichlet_mask, int num_points, void *stream);                      /* domain.okl:235-264 */
 
 int fdd_dom_solution_and_residual_update(double *u_k, double *r_kp1, const double *r_k, const double *p_k, const double *q_k, double alpha_k, int num_points, void *stream); /* domain.okl:186-193, domain.tpp:978 */

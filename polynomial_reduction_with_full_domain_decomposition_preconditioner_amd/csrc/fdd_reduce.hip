@@ -264,6 +264,119 @@ struct FlexGammaOp
     }
 };
 
+// FlexGammaOp with z's slice [lo, hi) not read but FORMED on the way: z[i] = (z[i] or 0) + sum_{k <= *last} c_k (vs_k v_k[i - lo]),
+// the statement of MultiAxpyDevOp (fdd_blas1.hip), stored, and entered into the two sums where the stored value would
+// have been loaded.  The traversal (pairs, accumulators, expressions, their order) is FlexGammaOp's, so z and both sums
+// have the bits of fdd_multi_lincomb_limited_dev followed by fdd_dom_inner_product_flexible_gamma -- without writing z
+// and reading it back, and, where v_0 is r1's own slice (the inner solve's right-hand side read in place), without
+// reading that twice.
+template <int M>
+struct LincombFlexGammaOp
+{
+    static constexpr int NV = 2;
+    const double *r, *r1;
+    double *z;
+    long long lo, hi;
+    const double *v[M]; // v[k][i - lo] belongs to node i
+    const double *c;
+    const double *vs;   // optional per-vector scales
+    const double *last; // optional: only vectors 0..(int)*last enter
+    bool from_zero;     // z's slice is taken as 0 and not read
+    bool v0_is_r1;      // v[0] == r1 + lo: its entries are the ones this pass loads from r1 anyway
+    bool v_pairs;       // lo is even and every v[k] is 16-byte aligned: a pair inside the slice is one 16-byte load per vector
+
+    __device__ __forceinline__ double form(long long i, double r1_i, int kmax) const
+    {
+        double x = from_zero ? 0.0 : z[i];
+#pragma unroll
+        for (int k = 0; k < M; k++)
+            if (k <= kmax)
+            {
+                const double b = (k == 0 && v0_is_r1) ? r1_i : v[k][i - lo];
+                x = 1.0 * x + c[k] * (vs ? vs[k] * b : b);
+            }
+        z[i] = x;
+        return x;
+    }
+    __device__ void vec2(long long i, Acc<2> &a) const
+    {
+        const double2 a0 = ld2(r, i), a1 = ld2(r1, i);
+        const long long g = 2 * i;
+        const bool in0 = g >= lo && g < hi, in1 = g + 1 >= lo && g + 1 < hi;
+        double2 zz;
+        if (in0 && in1)
+        {
+            const int kmax = last ? (int)*last : M - 1;
+            zz = from_zero ? make_double2(0.0, 0.0) : ld2(z, i);
+#pragma unroll
+            for (int k = 0; k < M; k++)
+            {
+                if (k > kmax) break;
+                const double ck = c[k];
+                double2 b;
+                if (k == 0 && v0_is_r1)
+                    b = a1;
+                else if (v_pairs)
+                    b = ld2(v[k], (g - lo) >> 1);
+                else
+                    b = make_double2(__builtin_nontemporal_load(v[k] + (g - lo)), __builtin_nontemporal_load(v[k] + (g - lo) + 1));
+                if (vs)
+                {
+                    const double sk = vs[k];
+                    b.x = sk * b.x;
+                    b.y = sk * b.y;
+                }
+                zz.x = 1.0 * zz.x + ck * b.x;
+                zz.y = 1.0 * zz.y + ck * b.y;
+            }
+            reinterpret_cast<double2 *>(z)[i] = zz; // default policy: the direction update reads it next
+        }
+        else if (in0 || in1) // a pair astride a slice end: per component
+        {
+            const int kmax = last ? (int)*last : M - 1;
+            zz.x = in0 ? form(g, a1.x, kmax) : z[g];
+            zz.y = in1 ? form(g + 1, a1.y, kmax) : z[g + 1];
+        }
+        else
+            zz = ld2(z, i);
+        a.v[0] += zz.x * a1.x;
+        a.v[0] += zz.y * a1.y;
+        a.v[1] += (a1.x - a0.x) * zz.x;
+        a.v[1] += (a1.y - a0.y) * zz.y;
+    }
+    __device__ void one(long long i, Acc<2> &a) const
+    {
+        const double r1_i = r1[i];
+        const double zi = (i >= lo && i < hi) ? form(i, r1_i, last ? (int)*last : M - 1) : z[i];
+        a.v[0] += zi * r1_i;
+        a.v[1] += (r1_i - r[i]) * zi;
+    }
+};
+
+template <int M>
+int launch_lincomb_flex_gamma(double *out2, double *ws, const double *r, const double *r1, double *z, int n, int lo, int nd, bool from_zero, const double *c, const double *const *v, const double *vs, const double *last, void *stream)
+{
+    LincombFlexGammaOp<M> op;
+    op.r = r;
+    op.r1 = r1;
+    op.z = z;
+    op.lo = lo;
+    op.hi = (long long)lo + nd;
+    op.c = c;
+    op.vs = vs;
+    op.last = last;
+    op.from_zero = from_zero;
+    op.v0_is_r1 = v[0] == r1 + lo;
+    op.v_pairs = (lo & 1) == 0;
+    for (int k = 0; k < M; k++)
+    {
+        op.v[k] = v[k];
+        op.v_pairs = op.v_pairs && fdd_aligned16(v[k]);
+    }
+    // the same selection as fdd_dom_inner_product_flexible_gamma's: the pairing of the sums is that entry's
+    return launch_reduce(op, out2, ws, n, fdd_aligned16(r) && fdd_aligned16(r1) && fdd_aligned16(z), stream);
+}
+
 struct FlexWOp // subdomain.okl:229-258
 {
     static constexpr int NV = 1;
@@ -569,6 +682,28 @@ int fdd_dom_inner_product_flexible_gamma(double *out2, double *ws, const double 
     FDD_REQUIRE(out2 != nullptr && ws != nullptr && num_points >= 0);
     FDD_REQUIRE(num_points == 0 || (r_k != nullptr && r_kp1 != nullptr && z_k != nullptr));
     return launch_reduce(FlexGammaOp{r_k, r_kp1, z_k}, out2, ws, num_points, al2(r_k, r_kp1) && fdd_aligned16(z_k), stream);
+}
+
+int fdd_dom_lincomb_flexible_gamma(double *out2, double *ws, const double *r_k, const double *r_kp1, double *z_k, int num_points, int slice_begin, int slice_size, int z_is_zero, const double *coeffs_dev, const double *const *v, const double *v_scale_dev, const double *last_dev, int m, void *stream)
+{
+    FDD_REQUIRE(out2 != nullptr && ws != nullptr && num_points >= 0 && m >= 1 && m <= FDD_MULTI_MAX);
+    FDD_REQUIRE(slice_begin >= 0 && slice_size >= 0 && (long long)slice_begin + slice_size <= num_points);
+    FDD_REQUIRE(num_points == 0 || (r_k != nullptr && r_kp1 != nullptr && z_k != nullptr));
+    FDD_REQUIRE(slice_size == 0 || (coeffs_dev != nullptr && v != nullptr));
+    if (slice_size == 0) return launch_reduce(FlexGammaOp{r_k, r_kp1, z_k}, out2, ws, num_points, al2(r_k, r_kp1) && fdd_aligned16(z_k), stream);
+    for (int k = 0; k < m; k++) FDD_REQUIRE(v[k] != nullptr && v[k] != z_k + slice_begin);
+    const bool zero = z_is_zero != 0;
+    switch (m)
+    {
+    case 1: return launch_lincomb_flex_gamma<1>(out2, ws, r_k, r_kp1, z_k, num_points, slice_begin, slice_size, zero, coeffs_dev, v, v_scale_dev, last_dev, stream);
+    case 2: return launch_lincomb_flex_gamma<2>(out2, ws, r_k, r_kp1, z_k, num_points, slice_begin, slice_size, zero, coeffs_dev, v, v_scale_dev, last_dev, stream);
+    case 3: return launch_lincomb_flex_gamma<3>(out2, ws, r_k, r_kp1, z_k, num_points, slice_begin, slice_size, zero, coeffs_dev, v, v_scale_dev, last_dev, stream);
+    case 4: return launch_lincomb_flex_gamma<4>(out2, ws, r_k, r_kp1, z_k, num_points, slice_begin, slice_size, zero, coeffs_dev, v, v_scale_dev, last_dev, stream);
+    case 5: return launch_lincomb_flex_gamma<5>(out2, ws, r_k, r_kp1, z_k, num_points, slice_begin, slice_size, zero, coeffs_dev, v, v_scale_dev, last_dev, stream);
+    case 6: return launch_lincomb_flex_gamma<6>(out2, ws, r_k, r_kp1, z_k, num_points, slice_begin, slice_size, zero, coeffs_dev, v, v_scale_dev, last_dev, stream);
+    case 7: return launch_lincomb_flex_gamma<7>(out2, ws, r_k, r_kp1, z_k, num_points, slice_begin, slice_size, zero, coeffs_dev, v, v_scale_dev, last_dev, stream);
+    default: return launch_lincomb_flex_gamma<8>(out2, ws, r_k, r_kp1, z_k, num_points, slice_begin, slice_size, zero, coeffs_dev, v, v_scale_dev, last_dev, stream);
+    }
 }
 
 int fdd_sub_inner_product(double *out, double *ws, const double *u, const double *v, int num_values, void *stream)

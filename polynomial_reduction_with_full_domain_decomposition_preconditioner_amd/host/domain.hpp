@@ -40,8 +40,26 @@
 // The "no preconditioner" plugin: Domain's solvers take any type with these
 // two methods (domain.tpp:639-642); with use_preconditioner == false neither
 // is called.
+namespace fdd
+{
+// An inner solve's final update u~ = sum_k y_k (s_k v_k), described instead of launched: a caller that reads u~ next in a
+// pass of its own sets defer_final_update around one gmres_dofs call and, where pending_update.active comes back set,
+// owes the update (Domain::fcg_nodes_step_direction forms it inside the flexible dot's pass).
+struct PendingUpdate
+{
+    bool active = false;
+    double *q = nullptr;
+    int q_is_zero = 1;
+    const double *coeffs_dev = nullptr, *scales_dev = nullptr, *last_dev = nullptr;
+    std::vector<const double *> v;
+    int n = 0;
+};
+} // namespace fdd
+
 struct NoPreconditioner
 {
+    bool defer_final_update = false;
+    fdd::PendingUpdate pending_update; // never active
     void flexible_conjugate_gradient(fdd::memory &, fdd::memory &) {}
     void generalized_minimum_residual(fdd::memory &, fdd::memory &) {}
     // the surface Domain's assembled flexible CG looks at (never taken: can_assemble() is false)
@@ -452,6 +470,7 @@ class Domain
     bool early_gamma = true;      // device scalars: the flexible dot also forms the next iteration's gamma = <z, r+> (same bits; the projection kernel is left with <p, q>)
     bool gamma_on_device = false;
     int gamma_slot = 0; // where the current gamma sits in `scalars`
+    bool fused_update_flexible_dot = true; // one rank, z~ written in place, early_gamma: the inner solve's final update of z~ is formed inside the flexible dot's pass (same bits; 0: a kernel of its own in front of the dot)
     bool unit_stitch_in_place = true; // stitching weights of the dof slice all exactly 1 (one rank): the inner solve writes z~ in place (0: the multiplication by the ones, the reference's sequence)
     bool mfma_stiffness = true; // N >= 11: stiffness on the fp64 matrix cores (not bit-identical; 1e-12 tolerance)
     DType tolerance = 1.0e-07;
@@ -1041,8 +1060,10 @@ class Domain
     // z~ = M^-1 r^ and the stitching (domain.tpp:639-645, 697-706)
     // rhs_norm2: device address of |rn's dof slice|^2 if the caller has just formed it from this very rn (node_norm_enqueue's
     // return value), else nullptr
+    // may_defer_update: the caller reads zn next in a pass of its own and can form the inner solve's final update there: where
+    // the inner solve agrees (subdomain.pending_update.active on return) zn's dof slice is still to be written
     template <typename PType>
-    void precondition_nodes(fdd::memory &zn, fdd::memory &rn, PType &subdomain, const double *rhs_norm2 = nullptr)
+    void precondition_nodes(fdd::memory &zn, fdd::memory &rn, PType &subdomain, const double *rhs_norm2 = nullptr, bool may_defer_update = false)
     {
         void *stream = fdd::dev().stream;
         if (use_preconditioner)
@@ -1067,7 +1088,11 @@ class Domain
                 if (stitch_is_one and unit_stitch_in_place)
                 {
                     fdd::memory z_slice = zn.slice(dof_shift, nodes_sub_dofs);
+                    // nothing stands between the in-place update and the caller's pass: one rank, no exchange below
+                    // (an update still owed from an earlier solve is an error there: gmres_dofs refuses to start)
+                    subdomain.defer_final_update = may_defer_update and fdd::comm().size == 1;
                     subdomain.gmres_dofs(z_slice, f_slice);
+                    subdomain.defer_final_update = false;
                 }
                 else
                     subdomain.gmres_dofs(sub_u, f_slice);
@@ -1200,7 +1225,9 @@ class Domain
     {
         const int nn = num_local_nodes;
         DType theta_k;
-        precondition_nodes(nz, nr1, subdomain, pending_rhs_norm2); // nr1 is untouched since its norm was enqueued (fcg_nodes_step_residual)
+        // the inner solve's final update of z~ may ride in the flexible dot's pass below, which reads z~ first
+        const bool fuse_update = fused_update_flexible_dot and device_scalars and early_gamma and &fdd_dom_lincomb_flexible_gamma != nullptr;
+        precondition_nodes(nz, nr1, subdomain, pending_rhs_norm2, fuse_update); // nr1 is untouched since its norm was enqueued (fcg_nodes_step_residual)
         pending_rhs_norm2 = nullptr;
         if (device_scalars)
         {
@@ -1214,7 +1241,24 @@ class Domain
                 // the norm's two parts in scalars[4..5], so that one all-reduce still carries all four
                 const int next = (gamma_slot == 2) ? 6 : 2;
                 theta_at = next + 1;
-                FDD_CALL(fdd_dom_inner_product_flexible_gamma(scalars.as<double>() + next, reduce_ws.as<double>(), nr.as<double>(), nr1.as<double>(), nz.as<double>(), nn, fdd::dev().stream));
+                if (use_preconditioner and subdomain.pending_update.active)
+                {
+                    // z~'s dof slice is formed here, by the statement the inner solve would have launched, and enters the two
+                    // sums without a trip through memory; the inner right-hand side (r+'s slice) is read once for both
+                    auto &pu = subdomain.pending_update;
+                    pu.active = false;
+                    if (pu.q != nz.as<double>() + dof_shift or pu.n > nodes_sub_dofs)
+                    {
+                        fprintf(stderr, "ERROR: the inner solve's deferred update is not the one of z~'s dof slice\n");
+                        exit(EXIT_FAILURE);
+                    }
+                    const bool rhs_shared = pu.v[0] == nr1.as<double>() + dof_shift;
+                    fdd::ProfileScope prof("reduce_vec2_kernel<LincombFlexGamma>", 8.0 * (2.0 * nn + (nn - pu.n) + (double)pu.n * ((double)pu.v.size() + (rhs_shared ? 0 : 1))));
+                    FDD_CALL(fdd_dom_lincomb_flexible_gamma(scalars.as<double>() + next, reduce_ws.as<double>(), nr.as<double>(), nr1.as<double>(), nz.as<double>(), nn, dof_shift, pu.n, pu.q_is_zero, pu.coeffs_dev, pu.v.data(),
+                                                            pu.scales_dev, pu.last_dev, (int)pu.v.size(), fdd::dev().stream));
+                }
+                else
+                    FDD_CALL(fdd_dom_inner_product_flexible_gamma(scalars.as<double>() + next, reduce_ws.as<double>(), nr.as<double>(), nr1.as<double>(), nz.as<double>(), nn, fdd::dev().stream));
                 if (fdd::comm().size > 1)
                 {
                     if (norm_reduce_pending)

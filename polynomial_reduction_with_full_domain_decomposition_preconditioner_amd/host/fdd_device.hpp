@@ -40,6 +40,8 @@
 #pragma weak fdd_amg_setup_lattice_interp_fill
 #pragma weak fdd_amg_setup_lattice_coarse_points
 #pragma weak fdd_amg_setup_memory_info
+// likewise the fused update-and-dot entry: without it the update and the dot stay two launches (Domain::fcg_nodes_step_direction)
+#pragma weak fdd_dom_lincomb_flexible_gamma
 
 namespace fdd
 {

@@ -981,6 +981,10 @@ int fddh_problem_set_flag(fddh_problem *p, const char *name, int value)
         {
             for (auto &kv : p->domains) kv.second.unit_stitch_in_place = value != 0;
         }
+        else if (s == "fused_update_flexible_dot")
+        {
+            for (auto &kv : p->domains) kv.second.fused_update_flexible_dot = value != 0;
+        }
         else if (s == "lazy_steps")
         {
             for (auto &kv : p->domains) kv.second.lazy_steps = value != 0;

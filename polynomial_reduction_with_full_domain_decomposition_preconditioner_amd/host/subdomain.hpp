@@ -1347,6 +1347,10 @@ class Subdomain
     bool skip_last_basis_store = true;    // device GMRES: the last Arnoldi step of a cycle forms the norm of its vector without storing it (nobody reads it)
     bool lazy_history = false;            // single-cycle inner solves do not synchronise at all; finish_history() fetches on demand
     bool history_pending = false;
+    // the lazy single cycle's final update, described instead of launched (fdd::PendingUpdate, domain.hpp): only the
+    // double-precision device GMRES on its lazy branch defers; every other solve leaves `active` clear and has updated u~
+    bool defer_final_update = false;
+    fdd::PendingUpdate pending_update;
 
     // residual_history of the last lazy solve (one blocking read of the device state)
     void finish_history()
@@ -2259,7 +2263,21 @@ class Subdomain
                 // device state and the host does not synchronise at all (finish_history() reads the state later)
                 const double *last_dev = nullptr;
                 FDD_CALL(fdd_gmres_last_column(st, &last_dev));
-                ops::lincomb_limited(ua, 1, y_dev, ptrs.data(), scales, last_dev, m, nd, stream);
+                bool deferred = false;
+                if constexpr (not f32)
+                    if (defer_final_update)
+                    {
+                        // the caller launches it, inside the pass that reads u~ first (Domain::fcg_nodes_step_direction)
+                        pending_update.active = deferred = true;
+                        pending_update.q = ua;
+                        pending_update.q_is_zero = 1;
+                        pending_update.coeffs_dev = y_dev;
+                        pending_update.scales_dev = scales;
+                        pending_update.last_dev = last_dev;
+                        pending_update.v.assign(ptrs.begin(), ptrs.begin() + m);
+                        pending_update.n = nd;
+                    }
+                if (not deferred) ops::lincomb_limited(ua, 1, y_dev, ptrs.data(), scales, last_dev, m, nd, stream);
                 history_pending = true;
                 iter = std::min(m, max_iterations); // the steps enqueued; an early stop is only known to the device
                 break;
@@ -2294,6 +2312,12 @@ class Subdomain
     // the solve itself, dof vectors in and out (callers that already hold assembled data skip Qt / Q)
     void gmres_dofs(fdd::memory &ua, fdd::memory &fa, bool print_history = true, bool use_relative = false)
     {
+        if (pending_update.active)
+        {
+            // a caller asked for the last solve's final update to be deferred and never formed it: that u~ was never written
+            fprintf(stderr, "ERROR: an inner solve's deferred final update was dropped\n");
+            exit(EXIT_FAILURE);
+        }
         if (device_bookkeeping and num_vectors <= FDD_MULTI_MAX)
         {
             gmres_dofs_device(ua, fa, print_history, use_relative);
