@@ -296,6 +296,23 @@ int fdd_multi_axpy_norm2_dev(double *out, double *ws, double *y, const double *c
 int fdd_vector_scaling_rsqrt_dev(double *au, const double *norm2_dev, const double *u, int n, void *stream);
 int fdd_multi_axpy_dev(double *q, const double *coeffs_dev, const double *const *v, int m, int n, void *stream); /* fdd_multi_axpy, coefficients in device memory */
 
+/* ---- successive-right-hand-side projection (csrc/fdd_projection.hip; an addition of this build, the reference has no
+ * counterpart): the passes around an outer solve that starts from the best approximation in the span of earlier solutions
+ * (host/projection.hpp).  The basis X and its images AX are one slab each: rows of `ld` doubles, ld even and >= n, base
+ * 16-byte aligned; the entries take (base, ld, K) with K <= FDD_PROJECTION_MAX rows in use.  `ws` is the common reduction
+ * workspace (fdd_reduce_workspace_doubles()).  Sums are deterministic for given n and K; their order is the kernels' own.
+ *   dots   out[k] = sum_i X[k][i] * f[i], k < K, one pass over f.  K == 0 writes nothing, n == 0 writes zeros.
+ *   apply  x = x_in + sign_x * sum_k c_k X[k],  b = b_in + sign_b * sum_k c_k AX[k]  (each sum in the order k = 0 .. K - 1,
+ *          as fdd_multi_axpy_dev forms it), coefficients read from device memory, one pass: 2K + 2 streams read, 2 written.
+ *          nu2_out != NULL: *nu2_out = sum_i x[i] * b[i] of the values just formed.  x_in == NULL: taken as 0 and not read.
+ *          x_in == x and b_in == b are allowed (in place).  The start of a solve uses sign_x = +1, sign_b = -1
+ *          (x0 = X alpha, f' = f - AX alpha); the basis update uses -1, -1 on (delta, A delta) with the dot.
+ *   store  Xk = x / sqrt(*nu2_dev), AXk = b / sqrt(*nu2_dev)  (the factor of fdd_vector_scaling_rsqrt_dev) */
+#define FDD_PROJECTION_MAX 16
+int fdd_projection_dots(double *out, double *ws, const double *X, int ld, int K, const double *f, int n, void *stream);
+int fdd_projection_apply(double *x, double *b, double *nu2_out, double *ws, const double *x_in, const double *b_in, const double *X, const double *AX, int ld, int K, const double *coeffs_dev, double sign_x, double sign_b, int n, void *stream);
+int fdd_projection_store(double *Xk, double *AXk, const double *x, const double *b, const double *nu2_dev, int n, void *stream);
+
 /* Scalar bookkeeping of one restart cycle of the inner flexible GMRES(m) (subdomain.tpp:4396-4477) on the device:
  * Hessenberg column + Givens rotations + residual recurrence + stopping tests per step, back-substitution at the
  * end, so that a cycle is enqueued without a host round trip per step.  `state` = fdd_gmres_state_bytes() bytes of

@@ -186,6 +186,10 @@ int fddh_problem_set_options(fddh_problem *p, int max_iterations, double toleran
  *                              that is not comes back to the host loop), bit-identical to the host build.  Applies to
  *                              fddh_problem_amg_build and to the build on first use; a composite region builds on the host
  *                              and says so.  Fails, naming the entry, when the kernel library lacks an fdd_amg_setup_* entry.
+ *   "fused_projection"         1 (default where the kernel library has the fdd_projection_* entries): the passes of the
+ *                              projection (below) are single launches of csrc/fdd_projection.hip; 0: they are composed from
+ *                              the multi-vector entries (the only form on a library without them; setting 1 there fails,
+ *                              naming the entry).  Same sums, same element-wise bits; the basis stays.
  *   "amg_num_vcycles" 1..16, "amg_cheby_order" 1..4 (subdomain.hpp:236-237), "amg_matrix_free_transfer",
  *   "preconditioner_precision" 64 / 32 (the whole inner solve)
  *
@@ -203,6 +207,9 @@ int fddh_problem_set_options(fddh_problem *p, int max_iterations, double toleran
  *                              that sets them in that other order is refused: not covered by the walks
  *   "preconditioner_precision" sets the V-cycle's precision too once a hierarchy exists: set "amg_precision" after it
  *   "amg_precision" / "preconditioner_precision" 32 need a Chebyshev order of at least 2 at the time they are set
+ * What changes the operator under a live projection basis (fddh_problem_projection_configure) empties the basis, since its
+ * stored images A X would no longer be the operator's: fddh_problem_set_D_hat (any level) and the flag "affine_geometry".
+ * Solver options and the other flags leave it alone.
  * Refused on a live problem, with an error that names the option, the option keeping its value (the closed list of
  * refused transitions; tests/reconfigure_walks.py REFUSED matches it line for line):
  *   "amg_cheby_order"          a new value once a hierarchy has been handed in (fddh_problem_amg_add_level): its
@@ -259,6 +266,26 @@ int fddh_problem_solve(fddh_problem *p, int solver_id, const double *f, double *
 /* The same solve with the right-hand side already uploaded and the clock around the device work only (stream
  * synchronised before and after): what bench.py reports as time to tolerance.  u may be NULL. */
 int fddh_problem_solve_timed(fddh_problem *p, int solver_id, const double *f, double *u, double *history, int history_cap, int *num_history, int *num_iterations, double *seconds);
+
+/* Successive-right-hand-side projection (an addition of this build; the reference starts every solve from u = 0): a few
+ * earlier solutions are kept as an A-orthonormal basis X with their images A_L X, the next solve starts from the A-norm best
+ * approximation x0 = X (X^T f), the Krylov solver removes only what is left, and the correction is folded back into the
+ * basis (host/projection.hpp).  Opt-in: with capacity 0, the default, nothing changes anywhere.
+ *   configure  capacity 0: off, the slabs are freed; 1..16 (FDD_PROJECTION_MAX): slabs allocated, the basis empty.  Another
+ *              value is an error naming the argument, and nothing changes.
+ *   clear      empties the basis (capacity and slabs stay)
+ *   info       capacity, vectors in the basis, restarts so far (a full basis restarts from the solution alone)
+ *   basis      host copies of X_k and A_L X_k, k < size (either may be NULL)
+ * fddh_problem_solve_projected is fddh_problem_solve from that start value: it stops at the same |r| <= tolerance |f|, a start
+ * value that already meets it takes 0 iterations (history = { |f - A x0| }), f = 0 gives u = 0 and stores nothing, and with
+ * capacity 0 it is the plain solve.  Every solver option and flag of the plain solve applies.  Collective on several ranks.
+ * projection[4] = { |f|, |f - A x0|, basis size used, basis size afterwards } (may be NULL); seconds (may be NULL): the device
+ * time as fddh_problem_solve_timed takes it, the projection's own passes included. */
+int fddh_problem_projection_configure(fddh_problem *p, int capacity);
+int fddh_problem_projection_clear(fddh_problem *p);
+int fddh_problem_projection_info(const fddh_problem *p, int *capacity, int *size, long long *restarts);
+int fddh_problem_projection_basis(const fddh_problem *p, int k, double *x, double *Ax);
+int fddh_problem_solve_projected(fddh_problem *p, int solver_id, const double *f, double *u, double *history, int history_cap, int *num_history, int *num_iterations, double *projection, double *seconds);
 
 /* Subdomain (preconditioner) operations; type 0 = flexible_conjugate_gradient,
  * 1 = generalized_minimum_residual */

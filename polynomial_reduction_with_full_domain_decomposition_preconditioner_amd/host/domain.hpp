@@ -35,6 +35,7 @@
 #include "gll.hpp"
 #include "gmres.hpp"
 #include "math.hpp"
+#include "projection.hpp"
 #include "timer.hpp"
 
 // The "no preconditioner" plugin: Domain's solvers take any type with these
@@ -1729,6 +1730,130 @@ class Domain
             }
         };
         num_iterations = fdd::gmres_solve(gmres_scalars, num_vectors, outer_gmres_control(use_relative), space, residual_history, print_outer_step);
+    }
+
+    // ------------------------------------------------------------------
+    // Successive-right-hand-side projection (projection.hpp; an addition of this build).  Off (capacity 0) unless
+    // configured; the solvers above are called unchanged.
+    // ------------------------------------------------------------------
+    fdd::Projection projection;
+
+    // The outer solve (solver_id 0: flexible CG, 1: GMRES) of A u = f started from x0 = X (X^T f), the best approximation
+    // in the A-norm the basis holds; f is overwritten by f' = f - AX (X^T f).  It stops where the plain solve stops,
+    // |r| <= tolerance |f| -- the solvers take that as an absolute tolerance for the duration of the call, and a start
+    // value that already meets it costs no iteration (they always take a step before they test).  The correction delta
+    // is then A-orthogonalised against the basis in one classical Gram-Schmidt sweep and stored with its image; a full
+    // basis restarts from the solution alone, as Nek5000 does.  proj = {|f|, |f'|, rows used, rows afterwards}.
+    // Dots are plain sums over the local points (the basis is continuous and zero on Dirichlet points, f and the images
+    // are unassembled), summed over the ranks; every rank takes the same branches because they hang on those sums.
+    template <typename PType>
+    void solve_projected(fdd::memory &u, fdd::memory &f, PType &subdomain, int solver_id, DType proj[4])
+    {
+        fdd::Projection &pj = projection;
+        void *stream = fdd::dev().stream;
+        const int n = num_local_points, K = pj.size;
+        const bool multi = fdd::comm().size > 1;
+        double *ws = reduce_ws.as<double>(), *c = pj.c.as<double>();
+        auto solve = [&](fdd::memory &out, bool use_relative) {
+            if (solver_id == 0)
+                flexible_conjugate_gradient(out, f, subdomain, use_relative);
+            else
+                generalized_minimum_residual(out, f, subdomain, use_relative);
+        };
+        auto nothing_to_iterate = [&](DType r_norm) {
+            residual_history.assign(1, r_norm);
+            num_iterations = 0;
+        };
+
+        DType b_norm, r_norm;
+        residual_norm(b_norm, f);
+        proj[0] = proj[1] = b_norm;
+        proj[2] = proj[3] = K;
+        if (b_norm == 0.0)
+        {
+            FDD_CALL(fdd_set_to_value(u.as<double>(), 0.0, n, 0, stream));
+            nothing_to_iterate(0.0);
+            return;
+        }
+        if (pj.capacity == 0) // off: the plain solve, nothing stored
+        {
+            solve(u, true);
+            return;
+        }
+
+        r_norm = b_norm;
+        if (K > 0)
+        {
+            pj.dots(c, ws, f.as<double>());
+            if (multi) fdd::comm().allreduce_sum(c, K);
+            pj.apply(pj.x0.as<double>(), f.as<double>(), nullptr, ws, nullptr, f.as<double>(), c, 1.0, -1.0);
+            residual_norm(r_norm, f);
+            proj[1] = r_norm;
+        }
+        if (r_norm <= tolerance * b_norm)
+        {
+            if (K > 0)
+                u.copyFrom(pj.x0, (size_t)n * sizeof(DType));
+            else
+                FDD_CALL(fdd_set_to_value(u.as<double>(), 0.0, n, 0, stream));
+            nothing_to_iterate(r_norm);
+            return;
+        }
+
+        // delta: into u itself while there is nothing to add it to
+        fdd::memory &delta = (K > 0) ? pj.d : u;
+        const DType relative_tolerance = tolerance;
+        tolerance = relative_tolerance * b_norm;
+        solve(delta, false);
+        tolerance = relative_tolerance;
+        if (K > 0) FDD_CALL(fdd_vector_vector_addition(u.as<double>(), 1.0, pj.x0.as<double>(), 1.0, delta.as<double>(), n, stream));
+
+        // the basis update: w = A_L delta, e0 = <delta, w>, beta = X^T w, (delta, w) -= (X, AX) beta, nu2 = <delta, w>
+        stiffness_matrix(pj.w, delta);
+        double *e0_dev = c + K, *nu2_dev = c + K + 1;
+        DType e0, nu2;
+        FDD_CALL(fdd_sub_inner_product(e0_dev, ws, delta.as<double>(), pj.w.as<double>(), n, stream));
+        if (K > 0)
+        {
+            pj.dots(c, ws, pj.w.as<double>());
+            if (multi) fdd::comm().allreduce_sum(c, K + 1);
+            pj.apply(delta.as<double>(), pj.w.as<double>(), nu2_dev, ws, delta.as<double>(), pj.w.as<double>(), c, -1.0, -1.0);
+            if (multi) fdd::comm().allreduce_sum(nu2_dev, 1);
+            DType both[2];
+            pj.c.slice(K, 2).copyTo(both, sizeof(both));
+            e0 = both[0];
+            nu2 = both[1];
+        }
+        else
+        {
+            if (multi) fdd::comm().allreduce_sum(e0_dev, 1);
+            pj.c.slice(K, 1).copyTo(&e0, sizeof(DType));
+            nu2 = e0;
+            nu2_dev = e0_dev;
+        }
+        // below 2^-52 e0 what is left of delta is the rounding of the sweep
+        if (not std::isfinite(nu2) or not(nu2 > std::ldexp(e0, -52))) return;
+        if (K == pj.capacity)
+        {
+            // full: start again from the solution alone, u / |u|_A (one more operator application)
+            pj.restarts++;
+            pj.size = 0;
+            stiffness_matrix(pj.w, u);
+            FDD_CALL(fdd_sub_inner_product(c, ws, u.as<double>(), pj.w.as<double>(), n, stream));
+            if (multi) fdd::comm().allreduce_sum(c, 1);
+            pj.c.copyTo(&nu2, sizeof(DType));
+            if (std::isfinite(nu2) and nu2 > 0.0)
+            {
+                pj.store(0, u.as<double>(), pj.w.as<double>(), c);
+                pj.size = 1;
+            }
+        }
+        else
+        {
+            pj.store(K, delta.as<double>(), pj.w.as<double>(), nu2_dev);
+            pj.size = K + 1;
+        }
+        proj[3] = pj.size;
     }
 };
 

@@ -615,6 +615,7 @@ int fddh_problem_destroy(fddh_problem *p)
         p->c.free();
         p->sa.free();
         p->sb.free();
+        p->fine().projection.release();
         delete p;
         return 0;
     }
@@ -850,6 +851,7 @@ int fddh_problem_set_D_hat(fddh_problem *p, int level, const double *D_hat, int 
         if (!p || !D_hat || level < 0 || level >= (int)p->degrees.size()) return fail("bad argument");
         if (n != p->degrees[level] + 1) return fail("D_hat of level %d is %d x %d", level, p->degrees[level] + 1, p->degrees[level] + 1);
         p->domains[p->degrees[level]].set_D_hat(D_hat, n);
+        p->fine().projection.clear(); // the basis and its images belong to the operator as it was
         return 0;
     }
     catch (const std::exception &e)
@@ -1024,6 +1026,15 @@ int fddh_problem_set_flag(fddh_problem *p, const char *name, int value)
             // arrays (element_operator.hpp); only where the mesh's own arrays have that form (fddh_problem_affine_info)
             for (auto &kv : p->domains) kv.second.set_affine_geometry(value != 0);
             if (p->subdomain) p->subdomain->set_affine_geometry(value != 0);
+            p->fine().projection.clear(); // the operator's arithmetic changes under the stored images
+        }
+        else if (s == "fused_projection")
+        {
+            // the projection's passes as single launches of csrc/fdd_projection.hip (default where the kernel library has
+            // them) or composed from the multi-vector entries (projection.hpp); the basis stays
+            if (value != 0)
+                if (const char *missing = fdd::missing_projection_entry()) return fail("fused_projection needs %s, which the loaded kernel library does not export", missing);
+            p->fine().projection.fused = value != 0;
         }
         else if (s == "amg_graph")
         {
@@ -1460,6 +1471,116 @@ int fddh_problem_solve_timed(fddh_problem *p, int solver_id, const double *f, do
             for (int i = 0; i < nh && i < history_cap; i++) history[i] = d.residual_history[i];
         if (num_history) *num_history = nh;
         if (num_iterations) *num_iterations = d.num_iterations;
+        return 0;
+    }
+    catch (const std::exception &e)
+    {
+        return fail("%s", e.what());
+    }
+}
+
+int fddh_problem_projection_configure(fddh_problem *p, int capacity)
+{
+    try
+    {
+        if (int rc = rank_check(p)) return rc;
+        if (!p) return fail("null argument");
+        if (capacity < 0 || capacity > FDD_PROJECTION_MAX) return fail("capacity %d: the projection basis holds 0 (off) to %d vectors", capacity, FDD_PROJECTION_MAX);
+        Domain<SType> &d = p->fine();
+        d.projection.configure(capacity, d.num_local_points);
+        return 0;
+    }
+    catch (const std::exception &e)
+    {
+        return fail("%s", e.what());
+    }
+}
+
+int fddh_problem_projection_clear(fddh_problem *p)
+{
+    try
+    {
+        if (int rc = rank_check(p)) return rc;
+        if (!p) return fail("null argument");
+        p->fine().projection.clear();
+        return 0;
+    }
+    catch (const std::exception &e)
+    {
+        return fail("%s", e.what());
+    }
+}
+
+int fddh_problem_projection_info(const fddh_problem *p, int *capacity, int *size, long long *restarts)
+{
+    try
+    {
+        if (int rc = rank_check(p)) return rc;
+        if (!p) return fail("null argument");
+        const fdd::Projection &pj = p->fine().projection;
+        if (capacity) *capacity = pj.capacity;
+        if (size) *size = pj.size;
+        if (restarts) *restarts = pj.restarts;
+        return 0;
+    }
+    catch (const std::exception &e)
+    {
+        return fail("%s", e.what());
+    }
+}
+
+int fddh_problem_projection_basis(const fddh_problem *p, int k, double *x, double *Ax)
+{
+    try
+    {
+        if (int rc = rank_check(p)) return rc;
+        if (!p) return fail("null argument");
+        const fdd::Projection &pj = p->fine().projection;
+        if (k < 0 || k >= pj.size) return fail("k = %d: the projection basis holds %d vectors", k, pj.size);
+        const size_t bytes = (size_t)pj.n * sizeof(double);
+        if (x && bytes) pj.X.slice((size_t)k * pj.ld, pj.n).copyTo(x, bytes);
+        if (Ax && bytes) pj.AX.slice((size_t)k * pj.ld, pj.n).copyTo(Ax, bytes);
+        return 0;
+    }
+    catch (const std::exception &e)
+    {
+        return fail("%s", e.what());
+    }
+}
+
+int fddh_problem_solve_projected(fddh_problem *p, int solver_id, const double *f, double *u, double *history, int history_cap, int *num_history, int *num_iterations, double *projection, double *seconds)
+{
+    try
+    {
+        if (int rc = rank_check(p)) return rc;
+        if (!p || !f || !u) return fail("null argument");
+        Domain<SType> &d = p->fine();
+        const size_t bytes = (size_t)d.num_local_points * sizeof(double);
+        p->a.copyFrom(f, bytes);
+        std::chrono::steady_clock::time_point t0;
+        if (seconds)
+        {
+            fdd::dev().finish();
+            fdd::comm().barrier();
+            t0 = std::chrono::steady_clock::now();
+        }
+        double proj[4];
+        if (p->subdomain)
+            d.solve_projected(p->b, p->a, *p->subdomain, solver_id, proj);
+        else
+            d.solve_projected(p->b, p->a, p->none, solver_id, proj);
+        if (seconds)
+        {
+            fdd::dev().finish();
+            *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        }
+        p->b.copyTo(u, bytes);
+        const int nh = (int)d.residual_history.size();
+        if (history)
+            for (int i = 0; i < nh && i < history_cap; i++) history[i] = d.residual_history[i];
+        if (num_history) *num_history = nh;
+        if (num_iterations) *num_iterations = d.num_iterations;
+        if (projection) memcpy(projection, proj, sizeof(proj));
         return 0;
     }
     catch (const std::exception &e)

@@ -452,6 +452,40 @@ class Problem:
         _H().call("fddh_problem_solve_timed", self.h, 0 if method == "fcg" else 1, _dp(np.ascontiguousarray(f)), _dp(u), _dp(hist), cap, ctypes.byref(nh), ctypes.byref(its), ctypes.byref(sec))
         return its.value, hist[: min(nh.value, cap)].copy(), sec.value
 
+    # --- successive-right-hand-side projection (an addition of this build, include/fdd_host.h) ---
+    def projection(self, capacity):
+        """Keep up to `capacity` (1..16) earlier solutions as a start-value basis for solve_projected; 0 switches it off."""
+        _H().call("fddh_problem_projection_configure", self.h, int(capacity))
+
+    def projection_clear(self):
+        _H().call("fddh_problem_projection_clear", self.h)
+
+    def projection_info(self):
+        cap, size, restarts = ctypes.c_int(), ctypes.c_int(), ctypes.c_longlong()
+        _H().call("fddh_problem_projection_info", self.h, ctypes.byref(cap), ctypes.byref(size), ctypes.byref(restarts))
+        return {"capacity": cap.value, "size": size.value, "restarts": restarts.value}
+
+    def projection_basis(self, k):
+        """(X_k, A_L X_k) of the basis, k < size"""
+        x, ax = np.zeros(self.n), np.zeros(self.n)
+        _H().call("fddh_problem_projection_basis", self.h, int(k), _dp(x), _dp(ax))
+        return x, ax
+
+    def solve_projected(self, f, method="fcg", timed=False):
+        """(u, iterations, history, proj): solve() started from the projection of f onto the basis, which then takes the
+        correction in.  proj = [|f|, |f - A x0|, basis size used, basis size afterwards] and, timed, a fifth entry: the
+        device seconds as solve_timed takes them, the projection included."""
+        u = np.zeros(self.n)
+        cap = 4096
+        hist = np.zeros(cap)
+        nh, its, sec = ctypes.c_int(), ctypes.c_int(), ctypes.c_double()
+        proj = np.zeros(4)
+        _H().call("fddh_problem_solve_projected", self.h, 0 if method == "fcg" else 1, _dp(np.ascontiguousarray(f, dtype=np.float64)), _dp(u), _dp(hist), cap, ctypes.byref(nh), ctypes.byref(its), _dp(proj),
+                  ctypes.byref(sec) if timed else None)
+        if timed:
+            proj = np.append(proj, sec.value)
+        return u, its.value, hist[: min(nh.value, cap)].copy(), proj
+
     def precond_apply(self, r, method="gmres"):
         z = np.zeros(self.n)
         hist = np.zeros(64)
