@@ -2,7 +2,9 @@
 // Replaces csr_matrix.okl (multiply / multiply_range / multiply_weight) and
 // the cusparseSpMV call of AMG/csr_matrix.cpp:129-131.
 //
-// Two kernels, both HBM-bound (12 B per non-zero + 12 B per row + x once):
+// A host-side plan (fdd_csr_plan) looks at a matrix's row lengths once and picks the kernel its entries run on;
+// plan_launch below states that choice once, for both value types.  The kernels, all HBM-bound (12 B per non-zero +
+// 12 B per row + x once), each described where it is defined:
 //
 //  * csr_row_kernel: one lane per row, the reference's own mapping.  With
 //    <= ~4 non-zeros per row (the boolean gather/scatter matrices Q, Qt,
@@ -19,6 +21,17 @@
 //    order, so the result is bit-identical to the thread-per-row kernel.
 //    A row longer than a block is reduced by the whole workgroup (shuffle
 //    tree; order differs).
+//
+//  * csr_one_per_row_kernel (and its pipelined form): rows of exactly one entry, the scatter matrices Q.
+//
+//  * csr_short_pipelined_kernel: the row blocks of a short-row plan walked by persistent workgroups with three
+//    blocks in flight; the sums of csr_block_kernel.
+//
+//  * sell_kernel (with sell_probe_kernel / sell_fill_kernel, which build its arrays): a sliced-ELL copy of a
+//    matrix with short, even rows (the AMG levels), one lane per row without LDS.
+//
+//  * dssum_block_kernel, gather_norm2_block_kernel (+ fold_partials_kernel): the gather-scatter of a boolean
+//    gather matrix Qt, and its weighted norm, on the plan's row blocks.
 #include <type_traits>
 
 #include "fdd_common.h"
@@ -37,17 +50,41 @@ constexpr int kBlock = 256;
 constexpr int kBlockNnzMax = FDD_CSR_BLOCK_NNZ;
 constexpr int kBlockNnzSmall = FDD_CSR_BLOCK_NNZ / 2;
 
+// The two compile-time choices of the kernels below, each made in one place: f is called with the choice as a
+// std::integral_constant.  The non-zeros per row block of a plan (fdd_csr_plan::block_nnz) ...
+template <typename F>
+void with_block_nnz(int block_nnz, F &&f)
+{
+    if (block_nnz == kBlockNnzSmall)
+        f(std::integral_constant<int, kBlockNnzSmall>{});
+    else
+        f(std::integral_constant<int, kBlockNnzMax>{});
+}
+// ... and whether every stored value is 1.0.  kMayBeUnit = false: there is no UNIT instantiation to choose (csr_block_kernel on float: a plan of the f32 entries
+// never has unit values, fdd_csr_plan_set_unit_values)
+template <bool kMayBeUnit = true, typename F>
+void with_unit(bool unit, F &&f)
+{
+    if constexpr (kMayBeUnit)
+    {
+        if (unit) return f(std::true_type{});
+    }
+    f(std::false_type{});
+}
+
 // Row epilogues.  apply() = operand() + finish(): the block kernel loads the operands of all its rows up front
 // (unconditionally, with its other loads) and finishes once the row sums are known.
 // kFreeOrder: the entry stands in for cusparseSpMV (AMG/csr_matrix.cpp:129-131), whose summation order is not
 // defined: wide rows may be summed by several lanes.  The csr_matrix.okl replacements keep the column order.
-struct EpiPlain
+template <typename T>
+struct EpiPlainT // T = float: the gather of the float preconditioner (subdomain.okl's kernels instantiated with DType = float)
 {
     static constexpr bool kFreeOrder = false;
-    typedef double Opnd;
-    __device__ double operand(int, const double *) const { return 0.0; }
-    __device__ double finish(double s, double, int) const { return s; }
+    typedef T Opnd;
+    __device__ T operand(int, const T *) const { return T(0); }
+    __device__ T finish(T s, T, int) const { return s; }
 };
+typedef EpiPlainT<double> EpiPlain;
 struct EpiWeight
 {
     static constexpr bool kFreeOrder = false;
@@ -371,60 +408,6 @@ __global__ __launch_bounds__(kBlock) void csr_block_kernel(T *__restrict__ Au, c
     }
 }
 
-// The gather half (MODE 1, no weight) on float vectors: the single-precision preconditioner's Qt (subdomain.okl's kernels
-// instantiated with DType = float).  Same staging, the row sums in column order in IEEE single.
-template <int kBlockNnz>
-__global__ __launch_bounds__(kBlock) void gather_block_f32_kernel(float *__restrict__ t, const int *__restrict__ Qt_ptr, const int *__restrict__ Qt_col, const float *__restrict__ u, const int *__restrict__ row_blocks, int block_first, int row_lo, int row_hi, int xcd_window)
-{
-    __shared__ float x[kBlockNnz];
-    __shared__ int sp[kBlockNnz + 1];
-    constexpr int kIts = kBlockNnz / kBlock;
-    // Row blocks follow the node order, which follows the element order: a block gathers the low-face points of the NEXT
-    // element(s), whose 64-byte sectors hold seven more points that the next block gathers.  In XCD-windowed order that
-    // next block runs on the same XCD (fdd_common.h).
-    const int b = block_first + fdd_xcd_windowed_block(blockIdx.x, gridDim.x, xcd_window);
-    const int r0 = row_blocks[b] > row_lo ? row_blocks[b] : row_lo;
-    const int r1 = row_blocks[b + 1] < row_hi ? row_blocks[b + 1] : row_hi;
-    if (r1 <= r0) return;
-    const int nrows = r1 - r0;
-    const int base = Qt_ptr[r0];
-    const int nnz = Qt_ptr[r1] - base;
-    int c[kIts], rp[kIts];
-#pragma unroll
-    for (int it = 0; it < kIts; it++)
-    {
-        const int k = threadIdx.x + it * kBlock;
-        c[it] = __builtin_nontemporal_load(Qt_col + ((k < nnz) ? base + k : ((nnz > 0) ? base : 0)));
-        rp[it] = Qt_ptr[r0 + ((k < nrows) ? k : 0) + 1];
-    }
-#pragma unroll
-    for (int it = 0; it < kIts; it++)
-    {
-        const int k = threadIdx.x + it * kBlock;
-        const float v = u[c[it]];
-        if (k < nnz) x[k] = v;
-    }
-    if (threadIdx.x == 0) sp[0] = 0;
-#pragma unroll
-    for (int it = 0; it < kIts; it++)
-    {
-        const int r = threadIdx.x + it * kBlock;
-        if (r < nrows) sp[r + 1] = rp[it] - base;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < kIts; it++)
-    {
-        const int r = threadIdx.x + it * kBlock;
-        if (r < nrows)
-        {
-            float s = 0.0f;
-            for (int j = sp[r]; j < sp[r + 1]; j++) s += x[j];
-            t[r0 + r] = s;
-        }
-    }
-}
-
 template <typename Epi>
 int launch_rows(double *Au, const int *A_ptr, const int *A_col, const double *A_val, const double *u, const Epi &epi, int row_start, int row_end, void *stream, bool unit_values = false)
 {
@@ -538,30 +521,21 @@ int launch_one_per_row(double *Au, const int *A_col, const double *A_val, const 
         const int ntiles = (n + kBlock * NPT - 1) / (kBlock * NPT);
         int g = per_cu * FDD_CU_COUNT;
         if (g > ntiles) g = ntiles;
-        if (unit_values)
-            hipLaunchKernelGGL((csr_one_per_row_pipelined_kernel<Epi, true, NPT>), dim3(g), dim3(kBlock), 0, fdd_stream(stream), Au, A_col, A_val, u, epi, n, ntiles, 32);
-        else
-            hipLaunchKernelGGL((csr_one_per_row_pipelined_kernel<Epi, false, NPT>), dim3(g), dim3(kBlock), 0, fdd_stream(stream), Au, A_col, A_val, u, epi, n, ntiles, 32);
+        with_unit(unit_values, [&](auto unit) {
+            hipLaunchKernelGGL((csr_one_per_row_pipelined_kernel<Epi, decltype(unit)::value, NPT>), dim3(g), dim3(kBlock), 0, fdd_stream(stream), Au, A_col, A_val, u, epi, n, ntiles, 32);
+        });
         FDD_LAUNCH_CHECK();
         return 0;
     }
     static const int npt = fdd_env_int("FDD_TUNE_CSR_ONE_NPT", 4);
     const int per = kBlock * ((npt == 8) ? 8 : 4);
     const int grid = (n + per - 1) / per;
-    if (unit_values)
-    {
+    with_unit(unit_values, [&](auto unit) {
         if (npt == 8)
-            hipLaunchKernelGGL((csr_one_per_row_kernel<Epi, true, 8>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, A_col, A_val, u, epi, n);
+            hipLaunchKernelGGL((csr_one_per_row_kernel<Epi, decltype(unit)::value, 8>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, A_col, A_val, u, epi, n);
         else
-            hipLaunchKernelGGL((csr_one_per_row_kernel<Epi, true, 4>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, A_col, A_val, u, epi, n);
-    }
-    else
-    {
-        if (npt == 8)
-            hipLaunchKernelGGL((csr_one_per_row_kernel<Epi, false, 8>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, A_col, A_val, u, epi, n);
-        else
-            hipLaunchKernelGGL((csr_one_per_row_kernel<Epi, false, 4>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, A_col, A_val, u, epi, n);
-    }
+            hipLaunchKernelGGL((csr_one_per_row_kernel<Epi, decltype(unit)::value, 4>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, A_col, A_val, u, epi, n);
+    });
     FDD_LAUNCH_CHECK();
     return 0;
 }
@@ -578,17 +552,22 @@ int launch_one_per_row(double *Au, const int *A_col, const double *A_val, const 
 // phase), only the LDS phase sees the raggedness.  Rows [row_lo, row_hi) only:
 // the boundary prefix of a multi-rank Domain is gathered / scattered apart.
 // MODE 0: gather + scatter, 1: gather only, 2: scatter only (s read from t).
+// T: double, and float for the gather half without weight alone (MODE 1): the single-precision preconditioner's Qt
+// (subdomain.okl's kernels instantiated with DType = float), the row sums in column order in IEEE single.
 // ---------------------------------------------------------------------------
-template <int MODE, bool WEIGHT, bool MASK, int kBlockNnz>
-__global__ __launch_bounds__(kBlock) void dssum_block_kernel(double *out, double *__restrict__ t, const int *__restrict__ Qt_ptr, const int *__restrict__ Qt_col, const double *u, const double *__restrict__ node_weight, const double *__restrict__ point_mask, const int *__restrict__ row_blocks, int block_first, int row_lo, int row_hi, int xcd_window)
+template <typename T, int MODE, bool WEIGHT, bool MASK, int kBlockNnz>
+__global__ __launch_bounds__(kBlock) void dssum_block_kernel(T *out, T *__restrict__ t, const int *__restrict__ Qt_ptr, const int *__restrict__ Qt_col, const T *u, const T *__restrict__ node_weight, const T *__restrict__ point_mask, const int *__restrict__ row_blocks, int block_first, int row_lo, int row_hi, int xcd_window)
 {
-    __shared__ double x[kBlockNnz];
+    __shared__ T x[kBlockNnz];
     constexpr int kBlockRowsMax = kBlockNnz;
     __shared__ int sp[kBlockRowsMax + 1]; // the block's row pointers, relative to its first non-zero
     constexpr int kIts = kBlockNnz / kBlock;
     constexpr int kRowIts = kBlockRowsMax / kBlock;
 
-    const int b = block_first + fdd_xcd_windowed_block(blockIdx.x, gridDim.x, xcd_window); // as in gather_block_f32_kernel
+    // Row blocks follow the node order, which follows the element order: a block gathers the low-face points of the NEXT
+    // element(s), whose 64-byte sectors hold seven more points that the next block gathers.  In XCD-windowed order that
+    // next block runs on the same XCD (fdd_common.h).
+    const int b = block_first + fdd_xcd_windowed_block(blockIdx.x, gridDim.x, xcd_window);
     const int r0 = row_blocks[b] > row_lo ? row_blocks[b] : row_lo;
     const int r1 = row_blocks[b + 1] < row_hi ? row_blocks[b + 1] : row_hi;
     if (r1 <= r0) return;
@@ -600,7 +579,7 @@ __global__ __launch_bounds__(kBlock) void dssum_block_kernel(double *out, double
     // entry 0): a load under a lane predicate compiles to a branch with its own s_waitcnt, and the loads
     // of a lane then complete one HBM latency after the other instead of together.
     int c[kIts], rp[kRowIts];
-    double wn[kRowIts], tv[kRowIts];
+    T wn[kRowIts], tv[kRowIts];
 #pragma unroll
     for (int it = 0; it < kIts; it++)
     {
@@ -622,8 +601,8 @@ __global__ __launch_bounds__(kBlock) void dssum_block_kernel(double *out, double
         for (int it = 0; it < kIts; it++)
         {
             const int k = threadIdx.x + it * kBlock;
-            const double v = u[c[it]];
-            if (k < nnz) x[k] = 1.0 * v;
+            const T v = u[c[it]];
+            if (k < nnz) x[k] = T(1) * v;
         }
     }
     if (threadIdx.x == 0) sp[0] = 0;
@@ -642,10 +621,10 @@ __global__ __launch_bounds__(kBlock) void dssum_block_kernel(double *out, double
         if (r < nrows)
         {
             const int j0 = sp[r], j1 = sp[r + 1];
-            double s;
+            T s;
             if (MODE != 2)
             {
-                s = 0.0;
+                s = T(0);
                 for (int j = j0; j < j1; j++) s += x[j];
                 if (WEIGHT) s = s * wn[it];
                 if (t) t[r0 + r] = s;
@@ -662,7 +641,7 @@ __global__ __launch_bounds__(kBlock) void dssum_block_kernel(double *out, double
     if (MODE != 1)
     {
         __syncthreads();
-        double mk[kIts];
+        T mk[kIts];
         if (MASK)
         {
 #pragma unroll
@@ -674,7 +653,7 @@ __global__ __launch_bounds__(kBlock) void dssum_block_kernel(double *out, double
             const int k = threadIdx.x + it * kBlock;
             if (k < nnz)
             {
-                const double v = 0.0 + 1.0 * x[k];
+                const T v = T(0) + T(1) * x[k];
                 out[c[it]] = MASK ? v * mk[it] : v;
             }
         }
@@ -811,14 +790,6 @@ __global__ __launch_bounds__(kBlock) void csr_short_pipelined_kernel(T *__restri
         }
     }
 }
-
-// the gather of the float preconditioner (subdomain.okl's kernels instantiated with DType = float): no epilogue
-struct EpiPlainF32
-{
-    typedef float Opnd;
-    __device__ float operand(int, const float *) const { return 0.0f; }
-    __device__ float finish(float s, float, int) const { return s; }
-};
 
 // workgroups per CU of the persistent gather (0: one row block per workgroup, the forms above).  C2's Qt: 72 us with one
 // block per workgroup, 73.6 / 59.1 / 62.9 / 63.3 us with 2 / 4 / 6 / 8 persistent workgroups per CU
@@ -1090,35 +1061,48 @@ struct fdd_csr_plan
     int sell_compact_slices = 0;
 };
 
+// the row blocks [first, last) that overlap the rows [row_lo, row_hi); last <= first: none
+struct BlockRange
+{
+    int first, last;
+    bool empty() const { return last <= first; }
+};
+static BlockRange blocks_overlapping(const fdd_csr_plan *plan, int row_lo, int row_hi)
+{
+    const std::vector<int> &rb = plan->row_blocks_host;
+    const int first = (int)(std::upper_bound(rb.begin(), rb.end(), row_lo) - rb.begin()) - 1;
+    const int last = (int)(std::lower_bound(rb.begin(), rb.end(), row_hi) - rb.begin());
+    return BlockRange{std::max(first, 0), std::min(last, plan->num_blocks)};
+}
+
+// FDD_TUNE_DSSUM_XCD_WINDOW: consecutive row blocks per XCD inside a window of 8x as many (0: dispatch order), for the
+// gather / scatter forms on row blocks.  C2's Qt gather: L2 fetches 415 -> 356 MB per launch (1.23 -> 1.05 x the 338 MB
+// it must move; profiles/r04_pmc_traffic_c2*.json), 74 -> 72 us
+static int dssum_xcd_window()
+{
+    static const int v = fdd_env_int("FDD_TUNE_DSSUM_XCD_WINDOW", 32);
+    return v;
+}
+
+// whether a plan's row blocks run on the persistent pipelined kernel (short rows only, none longer than a block)
+static bool short_pipelined_applies(const fdd_csr_plan *plan)
+{
+    return gather_pipelined_per_cu() > 0 && plan->block_nnz == kBlockNnzSmall && plan->block_meta_dev != nullptr && !plan->has_long_rows;
+}
+
 // y[rows of blocks first..last) in [row_lo, row_hi)] = epi(A x) on a short-row plan: the persistent pipelined kernel.
 // false: not applicable (the caller takes the one-block-per-workgroup form)
 template <typename T, typename Epi>
-static bool launch_short_pipelined(const fdd_csr_plan *plan, T *y, const int *ptr, const int *col, const T *val, const T *x, const Epi &epi, int first, int last, int row_lo, int row_hi, hipStream_t s, bool unit)
+static bool launch_short_pipelined(const fdd_csr_plan *plan, T *y, const int *ptr, const int *col, const T *val, const T *x, const Epi &epi, BlockRange blocks, int row_lo, int row_hi, hipStream_t s, bool unit)
 {
-    const int per_cu = gather_pipelined_per_cu();
-    if (per_cu <= 0 || plan->block_nnz != kBlockNnzSmall || plan->block_meta_dev == nullptr || plan->has_long_rows) return false;
-    const int nblocks = last - first;
+    if (!short_pipelined_applies(plan)) return false;
+    const int nblocks = blocks.last - blocks.first;
     if (nblocks <= 0) return true;
-    int g = per_cu * FDD_CU_COUNT;
-    if (g > nblocks) g = nblocks;
-    static const int xcd_window = fdd_env_int("FDD_TUNE_DSSUM_XCD_WINDOW", 32);
-    if (unit)
-        hipLaunchKernelGGL((csr_short_pipelined_kernel<T, Epi, true, kBlockNnzSmall>), dim3(g), dim3(kBlock), 0, s, y, ptr, col, val, x, epi, plan->block_meta_dev, first, nblocks, row_lo, row_hi, xcd_window);
-    else
-        hipLaunchKernelGGL((csr_short_pipelined_kernel<T, Epi, false, kBlockNnzSmall>), dim3(g), dim3(kBlock), 0, s, y, ptr, col, val, x, epi, plan->block_meta_dev, first, nblocks, row_lo, row_hi, xcd_window);
+    const int g = std::min(gather_pipelined_per_cu() * FDD_CU_COUNT, nblocks);
+    with_unit(unit, [&](auto u1) {
+        hipLaunchKernelGGL((csr_short_pipelined_kernel<T, Epi, decltype(u1)::value, kBlockNnzSmall>), dim3(g), dim3(kBlock), 0, s, y, ptr, col, val, x, epi, plan->block_meta_dev, blocks.first, nblocks, row_lo, row_hi, dssum_xcd_window());
+    });
     return true;
-}
-
-// the boolean gather t = Qt u (no values read, no epilogue)
-static bool launch_gather_pipelined(const fdd_csr_plan *plan, double *t, const int *ptr, const int *col, const double *u, int first, int last, int row_lo, int row_hi, hipStream_t s)
-{
-    if (!plan->unit_values) return false;
-    return launch_short_pipelined<double, EpiPlain>(plan, t, ptr, col, nullptr, u, EpiPlain{}, first, last, row_lo, row_hi, s, true);
-}
-static bool launch_gather_pipelined(const fdd_csr_plan *plan, float *t, const int *ptr, const int *col, const float *u, int first, int last, int row_lo, int row_hi, hipStream_t s)
-{
-    if (!plan->unit_values) return false;
-    return launch_short_pipelined<float, EpiPlainF32>(plan, t, ptr, col, nullptr, u, EpiPlainF32{}, first, last, row_lo, row_hi, s, true);
 }
 
 template <typename T, typename Epi>
@@ -1132,62 +1116,87 @@ static int sell_launch(const fdd_csr_plan *plan, T *y, const T *x, const Epi &ep
     return 0;
 }
 
-#define FDD_CSR_BLOCK(EPI, UNIT, ...)                                                          \
-    do                                                                                         \
-    {                                                                                          \
-        if (plan->block_nnz == kBlockNnzSmall)                                                 \
-            hipLaunchKernelGGL((csr_block_kernel<double, EPI, UNIT, kBlockNnzSmall>), __VA_ARGS__);    \
-        else                                                                                   \
-            hipLaunchKernelGGL((csr_block_kernel<double, EPI, UNIT, kBlockNnzMax>), __VA_ARGS__);      \
-    } while (0)
-
-template <typename Epi>
-static int plan_launch(const fdd_csr_plan *plan, double *y, const int *A_ptr, const int *A_col, const double *A_val, const double *x, const Epi &epi, void *stream)
+// Which kernel runs y = epi(A x) on a plan, for both value types and every SpMV entry of a plan:
+//   the sliced-ELL copy where one is attached (kUseSell = false: an entry that does not look at it) | rows of exactly one
+//   entry | one lane per row | the persistent pipelined kernel on short rows | one row block per workgroup.
+// The two lane-per-row rungs are the plans of kind 0, which the f32 entries never see (fdd_csr_plan_create_f32 makes row
+// blocks whatever the row lengths: the Float = float V-cycle, AMG/config.hpp:4).
+template <typename T, bool kUseSell = true, typename Epi>
+static int plan_launch(const fdd_csr_plan *plan, T *y, const int *A_ptr, const int *A_col, const T *A_val, const T *x, const Epi &epi, void *stream)
 {
-    if (plan->value_bytes != 8)
+    constexpr bool kDouble = std::is_same<T, double>::value;
+    if (kDouble ? plan->value_bytes != 8 : (plan->kind != 1 || plan->value_bytes != 4))
     {
-        fdd_set_error("fp64 SpMV on a plan of fdd_csr_plan_create_f32");
+        fdd_set_error("%s", kDouble ? "fp64 SpMV on a plan of fdd_csr_plan_create_f32" : "f32 SpMV: not a plan of fdd_csr_plan_create_f32");
         return 1;
     }
-    if (plan->sell_slices > 0) return sell_launch<double, Epi>(plan, y, x, epi, stream);
-    if (plan->one_per_row) return launch_one_per_row(y, A_col, A_val, x, epi, plan->num_rows, stream, plan->unit_values != 0);
-    if (plan->kind == 0) return launch_rows(y, A_ptr, A_col, A_val, x, epi, 0, plan->num_rows, stream, plan->unit_values != 0);
-    const dim3 grid(plan->num_blocks), block(kBlock);
-    static const int split_rows = fdd_env_int("FDD_TUNE_CSR_SPLIT_ROWS", 1);
-    if (launch_short_pipelined<double, Epi>(plan, y, A_ptr, A_col, A_val, x, epi, 0, plan->num_blocks, 0, plan->num_rows, fdd_stream(stream), plan->unit_values != 0))
+    if constexpr (kUseSell)
     {
-        // a short-row plan (the gather Qt, the hanging-point rows, the AMG's interpolators): the persistent pipelined
-        // kernel, the same products and sums in the same order
+        if (plan->sell_slices > 0) return sell_launch<T, Epi>(plan, y, x, epi, stream);
     }
-    else if (plan->unit_values)
-        FDD_CSR_BLOCK(Epi, true, grid, block, 0, fdd_stream(stream), y, A_ptr, A_col, A_val, x, epi, plan->row_blocks_dev, plan->xcd_chunked, split_rows);
-    else
-        FDD_CSR_BLOCK(Epi, false, grid, block, 0, fdd_stream(stream), y, A_ptr, A_col, A_val, x, epi, plan->row_blocks_dev, plan->xcd_chunked, split_rows);
+    const bool unit = plan->unit_values != 0;
+    if constexpr (kDouble)
+    {
+        if (plan->one_per_row) return launch_one_per_row(y, A_col, A_val, x, epi, plan->num_rows, stream, unit);
+        if (plan->kind == 0) return launch_rows(y, A_ptr, A_col, A_val, x, epi, 0, plan->num_rows, stream, unit);
+    }
+    hipStream_t s = fdd_stream(stream);
+    static const int split_rows = fdd_env_int("FDD_TUNE_CSR_SPLIT_ROWS", 1); // read by the free-order epilogues only
+    // short rows (the gather Qt, the hanging-point rows, the AMG's interpolators) on the persistent pipelined kernel: the
+    // same products and sums in the same order
+    if (!launch_short_pipelined<T, Epi>(plan, y, A_ptr, A_col, A_val, x, epi, BlockRange{0, plan->num_blocks}, 0, plan->num_rows, s, unit))
+        with_block_nnz(plan->block_nnz, [&](auto nnz) {
+            with_unit<kDouble>(unit, [&](auto u1) {
+                hipLaunchKernelGGL((csr_block_kernel<T, Epi, decltype(u1)::value, decltype(nnz)::value>), dim3(plan->num_blocks), dim3(kBlock), 0, s, y, A_ptr, A_col, A_val, x, epi, plan->row_blocks_dev, plan->xcd_chunked, split_rows);
+            });
+        });
     FDD_LAUNCH_CHECK();
     return 0;
 }
 
-// the Float = float V-cycle (AMG/config.hpp:4): row-block plans only (fdd_csr_plan_create_blocked)
-template <typename Epi>
-static int plan_launch_f32(const fdd_csr_plan *plan, float *y, const int *A_ptr, const int *A_col, const float *A_val, const float *x, const Epi &epi, void *stream)
+// The gather / scatter forms with one row block per workgroup, on the blocks that overlap [row_lo, row_hi)
+template <typename T, int MODE, bool WEIGHT, bool MASK>
+static void launch_dssum_blocks(const fdd_csr_plan *plan, BlockRange blocks, T *out, T *t, const int *Qt_ptr, const int *Qt_col, const T *u, const T *node_weight, const T *point_mask, int row_lo, int row_hi, hipStream_t s)
 {
-    if (plan->kind != 1 || plan->value_bytes != 4)
+    with_block_nnz(plan->block_nnz, [&](auto nnz) {
+        hipLaunchKernelGGL((dssum_block_kernel<T, MODE, WEIGHT, MASK, decltype(nnz)::value>), dim3(blocks.last - blocks.first), dim3(kBlock), 0, s, out, t, Qt_ptr, Qt_col, u, node_weight, point_mask, plan->row_blocks_dev, blocks.first, row_lo, row_hi,
+                           dssum_xcd_window());
+    });
+}
+
+// An entry's own precondition on its vectors, with the text FDD_REQUIRE reports it by
+struct Precondition
+{
+    bool holds;
+    const char *text;
+    int line;
+};
+#define FDD_PRECONDITION(cond) Precondition{(cond), #cond, __LINE__}
+
+// The body of a plan's AMG SpMV entries: y = epi(A x) once the entry's vectors pass its precondition
+template <typename T, typename Epi>
+static int plan_spmv_entry(const fdd_csr_plan *plan, T *y, const int *A_ptr, const int *A_col, const T *A_val, const T *x, const Epi &epi, void *stream, Precondition vectors)
+{
+    FDD_REQUIRE(plan != nullptr);
+    if (plan->num_rows == 0 || plan->num_cols == 0) return 0;
+    if (!vectors.holds)
     {
-        fdd_set_error("f32 SpMV: not a plan of fdd_csr_plan_create_f32");
-        return 1;
+        fdd_set_error("invalid argument: %s (%s:%d)", vectors.text, __FILE__, vectors.line);
+        return FDD_ERR_INVALID_ARGUMENT;
     }
-    if (plan->sell_slices > 0) return sell_launch<float, Epi>(plan, y, x, epi, stream);
-    const dim3 grid(plan->num_blocks), block(kBlock);
-    static const int split_rows = fdd_env_int("FDD_TUNE_CSR_SPLIT_ROWS", 1);
-    if (launch_short_pipelined<float, Epi>(plan, y, A_ptr, A_col, A_val, x, epi, 0, plan->num_blocks, 0, plan->num_rows, fdd_stream(stream), false))
-    {
-    }
-    else if (plan->block_nnz == kBlockNnzSmall)
-        hipLaunchKernelGGL((csr_block_kernel<float, Epi, false, kBlockNnzSmall>), grid, block, 0, fdd_stream(stream), y, A_ptr, A_col, A_val, x, epi, plan->row_blocks_dev, plan->xcd_chunked, split_rows);
-    else
-        hipLaunchKernelGGL((csr_block_kernel<float, Epi, false, kBlockNnzMax>), grid, block, 0, fdd_stream(stream), y, A_ptr, A_col, A_val, x, epi, plan->row_blocks_dev, plan->xcd_chunked, split_rows);
-    FDD_LAUNCH_CHECK();
-    return 0;
+    return plan_launch<T>(plan, y, A_ptr, A_col, A_val, x, epi, stream);
+}
+
+// frees the sliced-ELL copy of a plan, which is then as it was before fdd_csr_plan_attach_sell
+static void release_sell(fdd_csr_plan *plan)
+{
+    void *arrays[] = {plan->sell_off_dev, plan->sell_col_dev, plan->sell_val_dev, plan->sell_order_dev, plan->sell_col16_dev, plan->sell_slot_base_dev, plan->sell_wide_off_dev};
+    for (void *a : arrays)
+        if (a) (void)hipFree(a);
+    plan->sell_off_dev = plan->sell_col_dev = plan->sell_order_dev = plan->sell_slot_base_dev = plan->sell_wide_off_dev = nullptr;
+    plan->sell_val_dev = nullptr;
+    plan->sell_col16_dev = nullptr;
+    plan->sell_compact_slices = 0;
 }
 
 static int plan_create(fdd_csr_plan **plan, const int *A_ptr_host, int num_rows, int num_cols, int num_nnz, bool f32);
@@ -1340,13 +1349,7 @@ int fdd_csr_plan_destroy(fdd_csr_plan *plan)
     if (plan == nullptr) return 0;
     if (plan->row_blocks_dev) (void)hipFree(plan->row_blocks_dev);
     if (plan->block_meta_dev) (void)hipFree(plan->block_meta_dev);
-    if (plan->sell_off_dev) (void)hipFree(plan->sell_off_dev);
-    if (plan->sell_col_dev) (void)hipFree(plan->sell_col_dev);
-    if (plan->sell_val_dev) (void)hipFree(plan->sell_val_dev);
-    if (plan->sell_order_dev) (void)hipFree(plan->sell_order_dev);
-    if (plan->sell_col16_dev) (void)hipFree(plan->sell_col16_dev);
-    if (plan->sell_slot_base_dev) (void)hipFree(plan->sell_slot_base_dev);
-    if (plan->sell_wide_off_dev) (void)hipFree(plan->sell_wide_off_dev);
+    release_sell(plan);
     delete plan;
     return 0;
 }
@@ -1397,19 +1400,6 @@ int fdd_csr_plan_attach_sell(fdd_csr_plan *plan, const int *A_ptr_host, const in
     const size_t vb = (size_t)plan->value_bytes;
     const int per_block = kBlock / kSellSlice;
     const dim3 grid((slices + per_block - 1) / per_block), block(kBlock);
-    auto release = [&]() {
-        if (plan->sell_order_dev) (void)hipFree(plan->sell_order_dev);
-        if (plan->sell_off_dev) (void)hipFree(plan->sell_off_dev);
-        if (plan->sell_col_dev) (void)hipFree(plan->sell_col_dev);
-        if (plan->sell_val_dev) (void)hipFree(plan->sell_val_dev);
-        if (plan->sell_col16_dev) (void)hipFree(plan->sell_col16_dev);
-        if (plan->sell_slot_base_dev) (void)hipFree(plan->sell_slot_base_dev);
-        if (plan->sell_wide_off_dev) (void)hipFree(plan->sell_wide_off_dev);
-        plan->sell_order_dev = plan->sell_off_dev = plan->sell_col_dev = plan->sell_slot_base_dev = plan->sell_wide_off_dev = nullptr;
-        plan->sell_val_dev = nullptr;
-        plan->sell_col16_dev = nullptr;
-        plan->sell_compact_slices = 0;
-    };
     hipError_t err = hipMalloc((void **)&plan->sell_off_dev, off.size() * sizeof(int));
     if (err == hipSuccess) err = upload_table(plan->sell_off_dev, off.data(), off.size() * sizeof(int));
     // compact column form (16-bit offsets from a per-slot base) for the slices whose slots allow it
@@ -1458,7 +1448,7 @@ int fdd_csr_plan_attach_sell(fdd_csr_plan *plan, const int *A_ptr_host, const in
     if (err != hipSuccess)
     {
         fdd_set_error("fdd_csr_plan_attach_sell: %s", hipGetErrorString(err));
-        release();
+        release_sell(plan);
         return (int)err;
     }
     if (vb == 8)
@@ -1499,21 +1489,12 @@ int fdd_csr_plan_gather_f32(const fdd_csr_plan *plan, float *t, const int *Qt_pt
     if (row_hi == row_lo) return 0;
     FDD_REQUIRE(t != nullptr && Qt_ptr != nullptr && Qt_col != nullptr && u != nullptr);
     if (plan->kind == 0 || plan->has_long_rows) return fdd_gather_rows_f32(t, Qt_ptr, Qt_col, u, row_lo, row_hi, stream);
-    const std::vector<int> &rb = plan->row_blocks_host;
-    int first = (int)(std::upper_bound(rb.begin(), rb.end(), row_lo) - rb.begin()) - 1;
-    int last = (int)(std::lower_bound(rb.begin(), rb.end(), row_hi) - rb.begin()); // exclusive
-    if (first < 0) first = 0;
-    if (last > plan->num_blocks) last = plan->num_blocks;
-    if (last <= first) return 0;
-    const dim3 grid(last - first), block(kBlock);
-    static const int xcd_window = fdd_env_int("FDD_TUNE_DSSUM_XCD_WINDOW", 32);
-    if (launch_gather_pipelined(plan, t, Qt_ptr, Qt_col, u, first, last, row_lo, row_hi, fdd_stream(stream)))
-    {
-    }
-    else if (plan->block_nnz == kBlockNnzSmall)
-        hipLaunchKernelGGL((gather_block_f32_kernel<kBlockNnzSmall>), grid, block, 0, fdd_stream(stream), t, Qt_ptr, Qt_col, u, plan->row_blocks_dev, first, row_lo, row_hi, xcd_window);
-    else
-        hipLaunchKernelGGL((gather_block_f32_kernel<kBlockNnzMax>), grid, block, 0, fdd_stream(stream), t, Qt_ptr, Qt_col, u, plan->row_blocks_dev, first, row_lo, row_hi, xcd_window);
+    const BlockRange blocks = blocks_overlapping(plan, row_lo, row_hi);
+    if (blocks.empty()) return 0;
+    hipStream_t s = fdd_stream(stream);
+    // the persistent pipelined gather (no values read, no epilogue), or the gather half of the dssum with one row block per workgroup
+    if (!(plan->unit_values && launch_short_pipelined<float>(plan, t, Qt_ptr, Qt_col, (const float *)nullptr, u, EpiPlainT<float>{}, blocks, row_lo, row_hi, s, true)))
+        launch_dssum_blocks<float, 1, false, false>(plan, blocks, (float *)nullptr, t, Qt_ptr, Qt_col, u, (const float *)nullptr, (const float *)nullptr, row_lo, row_hi, s);
     FDD_LAUNCH_CHECK();
     return 0;
 }
@@ -1539,48 +1520,36 @@ int fdd_csr_plan_dssum(const fdd_csr_plan *plan, double *QQtu, double *t, const 
         return fdd_dssum_scatter(QQtu, t, Qt_ptr, Qt_col, point_mask, row_lo, row_hi, stream);
     }
 
-    // blocks overlapping the row range
-    const std::vector<int> &rb = plan->row_blocks_host;
-    int first = (int)(std::upper_bound(rb.begin(), rb.end(), row_lo) - rb.begin()) - 1;
-    int last = (int)(std::lower_bound(rb.begin(), rb.end(), row_hi) - rb.begin()); // exclusive
-    if (first < 0) first = 0;
-    if (last > plan->num_blocks) last = plan->num_blocks;
-    if (last <= first) return 0;
-
-    const dim3 grid(last - first), block(kBlock);
+    const BlockRange blocks = blocks_overlapping(plan, row_lo, row_hi);
+    if (blocks.empty()) return 0;
     hipStream_t s = fdd_stream(stream);
     const bool W = node_weight != nullptr && mode != 2, M = point_mask != nullptr && mode != 1;
-    static const int xcd_window = fdd_env_int("FDD_TUNE_DSSUM_XCD_WINDOW", 32); // consecutive row blocks per XCD inside a window of 8x as many (0: dispatch order).  C2's Qt gather: L2 fetches 415 -> 356 MB per launch (1.23 -> 1.05 x the 338 MB it must move; profiles/r04_pmc_traffic_c2*.json), 74 -> 72 us
-#define FDD_DSB(MODE, WW, MM)                                                                                                                                                                    \
-    do                                                                                                                                                                                          \
-    {                                                                                                                                                                                           \
-        if (plan->block_nnz == kBlockNnzSmall)                                                                                                                                                  \
-            hipLaunchKernelGGL((dssum_block_kernel<MODE, WW, MM, kBlockNnzSmall>), grid, block, 0, s, QQtu, t, Qt_ptr, Qt_col, u, node_weight, point_mask, plan->row_blocks_dev, first, row_lo, row_hi, xcd_window); \
-        else                                                                                                                                                                                    \
-            hipLaunchKernelGGL((dssum_block_kernel<MODE, WW, MM, kBlockNnzMax>), grid, block, 0, s, QQtu, t, Qt_ptr, Qt_col, u, node_weight, point_mask, plan->row_blocks_dev, first, row_lo, row_hi, xcd_window);   \
-    } while (0)
+    const auto run = [&](auto kMode, auto kWeight, auto kMask) {
+        launch_dssum_blocks<double, decltype(kMode)::value, decltype(kWeight)::value, decltype(kMask)::value>(plan, blocks, QQtu, t, Qt_ptr, Qt_col, u, node_weight, point_mask, row_lo, row_hi, s);
+    };
+    constexpr std::integral_constant<int, 0> fused{};
+    constexpr std::integral_constant<int, 1> gather{};
+    constexpr std::integral_constant<int, 2> scatter{};
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
     if (mode == 0)
     {
-        if (W && M) FDD_DSB(0, true, true);
-        else if (W) FDD_DSB(0, true, false);
-        else if (M) FDD_DSB(0, false, true);
-        else FDD_DSB(0, false, false);
+        if (W && M) run(fused, yes, yes);
+        else if (W) run(fused, yes, no);
+        else if (M) run(fused, no, yes);
+        else run(fused, no, no);
     }
     else if (mode == 1)
     {
-        if (W) FDD_DSB(1, true, false);
-        else if (launch_gather_pipelined(plan, t, Qt_ptr, Qt_col, u, first, last, row_lo, row_hi, s))
-        {
-            // persistent, pipelined form (FDD_TUNE_GATHER_PIPELINED = workgroups per CU; 0: one row block per workgroup)
-        }
-        else FDD_DSB(1, false, false);
+        if (W) run(gather, yes, no);
+        // the boolean gather t = Qt u (no values read, no epilogue): the persistent pipelined form where it applies
+        else if (!launch_short_pipelined<double>(plan, t, Qt_ptr, Qt_col, (const double *)nullptr, u, EpiPlain{}, blocks, row_lo, row_hi, s, true)) run(gather, no, no);
     }
     else
     {
-        if (M) FDD_DSB(2, false, true);
-        else FDD_DSB(2, false, false);
+        if (M) run(scatter, no, yes);
+        else run(scatter, no, no);
     }
-#undef FDD_DSB
     FDD_LAUNCH_CHECK();
     return 0;
 }
@@ -1594,10 +1563,9 @@ int fdd_csr_plan_gather_weighted_norm2(const fdd_csr_plan *plan, double *out, do
     FDD_REQUIRE(plan->unit_values != 0 && Qt_ptr != nullptr && Qt_col != nullptr && u != nullptr && node_weight != nullptr);
     if (plan->kind == 0 || plan->has_long_rows) return fdd_gather_weighted_norm2(out, ws, Qt_ptr, Qt_col, u, node_weight, plan->num_rows, stream);
     const int grid = plan->num_blocks < FDD_REDUCE_MAX_BLOCKS ? plan->num_blocks : FDD_REDUCE_MAX_BLOCKS;
-    if (plan->block_nnz == kBlockNnzSmall)
-        hipLaunchKernelGGL(gather_norm2_block_kernel<kBlockNnzSmall>, dim3(grid), dim3(kBlock), 0, s, ws, Qt_ptr, Qt_col, u, node_weight, plan->row_blocks_dev, plan->num_blocks);
-    else
-        hipLaunchKernelGGL(gather_norm2_block_kernel<kBlockNnzMax>, dim3(grid), dim3(kBlock), 0, s, ws, Qt_ptr, Qt_col, u, node_weight, plan->row_blocks_dev, plan->num_blocks);
+    with_block_nnz(plan->block_nnz, [&](auto nnz) {
+        hipLaunchKernelGGL(gather_norm2_block_kernel<decltype(nnz)::value>, dim3(grid), dim3(kBlock), 0, s, ws, Qt_ptr, Qt_col, u, node_weight, plan->row_blocks_dev, plan->num_blocks);
+    });
     FDD_LAUNCH_CHECK();
     hipLaunchKernelGGL(fold_partials_kernel, dim3(1), dim3(kBlock), 0, s, out, ws, grid);
     FDD_LAUNCH_CHECK();
@@ -1607,7 +1575,6 @@ int fdd_csr_plan_gather_weighted_norm2(const fdd_csr_plan *plan, double *out, do
 int fdd_csr_plan_set_unit_values(fdd_csr_plan *plan, int unit_values)
 {
     FDD_REQUIRE(plan != nullptr);
-    FDD_REQUIRE(plan->value_bytes == 8);
     FDD_REQUIRE(plan->value_bytes == 8);
     plan->unit_values = unit_values != 0;
     return 0;
@@ -1625,11 +1592,9 @@ int fdd_csr_plan_kind(const fdd_csr_plan *plan, int *kind)
 int fdd_csr_plan_pipelined(const fdd_csr_plan *plan, int *pipelined)
 {
     FDD_REQUIRE(plan != nullptr && pipelined != nullptr);
-    *pipelined = (gather_pipelined_per_cu() > 0 && plan->kind == 1 && plan->block_nnz == kBlockNnzSmall && plan->block_meta_dev != nullptr && !plan->has_long_rows && plan->sell_slices == 0) ? 1 : 0;
+    *pipelined = (plan->sell_slices == 0 && short_pipelined_applies(plan)) ? 1 : 0; // a plan of kind 0 has no block table
     return 0;
 }
-
-// launch csr_block_kernel for the plan's block size
 
 int fdd_csr_plan_multiply(const fdd_csr_plan *plan, double *Au, const int *A_ptr, const int *A_col, const double *A_val, const double *u, const double *weight, void *stream)
 {
@@ -1638,46 +1603,9 @@ int fdd_csr_plan_multiply(const fdd_csr_plan *plan, double *Au, const int *A_ptr
     if (plan->num_rows == 0 || plan->num_cols == 0) return 0; // csr_matrix.tpp:304,334
     FDD_REQUIRE(Au != nullptr && A_ptr != nullptr && u != nullptr);
 
-    if (plan->one_per_row)
-    {
-        if (weight) return launch_one_per_row(Au, A_col, A_val, u, EpiWeight{weight}, plan->num_rows, stream, plan->unit_values != 0);
-        return launch_one_per_row(Au, A_col, A_val, u, EpiPlain{}, plan->num_rows, stream, plan->unit_values != 0);
-    }
-    if (plan->kind == 0)
-    {
-        if (weight) return launch_rows(Au, A_ptr, A_col, A_val, u, EpiWeight{weight}, 0, plan->num_rows, stream, plan->unit_values != 0);
-        return launch_rows(Au, A_ptr, A_col, A_val, u, EpiPlain{}, 0, plan->num_rows, stream, plan->unit_values != 0);
-    }
-
-    const dim3 grid(plan->num_blocks), block(kBlock);
-    hipStream_t s = fdd_stream(stream);
-    if (plan->unit_values)
-    {
-        if (weight)
-        {
-            if (!launch_short_pipelined<double, EpiWeight>(plan, Au, A_ptr, A_col, A_val, u, EpiWeight{weight}, 0, plan->num_blocks, 0, plan->num_rows, s, true))
-                FDD_CSR_BLOCK(EpiWeight, true, grid, block, 0, s, Au, A_ptr, A_col, A_val, u, EpiWeight{weight}, plan->row_blocks_dev, plan->xcd_chunked, 0);
-        }
-        else if (launch_gather_pipelined(plan, Au, A_ptr, A_col, u, 0, plan->num_blocks, 0, plan->num_rows, s))
-        {
-            // boolean short rows (the gather Qt): the persistent pipelined gather, same sums in the same order
-        }
-        else
-            FDD_CSR_BLOCK(EpiPlain, true, grid, block, 0, s, Au, A_ptr, A_col, A_val, u, EpiPlain{}, plan->row_blocks_dev, plan->xcd_chunked, 0);
-    }
-    else
-    {
-        // valued matrices: short rows on the persistent pipelined kernel
-        if (weight)
-        {
-            if (!launch_short_pipelined<double, EpiWeight>(plan, Au, A_ptr, A_col, A_val, u, EpiWeight{weight}, 0, plan->num_blocks, 0, plan->num_rows, s, false))
-                FDD_CSR_BLOCK(EpiWeight, false, grid, block, 0, s, Au, A_ptr, A_col, A_val, u, EpiWeight{weight}, plan->row_blocks_dev, plan->xcd_chunked, 0);
-        }
-        else if (!launch_short_pipelined<double, EpiPlain>(plan, Au, A_ptr, A_col, A_val, u, EpiPlain{}, 0, plan->num_blocks, 0, plan->num_rows, s, false))
-            FDD_CSR_BLOCK(EpiPlain, false, grid, block, 0, s, Au, A_ptr, A_col, A_val, u, EpiPlain{}, plan->row_blocks_dev, plan->xcd_chunked, 0);
-    }
-    FDD_LAUNCH_CHECK();
-    return 0;
+    // this entry does not look at a sliced-ELL copy (the host attaches one to the AMG's matrices, which go through the entries below)
+    if (weight) return plan_launch<double, false>(plan, Au, A_ptr, A_col, A_val, u, EpiWeight{weight}, stream);
+    return plan_launch<double, false>(plan, Au, A_ptr, A_col, A_val, u, EpiPlain{}, stream);
 }
 
 // y = alpha*A*x + beta*y on a plan (the cusparseSpMV of AMG/csr_matrix.cpp:129-131); y must not alias x
@@ -1688,10 +1616,7 @@ int fdd_csr_plan_matvec(const fdd_csr_plan *plan, double *y, const int *A_ptr, c
 
 int fdd_csr_plan_matvec_to(const fdd_csr_plan *plan, double *y, const double *y_in, const int *A_ptr, const int *A_col, const double *A_val, const double *x, double alpha, double beta, void *stream)
 {
-    FDD_REQUIRE(plan != nullptr);
-    if (plan->num_rows == 0 || plan->num_cols == 0) return 0;
-    FDD_REQUIRE(y != nullptr && A_ptr != nullptr && x != nullptr && y != x);
-    return plan_launch(plan, y, A_ptr, A_col, A_val, x, EpiAxpby{alpha, beta, y_in}, stream);
+    return plan_spmv_entry(plan, y, A_ptr, A_col, A_val, x, EpiAxpby{alpha, beta, y_in}, stream, FDD_PRECONDITION(y != nullptr && A_ptr != nullptr && x != nullptr && y != x));
 }
 
 // The Chebyshev smoother with its element-wise kernels as SpMV epilogues (same arithmetic, statement for
@@ -1699,78 +1624,51 @@ int fdd_csr_plan_matvec_to(const fdd_csr_plan *plan, double *y, const double *y_
 // Sr = D*(f - A u), work = D*(coef*Sr)
 int fdd_amg_smooth_residual_matvec(const fdd_csr_plan *plan, double *work, double *Sr, const int *A_ptr, const int *A_col, const double *A_val, const double *u, const double *f, const double *D_val, double coef, void *stream)
 {
-    FDD_REQUIRE(plan != nullptr);
-    if (plan->num_rows == 0 || plan->num_cols == 0) return 0;
-    FDD_REQUIRE(work != nullptr && Sr != nullptr && A_ptr != nullptr && u != nullptr && f != nullptr && D_val != nullptr && work != u && Sr != u);
-    return plan_launch(plan, work, A_ptr, A_col, A_val, u, EpiSmoothResidual{f, D_val, Sr, coef}, stream);
+    return plan_spmv_entry(plan, work, A_ptr, A_col, A_val, u, EpiSmoothResidual{f, D_val, Sr, coef}, stream, FDD_PRECONDITION(work != nullptr && Sr != nullptr && A_ptr != nullptr && u != nullptr && f != nullptr && D_val != nullptr && work != u && Sr != u));
 }
 
 // work_out = D*(coef*Sr + D*(A work_in))
 int fdd_amg_smooth_polynomial_matvec(const fdd_csr_plan *plan, double *work_out, const int *A_ptr, const int *A_col, const double *A_val, const double *work_in, const double *Sr, const double *D_val, double coef, void *stream)
 {
-    FDD_REQUIRE(plan != nullptr);
-    if (plan->num_rows == 0 || plan->num_cols == 0) return 0;
-    FDD_REQUIRE(work_out != nullptr && A_ptr != nullptr && work_in != nullptr && Sr != nullptr && D_val != nullptr && work_out != work_in);
-    return plan_launch(plan, work_out, A_ptr, A_col, A_val, work_in, EpiSmoothPoly{Sr, D_val, coef}, stream);
+    return plan_spmv_entry(plan, work_out, A_ptr, A_col, A_val, work_in, EpiSmoothPoly{Sr, D_val, coef}, stream, FDD_PRECONDITION(work_out != nullptr && A_ptr != nullptr && work_in != nullptr && Sr != nullptr && D_val != nullptr && work_out != work_in));
 }
 
 // u += D*(coef*Sr + D*(A work_in))
 int fdd_amg_smooth_update_matvec(const fdd_csr_plan *plan, double *u, const int *A_ptr, const int *A_col, const double *A_val, const double *work_in, const double *Sr, const double *D_val, double coef, void *stream)
 {
-    FDD_REQUIRE(plan != nullptr);
-    if (plan->num_rows == 0 || plan->num_cols == 0) return 0;
-    FDD_REQUIRE(u != nullptr && A_ptr != nullptr && work_in != nullptr && Sr != nullptr && D_val != nullptr && u != work_in);
-    return plan_launch(plan, u, A_ptr, A_col, A_val, work_in, EpiSmoothUpdate{Sr, D_val, coef}, stream);
+    return plan_spmv_entry(plan, u, A_ptr, A_col, A_val, work_in, EpiSmoothUpdate{Sr, D_val, coef}, stream, FDD_PRECONDITION(u != nullptr && A_ptr != nullptr && work_in != nullptr && Sr != nullptr && D_val != nullptr && u != work_in));
 }
 
 // u = 0 + D*(coef*Sr + D*(A work_in)): the update above from a zero u, which is not read
 int fdd_amg_smooth_update_matvec_from_zero(const fdd_csr_plan *plan, double *u, const int *A_ptr, const int *A_col, const double *A_val, const double *work_in, const double *Sr, const double *D_val, double coef, void *stream)
 {
-    FDD_REQUIRE(plan != nullptr);
-    if (plan->num_rows == 0 || plan->num_cols == 0) return 0;
-    FDD_REQUIRE(u != nullptr && A_ptr != nullptr && work_in != nullptr && Sr != nullptr && D_val != nullptr && u != work_in);
-    return plan_launch(plan, u, A_ptr, A_col, A_val, work_in, EpiSmoothUpdateZeroT<double>{Sr, D_val, coef}, stream);
+    return plan_spmv_entry(plan, u, A_ptr, A_col, A_val, work_in, EpiSmoothUpdateZeroT<double>{Sr, D_val, coef}, stream, FDD_PRECONDITION(u != nullptr && A_ptr != nullptr && work_in != nullptr && Sr != nullptr && D_val != nullptr && u != work_in));
 }
 
 // ---- Float = float (AMG/config.hpp:4): the V-cycle's SpMV and fused smoother on f32 values and vectors ----
 int fdd_csr_plan_matvec_to_f32(const fdd_csr_plan *plan, float *y, const float *y_in, const int *A_ptr, const int *A_col, const float *A_val, const float *x, float alpha, float beta, void *stream)
 {
-    FDD_REQUIRE(plan != nullptr);
-    if (plan->num_rows == 0 || plan->num_cols == 0) return 0;
-    FDD_REQUIRE(y != nullptr && A_ptr != nullptr && A_val != nullptr && x != nullptr && y != x);
-    return plan_launch_f32(plan, y, A_ptr, A_col, A_val, x, EpiAxpbyT<float>{alpha, beta, y_in}, stream);
+    return plan_spmv_entry(plan, y, A_ptr, A_col, A_val, x, EpiAxpbyT<float>{alpha, beta, y_in}, stream, FDD_PRECONDITION(y != nullptr && A_ptr != nullptr && A_val != nullptr && x != nullptr && y != x));
 }
 
 int fdd_amg_smooth_residual_matvec_f32(const fdd_csr_plan *plan, float *work, float *Sr, const int *A_ptr, const int *A_col, const float *A_val, const float *u, const float *f, const float *D_val, float coef, void *stream)
 {
-    FDD_REQUIRE(plan != nullptr);
-    if (plan->num_rows == 0 || plan->num_cols == 0) return 0;
-    FDD_REQUIRE(work != nullptr && Sr != nullptr && A_ptr != nullptr && A_val != nullptr && u != nullptr && f != nullptr && D_val != nullptr && work != u && Sr != u);
-    return plan_launch_f32(plan, work, A_ptr, A_col, A_val, u, EpiSmoothResidualT<float>{f, D_val, Sr, coef}, stream);
+    return plan_spmv_entry(plan, work, A_ptr, A_col, A_val, u, EpiSmoothResidualT<float>{f, D_val, Sr, coef}, stream, FDD_PRECONDITION(work != nullptr && Sr != nullptr && A_ptr != nullptr && A_val != nullptr && u != nullptr && f != nullptr && D_val != nullptr && work != u && Sr != u));
 }
 
 int fdd_amg_smooth_polynomial_matvec_f32(const fdd_csr_plan *plan, float *work_out, const int *A_ptr, const int *A_col, const float *A_val, const float *work_in, const float *Sr, const float *D_val, float coef, void *stream)
 {
-    FDD_REQUIRE(plan != nullptr);
-    if (plan->num_rows == 0 || plan->num_cols == 0) return 0;
-    FDD_REQUIRE(work_out != nullptr && A_ptr != nullptr && A_val != nullptr && work_in != nullptr && Sr != nullptr && D_val != nullptr && work_out != work_in);
-    return plan_launch_f32(plan, work_out, A_ptr, A_col, A_val, work_in, EpiSmoothPolyT<float>{Sr, D_val, coef}, stream);
+    return plan_spmv_entry(plan, work_out, A_ptr, A_col, A_val, work_in, EpiSmoothPolyT<float>{Sr, D_val, coef}, stream, FDD_PRECONDITION(work_out != nullptr && A_ptr != nullptr && A_val != nullptr && work_in != nullptr && Sr != nullptr && D_val != nullptr && work_out != work_in));
 }
 
 int fdd_amg_smooth_update_matvec_f32(const fdd_csr_plan *plan, float *u, const int *A_ptr, const int *A_col, const float *A_val, const float *work_in, const float *Sr, const float *D_val, float coef, void *stream)
 {
-    FDD_REQUIRE(plan != nullptr);
-    if (plan->num_rows == 0 || plan->num_cols == 0) return 0;
-    FDD_REQUIRE(u != nullptr && A_ptr != nullptr && A_val != nullptr && work_in != nullptr && Sr != nullptr && D_val != nullptr && u != work_in);
-    return plan_launch_f32(plan, u, A_ptr, A_col, A_val, work_in, EpiSmoothUpdateT<float>{Sr, D_val, coef}, stream);
+    return plan_spmv_entry(plan, u, A_ptr, A_col, A_val, work_in, EpiSmoothUpdateT<float>{Sr, D_val, coef}, stream, FDD_PRECONDITION(u != nullptr && A_ptr != nullptr && A_val != nullptr && work_in != nullptr && Sr != nullptr && D_val != nullptr && u != work_in));
 }
 
 int fdd_amg_smooth_update_matvec_from_zero_f32(const fdd_csr_plan *plan, float *u, const int *A_ptr, const int *A_col, const float *A_val, const float *work_in, const float *Sr, const float *D_val, float coef, void *stream)
 {
-    FDD_REQUIRE(plan != nullptr);
-    if (plan->num_rows == 0 || plan->num_cols == 0) return 0;
-    FDD_REQUIRE(u != nullptr && A_ptr != nullptr && A_val != nullptr && work_in != nullptr && Sr != nullptr && D_val != nullptr && u != work_in);
-    return plan_launch_f32(plan, u, A_ptr, A_col, A_val, work_in, EpiSmoothUpdateZeroT<float>{Sr, D_val, coef}, stream);
+    return plan_spmv_entry(plan, u, A_ptr, A_col, A_val, work_in, EpiSmoothUpdateZeroT<float>{Sr, D_val, coef}, stream, FDD_PRECONDITION(u != nullptr && A_ptr != nullptr && A_val != nullptr && work_in != nullptr && Sr != nullptr && D_val != nullptr && u != work_in));
 }
 
 } // extern "C"
