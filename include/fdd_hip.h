@@ -313,6 +313,22 @@ int fdd_projection_dots(double *out, double *ws, const double *X, int ld, int K,
 int fdd_projection_apply(double *x, double *b, double *nu2_out, double *ws, const double *x_in, const double *b_in, const double *X, const double *AX, int ld, int K, const double *coeffs_dev, double sign_x, double sign_b, int n, void *stream);
 int fdd_projection_store(double *Xk, double *AXk, const double *x, const double *b, const double *nu2_dev, int n, void *stream);
 
+/* ---- Chebyshev-Jacobi inner solve (an addition of this build, host/subdomain.hpp chebyshev_dofs): one step of
+ * the recurrence as ONE element-wise pass, coefficients by value.
+ *   first : t = dinv .* r_in;  d = c_r*t + 0*t;  x = d                                       (q, r_out, c_d not used)
+ *   later : r = 1*r_in + (-1)*q;  t = dinv .* r;  d = c_d*d + c_r*t;  x = 1*x + 1*d;  r_out = r   (r_out may be r_in)
+ *   last  : d and r_out are not stored (may be NULL where they are not read either).
+ * The statements are those of fdd_vector_vector_addition and fdd_vector_diagonal_scaling_dev in that order, so a step
+ * composed from those entries has the same bits.  Any n, any alignment (16 bytes per lane where every pointer allows it).
+ * fdd_csr_plan_gather_cheby: a later step with q = Qt u formed by the kernel itself, u the point vector and Qt a boolean
+ * gather matrix whose plan runs on the persistent pipelined kernel (fdd_csr_plan_pipelined; any other plan is an error):
+ * q never goes through memory.  Rows are summed in column order, as fdd_csr_plan_dssum mode 1 sums them: same bits as the
+ * gather followed by fdd_cheby_step.  u must not alias x, d or r_out. */
+int fdd_cheby_step(double *x, double *d, double *r_out, const double *r_in, const double *q, const double *dinv, double c_d, double c_r, int first, int last, int n, void *stream);
+int fdd_cheby_step_f32(float *x, float *d, float *r_out, const float *r_in, const float *q, const float *dinv, float c_d, float c_r, int first, int last, int n, void *stream);
+int fdd_csr_plan_gather_cheby(const fdd_csr_plan *plan, double *x, double *d, double *r_out, const int *Qt_ptr, const int *Qt_col, const double *u, const double *r_in, const double *dinv, double c_d, double c_r, int last, void *stream);
+int fdd_csr_plan_gather_cheby_f32(const fdd_csr_plan *plan, float *x, float *d, float *r_out, const int *Qt_ptr, const int *Qt_col, const float *u, const float *r_in, const float *dinv, float c_d, float c_r, int last, void *stream);
+
 /* Scalar bookkeeping of one restart cycle of the inner flexible GMRES(m) (subdomain.tpp:4396-4477) on the device:
  * Hessenberg column + Givens rotations + residual recurrence + stopping tests per step, back-substitution at the
  * end, so that a cycle is enqueued without a host round trip per step.  `state` = fdd_gmres_state_bytes() bytes of

@@ -190,6 +190,15 @@ int fddh_problem_set_options(fddh_problem *p, int max_iterations, double toleran
  *                              projection (below) are single launches of csrc/fdd_projection.hip; 0: they are composed from
  *                              the multi-vector entries (the only form on a library without them; setting 1 there fails,
  *                              naming the entry).  Same sums, same element-wise bits; the basis stays.
+ *   "inner_solver"             0 (default): the inner FCG / GMRES(m); 1: the Chebyshev-Jacobi iteration (an option of this
+ *                              build, see fddh_problem_inner_chebyshev_configure below), which takes the place of either.
+ *   "inner_chebyshev_order"    1..16 (default 4): diagonal scalings per application; one operator application fewer
+ *   "inner_chebyshev_lower_permille" 1..999 (default 100): the lower end of the interval in thousandths of lambda
+ *   "chebyshev_kernels"        1 (default where the kernel library has fdd_cheby_step / _f32): a step of that iteration is one
+ *                              launch; 0: composed from vector_vector_addition and vector_diagonal_scaling_dev.  Same bits.
+ *   "fused_chebyshev"          1 (default where the library has fdd_csr_plan_gather_cheby / _f32): in a conforming region of unit
+ *                              norm weight the step is the epilogue of the gather Qt in front of it; 0: gather, then the step.
+ *                              Same bits.  Either flag set to 1 on a library without the entries fails, naming the entry.
  *   "amg_num_vcycles" 1..16, "amg_cheby_order" 1..4 (subdomain.hpp:236-237), "amg_matrix_free_transfer",
  *   "preconditioner_precision" 64 / 32 (the whole inner solve)
  *
@@ -209,6 +218,7 @@ int fddh_problem_set_options(fddh_problem *p, int max_iterations, double toleran
  *   "amg_precision" / "preconditioner_precision" 32 need a Chebyshev order of at least 2 at the time they are set
  * What changes the operator under a live projection basis (fddh_problem_projection_configure) empties the basis, since its
  * stored images A X would no longer be the operator's: fddh_problem_set_D_hat (any level) and the flag "affine_geometry".
+ * The same two drop the point-Jacobi diagonal and the Chebyshev-Jacobi eigenvalue bound, which are made again at next use.
  * Solver options and the other flags leave it alone.
  * Refused on a live problem, with an error that names the option, the option keeping its value (the closed list of
  * refused transitions; tests/reconfigure_walks.py REFUSED matches it line for line):
@@ -301,6 +311,25 @@ int fddh_problem_sub_residual_norm(fddh_problem *p, const double *r, double *nor
 int fddh_problem_sub_dof_op(fddh_problem *p, int op, const double *in, double *out, int n);
 /* the diagonal of that operator over the n unique dofs, as the point-Jacobi option ("sub_use_preconditioner" = 2) uses it */
 int fddh_problem_sub_jacobi_diagonal(fddh_problem *p, double *out, int n);
+/* out (n dofs) = the configured inner solve (GMRES(m) with the current options, or Chebyshev-Jacobi) applied to the dof-space
+ * right-hand side fa, from a zero start.  Analysis and tests, like fddh_problem_sub_dof_op. */
+int fddh_problem_sub_dof_solve(fddh_problem *p, const double *fa, double *ua, int n);
+
+/* Chebyshev-Jacobi inner solve (flag "inner_solver" = 1; an addition of this build, off by default): the local
+ * problems are answered by the Chebyshev polynomial of order m in D^-1 A for the interval [lower, upper] * lambda, with D the
+ * exact diagonal of fddh_problem_sub_jacobi_diagonal and lambda the Rayleigh quotient of D^-1/2 A D^-1/2 after
+ * power_iterations steps of the power iteration (each rank on its own region: no communication).  m diagonal scalings and
+ * m - 1 operator applications per application, no inner product, no synchronisation; a fixed, linear, symmetric operator.
+ * The outer solver's preconditioner_type (set_options) is not looked at while it is on; "preconditioner_precision" 32 runs
+ * it on float vectors.  lambda is computed at first use and kept; fddh_problem_set_D_hat and the flag "affine_geometry"
+ * drop it together with the diagonal.
+ *   configure  order 1..16, 0 < lower < upper, power_iterations 1..10000; defaults 4, 0.1, 1.1, 25.  A new lower or upper keeps
+ *              lambda, a new power_iterations drops it.  A bad value is an error and nothing changes.
+ *   info       the settings and lambda, which is computed now if it is not there (lambda NULL: not computed)
+ * Refused when a solve starts (error return, the problem stays usable): "sub_use_preconditioner" = 1 (Chebyshev around the
+ * V-cycle is not built), and a problem whose inner iteration does not run in dof space (2-D, "assembled_inner_solve" = 0). */
+int fddh_problem_inner_chebyshev_configure(fddh_problem *p, int order, double lower, double upper, int power_iterations);
+int fddh_problem_inner_chebyshev_info(fddh_problem *p, int *order, double *lower, double *upper, double *lambda, int *power_iterations);
 
 /* Average launch time (HIP events on the stream) and algorithmic bytes (12 B per non-zero,
  * 12 B per row, 8 B per column) of the assembly SpMVs of csr_matrix.okl on the problem's matrices:

@@ -178,6 +178,52 @@ struct XmayRatioDevOp
     __device__ void one(long long i) const { out[i] = x[i] - (*num / *den) * y[i]; }
 };
 
+// One step of the Chebyshev-Jacobi inner solve (host/subdomain.hpp, chebyshev_dofs) as one pass.  The statements are those
+// of the entries the step can also be composed from, in their order -- vector_vector_addition (AxpbyOp) and
+// vector_diagonal_scaling_dev (DiagScaleDevOp) above -- so the bits are the same either way:
+//   first : t = dinv .* r_in;  d = c_r*t + 0*t;                                x = d
+//   later : r = 1*r_in + (-1)*q;  t = dinv .* r;  d = c_d*d + c_r*t;            x = 1*x + 1*d
+// r_in is the right-hand side at the second step (never written) and r_out itself afterwards; the last step stores x only.
+// f64 bytes per dof: first 32, middle 64, last 48.
+struct ChebyStepOp
+{
+    double *x, *d, *r_out;
+    const double *r_in, *q, *dinv;
+    double c_d, c_r;
+    int first, last;
+    __device__ double direction(double rv, double dv, double di) const
+    {
+        const double t = di * rv;
+        return first ? c_r * t + 0.0 * t : c_d * dv + c_r * t;
+    }
+    __device__ void vec2(long long i) const
+    {
+        const double2 di = ld2(dinv, i);
+        double2 r = ld2(r_in, i), dv = make_double2(0.0, 0.0), xv = dv;
+        if (!first)
+        {
+            const double2 qv = ld2(q, i);
+            dv = ld2(d, i);
+            xv = ld2(x, i);
+            r = make_double2(1.0 * r.x + (-1.0) * qv.x, 1.0 * r.y + (-1.0) * qv.y);
+        }
+        dv = make_double2(direction(r.x, dv.x, di.x), direction(r.y, dv.y, di.y));
+        st2(x, i, first ? dv : make_double2(1.0 * xv.x + 1.0 * dv.x, 1.0 * xv.y + 1.0 * dv.y));
+        if (last) return;
+        st2(d, i, dv);
+        if (!first) st2(r_out, i, r);
+    }
+    __device__ void one(long long i) const
+    {
+        const double r = first ? r_in[i] : 1.0 * r_in[i] + (-1.0) * q[i];
+        const double dn = direction(r, first ? 0.0 : d[i], dinv[i]);
+        x[i] = first ? dn : 1.0 * x[i] + 1.0 * dn;
+        if (last) return;
+        d[i] = dn;
+        if (!first) r_out[i] = r;
+    }
+};
+
 } // namespace
 __global__ void fdd_sqrt_sum_kernel(double *out, const double *parts, int nparts)
 {
@@ -649,6 +695,17 @@ int fdd_vector_diagonal_scaling_dev(double *z, const double *d, const double *sc
     if (n == 0) return 0;
     FDD_REQUIRE(z != nullptr && u != nullptr && d != nullptr);
     return launch_ew(DiagScaleDevOp{z, d, u, scale_dev}, n, fdd_aligned16(z) && fdd_aligned16(u) && fdd_aligned16(d), stream);
+}
+
+int fdd_cheby_step(double *x, double *d, double *r_out, const double *r_in, const double *q, const double *dinv, double c_d, double c_r, int first, int last, int n, void *stream)
+{
+    FDD_REQUIRE(n >= 0);
+    if (n == 0) return 0;
+    FDD_REQUIRE(x != nullptr && r_in != nullptr && dinv != nullptr);
+    FDD_REQUIRE(last || d != nullptr);
+    FDD_REQUIRE(first || (q != nullptr && d != nullptr && (last || r_out != nullptr)));
+    const bool al = fdd_aligned16(x) && fdd_aligned16(r_in) && fdd_aligned16(dinv) && (last || fdd_aligned16(d)) && (first || (fdd_aligned16(q) && fdd_aligned16(d) && (last || fdd_aligned16(r_out))));
+    return launch_ew(ChebyStepOp{x, d, r_out, r_in, q, dinv, c_d, c_r, first ? 1 : 0, last ? 1 : 0}, n, al, stream);
 }
 
 int fdd_vector_scaling_rsqrt_dev(double *au, const double *norm2_dev, const double *u, int n, void *stream)

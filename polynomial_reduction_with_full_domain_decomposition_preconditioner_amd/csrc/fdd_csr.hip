@@ -191,6 +191,39 @@ typedef EpiSmoothResidualT<double> EpiSmoothResidual;
 typedef EpiSmoothPolyT<double> EpiSmoothPoly;
 typedef EpiSmoothUpdateT<double> EpiSmoothUpdate;
 
+// A later step of the Chebyshev-Jacobi inner solve (fdd_cheby_step, fdd_blas1.hip / fdd_f32.hip) as the epilogue of the
+// gather q = Qt (A_L Q d) in front of it: the row sum is q, which never goes through HBM.  The statements of the
+// element-wise kernel in their order: r = 1*r_in + (-1)*q | t = dinv*r | d = c_d*d + c_r*t | x = 1*x + 1*d.
+// r and d are side outputs (not at the last step); the output vector is x.  r_out may be r_in.
+template <typename T>
+struct Opnd4
+{
+    T a, b, c, d;
+};
+template <typename T>
+struct EpiChebyStepT
+{
+    static constexpr bool kFreeOrder = false; // the gather's sums, in column order
+    typedef Opnd4<T> Opnd;
+    const T *r_in, *dinv;
+    T *r_out, *d;
+    T c_d, c_r;
+    int last;
+    __device__ Opnd operand(int row, const T *x_old) const { return Opnd{r_in[row], d[row], x_old[row], dinv[row]}; }
+    __device__ T finish(T s, Opnd o, int row) const
+    {
+        const T r = T(1) * o.a + T(-1) * s;
+        const T t = o.d * r;
+        const T dn = c_d * o.b + c_r * t;
+        if (!last)
+        {
+            r_out[row] = r;
+            d[row] = dn;
+        }
+        return T(1) * o.c + T(1) * dn;
+    }
+};
+
 // Lane-per-row SpMV.  Each lane owns NPT rows (strided by the workgroup size,
 // so every access stays coalesced across lanes) and keeps the column loads,
 // then the x gathers, of all of them in flight together (fdd_multi_row_sum);
@@ -1497,6 +1530,38 @@ int fdd_csr_plan_gather_f32(const fdd_csr_plan *plan, float *t, const int *Qt_pt
         launch_dssum_blocks<float, 1, false, false>(plan, blocks, (float *)nullptr, t, Qt_ptr, Qt_col, u, (const float *)nullptr, (const float *)nullptr, row_lo, row_hi, s);
     FDD_LAUNCH_CHECK();
     return 0;
+}
+
+// x = x + d', d' = c_d*d + c_r*(dinv .* (r_in - Qt u)), r_out = r_in - Qt u over every row of a boolean gather matrix: one
+// later step of the Chebyshev-Jacobi inner solve with the gather as the kernel's front half (EpiChebyStepT).  On the
+// persistent pipelined kernel only (fdd_csr_plan_pipelined): any other plan is refused and the caller launches the gather
+// and fdd_cheby_step one after the other.  The plan's value type is not looked at: no value is read (as fdd_csr_plan_gather_f32).
+} // extern "C"
+template <typename T>
+static int plan_gather_cheby(const fdd_csr_plan *plan, T *x, T *d, T *r_out, const int *Qt_ptr, const int *Qt_col, const T *u, const T *r_in, const T *dinv, T c_d, T c_r, int last, void *stream)
+{
+    FDD_REQUIRE(plan != nullptr);
+    if (plan->num_rows == 0) return 0;
+    FDD_REQUIRE(x != nullptr && d != nullptr && Qt_ptr != nullptr && Qt_col != nullptr && u != nullptr && r_in != nullptr && dinv != nullptr && (last || r_out != nullptr));
+    FDD_REQUIRE((const void *)u != (const void *)x && (const void *)u != (const void *)d && (const void *)u != (const void *)r_out);
+    if (!(plan->unit_values && plan->sell_slices == 0 && launch_short_pipelined<T>(plan, x, Qt_ptr, Qt_col, (const T *)nullptr, u, EpiChebyStepT<T>{r_in, dinv, r_out, d, c_d, c_r, last ? 1 : 0}, BlockRange{0, plan->num_blocks}, 0, plan->num_rows, fdd_stream(stream), true)))
+    {
+        fdd_set_error("fdd_csr_plan_gather_cheby: not a unit-value plan of the pipelined short-row kernel");
+        return FDD_ERR_INVALID_ARGUMENT;
+    }
+    FDD_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" {
+
+int fdd_csr_plan_gather_cheby(const fdd_csr_plan *plan, double *x, double *d, double *r_out, const int *Qt_ptr, const int *Qt_col, const double *u, const double *r_in, const double *dinv, double c_d, double c_r, int last, void *stream)
+{
+    return plan_gather_cheby<double>(plan, x, d, r_out, Qt_ptr, Qt_col, u, r_in, dinv, c_d, c_r, last, stream);
+}
+
+int fdd_csr_plan_gather_cheby_f32(const fdd_csr_plan *plan, float *x, float *d, float *r_out, const int *Qt_ptr, const int *Qt_col, const float *u, const float *r_in, const float *dinv, float c_d, float c_r, int last, void *stream)
+{
+    return plan_gather_cheby<float>(plan, x, d, r_out, Qt_ptr, Qt_col, u, r_in, dinv, c_d, c_r, last, stream);
 }
 
 // dssum on a plan of the boolean gather matrix Qt; mode 0 = gather + scatter,

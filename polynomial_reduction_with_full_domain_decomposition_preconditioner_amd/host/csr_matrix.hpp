@@ -440,6 +440,21 @@ class CSR_Matrix
         FDD_CALL(fdd_csr_plan_gather_f32(plan, t, ptr.as<int>(), col.as<int>(), u, row_lo, row_hi, fdd::dev().stream));
     }
 
+    // A later step of the Chebyshev-Jacobi inner solve with this gather as the kernel's front half (fdd_csr_plan_gather_cheby,
+    // fdd_hip.h): x += d', d' = c_d d + c_r dinv .* (r_in - this u), r_out = r_in - this u; the last step stores x only.
+    // Where gather_cheby_applies(): a boolean matrix on the persistent pipelined kernel and a kernel library with the entries.
+    bool gather_cheby_applies() const { return &fdd_csr_plan_gather_cheby != nullptr and &fdd_csr_plan_gather_cheby_f32 != nullptr and plan != nullptr and plan_pipelined and unit_values and num_rows > 0 and num_nnz > 0; }
+    void gather_cheby(double *x, double *d, double *r_out, const double *u, const double *r_in, const double *dinv, double c_d, double c_r, bool last)
+    {
+        fdd::ProfileScope prof("csr_short_pipelined_kernel<gather, ChebyStep>", 4.0 * num_rows + 12.0 * num_nnz + 8.0 * num_rows * (last ? 5.0 : 7.0));
+        FDD_CALL(fdd_csr_plan_gather_cheby(plan, x, d, r_out, ptr.as<int>(), col.as<int>(), u, r_in, dinv, c_d, c_r, last ? 1 : 0, fdd::dev().stream));
+    }
+    void gather_cheby(float *x, float *d, float *r_out, const float *u, const float *r_in, const float *dinv, double c_d, double c_r, bool last)
+    {
+        fdd::ProfileScope prof("csr_short_pipelined_kernel<gather, ChebyStep, f32>", 4.0 * num_rows + 8.0 * num_nnz + 4.0 * num_rows * (last ? 5.0 : 7.0));
+        FDD_CALL(fdd_csr_plan_gather_cheby_f32(plan, x, d, r_out, ptr.as<int>(), col.as<int>(), u, r_in, dinv, (float)c_d, (float)c_r, last ? 1 : 0, fdd::dev().stream));
+    }
+
     // out_dev[0] = sum_rows s*s*w with s = (this u)[row]*w[row]
     void gather_weighted_norm2(double *out_dev, double *ws, const double *u, const double *node_weight)
     {

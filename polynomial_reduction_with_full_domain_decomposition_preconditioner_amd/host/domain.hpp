@@ -82,6 +82,7 @@ struct NoPreconditioner
     void gmres_composite_dofs(fdd::memory &, fdd::memory &, bool = true, bool = false, const double * = nullptr) {}
     const double *known_rhs_norm2_dev = nullptr;
     bool unit_norm_weight() const { return false; }
+    bool chebyshev() const { return false; }
 };
 
 template <typename DType>
@@ -875,7 +876,7 @@ class Domain
     {
         if (not(assembled_outer and Qt.unit_values and mesh.dim == 3 and poly_degree <= 15)) return false;
         if (not use_preconditioner) return true;
-        if (preconditioner_type != 1) return false;
+        if (preconditioner_type != 1 and not subdomain.chebyshev()) return false; // the Chebyshev-Jacobi inner solve stands in for either Krylov solve
         if (subdomain.composite()) return subdomain.composite_dof_space() and own_nodes_have_dofs(subdomain);
         return subdomain.assembled_inner and subdomain.can_assemble() and (int)subdomain.point_dof.size() == num_local_points;
     }

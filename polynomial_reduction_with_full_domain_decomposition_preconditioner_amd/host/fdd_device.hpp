@@ -47,6 +47,13 @@
 #pragma weak fdd_projection_dots
 #pragma weak fdd_projection_apply
 #pragma weak fdd_projection_store
+// and the steps of the Chebyshev-Jacobi inner solve: without them a step is composed from vector_vector_addition and
+// vector_diagonal_scaling_dev (Subdomain::chebyshev_dofs, same bits), and the flags "chebyshev_kernels" / "fused_chebyshev"
+// refuse to be set to 1, naming the missing entry (missing_chebyshev_entry)
+#pragma weak fdd_cheby_step
+#pragma weak fdd_cheby_step_f32
+#pragma weak fdd_csr_plan_gather_cheby
+#pragma weak fdd_csr_plan_gather_cheby_f32
 
 namespace fdd
 {
@@ -66,6 +73,16 @@ inline const char *missing_amg_setup_entry()
 #undef FDD_SETUP_ENTRY
     for (const auto &e : entries)
         if (e.fn == nullptr) return e.name;
+    return nullptr;
+}
+
+// the first entry of the Chebyshev-Jacobi step the loaded kernel library does not export, or nullptr (fused: the gather's epilogue too)
+inline const char *missing_chebyshev_entry(bool fused)
+{
+    if (&fdd_cheby_step == nullptr) return "fdd_cheby_step";
+    if (&fdd_cheby_step_f32 == nullptr) return "fdd_cheby_step_f32";
+    if (fused and &fdd_csr_plan_gather_cheby == nullptr) return "fdd_csr_plan_gather_cheby";
+    if (fused and &fdd_csr_plan_gather_cheby_f32 == nullptr) return "fdd_csr_plan_gather_cheby_f32";
     return nullptr;
 }
 

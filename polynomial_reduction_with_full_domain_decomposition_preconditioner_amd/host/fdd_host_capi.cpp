@@ -92,6 +92,14 @@ static void setup_lap(const char *what, int degree, double &mark)
     mark = t;
 }
 
+// an entry that is about to run the inner solve: why the Chebyshev-Jacobi option cannot run on this problem as it is
+// configured (the flags may be set in any order, so this is looked at when a solve starts), or nullptr
+static const char *inner_solver_refusal(const fddh_problem *p)
+{
+    if (!p->subdomain || !p->subdomain->chebyshev()) return nullptr;
+    return p->subdomain->chebyshev_refusal();
+}
+
 static void finish_problem(fddh_problem *p, int flags, int sub_overlap, int sup_overlap)
 {
     double mark = setup_clock();
@@ -852,6 +860,7 @@ int fddh_problem_set_D_hat(fddh_problem *p, int level, const double *D_hat, int 
         if (n != p->degrees[level] + 1) return fail("D_hat of level %d is %d x %d", level, p->degrees[level] + 1, p->degrees[level] + 1);
         p->domains[p->degrees[level]].set_D_hat(D_hat, n);
         p->fine().projection.clear(); // the basis and its images belong to the operator as it was
+        if (p->subdomain) p->subdomain->operator_changed(p->degrees[level], D_hat, n); // and so do the point-Jacobi diagonal and the Chebyshev bound
         return 0;
     }
     catch (const std::exception &e)
@@ -1027,6 +1036,7 @@ int fddh_problem_set_flag(fddh_problem *p, const char *name, int value)
             for (auto &kv : p->domains) kv.second.set_affine_geometry(value != 0);
             if (p->subdomain) p->subdomain->set_affine_geometry(value != 0);
             p->fine().projection.clear(); // the operator's arithmetic changes under the stored images
+            if (p->subdomain) p->subdomain->operator_changed();
         }
         else if (s == "fused_projection")
         {
@@ -1035,6 +1045,38 @@ int fddh_problem_set_flag(fddh_problem *p, const char *name, int value)
             if (value != 0)
                 if (const char *missing = fdd::missing_projection_entry()) return fail("fused_projection needs %s, which the loaded kernel library does not export", missing);
             p->fine().projection.fused = value != 0;
+        }
+        else if (s == "inner_solver")
+        {
+            // 0: the inner FCG / GMRES(m) (set_options' preconditioner_type); 1: the Chebyshev-Jacobi iteration (an option of this
+            // build, Subdomain::chebyshev_dofs), which takes the place of either.  What it cannot run on is refused when a solve starts.
+            if (!p->subdomain) return fail("problem was created without a Subdomain");
+            if (value != 0 && value != 1) return fail("inner_solver is 0 (FCG / GMRES) or 1 (Chebyshev-Jacobi)");
+            p->subdomain->inner_solver = value;
+        }
+        else if (s == "inner_chebyshev_order")
+        {
+            if (!p->subdomain) return fail("problem was created without a Subdomain");
+            if (value < 1 || value > 16) return fail("inner_chebyshev_order must lie in 1..16, got %d", value);
+            p->subdomain->cheby.order = value;
+        }
+        else if (s == "inner_chebyshev_lower_permille")
+        {
+            if (!p->subdomain) return fail("problem was created without a Subdomain");
+            if (value < 1 || value > 999) return fail("inner_chebyshev_lower_permille must lie in 1..999, got %d", value);
+            if (!(value / 1000.0 < p->subdomain->cheby.upper)) return fail("inner_chebyshev_lower_permille %d is not below the upper factor %g", value, p->subdomain->cheby.upper);
+            p->subdomain->cheby.lower = value / 1000.0;
+        }
+        else if (s == "chebyshev_kernels" || s == "fused_chebyshev")
+        {
+            // chebyshev_kernels: a step of the Chebyshev-Jacobi solve as one launch of fdd_cheby_step (default where the kernel
+            // library has it) or, 0, composed from vector_vector_addition / vector_diagonal_scaling_dev.  fused_chebyshev: the step
+            // as the epilogue of the gather in front of it where that applies (default likewise); 0: gather, then the step.
+            if (!p->subdomain) return fail("problem was created without a Subdomain");
+            const bool fused = s == "fused_chebyshev";
+            if (value != 0)
+                if (const char *missing = fdd::missing_chebyshev_entry(fused)) return fail("%s needs %s, which the loaded kernel library does not export", name, missing);
+            (fused ? p->subdomain->cheby.fused : p->subdomain->cheby.use_kernels) = value != 0;
         }
         else if (s == "amg_graph")
         {
@@ -1404,6 +1446,8 @@ int fddh_problem_solve(fddh_problem *p, int solver_id, const double *f, double *
     {
         if (int rc = rank_check(p)) return rc;
         if (!p || !f || !u) return fail("null argument");
+        if (p->subdomain && p->fine().use_preconditioner)
+            if (const char *why = inner_solver_refusal(p)) return fail("%s", why);
         Domain<SType> &d = p->fine();
         const size_t bytes = (size_t)d.num_local_points * sizeof(double);
         p->a.copyFrom(f, bytes);
@@ -1443,6 +1487,8 @@ int fddh_problem_solve_timed(fddh_problem *p, int solver_id, const double *f, do
     {
         if (int rc = rank_check(p)) return rc;
         if (!p || !f || !seconds) return fail("null argument");
+        if (p->subdomain && p->fine().use_preconditioner)
+            if (const char *why = inner_solver_refusal(p)) return fail("%s", why);
         Domain<SType> &d = p->fine();
         const size_t bytes = (size_t)d.num_local_points * sizeof(double);
         p->a.copyFrom(f, bytes);
@@ -1554,6 +1600,8 @@ int fddh_problem_solve_projected(fddh_problem *p, int solver_id, const double *f
     {
         if (int rc = rank_check(p)) return rc;
         if (!p || !f || !u) return fail("null argument");
+        if (p->subdomain && p->fine().use_preconditioner)
+            if (const char *why = inner_solver_refusal(p)) return fail("%s", why);
         Domain<SType> &d = p->fine();
         const size_t bytes = (size_t)d.num_local_points * sizeof(double);
         p->a.copyFrom(f, bytes);
@@ -1597,6 +1645,7 @@ int fddh_problem_precond_apply(fddh_problem *p, int type, const double *r, doubl
         if (!p || !r || !z) return fail("null argument");
         if (!p->subdomain) return fail("problem was created without a Subdomain");
         Domain<SType> &d = p->fine();
+        if (const char *why = inner_solver_refusal(p)) return fail("%s", why);
         const size_t bytes = (size_t)d.num_local_points * sizeof(double);
         p->a.copyFrom(r, bytes);
         if (type == 0)
@@ -1696,6 +1745,75 @@ int fddh_problem_sub_jacobi_diagonal(fddh_problem *p, double *out, int n)
     }
 }
 
+int fddh_problem_sub_dof_solve(fddh_problem *p, const double *fa, double *ua, int n)
+{
+    try
+    {
+        if (int rc = rank_check(p)) return rc;
+        if (!p || !fa || !ua) return fail("null argument");
+        if (!p->subdomain) return fail("problem was created without a Subdomain");
+        Subdomain<PType> &s = *p->subdomain;
+        if (const char *why = inner_solver_refusal(p)) return fail("%s", why);
+        if (not s.dof_space_available()) return fail("the inner iteration of this problem does not run in dof space");
+        if (n != s.dof_count()) return fail("dof vectors have %d entries, got %d", s.dof_count(), n);
+        s.host_solve_dofs(ua, fa);
+        return 0;
+    }
+    catch (const std::exception &e)
+    {
+        return fail("%s", e.what());
+    }
+}
+
+int fddh_problem_inner_chebyshev_configure(fddh_problem *p, int order, double lower, double upper, int power_iterations)
+{
+    try
+    {
+        if (int rc = rank_check(p)) return rc;
+        if (!p) return fail("null argument");
+        if (!p->subdomain) return fail("problem was created without a Subdomain");
+        if (order < 1 || order > 16) return fail("the Chebyshev order must lie in 1..16, got %d", order);
+        if (!(lower > 0.0) || !(upper > lower) || !std::isfinite(upper)) return fail("the Chebyshev interval needs 0 < lower < upper, got [%g, %g]", lower, upper);
+        if (power_iterations < 1 || power_iterations > 10000) return fail("power_iterations must lie in 1..10000, got %d", power_iterations);
+        auto &c = p->subdomain->cheby;
+        c.order = order;
+        c.lower = lower;
+        c.upper = upper;
+        if (power_iterations != c.power_iterations) c.lambda = 0.0; // the estimate belongs to its iteration count; the factors do not touch it
+        c.power_iterations = power_iterations;
+        return 0;
+    }
+    catch (const std::exception &e)
+    {
+        return fail("%s", e.what());
+    }
+}
+
+int fddh_problem_inner_chebyshev_info(fddh_problem *p, int *order, double *lower, double *upper, double *lambda, int *power_iterations)
+{
+    try
+    {
+        if (int rc = rank_check(p)) return rc;
+        if (!p) return fail("null argument");
+        if (!p->subdomain) return fail("problem was created without a Subdomain");
+        Subdomain<PType> &s = *p->subdomain;
+        if (lambda)
+        {
+            if (not s.dof_space_available()) return fail("the inner iteration of this problem does not run in dof space: there is no operator to bound");
+            *lambda = s.chebyshev_lambda();
+        }
+        if (order) *order = s.cheby.order;
+        if (lower) *lower = s.cheby.lower;
+        if (upper) *upper = s.cheby.upper;
+        if (power_iterations) *power_iterations = s.cheby.power_iterations;
+        return 0;
+    }
+    catch (const std::exception &e)
+    {
+        return fail("%s", e.what());
+    }
+}
+
 int fddh_problem_sub_residual_norm(fddh_problem *p, const double *r, double *norm)
 {
     try
@@ -1719,6 +1837,8 @@ int fddh_problem_pcg_begin(fddh_problem *p, const double *f)
     {
         if (int rc = rank_check(p)) return rc;
         if (!p || !f) return fail("null argument");
+        if (p->subdomain && p->fine().use_preconditioner)
+            if (const char *why = inner_solver_refusal(p)) return fail("%s", why);
         Domain<SType> &d = p->fine();
         p->a.copyFrom(f, (size_t)d.num_local_points * sizeof(double));
         if (p->subdomain && d.use_preconditioner)
@@ -1739,6 +1859,8 @@ int fddh_problem_pcg_steps(fddh_problem *p, int steps, double *last_residual)
     {
         if (int rc = rank_check(p)) return rc;
         if (!p || steps < 0) return fail("bad argument");
+        if (p->subdomain && p->fine().use_preconditioner)
+            if (const char *why = inner_solver_refusal(p)) return fail("%s", why);
         Domain<SType> &d = p->fine();
         double r = std::numeric_limits<double>::quiet_NaN();
         if (p->subdomain && d.use_preconditioner)

@@ -26,6 +26,8 @@
  *                        (subdomain.hpp:229-230 num_vectors = max_iterations;
  *                        run.py:151-152 sweeps 1, 2, 4, 8; default 4)
  *     --inner-solver fcg|gmres   domain.hpp:116 preconditioner_type (run.py:150)
+ *     --inner-solver chebyshev   the Chebyshev-Jacobi inner solve of this build (flag "inner_solver" = 1; --inner K
+ *                        is then its order); needs --no-amg, which it runs with point-Jacobi's diagonal
  *     --vcycles V        subdomain.hpp:236 num_vcycles (run.py:153)
  *     --cheby C          subdomain.hpp:237 cheby_order, 1..4 (run.py:154)
  *     --float            the preconditioner in single precision
@@ -153,7 +155,7 @@ int main(int argc, char *argv[])
     int block_local = 0;
     const char *write_dir = nullptr;
     double kershaw_eps = 1.0;
-    int inner_steps = 0, inner_solver = -1, vcycles = 0, cheby = 0, single = 0;
+    int inner_steps = 0, inner_solver = -1, vcycles = 0, cheby = 0, single = 0, inner_chebyshev = 0;
     for (int a = 6; a < argc; a++)
     {
         if (!strcmp(argv[a], "--box") && a + 3 < argc)
@@ -166,7 +168,11 @@ int main(int argc, char *argv[])
         else if (!strcmp(argv[a], "--inner") && a + 1 < argc)
             inner_steps = atoi(argv[++a]);
         else if (!strcmp(argv[a], "--inner-solver") && a + 1 < argc)
-            inner_solver = !strcmp(argv[++a], "fcg") ? 0 : 1;
+        {
+            a++;
+            inner_chebyshev = !strcmp(argv[a], "chebyshev");
+            if (!inner_chebyshev) inner_solver = !strcmp(argv[a], "fcg") ? 0 : 1;
+        }
         else if (!strcmp(argv[a], "--vcycles") && a + 1 < argc)
             vcycles = atoi(argv[++a]);
         else if (!strcmp(argv[a], "--cheby") && a + 1 < argc)
@@ -240,6 +246,12 @@ int main(int argc, char *argv[])
         if (cheby > 0 && fddh_problem_set_flag(problem, "amg_cheby_order", cheby)) die("amg_cheby_order");
         if (vcycles > 0 && fddh_problem_set_flag(problem, "amg_num_vcycles", vcycles)) die("amg_num_vcycles");
         if (single && fddh_problem_set_flag(problem, "preconditioner_precision", 32)) die("preconditioner_precision");
+        if (inner_chebyshev)
+        {
+            if (fddh_problem_set_flag(problem, "inner_solver", 1)) die("fddh_problem_set_flag");
+            if (inner_steps > 0 && fddh_problem_set_flag(problem, "inner_chebyshev_order", inner_steps)) die("fddh_problem_set_flag");
+            inner_steps = 0;
+        }
         if ((inner_steps > 0 || inner_solver >= 0) && fddh_problem_set_options(problem, -1, NAN, -1, -1, inner_solver, inner_steps > 0 ? inner_steps : -1, inner_steps > 0 ? inner_steps : -1, -1)) die("fddh_problem_set_options");
     }
 

@@ -28,6 +28,19 @@ inline void gather_indexed(double *out, const double *in, const int *index, int 
 inline void gather_indexed(float *out, const float *in, const int *index, int n, void *s) { FDD_CALL(fdd_gather_indexed_f32(out, in, index, n, s)); }
 inline void scatter_add_indexed(double *y, const int *index, const double *t, int n, void *s) { FDD_CALL(fdd_scatter_add_indexed(y, index, t, n, s)); }
 inline void scatter_add_indexed(float *y, const int *index, const float *t, int n, void *s) { FDD_CALL(fdd_scatter_add_indexed_f32(y, index, t, n, s)); }
+inline void copy(double *u, const double *v, int n, void *s) { FDD_CALL(fdd_memcpy_d2d(u, v, (size_t)n * sizeof(double), s)); }
+inline void copy(float *u, const float *v, int n, void *s) { FDD_CALL(fdd_memcpy_d2d(u, v, (size_t)n * sizeof(float), s)); }
+// one step of the Chebyshev-Jacobi inner solve as one pass (Subdomain::chebyshev_dofs)
+inline void cheby_step(double *x, double *d, double *r_out, const double *r_in, const double *q, const double *dinv, double c_d, double c_r, bool first, bool last, int n, void *s)
+{
+    ProfileScope prof("ew_vec2_kernel<ChebyStep>", 8.0 * n * (first ? 4 : (last ? 6 : 8)));
+    FDD_CALL(fdd_cheby_step(x, d, r_out, r_in, q, dinv, c_d, c_r, first ? 1 : 0, last ? 1 : 0, n, s));
+}
+inline void cheby_step(float *x, float *d, float *r_out, const float *r_in, const float *q, const float *dinv, double c_d, double c_r, bool first, bool last, int n, void *s)
+{
+    ProfileScope prof("cheby_step_f32_kernel", 4.0 * n * (first ? 4 : (last ? 6 : 8)));
+    FDD_CALL(fdd_cheby_step_f32(x, d, r_out, r_in, q, dinv, (float)c_d, (float)c_r, first ? 1 : 0, last ? 1 : 0, n, s));
+}
 
 // ---- the Arnoldi step's reductions: out[k] = <a, s_k b_k>, and dst = y + sign sum c_k (s_k x_k) with |dst|^2 ----
 // w: the norm weight of the dofs (null: 1 everywhere, not read).  The float entries take none.

@@ -43,6 +43,7 @@
 #include <algorithm>
 #include <cmath>
 #include <map>
+#include <stdexcept>
 #include <unordered_map>
 #include <chrono>
 #include <vector>
@@ -1054,6 +1055,44 @@ class Subdomain
         ensure_jacobi();
         return jacobi_diag_hst;
     }
+
+    // The operator under the diagonal has changed (a level's D_hat, the arithmetic of the element kernels): the diagonal, its
+    // inverses and the eigenvalue bound of the Chebyshev inner solve are made again at their next use.  D != nullptr: the
+    // table of the level of that degree, whose host copy this class keeps (the device table is the Domain's own).
+    void operator_changed(int degree = -1, const double *D = nullptr, int n = 0)
+    {
+        for (int l = 0; D != nullptr and l < num_levels; l++)
+            if (poly_degree[l] == degree) D_hat[l].first.assign(D, D + (size_t)n * n);
+        jacobi_dinv.free();
+        jacobi_dinv_f32.free();
+        jacobi_diag_hst.clear();
+        cheby.lambda = 0.0;
+        operator_generation++;
+    }
+
+    // ---- Chebyshev-Jacobi inner solve (chebyshev_dofs below): a LABELLED OPTION of this build, off by default ----
+    int inner_solver = 0; // 0: the inner FCG / GMRES(m) as in the reference; 1: a fixed Chebyshev polynomial in D^-1 A
+    bool chebyshev() const { return inner_solver == 1; }
+    struct ChebyshevOptions
+    {
+        int order = 4;                   // m: m diagonal scalings, m - 1 operator applications
+        double lower = 0.1, upper = 1.1; // the interval [lower, upper] * lambda
+        int power_iterations = 25;
+        bool use_kernels = true; // fdd_cheby_step where the library has it; false: composed from the entries that were there before
+        bool fused = true;       // the step as the epilogue of the gather Qt where that applies (conforming region, unit norm weight)
+        double lambda = 0.0;     // Rayleigh quotient of D^-1/2 A D^-1/2 after power_iterations steps; 0: not computed yet
+    } cheby;
+    template <typename Real>
+    struct ChebyVectors
+    {
+        fdd::memory d, r, q, t, x, f; // direction, residual, A d, scratch of the composed step; x, f: the float solve's own
+        fdd::memory w;                // 1 / (theta diag): the first step's scaling, rounded once more than fa / (theta diag) itself
+        double w_theta = 0.0;
+        int w_generation = -1, na = 0;
+    };
+    ChebyVectors<double> cheby64;
+    ChebyVectors<float> cheby32;
+    int operator_generation = 0; // counts operator_changed(): what was derived from the diagonal knows whether it still holds
     DType tolerance = 1.0e-12;
     DType epsilon = 1.0e-12;
 
@@ -1867,6 +1906,7 @@ class Subdomain
     // subdomain.tpp:4161-4268
     void flexible_conjugate_gradient(fdd::memory &u_l, fdd::memory &f_l, bool print_history = true, bool use_relative = false)
     {
+        if (inner_solver == 1) return generalized_minimum_residual(u_l, f_l, print_history, use_relative); // Chebyshev-Jacobi takes the place of either Krylov solve
         residual_history.clear();
         history_pending = false; // a lazy solve before this one (pcg_steps) may have left its history on the device: it is not this solve's
         tree_operator(r_k, f_l);
@@ -2139,6 +2179,7 @@ class Subdomain
     // nobody uses and the update takes the columns the reference would have taken.
     void gmres_dofs_device(fdd::memory &ua, fdd::memory &fa, bool print_history, bool use_relative)
     {
+        if (inner_solver == 1) return chebyshev_dofs(ua, fa);
         if (precision == 32)
             gmres_dofs_device_t(krylov32, ua, fa, print_history, use_relative);
         else
@@ -2309,6 +2350,178 @@ class Subdomain
         num_iterations += iter;
     }
 
+    // ------------------------------------------------------------------
+    // CHEBYSHEV-JACOBI inner solve -- a LABELLED OPTION of this build (inner_solver = 1), not in the reference, which runs
+    // the Chebyshev recurrence on the CSR levels of the V-cycle only (subdomain.tpp:19-83).  u~ = p_m(D^-1 A) D^-1 f~ with
+    // p_m the Chebyshev polynomial of the interval [lower, upper] * lambda, D the exact diagonal of ensure_jacobi and
+    // lambda a Rayleigh quotient of D^-1/2 A D^-1/2 (chebyshev_lambda).  From x = 0, with theta = (a + b)/2,
+    // delta = (b - a)/2, sigma = theta/delta, rho_0 = 1/sigma:
+    //   k = 0       : d = w .* f, w = 1 / (theta diag) formed once on the host     x = d
+    //                 (one rounding fewer than (1/theta) (dinv .* f): the order-1 solve is within 1 ulp of f / (theta diag))
+    //   k = 1..m-1  : r = r_prev - A d (r_prev = f at k = 1: f is never written)
+    //                 rho_k = 1/(2 sigma - rho_{k-1});  d = rho_k rho_{k-1} d + (2 rho_k/delta) D^-1 r;   x = x + d
+    // m diagonal scalings, m - 1 operator applications, no inner product, no host synchronisation: M^-1 is a fixed,
+    // symmetric, linear operator.  The coefficients are formed here in double and passed by value.  One pass per step
+    // (fdd_cheby_step), in a conforming region as the epilogue of the gather Qt that ends the operator application
+    // (fdd_csr_plan_gather_cheby), or composed from vector_vector_addition / diagonal_scaling where the kernel library
+    // has neither: the same bits in all three.  The history stays empty; known_rhs_norm2_dev and defer_final_update are
+    // not looked at (x is written in place, no update is left pending).
+    // ------------------------------------------------------------------
+    // why this problem cannot run it, or nullptr
+    const char *chebyshev_refusal() const
+    {
+        if (use_preconditioner) return "inner_solver = 1 (Chebyshev-Jacobi) with sub_use_preconditioner = 1: the Chebyshev iteration around the V-cycle is not part of this build (use sub_use_preconditioner 0 or 2)";
+        if (not dof_space_available()) return "inner_solver = 1 (Chebyshev-Jacobi) needs the dof-space inner solve: a 3-D region with assembled_inner_solve = 1";
+        return nullptr;
+    }
+
+    // lambda: the Rayleigh quotient after cheby.power_iterations steps of the power iteration on S A S, S = 1/sqrt(diag) -- the
+    // launch sequence of device_lambda_max with operator_dofs in place of the SpMV.  The region is the rank's own operator: no
+    // communication.  Kept until the operator changes (operator_changed) or the iteration count does.
+    double chebyshev_lambda()
+    {
+        if (cheby.lambda > 0.0) return cheby.lambda;
+        ensure_jacobi();
+        const int nd = dof_space_size(), na = std::max(dof_alloc_size(), 1);
+        if (nd <= 0 or cheby.power_iterations <= 0) return cheby.lambda = 1.0;
+        fdd::device_t &dv = fdd::dev();
+        void *stream = dv.stream;
+        std::vector<double> s_hst(nd);
+        for (int i = 0; i < nd; i++) s_hst[i] = 1.0 / std::sqrt(jacobi_diag_hst[i]);
+        fdd::memory S = dv.malloc<double>(nd), v = dv.malloc<double>(nd), vn = dv.malloc<double>(nd), t = dv.malloc<double>(na), w = dv.malloc<double>(na);
+        fdd::memory ws = dv.malloc<double>(fdd_reduce_workspace_doubles()), sc = dv.malloc<double>(2);
+        S.copyFrom(s_hst.data(), (size_t)nd * sizeof(double));
+        {
+            const std::vector<double> start = fdd::low_order::power_iteration_start(nd);
+            v.copyFrom(start.data(), (size_t)nd * sizeof(double));
+        }
+        FDD_CALL(fdd_set_to_value(t.as<double>(), 0.0, na, 0, stream));
+        double *scp = sc.as<double>();
+        for (int it = 0; it < cheby.power_iterations; it++)
+        {
+            FDD_CALL(fdd_sub_inner_product(scp, ws.as<double>(), v.as<double>(), v.as<double>(), nd, stream));
+            FDD_CALL(fdd_vector_scaling_rsqrt_dev(vn.as<double>(), scp, v.as<double>(), nd, stream));                          // vn = v / |v|
+            FDD_CALL(fdd_vector_diagonal_scaling_dev(t.as<double>(), S.as<double>(), nullptr, vn.as<double>(), nd, stream)); // t = S vn
+            operator_dofs(w.as<double>(), t.as<double>());
+            FDD_CALL(fdd_vector_diagonal_scaling_dev(v.as<double>(), S.as<double>(), nullptr, w.as<double>(), nd, stream)); // v = S A S vn
+            FDD_CALL(fdd_sub_inner_product(scp + 1, ws.as<double>(), v.as<double>(), vn.as<double>(), nd, stream));
+        }
+        double lambda = 1.0;
+        sc.slice(1, 1).copyTo(&lambda, sizeof(double));
+        for (fdd::memory *m : {&S, &v, &vn, &t, &w, &ws, &sc}) m->free();
+        if (not(lambda > 0.0) or not std::isfinite(lambda)) throw std::runtime_error("Chebyshev-Jacobi inner solve: the power iteration gave no positive eigenvalue estimate");
+        return cheby.lambda = lambda;
+    }
+
+    void chebyshev_dofs(fdd::memory &ua, fdd::memory &fa)
+    {
+        if (const char *why = chebyshev_refusal()) throw std::runtime_error(why);
+        if (precision == 32)
+            chebyshev_dofs_t(cheby32, ua, fa);
+        else
+            chebyshev_dofs_t(cheby64, ua, fa);
+    }
+
+    // ua_io / fa_io are double either way (Real = float: the casts of subdomain.okl:268-282 at the two ends); fa_io is read only
+    template <typename Real>
+    void chebyshev_dofs_t(ChebyVectors<Real> &C, fdd::memory &ua_io, fdd::memory &fa_io)
+    {
+        constexpr bool f32 = std::is_same<Real, float>::value;
+        namespace ops = fdd::ops;
+        const int nd = dof_space_size(), na = std::max(dof_alloc_size(), 1), m = cheby.order;
+        void *stream = fdd::dev().stream;
+        const double lambda = chebyshev_lambda(); // makes the diagonal too
+        if constexpr (f32) prepare_single_precision();
+        if (C.na != na)
+        {
+            for (fdd::memory *v : {&C.d, &C.r, &C.q, &C.t, &C.x, &C.f, &C.w}) v->free();
+            for (fdd::memory *v : {&C.d, &C.r, &C.q, &C.t}) *v = fdd::dev().malloc<Real>(na); // d is an operator input: in a composite the copies and hanging values sit behind its dofs
+            if (f32) C.x = fdd::dev().malloc<Real>(na), C.f = fdd::dev().malloc<Real>(na);
+            ops::set_to_zero(C.d.template as<Real>(), na, stream);
+            C.na = na;
+        }
+        if constexpr (f32) FDD_CALL(fdd_sub_copy_f32_f64(C.f.template as<float>(), fa_io.as<double>(), nd, stream));
+        Real *x = (f32 ? C.x : ua_io).template as<Real>(), *d = C.d.template as<Real>(), *r = C.r.template as<Real>(), *q = C.q.template as<Real>(), *t = C.t.template as<Real>();
+        const Real *f = (f32 ? C.f : fa_io).template as<Real>();
+        const Real *dinv = (f32 ? jacobi_dinv_f32 : jacobi_dinv).template as<Real>();
+        residual_history.clear();
+        history_pending = false;
+
+        const bool kernels = cheby.use_kernels and fdd::missing_chebyshev_entry(false) == nullptr;
+        // the float gather takes no norm weight; the double one may: then the separate pass stays
+        const bool fused = kernels and cheby.fused and not is_composite and (f32 or norm_weight_is_one) and subdomain_operator.Qt.num_rows == nd and subdomain_operator.Qt.gather_cheby_applies();
+        const double a = cheby.lower * lambda, b = cheby.upper * lambda, theta = 0.5 * (a + b), delta = 0.5 * (b - a), sigma = theta / delta;
+        double rho = 1.0 / sigma;
+
+        // k = 0, with the scaling 1 / (theta diag) of this interval and this diagonal and the factor 1
+        if (not C.w.ptr() or C.w_theta != theta or C.w_generation != operator_generation)
+        {
+            std::vector<Real> w_hst(std::max(nd, 1), Real(1));
+            for (int i = 0; i < nd; i++) w_hst[i] = (Real)(1.0 / (theta * jacobi_diag_hst[i]));
+            if (not C.w.ptr()) C.w = fdd::dev().malloc<Real>(w_hst.size());
+            C.w.copyFrom(w_hst.data(), w_hst.size() * sizeof(Real));
+            C.w_theta = theta;
+            C.w_generation = operator_generation;
+        }
+        const Real *w = C.w.template as<Real>();
+        if (kernels)
+            ops::cheby_step(x, d, (Real *)nullptr, f, (const Real *)nullptr, w, 0.0, 1.0, true, m == 1, nd, stream);
+        else
+        {
+            ops::diagonal_scaling_dev(t, w, nullptr, f, nd, stream);
+            ops::vector_vector_addition(m == 1 ? x : d, (Real)1, t, (Real)0, t, nd, stream);
+            if (m > 1) ops::copy(x, d, nd, stream);
+        }
+        for (int k = 1; k < m; k++)
+        {
+            const double rho_k = 1.0 / (2.0 * sigma - rho), c_d = rho_k * rho, c_r = 2.0 * rho_k / delta;
+            const Real *r_in = k == 1 ? f : r;
+            const bool last = k == m - 1;
+            if (fused)
+            {
+                Real *q_pts = (f32 ? sp.q_pts : q_k).template as<Real>();
+                stiffness_from_dofs(q_pts, d);
+                subdomain_operator.Qt.gather_cheby(x, d, r, q_pts, r_in, dinv, c_d, c_r, last);
+            }
+            else
+            {
+                operator_dofs(q, d);
+                if (kernels)
+                    ops::cheby_step(x, d, r, r_in, q, dinv, c_d, c_r, false, last, nd, stream);
+                else
+                {
+                    Real *rr = last ? t : r; // the last step stores neither r nor d
+                    ops::vector_vector_addition(rr, (Real)1, r_in, (Real)-1, q, nd, stream);
+                    ops::diagonal_scaling_dev(t, dinv, nullptr, rr, nd, stream);
+                    Real *dn = last ? t : d;
+                    ops::vector_vector_addition(dn, (Real)c_d, d, (Real)c_r, t, nd, stream);
+                    ops::vector_vector_addition(x, (Real)1, x, (Real)1, dn, nd, stream);
+                }
+            }
+            rho = rho_k;
+        }
+        if constexpr (f32) FDD_CALL(fdd_sub_copy_f64_f32(ua_io.as<double>(), x, nd, stream));
+        num_iterations += m;
+    }
+
+    // test hook: the configured inner solve on host dof vectors of dof_count() values
+    void host_solve_dofs(double *ua_hst, const double *fa_hst)
+    {
+        const int nd = dof_space_size(), na = std::max(dof_alloc_size(), 1);
+        fdd::memory fa = fdd::dev().malloc<DType>(na), ua = fdd::dev().malloc<DType>(na);
+        FDD_CALL(fdd_set_to_value(fa.as<double>(), 0.0, na, 0, fdd::dev().stream));
+        FDD_CALL(fdd_set_to_value(ua.as<double>(), 0.0, na, 0, fdd::dev().stream));
+        fa.copyFrom(fa_hst, (size_t)nd * sizeof(DType));
+        if (is_composite)
+            gmres_dofs_device(ua, fa, false, false);
+        else
+            gmres_dofs(ua, fa, false, false);
+        finish_history();
+        ua.copyTo(ua_hst, (size_t)nd * sizeof(DType));
+        fa.free();
+        ua.free();
+    }
+
     // the solve itself, dof vectors in and out (callers that already hold assembled data skip Qt / Q)
     void gmres_dofs(fdd::memory &ua, fdd::memory &fa, bool print_history = true, bool use_relative = false)
     {
@@ -2318,6 +2531,7 @@ class Subdomain
             fprintf(stderr, "ERROR: an inner solve's deferred final update was dropped\n");
             exit(EXIT_FAILURE);
         }
+        if (inner_solver == 1) return chebyshev_dofs(ua, fa);
         if (device_bookkeeping and num_vectors <= FDD_MULTI_MAX)
         {
             gmres_dofs_device(ua, fa, print_history, use_relative);
@@ -2413,6 +2627,8 @@ class Subdomain
     // subdomain.tpp:4309-4489
     void generalized_minimum_residual(fdd::memory &u_l, fdd::memory &f_l, bool print_history = true, bool use_relative = false)
     {
+        if (inner_solver == 1)
+            if (const char *why = chebyshev_refusal()) throw std::runtime_error(why);
         if ((assembled_inner and can_assemble()) or composite_dof_space())
         {
             gmres_assembled(u_l, f_l, print_history, use_relative);

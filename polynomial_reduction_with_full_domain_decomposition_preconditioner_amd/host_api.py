@@ -522,6 +522,28 @@ class Problem:
         _H().call("fddh_problem_sub_jacobi_diagonal", self.h, _dp(d), n)
         return d
 
+    def sub_dof_solve(self, fa):
+        """ua = the configured inner solve (GMRES(m), or Chebyshev-Jacobi with the flag "inner_solver" = 1) of the dof-space
+        right-hand side fa, from a zero start"""
+        fa = np.ascontiguousarray(fa, dtype=np.float64)
+        ua = np.zeros(len(fa))
+        _H().call("fddh_problem_sub_dof_solve", self.h, _dp(fa), _dp(ua), len(fa))
+        return ua
+
+    # --- Chebyshev-Jacobi inner solve (an addition of this build, include/fdd_host.h) ---
+    def inner_chebyshev(self, order=None, lower=None, upper=None, power_iterations=None):
+        """Settings of the Chebyshev-Jacobi inner solve (switched on by set_flag("inner_solver", 1)); None keeps a value."""
+        o, lo, up, it = ctypes.c_int(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
+        _H().call("fddh_problem_inner_chebyshev_info", self.h, ctypes.byref(o), ctypes.byref(lo), ctypes.byref(up), None, ctypes.byref(it))
+        _H().call("fddh_problem_inner_chebyshev_configure", self.h, int(o.value if order is None else order), ctypes.c_double(lo.value if lower is None else lower),
+                  ctypes.c_double(up.value if upper is None else upper), int(it.value if power_iterations is None else power_iterations))
+
+    def inner_chebyshev_info(self):
+        """{"order", "lower", "upper", "lambda", "power_iterations"}; lambda is computed now if it is not cached"""
+        o, lo, up, lam, it = ctypes.c_int(), ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
+        _H().call("fddh_problem_inner_chebyshev_info", self.h, ctypes.byref(o), ctypes.byref(lo), ctypes.byref(up), ctypes.byref(lam), ctypes.byref(it))
+        return {"order": o.value, "lower": lo.value, "upper": up.value, "lambda": lam.value, "power_iterations": it.value}
+
     def sub_dof_rhs(self, r):
         """the dof-space right-hand side of the inner solve for the outer point vector r (collective on a composite)"""
         n = self.sub_info()["unique_dofs"]
