@@ -98,7 +98,8 @@ int fdd_csr_plan_kind(const fdd_csr_plan *plan, int *kind); /* 0 = thread-per-ro
 int fdd_csr_plan_pipelined(const fdd_csr_plan *plan, int *pipelined); /* 1: a short-row plan whose SpMV / gather entries run on the persistent, software-pipelined kernel (profile labels) */
 /* Tell the plan that every stored value is exactly 1.0 (the boolean gather / scatter matrices Q, Qt,
  * Q_int, ...; CSR_Matrix::assemble checks its host values): the kernels then skip the val array --
- * 1.0*x is x, so results are unchanged and 8 of the 12 bytes per non-zero are not moved. */
+ * 1.0*x is x, so results are unchanged and 8 of the 12 bytes per non-zero are not moved.  A plan of either
+ * precision (fdd_csr_plan_create_f32: what fdd_csr_plan_gather_cheby_f32 runs on). */
 int fdd_csr_plan_set_unit_values(fdd_csr_plan *plan, int unit_values);
 /* Give the plan a sliced-ELL copy of the matrix (slices of 64 rows, column-major, padded to the slice's longest row)
  * when that costs at most max_padding times the stored entries and no row exceeds 64 entries: the form for the
@@ -323,7 +324,9 @@ int fdd_projection_store(double *Xk, double *AXk, const double *x, const double 
  * fdd_csr_plan_gather_cheby: a later step with q = Qt u formed by the kernel itself, u the point vector and Qt a boolean
  * gather matrix whose plan runs on the persistent pipelined kernel (fdd_csr_plan_pipelined; any other plan is an error):
  * q never goes through memory.  Rows are summed in column order, as fdd_csr_plan_dssum mode 1 sums them: same bits as the
- * gather followed by fdd_cheby_step.  u must not alias x, d or r_out. */
+ * gather followed by fdd_cheby_step.  u must not alias x, d or r_out.  Each entry takes a plan of its own precision, as the
+ * SpMV entries do: fdd_csr_plan_gather_cheby refuses a plan of fdd_csr_plan_create_f32 and fdd_csr_plan_gather_cheby_f32
+ * refuses any other (no value is read; the row blocks of the two plans of one short-row matrix are the same). */
 int fdd_cheby_step(double *x, double *d, double *r_out, const double *r_in, const double *q, const double *dinv, double c_d, double c_r, int first, int last, int n, void *stream);
 int fdd_cheby_step_f32(float *x, float *d, float *r_out, const float *r_in, const float *q, const float *dinv, float c_d, float c_r, int first, int last, int n, void *stream);
 int fdd_csr_plan_gather_cheby(const fdd_csr_plan *plan, double *x, double *d, double *r_out, const int *Qt_ptr, const int *Qt_col, const double *u, const double *r_in, const double *dinv, double c_d, double c_r, int last, void *stream);

@@ -60,8 +60,8 @@ void with_block_nnz(int block_nnz, F &&f)
     else
         f(std::integral_constant<int, kBlockNnzMax>{});
 }
-// ... and whether every stored value is 1.0.  kMayBeUnit = false: there is no UNIT instantiation to choose (csr_block_kernel on float: a plan of the f32 entries
-// never has unit values, fdd_csr_plan_set_unit_values)
+// ... and whether every stored value is 1.0.  kMayBeUnit = false: there is no UNIT instantiation to choose (csr_block_kernel on float: the f32 SpMV entries run
+// on the AMG's matrices; a unit-value plan given to them has its 1.0 values read, 1.0*x is x)
 template <bool kMayBeUnit = true, typename F>
 void with_unit(bool unit, F &&f)
 {
@@ -1535,7 +1535,8 @@ int fdd_csr_plan_gather_f32(const fdd_csr_plan *plan, float *t, const int *Qt_pt
 // x = x + d', d' = c_d*d + c_r*(dinv .* (r_in - Qt u)), r_out = r_in - Qt u over every row of a boolean gather matrix: one
 // later step of the Chebyshev-Jacobi inner solve with the gather as the kernel's front half (EpiChebyStepT).  On the
 // persistent pipelined kernel only (fdd_csr_plan_pipelined): any other plan is refused and the caller launches the gather
-// and fdd_cheby_step one after the other.  The plan's value type is not looked at: no value is read (as fdd_csr_plan_gather_f32).
+// and fdd_cheby_step one after the other.  No value is read, yet each entry takes a plan of its own precision only, as the
+// SpMV entries do (plan_launch): fdd_csr_plan_create for the fp64 entry, fdd_csr_plan_create_f32 for the f32 one.
 } // extern "C"
 template <typename T>
 static int plan_gather_cheby(const fdd_csr_plan *plan, T *x, T *d, T *r_out, const int *Qt_ptr, const int *Qt_col, const T *u, const T *r_in, const T *dinv, T c_d, T c_r, int last, void *stream)
@@ -1544,9 +1545,15 @@ static int plan_gather_cheby(const fdd_csr_plan *plan, T *x, T *d, T *r_out, con
     if (plan->num_rows == 0) return 0;
     FDD_REQUIRE(x != nullptr && d != nullptr && Qt_ptr != nullptr && Qt_col != nullptr && u != nullptr && r_in != nullptr && dinv != nullptr && (last || r_out != nullptr));
     FDD_REQUIRE((const void *)u != (const void *)x && (const void *)u != (const void *)d && (const void *)u != (const void *)r_out);
+    constexpr bool kDouble = std::is_same<T, double>::value;
+    if (plan->value_bytes != (int)sizeof(T))
+    {
+        fdd_set_error("%s", kDouble ? "fdd_csr_plan_gather_cheby: a plan of fdd_csr_plan_create_f32" : "fdd_csr_plan_gather_cheby_f32: not a plan of fdd_csr_plan_create_f32");
+        return FDD_ERR_INVALID_ARGUMENT;
+    }
     if (!(plan->unit_values && plan->sell_slices == 0 && launch_short_pipelined<T>(plan, x, Qt_ptr, Qt_col, (const T *)nullptr, u, EpiChebyStepT<T>{r_in, dinv, r_out, d, c_d, c_r, last ? 1 : 0}, BlockRange{0, plan->num_blocks}, 0, plan->num_rows, fdd_stream(stream), true)))
     {
-        fdd_set_error("fdd_csr_plan_gather_cheby: not a unit-value plan of the pipelined short-row kernel");
+        fdd_set_error("fdd_csr_plan_gather_cheby%s: not a unit-value plan of the pipelined short-row kernel", kDouble ? "" : "_f32");
         return FDD_ERR_INVALID_ARGUMENT;
     }
     FDD_LAUNCH_CHECK();
@@ -1640,7 +1647,6 @@ int fdd_csr_plan_gather_weighted_norm2(const fdd_csr_plan *plan, double *out, do
 int fdd_csr_plan_set_unit_values(fdd_csr_plan *plan, int unit_values)
 {
     FDD_REQUIRE(plan != nullptr);
-    FDD_REQUIRE(plan->value_bytes == 8);
     plan->unit_values = unit_values != 0;
     return 0;
 }

@@ -33,6 +33,7 @@ class CSR_Matrix
     DType sparse_tolerance = 1.0e-12;
     std::vector<std::tuple<int, int, DType>> entries;
     fdd_csr_plan *plan = nullptr;
+    fdd_csr_plan *plan_f32 = nullptr; // the same row blocks as a plan of the f32 entries (prepare_gather_cheby_f32)
     int plan_kind = 0;
     bool plan_pipelined = false; // a short-row plan served by the persistent pipelined kernel (profile labels name the kernel that runs)
     bool lazy_identity = false; // initialize_identity(): the arrays do not exist yet
@@ -313,6 +314,8 @@ class CSR_Matrix
     void make_plan()
     {
         if (plan) FDD_CALL(fdd_csr_plan_destroy(plan));
+        if (plan_f32) FDD_CALL(fdd_csr_plan_destroy(plan_f32));
+        plan_f32 = nullptr;
         FDD_CALL(fdd_csr_plan_create(&plan, ptr_hst.data(), num_rows, num_cols, num_nnz));
         FDD_CALL(fdd_csr_plan_kind(plan, &plan_kind));
         {
@@ -449,10 +452,25 @@ class CSR_Matrix
         fdd::ProfileScope prof("csr_short_pipelined_kernel<gather, ChebyStep>", 4.0 * num_rows + 12.0 * num_nnz + 8.0 * num_rows * (last ? 5.0 : 7.0));
         FDD_CALL(fdd_csr_plan_gather_cheby(plan, x, d, r_out, ptr.as<int>(), col.as<int>(), u, r_in, dinv, c_d, c_r, last ? 1 : 0, fdd::dev().stream));
     }
+    // The float entry takes a plan of the f32 entries: made here, once, before the first float step (the row pointers come
+    // back from the device where release_host() dropped the host's).
+    void prepare_gather_cheby_f32()
+    {
+        if (plan_f32 or not gather_cheby_applies()) return;
+        std::vector<int> fetched;
+        if (ptr_hst.empty())
+        {
+            fetched.resize((size_t)num_rows + 1);
+            ptr.copyTo(fetched.data(), fetched.size() * sizeof(int));
+        }
+        FDD_CALL(fdd_csr_plan_create_f32(&plan_f32, (ptr_hst.empty() ? fetched : ptr_hst).data(), num_rows, num_cols, num_nnz));
+        FDD_CALL(fdd_csr_plan_set_unit_values(plan_f32, 1));
+    }
     void gather_cheby(float *x, float *d, float *r_out, const float *u, const float *r_in, const float *dinv, double c_d, double c_r, bool last)
     {
+        prepare_gather_cheby_f32();
         fdd::ProfileScope prof("csr_short_pipelined_kernel<gather, ChebyStep, f32>", 4.0 * num_rows + 8.0 * num_nnz + 4.0 * num_rows * (last ? 5.0 : 7.0));
-        FDD_CALL(fdd_csr_plan_gather_cheby_f32(plan, x, d, r_out, ptr.as<int>(), col.as<int>(), u, r_in, dinv, (float)c_d, (float)c_r, last ? 1 : 0, fdd::dev().stream));
+        FDD_CALL(fdd_csr_plan_gather_cheby_f32(plan_f32, x, d, r_out, ptr.as<int>(), col.as<int>(), u, r_in, dinv, (float)c_d, (float)c_r, last ? 1 : 0, fdd::dev().stream));
     }
 
     // out_dev[0] = sum_rows s*s*w with s = (this u)[row]*w[row]

@@ -1,8 +1,11 @@
 """The low-order AMG hierarchy built on the device ("amg_device_setup", csrc/fdd_amg_setup.hip) against the host build.
 
-The host setup (host/low_order.hpp) fixes the order of every sum, so the device build must reproduce it bit for bit:
-the kernels are checked against Python restatements of the host routines, and whole hierarchies against the host's,
-level by level, as uint64 bits."""
+The host setup (host/low_order.hpp) fixes the order of every sum, so the device build must reproduce it bit for bit.
+Held here: spgemm_count / _fill (against gustavson() below), transpose_count / _fill (against scipy), row_pointers (its
+overflow refusal), and whole hierarchies against the host's, level by level, as uint64 bits.  The other eleven setup
+entries -- fem_stencils / _count / _fill, inv_sqrt_diagonal, unit_values, the six lattice_* -- run here only inside those
+hierarchy builds; entry by entry they are held in test_gpu_amg_setup_kernels.py, against the restatements of
+tests/amg_setup_restatements.py."""
 import ctypes
 import os
 import tempfile

@@ -83,6 +83,231 @@ def test_step_kernel_equals_its_composition(gpu, n, dtype):
                 assert bool((whole[:base] == GUARD).all()) and bool((whole[base + n :] == GUARD).all()), case
 
 
+def boolean_gather_matrix(rows, seed):
+    """Qt of a gather, built here: row lengths from {0, 1, 2, 4, 8} and a few up to 27 (mean about 1.7: more than one entry
+    per row, so the plan has row blocks, fewer than four, so they are the short-row blocks of the pipelined kernel), runs of
+    empty rows -- one longer than the 1024 rows a block may hold, where there is room for it -- sorted distinct columns."""
+    rng = np.random.default_rng(seed)
+    length = rng.choice([0, 1, 2, 4, 8], size=rows, p=[0.3, 0.3, 0.25, 0.1, 0.05])
+    odd = rng.choice(rows, size=max(3, rows // 500), replace=False)
+    length[odd] = rng.integers(9, 28, len(odd))
+    for start, run in ((rows // 3, min(1100, rows // 8)), (rows // 2, 40), (rows - 7, 7)):
+        length[start : start + run] = 0
+    ptr = np.concatenate([[0], np.cumsum(length)]).astype(np.int32)
+    nnz = int(ptr[-1])
+    cols = max(256, nnz)
+    step = np.cumsum(rng.integers(1, 4, nnz))  # ascending inside every row, spans at most 3 * 27 columns
+    row_of = np.repeat(np.arange(rows), length)
+    base = rng.integers(0, cols - 3 * 27 - 1, rows)
+    col = (step - step[ptr[:-1][row_of]] + base[row_of]).astype(np.int32)
+    assert col.min() >= 0 and col.max() < cols and (np.diff(col)[np.diff(row_of) == 0] > 0).all()
+    return ptr, col, cols
+
+
+def row_sums_in_column_order(ptr, col, u):
+    """s = 0; s += u[col[j]] entry after entry, in u's own precision"""
+    s = np.zeros(len(ptr) - 1, u.dtype)
+    length = np.diff(ptr)
+    for j in range(int(length.max())):
+        on = length > j
+        s[on] = s[on] + u[col[ptr[:-1][on] + j]]
+    return s
+
+
+class Plan:
+    def __init__(self, ptr, cols, f32=False, unit=True):
+        self.h = ctypes.c_void_p()
+        self.ptr = np.ascontiguousarray(ptr, np.int32)
+        L = lib.hip()
+        L.call("fdd_csr_plan_create_f32" if f32 else "fdd_csr_plan_create", ctypes.byref(self.h), lib.ptr(self.ptr), len(ptr) - 1, cols, int(ptr[-1]))
+        if unit:
+            L.call("fdd_csr_plan_set_unit_values", self.h, 1)
+
+    def query(self, what):
+        out = ctypes.c_int(-1)
+        lib.hip().call("fdd_csr_plan_" + what, self.h, ctypes.byref(out))
+        return out.value
+
+    def close(self):
+        lib.hip().call("fdd_csr_plan_destroy", self.h)
+
+
+def guarded(values, dtype, gpu):
+    whole = torch.full((len(values) + 16,), GUARD, dtype=dtype, device=gpu)
+    whole[8 : 8 + len(values)] = torch.from_numpy(values).to(gpu)
+    return whole, whole[8 : 8 + len(values)]
+
+
+def guards_stand(whole):
+    return bool((whole[:8] == GUARD).all()) and bool((whole[-8:] == GUARD).all())
+
+
+# Row blocks of a short-row plan hold at most 1024 entries and the persistent kernel runs min(4 * 256, blocks) = 1024
+# workgroups (4 per CU), each taking the blocks b, b + 1024, ...: from 2049 blocks on every workgroup takes more than one.
+PERSISTENT_WORKGROUPS = 4 * 256
+GATHER_SIZES = {"one_block": 400, "several_blocks": 20_000, "two_blocks_per_workgroup": 1_400_000}
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=["double", "float"])
+@pytest.mark.parametrize("size", list(GATHER_SIZES))
+def test_fused_gather_step_equals_gather_then_step(gpu, size, dtype):
+    """fdd_csr_plan_gather_cheby / _f32 on their own inputs against the documented composition -- the plan's gather (dssum
+    mode 1; fdd_csr_plan_gather_f32 in float), then fdd_cheby_step with first = 0 -- as bits in x, d and r_out: r_out
+    separate, r_out == r_in, and the last step (r_out = NULL: d and r_in unchanged); the gather's rows summed in column
+    order, empty rows included, and x against the five statements of the header evaluated in numpy (exact: element-wise,
+    no contraction).  Guard values around every output."""
+    f32 = dtype == torch.float32
+    npdt = np.float32 if f32 else np.float64
+    sfx = "_f32" if f32 else ""
+    rows = GATHER_SIZES[size]
+    ptr, col, cols = boolean_gather_matrix(rows, rows)
+    rng = np.random.default_rng(rows + 1)
+    u, x0, d0, r0 = (rng.uniform(-1.0, 1.0, m).astype(npdt) for m in (cols, rows, rows, rows))
+    dinv = rng.uniform(0.5, 1.5, rows).astype(npdt)
+    c_d, c_r = 0.37, 1.83
+    plan = Plan(ptr, cols)
+    # each fused entry takes a plan of its own precision; the float gather of the composition takes the matrix's fp64 plan, as the host layer hands it
+    fused_plan = Plan(ptr, cols, f32=True) if f32 else plan
+    try:
+        blocks = plan.query("num_blocks")
+        assert plan.query("kind") == 1 and plan.query("pipelined") == 1
+        assert fused_plan.query("kind") == 1 and fused_plan.query("pipelined") == 1 and fused_plan.query("num_blocks") == blocks
+        if size == "one_block":
+            assert blocks == 1
+        elif size == "several_blocks":
+            assert 8 < blocks < PERSISTENT_WORKGROUPS
+        else:
+            assert blocks > 2 * PERSISTENT_WORKGROUPS, blocks  # 2237 blocks of this matrix on 1024 workgroups
+        dptr, dcol, du, ddinv = (torch.from_numpy(a).to(gpu) for a in (ptr, col, u, dinv))
+        # the composition
+        q = torch.full((rows,), GUARD, dtype=dtype, device=gpu)
+        if f32:
+            k("fdd_csr_plan_gather_f32", plan.h, q, dptr, dcol, du, 0, rows)
+        else:
+            k("fdd_csr_plan_dssum", plan.h, None, q, dptr, dcol, du, None, None, 0, rows, 1)
+        ref = {}
+        for last in (0, 1):
+            xr, dr, rin = (torch.from_numpy(a).to(gpu) for a in (x0, d0, r0))
+            rout = torch.full((rows,), GUARD, dtype=dtype, device=gpu)
+            k("fdd_cheby_step" + sfx, xr, dr, None if last else rout, rin, q, ddinv, c_d, c_r, 0, last, rows)
+            ref[last] = (xr, dr, rout)
+        torch.cuda.synchronize()
+        # the gather itself and the five statements, in numpy
+        qh = q.cpu().numpy()
+        assert np.array_equal(qh, row_sums_in_column_order(ptr, col, u))
+        assert not qh[np.diff(ptr) == 0].any() and (np.diff(ptr) == 0).sum() > 40
+        one, cd, cr = npdt(1.0), npdt(c_d), npdt(c_r)
+        r = one * r0 + (-one) * qh
+        t = dinv * r
+        dn = cd * d0 + cr * t
+        xn = one * x0 + one * dn
+        for last in (0, 1):
+            assert np.array_equal(ref[last][0].cpu().numpy(), xn)
+        assert np.array_equal(ref[0][1].cpu().numpy(), dn) and np.array_equal(ref[0][2].cpu().numpy(), r)
+        # the fused entry
+        for form in ("r_out separate", "r_out is r_in", "last"):
+            (X, x), (D, d), (Rin, rin) = (guarded(a, dtype, gpu) for a in (x0, d0, r0))
+            Rout, rout = guarded(np.full(rows, GUARD, npdt), dtype, gpu)
+            last = 1 if form == "last" else 0
+            r_out = None if last else (rin if form == "r_out is r_in" else rout)
+            k("fdd_csr_plan_gather_cheby" + sfx, fused_plan.h, x, d, r_out, dptr, dcol, du, rin, ddinv, c_d, c_r, last)
+            torch.cuda.synchronize()
+            case = (size, form)
+            xr, dr, rr = ref[last]
+            assert torch.equal(x, xr), case
+            if last:  # neither d nor the r_in buffer is written
+                assert np.array_equal(d.cpu().numpy(), d0) and np.array_equal(rin.cpu().numpy(), r0), case
+            else:
+                assert torch.equal(d, dr), case
+                assert torch.equal(rin if form == "r_out is r_in" else rout, rr), case
+                if form == "r_out separate":
+                    assert np.array_equal(rin.cpu().numpy(), r0), case
+            if form != "r_out separate":
+                assert bool((rout == GUARD).all()), case
+            assert all(guards_stand(w) for w in (X, D, Rin, Rout)), case
+    finally:
+        if f32:
+            fused_plan.close()
+        plan.close()
+
+
+def fused_gather_call(plan, sfx, dtype, gpu, ptr, col, cols):
+    """one call of the fused entry on valid buffers; returns the outputs and what they held"""
+    rows = len(ptr) - 1
+    npdt = np.float32 if dtype == torch.float32 else np.float64
+    rng = np.random.default_rng(3)
+    u, x0, d0, r0, dinv = (rng.uniform(0.5, 1.5, m).astype(npdt) for m in (cols, rows, rows, rows, rows))
+    bufs = [guarded(a, dtype, gpu) for a in (x0, d0, np.full(rows, GUARD, npdt))]
+    dptr, dcol, du, drin, ddinv = (torch.from_numpy(a).to(gpu) for a in (ptr, col, u, r0, dinv))
+
+    def run():
+        k("fdd_csr_plan_gather_cheby" + sfx, plan.h, bufs[0][1], bufs[1][1], bufs[2][1], dptr, dcol, du, drin, ddinv, 0.37, 1.83, 0)
+
+    def untouched():
+        torch.cuda.synchronize()
+        return all(np.array_equal(w.cpu().numpy()[8:-8], a) and guards_stand(w) for (w, _), a in zip(bufs, (x0, d0, np.full(rows, GUARD, npdt))))
+
+    return run, untouched
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=["double", "float"])
+def test_fused_gather_refuses_every_other_plan(gpu, dtype):
+    """a plan of kind 0 (thread-per-row; fp64 plans only, fdd_csr_plan_create_f32 makes none), and in the entry's own
+    precision a plan without set_unit_values and a plan with a sliced-ELL copy attached: FddError naming the entry and its
+    reason, outputs untouched"""
+    f32 = dtype == torch.float32
+    sfx = "_f32" if f32 else ""
+    ptr, col, cols = boolean_gather_matrix(3000, 11)
+    one_ptr, one_col = np.arange(3001, dtype=np.int32), np.arange(3000, dtype=np.int32)  # one entry per row: kind 0
+    plans = {}
+    try:
+        plans["kind 0"] = (Plan(one_ptr, 3000), one_ptr, one_col, 3000)
+        assert plans["kind 0"][0].query("kind") == 0
+        plans["not unit"] = (Plan(ptr, cols, f32=f32, unit=False), ptr, col, cols)
+        assert plans["not unit"][0].query("pipelined") == 1
+        sell = Plan(ptr, cols, f32=f32, unit=False)
+        plans["sliced-ELL"] = (sell, ptr, col, cols)
+        attached = ctypes.c_int(0)
+        dptr, dcol, dval = torch.from_numpy(ptr).to(gpu), torch.from_numpy(col).to(gpu), torch.ones(len(col), dtype=dtype, device=gpu)
+        lib.hip().call("fdd_csr_plan_attach_sell", sell.h, lib.ptr(sell.ptr), lib.ptr(dptr), lib.ptr(dcol), lib.ptr(dval), ctypes.c_double(1.0e9), ctypes.byref(attached), lib.current_stream())
+        assert attached.value == 1
+        lib.hip().call("fdd_csr_plan_set_unit_values", sell.h, 1)
+        assert sell.query("pipelined") == 0
+        for what, (plan, p, c, nc) in plans.items():
+            run, untouched = fused_gather_call(plan, sfx, dtype, gpu, p, c, nc)
+            with pytest.raises(lib.FddError) as exc:
+                run()
+            assert "fdd_csr_plan_gather_cheby" + sfx in str(exc.value), what
+            if what != "kind 0" or not f32:  # the float entry refuses an fp64 plan of kind 0 as an fp64 plan
+                assert "not a unit-value plan of the pipelined short-row kernel" in str(exc.value), what
+            assert untouched(), what
+    finally:
+        torch.cuda.synchronize()
+        for plan, *_ in plans.values():
+            plan.close()
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32], ids=["double", "float"])
+def test_fused_gather_refuses_a_plan_of_the_other_precision(gpu, dtype):
+    """the fp64 entry refuses a plan of fdd_csr_plan_create_f32 and the f32 entry refuses an fp64 plan, each a unit-value plan
+    on the pipelined kernel that the entry of its own precision takes: FddError naming the entry and the plan's kind,
+    outputs untouched"""
+    f32 = dtype == torch.float32
+    sfx = "_f32" if f32 else ""
+    ptr, col, cols = boolean_gather_matrix(3000, 11)
+    plan = Plan(ptr, cols, f32=not f32)
+    try:
+        assert plan.query("kind") == 1 and plan.query("pipelined") == 1
+        run, untouched = fused_gather_call(plan, sfx, dtype, gpu, ptr, col, cols)
+        with pytest.raises(lib.FddError) as exc:
+            run()
+        assert "fdd_csr_plan_gather_cheby" + sfx + ":" in str(exc.value) and "fdd_csr_plan_create_f32" in str(exc.value)
+        assert untouched()
+    finally:
+        torch.cuda.synchronize()
+        plan.close()
+
+
 @pytest.mark.parametrize("shape", ["E2N3", "E3N3", "E3N7"])
 def test_recurrence_bound_map_and_outer_solves(setup, shape):
     """tests/chebyshev_checks.py run_shape on the product libraries (what it holds: test_cpu_chebyshev.py)"""

@@ -1261,6 +1261,59 @@ def test_limited_linear_combination_and_small_device_ops(gpu):
     assert host(out)[0] == 2.5
 
 
+@pytest.mark.parametrize("n", [1, 2, 129, 4097])
+def test_xmay_ratio_dev(gpu, n):
+    """fdd_xmay_ratio_dev: out = x - (*num / *den) * y against numpy, as bits; out separate and out == x; every pointer on
+    a 16-byte boundary and every pointer 8 bytes off one (the one-value-per-lane path); guard values around out"""
+    x, y = rnd(n, 340 + n), rnd(n, 341 + n)
+    num, den = np.array([0.37]), np.array([-1.9])
+    expect = x - (num[0] / den[0]) * y
+    dnum, dden = dev(num, gpu), dev(den, gpu)
+    for shift in (0, 1):
+        for alias in (False, True):
+            X, Y, O = (torch.full((n + shift + 3,), 777.0, dtype=torch.float64, device=gpu) for _ in range(3))
+            dx, dy = X[shift : shift + n], Y[shift : shift + n]
+            dx.copy_(dev(x, gpu))
+            dy.copy_(dev(y, gpu))
+            out = dx if alias else O[shift : shift + n]
+            assert out.data_ptr() % 16 == 8 * shift and dy.data_ptr() % 16 == 8 * shift
+            k("fdd_xmay_ratio_dev", out, dx, dnum, dden, dy, n)
+            case = (n, shift, alias)
+            assert np.array_equal(host(out).view(np.uint64), expect.view(np.uint64)), case
+            assert np.array_equal(host(dy), y) and (alias or np.array_equal(host(dx), x)), case
+            for whole in (X, Y, O):
+                w = host(whole)
+                assert (w[:shift] == 777.0).all() and (w[shift + n :] == 777.0).all(), case
+            if alias:
+                assert (host(O) == 777.0).all(), case
+
+
+@pytest.mark.parametrize("scaled", [False, True])
+@pytest.mark.parametrize("m", [1, 5, 8])
+def test_multi_lincomb_scaled_dev(gpu, m, scaled):
+    """fdd_multi_lincomb_scaled_dev: the bits of fdd_multi_axpy_scaled_dev on a zeroed q and of
+    fdd_multi_lincomb_limited_dev without a limit; with q_is_zero = 1 a q full of NaN is not read"""
+    n = 4099
+    V = [dev(rnd(n, 350 + i), gpu) for i in range(m)]
+    dc = dev(rnd(m, 360), gpu)
+    dinv = dev(np.abs(rnd(m, 361)) + 0.5, gpu) if scaled else None
+    q_axpy = torch.zeros(n, dtype=torch.float64, device=gpu)
+    k("fdd_multi_axpy_scaled_dev", q_axpy, dc, V, dinv, m, n)
+    assert np.abs(host(q_axpy)).max() > 0.0
+    for q_is_zero in (1, 0):
+        start = float("nan") if q_is_zero else 0.0
+        Q1, Q2 = (torch.full((n + 16,), 777.0, dtype=torch.float64, device=gpu) for _ in range(2))
+        q1, q2 = Q1[8 : 8 + n], Q2[8 : 8 + n]
+        q1.fill_(start)
+        q2.fill_(start)
+        k("fdd_multi_lincomb_scaled_dev", q1, q_is_zero, dc, V, dinv, m, n)
+        k("fdd_multi_lincomb_limited_dev", q2, q_is_zero, dc, V, dinv, None, m, n)
+        case = (m, scaled, q_is_zero)
+        assert np.array_equal(host(q1).view(np.uint64), host(q_axpy).view(np.uint64)), case
+        assert np.array_equal(host(q1).view(np.uint64), host(q2).view(np.uint64)), case
+        assert (host(Q1)[:8] == 777.0).all() and (host(Q1)[8 + n :] == 777.0).all(), case
+
+
 def test_gather_indexed(gpu):
     n_in, n_out = 5000, 7001
     x, sc = rnd(n_in, 70), rnd(n_out, 71)
@@ -1648,6 +1701,20 @@ def test_gmres_bookkeeping_on_device(gpu, case):
     dq = dev(q, gpu)
     k("fdd_multi_axpy_dev", dq, yp, [dev(v, gpu) for v in V], j_last + 1, n)
     assert np.array_equal(host(dq), ref)
+    if case in ("full", "tolerance"):
+        # fdd_gmres_scales / fdd_gmres_last_column: the device addresses the *_scaled and *_limited entries read, inside the
+        # state; inv[0] = 1 / gamma_0, inv[j + 1] = 1 / ||q_j|| of the columns that were taken, j_last as a double
+        ip, jp = vp(), vp()
+        L.call("fdd_gmres_scales", vp(st.data_ptr()), ctypes.byref(ip))
+        L.call("fdd_gmres_last_column", vp(st.data_ptr()), ctypes.byref(jp))
+        lo, hi = st.data_ptr(), st.data_ptr() + nbytes
+        assert lo <= ip.value and ip.value + 8 * (m + 1) <= hi and lo <= jp.value and jp.value + 8 <= hi
+        inv, jl_dev = np.zeros(m + 1), np.zeros(1)
+        L.call("fdd_fetch_scalars", P(inv), ip, 8 * (m + 1), stream)
+        L.call("fdd_fetch_scalars", P(jl_dev), jp, 8, stream)
+        expect = 1.0 / np.sqrt(np.array([norm2] + [cols[j][j + 1] for j in range(j_last + 1)]))
+        assert np.array_equal(inv[: j_last + 2].view(np.uint64), expect.view(np.uint64))
+        assert jl_dev[0] == float(jl.value) == float(j_last)
 
 
 def test_fetch_scalars(gpu):
