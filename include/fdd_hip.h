@@ -375,6 +375,18 @@ int fdd_stiffness_matrix_mfma_affine(double *Au, const double *v, const double *
  * point, deviation[e] = max over points and factors of |G_f(p) - elem_factors[6 e + f] W(p)| / (max_f |elem_factors| W(p)),
  * W(p) = (w_i w_j) w_k.  3-D elements. */
 int fdd_stiffness_affine_detect(double *elem_factors, double *deviation, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const double *gll_weights, int num_elements, int poly_degree, void *stream);
+/* The fused kernel where the three off-diagonal factor arrays G[3..5] are 0.0 at every point of the list (every mesh whose
+ * elements have orthogonal axes: boxes, rectilinear grids): they are not read -- G is still the six-pointer array, entries
+ * 3..5 are never dereferenced -- and GDu_d = G[d] Du_d.  36 B per point instead of 60 in the gather form (20 instead of 32
+ * in float), 40 instead of 64 in the local form.  What is dropped is the addition of exact zeros: every output is the IEEE
+ * value of the six-array entries for finite v, bit for bit up to the sign of a zero.  v_scale_dev, point_dof and elem_offset
+ * may each be NULL, as for fdd_stiffness_matrix_affine.  poly_degree 1..15, FDD_ERR_UNSUPPORTED above. */
+int fdd_stiffness_matrix_diag(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream);
+int fdd_stiffness_matrix_diag_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream);
+/* Are they?  One pass over G[3], G[4], G[5] on the points of the list (3-D elements): flags_out (three ints in device
+ * memory) [f] = 0 exactly when every value of G[3 + f] there compares == 0.0 (-0.0 does; a denormal or a NaN does not),
+ * 1 otherwise. */
+int fdd_stiffness_offdiag_zero(int *flags_out, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream);
 int fdd_stiffness_matrix_affine_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *elem_factors, const float *gll_weights, const int *elem_offset, int num_elements, int poly_degree, void *stream);
 int fdd_sub_stiffness_matrix_gather_scaled_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream);
 int fdd_multi_inner_product_scaled_f32(double *out, double *ws, const float *a, const float *const *b, const double *b_scale_dev, int m, int n, void *stream); /* out[k] = sum a * (s_k b_k), k < m <= 8 */

@@ -232,6 +232,16 @@ int fddh_problem_set_options(fddh_problem *p, int max_iterations, double toleran
  * and how many of the Subdomain's level lists -- and the largest relative deviation of the mesh's own factor arrays
  * from that form (-1 before the flag was ever set).  Any argument may be NULL. */
 int fddh_problem_affine_info(fddh_problem *p, int *fine_domain_affine, int *sub_lists_affine, int *sub_lists, double *max_deviation);
+/* Flag "skip_zero_factors" (default 1 where the kernel library exports fdd_stiffness_matrix_diag, _diag_f32 and
+ * fdd_stiffness_offdiag_zero; setting it to 1 on a library without them is refused, naming the missing entry): a 3-D element
+ * list of degree <= 15 whose three off-diagonal factor arrays are 0.0 at every point -- checked once on the device when the
+ * list's factor pointers are set; every box and rectilinear mesh -- runs the stiffness kernel that streams three factor arrays
+ * instead of six, unless "affine_geometry" has switched it over or it runs on the matrix cores.  Unlike "affine_geometry" this
+ * leaves the operator's values as they are (the addition of exact zeros is all that is dropped; the sign of a zero may
+ * differ), so nothing that hangs on the operator is emptied.  0: six arrays everywhere.
+ * The info entry: is the flag on, does the fine Domain's list run that kernel, how many of the Subdomain's level lists do (in
+ * the precision in use), of how many.  Any argument may be NULL. */
+int fddh_problem_zero_factor_info(fddh_problem *p, int *enabled, int *fine_domain_diag, int *sub_lists_diag, int *sub_lists);
 int fddh_problem_set_flag(fddh_problem *p, const char *name, int value);
 
 /* Low-order AMG preconditioner of the inner solve (Subdomain::low_order_preconditioner,

@@ -261,7 +261,14 @@ __device__ __forceinline__ void element_sync()
 // of the reference cube (every element of a box mesh).  G.g[0] then points to c (element-major, 6 per element of this
 // list), G.g[1] to the n weights.  An option of this build (the reference always streams G): the host layer offers it
 // only where the mesh's own factor arrays satisfy the product form to rounding (host/element.hpp: affine_factors).
-template <typename T, int n, bool kGather, bool kNTStore, bool kAffine = false>
+// kDiag: the three off-diagonal factor arrays G.g[3..5] are NOT streamed (24 of the 64 B per point): the caller has
+// established that they are 0.0 at every point of the list (fdd_stiffness_offdiag_zero; every mesh whose elements have
+// orthogonal axes), and GDu_d = g[d] * Du_d.  What is left out is the addition of exact zeros: every output is the IEEE
+// value the six-array kernel gives, for finite u, up to the sign of a zero.  Three factor registers per slab in flight: the
+// double gather instance at n = 8 takes 131 VGPRs (148 with six arrays), 3 waves per SIMD, no scratch, 136 us per launch at
+// 32^3 elements against 170.  A launch bound of 4 waves (126 VGPRs) and kPF = 2 (144 VGPRs) both measured 134-136 us, inside
+// the spread; kPF = 2 under the bound of 4 spills.
+template <typename T, int n, bool kGather, bool kNTStore, bool kAffine = false, bool kDiag = false>
 __global__ __launch_bounds__(kBlock, (kAffine && n == 8 && sizeof(T) == 8) ? 4 : 1) void fused_stiffness_kernel_t(T *__restrict__ Au, const T *__restrict__ u, const int *__restrict__ point_dof, const double *__restrict__ u_scale, const T *__restrict__ D_hat, GPtrsT<T> G, const int *__restrict__ elem_offset, int num_elements)
 {
     using C = FusedCfg<n>;
@@ -300,8 +307,9 @@ __global__ __launch_bounds__(kBlock, (kAffine && n == 8 && sizeof(T) == 8) ? 4 :
     // geometric factors of the first kPF slabs right behind it (inside the loop slab
     // k + kPF is requested as soon as slab k's are consumed).  All of it is in
     // flight before D_hat is staged.
-    constexpr int kPF = 1; // slabs of geometric factors in flight (2 measured no faster at n = 8: the kernel is not latency-bound)
-    T r_u[n], r_3[n], gq[kPF][FDD_NUM_GEOM_FACTS];
+    constexpr int kPF = 1; // slabs of geometric factors in flight (2 measured no faster at n = 8, with six arrays and with three: the kernel is not latency-bound)
+    constexpr int nG = kDiag ? 3 : FDD_NUM_GEOM_FACTS;                          // factor arrays streamed
+    T r_u[n], r_3[n], gq[kPF][nG];
     T cf[FDD_NUM_GEOM_FACTS], wij = T(0); // kAffine: the element's six numbers, w_i w_j of this lane
 #pragma unroll
     for (int f = 0; f < FDD_NUM_GEOM_FACTS; f++) cf[f] = T(0);
@@ -310,7 +318,7 @@ __global__ __launch_bounds__(kBlock, (kAffine && n == 8 && sizeof(T) == 8) ? 4 :
 #pragma unroll
     for (int s = 0; s < kPF; s++)
 #pragma unroll
-        for (int f = 0; f < FDD_NUM_GEOM_FACTS; f++) gq[s][f] = T(0);
+        for (int f = 0; f < nG; f++) gq[s][f] = T(0);
     if (active)
     {
         if (kGather)
@@ -349,7 +357,7 @@ __global__ __launch_bounds__(kBlock, (kAffine && n == 8 && sizeof(T) == 8) ? 4 :
 #pragma unroll
             for (int s = 0; s < kPF; s++)
 #pragma unroll
-                for (int f = 0; f < FDD_NUM_GEOM_FACTS; f++) gq[s][f] = __builtin_nontemporal_load(G.g[f] + base + (ij + s * nn));
+                for (int f = 0; f < nG; f++) gq[s][f] = __builtin_nontemporal_load(G.g[f] + base + (ij + s * nn));
         }
     }
 
@@ -392,7 +400,7 @@ __global__ __launch_bounds__(kBlock, (kAffine && n == 8 && sizeof(T) == 8) ? 4 :
             const int k = k0 + s;
             if ((n % kPF != 0) && k >= n) continue;
             // this slot's factors move to g; slab k + kPF is requested into the slot
-            T g[FDD_NUM_GEOM_FACTS];
+            T g[kAffine ? FDD_NUM_GEOM_FACTS : nG];
             if (kAffine)
             {
                 const T w3 = wij * G.g[1][k]; // w_k: wave-uniform address
@@ -402,13 +410,13 @@ __global__ __launch_bounds__(kBlock, (kAffine && n == 8 && sizeof(T) == 8) ? 4 :
             else
             {
 #pragma unroll
-                for (int f = 0; f < FDD_NUM_GEOM_FACTS; f++) g[f] = gq[s][f];
+                for (int f = 0; f < nG; f++) g[f] = gq[s][f];
             }
             if (!kAffine && active && k + kPF < n)
             {
                 const int off = ij + (k + kPF) * nn;
 #pragma unroll
-                for (int f = 0; f < FDD_NUM_GEOM_FACTS; f++) gq[s][f] = __builtin_nontemporal_load(G.g[f] + base + off);
+                for (int f = 0; f < nG; f++) gq[s][f] = __builtin_nontemporal_load(G.g[f] + base + off);
             }
 
             // row k of D_hat: wave-uniform address -> scalar loads, lives in SGPRs
@@ -433,9 +441,19 @@ __global__ __launch_bounds__(kBlock, (kAffine && n == 8 && sizeof(T) == 8) ? 4 :
                 Du_3 += Dk[p] * r_u[p];
             }
 
-            const T GDu_1 = g[0] * Du_1 + g[3] * Du_2 + g[4] * Du_3;
-            const T GDu_2 = g[3] * Du_1 + g[1] * Du_2 + g[5] * Du_3;
-            const T GDu_3 = g[4] * Du_1 + g[5] * Du_2 + g[2] * Du_3;
+            T GDu_1, GDu_2, GDu_3;
+            if constexpr (kDiag)
+            {
+                GDu_1 = g[0] * Du_1;
+                GDu_2 = g[1] * Du_2;
+                GDu_3 = g[2] * Du_3;
+            }
+            else
+            {
+                GDu_1 = g[0] * Du_1 + g[3] * Du_2 + g[4] * Du_3;
+                GDu_2 = g[3] * Du_1 + g[1] * Du_2 + g[5] * Du_3;
+                GDu_3 = g[4] * Du_1 + g[5] * Du_2 + g[2] * Du_3;
+            }
 
             T *sg1 = s_g[k & 1][0][el];
             T *sg2 = s_g[k & 1][1][el];
@@ -497,6 +515,82 @@ int launch_fused_t(T *Au, const T *u, const int *point_dof, const double *u_scal
         hipLaunchKernelGGL((fused_stiffness_kernel_t<T, n, false, false>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements);
     FDD_LAUNCH_CHECK();
     return 0;
+}
+
+// the kDiag instances: G.g[3..5] are not passed on (never dereferenced)
+template <typename T, int n>
+int launch_fused_diag_t(T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const GPtrsT<T> &G, const int *elem_offset, int num_elements, void *stream)
+{
+    using C = FusedCfg<n>;
+    const int grid = (num_elements + C::epb - 1) / C::epb;
+    static const bool nt_store = fdd_env_int("FDD_TUNE_STIFFNESS_NT_STORE", 1) != 0;
+    if (point_dof and nt_store)
+        hipLaunchKernelGGL((fused_stiffness_kernel_t<T, n, true, true, false, true>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements);
+    else if (point_dof)
+        hipLaunchKernelGGL((fused_stiffness_kernel_t<T, n, true, false, false, true>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements);
+    else if (nt_store)
+        hipLaunchKernelGGL((fused_stiffness_kernel_t<T, n, false, true, false, true>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements);
+    else
+        hipLaunchKernelGGL((fused_stiffness_kernel_t<T, n, false, false, false, true>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements);
+    FDD_LAUNCH_CHECK();
+    return 0;
+}
+
+template <typename T>
+int fused_dispatch_diag(T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const T *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
+{
+    FDD_REQUIRE(num_elements >= 0);
+    if (num_elements == 0) return 0;
+    FDD_REQUIRE(Au != nullptr && u != nullptr && D_hat != nullptr && G != nullptr);
+    GPtrsT<T> g;
+    for (int k = 0; k < FDD_NUM_GEOM_FACTS; k++) g.g[k] = nullptr;
+    for (int k = 0; k < 3; k++)
+    {
+        FDD_REQUIRE(G[k] != nullptr);
+        g.g[k] = G[k];
+    }
+    switch (poly_degree + 1)
+    {
+#define FDD_DIAG_CASE(N_) \
+    case N_: return launch_fused_diag_t<T, N_>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
+        FDD_DIAG_CASE(2)
+        FDD_DIAG_CASE(3)
+        FDD_DIAG_CASE(4)
+        FDD_DIAG_CASE(5)
+        FDD_DIAG_CASE(6)
+        FDD_DIAG_CASE(7)
+        FDD_DIAG_CASE(8)
+        FDD_DIAG_CASE(9)
+        FDD_DIAG_CASE(10)
+        FDD_DIAG_CASE(11)
+        FDD_DIAG_CASE(12)
+        FDD_DIAG_CASE(13)
+        FDD_DIAG_CASE(14)
+        FDD_DIAG_CASE(15)
+        FDD_DIAG_CASE(16)
+#undef FDD_DIAG_CASE
+    default:
+        fdd_set_error("fused stiffness kernel supports poly_degree 1..15, got %d (use the two-launch form)", poly_degree);
+        return FDD_ERR_UNSUPPORTED;
+    }
+}
+
+// flags[f] = 1 where array 3 + f of the list holds a value that is not a zero: any bit besides the sign set, so -0.0 passes
+// and a denormal or a NaN does not, whatever the denormal mode.  flags are cleared by the caller; every lane that finds
+// such a value stores the same 1.
+__global__ __launch_bounds__(kBlock) void offdiag_zero_kernel(int *__restrict__ flags, GPtrs G, const int *__restrict__ elem_offset, int n3, size_t num_points)
+{
+    bool nz[3] = {false, false, false};
+    for (size_t idx = (size_t)blockIdx.x * kBlock + threadIdx.x; idx < num_points; idx += (size_t)gridDim.x * kBlock)
+    {
+        const size_t e = idx / n3;
+        const size_t at = elem_offset ? (size_t)elem_offset[e] + (idx - e * n3) : idx;
+#pragma unroll
+        for (int f = 0; f < 3; f++) nz[f] = nz[f] or (__double_as_longlong(G.g[3 + f][at]) & 0x7fffffffffffffffLL) != 0;
+    }
+#pragma unroll
+    for (int f = 0; f < 3; f++)
+        if (nz[f]) flags[f] = 1;
 }
 
 // One workgroup per element: c_f = G_f(p0) / W(p0) at the element's middle point, and the largest deviation of any
@@ -924,6 +1018,31 @@ int fdd_sub_stiffness_matrix_gather_scaled(double *Au, const double *v, const do
 int fdd_stiffness_matrix_affine(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *elem_factors, const double *gll_weights, const int *elem_offset, int num_elements, int poly_degree, void *stream)
 {
     return fused_dispatch_affine<double>(Au, v, point_dof, v_scale_dev, D_hat, elem_factors, gll_weights, elem_offset, num_elements, poly_degree, stream);
+}
+
+int fdd_stiffness_matrix_diag(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
+{
+    return fused_dispatch_diag<double>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, num_elements, poly_degree, stream);
+}
+
+int fdd_stiffness_matrix_diag_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
+{
+    return fused_dispatch_diag<float>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, num_elements, poly_degree, stream);
+}
+
+int fdd_stiffness_offdiag_zero(int *flags_out, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
+{
+    FDD_REQUIRE(num_elements >= 0 && poly_degree >= 1 && flags_out != nullptr);
+    FDD_HIP_CHECK(hipMemsetAsync(flags_out, 0, 3 * sizeof(int), fdd_stream(stream)));
+    if (num_elements == 0) return 0;
+    FDD_REQUIRE(G != nullptr && G[3] != nullptr && G[4] != nullptr && G[5] != nullptr);
+    GPtrs g;
+    for (int k = 0; k < FDD_NUM_GEOM_FACTS; k++) g.g[k] = G[k];
+    const int n = poly_degree + 1, n3 = n * n * n;
+    const size_t num_points = (size_t)num_elements * n3;
+    hipLaunchKernelGGL(offdiag_zero_kernel, dim3(fdd_stream_grid((long long)num_points, kBlock)), dim3(kBlock), 0, fdd_stream(stream), flags_out, g, elem_offset, n3, num_points);
+    FDD_LAUNCH_CHECK();
+    return 0;
 }
 
 int fdd_stiffness_affine_detect(double *elem_factors, double *deviation, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const double *gll_weights, int num_elements, int poly_degree, void *stream)

@@ -475,6 +475,7 @@ class Domain
     bool fused_update_flexible_dot = true; // one rank, z~ written in place, early_gamma: the inner solve's final update of z~ is formed inside the flexible dot's pass (same bits; 0: a kernel of its own in front of the dot)
     bool unit_stitch_in_place = true; // stitching weights of the dof slice all exactly 1 (one rank): the inner solve writes z~ in place (0: the multiplication by the ones, the reference's sequence)
     bool mfma_stiffness = true; // N >= 11: stiffness on the fp64 matrix cores (not bit-identical; 1e-12 tolerance)
+    bool skip_zero_factors = fdd::missing_zero_factor_entry() == nullptr; // off-diagonal factor arrays that are identically zero are not streamed (element_operator.hpp)
     DType tolerance = 1.0e-07;
     std::vector<DType> residual_history; // what the reference prints per iteration
 
@@ -761,6 +762,7 @@ class Domain
         list.dim = dim;
         list.num_elements = num_local_elements;
         list.D_hat = D_hat.as<double>(); // set_D_hat rewrites this buffer in place
+        fdd::detect_zero_factors(list); // the list is complete: are its off-diagonal factor arrays zero everywhere?
 
         // Solver vectors (GMRES bases are allocated on first use)
         r_k = fdd::dev().malloc<DType>(num_local_points);
@@ -849,7 +851,7 @@ class Domain
     // domain.tpp:602-609
     void stiffness_matrix(fdd::memory &Au, fdd::memory &u, bool apply_dssum = false)
     {
-        fdd::apply_local(list, Au.as<double>(), u.as<double>(), work_dev, mfma_stiffness);
+        fdd::apply_local(list, Au.as<double>(), u.as<double>(), work_dev, mfma_stiffness, skip_zero_factors);
         if (apply_dssum) direct_stiffness_summation(Au, Au, true, false);
     }
 
@@ -964,6 +966,7 @@ class Domain
     // set_affine_geometry(true) switches the node-space operator over only if every element of the mesh passes the check
     // (a box mesh); false: it did not, or the mesh cannot run that kernel.
     const fdd::LevelList &operator_list() const { return list; }
+    bool runs_diag_kernel() const { return fdd::on_diag_kernel<double>(list, mfma_stiffness, skip_zero_factors); } // flag "skip_zero_factors"
     bool set_affine_geometry(bool on)
     {
         list.affine = on and fdd::detect_affine(list);
@@ -973,7 +976,7 @@ class Domain
     // q (points) = A_local (Q p~)
     void stiffness_from_nodes(fdd::memory &q, fdd::memory &pn)
     {
-        fdd::apply_gather(list, q.as<double>(), pn.as<double>(), point_node_dev.as<int>(), nullptr, num_local_nodes, mfma_stiffness);
+        fdd::apply_gather(list, q.as<double>(), pn.as<double>(), point_node_dev.as<int>(), nullptr, num_local_nodes, mfma_stiffness, skip_zero_factors);
     }
 
     // sqrt(<r, QQt r>) (domain.tpp:916-931) from r^ = Qt r: sum_n r^_n * gs(r^)_n * mask_n.

@@ -44,6 +44,9 @@ struct LevelList
     bool affine = false;            // in use
     double affine_deviation = -1.0; // largest relative deviation found (-1: not checked)
     memory affine_c, affine_w, affine_c32, affine_w32;
+    // are the three off-diagonal factor arrays G[3..5] zero at every point of the list (detect_zero_factors, once, when the
+    // factor pointers are set)?  Then the kernel that does not stream them applies; G32 are casts of the same arrays
+    bool offdiag_zero = false;
 
     size_t num_points() const { return (size_t)num_elements * (poly_degree + 1) * (poly_degree + 1) * (dim == 3 ? poly_degree + 1 : 1); }
 };
@@ -55,9 +58,43 @@ inline bool on_matrix_cores(const LevelList &ll, bool mfma_enabled)
     return std::is_same<Real, double>::value and mfma_enabled and ll.dim == 3 and ll.poly_degree >= 11 and ll.poly_degree <= 15;
 }
 
+// the first entry of the three-array stiffness kernel the loaded kernel library does not export, or nullptr
+inline const char *missing_zero_factor_entry()
+{
+    if (&fdd_stiffness_offdiag_zero == nullptr) return "fdd_stiffness_offdiag_zero";
+    if (&fdd_stiffness_matrix_diag == nullptr) return "fdd_stiffness_matrix_diag";
+    if (&fdd_stiffness_matrix_diag_f32 == nullptr) return "fdd_stiffness_matrix_diag_f32";
+    return nullptr;
+}
+
+// ---- factor arrays that are identically zero (flag "skip_zero_factors") ----
+// On a mesh whose elements have orthogonal axes (every box, every rectilinear grid) G[3..5] are 0.0 at every point.
+// detect_zero_factors establishes that from the list's OWN arrays in one pass on the device; where it holds (and the flag
+// is on) the list runs the kernel that streams G[0..2] only.  Unlike the affine option the arithmetic left out is the
+// addition of exact zeros: the operator's values are the same, to the sign of a zero.  Only 3-D lists of degree <= 15 are
+// checked (the matrix-core, 2-D and two-launch forms keep six arrays); without the entries nothing is, and nothing switches.
+inline void detect_zero_factors(LevelList &ll)
+{
+    ll.offdiag_zero = false;
+    if (ll.dim != 3 or ll.poly_degree > 15 or ll.num_elements == 0 or missing_zero_factor_entry()) return;
+    int flags[3] = {1, 1, 1};
+    memory flags_dev = dev().malloc<int>(3);
+    FDD_CALL(fdd_stiffness_offdiag_zero(flags_dev.as<int>(), ll.G, nullptr, ll.num_elements, ll.poly_degree, dev().stream));
+    flags_dev.copyTo(flags, sizeof(flags));
+    flags_dev.free();
+    ll.offdiag_zero = flags[0] == 0 and flags[1] == 0 and flags[2] == 0;
+}
+
+// does the list run the three-array kernel for this precision?  (affine, where switched on, takes precedence: see the callers)
+template <typename Real>
+inline bool on_diag_kernel(const LevelList &ll, bool mfma_enabled, bool skip_zero_factors)
+{
+    return skip_zero_factors and ll.offdiag_zero and not ll.affine and not on_matrix_cores<Real>(ll, mfma_enabled);
+}
+
 // Au = A_L u on the points of the list (Au, u: the vectors the list's first_offset counts in).  workspace: three vectors
 // of the list's points for the two-launch form above degree 15.
-inline void apply_local(const LevelList &ll, double *Au, const double *u, const std::vector<memory> &workspace, bool mfma_enabled)
+inline void apply_local(const LevelList &ll, double *Au, const double *u, const std::vector<memory> &workspace, bool mfma_enabled, bool skip_zero_factors)
 {
     void *stream = dev().stream;
     const double points = (double)ll.num_points();
@@ -67,6 +104,13 @@ inline void apply_local(const LevelList &ll, double *Au, const double *u, const 
         // high order: the six contractions on the fp64 matrix cores (tolerance-level parity, fdd_hip.h)
         ProfileScope prof("mfma_stiffness_kernel", 64.0 * points);
         FDD_CALL(fdd_stiffness_matrix_mfma(Au, u, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, stream));
+    }
+    else if (on_diag_kernel<double>(ll, mfma_enabled, skip_zero_factors)) // the gather form's predicate: one answer per list (3-D, degree <= 15: nothing else is checked)
+    {
+        // the labels of the three-array instances are not "fused_stiffness_kernel...": the committed counters bench.py
+        // matches by family are the six-array kernel's
+        ProfileScope prof("diag_stiffness_kernel", 40.0 * points);
+        FDD_CALL(fdd_stiffness_matrix_diag(Au, u, nullptr, nullptr, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, stream));
     }
     else if (ll.dim == 3 and ll.poly_degree <= 15)
     {
@@ -100,6 +144,16 @@ inline void stiffness_gather(const LevelList &ll, float *q, const float *v, cons
     for (int g = 0; g < NUM_GEOM_FACTS; g++) G[g] = ll.G32[g].as<float>();
     FDD_CALL(fdd_sub_stiffness_matrix_gather_scaled_f32(q, v, scale_dev, point_index, ll.D_hat32.as<float>(), G, nullptr, ll.num_elements, ll.poly_degree, s));
 }
+inline void stiffness_diag(const LevelList &ll, double *q, const double *v, const double *scale_dev, const int *point_index, void *s)
+{
+    FDD_CALL(fdd_stiffness_matrix_diag(q, v, scale_dev, point_index, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, s));
+}
+inline void stiffness_diag(const LevelList &ll, float *q, const float *v, const double *scale_dev, const int *point_index, void *s)
+{
+    const float *G[NUM_GEOM_FACTS];
+    for (int g = 0; g < NUM_GEOM_FACTS; g++) G[g] = ll.G32[g].as<float>();
+    FDD_CALL(fdd_stiffness_matrix_diag_f32(q, v, scale_dev, point_index, ll.D_hat32.as<float>(), G, nullptr, ll.num_elements, ll.poly_degree, s));
+}
 inline void stiffness_affine(const LevelList &ll, double *q, const double *v, const double *scale_dev, const int *point_index, bool mfma, void *s)
 {
     FDD_CALL((mfma ? fdd_stiffness_matrix_mfma_affine : fdd_stiffness_matrix_affine)(q, v, scale_dev, point_index, ll.D_hat, ll.affine_c.as<double>(), ll.affine_w.as<double>(), nullptr, ll.num_elements, ll.poly_degree, s));
@@ -114,7 +168,7 @@ inline void stiffness_affine(const LevelList &ll, float *q, const float *v, cons
 // (null: 1).  q, point_index: the arrays the list's first_offset counts in; gathered_values: the length of v (the bytes it
 // adds to the count).  3-D lists of degree <= 15.
 template <typename Real>
-inline void apply_gather(const LevelList &ll, Real *q, const Real *v, const int *point_index, const double *scale_dev, int gathered_values, bool mfma_enabled)
+inline void apply_gather(const LevelList &ll, Real *q, const Real *v, const int *point_index, const double *scale_dev, int gathered_values, bool mfma_enabled, bool skip_zero_factors)
 {
     constexpr bool f32 = std::is_same<Real, float>::value;
     const bool mfma = on_matrix_cores<Real>(ll, mfma_enabled);
@@ -124,6 +178,12 @@ inline void apply_gather(const LevelList &ll, Real *q, const Real *v, const int 
     {
         ProfileScope prof(f32 ? "fused_stiffness_kernel<gather,f32,affine>" : mfma ? "mfma_stiffness_kernel<gather,affine>" : "fused_stiffness_kernel<gather,affine>", (f32 ? 8.0 : 12.0) * points + gathered);
         ops::stiffness_affine(ll, q, v, scale_dev, point_index, mfma, dev().stream);
+        return;
+    }
+    if (on_diag_kernel<Real>(ll, mfma_enabled, skip_zero_factors))
+    {
+        ProfileScope prof(f32 ? "diag_stiffness_kernel<gather,f32>" : "diag_stiffness_kernel<gather>", (f32 ? 20.0 : 36.0) * points + gathered);
+        ops::stiffness_diag(ll, q, v, scale_dev, point_index, dev().stream);
         return;
     }
     ProfileScope prof(f32 ? "fused_stiffness_kernel<gather,f32>" : mfma ? "mfma_stiffness_kernel<gather>" : "fused_stiffness_kernel<gather>", (f32 ? 32.0 : 60.0) * points + gathered);

@@ -54,6 +54,12 @@
 #pragma weak fdd_cheby_step_f32
 #pragma weak fdd_csr_plan_gather_cheby
 #pragma weak fdd_csr_plan_gather_cheby_f32
+// and the stiffness kernel that does not stream factor arrays that are identically zero, with its check: without them every
+// list streams six arrays, and the flag "skip_zero_factors" refuses to be set to 1, naming the missing entry
+// (missing_zero_factor_entry, element_operator.hpp)
+#pragma weak fdd_stiffness_matrix_diag
+#pragma weak fdd_stiffness_matrix_diag_f32
+#pragma weak fdd_stiffness_offdiag_zero
 
 namespace fdd
 {

@@ -944,6 +944,25 @@ int fddh_problem_affine_info(fddh_problem *p, int *fine_domain_affine, int *sub_
     }
 }
 
+int fddh_problem_zero_factor_info(fddh_problem *p, int *enabled, int *fine_domain_diag, int *sub_lists_diag, int *sub_lists)
+{
+    try
+    {
+        if (int rc = rank_check(p)) return rc;
+        if (!p) return fail("null argument");
+        Domain<SType> &dom = p->fine();
+        if (enabled) *enabled = dom.skip_zero_factors ? 1 : 0;
+        if (fine_domain_diag) *fine_domain_diag = dom.runs_diag_kernel() ? 1 : 0;
+        if (sub_lists_diag) *sub_lists_diag = p->subdomain ? p->subdomain->lists_on_diag_kernel() : 0;
+        if (sub_lists) *sub_lists = p->subdomain ? (int)p->subdomain->operator_lists().size() : 0;
+        return 0;
+    }
+    catch (const std::exception &e)
+    {
+        return fail("%s", e.what());
+    }
+}
+
 int fddh_problem_set_flag(fddh_problem *p, const char *name, int value)
 {
     try
@@ -1037,6 +1056,17 @@ int fddh_problem_set_flag(fddh_problem *p, const char *name, int value)
             if (p->subdomain) p->subdomain->set_affine_geometry(value != 0);
             p->fine().projection.clear(); // the operator's arithmetic changes under the stored images
             if (p->subdomain) p->subdomain->operator_changed();
+        }
+        else if (s == "skip_zero_factors")
+        {
+            // lists whose three off-diagonal factor arrays are zero at every point (checked once, when a list's factor
+            // pointers are set) run the kernel that streams three arrays (default where the kernel library has it); 0: six
+            // arrays everywhere.  The operator's values do not change -- what is left out is the addition of exact zeros --
+            // so the projection basis, the point-Jacobi diagonal and the Chebyshev bound stay.
+            if (value != 0)
+                if (const char *missing = fdd::missing_zero_factor_entry()) return fail("skip_zero_factors needs %s, which the loaded kernel library does not export", missing);
+            for (auto &kv : p->domains) kv.second.skip_zero_factors = value != 0;
+            if (p->subdomain) p->subdomain->skip_zero_factors = value != 0;
         }
         else if (s == "fused_projection")
         {

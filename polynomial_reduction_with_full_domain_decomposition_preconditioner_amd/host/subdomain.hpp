@@ -927,7 +927,7 @@ class Subdomain
     template <typename Real>
     void stiffness_from_dofs(Real *q, const Real *za, const double *scale_dev = nullptr)
     {
-        for (auto &ll : subdomain_operator.level_lists) fdd::apply_gather(ll, q, za, point_dof_dev.template as<int>(), scale_dev, subdomain_operator.num_extended_dofs, mfma_stiffness);
+        for (auto &ll : subdomain_operator.level_lists) fdd::apply_gather(ll, q, za, point_dof_dev.template as<int>(), scale_dev, subdomain_operator.num_extended_dofs, mfma_stiffness, skip_zero_factors);
     }
 
     // y (dofs) = [Qt A_L Q | A_sup] (s x~): the operator of the inner iteration on a dof vector.  x~ is one of the
@@ -1402,6 +1402,7 @@ class Subdomain
         history_pending = false;
     }
     bool mfma_stiffness = true;           // N >= 11 element lists on the fp64 matrix cores
+    bool skip_zero_factors = fdd::missing_zero_factor_entry() == nullptr; // lists whose off-diagonal factor arrays are identically zero do not stream them (element_operator.hpp)
     std::vector<DType> residual_history;  // inner history of the last application
 
     int num_values = 0;
@@ -1599,6 +1600,7 @@ class Subdomain
             ll.num_elements = domain.num_local_elements;
             ll.first_offset = 0;
             for (int g = 0; g < NUM_GEOM_FACTS; g++) ll.G[g] = subdomain_operator.geom_fact[g].template as<double>();
+            fdd::detect_zero_factors(ll);
             subdomain_operator.level_lists.push_back(ll);
         }
 
@@ -1717,6 +1719,7 @@ class Subdomain
             ll.num_elements = count;
             ll.first_offset = c.sub[first].offset;
             for (int g = 0; g < NUM_GEOM_FACTS; g++) ll.G[g] = subdomain_operator.geom_fact[g].template as<double>() + ll.first_offset;
+            fdd::detect_zero_factors(ll); // own elements and every ring's run, each on its own
             subdomain_operator.level_lists.push_back(ll);
         }
 
@@ -1900,7 +1903,7 @@ class Subdomain
 
         superdomain_operator.A.multiply(Au_sup, u_sup); // empty: no-op
 
-        for (auto &ll : subdomain_operator.level_lists) fdd::apply_local(ll, Au_sub_l.as<double>(), u_sub_l.as<double>(), work_dev, mfma_stiffness);
+        for (auto &ll : subdomain_operator.level_lists) fdd::apply_local(ll, Au_sub_l.as<double>(), u_sub_l.as<double>(), work_dev, mfma_stiffness, skip_zero_factors);
     }
 
     // subdomain.tpp:4161-4268
@@ -2130,6 +2133,14 @@ class Subdomain
     // factor arrays all have the form c_f(e) (w_i w_j) w_k to rounding runs on the kernel that does not stream them.
     // Returns the number of lists switched over.
     const std::vector<fdd::LevelList> &operator_lists() const { return subdomain_operator.level_lists; }
+    // how many of them run the three-array kernel in the gather form of the precision in use (flag "skip_zero_factors")
+    int lists_on_diag_kernel() const
+    {
+        int count = 0;
+        for (auto &ll : subdomain_operator.level_lists)
+            if (precision == 32 ? fdd::on_diag_kernel<float>(ll, mfma_stiffness, skip_zero_factors) : fdd::on_diag_kernel<double>(ll, mfma_stiffness, skip_zero_factors)) count++;
+        return count;
+    }
     int set_affine_geometry(bool on)
     {
         int count = 0;

@@ -409,6 +409,13 @@ class Problem:
         _H().call("fddh_problem_affine_info", self.h, ctypes.byref(dom), ctypes.byref(aff), ctypes.byref(lists), ctypes.byref(dev))
         return {"fine_domain": bool(dom.value), "sub_lists_affine": aff.value, "sub_lists": lists.value, "max_deviation": dev.value}
 
+    def zero_factor_info(self):
+        """flag "skip_zero_factors": is it on, does the fine domain's list run the kernel that streams three factor arrays
+        (its three off-diagonal arrays are zero at every point), and how many of the subdomain's lists do, of how many"""
+        on, dom, diag, lists = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        _H().call("fddh_problem_zero_factor_info", self.h, ctypes.byref(on), ctypes.byref(dom), ctypes.byref(diag), ctypes.byref(lists))
+        return {"enabled": bool(on.value), "fine_domain": bool(dom.value), "sub_lists_diag": diag.value, "sub_lists": lists.value}
+
     def dssum(self, u, mask=True, weight=False):
         out = np.zeros(self.n)
         _H().call("fddh_problem_dssum", self.h, _dp(out), _dp(np.ascontiguousarray(u)), int(mask), int(weight))
