@@ -383,6 +383,14 @@ int fdd_stiffness_affine_detect(double *elem_factors, double *deviation, const d
  * may each be NULL, as for fdd_stiffness_matrix_affine.  poly_degree 1..15, FDD_ERR_UNSUPPORTED above. */
 int fdd_stiffness_matrix_diag(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream);
 int fdd_stiffness_matrix_diag_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream);
+/* The line form of the same kernel for poly_degree 7 (an element is one wavefront; a lane owns a whole x-row, y-column and
+ * z-column of it in turn and contracts each in registers, LDS only transposes between the three): the argument list of
+ * fdd_stiffness_matrix_diag plus diag.  diag = 1: three factor arrays, G[3..5] never dereferenced, every output bit for bit
+ * that of fdd_stiffness_matrix_diag[_f32] (signs of zeros included).  diag = 0 (six arrays): that form measured no faster
+ * than fdd_sub_stiffness_matrix_gather_scaled[_f32] and is not compiled in: FDD_ERR_UNSUPPORTED, as for every poly_degree
+ * other than 7; the output is not touched then. */
+int fdd_stiffness_matrix_lines(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, int diag, void *stream);
+int fdd_stiffness_matrix_lines_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, int diag, void *stream);
 /* Are they?  One pass over G[3], G[4], G[5] on the points of the list (3-D elements): flags_out (three ints in device
  * memory) [f] = 0 exactly when every value of G[3 + f] there compares == 0.0 (-0.0 does; a denormal or a NaN does not),
  * 1 otherwise. */

@@ -242,6 +242,14 @@ int fddh_problem_affine_info(fddh_problem *p, int *fine_domain_affine, int *sub_
  * The info entry: is the flag on, does the fine Domain's list run that kernel, how many of the Subdomain's level lists do (in
  * the precision in use), of how many.  Any argument may be NULL. */
 int fddh_problem_zero_factor_info(fddh_problem *p, int *enabled, int *fine_domain_diag, int *sub_lists_diag, int *sub_lists);
+/* Flag "line_stiffness" (default 1 where the kernel library exports fdd_stiffness_matrix_lines and _lines_f32; setting it to 1
+ * on a library without them is refused, naming the missing entry): a 3-D list of degree 7 that runs the three-array kernel
+ * (see "skip_zero_factors") runs its line form, in both precisions, in the local and the gather form.  The line form gives
+ * the bits of the slab form, so histories and iterates do not change with the flag.  Lists that stream six arrays keep the
+ * slab form: their line form was built and measured no faster, and is not compiled in.  0: the slab form everywhere.
+ * The info entry: is the flag on, does the fine Domain's list run the line form, how many of the Subdomain's level lists do
+ * (in the precision in use), of how many.  Any argument may be NULL. */
+int fddh_problem_line_stiffness_info(fddh_problem *p, int *enabled, int *fine_domain_lines, int *sub_lists_lines, int *sub_lists);
 int fddh_problem_set_flag(fddh_problem *p, const char *name, int value);
 
 /* Low-order AMG preconditioner of the inner solve (Subdomain::low_order_preconditioner,

@@ -575,6 +575,257 @@ int fused_dispatch_diag(T *Au, const T *u, const int *point_dof, const double *u
     }
 }
 
+// ---------------------------------------------------------------------------
+// (2b) line form of the three-array fused kernel, 3-D, n = 8 only
+// ---------------------------------------------------------------------------
+// The same arithmetic as fused_stiffness_kernel_t<T, 8, ., ., false, true>, bit for bit, under another thread-to-data
+// mapping.  An element is one wavefront, and lane l = a + 8 b plays three roles in turn:
+//   (i, j) = (a, b)  owns the k-column: coalesced loads of u / the index gather, the z contraction, the final sum, the store;
+//   (j, k) = (a, b)  owns the x-row    u(0..7, j, k);
+//   (i, k) = (a, b)  owns the y-column u(i, 0..7, k).
+// In each role the lane holds a whole line, so D u, g * (D u) and D^T (g D u) along it are register-only 8 x 8 mat-vecs
+// with D_hat as a wave-uniform (scalar) operand: eight independent sums per pass, every one over p ascending from 0 as
+// in the reference.  Both passes walk D_hat by rows (Du_i = sum_p D[p + 8 i] u_p has i outside; Au_i += D[i + 8 p] GDu_p
+// has p outside), so no transposed table is needed.  LDS only transposes between the roles: 8 stores of u, 8 + 8 loads,
+// 8 + 8 stores of the Au_1 / Au_2 lines, 8 + 8 loads = 56 accesses per lane and element (7 per point; the slab form: 34)
+// in two round trips (the slab form: sixteen).  No workgroup barrier: a wave past the last element leaves at once.
+//
+// LDS tile of one element, in words of T: point (i, j, k) lives at  ((i + j) & 7) + 8 j + 72 k  -- rows of 8 rotated by
+// their j, slabs 72 apart.  The LDS services 8-byte reads in lane groups of 32 over 32 double-wide banks and 8-byte
+// writes in groups of 16 over 16 (MI355X: ds_read_b64 2 x 32 lanes, bank = (byte address / 4) mod 64; ds_write_b64
+// 4 x 16 lanes, mod 32); for float the groups are 32 lanes over 32 banks both ways, the same arithmetic mod 32.  With
+// r = (i + j) & 7 and s = (j + k) & 3 the bank of a point is r + 8 s (72 k = 8 k mod 32), and in every role the 8 values
+// of a give 8 different r while the 4 values of b in a group give 4 different s (2 different s mod 2 in a write group):
+//   k-column, k fixed:  r = (a + b) & 7 runs through 0..7 with a;  s = (b + k) & 3 with b;
+//   x-row,    i = p:    r = (p + a) & 7 with a;                     s = (a + b) & 3 with b at fixed a, i.e. fixed r;
+//   y-column, j = p:    r = (a + p) & 7 with a;                     s = (p + b) & 3 with b.
+// So all six patterns (k-column store, x-row and y-column loads, the two line stores, the k-column load) are free of
+// bank conflicts.  The x-row is not contiguous in LDS under the rotation: its loads are 8-byte, which run at the same
+// 256 B per clock as 16-byte ones.  Au_1 has a tile of its own; the y-column role writes Au_2 over the u tile (every
+// lane's loads of u precede those stores in the wave's instruction order, which the LDS keeps), so only one of the two
+// lines of u is in registers at a time: 2 x 4.5 KiB per element in double, 36 KiB per workgroup, four workgroups per CU.
+//
+// Three arrays (kDiag): g[2] coalesced in k-column role, g[1] in y-column role (8 lanes x 8 B per 64-byte segment:
+// sector-exact), g[0] in x-row role as 64 contiguous bytes per lane (plain loads, the lanes of a row share cache lines
+// across them; loaded coalesced and transposed through LDS instead it measured 107.6 against 106.6 us per launch at 32^3
+// elements in double and 69.5 against 65.0 in float, and was taken out).  Each role forms D u, g * (D u) and D^T (g D u)
+// of its line without leaving registers: two LDS round trips per element.
+// Six arrays: G Du mixes the three directions at a point, so Du_1 and Du_2 have to go back to the k-column role through
+// the two tiles for the 3 x 3 combination (factors coalesced as in the slab form) and GDu_1 / GDu_2 out again to the row
+// and column roles for D^T: four round trips, 15 accesses per point.  Built that way (84 VGPRs, 4 waves per SIMD, the
+// same bits) it ran 172.9 us per launch at 32^3 elements against the slab form's 169.7 in double and 94.2 against 93.6
+// in float -- that instance streams 1.10 GB and is at the memory system's rate already -- so the six-array lists keep
+// the slab form and no six-array line instance is compiled.
+struct LineCfg
+{
+    static constexpr int n = 8, nn = 64, n3 = 512;
+    static constexpr int epb = kBlock / nn; // elements (waves) per workgroup
+    static constexpr int slab = 72;
+    static constexpr int tile = n * slab;
+    __device__ static __forceinline__ int at(int i, int j, int k) { return ((i + j) & 7) + 8 * j + slab * k; }
+};
+
+// Row r of D_hat at an offset the compiler cannot see through (the offset, not the pointer: D_hat stays the read-only
+// kernel argument that scalar loads need).  The kernel uses every row six times; read off the one
+// kernel argument the 64 entries become 128 scalar registers that live from end to end, more than there are, and come
+// back out of VGPR lanes one v_readlane per use.  Opaque, a row is 8 values in scalar registers for as long as its 16
+// products last, re-read (scalar cache) by the next pass.
+template <typename T>
+__device__ __forceinline__ const T *line_row(const T *D_hat, int r)
+{
+    int at = 8 * r;
+    asm volatile("" : "+s"(at));
+    return D_hat + at;
+}
+
+// the two halves of a line's work, sums in the reference's order; D_hat is wave-uniform: scalar loads
+template <typename T>
+__device__ __forceinline__ void line_du(T (&du)[8], const T (&ul)[8], const T *__restrict__ D_hat) // du_i = sum_p D[p + 8 i] u_p
+{
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+    {
+        const T *Di = line_row(D_hat, i);
+        du[i] = T(0);
+#pragma unroll
+        for (int p = 0; p < 8; p++) du[i] += Di[p] * ul[p];
+    }
+}
+template <typename T>
+__device__ __forceinline__ void line_au(T (&au)[8], const T (&gdu)[8], const T *__restrict__ D_hat) // au_i = sum_p D[i + 8 p] gdu_p
+{
+#pragma unroll
+    for (int i = 0; i < 8; i++) au[i] = T(0);
+#pragma unroll
+    for (int p = 0; p < 8; p++)
+    {
+        const T *Dp = line_row(D_hat, p);
+#pragma unroll
+        for (int i = 0; i < 8; i++) au[i] += Dp[i] * gdu[p];
+    }
+}
+
+template <typename T, bool kGather, bool kNTStore>
+__global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restrict__ Au, const T *__restrict__ u, const int *__restrict__ point_dof, const double *__restrict__ u_scale, const T *__restrict__ D_hat, GPtrsT<T> G, const int *__restrict__ elem_offset, int num_elements)
+{
+    using C = LineCfg;
+    constexpr int n = C::n, nn = C::nn;
+    __shared__ T s_a[C::epb][C::tile]; // u, then Au_2
+    __shared__ T s_b[C::epb][C::tile]; // Au_1
+
+    const int tid = threadIdx.x;
+    const int e_loc = __builtin_amdgcn_readfirstlane(tid >> 6); // the wave is the element: bases stay in scalar registers
+    const int l = tid & 63;
+    const int a = l & 7, b = l >> 3;
+    const int elem = blockIdx.x * C::epb + e_loc;
+    if (elem >= num_elements) return; // wave-uniform; nothing below waits for another wave
+    const size_t base = elem_offset ? (size_t)elem_offset[elem] : (size_t)elem * C::n3;
+    T *ta = s_a[e_loc], *tb = s_b[e_loc];
+
+    // k-column role: u as in the slab form
+    T r_u[n];
+    if (kGather)
+    {
+        const int *pd = point_dof + base;
+        int d[n];
+#pragma unroll
+        for (int k = 0; k < n; k++) d[k] = __builtin_nontemporal_load(pd + (l + k * nn));
+#pragma unroll
+        for (int k = 0; k < n; k++) r_u[k] = u[d[k] < 0 ? 0 : d[k]];
+#pragma unroll
+        for (int k = 0; k < n; k++) r_u[k] = (d[k] < 0) ? T(0) : r_u[k];
+        if (u_scale)
+        {
+            const T sc = (T)(*u_scale);
+#pragma unroll
+            for (int k = 0; k < n; k++) r_u[k] = sc * r_u[k];
+        }
+    }
+    else
+    {
+        const T *up = u + base;
+#pragma unroll
+        for (int k = 0; k < n; k++) r_u[k] = __builtin_nontemporal_load(up + (l + k * nn));
+    }
+
+    T r_3[n];
+#pragma unroll
+    for (int m = 0; m < n; m++) r_3[m] = T(0);
+
+    {
+        // the three factor lines of this lane, all requested before anything waits
+        T g0[n], g1[n], g2[n];
+#pragma unroll
+        for (int k = 0; k < n; k++) g2[k] = __builtin_nontemporal_load(G.g[2] + base + (l + k * nn)); // (i, j) = (a, b), k
+        {
+            const T *g0p = G.g[0] + base + 8 * l; // (j, k) = (a, b): the row starts at 8 a + 64 b
+#pragma unroll
+            for (int p = 0; p < n; p++) g0[p] = g0p[p];
+        }
+        {
+            const T *g1p = G.g[1] + base + (a + nn * b); // (i, k) = (a, b): the column steps by 8
+#pragma unroll
+            for (int p = 0; p < n; p++) g1[p] = __builtin_nontemporal_load(g1p + 8 * p);
+        }
+
+#pragma unroll
+        for (int k = 0; k < n; k++) ta[C::at(a, b, k)] = r_u[k];
+        element_sync<true>();
+
+        // z: registers only, Au_3(i, j, m) = sum_k D_hat[m + 8 k] * (g2_k * Du_3_k), k ascending
+#pragma unroll
+        for (int k = 0; k < n; k++)
+        {
+            const T *Dk = line_row(D_hat, k);
+            T Du_3 = T(0);
+#pragma unroll
+            for (int p = 0; p < n; p++) Du_3 += Dk[p] * r_u[p];
+            const T GDu_3 = g2[k] * Du_3;
+#pragma unroll
+            for (int m = 0; m < n; m++) r_3[m] += Dk[m] * GDu_3;
+        }
+
+        // x: the row out of the u tile, Au_1 into the other tile
+        T ul[n], w[n], au[n];
+#pragma unroll
+        for (int p = 0; p < n; p++) ul[p] = ta[C::at(p, a, b)];
+        line_du(w, ul, D_hat);
+#pragma unroll
+        for (int p = 0; p < n; p++) w[p] = g0[p] * w[p];
+        line_au(au, w, D_hat);
+#pragma unroll
+        for (int p = 0; p < n; p++) tb[C::at(p, a, b)] = au[p];
+        // y: the column out of the u tile, Au_2 over it: every lane's row and column loads precede these stores in the
+        // wave's instruction order, which the LDS keeps
+#pragma unroll
+        for (int p = 0; p < n; p++) ul[p] = ta[C::at(a, p, b)];
+        element_sync<true>();
+        line_du(w, ul, D_hat);
+#pragma unroll
+        for (int p = 0; p < n; p++) w[p] = g1[p] * w[p];
+        line_au(au, w, D_hat);
+#pragma unroll
+        for (int p = 0; p < n; p++) ta[C::at(a, p, b)] = au[p];
+        element_sync<true>();
+    }
+
+    T *Aup = Au + base;
+#pragma unroll
+    for (int k = 0; k < n; k++)
+    {
+        const T v = (tb[C::at(a, b, k)] + ta[C::at(a, b, k)]) + r_3[k];
+        if (kNTStore)
+            __builtin_nontemporal_store(v, Aup + (l + k * nn));
+        else
+            Aup[l + k * nn] = v;
+    }
+}
+
+template <typename T>
+int launch_lines_t(T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const GPtrsT<T> &G, const int *elem_offset, int num_elements, void *stream)
+{
+    const int grid = (num_elements + LineCfg::epb - 1) / LineCfg::epb;
+    static const bool nt_store = fdd_env_int("FDD_TUNE_STIFFNESS_NT_STORE", 1) != 0;
+    if (point_dof and nt_store)
+        hipLaunchKernelGGL((line_stiffness_kernel_t<T, true, true>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements);
+    else if (point_dof)
+        hipLaunchKernelGGL((line_stiffness_kernel_t<T, true, false>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements);
+    else if (nt_store)
+        hipLaunchKernelGGL((line_stiffness_kernel_t<T, false, true>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements);
+    else
+        hipLaunchKernelGGL((line_stiffness_kernel_t<T, false, false>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements);
+    FDD_LAUNCH_CHECK();
+    return 0;
+}
+
+// diag = 1: three factor arrays, G[3..5] are not passed on (never dereferenced).  diag = 0: six arrays -- that form was built
+// and timed (see above), was not ahead of the slab form and is not compiled in: FDD_ERR_UNSUPPORTED
+template <typename T>
+int lines_dispatch(T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const T *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, int diag, void *stream)
+{
+    FDD_REQUIRE(num_elements >= 0 && (diag == 0 || diag == 1));
+    if (poly_degree != 7)
+    {
+        fdd_set_error("the line form of the stiffness kernel supports poly_degree 7 only, got %d", poly_degree);
+        return FDD_ERR_UNSUPPORTED;
+    }
+    if (diag == 0)
+    {
+        fdd_set_error("the line form of the stiffness kernel on six factor arrays measured no faster than the slab form and is not compiled in (diag = 0)");
+        return FDD_ERR_UNSUPPORTED;
+    }
+    if (num_elements == 0) return 0;
+    FDD_REQUIRE(Au != nullptr && u != nullptr && D_hat != nullptr && G != nullptr);
+    GPtrsT<T> g;
+    for (int k = 0; k < FDD_NUM_GEOM_FACTS; k++) g.g[k] = nullptr;
+    for (int k = 0; k < 3; k++)
+    {
+        FDD_REQUIRE(G[k] != nullptr);
+        g.g[k] = G[k];
+    }
+    return launch_lines_t<T>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
+}
+
 // flags[f] = 1 where array 3 + f of the list holds a value that is not a zero: any bit besides the sign set, so -0.0 passes
 // and a denormal or a NaN does not, whatever the denormal mode.  flags are cleared by the caller; every lane that finds
 // such a value stores the same 1.
@@ -1028,6 +1279,16 @@ int fdd_stiffness_matrix_diag(double *Au, const double *v, const double *v_scale
 int fdd_stiffness_matrix_diag_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
 {
     return fused_dispatch_diag<float>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, num_elements, poly_degree, stream);
+}
+
+int fdd_stiffness_matrix_lines(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, int diag, void *stream)
+{
+    return lines_dispatch<double>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, num_elements, poly_degree, diag, stream);
+}
+
+int fdd_stiffness_matrix_lines_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, int diag, void *stream)
+{
+    return lines_dispatch<float>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, num_elements, poly_degree, diag, stream);
 }
 
 int fdd_stiffness_offdiag_zero(int *flags_out, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)

@@ -475,6 +475,7 @@ class Domain
     bool fused_update_flexible_dot = true; // one rank, z~ written in place, early_gamma: the inner solve's final update of z~ is formed inside the flexible dot's pass (same bits; 0: a kernel of its own in front of the dot)
     bool unit_stitch_in_place = true; // stitching weights of the dof slice all exactly 1 (one rank): the inner solve writes z~ in place (0: the multiplication by the ones, the reference's sequence)
     bool mfma_stiffness = true; // N >= 11: stiffness on the fp64 matrix cores (not bit-identical; 1e-12 tolerance)
+    bool line_stiffness = fdd::missing_line_stiffness_entry() == nullptr;  // degree-7 lists on the three-array kernel run its line form (element_operator.hpp)
     bool skip_zero_factors = fdd::missing_zero_factor_entry() == nullptr; // off-diagonal factor arrays that are identically zero are not streamed (element_operator.hpp)
     DType tolerance = 1.0e-07;
     std::vector<DType> residual_history; // what the reference prints per iteration
@@ -851,7 +852,7 @@ class Domain
     // domain.tpp:602-609
     void stiffness_matrix(fdd::memory &Au, fdd::memory &u, bool apply_dssum = false)
     {
-        fdd::apply_local(list, Au.as<double>(), u.as<double>(), work_dev, mfma_stiffness, skip_zero_factors);
+        fdd::apply_local(list, Au.as<double>(), u.as<double>(), work_dev, mfma_stiffness, skip_zero_factors, line_stiffness);
         if (apply_dssum) direct_stiffness_summation(Au, Au, true, false);
     }
 
@@ -967,6 +968,7 @@ class Domain
     // (a box mesh); false: it did not, or the mesh cannot run that kernel.
     const fdd::LevelList &operator_list() const { return list; }
     bool runs_diag_kernel() const { return fdd::on_diag_kernel<double>(list, mfma_stiffness, skip_zero_factors); } // flag "skip_zero_factors"
+    bool runs_line_kernel() const { return fdd::on_line_kernel<double>(list, mfma_stiffness, skip_zero_factors, line_stiffness); } // flag "line_stiffness"
     bool set_affine_geometry(bool on)
     {
         list.affine = on and fdd::detect_affine(list);
@@ -976,7 +978,7 @@ class Domain
     // q (points) = A_local (Q p~)
     void stiffness_from_nodes(fdd::memory &q, fdd::memory &pn)
     {
-        fdd::apply_gather(list, q.as<double>(), pn.as<double>(), point_node_dev.as<int>(), nullptr, num_local_nodes, mfma_stiffness, skip_zero_factors);
+        fdd::apply_gather(list, q.as<double>(), pn.as<double>(), point_node_dev.as<int>(), nullptr, num_local_nodes, mfma_stiffness, skip_zero_factors, line_stiffness);
     }
 
     // sqrt(<r, QQt r>) (domain.tpp:916-931) from r^ = Qt r: sum_n r^_n * gs(r^)_n * mask_n.

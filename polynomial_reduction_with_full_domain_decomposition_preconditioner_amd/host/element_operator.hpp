@@ -92,9 +92,30 @@ inline bool on_diag_kernel(const LevelList &ll, bool mfma_enabled, bool skip_zer
     return skip_zero_factors and ll.offdiag_zero and not ll.affine and not on_matrix_cores<Real>(ll, mfma_enabled);
 }
 
+// ---- the line form of the stiffness kernel (flag "line_stiffness") ----
+// the first entry of the line form the loaded kernel library does not export, or nullptr
+inline const char *missing_line_stiffness_entry()
+{
+    if (&fdd_stiffness_matrix_lines == nullptr) return "fdd_stiffness_matrix_lines";
+    if (&fdd_stiffness_matrix_lines_f32 == nullptr) return "fdd_stiffness_matrix_lines_f32";
+    return nullptr;
+}
+
+// does the list run the line form for this precision, in the local and in the gather form alike?  3-D, degree 7 (an element
+// is one wavefront), not affine, not on the matrix cores, entry present, flag on -- and on the three-array kernel
+// (on_diag_kernel): the six-array line form measured no faster than the slab form in either precision (172.9 against 169.7
+// and 94.2 against 93.6 us per launch at 32^3 elements), so those lists keep the slab form and the kernel library compiles
+// no six-array line instance.  The line form gives the bits of the instance it replaces, so nothing that hangs on the
+// operator changes with the flag.
+template <typename Real>
+inline bool on_line_kernel(const LevelList &ll, bool mfma_enabled, bool skip_zero_factors, bool line_stiffness)
+{
+    return line_stiffness and ll.dim == 3 and ll.poly_degree == 7 and on_diag_kernel<Real>(ll, mfma_enabled, skip_zero_factors) and missing_line_stiffness_entry() == nullptr;
+}
+
 // Au = A_L u on the points of the list (Au, u: the vectors the list's first_offset counts in).  workspace: three vectors
 // of the list's points for the two-launch form above degree 15.
-inline void apply_local(const LevelList &ll, double *Au, const double *u, const std::vector<memory> &workspace, bool mfma_enabled, bool skip_zero_factors)
+inline void apply_local(const LevelList &ll, double *Au, const double *u, const std::vector<memory> &workspace, bool mfma_enabled, bool skip_zero_factors, bool line_stiffness)
 {
     void *stream = dev().stream;
     const double points = (double)ll.num_points();
@@ -104,6 +125,11 @@ inline void apply_local(const LevelList &ll, double *Au, const double *u, const 
         // high order: the six contractions on the fp64 matrix cores (tolerance-level parity, fdd_hip.h)
         ProfileScope prof("mfma_stiffness_kernel", 64.0 * points);
         FDD_CALL(fdd_stiffness_matrix_mfma(Au, u, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, stream));
+    }
+    else if (on_line_kernel<double>(ll, mfma_enabled, skip_zero_factors, line_stiffness))
+    {
+        ProfileScope prof("line_stiffness_kernel", 40.0 * points); // the bytes of the three-array instance it replaces
+        FDD_CALL(fdd_stiffness_matrix_lines(Au, u, nullptr, nullptr, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, 1, stream));
     }
     else if (on_diag_kernel<double>(ll, mfma_enabled, skip_zero_factors)) // the gather form's predicate: one answer per list (3-D, degree <= 15: nothing else is checked)
     {
@@ -154,6 +180,16 @@ inline void stiffness_diag(const LevelList &ll, float *q, const float *v, const 
     for (int g = 0; g < NUM_GEOM_FACTS; g++) G[g] = ll.G32[g].as<float>();
     FDD_CALL(fdd_stiffness_matrix_diag_f32(q, v, scale_dev, point_index, ll.D_hat32.as<float>(), G, nullptr, ll.num_elements, ll.poly_degree, s));
 }
+inline void stiffness_lines(const LevelList &ll, double *q, const double *v, const double *scale_dev, const int *point_index, void *s)
+{
+    FDD_CALL(fdd_stiffness_matrix_lines(q, v, scale_dev, point_index, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, 1, s));
+}
+inline void stiffness_lines(const LevelList &ll, float *q, const float *v, const double *scale_dev, const int *point_index, void *s)
+{
+    const float *G[NUM_GEOM_FACTS];
+    for (int g = 0; g < NUM_GEOM_FACTS; g++) G[g] = ll.G32[g].as<float>();
+    FDD_CALL(fdd_stiffness_matrix_lines_f32(q, v, scale_dev, point_index, ll.D_hat32.as<float>(), G, nullptr, ll.num_elements, ll.poly_degree, 1, s));
+}
 inline void stiffness_affine(const LevelList &ll, double *q, const double *v, const double *scale_dev, const int *point_index, bool mfma, void *s)
 {
     FDD_CALL((mfma ? fdd_stiffness_matrix_mfma_affine : fdd_stiffness_matrix_affine)(q, v, scale_dev, point_index, ll.D_hat, ll.affine_c.as<double>(), ll.affine_w.as<double>(), nullptr, ll.num_elements, ll.poly_degree, s));
@@ -168,7 +204,7 @@ inline void stiffness_affine(const LevelList &ll, float *q, const float *v, cons
 // (null: 1).  q, point_index: the arrays the list's first_offset counts in; gathered_values: the length of v (the bytes it
 // adds to the count).  3-D lists of degree <= 15.
 template <typename Real>
-inline void apply_gather(const LevelList &ll, Real *q, const Real *v, const int *point_index, const double *scale_dev, int gathered_values, bool mfma_enabled, bool skip_zero_factors)
+inline void apply_gather(const LevelList &ll, Real *q, const Real *v, const int *point_index, const double *scale_dev, int gathered_values, bool mfma_enabled, bool skip_zero_factors, bool line_stiffness)
 {
     constexpr bool f32 = std::is_same<Real, float>::value;
     const bool mfma = on_matrix_cores<Real>(ll, mfma_enabled);
@@ -178,6 +214,12 @@ inline void apply_gather(const LevelList &ll, Real *q, const Real *v, const int 
     {
         ProfileScope prof(f32 ? "fused_stiffness_kernel<gather,f32,affine>" : mfma ? "mfma_stiffness_kernel<gather,affine>" : "fused_stiffness_kernel<gather,affine>", (f32 ? 8.0 : 12.0) * points + gathered);
         ops::stiffness_affine(ll, q, v, scale_dev, point_index, mfma, dev().stream);
+        return;
+    }
+    if (on_line_kernel<Real>(ll, mfma_enabled, skip_zero_factors, line_stiffness))
+    {
+        ProfileScope prof(f32 ? "line_stiffness_kernel<gather,f32>" : "line_stiffness_kernel<gather>", (f32 ? 20.0 : 36.0) * points + gathered); // the bytes of the instance it replaces
+        ops::stiffness_lines(ll, q, v, scale_dev, point_index, dev().stream);
         return;
     }
     if (on_diag_kernel<Real>(ll, mfma_enabled, skip_zero_factors))

@@ -60,6 +60,10 @@
 #pragma weak fdd_stiffness_matrix_diag
 #pragma weak fdd_stiffness_matrix_diag_f32
 #pragma weak fdd_stiffness_offdiag_zero
+// and the line form of the stiffness kernel at degree 7: without it those lists stay on the slab form, and the flag
+// "line_stiffness" refuses to be set to 1, naming the missing entry (missing_line_stiffness_entry, element_operator.hpp)
+#pragma weak fdd_stiffness_matrix_lines
+#pragma weak fdd_stiffness_matrix_lines_f32
 
 namespace fdd
 {

@@ -963,6 +963,25 @@ int fddh_problem_zero_factor_info(fddh_problem *p, int *enabled, int *fine_domai
     }
 }
 
+int fddh_problem_line_stiffness_info(fddh_problem *p, int *enabled, int *fine_domain_lines, int *sub_lists_lines, int *sub_lists)
+{
+    try
+    {
+        if (int rc = rank_check(p)) return rc;
+        if (!p) return fail("null argument");
+        Domain<SType> &dom = p->fine();
+        if (enabled) *enabled = dom.line_stiffness ? 1 : 0;
+        if (fine_domain_lines) *fine_domain_lines = dom.runs_line_kernel() ? 1 : 0;
+        if (sub_lists_lines) *sub_lists_lines = p->subdomain ? p->subdomain->lists_on_line_kernel() : 0;
+        if (sub_lists) *sub_lists = p->subdomain ? (int)p->subdomain->operator_lists().size() : 0;
+        return 0;
+    }
+    catch (const std::exception &e)
+    {
+        return fail("%s", e.what());
+    }
+}
+
 int fddh_problem_set_flag(fddh_problem *p, const char *name, int value)
 {
     try
@@ -1067,6 +1086,15 @@ int fddh_problem_set_flag(fddh_problem *p, const char *name, int value)
                 if (const char *missing = fdd::missing_zero_factor_entry()) return fail("skip_zero_factors needs %s, which the loaded kernel library does not export", missing);
             for (auto &kv : p->domains) kv.second.skip_zero_factors = value != 0;
             if (p->subdomain) p->subdomain->skip_zero_factors = value != 0;
+        }
+        else if (s == "line_stiffness")
+        {
+            // 3-D degree-7 lists on the three-array kernel run its line form (default where the kernel library has it); 0: the
+            // slab form.  Same bits either way, so nothing that hangs on the operator is emptied.
+            if (value != 0)
+                if (const char *missing = fdd::missing_line_stiffness_entry()) return fail("line_stiffness needs %s, which the loaded kernel library does not export", missing);
+            for (auto &kv : p->domains) kv.second.line_stiffness = value != 0;
+            if (p->subdomain) p->subdomain->line_stiffness = value != 0;
         }
         else if (s == "fused_projection")
         {

@@ -927,7 +927,7 @@ class Subdomain
     template <typename Real>
     void stiffness_from_dofs(Real *q, const Real *za, const double *scale_dev = nullptr)
     {
-        for (auto &ll : subdomain_operator.level_lists) fdd::apply_gather(ll, q, za, point_dof_dev.template as<int>(), scale_dev, subdomain_operator.num_extended_dofs, mfma_stiffness, skip_zero_factors);
+        for (auto &ll : subdomain_operator.level_lists) fdd::apply_gather(ll, q, za, point_dof_dev.template as<int>(), scale_dev, subdomain_operator.num_extended_dofs, mfma_stiffness, skip_zero_factors, line_stiffness);
     }
 
     // y (dofs) = [Qt A_L Q | A_sup] (s x~): the operator of the inner iteration on a dof vector.  x~ is one of the
@@ -1402,6 +1402,7 @@ class Subdomain
         history_pending = false;
     }
     bool mfma_stiffness = true;           // N >= 11 element lists on the fp64 matrix cores
+    bool line_stiffness = fdd::missing_line_stiffness_entry() == nullptr;  // degree-7 lists on the three-array kernel run its line form (element_operator.hpp)
     bool skip_zero_factors = fdd::missing_zero_factor_entry() == nullptr; // lists whose off-diagonal factor arrays are identically zero do not stream them (element_operator.hpp)
     std::vector<DType> residual_history;  // inner history of the last application
 
@@ -1903,7 +1904,7 @@ class Subdomain
 
         superdomain_operator.A.multiply(Au_sup, u_sup); // empty: no-op
 
-        for (auto &ll : subdomain_operator.level_lists) fdd::apply_local(ll, Au_sub_l.as<double>(), u_sub_l.as<double>(), work_dev, mfma_stiffness, skip_zero_factors);
+        for (auto &ll : subdomain_operator.level_lists) fdd::apply_local(ll, Au_sub_l.as<double>(), u_sub_l.as<double>(), work_dev, mfma_stiffness, skip_zero_factors, line_stiffness);
     }
 
     // subdomain.tpp:4161-4268
@@ -2139,6 +2140,14 @@ class Subdomain
         int count = 0;
         for (auto &ll : subdomain_operator.level_lists)
             if (precision == 32 ? fdd::on_diag_kernel<float>(ll, mfma_stiffness, skip_zero_factors) : fdd::on_diag_kernel<double>(ll, mfma_stiffness, skip_zero_factors)) count++;
+        return count;
+    }
+    // and how many the line form of it (flag "line_stiffness")
+    int lists_on_line_kernel() const
+    {
+        int count = 0;
+        for (auto &ll : subdomain_operator.level_lists)
+            if (precision == 32 ? fdd::on_line_kernel<float>(ll, mfma_stiffness, skip_zero_factors, line_stiffness) : fdd::on_line_kernel<double>(ll, mfma_stiffness, skip_zero_factors, line_stiffness)) count++;
         return count;
     }
     int set_affine_geometry(bool on)

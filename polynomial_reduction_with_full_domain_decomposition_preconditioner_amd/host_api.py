@@ -416,6 +416,13 @@ class Problem:
         _H().call("fddh_problem_zero_factor_info", self.h, ctypes.byref(on), ctypes.byref(dom), ctypes.byref(diag), ctypes.byref(lists))
         return {"enabled": bool(on.value), "fine_domain": bool(dom.value), "sub_lists_diag": diag.value, "sub_lists": lists.value}
 
+    def line_stiffness_info(self):
+        """flag "line_stiffness": is it on, does the fine domain's list run the line form of the three-array stiffness
+        kernel (degree 7), and how many of the subdomain's lists do, of how many"""
+        on, dom, lines, lists = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        _H().call("fddh_problem_line_stiffness_info", self.h, ctypes.byref(on), ctypes.byref(dom), ctypes.byref(lines), ctypes.byref(lists))
+        return {"enabled": bool(on.value), "fine_domain": bool(dom.value), "sub_lists_lines": lines.value, "sub_lists": lists.value}
+
     def dssum(self, u, mask=True, weight=False):
         out = np.zeros(self.n)
         _H().call("fddh_problem_dssum", self.h, _dp(out), _dp(np.ascontiguousarray(u)), int(mask), int(weight))
