@@ -236,12 +236,22 @@ int fddh_problem_affine_info(fddh_problem *p, int *fine_domain_affine, int *sub_
  * fdd_stiffness_offdiag_zero; setting it to 1 on a library without them is refused, naming the missing entry): a 3-D element
  * list of degree <= 15 whose three off-diagonal factor arrays are 0.0 at every point -- checked once on the device when the
  * list's factor pointers are set; every box and rectilinear mesh -- runs the stiffness kernel that streams three factor arrays
- * instead of six, unless "affine_geometry" has switched it over or it runs on the matrix cores.  Unlike "affine_geometry" this
+ * instead of six, unless "affine_geometry" has switched it over; a list on the matrix cores (degree 11..15, "mfma_stiffness")
+ * takes their three-array instance under "mfma_skip_zero_factors" below and is not counted here.  Unlike "affine_geometry" this
  * leaves the operator's values as they are (the addition of exact zeros is all that is dropped; the sign of a zero may
  * differ), so nothing that hangs on the operator is emptied.  0: six arrays everywhere.
  * The info entry: is the flag on, does the fine Domain's list run that kernel, how many of the Subdomain's level lists do (in
  * the precision in use), of how many.  Any argument may be NULL. */
 int fddh_problem_zero_factor_info(fddh_problem *p, int *enabled, int *fine_domain_diag, int *sub_lists_diag, int *sub_lists);
+/* Flag "mfma_skip_zero_factors" (default 1 where the kernel library exports fdd_stiffness_matrix_mfma_diag besides the entries
+ * above; setting it to 1 on a library without it is refused, naming the missing entry): a list whose off-diagonal factor
+ * arrays are zero (the same check) and that runs on the matrix cores runs their three-array instance.  It takes effect only
+ * while "skip_zero_factors" and "mfma_stiffness" are both on -- "skip_zero_factors" = 0 goes on meaning six arrays everywhere --
+ * and "affine_geometry" keeps precedence.  The values are those of the six-array matrix-core kernel (the sign of a zero may
+ * differ), so nothing that hangs on the operator is emptied.  The info entry: is the flag on, does the fine Domain's list run
+ * that instance, how many of the Subdomain's level lists do (in the precision in use: none in a float inner solve, which has
+ * no matrix-core kernel), of how many.  Any argument may be NULL. */
+int fddh_problem_mfma_zero_factor_info(fddh_problem *p, int *enabled, int *fine_domain_mfma_diag, int *sub_lists_mfma_diag, int *sub_lists);
 /* Flag "line_stiffness" (default 1 where the kernel library exports fdd_stiffness_matrix_lines and _lines_f32; setting it to 1
  * on a library without them is refused, naming the missing entry): a 3-D list of degree 7 that runs the three-array kernel
  * (see "skip_zero_factors") runs its line form, in both precisions, in the local and the gather form.  The line form gives

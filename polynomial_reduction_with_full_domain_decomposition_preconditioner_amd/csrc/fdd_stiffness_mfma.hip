@@ -45,6 +45,9 @@ namespace
 #ifndef FDD_MFMA_TRACE
 #define FDD_MFMA_TRACE 0 // 1: wave 0 of workgroup 0 accumulates the cycles spent in each phase and prints them (development)
 #endif
+#ifndef FDD_MFMA_DIAG_DT_REGS
+#define FDD_MFMA_DIAG_DT_REGS 0 // 1: the kDiag instances keep the D^T fragments in registers too (development A/B: no faster, see kDiag below)
+#endif
 #if FDD_MFMA_TRACE
 #define FDD_TR(k)                                   \
     do                                              \
@@ -140,7 +143,16 @@ __device__ __forceinline__ void tile_add(double *dst, int base, int rs, int cs, 
 // kAffine: the factors of a point are c_f(e) (w_i w_j) w_k, formed in P2 from six numbers per element (G.g[0], element-
 // major) and the GLL weights (G.g[1]) instead of prefetched from the six arrays -- 48 of the 64 bytes per point are not
 // read (fdd_stiffness.hip, fused_stiffness_kernel_t; an option of this build for affine elements).
-template <int n, bool kGather, bool kAffine = false>
+// kDiag: the three off-diagonal factor arrays G.g[3..5] are NOT streamed: the caller has established that they are 0.0 at
+// every point of the list (fdd_stiffness_offdiag_zero; every mesh whose elements have orthogonal axes).  Three factor
+// registers per point instead of six (12 of the lane's 24), P2 is sA_d = rg[d] * Du_d; what is left out is the addition of
+// exact zero products, so every output is the six-array instance's IEEE value for finite u, up to the sign of a zero,
+// whichever way P2 is contracted.  40 B per point instead of 64 (gather form: 36 + the dofs instead of 60).  The gather
+// instance at n = 16 takes 109 VGPRs (six arrays: 126), no scratch, 4 waves per SIMD; at 32^3 elements, N = 15 it runs
+// 1.03 ms per launch against 1.60 ms.  With the freed registers the D^T fragments fit too (FDD_MFMA_DIAG_DT_REGS: 118 VGPRs,
+// no scratch), but that measured 1.030-1.033 ms against 1.026-1.030 ms: the LDS reads of the fragments are not what holds
+// this kernel, and the fragments stay in LDS.
+template <int n, bool kGather, bool kAffine = false, bool kDiag = false>
 __global__ __launch_bounds__(kThreads) void mfma_stiffness_kernel(double *__restrict__ Au, const double *__restrict__ u, const int *__restrict__ point_dof, const double *__restrict__ u_scale, const double *__restrict__ D_hat, GPtrs G, const int *__restrict__ elem_offset, int num_elements, int xcd_window)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -160,6 +172,12 @@ __global__ __launch_bounds__(kThreads) void mfma_stiffness_kernel(double *__rest
     // reload waits on the in-order vector-memory counter, i.e. on the next element's prefetched loads and on the stores
     // of the previous one.
     double a_D[4];
+#if FDD_MFMA_DIAG_DT_REGS
+    double a_Dt[4]; // development A/B: the three-array instance has the registers for them (used where kDiag)
+#define FDD_PRODUCT_DT(src, base, rs, cs) (kDiag ? tile_product(src, base, rs, cs, a_Dt, lane) : tile_product_lds(src, base, rs, cs, sDt, lane))
+#else
+#define FDD_PRODUCT_DT(src, base, rs, cs) tile_product_lds(src, base, rs, cs, sDt, lane)
+#endif
     {
         const int row = lane & 15, kk = lane >> 4;
 #pragma unroll
@@ -169,6 +187,9 @@ __global__ __launch_bounds__(kThreads) void mfma_stiffness_kernel(double *__rest
             const bool in = (row < n) && (p < n);
             a_D[s] = in ? D_hat[p + row * n] : 0.0;                              // D[row][p]   = D_hat[p + row*n_x] (domain.okl:42)
             if (wave == 0) sDt[s * 64 + lane] = in ? D_hat[row + p * n] : 0.0;  // D^T[row][p] = D_hat[row + p*n_x] (domain.okl:90)
+#if FDD_MFMA_DIAG_DT_REGS
+            a_Dt[s] = in ? D_hat[row + p * n] : 0.0;
+#endif
         }
     }
     __syncthreads();
@@ -198,7 +219,8 @@ __global__ __launch_bounds__(kThreads) void mfma_stiffness_kernel(double *__rest
     if (blockIdx.x & 1)
         for (int w_ = 0; w_ < FDD_MFMA_STAGGER; w_++) __builtin_amdgcn_s_sleep(127);
 #endif
-    double ru[kPts], rg[FDD_NUM_GEOM_FACTS][kPts];
+    constexpr int nG = kDiag ? 3 : FDD_NUM_GEOM_FACTS; // factor arrays streamed
+    double ru[kPts], rg[nG][kPts];
     int rd[kGather ? kPts : 1];
     // Which elements the persistent workgroups visit together.  Under round-robin dispatch workgroup b sits on XCD b % 8, so
     // in plain order the x-neighbours e and e + 1 -- which share a face whose 256 dofs are the LAST dof of 256 different
@@ -233,7 +255,7 @@ __global__ __launch_bounds__(kThreads) void mfma_stiffness_kernel(double *__rest
 #pragma unroll
             for (int m = 0; m < kPts; m++)
 #pragma unroll
-                for (int g = 0; g < FDD_NUM_GEOM_FACTS; g++) rg[g][m] = valid(m) ? (G.g[g] + base)[goff(m)] : 0.0;
+                for (int g = 0; g < nG; g++) rg[g][m] = valid(m) ? (G.g[g] + base)[goff(m)] : 0.0;
         }
     }
     // kAffine: (w_i w_j) of the lane's four points and w_k of its slab; zero on the padding
@@ -315,26 +337,35 @@ __global__ __launch_bounds__(kThreads) void mfma_stiffness_kernel(double *__rest
         for (int m = 0; m < kPts; m++)
         {
             const double Du_1 = sA1[lidx(m)], Du_2 = sA2[lidx(m)], Du_3 = sA3[lidx(m)];
-            sA1[lidx(m)] = rg[0][m] * Du_1 + rg[3][m] * Du_2 + rg[4][m] * Du_3;
-            sA2[lidx(m)] = rg[3][m] * Du_1 + rg[1][m] * Du_2 + rg[5][m] * Du_3;
-            sA3[lidx(m)] = rg[4][m] * Du_1 + rg[5][m] * Du_2 + rg[2][m] * Du_3;
+            if constexpr (kDiag)
+            {
+                sA1[lidx(m)] = rg[0][m] * Du_1;
+                sA2[lidx(m)] = rg[1][m] * Du_2;
+                sA3[lidx(m)] = rg[2][m] * Du_3;
+            }
+            else
+            {
+                sA1[lidx(m)] = rg[0][m] * Du_1 + rg[3][m] * Du_2 + rg[4][m] * Du_3;
+                sA2[lidx(m)] = rg[3][m] * Du_1 + rg[1][m] * Du_2 + rg[5][m] * Du_3;
+                sA3[lidx(m)] = rg[4][m] * Du_1 + rg[5][m] * Du_2 + rg[2][m] * Du_3;
+            }
         }
         if (!kAffine && (FDD_MFMA_UNCOND_PREFETCH || more))
         {
 #pragma unroll
             for (int m = 0; m < kPts; m++)
 #pragma unroll
-                for (int g = 0; g < FDD_NUM_GEOM_FACTS; g++) rg[g][m] = valid(m) ? (G.g[g] + base_n)[goff(m)] : 0.0;
+                for (int g = 0; g < nG; g++) rg[g][m] = valid(m) ? (G.g[g] + base_n)[goff(m)] : 0.0;
         }
         wave_lds_sync(); // P2 wrote this wave's slab of sA1 / sA2, which is all P3a reads
         FDD_TR(5);
 
         // P3a: Au_x then + Au_y on this wave's xy-slab (sU is free: the z products that read it are behind a barrier)
         {
-            v4f64 y = tile_product_lds(sA1, wave * PL, 1, LD, sDt, lane);
+            v4f64 y = FDD_PRODUCT_DT(sA1, wave * PL, 1, LD);
             tile_store(sU, wave * PL, 1, LD, y, lane);
             wave_lds_sync();
-            y = tile_product_lds(sA2, wave * PL, LD, 1, sDt, lane);
+            y = FDD_PRODUCT_DT(sA2, wave * PL, LD, 1);
             tile_add(sU, wave * PL, LD, 1, y, lane);
         }
         FDD_TR(6);
@@ -343,7 +374,7 @@ __global__ __launch_bounds__(kThreads) void mfma_stiffness_kernel(double *__rest
 
         // P3b: + Au_z on this wave's xz-slab
         {
-            v4f64 y = tile_product_lds(sA3, wave * LD, PL, 1, sDt, lane);
+            v4f64 y = FDD_PRODUCT_DT(sA3, wave * LD, PL, 1);
             tile_add(sU, wave * LD, PL, 1, y, lane);
         }
         FDD_TR(8);
@@ -361,12 +392,13 @@ __global__ __launch_bounds__(kThreads) void mfma_stiffness_kernel(double *__rest
         printf("mfma trace (cycles per element, wave 0 of workgroup 0, %d elements): P0+issue %llu | xy %llu | wait %llu | z %llu | wait %llu | P2+issue %llu | P3a %llu | wait %llu | P3b %llu | wait %llu | P4 %llu\n", tr_elems,
                tr_[0] / tr_elems, tr_[1] / tr_elems, tr_[2] / tr_elems, tr_[3] / tr_elems, tr_[4] / tr_elems, tr_[5] / tr_elems, tr_[6] / tr_elems, tr_[7] / tr_elems, tr_[8] / tr_elems, tr_[9] / tr_elems, tr_[10] / tr_elems);
 #endif
+#undef FDD_PRODUCT_DT
 #undef lidx
 #undef goff
 #undef valid
 }
 
-template <int n, bool kAffine = false>
+template <int n, bool kAffine = false, bool kDiag = false>
 int launch_mfma(double *Au, const double *u, const int *point_dof, const double *u_scale, const double *D_hat, const GPtrs &G, const int *elem_offset, int num_elements, void *stream)
 {
     const size_t lds = (4 * (size_t)ARR + 4 * 64) * sizeof(double);
@@ -374,8 +406,8 @@ int launch_mfma(double *Au, const double *u, const int *point_dof, const double 
     static std::once_flag configured;
     hipError_t attr_a = hipSuccess, attr_b = hipSuccess;
     std::call_once(configured, [&] {
-        attr_a = hipFuncSetAttribute(reinterpret_cast<const void *>(mfma_stiffness_kernel<n, false, kAffine>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_b = hipFuncSetAttribute(reinterpret_cast<const void *>(mfma_stiffness_kernel<n, true, kAffine>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        attr_a = hipFuncSetAttribute(reinterpret_cast<const void *>(mfma_stiffness_kernel<n, false, kAffine, kDiag>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        attr_b = hipFuncSetAttribute(reinterpret_cast<const void *>(mfma_stiffness_kernel<n, true, kAffine, kDiag>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     });
     FDD_HIP_CHECK(attr_a);
     FDD_HIP_CHECK(attr_b);
@@ -386,9 +418,9 @@ int launch_mfma(double *Au, const double *u, const int *point_dof, const double 
     static const int xcd_env = fdd_env_int("FDD_TUNE_MFMA_XCD_WINDOW", -1);
     const int xcd_window = xcd_env < 0 ? grid / FDD_NUM_XCD : xcd_env;
     if (point_dof)
-        hipLaunchKernelGGL((mfma_stiffness_kernel<n, true, kAffine>), dim3(grid), dim3(kThreads), lds, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, xcd_window);
+        hipLaunchKernelGGL((mfma_stiffness_kernel<n, true, kAffine, kDiag>), dim3(grid), dim3(kThreads), lds, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, xcd_window);
     else
-        hipLaunchKernelGGL((mfma_stiffness_kernel<n, false, kAffine>), dim3(grid), dim3(kThreads), lds, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, xcd_window);
+        hipLaunchKernelGGL((mfma_stiffness_kernel<n, false, kAffine, kDiag>), dim3(grid), dim3(kThreads), lds, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, xcd_window);
     FDD_LAUNCH_CHECK();
     return 0;
 }
@@ -412,6 +444,35 @@ int mfma_dispatch_affine(double *Au, const double *u, const int *point_dof, cons
     case 14: return launch_mfma<14, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
     case 15: return launch_mfma<15, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
     case 16: return launch_mfma<16, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
+    default:
+        fdd_set_error("fp64-MFMA stiffness kernel supports poly_degree 8..15, got %d", poly_degree);
+        return FDD_ERR_UNSUPPORTED;
+    }
+}
+
+// the kDiag instances: G[3..5] are not passed on (never dereferenced)
+int mfma_dispatch_diag(double *Au, const double *u, const int *point_dof, const double *u_scale, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
+{
+    FDD_REQUIRE(num_elements >= 0);
+    if (num_elements == 0) return 0;
+    FDD_REQUIRE(Au != nullptr && u != nullptr && D_hat != nullptr && G != nullptr && Au != u);
+    GPtrs g;
+    for (int k = 0; k < FDD_NUM_GEOM_FACTS; k++) g.g[k] = nullptr;
+    for (int k = 0; k < 3; k++)
+    {
+        FDD_REQUIRE(G[k] != nullptr);
+        g.g[k] = G[k];
+    }
+    switch (poly_degree + 1)
+    {
+    case 9: return launch_mfma<9, false, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
+    case 10: return launch_mfma<10, false, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
+    case 11: return launch_mfma<11, false, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
+    case 12: return launch_mfma<12, false, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
+    case 13: return launch_mfma<13, false, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
+    case 14: return launch_mfma<14, false, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
+    case 15: return launch_mfma<15, false, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
+    case 16: return launch_mfma<16, false, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
     default:
         fdd_set_error("fp64-MFMA stiffness kernel supports poly_degree 8..15, got %d", poly_degree);
         return FDD_ERR_UNSUPPORTED;
@@ -457,6 +518,11 @@ int fdd_stiffness_matrix_mfma(double *Au, const double *u, const double *D_hat, 
 int fdd_stiffness_matrix_mfma_affine(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *elem_factors, const double *gll_weights, const int *elem_offset, int num_elements, int poly_degree, void *stream)
 {
     return mfma_dispatch_affine(Au, v, point_dof, v_scale_dev, D_hat, elem_factors, gll_weights, elem_offset, num_elements, poly_degree, stream);
+}
+
+int fdd_stiffness_matrix_mfma_diag(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
+{
+    return mfma_dispatch_diag(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, num_elements, poly_degree, stream);
 }
 
 int fdd_stiffness_matrix_mfma_gather(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)

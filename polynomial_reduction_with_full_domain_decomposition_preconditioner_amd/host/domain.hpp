@@ -477,6 +477,7 @@ class Domain
     bool mfma_stiffness = true; // N >= 11: stiffness on the fp64 matrix cores (not bit-identical; 1e-12 tolerance)
     bool line_stiffness = fdd::missing_line_stiffness_entry() == nullptr;  // degree-7 lists on the three-array kernel run its line form (element_operator.hpp)
     bool skip_zero_factors = fdd::missing_zero_factor_entry() == nullptr; // off-diagonal factor arrays that are identically zero are not streamed (element_operator.hpp)
+    bool mfma_skip_zero_factors = fdd::missing_mfma_zero_factor_entry() == nullptr; // nor by the matrix-core kernel (N >= 11), while skip_zero_factors and mfma_stiffness are on
     DType tolerance = 1.0e-07;
     std::vector<DType> residual_history; // what the reference prints per iteration
 
@@ -852,7 +853,7 @@ class Domain
     // domain.tpp:602-609
     void stiffness_matrix(fdd::memory &Au, fdd::memory &u, bool apply_dssum = false)
     {
-        fdd::apply_local(list, Au.as<double>(), u.as<double>(), work_dev, mfma_stiffness, skip_zero_factors, line_stiffness);
+        fdd::apply_local(list, Au.as<double>(), u.as<double>(), work_dev, mfma_stiffness, skip_zero_factors, line_stiffness, mfma_skip_zero_factors);
         if (apply_dssum) direct_stiffness_summation(Au, Au, true, false);
     }
 
@@ -968,6 +969,7 @@ class Domain
     // (a box mesh); false: it did not, or the mesh cannot run that kernel.
     const fdd::LevelList &operator_list() const { return list; }
     bool runs_diag_kernel() const { return fdd::on_diag_kernel<double>(list, mfma_stiffness, skip_zero_factors); } // flag "skip_zero_factors"
+    bool runs_mfma_diag_kernel() const { return fdd::on_mfma_diag_kernel<double>(list, mfma_stiffness, skip_zero_factors, mfma_skip_zero_factors); } // flag "mfma_skip_zero_factors"
     bool runs_line_kernel() const { return fdd::on_line_kernel<double>(list, mfma_stiffness, skip_zero_factors, line_stiffness); } // flag "line_stiffness"
     bool set_affine_geometry(bool on)
     {
@@ -978,7 +980,7 @@ class Domain
     // q (points) = A_local (Q p~)
     void stiffness_from_nodes(fdd::memory &q, fdd::memory &pn)
     {
-        fdd::apply_gather(list, q.as<double>(), pn.as<double>(), point_node_dev.as<int>(), nullptr, num_local_nodes, mfma_stiffness, skip_zero_factors, line_stiffness);
+        fdd::apply_gather(list, q.as<double>(), pn.as<double>(), point_node_dev.as<int>(), nullptr, num_local_nodes, mfma_stiffness, skip_zero_factors, line_stiffness, mfma_skip_zero_factors);
     }
 
     // sqrt(<r, QQt r>) (domain.tpp:916-931) from r^ = Qt r: sum_n r^_n * gs(r^)_n * mask_n.

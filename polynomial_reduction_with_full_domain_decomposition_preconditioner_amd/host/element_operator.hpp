@@ -67,12 +67,20 @@ inline const char *missing_zero_factor_entry()
     return nullptr;
 }
 
+// the entry of the matrix-core kernel on three factor arrays, where the loaded kernel library does not export it, or nullptr
+inline const char *missing_mfma_zero_factor_entry()
+{
+    if (&fdd_stiffness_matrix_mfma_diag == nullptr) return "fdd_stiffness_matrix_mfma_diag";
+    return missing_zero_factor_entry(); // the check that sets LevelList::offdiag_zero
+}
+
 // ---- factor arrays that are identically zero (flag "skip_zero_factors") ----
 // On a mesh whose elements have orthogonal axes (every box, every rectilinear grid) G[3..5] are 0.0 at every point.
 // detect_zero_factors establishes that from the list's OWN arrays in one pass on the device; where it holds (and the flag
 // is on) the list runs the kernel that streams G[0..2] only.  Unlike the affine option the arithmetic left out is the
 // addition of exact zeros: the operator's values are the same, to the sign of a zero.  Only 3-D lists of degree <= 15 are
-// checked (the matrix-core, 2-D and two-launch forms keep six arrays); without the entries nothing is, and nothing switches.
+// checked (the 2-D and two-launch forms keep six arrays); without the entries nothing is, and nothing switches.  A list that
+// runs on the matrix cores takes their three-array instance (on_mfma_diag_kernel, flag "mfma_skip_zero_factors").
 inline void detect_zero_factors(LevelList &ll)
 {
     ll.offdiag_zero = false;
@@ -90,6 +98,14 @@ template <typename Real>
 inline bool on_diag_kernel(const LevelList &ll, bool mfma_enabled, bool skip_zero_factors)
 {
     return skip_zero_factors and ll.offdiag_zero and not ll.affine and not on_matrix_cores<Real>(ll, mfma_enabled);
+}
+
+// does the list run the matrix-core kernel on three factor arrays?  Both flags: "skip_zero_factors" = 0 goes on meaning six
+// arrays everywhere.  The values are those of the six-array matrix-core kernel, to the sign of a zero.
+template <typename Real>
+inline bool on_mfma_diag_kernel(const LevelList &ll, bool mfma_enabled, bool skip_zero_factors, bool mfma_skip_zero_factors)
+{
+    return on_matrix_cores<Real>(ll, mfma_enabled) and skip_zero_factors and mfma_skip_zero_factors and ll.offdiag_zero and not ll.affine and missing_mfma_zero_factor_entry() == nullptr;
 }
 
 // ---- the line form of the stiffness kernel (flag "line_stiffness") ----
@@ -115,12 +131,18 @@ inline bool on_line_kernel(const LevelList &ll, bool mfma_enabled, bool skip_zer
 
 // Au = A_L u on the points of the list (Au, u: the vectors the list's first_offset counts in).  workspace: three vectors
 // of the list's points for the two-launch form above degree 15.
-inline void apply_local(const LevelList &ll, double *Au, const double *u, const std::vector<memory> &workspace, bool mfma_enabled, bool skip_zero_factors, bool line_stiffness)
+inline void apply_local(const LevelList &ll, double *Au, const double *u, const std::vector<memory> &workspace, bool mfma_enabled, bool skip_zero_factors, bool line_stiffness, bool mfma_skip_zero_factors)
 {
     void *stream = dev().stream;
     const double points = (double)ll.num_points();
     Au += ll.first_offset, u += ll.first_offset;
-    if (on_matrix_cores<double>(ll, mfma_enabled) and Au != u)
+    if (on_mfma_diag_kernel<double>(ll, mfma_enabled, skip_zero_factors, mfma_skip_zero_factors) and Au != u)
+    {
+        // not "mfma_stiffness_kernel...": the committed counters bench.py matches by that prefix are the six-array kernel's
+        ProfileScope prof("mfma_diag_stiffness_kernel", 40.0 * points);
+        FDD_CALL(fdd_stiffness_matrix_mfma_diag(Au, u, nullptr, nullptr, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, stream));
+    }
+    else if (on_matrix_cores<double>(ll, mfma_enabled) and Au != u)
     {
         // high order: the six contractions on the fp64 matrix cores (tolerance-level parity, fdd_hip.h)
         ProfileScope prof("mfma_stiffness_kernel", 64.0 * points);
@@ -180,6 +202,10 @@ inline void stiffness_diag(const LevelList &ll, float *q, const float *v, const 
     for (int g = 0; g < NUM_GEOM_FACTS; g++) G[g] = ll.G32[g].as<float>();
     FDD_CALL(fdd_stiffness_matrix_diag_f32(q, v, scale_dev, point_index, ll.D_hat32.as<float>(), G, nullptr, ll.num_elements, ll.poly_degree, s));
 }
+inline void stiffness_mfma_diag(const LevelList &ll, double *q, const double *v, const double *scale_dev, const int *point_index, void *s)
+{
+    FDD_CALL(fdd_stiffness_matrix_mfma_diag(q, v, scale_dev, point_index, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, s));
+}
 inline void stiffness_lines(const LevelList &ll, double *q, const double *v, const double *scale_dev, const int *point_index, void *s)
 {
     FDD_CALL(fdd_stiffness_matrix_lines(q, v, scale_dev, point_index, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, 1, s));
@@ -204,7 +230,7 @@ inline void stiffness_affine(const LevelList &ll, float *q, const float *v, cons
 // (null: 1).  q, point_index: the arrays the list's first_offset counts in; gathered_values: the length of v (the bytes it
 // adds to the count).  3-D lists of degree <= 15.
 template <typename Real>
-inline void apply_gather(const LevelList &ll, Real *q, const Real *v, const int *point_index, const double *scale_dev, int gathered_values, bool mfma_enabled, bool skip_zero_factors, bool line_stiffness)
+inline void apply_gather(const LevelList &ll, Real *q, const Real *v, const int *point_index, const double *scale_dev, int gathered_values, bool mfma_enabled, bool skip_zero_factors, bool line_stiffness, bool mfma_skip_zero_factors)
 {
     constexpr bool f32 = std::is_same<Real, float>::value;
     const bool mfma = on_matrix_cores<Real>(ll, mfma_enabled);
@@ -216,6 +242,13 @@ inline void apply_gather(const LevelList &ll, Real *q, const Real *v, const int 
         ops::stiffness_affine(ll, q, v, scale_dev, point_index, mfma, dev().stream);
         return;
     }
+    if constexpr (not f32) // the matrix-core kernels exist in double only
+        if (on_mfma_diag_kernel<Real>(ll, mfma_enabled, skip_zero_factors, mfma_skip_zero_factors))
+        {
+            ProfileScope prof("mfma_diag_stiffness_kernel<gather>", 36.0 * points + gathered);
+            ops::stiffness_mfma_diag(ll, q, v, scale_dev, point_index, dev().stream);
+            return;
+        }
     if (on_line_kernel<Real>(ll, mfma_enabled, skip_zero_factors, line_stiffness))
     {
         ProfileScope prof(f32 ? "line_stiffness_kernel<gather,f32>" : "line_stiffness_kernel<gather>", (f32 ? 20.0 : 36.0) * points + gathered); // the bytes of the instance it replaces

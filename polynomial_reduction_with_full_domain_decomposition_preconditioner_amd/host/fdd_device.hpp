@@ -60,6 +60,9 @@
 #pragma weak fdd_stiffness_matrix_diag
 #pragma weak fdd_stiffness_matrix_diag_f32
 #pragma weak fdd_stiffness_offdiag_zero
+// and its matrix-core instance (degree 11..15): without it those lists keep the six-array matrix-core kernel, and the flag
+// "mfma_skip_zero_factors" refuses to be set to 1 (missing_mfma_zero_factor_entry, element_operator.hpp)
+#pragma weak fdd_stiffness_matrix_mfma_diag
 // and the line form of the stiffness kernel at degree 7: without it those lists stay on the slab form, and the flag
 // "line_stiffness" refuses to be set to 1, naming the missing entry (missing_line_stiffness_entry, element_operator.hpp)
 #pragma weak fdd_stiffness_matrix_lines

@@ -963,6 +963,25 @@ int fddh_problem_zero_factor_info(fddh_problem *p, int *enabled, int *fine_domai
     }
 }
 
+int fddh_problem_mfma_zero_factor_info(fddh_problem *p, int *enabled, int *fine_domain_mfma_diag, int *sub_lists_mfma_diag, int *sub_lists)
+{
+    try
+    {
+        if (int rc = rank_check(p)) return rc;
+        if (!p) return fail("null argument");
+        Domain<SType> &dom = p->fine();
+        if (enabled) *enabled = dom.mfma_skip_zero_factors ? 1 : 0;
+        if (fine_domain_mfma_diag) *fine_domain_mfma_diag = dom.runs_mfma_diag_kernel() ? 1 : 0;
+        if (sub_lists_mfma_diag) *sub_lists_mfma_diag = p->subdomain ? p->subdomain->lists_on_mfma_diag_kernel() : 0;
+        if (sub_lists) *sub_lists = p->subdomain ? (int)p->subdomain->operator_lists().size() : 0;
+        return 0;
+    }
+    catch (const std::exception &e)
+    {
+        return fail("%s", e.what());
+    }
+}
+
 int fddh_problem_line_stiffness_info(fddh_problem *p, int *enabled, int *fine_domain_lines, int *sub_lists_lines, int *sub_lists)
 {
     try
@@ -1086,6 +1105,16 @@ int fddh_problem_set_flag(fddh_problem *p, const char *name, int value)
                 if (const char *missing = fdd::missing_zero_factor_entry()) return fail("skip_zero_factors needs %s, which the loaded kernel library does not export", missing);
             for (auto &kv : p->domains) kv.second.skip_zero_factors = value != 0;
             if (p->subdomain) p->subdomain->skip_zero_factors = value != 0;
+        }
+        else if (s == "mfma_skip_zero_factors")
+        {
+            // the same for lists on the matrix cores (degree 11..15): their three-array instance, while "skip_zero_factors"
+            // and "mfma_stiffness" are both on (default where the kernel library has it); 0: those lists stream six arrays.
+            // The values are the six-array matrix-core kernel's, to the sign of a zero, so nothing is emptied here either.
+            if (value != 0)
+                if (const char *missing = fdd::missing_mfma_zero_factor_entry()) return fail("mfma_skip_zero_factors needs %s, which the loaded kernel library does not export", missing);
+            for (auto &kv : p->domains) kv.second.mfma_skip_zero_factors = value != 0;
+            if (p->subdomain) p->subdomain->mfma_skip_zero_factors = value != 0;
         }
         else if (s == "line_stiffness")
         {

@@ -927,7 +927,7 @@ class Subdomain
     template <typename Real>
     void stiffness_from_dofs(Real *q, const Real *za, const double *scale_dev = nullptr)
     {
-        for (auto &ll : subdomain_operator.level_lists) fdd::apply_gather(ll, q, za, point_dof_dev.template as<int>(), scale_dev, subdomain_operator.num_extended_dofs, mfma_stiffness, skip_zero_factors, line_stiffness);
+        for (auto &ll : subdomain_operator.level_lists) fdd::apply_gather(ll, q, za, point_dof_dev.template as<int>(), scale_dev, subdomain_operator.num_extended_dofs, mfma_stiffness, skip_zero_factors, line_stiffness, mfma_skip_zero_factors);
     }
 
     // y (dofs) = [Qt A_L Q | A_sup] (s x~): the operator of the inner iteration on a dof vector.  x~ is one of the
@@ -1404,6 +1404,7 @@ class Subdomain
     bool mfma_stiffness = true;           // N >= 11 element lists on the fp64 matrix cores
     bool line_stiffness = fdd::missing_line_stiffness_entry() == nullptr;  // degree-7 lists on the three-array kernel run its line form (element_operator.hpp)
     bool skip_zero_factors = fdd::missing_zero_factor_entry() == nullptr; // lists whose off-diagonal factor arrays are identically zero do not stream them (element_operator.hpp)
+    bool mfma_skip_zero_factors = fdd::missing_mfma_zero_factor_entry() == nullptr; // nor where they run on the matrix cores, while skip_zero_factors and mfma_stiffness are on
     std::vector<DType> residual_history;  // inner history of the last application
 
     int num_values = 0;
@@ -1904,7 +1905,7 @@ class Subdomain
 
         superdomain_operator.A.multiply(Au_sup, u_sup); // empty: no-op
 
-        for (auto &ll : subdomain_operator.level_lists) fdd::apply_local(ll, Au_sub_l.as<double>(), u_sub_l.as<double>(), work_dev, mfma_stiffness, skip_zero_factors, line_stiffness);
+        for (auto &ll : subdomain_operator.level_lists) fdd::apply_local(ll, Au_sub_l.as<double>(), u_sub_l.as<double>(), work_dev, mfma_stiffness, skip_zero_factors, line_stiffness, mfma_skip_zero_factors);
     }
 
     // subdomain.tpp:4161-4268
@@ -2140,6 +2141,15 @@ class Subdomain
         int count = 0;
         for (auto &ll : subdomain_operator.level_lists)
             if (precision == 32 ? fdd::on_diag_kernel<float>(ll, mfma_stiffness, skip_zero_factors) : fdd::on_diag_kernel<double>(ll, mfma_stiffness, skip_zero_factors)) count++;
+        return count;
+    }
+    // how many run the matrix-core kernel on three factor arrays (flag "mfma_skip_zero_factors"): none in a float inner solve,
+    // which has no matrix-core kernel
+    int lists_on_mfma_diag_kernel() const
+    {
+        int count = 0;
+        for (auto &ll : subdomain_operator.level_lists)
+            if (precision == 32 ? fdd::on_mfma_diag_kernel<float>(ll, mfma_stiffness, skip_zero_factors, mfma_skip_zero_factors) : fdd::on_mfma_diag_kernel<double>(ll, mfma_stiffness, skip_zero_factors, mfma_skip_zero_factors)) count++;
         return count;
     }
     // and how many the line form of it (flag "line_stiffness")

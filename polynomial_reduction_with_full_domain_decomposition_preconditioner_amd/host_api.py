@@ -416,6 +416,14 @@ class Problem:
         _H().call("fddh_problem_zero_factor_info", self.h, ctypes.byref(on), ctypes.byref(dom), ctypes.byref(diag), ctypes.byref(lists))
         return {"enabled": bool(on.value), "fine_domain": bool(dom.value), "sub_lists_diag": diag.value, "sub_lists": lists.value}
 
+    def mfma_zero_factor_info(self):
+        """flag "mfma_skip_zero_factors": is it on, does the fine domain's list run the matrix-core kernel that streams three
+        factor arrays (degree 11..15, off-diagonal arrays zero at every point), and how many of the subdomain's lists do, of
+        how many"""
+        on, dom, diag, lists = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        _H().call("fddh_problem_mfma_zero_factor_info", self.h, ctypes.byref(on), ctypes.byref(dom), ctypes.byref(diag), ctypes.byref(lists))
+        return {"enabled": bool(on.value), "fine_domain": bool(dom.value), "sub_lists_mfma_diag": diag.value, "sub_lists": lists.value}
+
     def line_stiffness_info(self):
         """flag "line_stiffness": is it on, does the fine domain's list run the line form of the three-array stiffness
         kernel (degree 7), and how many of the subdomain's lists do, of how many"""
