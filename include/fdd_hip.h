@@ -403,6 +403,24 @@ int fdd_stiffness_matrix_lines_f32(float *Au, const float *v, const double *v_sc
  * memory) [f] = 0 exactly when every value of G[3 + f] there compares == 0.0 (-0.0 does; a denormal or a NaN does not),
  * 1 otherwise. */
 int fdd_stiffness_offdiag_zero(int *flags_out, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream);
+/* The line form where factor blocks repeat from element to element (a uniform box: every element's (N+1)^3 values of each
+ * array are bit for bit those of element 0): the argument list of fdd_stiffness_matrix_lines plus factor_elem, num_elements
+ * ints in device memory, each in 0..num_elements-1.  Element e reads its three factor lines from the block of element
+ * factor_elem[e] of the same arrays (at elem_offset[factor_elem[e]], or factor_elem[e] (N+1)^3 where elem_offset is NULL), with
+ * plain loads, so that the few blocks named stay in cache: 12 B per point + the gathered values instead of 36 (8 instead of
+ * 20 in float; 16 instead of 40 in the local form).  v, point_dof and Au keep the element's own offset.  Where the block
+ * named holds the element's own words -- fdd_stiffness_factor_block_verify says whether it does -- every output bit is that
+ * of fdd_stiffness_matrix_lines[_f32].  poly_degree 7 and diag = 1 only: FDD_ERR_UNSUPPORTED otherwise, output untouched. */
+int fdd_stiffness_matrix_lines_shared(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream);
+int fdd_stiffness_matrix_lines_shared_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream);
+/* Which blocks repeat?  out[e] (num_elements 64-bit words in device memory) = a hash of the bit patterns of element e's block
+ * of G[0], G[1], G[2] that depends on the position of every word: equal blocks give equal hashes, and two blocks that differ
+ * in a single word give different ones.  3-D elements, poly_degree 1..15. */
+int fdd_stiffness_factor_block_hash(unsigned long long *out, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream);
+/* *mismatches (one int in device memory, cleared by the entry) = the number of elements e whose block differs from the block
+ * of element factor_elem[e] in any bit of any of the three arrays (-0.0 differs from 0.0, NaN payloads count), or whose
+ * factor_elem[e] lies outside 0..num_elements-1.  0: the map is safe to hand to fdd_stiffness_matrix_lines_shared[_f32]. */
+int fdd_stiffness_factor_block_verify(int *mismatches, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, void *stream);
 int fdd_stiffness_matrix_affine_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *elem_factors, const float *gll_weights, const int *elem_offset, int num_elements, int poly_degree, void *stream);
 int fdd_sub_stiffness_matrix_gather_scaled_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream);
 int fdd_multi_inner_product_scaled_f32(double *out, double *ws, const float *a, const float *const *b, const double *b_scale_dev, int m, int n, void *stream); /* out[k] = sum a * (s_k b_k), k < m <= 8 */

@@ -260,6 +260,19 @@ int fddh_problem_mfma_zero_factor_info(fddh_problem *p, int *enabled, int *fine_
  * The info entry: is the flag on, does the fine Domain's list run the line form, how many of the Subdomain's level lists do
  * (in the precision in use), of how many.  Any argument may be NULL. */
 int fddh_problem_line_stiffness_info(fddh_problem *p, int *enabled, int *fine_domain_lines, int *sub_lists_lines, int *sub_lists);
+/* Flag "shared_factor_blocks" (default 1 where the kernel library exports fdd_stiffness_matrix_lines_shared, _lines_shared_f32,
+ * fdd_stiffness_factor_block_hash and _factor_block_verify; setting it to 1 on a library without them is refused, naming the
+ * missing entry): a list that runs the line form (see "line_stiffness") and whose elements hold, bit for bit, the G[0..2] blocks
+ * of a few of them -- a uniform box, a piecewise-uniform grid; established once from the list's own arrays on the device, by
+ * hash and then by comparison of every bit; at most 1 MiB of distinct blocks and at most half as many as elements -- reads
+ * those few blocks instead of streaming every element's copy, in both precisions, in the local and the gather form.  The
+ * words read are the mesh's own, so histories and iterates do not change with the flag.  It takes effect only where the line
+ * form runs: "line_stiffness" = 0, "skip_zero_factors" = 0, "affine_geometry" = 1, six-array lists and other degrees keep
+ * their meaning.  A deformed mesh shares nothing and keeps the streamed instance.  0: every element streams its own block.
+ * The info entry: is the flag on, does the fine Domain's list run the shared instance, how many distinct blocks its check
+ * found (0: not looked for), how many of the Subdomain's level lists run it (in the precision in use), of how many.  Any
+ * argument may be NULL. */
+int fddh_problem_shared_factor_info(fddh_problem *p, int *enabled, int *fine_domain_shared, int *fine_domain_classes, int *sub_lists_shared, int *sub_lists);
 int fddh_problem_set_flag(fddh_problem *p, const char *name, int value);
 
 /* Low-order AMG preconditioner of the inner solve (Subdomain::low_order_preconditioner,

@@ -665,8 +665,14 @@ __device__ __forceinline__ void line_au(T (&au)[8], const T (&gdu)[8], const T *
     }
 }
 
-template <typename T, bool kGather, bool kNTStore>
-__global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restrict__ Au, const T *__restrict__ u, const int *__restrict__ point_dof, const double *__restrict__ u_scale, const T *__restrict__ D_hat, GPtrsT<T> G, const int *__restrict__ elem_offset, int num_elements)
+// kShared: element e reads its three factor lines from the block of element factor_elem[e] of the same arrays (the host
+// layer establishes, from the list's own arrays, which elements hold bit for bit the block of an earlier one:
+// fdd_stiffness_factor_block_hash / _verify).  The lookup is wave-uniform, so the factor base stays in scalar registers
+// like the element's own; the factor loads are plain loads, since the few distinct blocks are meant to stay in cache
+// (a nontemporal load goes past L1).  u, point_dof and Au keep the element's own base, and nothing else differs: the same
+// words reach the same arithmetic.  factor_elem is not read by the streamed instances.
+template <typename T, bool kGather, bool kNTStore, bool kShared = false>
+__global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restrict__ Au, const T *__restrict__ u, const int *__restrict__ point_dof, const double *__restrict__ u_scale, const T *__restrict__ D_hat, GPtrsT<T> G, const int *__restrict__ elem_offset, int num_elements, const int *__restrict__ factor_elem)
 {
     using C = LineCfg;
     constexpr int n = C::n, nn = C::nn;
@@ -680,6 +686,12 @@ __global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restri
     const int elem = blockIdx.x * C::epb + e_loc;
     if (elem >= num_elements) return; // wave-uniform; nothing below waits for another wave
     const size_t base = elem_offset ? (size_t)elem_offset[elem] : (size_t)elem * C::n3;
+    size_t fbase = base; // where the element's factor block is read
+    if (kShared)
+    {
+        const int rep = factor_elem[elem];
+        fbase = elem_offset ? (size_t)elem_offset[rep] : (size_t)rep * C::n3;
+    }
     T *ta = s_a[e_loc], *tb = s_b[e_loc];
 
     // k-column role: u as in the slab form
@@ -716,16 +728,16 @@ __global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restri
         // the three factor lines of this lane, all requested before anything waits
         T g0[n], g1[n], g2[n];
 #pragma unroll
-        for (int k = 0; k < n; k++) g2[k] = __builtin_nontemporal_load(G.g[2] + base + (l + k * nn)); // (i, j) = (a, b), k
+        for (int k = 0; k < n; k++) g2[k] = kShared ? G.g[2][fbase + (l + k * nn)] : __builtin_nontemporal_load(G.g[2] + fbase + (l + k * nn)); // (i, j) = (a, b), k
         {
-            const T *g0p = G.g[0] + base + 8 * l; // (j, k) = (a, b): the row starts at 8 a + 64 b
+            const T *g0p = G.g[0] + fbase + 8 * l; // (j, k) = (a, b): the row starts at 8 a + 64 b
 #pragma unroll
             for (int p = 0; p < n; p++) g0[p] = g0p[p];
         }
         {
-            const T *g1p = G.g[1] + base + (a + nn * b); // (i, k) = (a, b): the column steps by 8
+            const T *g1p = G.g[1] + fbase + (a + nn * b); // (i, k) = (a, b): the column steps by 8
 #pragma unroll
-            for (int p = 0; p < n; p++) g1[p] = __builtin_nontemporal_load(g1p + 8 * p);
+            for (int p = 0; p < n; p++) g1[p] = kShared ? g1p[8 * p] : __builtin_nontemporal_load(g1p + 8 * p);
         }
 
 #pragma unroll
@@ -781,27 +793,29 @@ __global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restri
     }
 }
 
-template <typename T>
-int launch_lines_t(T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const GPtrsT<T> &G, const int *elem_offset, int num_elements, void *stream)
+template <typename T, bool kShared>
+int launch_lines_t(T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const GPtrsT<T> &G, const int *elem_offset, const int *factor_elem, int num_elements, void *stream)
 {
     const int grid = (num_elements + LineCfg::epb - 1) / LineCfg::epb;
     static const bool nt_store = fdd_env_int("FDD_TUNE_STIFFNESS_NT_STORE", 1) != 0;
     if (point_dof and nt_store)
-        hipLaunchKernelGGL((line_stiffness_kernel_t<T, true, true>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements);
+        hipLaunchKernelGGL((line_stiffness_kernel_t<T, true, true, kShared>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem);
     else if (point_dof)
-        hipLaunchKernelGGL((line_stiffness_kernel_t<T, true, false>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements);
+        hipLaunchKernelGGL((line_stiffness_kernel_t<T, true, false, kShared>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem);
     else if (nt_store)
-        hipLaunchKernelGGL((line_stiffness_kernel_t<T, false, true>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements);
+        hipLaunchKernelGGL((line_stiffness_kernel_t<T, false, true, kShared>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem);
     else
-        hipLaunchKernelGGL((line_stiffness_kernel_t<T, false, false>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements);
+        hipLaunchKernelGGL((line_stiffness_kernel_t<T, false, false, kShared>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem);
     FDD_LAUNCH_CHECK();
     return 0;
 }
 
 // diag = 1: three factor arrays, G[3..5] are not passed on (never dereferenced).  diag = 0: six arrays -- that form was built
 // and timed (see above), was not ahead of the slab form and is not compiled in: FDD_ERR_UNSUPPORTED
+// shared (fdd_stiffness_matrix_lines_shared[_f32]): factor_elem names the element whose factor block each element reads;
+// three arrays only
 template <typename T>
-int lines_dispatch(T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const T *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, int diag, void *stream)
+int lines_dispatch(T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const T *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, bool shared, int num_elements, int poly_degree, int diag, void *stream)
 {
     FDD_REQUIRE(num_elements >= 0 && (diag == 0 || diag == 1));
     if (poly_degree != 7)
@@ -816,6 +830,7 @@ int lines_dispatch(T *Au, const T *u, const int *point_dof, const double *u_scal
     }
     if (num_elements == 0) return 0;
     FDD_REQUIRE(Au != nullptr && u != nullptr && D_hat != nullptr && G != nullptr);
+    FDD_REQUIRE(not shared || factor_elem != nullptr);
     GPtrsT<T> g;
     for (int k = 0; k < FDD_NUM_GEOM_FACTS; k++) g.g[k] = nullptr;
     for (int k = 0; k < 3; k++)
@@ -823,7 +838,71 @@ int lines_dispatch(T *Au, const T *u, const int *point_dof, const double *u_scal
         FDD_REQUIRE(G[k] != nullptr);
         g.g[k] = G[k];
     }
-    return launch_lines_t<T>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
+    if (shared) return launch_lines_t<T, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, factor_elem, num_elements, stream);
+    return launch_lines_t<T, false>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, nullptr, num_elements, stream);
+}
+
+// ---- factor blocks that repeat from element to element (the kShared line instance) ----
+// One 64-bit hash per element over the bit patterns of its G[0..2] block.  Every word is mixed with its position in the
+// block (array and point) through a bijection of 64-bit words and the results are added mod 2^64: two blocks that differ
+// in one word differ in exactly one term and so in the hash, for certain; blocks that differ in more may collide, which
+// is why fdd_stiffness_factor_block_verify has the last word.  The sum does not depend on the order of its terms.
+__device__ __forceinline__ unsigned long long factor_word_mix(unsigned long long bits, unsigned long long position)
+{
+    unsigned long long z = bits + (position + 1ull) * 0x9e3779b97f4a7c15ull;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
+__global__ __launch_bounds__(kBlock) void factor_block_hash_kernel(unsigned long long *__restrict__ out, GPtrs G, const int *__restrict__ elem_offset, int n3, int num_elements)
+{
+    __shared__ unsigned long long s_h[kBlock];
+    for (int e = blockIdx.x; e < num_elements; e += gridDim.x) // block-uniform
+    {
+        const size_t base = elem_offset ? (size_t)elem_offset[e] : (size_t)e * n3;
+        unsigned long long h = 0;
+        for (int idx = threadIdx.x; idx < 3 * n3; idx += kBlock)
+        {
+            const int f = idx / n3;
+            h += factor_word_mix((unsigned long long)__double_as_longlong(G.g[f][base + (idx - f * n3)]), (unsigned long long)idx);
+        }
+        s_h[threadIdx.x] = h;
+        __syncthreads();
+        for (int w = kBlock / 2; w > 0; w >>= 1)
+        {
+            if ((int)threadIdx.x < w) s_h[threadIdx.x] += s_h[threadIdx.x + w];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) out[e] = s_h[0];
+        __syncthreads();
+    }
+}
+
+// *mismatches += the number of elements whose block differs from the block of element factor_elem[e] in any bit of any of
+// the three arrays (bits, not values: -0.0 is not 0.0, and NaN payloads count), or whose factor_elem[e] names no element.
+// The entry clears mismatches before the launch.
+__global__ __launch_bounds__(kBlock) void factor_block_verify_kernel(int *__restrict__ mismatches, GPtrs G, const int *__restrict__ elem_offset, const int *__restrict__ factor_elem, int n3, int num_elements)
+{
+    for (int e = blockIdx.x; e < num_elements; e += gridDim.x) // block-uniform
+    {
+        const int rep = factor_elem[e];
+        int differs = 0;
+        if (rep < 0 or rep >= num_elements)
+            differs = 1;
+        else if (rep != e)
+        {
+            const size_t base = elem_offset ? (size_t)elem_offset[e] : (size_t)e * n3;
+            const size_t rbase = elem_offset ? (size_t)elem_offset[rep] : (size_t)rep * n3;
+            for (int idx = threadIdx.x; idx < 3 * n3; idx += kBlock)
+            {
+                const int f = idx / n3;
+                const int at = idx - f * n3;
+                differs |= __double_as_longlong(G.g[f][base + at]) != __double_as_longlong(G.g[f][rbase + at]);
+            }
+        }
+        if (__syncthreads_or(differs) and threadIdx.x == 0) atomicAdd(mismatches, 1);
+    }
 }
 
 // flags[f] = 1 where array 3 + f of the list holds a value that is not a zero: any bit besides the sign set, so -0.0 passes
@@ -1283,12 +1362,75 @@ int fdd_stiffness_matrix_diag_f32(float *Au, const float *v, const double *v_sca
 
 int fdd_stiffness_matrix_lines(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, int diag, void *stream)
 {
-    return lines_dispatch<double>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, num_elements, poly_degree, diag, stream);
+    return lines_dispatch<double>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, nullptr, false, num_elements, poly_degree, diag, stream);
 }
 
 int fdd_stiffness_matrix_lines_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, int diag, void *stream)
 {
-    return lines_dispatch<float>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, num_elements, poly_degree, diag, stream);
+    return lines_dispatch<float>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, nullptr, false, num_elements, poly_degree, diag, stream);
+}
+
+static int lines_shared_diag_only(int diag)
+{
+    if (diag == 1) return 0;
+    fdd_set_error("the shared-block line form of the stiffness kernel exists on three factor arrays only (diag = 1), got diag = %d", diag);
+    return FDD_ERR_UNSUPPORTED;
+}
+
+int fdd_stiffness_matrix_lines_shared(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream)
+{
+    if (int rc = lines_shared_diag_only(diag)) return rc;
+    return lines_dispatch<double>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, factor_elem, true, num_elements, poly_degree, diag, stream);
+}
+
+int fdd_stiffness_matrix_lines_shared_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream)
+{
+    if (int rc = lines_shared_diag_only(diag)) return rc;
+    return lines_dispatch<float>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, factor_elem, true, num_elements, poly_degree, diag, stream);
+}
+
+constexpr int kFactorBlockGrid = 1 << 20; // workgroups; beyond it a workgroup takes several elements in turn
+static int factor_block_args(GPtrs &g, const double *const G[FDD_NUM_GEOM_FACTS], int num_elements, int poly_degree)
+{
+    FDD_REQUIRE(num_elements >= 0 && poly_degree >= 1 && G != nullptr);
+    if (poly_degree > 15)
+    {
+        fdd_set_error("the factor-block entries support poly_degree 1..15, got %d", poly_degree);
+        return FDD_ERR_UNSUPPORTED;
+    }
+    for (int k = 0; k < FDD_NUM_GEOM_FACTS; k++) g.g[k] = nullptr;
+    for (int k = 0; k < 3; k++)
+    {
+        FDD_REQUIRE(G[k] != nullptr);
+        g.g[k] = G[k];
+    }
+    return 0;
+}
+
+int fdd_stiffness_factor_block_hash(unsigned long long *out, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
+{
+    GPtrs g;
+    if (int rc = factor_block_args(g, G, num_elements, poly_degree)) return rc;
+    if (num_elements == 0) return 0;
+    FDD_REQUIRE(out != nullptr);
+    const int n = poly_degree + 1;
+    hipLaunchKernelGGL(factor_block_hash_kernel, dim3(num_elements < kFactorBlockGrid ? num_elements : kFactorBlockGrid), dim3(kBlock), 0, fdd_stream(stream), out, g, elem_offset, n * n * n, num_elements);
+    FDD_LAUNCH_CHECK();
+    return 0;
+}
+
+int fdd_stiffness_factor_block_verify(int *mismatches, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, void *stream)
+{
+    GPtrs g;
+    if (int rc = factor_block_args(g, G, num_elements, poly_degree)) return rc;
+    FDD_REQUIRE(mismatches != nullptr);
+    FDD_HIP_CHECK(hipMemsetAsync(mismatches, 0, sizeof(int), fdd_stream(stream)));
+    if (num_elements == 0) return 0;
+    FDD_REQUIRE(factor_elem != nullptr);
+    const int n = poly_degree + 1;
+    hipLaunchKernelGGL(factor_block_verify_kernel, dim3(num_elements < kFactorBlockGrid ? num_elements : kFactorBlockGrid), dim3(kBlock), 0, fdd_stream(stream), mismatches, g, elem_offset, factor_elem, n * n * n, num_elements);
+    FDD_LAUNCH_CHECK();
+    return 0;
 }
 
 int fdd_stiffness_offdiag_zero(int *flags_out, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)

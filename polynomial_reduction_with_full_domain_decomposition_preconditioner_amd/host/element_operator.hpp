@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <type_traits>
+#include <unordered_map>
 #include <vector>
 
 #include "config.hpp"
@@ -47,6 +48,12 @@ struct LevelList
     // are the three off-diagonal factor arrays G[3..5] zero at every point of the list (detect_zero_factors, once, when the
     // factor pointers are set)?  Then the kernel that does not stream them applies; G32 are casts of the same arrays
     bool offdiag_zero = false;
+    // do the list's elements share their G[0..2] blocks with a few representatives, bit for bit (detect_shared_blocks, once,
+    // after the check above)?  factor_elem[e]: the lowest element of the list that holds element e's block; G32 are casts
+    // of the same arrays, so equal double blocks are equal float blocks and the one map serves both precisions
+    bool shared_blocks = false;
+    int factor_classes = 0; // distinct blocks found (0: not looked for)
+    memory factor_elem;     // device ints, allocated only where shared_blocks holds
 
     size_t num_points() const { return (size_t)num_elements * (poly_degree + 1) * (poly_degree + 1) * (dim == 3 ? poly_degree + 1 : 1); }
 };
@@ -129,9 +136,73 @@ inline bool on_line_kernel(const LevelList &ll, bool mfma_enabled, bool skip_zer
     return line_stiffness and ll.dim == 3 and ll.poly_degree == 7 and on_diag_kernel<Real>(ll, mfma_enabled, skip_zero_factors) and missing_line_stiffness_entry() == nullptr;
 }
 
+// ---- factor blocks that repeat from element to element (flag "shared_factor_blocks") ----
+// the first entry of the shared-block line instance and its detection the loaded kernel library does not export, or nullptr
+inline const char *missing_shared_factor_entry()
+{
+    if (&fdd_stiffness_matrix_lines_shared == nullptr) return "fdd_stiffness_matrix_lines_shared";
+    if (&fdd_stiffness_matrix_lines_shared_f32 == nullptr) return "fdd_stiffness_matrix_lines_shared_f32";
+    if (&fdd_stiffness_factor_block_hash == nullptr) return "fdd_stiffness_factor_block_hash";
+    if (&fdd_stiffness_factor_block_verify == nullptr) return "fdd_stiffness_factor_block_verify";
+    return nullptr;
+}
+
+// The distinct blocks of a shared list occupy at most this many bytes (85 of them at degree 7): a quarter of the 4 MiB of
+// L2 of one XCD, so that they stay there beside the streamed vectors.  A design bound from the cache size, not a tuned value.
+constexpr size_t shared_factor_bytes_limit = (size_t)1 << 20;
+
+// On a mesh whose elements are translated copies of a few shapes (a uniform box, a piecewise-uniform grid) every element's
+// block of G[0..2] is bit for bit the block of one of a few elements, and the line kernel's shared instance reads that one
+// instead of streaming the copies.  Established from the list's OWN arrays, once, like detect_zero_factors (the factor arrays
+// are written at initialisation and never in place afterwards): a hash per element on the device, equal hashes grouped on
+// the host with the lowest element as representative, then every element compared with its representative bit by bit on
+// the device -- a hash collision makes the list not shared, it never reaches the operator.  Shared: verified, the distinct
+// blocks within shared_factor_bytes_limit, and at most half as many of them as elements (the factor stream at least halves).
+// Only lists with offdiag_zero are looked at; a deformed mesh pays one pass over three arrays and stays as it is.
+inline void detect_shared_blocks(LevelList &ll)
+{
+    ll.shared_blocks = false;
+    ll.factor_classes = 0;
+    ll.factor_elem.free();
+    if (not ll.offdiag_zero or ll.dim != 3 or ll.poly_degree > 15 or ll.num_elements == 0 or missing_shared_factor_entry()) return;
+    const size_t ne = (size_t)ll.num_elements;
+    std::vector<unsigned long long> hash(ne);
+    memory hash_dev = dev().malloc<unsigned long long>(ne);
+    FDD_CALL(fdd_stiffness_factor_block_hash(hash_dev.as<unsigned long long>(), ll.G, nullptr, ll.num_elements, ll.poly_degree, dev().stream));
+    hash_dev.copyTo(hash.data(), ne * sizeof(unsigned long long));
+    hash_dev.free();
+    std::vector<int> rep(ne);
+    std::unordered_map<unsigned long long, int> first; // elements in ascending order: the first of a group is its lowest
+    for (size_t e = 0; e < ne; e++) rep[e] = first.emplace(hash[e], (int)e).first->second;
+    ll.factor_classes = (int)first.size();
+    const size_t block_bytes = 3 * (ll.num_points() / ne) * sizeof(double);
+    if (first.size() * block_bytes > shared_factor_bytes_limit or 2 * first.size() > ne) return;
+    int mismatches = 1;
+    memory rep_dev = dev().malloc<int>(ne), mismatches_dev = dev().malloc<int>(1);
+    rep_dev.copyFrom(rep.data(), ne * sizeof(int));
+    FDD_CALL(fdd_stiffness_factor_block_verify(mismatches_dev.as<int>(), ll.G, nullptr, rep_dev.as<int>(), ll.num_elements, ll.poly_degree, dev().stream));
+    mismatches_dev.copyTo(&mismatches, sizeof(int));
+    mismatches_dev.free();
+    if (mismatches != 0)
+    {
+        rep_dev.free();
+        return;
+    }
+    ll.factor_elem = rep_dev;
+    ll.shared_blocks = true;
+}
+
+// does the list run the shared instance of the line form?  Only where it runs the line form at all, so every flag and
+// condition on_line_kernel looks at keeps its meaning and precedence.  Same bits as the streamed instance.
+template <typename Real>
+inline bool on_shared_line_kernel(const LevelList &ll, bool mfma_enabled, bool skip_zero_factors, bool line_stiffness, bool shared_factor_blocks)
+{
+    return shared_factor_blocks and ll.shared_blocks and on_line_kernel<Real>(ll, mfma_enabled, skip_zero_factors, line_stiffness) and missing_shared_factor_entry() == nullptr;
+}
+
 // Au = A_L u on the points of the list (Au, u: the vectors the list's first_offset counts in).  workspace: three vectors
 // of the list's points for the two-launch form above degree 15.
-inline void apply_local(const LevelList &ll, double *Au, const double *u, const std::vector<memory> &workspace, bool mfma_enabled, bool skip_zero_factors, bool line_stiffness, bool mfma_skip_zero_factors)
+inline void apply_local(const LevelList &ll, double *Au, const double *u, const std::vector<memory> &workspace, bool mfma_enabled, bool skip_zero_factors, bool line_stiffness, bool mfma_skip_zero_factors, bool shared_factor_blocks)
 {
     void *stream = dev().stream;
     const double points = (double)ll.num_points();
@@ -147,6 +218,11 @@ inline void apply_local(const LevelList &ll, double *Au, const double *u, const 
         // high order: the six contractions on the fp64 matrix cores (tolerance-level parity, fdd_hip.h)
         ProfileScope prof("mfma_stiffness_kernel", 64.0 * points);
         FDD_CALL(fdd_stiffness_matrix_mfma(Au, u, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, stream));
+    }
+    else if (on_shared_line_kernel<double>(ll, mfma_enabled, skip_zero_factors, line_stiffness, shared_factor_blocks))
+    {
+        ProfileScope prof("line_stiffness_kernel<shared>", 16.0 * points); // u and Au; the few factor blocks stay in cache
+        FDD_CALL(fdd_stiffness_matrix_lines_shared(Au, u, nullptr, nullptr, ll.D_hat, ll.G, nullptr, ll.factor_elem.as<int>(), ll.num_elements, ll.poly_degree, 1, stream));
     }
     else if (on_line_kernel<double>(ll, mfma_enabled, skip_zero_factors, line_stiffness))
     {
@@ -216,6 +292,16 @@ inline void stiffness_lines(const LevelList &ll, float *q, const float *v, const
     for (int g = 0; g < NUM_GEOM_FACTS; g++) G[g] = ll.G32[g].as<float>();
     FDD_CALL(fdd_stiffness_matrix_lines_f32(q, v, scale_dev, point_index, ll.D_hat32.as<float>(), G, nullptr, ll.num_elements, ll.poly_degree, 1, s));
 }
+inline void stiffness_lines_shared(const LevelList &ll, double *q, const double *v, const double *scale_dev, const int *point_index, void *s)
+{
+    FDD_CALL(fdd_stiffness_matrix_lines_shared(q, v, scale_dev, point_index, ll.D_hat, ll.G, nullptr, ll.factor_elem.as<int>(), ll.num_elements, ll.poly_degree, 1, s));
+}
+inline void stiffness_lines_shared(const LevelList &ll, float *q, const float *v, const double *scale_dev, const int *point_index, void *s)
+{
+    const float *G[NUM_GEOM_FACTS];
+    for (int g = 0; g < NUM_GEOM_FACTS; g++) G[g] = ll.G32[g].as<float>();
+    FDD_CALL(fdd_stiffness_matrix_lines_shared_f32(q, v, scale_dev, point_index, ll.D_hat32.as<float>(), G, nullptr, ll.factor_elem.as<int>(), ll.num_elements, ll.poly_degree, 1, s));
+}
 inline void stiffness_affine(const LevelList &ll, double *q, const double *v, const double *scale_dev, const int *point_index, bool mfma, void *s)
 {
     FDD_CALL((mfma ? fdd_stiffness_matrix_mfma_affine : fdd_stiffness_matrix_affine)(q, v, scale_dev, point_index, ll.D_hat, ll.affine_c.as<double>(), ll.affine_w.as<double>(), nullptr, ll.num_elements, ll.poly_degree, s));
@@ -230,7 +316,7 @@ inline void stiffness_affine(const LevelList &ll, float *q, const float *v, cons
 // (null: 1).  q, point_index: the arrays the list's first_offset counts in; gathered_values: the length of v (the bytes it
 // adds to the count).  3-D lists of degree <= 15.
 template <typename Real>
-inline void apply_gather(const LevelList &ll, Real *q, const Real *v, const int *point_index, const double *scale_dev, int gathered_values, bool mfma_enabled, bool skip_zero_factors, bool line_stiffness, bool mfma_skip_zero_factors)
+inline void apply_gather(const LevelList &ll, Real *q, const Real *v, const int *point_index, const double *scale_dev, int gathered_values, bool mfma_enabled, bool skip_zero_factors, bool line_stiffness, bool mfma_skip_zero_factors, bool shared_factor_blocks)
 {
     constexpr bool f32 = std::is_same<Real, float>::value;
     const bool mfma = on_matrix_cores<Real>(ll, mfma_enabled);
@@ -249,6 +335,12 @@ inline void apply_gather(const LevelList &ll, Real *q, const Real *v, const int 
             ops::stiffness_mfma_diag(ll, q, v, scale_dev, point_index, dev().stream);
             return;
         }
+    if (on_shared_line_kernel<Real>(ll, mfma_enabled, skip_zero_factors, line_stiffness, shared_factor_blocks))
+    {
+        ProfileScope prof(f32 ? "line_stiffness_kernel<gather,shared,f32>" : "line_stiffness_kernel<gather,shared>", (f32 ? 8.0 : 12.0) * points + gathered); // index and q; the few factor blocks stay in cache
+        ops::stiffness_lines_shared(ll, q, v, scale_dev, point_index, dev().stream);
+        return;
+    }
     if (on_line_kernel<Real>(ll, mfma_enabled, skip_zero_factors, line_stiffness))
     {
         ProfileScope prof(f32 ? "line_stiffness_kernel<gather,f32>" : "line_stiffness_kernel<gather>", (f32 ? 20.0 : 36.0) * points + gathered); // the bytes of the instance it replaces

@@ -67,6 +67,13 @@
 // "line_stiffness" refuses to be set to 1, naming the missing entry (missing_line_stiffness_entry, element_operator.hpp)
 #pragma weak fdd_stiffness_matrix_lines
 #pragma weak fdd_stiffness_matrix_lines_f32
+// and its instance for factor blocks that repeat from element to element, with the two entries that establish which do:
+// without them every list streams its own blocks, and the flag "shared_factor_blocks" refuses to be set to 1, naming the
+// missing entry (missing_shared_factor_entry, element_operator.hpp)
+#pragma weak fdd_stiffness_matrix_lines_shared
+#pragma weak fdd_stiffness_matrix_lines_shared_f32
+#pragma weak fdd_stiffness_factor_block_hash
+#pragma weak fdd_stiffness_factor_block_verify
 
 namespace fdd
 {

@@ -1001,6 +1001,26 @@ int fddh_problem_line_stiffness_info(fddh_problem *p, int *enabled, int *fine_do
     }
 }
 
+int fddh_problem_shared_factor_info(fddh_problem *p, int *enabled, int *fine_domain_shared, int *fine_domain_classes, int *sub_lists_shared, int *sub_lists)
+{
+    try
+    {
+        if (int rc = rank_check(p)) return rc;
+        if (!p) return fail("null argument");
+        Domain<SType> &dom = p->fine();
+        if (enabled) *enabled = dom.shared_factor_blocks ? 1 : 0;
+        if (fine_domain_shared) *fine_domain_shared = dom.runs_shared_line_kernel() ? 1 : 0;
+        if (fine_domain_classes) *fine_domain_classes = dom.operator_list().factor_classes;
+        if (sub_lists_shared) *sub_lists_shared = p->subdomain ? p->subdomain->lists_on_shared_line_kernel() : 0;
+        if (sub_lists) *sub_lists = p->subdomain ? (int)p->subdomain->operator_lists().size() : 0;
+        return 0;
+    }
+    catch (const std::exception &e)
+    {
+        return fail("%s", e.what());
+    }
+}
+
 int fddh_problem_set_flag(fddh_problem *p, const char *name, int value)
 {
     try
@@ -1124,6 +1144,16 @@ int fddh_problem_set_flag(fddh_problem *p, const char *name, int value)
                 if (const char *missing = fdd::missing_line_stiffness_entry()) return fail("line_stiffness needs %s, which the loaded kernel library does not export", missing);
             for (auto &kv : p->domains) kv.second.line_stiffness = value != 0;
             if (p->subdomain) p->subdomain->line_stiffness = value != 0;
+        }
+        else if (s == "shared_factor_blocks")
+        {
+            // lists on the line form whose elements share their factor blocks bit for bit (established once, when a list's
+            // factor pointers are set) read the few distinct blocks instead of streaming every copy (default where the kernel
+            // library has the entries); 0: every element streams its own.  The words read are the same, so are all bits.
+            if (value != 0)
+                if (const char *missing = fdd::missing_shared_factor_entry()) return fail("shared_factor_blocks needs %s, which the loaded kernel library does not export", missing);
+            for (auto &kv : p->domains) kv.second.shared_factor_blocks = value != 0;
+            if (p->subdomain) p->subdomain->shared_factor_blocks = value != 0;
         }
         else if (s == "fused_projection")
         {

@@ -927,7 +927,7 @@ class Subdomain
     template <typename Real>
     void stiffness_from_dofs(Real *q, const Real *za, const double *scale_dev = nullptr)
     {
-        for (auto &ll : subdomain_operator.level_lists) fdd::apply_gather(ll, q, za, point_dof_dev.template as<int>(), scale_dev, subdomain_operator.num_extended_dofs, mfma_stiffness, skip_zero_factors, line_stiffness, mfma_skip_zero_factors);
+        for (auto &ll : subdomain_operator.level_lists) fdd::apply_gather(ll, q, za, point_dof_dev.template as<int>(), scale_dev, subdomain_operator.num_extended_dofs, mfma_stiffness, skip_zero_factors, line_stiffness, mfma_skip_zero_factors, shared_factor_blocks);
     }
 
     // y (dofs) = [Qt A_L Q | A_sup] (s x~): the operator of the inner iteration on a dof vector.  x~ is one of the
@@ -1403,6 +1403,7 @@ class Subdomain
     }
     bool mfma_stiffness = true;           // N >= 11 element lists on the fp64 matrix cores
     bool line_stiffness = fdd::missing_line_stiffness_entry() == nullptr;  // degree-7 lists on the three-array kernel run its line form (element_operator.hpp)
+    bool shared_factor_blocks = fdd::missing_shared_factor_entry() == nullptr; // lists on the line form whose factor blocks repeat from element to element read the few distinct ones (element_operator.hpp)
     bool skip_zero_factors = fdd::missing_zero_factor_entry() == nullptr; // lists whose off-diagonal factor arrays are identically zero do not stream them (element_operator.hpp)
     bool mfma_skip_zero_factors = fdd::missing_mfma_zero_factor_entry() == nullptr; // nor where they run on the matrix cores, while skip_zero_factors and mfma_stiffness are on
     std::vector<DType> residual_history;  // inner history of the last application
@@ -1603,6 +1604,7 @@ class Subdomain
             ll.first_offset = 0;
             for (int g = 0; g < NUM_GEOM_FACTS; g++) ll.G[g] = subdomain_operator.geom_fact[g].template as<double>();
             fdd::detect_zero_factors(ll);
+            fdd::detect_shared_blocks(ll);
             subdomain_operator.level_lists.push_back(ll);
         }
 
@@ -1708,6 +1710,7 @@ class Subdomain
         setup_timing.lap("region geometry to the device");
         // level-sorted element lists (subdomain.tpp:1603-1630 sorted by level): the region is ordered by level, so
         // every degree is one contiguous run of elements
+        for (auto &ll : subdomain_operator.level_lists) ll.factor_elem.free();
         subdomain_operator.level_lists.clear();
         for (int l = 0; l < num_levels; l++)
         {
@@ -1722,6 +1725,7 @@ class Subdomain
             ll.first_offset = c.sub[first].offset;
             for (int g = 0; g < NUM_GEOM_FACTS; g++) ll.G[g] = subdomain_operator.geom_fact[g].template as<double>() + ll.first_offset;
             fdd::detect_zero_factors(ll); // own elements and every ring's run, each on its own
+            fdd::detect_shared_blocks(ll);
             subdomain_operator.level_lists.push_back(ll);
         }
 
@@ -1905,7 +1909,7 @@ class Subdomain
 
         superdomain_operator.A.multiply(Au_sup, u_sup); // empty: no-op
 
-        for (auto &ll : subdomain_operator.level_lists) fdd::apply_local(ll, Au_sub_l.as<double>(), u_sub_l.as<double>(), work_dev, mfma_stiffness, skip_zero_factors, line_stiffness, mfma_skip_zero_factors);
+        for (auto &ll : subdomain_operator.level_lists) fdd::apply_local(ll, Au_sub_l.as<double>(), u_sub_l.as<double>(), work_dev, mfma_stiffness, skip_zero_factors, line_stiffness, mfma_skip_zero_factors, shared_factor_blocks);
     }
 
     // subdomain.tpp:4161-4268
@@ -2150,6 +2154,14 @@ class Subdomain
         int count = 0;
         for (auto &ll : subdomain_operator.level_lists)
             if (precision == 32 ? fdd::on_mfma_diag_kernel<float>(ll, mfma_stiffness, skip_zero_factors, mfma_skip_zero_factors) : fdd::on_mfma_diag_kernel<double>(ll, mfma_stiffness, skip_zero_factors, mfma_skip_zero_factors)) count++;
+        return count;
+    }
+    // how many on the shared instance of the line form (flag "shared_factor_blocks"), in the precision in use
+    int lists_on_shared_line_kernel() const
+    {
+        int count = 0;
+        for (auto &ll : subdomain_operator.level_lists)
+            if (precision == 32 ? fdd::on_shared_line_kernel<float>(ll, mfma_stiffness, skip_zero_factors, line_stiffness, shared_factor_blocks) : fdd::on_shared_line_kernel<double>(ll, mfma_stiffness, skip_zero_factors, line_stiffness, shared_factor_blocks)) count++;
         return count;
     }
     // and how many the line form of it (flag "line_stiffness")

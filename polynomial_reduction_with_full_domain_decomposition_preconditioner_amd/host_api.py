@@ -431,6 +431,14 @@ class Problem:
         _H().call("fddh_problem_line_stiffness_info", self.h, ctypes.byref(on), ctypes.byref(dom), ctypes.byref(lines), ctypes.byref(lists))
         return {"enabled": bool(on.value), "fine_domain": bool(dom.value), "sub_lists_lines": lines.value, "sub_lists": lists.value}
 
+    def shared_factor_info(self):
+        """flag "shared_factor_blocks": is it on, does the fine domain's list run the line kernel's shared instance (its
+        elements hold the factor blocks of a few of them, bit for bit) and how many distinct blocks were found there, and
+        how many of the subdomain's lists run it, of how many"""
+        on, dom, classes, shared, lists = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        _H().call("fddh_problem_shared_factor_info", self.h, ctypes.byref(on), ctypes.byref(dom), ctypes.byref(classes), ctypes.byref(shared), ctypes.byref(lists))
+        return {"enabled": bool(on.value), "fine_domain": bool(dom.value), "fine_domain_classes": classes.value, "sub_lists_shared": shared.value, "sub_lists": lists.value}
+
     def dssum(self, u, mask=True, weight=False):
         out = np.zeros(self.n)
         _H().call("fddh_problem_dssum", self.h, _dp(out), _dp(np.ascontiguousarray(u)), int(mask), int(weight))
