@@ -13,13 +13,15 @@ import pytest
 import torch
 
 import chebyshev_checks as C
+import support as S
+from support import Plan, boolean_gather_matrix, guarded, guards_stand, row_sums_in_column_order
 from polynomial_reduction_with_full_domain_decomposition_preconditioner_amd import host_api as H
 from polynomial_reduction_with_full_domain_decomposition_preconditioner_amd import lib
 from polynomial_reduction_with_full_domain_decomposition_preconditioner_amd.kernels import k
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 777.0
+GUARD = S.GUARD
 FUSED_LABELS = {"csr_short_pipelined_kernel<gather, ChebyStep>", "csr_short_pipelined_kernel<gather, ChebyStep, f32>"}
 STEP_LABELS = {"ew_vec2_kernel<ChebyStep>", "cheby_step_f32_kernel"}
 
@@ -81,65 +83,6 @@ def test_step_kernel_equals_its_composition(gpu, n, dtype):
             assert torch.equal(r, r0 if (last or first) else rr), case
             for whole, part in ((X, x), (D, d), (R, r)):
                 assert bool((whole[:base] == GUARD).all()) and bool((whole[base + n :] == GUARD).all()), case
-
-
-def boolean_gather_matrix(rows, seed):
-    """Qt of a gather, built here: row lengths from {0, 1, 2, 4, 8} and a few up to 27 (mean about 1.7: more than one entry
-    per row, so the plan has row blocks, fewer than four, so they are the short-row blocks of the pipelined kernel), runs of
-    empty rows -- one longer than the 1024 rows a block may hold, where there is room for it -- sorted distinct columns."""
-    rng = np.random.default_rng(seed)
-    length = rng.choice([0, 1, 2, 4, 8], size=rows, p=[0.3, 0.3, 0.25, 0.1, 0.05])
-    odd = rng.choice(rows, size=max(3, rows // 500), replace=False)
-    length[odd] = rng.integers(9, 28, len(odd))
-    for start, run in ((rows // 3, min(1100, rows // 8)), (rows // 2, 40), (rows - 7, 7)):
-        length[start : start + run] = 0
-    ptr = np.concatenate([[0], np.cumsum(length)]).astype(np.int32)
-    nnz = int(ptr[-1])
-    cols = max(256, nnz)
-    step = np.cumsum(rng.integers(1, 4, nnz))  # ascending inside every row, spans at most 3 * 27 columns
-    row_of = np.repeat(np.arange(rows), length)
-    base = rng.integers(0, cols - 3 * 27 - 1, rows)
-    col = (step - step[ptr[:-1][row_of]] + base[row_of]).astype(np.int32)
-    assert col.min() >= 0 and col.max() < cols and (np.diff(col)[np.diff(row_of) == 0] > 0).all()
-    return ptr, col, cols
-
-
-def row_sums_in_column_order(ptr, col, u):
-    """s = 0; s += u[col[j]] entry after entry, in u's own precision"""
-    s = np.zeros(len(ptr) - 1, u.dtype)
-    length = np.diff(ptr)
-    for j in range(int(length.max())):
-        on = length > j
-        s[on] = s[on] + u[col[ptr[:-1][on] + j]]
-    return s
-
-
-class Plan:
-    def __init__(self, ptr, cols, f32=False, unit=True):
-        self.h = ctypes.c_void_p()
-        self.ptr = np.ascontiguousarray(ptr, np.int32)
-        L = lib.hip()
-        L.call("fdd_csr_plan_create_f32" if f32 else "fdd_csr_plan_create", ctypes.byref(self.h), lib.ptr(self.ptr), len(ptr) - 1, cols, int(ptr[-1]))
-        if unit:
-            L.call("fdd_csr_plan_set_unit_values", self.h, 1)
-
-    def query(self, what):
-        out = ctypes.c_int(-1)
-        lib.hip().call("fdd_csr_plan_" + what, self.h, ctypes.byref(out))
-        return out.value
-
-    def close(self):
-        lib.hip().call("fdd_csr_plan_destroy", self.h)
-
-
-def guarded(values, dtype, gpu):
-    whole = torch.full((len(values) + 16,), GUARD, dtype=dtype, device=gpu)
-    whole[8 : 8 + len(values)] = torch.from_numpy(values).to(gpu)
-    return whole, whole[8 : 8 + len(values)]
-
-
-def guards_stand(whole):
-    return bool((whole[:8] == GUARD).all()) and bool((whole[-8:] == GUARD).all())
 
 
 # Row blocks of a short-row plan hold at most 1024 entries and the persistent kernel runs min(4 * 256, blocks) = 1024
