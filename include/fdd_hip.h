@@ -413,6 +413,20 @@ int fdd_stiffness_offdiag_zero(int *flags_out, const double *const G[FDD_NUM_GEO
  * of fdd_stiffness_matrix_lines[_f32].  poly_degree 7 and diag = 1 only: FDD_ERR_UNSUPPORTED otherwise, output untouched. */
 int fdd_stiffness_matrix_lines_shared(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream);
 int fdd_stiffness_matrix_lines_shared_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream);
+/* The lean instances of the line form, for a D_hat of which the CALLER guarantees, bit for bit: D_hat[i + 8 i] is +-0.0 for
+ * i = 1..6 (the interior diagonal, either sign), and D_hat[63 - m] has the bits of -D_hat[m] for every other m in 0..63 (the
+ * table of GLL nodes that mirror exactly; the entry does not check).  The argument list of fdd_stiffness_matrix_lines_shared, with factor_elem allowed
+ * to be NULL: NULL means streamed factors (every element reads its own block), otherwise the shared instance as above.  The
+ * kernel leaves out the products with the interior diagonal and starts every partial sum from its first product instead of
+ * 0 +; the double entry also reads D_hat once per wavefront (the 29 entries of rows 0..3 off the diagonal; the others are used
+ * as the negation of their mirror image, D_hat[32..63] and the diagonal are never read), the float entry reads the rows as
+ * the parent does and relies on the first condition only.
+ * The order of the remaining terms is that of the parent.  What is dropped is only the addition of
+ * exact zeros, the caveat fdd_stiffness_matrix_diag carries: for finite inputs every output is the value of
+ * fdd_stiffness_matrix_lines[_shared][_f32], bit for bit up to the sign of a zero.  poly_degree 7 and diag = 1 only:
+ * FDD_ERR_UNSUPPORTED otherwise, output untouched. */
+int fdd_stiffness_matrix_lines_lean(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream);
+int fdd_stiffness_matrix_lines_lean_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream);
 /* Which blocks repeat?  out[e] (num_elements 64-bit words in device memory) = a hash of the bit patterns of element e's block
  * of G[0], G[1], G[2] that depends on the position of every word: equal blocks give equal hashes, and two blocks that differ
  * in a single word give different ones.  3-D elements, poly_degree 1..15. */

@@ -273,6 +273,18 @@ int fddh_problem_line_stiffness_info(fddh_problem *p, int *enabled, int *fine_do
  * found (0: not looked for), how many of the Subdomain's level lists run it (in the precision in use), of how many.  Any
  * argument may be NULL. */
 int fddh_problem_shared_factor_info(fddh_problem *p, int *enabled, int *fine_domain_shared, int *fine_domain_classes, int *sub_lists_shared, int *sub_lists);
+/* Flag "lean_line_stiffness" (default 1 where the kernel library exports fdd_stiffness_matrix_lines_lean and _lines_lean_f32;
+ * setting it to 1 on a library without them is refused, naming the missing entry): a list that runs the line form (see
+ * "line_stiffness"), shared or streamed, runs its lean instance where the derivative table the list uploads has an interior
+ * diagonal of +-0.0 and is off that diagonal bit for bit its own negated mirror image (D_hat[63 - m] = -D_hat[m]) -- checked on the host on the
+ * very array that is uploaded, at set-up and at every fddh_problem_set_D_hat, the float copy of the single-precision inner
+ * solve on its own.  The table of this library's GLL nodes passes in both precisions.  A table that fails keeps the parent
+ * instance, silently.  The lean instance leaves out the addition of exact zeros and nothing else (fdd_hip.h): the operator's
+ * values are the parent's, to the sign of a zero, so nothing that hangs on the operator is emptied.  It takes effect only
+ * where the line form runs.  0: the parent instances everywhere.
+ * The info entry: is the flag on, does the fine Domain's table pass the check, does its list run the lean instance, how many
+ * of the Subdomain's level lists run it (in the precision in use), of how many.  Any argument may be NULL. */
+int fddh_problem_lean_line_info(fddh_problem *p, int *enabled, int *fine_domain_table_ok, int *fine_domain_lean, int *sub_lists_lean, int *sub_lists);
 int fddh_problem_set_flag(fddh_problem *p, const char *name, int value);
 
 /* Low-order AMG preconditioner of the inner solve (Subdomain::low_order_preconditioner,

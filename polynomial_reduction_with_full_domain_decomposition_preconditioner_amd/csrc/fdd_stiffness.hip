@@ -665,13 +665,104 @@ __device__ __forceinline__ void line_au(T (&au)[8], const T (&gdu)[8], const T *
     }
 }
 
+// ---- the lean instances (kLean != 0; fdd_stiffness_matrix_lines_lean[_f32]) ----
+// The caller guarantees two things about D_hat, bit for bit: the interior diagonal D_hat[i + 8 i], i = 1..6, is +-0.0, and
+// D_hat[63 - m] = -D_hat[m] for every other m (both hold for the table of mirrored GLL nodes).  The lean instances then leave out
+// work the value of the result does not need; each part is one bit of kLean:
+//   kLeanTerms     every partial sum starts from its first product instead of T(0) +, and the products with an interior
+//                  diagonal entry are left out; the remaining terms keep their ascending order.  120 of the 816
+//                  floating-point instructions per lane.  What is dropped is the addition of exact zeros: for finite
+//                  inputs the result is the parent's, to the sign of a zero.
+//   kLeanResident  D_hat is read once at kernel entry: the 29 entries m < 32 off the diagonal, 58 scalar registers in
+//                  double.  Entry m >= 32 is used as -D_hat[63 - m] (a source modifier on the multiply, the same bits as
+//                  the stored entry).  The body has no scalar load, so no lgkmcnt(0) wait for one sits between its LDS
+//                  accesses.  Needs kLeanTerms (the diagonal entries are not kept).
+// Requesting the shared instance's factor lines ahead of the point_dof gather was built as a third part and measured no
+// faster (HISTORY); it is not in the kernel.  In float the resident table measured no faster than the row loads either, so
+// the float entries run kLeanTerms alone.
+enum : int
+{
+    kLeanTerms = 1,
+    kLeanResident = 2
+};
+
+// D_hat as the lean instances read it: entry (r, c) = D_hat[c + 8 r], r and c known at compile time after unrolling
+template <typename T, bool kResident>
+struct LeanTable
+{
+    static constexpr int slot(int m) { return m - (m > 9) - (m > 18) - (m > 27); } // m < 32 without the diagonal 9, 18, 27
+    const T *D_hat;
+    T d[kResident ? 29 : 1];
+    __device__ __forceinline__ explicit LeanTable(const T *__restrict__ D) : D_hat(D)
+    {
+        if constexpr (kResident)
+        {
+            T top[32]; // rows 0..3 in a few wide scalar loads, all requested before the first is waited for
+#pragma unroll
+            for (int m = 0; m < 32; m++) top[m] = D[m];
+#pragma unroll
+            for (int m = 0; m < 32; m++)
+                if (m != 9 and m != 18 and m != 27)
+                {
+                    T v = top[m];
+                    asm volatile("" : "+s"(v)); // a scalar register from here on: not re-read, not moved into lanes
+                    d[slot(m)] = v;
+                }
+        }
+    }
+    __device__ __forceinline__ const T *row(int r) const { return kResident ? nullptr : line_row(D_hat, r); }
+    __device__ __forceinline__ T at(const T *row_r, int r, int c) const
+    {
+        if constexpr (kResident)
+        {
+            const int m = c + 8 * r;
+            return m < 32 ? d[slot(m)] : -d[slot(63 - m)];
+        }
+        else
+            return row_r[c];
+    }
+};
+__device__ __forceinline__ constexpr bool lean_zero_entry(int r, int c) { return r == c and r >= 1 and r <= 6; }
+
+// line_du / line_au without the zero terms: the first product starts the sum, the others follow in ascending order
+template <typename T, bool kResident>
+__device__ __forceinline__ void lean_du(T (&du)[8], const T (&ul)[8], const LeanTable<T, kResident> &D)
+{
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+    {
+        const T *Di = D.row(i);
+        du[i] = D.at(Di, i, 0) * ul[0];
+#pragma unroll
+        for (int p = 1; p < 8; p++)
+            if (not lean_zero_entry(i, p)) du[i] += D.at(Di, i, p) * ul[p];
+    }
+}
+template <typename T, bool kResident>
+__device__ __forceinline__ void lean_au(T (&au)[8], const T (&gdu)[8], const LeanTable<T, kResident> &D)
+{
+#pragma unroll
+    for (int p = 0; p < 8; p++)
+    {
+        const T *Dp = D.row(p);
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+        {
+            if (p == 0)
+                au[i] = D.at(Dp, 0, i) * gdu[0];
+            else if (not lean_zero_entry(p, i))
+                au[i] += D.at(Dp, p, i) * gdu[p];
+        }
+    }
+}
+
 // kShared: element e reads its three factor lines from the block of element factor_elem[e] of the same arrays (the host
 // layer establishes, from the list's own arrays, which elements hold bit for bit the block of an earlier one:
 // fdd_stiffness_factor_block_hash / _verify).  The lookup is wave-uniform, so the factor base stays in scalar registers
 // like the element's own; the factor loads are plain loads, since the few distinct blocks are meant to stay in cache
 // (a nontemporal load goes past L1).  u, point_dof and Au keep the element's own base, and nothing else differs: the same
 // words reach the same arithmetic.  factor_elem is not read by the streamed instances.
-template <typename T, bool kGather, bool kNTStore, bool kShared = false>
+template <typename T, bool kGather, bool kNTStore, bool kShared = false, int kLean = 0>
 __global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restrict__ Au, const T *__restrict__ u, const int *__restrict__ point_dof, const double *__restrict__ u_scale, const T *__restrict__ D_hat, GPtrsT<T> G, const int *__restrict__ elem_offset, int num_elements, const int *__restrict__ factor_elem)
 {
     using C = LineCfg;
@@ -693,6 +784,9 @@ __global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restri
         fbase = elem_offset ? (size_t)elem_offset[rep] : (size_t)rep * C::n3;
     }
     T *ta = s_a[e_loc], *tb = s_b[e_loc];
+    constexpr bool kTerms = (kLean & kLeanTerms) != 0, kResident = (kLean & kLeanResident) != 0;
+    static_assert(kTerms or not kResident, "the resident table does not hold the diagonal entries");
+    const LeanTable<T, kResident> Dl(D_hat);
 
     // k-column role: u as in the slab form
     T r_u[n];
@@ -721,8 +815,11 @@ __global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restri
     }
 
     T r_3[n];
+    if constexpr (not kTerms)
+    {
 #pragma unroll
-    for (int m = 0; m < n; m++) r_3[m] = T(0);
+        for (int m = 0; m < n; m++) r_3[m] = T(0);
+    }
 
     {
         // the three factor lines of this lane, all requested before anything waits
@@ -748,23 +845,43 @@ __global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restri
 #pragma unroll
         for (int k = 0; k < n; k++)
         {
-            const T *Dk = line_row(D_hat, k);
-            T Du_3 = T(0);
+            if constexpr (kTerms)
+            {
+                const T *Dk = Dl.row(k);
+                T Du_3 = Dl.at(Dk, k, 0) * r_u[0];
 #pragma unroll
-            for (int p = 0; p < n; p++) Du_3 += Dk[p] * r_u[p];
-            const T GDu_3 = g2[k] * Du_3;
+                for (int p = 1; p < n; p++)
+                    if (not lean_zero_entry(k, p)) Du_3 += Dl.at(Dk, k, p) * r_u[p];
+                const T GDu_3 = g2[k] * Du_3;
 #pragma unroll
-            for (int m = 0; m < n; m++) r_3[m] += Dk[m] * GDu_3;
+                for (int m = 0; m < n; m++)
+                {
+                    if (k == 0)
+                        r_3[m] = Dl.at(Dk, 0, m) * GDu_3;
+                    else if (not lean_zero_entry(k, m))
+                        r_3[m] += Dl.at(Dk, k, m) * GDu_3;
+                }
+            }
+            else
+            {
+                const T *Dk = line_row(D_hat, k);
+                T Du_3 = T(0);
+#pragma unroll
+                for (int p = 0; p < n; p++) Du_3 += Dk[p] * r_u[p];
+                const T GDu_3 = g2[k] * Du_3;
+#pragma unroll
+                for (int m = 0; m < n; m++) r_3[m] += Dk[m] * GDu_3;
+            }
         }
 
         // x: the row out of the u tile, Au_1 into the other tile
         T ul[n], w[n], au[n];
 #pragma unroll
         for (int p = 0; p < n; p++) ul[p] = ta[C::at(p, a, b)];
-        line_du(w, ul, D_hat);
+        if constexpr (kTerms) lean_du(w, ul, Dl); else line_du(w, ul, D_hat);
 #pragma unroll
         for (int p = 0; p < n; p++) w[p] = g0[p] * w[p];
-        line_au(au, w, D_hat);
+        if constexpr (kTerms) lean_au(au, w, Dl); else line_au(au, w, D_hat);
 #pragma unroll
         for (int p = 0; p < n; p++) tb[C::at(p, a, b)] = au[p];
         // y: the column out of the u tile, Au_2 over it: every lane's row and column loads precede these stores in the
@@ -772,10 +889,10 @@ __global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restri
 #pragma unroll
         for (int p = 0; p < n; p++) ul[p] = ta[C::at(a, p, b)];
         element_sync<true>();
-        line_du(w, ul, D_hat);
+        if constexpr (kTerms) lean_du(w, ul, Dl); else line_du(w, ul, D_hat);
 #pragma unroll
         for (int p = 0; p < n; p++) w[p] = g1[p] * w[p];
-        line_au(au, w, D_hat);
+        if constexpr (kTerms) lean_au(au, w, Dl); else line_au(au, w, D_hat);
 #pragma unroll
         for (int p = 0; p < n; p++) ta[C::at(a, p, b)] = au[p];
         element_sync<true>();
@@ -793,19 +910,19 @@ __global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restri
     }
 }
 
-template <typename T, bool kShared>
+template <typename T, bool kShared, int kLean = 0>
 int launch_lines_t(T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const GPtrsT<T> &G, const int *elem_offset, const int *factor_elem, int num_elements, void *stream)
 {
     const int grid = (num_elements + LineCfg::epb - 1) / LineCfg::epb;
     static const bool nt_store = fdd_env_int("FDD_TUNE_STIFFNESS_NT_STORE", 1) != 0;
     if (point_dof and nt_store)
-        hipLaunchKernelGGL((line_stiffness_kernel_t<T, true, true, kShared>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem);
+        hipLaunchKernelGGL((line_stiffness_kernel_t<T, true, true, kShared, kLean>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem);
     else if (point_dof)
-        hipLaunchKernelGGL((line_stiffness_kernel_t<T, true, false, kShared>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem);
+        hipLaunchKernelGGL((line_stiffness_kernel_t<T, true, false, kShared, kLean>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem);
     else if (nt_store)
-        hipLaunchKernelGGL((line_stiffness_kernel_t<T, false, true, kShared>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem);
+        hipLaunchKernelGGL((line_stiffness_kernel_t<T, false, true, kShared, kLean>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem);
     else
-        hipLaunchKernelGGL((line_stiffness_kernel_t<T, false, false, kShared>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem);
+        hipLaunchKernelGGL((line_stiffness_kernel_t<T, false, false, kShared, kLean>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem);
     FDD_LAUNCH_CHECK();
     return 0;
 }
@@ -840,6 +957,54 @@ int lines_dispatch(T *Au, const T *u, const int *point_dof, const double *u_scal
     }
     if (shared) return launch_lines_t<T, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, factor_elem, num_elements, stream);
     return launch_lines_t<T, false>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, nullptr, num_elements, stream);
+}
+
+// lean (fdd_stiffness_matrix_lines_lean[_f32]): the kLean instances, shared where factor_elem is given and streamed where
+// it is null; degree 7 on three arrays only, anything else is refused before the output is touched.  The caller's
+// guarantee about D_hat is in fdd_hip.h.  Double runs both parts, float kLeanTerms (see above).  A development build
+// (-DFDD_LEAN_LINE_DEV) compiles both choices for both precisions and exports fdd_dev_lean_line_parts to choose between
+// them at run time, for tools/lean_line_ab.py's per-part timings.
+#ifdef FDD_LEAN_LINE_DEV
+static int g_lean_line_parts = 0; // 0: the choice of the release build
+extern "C" int fdd_dev_lean_line_parts(int parts)
+{
+    if (parts != 0 && parts != kLeanTerms && parts != (kLeanTerms | kLeanResident)) return FDD_ERR_UNSUPPORTED;
+    g_lean_line_parts = parts;
+    return 0;
+}
+#endif
+
+template <typename T, int kLean>
+int launch_lines_lean_t(T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const GPtrsT<T> &g, const int *elem_offset, const int *factor_elem, int num_elements, void *stream)
+{
+    if (factor_elem) return launch_lines_t<T, true, kLean>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, factor_elem, num_elements, stream);
+    return launch_lines_t<T, false, kLean>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, nullptr, num_elements, stream);
+}
+
+template <typename T>
+int lines_lean_dispatch(T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const T *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream)
+{
+    FDD_REQUIRE(num_elements >= 0);
+    if (poly_degree != 7 || diag != 1)
+    {
+        fdd_set_error("the lean line form of the stiffness kernel supports poly_degree 7 on three factor arrays (diag = 1) only, got poly_degree %d, diag = %d", poly_degree, diag);
+        return FDD_ERR_UNSUPPORTED;
+    }
+    if (num_elements == 0) return 0;
+    FDD_REQUIRE(Au != nullptr && u != nullptr && D_hat != nullptr && G != nullptr);
+    GPtrsT<T> g;
+    for (int k = 0; k < FDD_NUM_GEOM_FACTS; k++) g.g[k] = nullptr;
+    for (int k = 0; k < 3; k++)
+    {
+        FDD_REQUIRE(G[k] != nullptr);
+        g.g[k] = G[k];
+    }
+    constexpr int kParts = sizeof(T) == 8 ? (kLeanTerms | kLeanResident) : kLeanTerms;
+#ifdef FDD_LEAN_LINE_DEV
+    constexpr int kOther = kParts ^ kLeanResident;
+    if (g_lean_line_parts == kOther) return launch_lines_lean_t<T, kOther>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, factor_elem, num_elements, stream);
+#endif
+    return launch_lines_lean_t<T, kParts>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, factor_elem, num_elements, stream);
 }
 
 // ---- factor blocks that repeat from element to element (the kShared line instance) ----
@@ -1387,6 +1552,16 @@ int fdd_stiffness_matrix_lines_shared_f32(float *Au, const float *v, const doubl
 {
     if (int rc = lines_shared_diag_only(diag)) return rc;
     return lines_dispatch<float>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, factor_elem, true, num_elements, poly_degree, diag, stream);
+}
+
+int fdd_stiffness_matrix_lines_lean(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream)
+{
+    return lines_lean_dispatch<double>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, factor_elem, num_elements, poly_degree, diag, stream);
+}
+
+int fdd_stiffness_matrix_lines_lean_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream)
+{
+    return lines_lean_dispatch<float>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, factor_elem, num_elements, poly_degree, diag, stream);
 }
 
 constexpr int kFactorBlockGrid = 1 << 20; // workgroups; beyond it a workgroup takes several elements in turn

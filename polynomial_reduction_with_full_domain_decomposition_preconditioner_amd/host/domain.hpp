@@ -477,6 +477,7 @@ class Domain
     bool mfma_stiffness = true; // N >= 11: stiffness on the fp64 matrix cores (not bit-identical; 1e-12 tolerance)
     bool line_stiffness = fdd::missing_line_stiffness_entry() == nullptr;  // degree-7 lists on the three-array kernel run its line form (element_operator.hpp)
     bool shared_factor_blocks = fdd::missing_shared_factor_entry() == nullptr; // lists on the line form whose factor blocks repeat from element to element read the few distinct ones (element_operator.hpp)
+    bool lean_line_stiffness = fdd::missing_lean_line_entry() == nullptr; // lists on the line form whose D_hat allows it run the instance without the zero terms (element_operator.hpp)
     bool skip_zero_factors = fdd::missing_zero_factor_entry() == nullptr; // off-diagonal factor arrays that are identically zero are not streamed (element_operator.hpp)
     bool mfma_skip_zero_factors = fdd::missing_mfma_zero_factor_entry() == nullptr; // nor by the matrix-core kernel (N >= 11), while skip_zero_factors and mfma_stiffness are on
     DType tolerance = 1.0e-07;
@@ -767,6 +768,7 @@ class Domain
         list.D_hat = D_hat.as<double>(); // set_D_hat rewrites this buffer in place
         fdd::detect_zero_factors(list); // the list is complete: are its off-diagonal factor arrays zero everywhere?
         fdd::detect_shared_blocks(list); // and do its elements share their factor blocks?
+        fdd::check_lean_table(list, D_hat_hst); // and does the table uploaded above allow the lean line instance?
 
         // Solver vectors (GMRES bases are allocated on first use)
         r_k = fdd::dev().malloc<DType>(num_local_points);
@@ -784,6 +786,7 @@ class Domain
     {
         D_hat_hst.assign(D, D + (size_t)n * n);
         D_hat.copyFrom(D_hat_hst.data(), (size_t)n * n * sizeof(DType));
+        fdd::check_lean_table(list, D_hat_hst);
     }
 
     // domain.tpp:527-580
@@ -855,7 +858,7 @@ class Domain
     // domain.tpp:602-609
     void stiffness_matrix(fdd::memory &Au, fdd::memory &u, bool apply_dssum = false)
     {
-        fdd::apply_local(list, Au.as<double>(), u.as<double>(), work_dev, mfma_stiffness, skip_zero_factors, line_stiffness, mfma_skip_zero_factors, shared_factor_blocks);
+        fdd::apply_local(list, Au.as<double>(), u.as<double>(), work_dev, mfma_stiffness, skip_zero_factors, line_stiffness, mfma_skip_zero_factors, shared_factor_blocks, lean_line_stiffness);
         if (apply_dssum) direct_stiffness_summation(Au, Au, true, false);
     }
 
@@ -973,6 +976,7 @@ class Domain
     bool runs_diag_kernel() const { return fdd::on_diag_kernel<double>(list, mfma_stiffness, skip_zero_factors); } // flag "skip_zero_factors"
     bool runs_mfma_diag_kernel() const { return fdd::on_mfma_diag_kernel<double>(list, mfma_stiffness, skip_zero_factors, mfma_skip_zero_factors); } // flag "mfma_skip_zero_factors"
     bool runs_line_kernel() const { return fdd::on_line_kernel<double>(list, mfma_stiffness, skip_zero_factors, line_stiffness); } // flag "line_stiffness"
+    bool runs_lean_line_kernel() const { return fdd::on_lean_line_kernel<double>(list, mfma_stiffness, skip_zero_factors, line_stiffness, lean_line_stiffness); } // flag "lean_line_stiffness"
     bool runs_shared_line_kernel() const { return fdd::on_shared_line_kernel<double>(list, mfma_stiffness, skip_zero_factors, line_stiffness, shared_factor_blocks); } // flag "shared_factor_blocks"
     bool set_affine_geometry(bool on)
     {
@@ -983,7 +987,7 @@ class Domain
     // q (points) = A_local (Q p~)
     void stiffness_from_nodes(fdd::memory &q, fdd::memory &pn)
     {
-        fdd::apply_gather(list, q.as<double>(), pn.as<double>(), point_node_dev.as<int>(), nullptr, num_local_nodes, mfma_stiffness, skip_zero_factors, line_stiffness, mfma_skip_zero_factors, shared_factor_blocks);
+        fdd::apply_gather(list, q.as<double>(), pn.as<double>(), point_node_dev.as<int>(), nullptr, num_local_nodes, mfma_stiffness, skip_zero_factors, line_stiffness, mfma_skip_zero_factors, shared_factor_blocks, lean_line_stiffness);
     }
 
     // sqrt(<r, QQt r>) (domain.tpp:916-931) from r^ = Qt r: sum_n r^_n * gs(r^)_n * mask_n.

@@ -9,6 +9,7 @@
 #define FDD_ELEMENT_OPERATOR_HPP
 
 #include <algorithm>
+#include <cstring>
 #include <type_traits>
 #include <unordered_map>
 #include <vector>
@@ -54,6 +55,9 @@ struct LevelList
     bool shared_blocks = false;
     int factor_classes = 0; // distinct blocks found (0: not looked for)
     memory factor_elem;     // device ints, allocated only where shared_blocks holds
+    // does the table behind D_hat / D_hat32 meet the lean line instance's conditions (check_lean_table, on the host array
+    // each upload is made from; each precision on its own)?
+    bool lean_D_hat = false, lean_D_hat32 = false;
 
     size_t num_points() const { return (size_t)num_elements * (poly_degree + 1) * (poly_degree + 1) * (dim == 3 ? poly_degree + 1 : 1); }
 };
@@ -200,9 +204,60 @@ inline bool on_shared_line_kernel(const LevelList &ll, bool mfma_enabled, bool s
     return shared_factor_blocks and ll.shared_blocks and on_line_kernel<Real>(ll, mfma_enabled, skip_zero_factors, line_stiffness) and missing_shared_factor_entry() == nullptr;
 }
 
+// ---- the lean instances of the line form (flag "lean_line_stiffness") ----
+// the first entry of the lean line instances the loaded kernel library does not export, or nullptr
+inline const char *missing_lean_line_entry()
+{
+    if (&fdd_stiffness_matrix_lines_lean == nullptr) return "fdd_stiffness_matrix_lines_lean";
+    if (&fdd_stiffness_matrix_lines_lean_f32 == nullptr) return "fdd_stiffness_matrix_lines_lean_f32";
+    return nullptr;
+}
+
+// What fdd_stiffness_matrix_lines_lean[_f32] asks of an 8 x 8 table, bit for bit: the interior diagonal is +-0.0 (either
+// sign, each entry on its own: gll::dgll writes +0.0 on all six) and everywhere else entry 63 - m has the bits of the negation
+// of entry m.  A NaN passes only with its mirror image's payload and the other sign.
+template <typename Real>
+inline bool lean_table_ok(const Real *D)
+{
+    using Bits = typename std::conditional<sizeof(Real) == 8, unsigned long long, unsigned int>::type;
+    const Bits sign = (Bits)1 << (8 * sizeof(Real) - 1);
+    Bits w[64];
+    memcpy(w, D, sizeof(w));
+    for (int i = 1; i <= 6; i++)
+        if ((w[9 * i] & ~sign) != 0) return false;
+    for (int m = 0; m < 32; m++)
+        if (m != 9 and m != 18 and m != 27 and w[63 - m] != (w[m] ^ sign)) return false;
+    return true;
+}
+
+// The float table is the cast to_float makes of the double one when the single-precision inner solve is prepared
+// (Subdomain::prepare_single_precision) and is not remade afterwards: the verdict on it follows the same rule.
+inline void check_lean_table32(LevelList &ll, const std::vector<double> &D)
+{
+    const std::vector<float> D32(D.begin(), D.end());
+    ll.lean_D_hat32 = ll.poly_degree == 7 and D32.size() == 64 and lean_table_ok(D32.data());
+}
+
+// Called wherever a list's double table is uploaded (set-up, set_D_hat), with the host array the upload is made from.
+// Tables of other sizes fail.  While no float copy exists yet the verdict on it is that of the cast it would be made from.
+inline void check_lean_table(LevelList &ll, const std::vector<double> &D)
+{
+    ll.lean_D_hat = ll.poly_degree == 7 and D.size() == 64 and lean_table_ok(D.data());
+    if (not ll.D_hat32.ptr()) check_lean_table32(ll, D);
+}
+
+// does the list run a lean instance of the line form (shared where on_shared_line_kernel holds, streamed otherwise)?  Only
+// where it runs the line form at all and its table in this precision passed the check; a table that did not keeps the parent
+// instance.  The parent's values, to the sign of a zero.
+template <typename Real>
+inline bool on_lean_line_kernel(const LevelList &ll, bool mfma_enabled, bool skip_zero_factors, bool line_stiffness, bool lean_line_stiffness)
+{
+    return lean_line_stiffness and (std::is_same<Real, float>::value ? ll.lean_D_hat32 : ll.lean_D_hat) and on_line_kernel<Real>(ll, mfma_enabled, skip_zero_factors, line_stiffness) and missing_lean_line_entry() == nullptr;
+}
+
 // Au = A_L u on the points of the list (Au, u: the vectors the list's first_offset counts in).  workspace: three vectors
 // of the list's points for the two-launch form above degree 15.
-inline void apply_local(const LevelList &ll, double *Au, const double *u, const std::vector<memory> &workspace, bool mfma_enabled, bool skip_zero_factors, bool line_stiffness, bool mfma_skip_zero_factors, bool shared_factor_blocks)
+inline void apply_local(const LevelList &ll, double *Au, const double *u, const std::vector<memory> &workspace, bool mfma_enabled, bool skip_zero_factors, bool line_stiffness, bool mfma_skip_zero_factors, bool shared_factor_blocks, bool lean_line_stiffness)
 {
     void *stream = dev().stream;
     const double points = (double)ll.num_points();
@@ -218,6 +273,12 @@ inline void apply_local(const LevelList &ll, double *Au, const double *u, const 
         // high order: the six contractions on the fp64 matrix cores (tolerance-level parity, fdd_hip.h)
         ProfileScope prof("mfma_stiffness_kernel", 64.0 * points);
         FDD_CALL(fdd_stiffness_matrix_mfma(Au, u, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, stream));
+    }
+    else if (on_lean_line_kernel<double>(ll, mfma_enabled, skip_zero_factors, line_stiffness, lean_line_stiffness))
+    {
+        const bool shared = on_shared_line_kernel<double>(ll, mfma_enabled, skip_zero_factors, line_stiffness, shared_factor_blocks);
+        ProfileScope prof(shared ? "line_stiffness_kernel<shared,lean>" : "line_stiffness_kernel<lean>", (shared ? 16.0 : 40.0) * points); // the bytes of the parent instance
+        FDD_CALL(fdd_stiffness_matrix_lines_lean(Au, u, nullptr, nullptr, ll.D_hat, ll.G, nullptr, shared ? ll.factor_elem.as<int>() : nullptr, ll.num_elements, ll.poly_degree, 1, stream));
     }
     else if (on_shared_line_kernel<double>(ll, mfma_enabled, skip_zero_factors, line_stiffness, shared_factor_blocks))
     {
@@ -302,6 +363,16 @@ inline void stiffness_lines_shared(const LevelList &ll, float *q, const float *v
     for (int g = 0; g < NUM_GEOM_FACTS; g++) G[g] = ll.G32[g].as<float>();
     FDD_CALL(fdd_stiffness_matrix_lines_shared_f32(q, v, scale_dev, point_index, ll.D_hat32.as<float>(), G, nullptr, ll.factor_elem.as<int>(), ll.num_elements, ll.poly_degree, 1, s));
 }
+inline void stiffness_lines_lean(const LevelList &ll, double *q, const double *v, const double *scale_dev, const int *point_index, bool shared, void *s)
+{
+    FDD_CALL(fdd_stiffness_matrix_lines_lean(q, v, scale_dev, point_index, ll.D_hat, ll.G, nullptr, shared ? ll.factor_elem.as<int>() : nullptr, ll.num_elements, ll.poly_degree, 1, s));
+}
+inline void stiffness_lines_lean(const LevelList &ll, float *q, const float *v, const double *scale_dev, const int *point_index, bool shared, void *s)
+{
+    const float *G[NUM_GEOM_FACTS];
+    for (int g = 0; g < NUM_GEOM_FACTS; g++) G[g] = ll.G32[g].as<float>();
+    FDD_CALL(fdd_stiffness_matrix_lines_lean_f32(q, v, scale_dev, point_index, ll.D_hat32.as<float>(), G, nullptr, shared ? ll.factor_elem.as<int>() : nullptr, ll.num_elements, ll.poly_degree, 1, s));
+}
 inline void stiffness_affine(const LevelList &ll, double *q, const double *v, const double *scale_dev, const int *point_index, bool mfma, void *s)
 {
     FDD_CALL((mfma ? fdd_stiffness_matrix_mfma_affine : fdd_stiffness_matrix_affine)(q, v, scale_dev, point_index, ll.D_hat, ll.affine_c.as<double>(), ll.affine_w.as<double>(), nullptr, ll.num_elements, ll.poly_degree, s));
@@ -316,7 +387,7 @@ inline void stiffness_affine(const LevelList &ll, float *q, const float *v, cons
 // (null: 1).  q, point_index: the arrays the list's first_offset counts in; gathered_values: the length of v (the bytes it
 // adds to the count).  3-D lists of degree <= 15.
 template <typename Real>
-inline void apply_gather(const LevelList &ll, Real *q, const Real *v, const int *point_index, const double *scale_dev, int gathered_values, bool mfma_enabled, bool skip_zero_factors, bool line_stiffness, bool mfma_skip_zero_factors, bool shared_factor_blocks)
+inline void apply_gather(const LevelList &ll, Real *q, const Real *v, const int *point_index, const double *scale_dev, int gathered_values, bool mfma_enabled, bool skip_zero_factors, bool line_stiffness, bool mfma_skip_zero_factors, bool shared_factor_blocks, bool lean_line_stiffness)
 {
     constexpr bool f32 = std::is_same<Real, float>::value;
     const bool mfma = on_matrix_cores<Real>(ll, mfma_enabled);
@@ -335,6 +406,14 @@ inline void apply_gather(const LevelList &ll, Real *q, const Real *v, const int 
             ops::stiffness_mfma_diag(ll, q, v, scale_dev, point_index, dev().stream);
             return;
         }
+    if (on_lean_line_kernel<Real>(ll, mfma_enabled, skip_zero_factors, line_stiffness, lean_line_stiffness))
+    {
+        const bool shared = on_shared_line_kernel<Real>(ll, mfma_enabled, skip_zero_factors, line_stiffness, shared_factor_blocks);
+        const char *label = shared ? (f32 ? "line_stiffness_kernel<gather,shared,f32,lean>" : "line_stiffness_kernel<gather,shared,lean>") : (f32 ? "line_stiffness_kernel<gather,f32,lean>" : "line_stiffness_kernel<gather,lean>");
+        ProfileScope prof(label, (shared ? (f32 ? 8.0 : 12.0) : (f32 ? 20.0 : 36.0)) * points + gathered); // the bytes of the parent instance
+        ops::stiffness_lines_lean(ll, q, v, scale_dev, point_index, shared, dev().stream);
+        return;
+    }
     if (on_shared_line_kernel<Real>(ll, mfma_enabled, skip_zero_factors, line_stiffness, shared_factor_blocks))
     {
         ProfileScope prof(f32 ? "line_stiffness_kernel<gather,shared,f32>" : "line_stiffness_kernel<gather,shared>", (f32 ? 8.0 : 12.0) * points + gathered); // index and q; the few factor blocks stay in cache

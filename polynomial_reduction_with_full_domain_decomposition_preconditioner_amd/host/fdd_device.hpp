@@ -74,6 +74,11 @@
 #pragma weak fdd_stiffness_matrix_lines_shared_f32
 #pragma weak fdd_stiffness_factor_block_hash
 #pragma weak fdd_stiffness_factor_block_verify
+// and the lean instances of the line form (a D_hat with a zero interior diagonal that is its own negated mirror image):
+// without them every list keeps the parent instance, and the flag "lean_line_stiffness" refuses to be set to 1, naming the
+// missing entry (missing_lean_line_entry, element_operator.hpp)
+#pragma weak fdd_stiffness_matrix_lines_lean
+#pragma weak fdd_stiffness_matrix_lines_lean_f32
 
 namespace fdd
 {

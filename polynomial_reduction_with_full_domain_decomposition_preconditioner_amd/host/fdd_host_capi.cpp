@@ -1021,6 +1021,26 @@ int fddh_problem_shared_factor_info(fddh_problem *p, int *enabled, int *fine_dom
     }
 }
 
+int fddh_problem_lean_line_info(fddh_problem *p, int *enabled, int *fine_domain_table_ok, int *fine_domain_lean, int *sub_lists_lean, int *sub_lists)
+{
+    try
+    {
+        if (int rc = rank_check(p)) return rc;
+        if (!p) return fail("null argument");
+        Domain<SType> &dom = p->fine();
+        if (enabled) *enabled = dom.lean_line_stiffness ? 1 : 0;
+        if (fine_domain_table_ok) *fine_domain_table_ok = dom.operator_list().lean_D_hat ? 1 : 0;
+        if (fine_domain_lean) *fine_domain_lean = dom.runs_lean_line_kernel() ? 1 : 0;
+        if (sub_lists_lean) *sub_lists_lean = p->subdomain ? p->subdomain->lists_on_lean_line_kernel() : 0;
+        if (sub_lists) *sub_lists = p->subdomain ? (int)p->subdomain->operator_lists().size() : 0;
+        return 0;
+    }
+    catch (const std::exception &e)
+    {
+        return fail("%s", e.what());
+    }
+}
+
 int fddh_problem_set_flag(fddh_problem *p, const char *name, int value)
 {
     try
@@ -1154,6 +1174,17 @@ int fddh_problem_set_flag(fddh_problem *p, const char *name, int value)
                 if (const char *missing = fdd::missing_shared_factor_entry()) return fail("shared_factor_blocks needs %s, which the loaded kernel library does not export", missing);
             for (auto &kv : p->domains) kv.second.shared_factor_blocks = value != 0;
             if (p->subdomain) p->subdomain->shared_factor_blocks = value != 0;
+        }
+        else if (s == "lean_line_stiffness")
+        {
+            // lists on the line form whose uploaded D_hat has a zero interior diagonal and is its own negated mirror image
+            // (checked on the host whenever a table is uploaded) run the lean instance, which leaves out the addition of
+            // exact zeros (default where the kernel library has the entries); 0: the parent instances.  The values are the
+            // parent's, to the sign of a zero, so nothing that hangs on the operator is emptied.
+            if (value != 0)
+                if (const char *missing = fdd::missing_lean_line_entry()) return fail("lean_line_stiffness needs %s, which the loaded kernel library does not export", missing);
+            for (auto &kv : p->domains) kv.second.lean_line_stiffness = value != 0;
+            if (p->subdomain) p->subdomain->lean_line_stiffness = value != 0;
         }
         else if (s == "fused_projection")
         {

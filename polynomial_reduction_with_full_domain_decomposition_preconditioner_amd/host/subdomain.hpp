@@ -897,7 +897,11 @@ class Subdomain
                 FDD_CALL(fdd_sub_copy_f32_f64(ll.G32[g].template as<float>(), ll.G[g], (int)np, stream));
             }
         }
-        for (auto &ll : subdomain_operator.level_lists) ll.D_hat32 = fdd::to_float(D_hat[ll.level].first);
+        for (auto &ll : subdomain_operator.level_lists)
+        {
+            ll.D_hat32 = fdd::to_float(D_hat[ll.level].first);
+            fdd::check_lean_table32(ll, D_hat[ll.level].first);
+        }
         auto plan32 = [](amg::Csr32 &M32, CSR_Matrix<DType> &M) {
             if (M.num_rows == 0 or M.num_nnz == 0) return;
             M32.val = fdd::to_float(M.val_hst);
@@ -927,7 +931,7 @@ class Subdomain
     template <typename Real>
     void stiffness_from_dofs(Real *q, const Real *za, const double *scale_dev = nullptr)
     {
-        for (auto &ll : subdomain_operator.level_lists) fdd::apply_gather(ll, q, za, point_dof_dev.template as<int>(), scale_dev, subdomain_operator.num_extended_dofs, mfma_stiffness, skip_zero_factors, line_stiffness, mfma_skip_zero_factors, shared_factor_blocks);
+        for (auto &ll : subdomain_operator.level_lists) fdd::apply_gather(ll, q, za, point_dof_dev.template as<int>(), scale_dev, subdomain_operator.num_extended_dofs, mfma_stiffness, skip_zero_factors, line_stiffness, mfma_skip_zero_factors, shared_factor_blocks, lean_line_stiffness);
     }
 
     // y (dofs) = [Qt A_L Q | A_sup] (s x~): the operator of the inner iteration on a dof vector.  x~ is one of the
@@ -1063,6 +1067,8 @@ class Subdomain
     {
         for (int l = 0; D != nullptr and l < num_levels; l++)
             if (poly_degree[l] == degree) D_hat[l].first.assign(D, D + (size_t)n * n);
+        for (auto &ll : subdomain_operator.level_lists)
+            if (D != nullptr and poly_degree[ll.level] == degree) fdd::check_lean_table(ll, D_hat[ll.level].first); // the Domain has uploaded this table
         jacobi_dinv.free();
         jacobi_dinv_f32.free();
         jacobi_diag_hst.clear();
@@ -1404,6 +1410,7 @@ class Subdomain
     bool mfma_stiffness = true;           // N >= 11 element lists on the fp64 matrix cores
     bool line_stiffness = fdd::missing_line_stiffness_entry() == nullptr;  // degree-7 lists on the three-array kernel run its line form (element_operator.hpp)
     bool shared_factor_blocks = fdd::missing_shared_factor_entry() == nullptr; // lists on the line form whose factor blocks repeat from element to element read the few distinct ones (element_operator.hpp)
+    bool lean_line_stiffness = fdd::missing_lean_line_entry() == nullptr; // lists on the line form whose D_hat allows it run the instance without the zero terms (element_operator.hpp)
     bool skip_zero_factors = fdd::missing_zero_factor_entry() == nullptr; // lists whose off-diagonal factor arrays are identically zero do not stream them (element_operator.hpp)
     bool mfma_skip_zero_factors = fdd::missing_mfma_zero_factor_entry() == nullptr; // nor where they run on the matrix cores, while skip_zero_factors and mfma_stiffness are on
     std::vector<DType> residual_history;  // inner history of the last application
@@ -1605,6 +1612,7 @@ class Subdomain
             for (int g = 0; g < NUM_GEOM_FACTS; g++) ll.G[g] = subdomain_operator.geom_fact[g].template as<double>();
             fdd::detect_zero_factors(ll);
             fdd::detect_shared_blocks(ll);
+            fdd::check_lean_table(ll, D_hat[ll.level].first);
             subdomain_operator.level_lists.push_back(ll);
         }
 
@@ -1726,6 +1734,7 @@ class Subdomain
             for (int g = 0; g < NUM_GEOM_FACTS; g++) ll.G[g] = subdomain_operator.geom_fact[g].template as<double>() + ll.first_offset;
             fdd::detect_zero_factors(ll); // own elements and every ring's run, each on its own
             fdd::detect_shared_blocks(ll);
+            fdd::check_lean_table(ll, D_hat[ll.level].first);
             subdomain_operator.level_lists.push_back(ll);
         }
 
@@ -1909,7 +1918,7 @@ class Subdomain
 
         superdomain_operator.A.multiply(Au_sup, u_sup); // empty: no-op
 
-        for (auto &ll : subdomain_operator.level_lists) fdd::apply_local(ll, Au_sub_l.as<double>(), u_sub_l.as<double>(), work_dev, mfma_stiffness, skip_zero_factors, line_stiffness, mfma_skip_zero_factors, shared_factor_blocks);
+        for (auto &ll : subdomain_operator.level_lists) fdd::apply_local(ll, Au_sub_l.as<double>(), u_sub_l.as<double>(), work_dev, mfma_stiffness, skip_zero_factors, line_stiffness, mfma_skip_zero_factors, shared_factor_blocks, lean_line_stiffness);
     }
 
     // subdomain.tpp:4161-4268
@@ -2162,6 +2171,14 @@ class Subdomain
         int count = 0;
         for (auto &ll : subdomain_operator.level_lists)
             if (precision == 32 ? fdd::on_shared_line_kernel<float>(ll, mfma_stiffness, skip_zero_factors, line_stiffness, shared_factor_blocks) : fdd::on_shared_line_kernel<double>(ll, mfma_stiffness, skip_zero_factors, line_stiffness, shared_factor_blocks)) count++;
+        return count;
+    }
+    // how many on a lean instance of the line form (flag "lean_line_stiffness"), in the precision in use
+    int lists_on_lean_line_kernel() const
+    {
+        int count = 0;
+        for (auto &ll : subdomain_operator.level_lists)
+            if (precision == 32 ? fdd::on_lean_line_kernel<float>(ll, mfma_stiffness, skip_zero_factors, line_stiffness, lean_line_stiffness) : fdd::on_lean_line_kernel<double>(ll, mfma_stiffness, skip_zero_factors, line_stiffness, lean_line_stiffness)) count++;
         return count;
     }
     // and how many the line form of it (flag "line_stiffness")

@@ -439,6 +439,14 @@ class Problem:
         _H().call("fddh_problem_shared_factor_info", self.h, ctypes.byref(on), ctypes.byref(dom), ctypes.byref(classes), ctypes.byref(shared), ctypes.byref(lists))
         return {"enabled": bool(on.value), "fine_domain": bool(dom.value), "fine_domain_classes": classes.value, "sub_lists_shared": shared.value, "sub_lists": lists.value}
 
+    def lean_line_info(self):
+        """flag "lean_line_stiffness": is it on, does the fine domain's uploaded D_hat meet the lean line instance's
+        conditions (zero interior diagonal, negated mirror image bit for bit), does its list run that instance, and how
+        many of the subdomain's lists do, of how many"""
+        on, ok, dom, lean, lists = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        _H().call("fddh_problem_lean_line_info", self.h, ctypes.byref(on), ctypes.byref(ok), ctypes.byref(dom), ctypes.byref(lean), ctypes.byref(lists))
+        return {"enabled": bool(on.value), "fine_domain_table_ok": bool(ok.value), "fine_domain": bool(dom.value), "sub_lists_lean": lean.value, "sub_lists": lists.value}
+
     def dssum(self, u, mask=True, weight=False):
         out = np.zeros(self.n)
         _H().call("fddh_problem_dssum", self.h, _dp(out), _dp(np.ascontiguousarray(u)), int(mask), int(weight))

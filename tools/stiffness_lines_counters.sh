@@ -1,7 +1,9 @@
 #!/bin/bash
 # Run on the GPU box: hardware counters of ONE double three-array gather stiffness instance at config C2, every counter
 # group in a rocprofv3 --pmc run of its own (three launches each).
-# usage: tools/stiffness_lines_counters.sh <out dir> old|new [pass names: lds valu waits fetch write]
+# usage: tools/stiffness_lines_counters.sh <out dir> old|new|parent|lean [pass names: lds valu waits fetch write]
+# old / new: the slab and the streamed line instance (tools/stiffness_lines_ab.py); parent / lean: the shared line instance
+# and its lean form on one repeated factor block (tools/lean_line_ab.py).
 # FETCH_SIZE and WRITE_SIZE do not fit into one pass on gfx950 (rocprofv3 refuses the pair), so each has its own.
 # Any pass that does not end with status 0 ends the script: nothing more starts on the GPU after a failure.  Leave a pass
 # whose counters this rocprofv3 refuses out of the next call by naming the others.
@@ -9,11 +11,13 @@ out=$1; which=$2; shift 2
 passes=${*:-lds valu waits fetch write}
 want() { case " $passes " in *" $1 "*) return 0;; esac; return 1; }
 root=$(pwd)
+tool=stiffness_lines_ab.py
+case "$which" in parent|lean) tool=lean_line_ab.py;; esac
 mkdir -p "$out"
 pass() {
     name=$1; shift
     dir=$(mktemp -d /tmp/pmc_XXXXXX)
-    (cd /tmp && TMPDIR=/tmp timeout -k 10 240 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$dir" -o run -- python3 "$root/tools/stiffness_lines_ab.py" --counters "$which") > "$out/${which}_$name.run.log" 2>&1
+    (cd /tmp && TMPDIR=/tmp timeout -k 10 240 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d "$dir" -o run -- python3 "$root/tools/$tool" --counters "$which") > "$out/${which}_$name.run.log" 2>&1
     rc=$?
     if [ $rc -ne 0 ]; then echo "pass $name ($*) ended with status $rc: stopping" | tee -a "$out/${which}_counters.txt"; rm -rf "$dir"; exit $rc; fi
     python3 - "$dir" "$name" "$*" >> "$out/${which}_counters.txt" <<'PY'
