@@ -8,6 +8,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <type_traits>
 
 #include "fdd_hip.h"
 
@@ -170,6 +171,45 @@ static inline int fdd_env_int(const char *name, int fallback)
 {
     const char *e = getenv(name);
     return (e && *e) ? atoi(e) : fallback;
+}
+
+// ---- run-time values to compile-time ones, for choosing a kernel instance (host code) ----
+// n in [lo, hi]: f(std::integral_constant<int, n>{}) is called and the answer is true; any other n: false, nothing called
+// (the caller sets its own error text)
+template <int lo, int hi, typename F>
+static inline bool fdd_for_n(int n, F &&f)
+{
+    if constexpr (lo > hi)
+        return false;
+    else
+    {
+        if (n != lo) return fdd_for_n<lo + 1, hi>(n, f);
+        f(std::integral_constant<int, lo>{});
+        return true;
+    }
+}
+
+// f(std::true_type{}) or f(std::false_type{})
+template <typename F>
+static inline void fdd_for_bool(bool b, F &&f)
+{
+    if (b)
+        f(std::true_type{});
+    else
+        f(std::false_type{});
+}
+
+// three factor arrays: G[0..2] are required, g.g[3..5] are null (never dereferenced by the instances that take them)
+template <typename Ptrs, typename T>
+static inline int fdd_three_factors(Ptrs &g, const T *const G[FDD_NUM_GEOM_FACTS])
+{
+    for (int k = 0; k < FDD_NUM_GEOM_FACTS; k++) g.g[k] = nullptr;
+    for (int k = 0; k < 3; k++)
+    {
+        FDD_REQUIRE(G[k] != nullptr);
+        g.g[k] = G[k];
+    }
+    return 0;
 }
 
 #endif

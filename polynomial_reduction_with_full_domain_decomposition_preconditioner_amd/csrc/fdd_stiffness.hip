@@ -499,80 +499,59 @@ __global__ __launch_bounds__(kBlock, (kAffine && n == 8 && sizeof(T) == 8) ? 4 :
     }
 }
 
-template <typename T, int n>
+// FDD_TUNE_STIFFNESS_NT_STORE, read once
+inline bool stiffness_nt_store()
+{
+    static const bool nt_store = fdd_env_int("FDD_TUNE_STIFFNESS_NT_STORE", 1) != 0;
+    return nt_store;
+}
+
+// the instance of a kernel by (gather on load, non-temporal stores): f(gather, nt_store) with two std::bool_constant
+template <typename F>
+inline void for_gather_nt_store(const int *point_dof, F &&f)
+{
+    fdd_for_bool(point_dof != nullptr, [&](auto gather) { fdd_for_bool(stiffness_nt_store(), [&](auto nt) { f(gather, nt); }); });
+}
+
+// kDiag: the three-array instances; G.g[3..5] are not passed on (never dereferenced)
+template <typename T, int n, bool kDiag>
 int launch_fused_t(T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const GPtrsT<T> &G, const int *elem_offset, int num_elements, void *stream)
 {
     using C = FusedCfg<n>;
     const int grid = (num_elements + C::epb - 1) / C::epb;
-    static const bool nt_store = fdd_env_int("FDD_TUNE_STIFFNESS_NT_STORE", 1) != 0;
-    if (point_dof and nt_store)
-        hipLaunchKernelGGL((fused_stiffness_kernel_t<T, n, true, true>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements);
-    else if (point_dof)
-        hipLaunchKernelGGL((fused_stiffness_kernel_t<T, n, true, false>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements);
-    else if (nt_store)
-        hipLaunchKernelGGL((fused_stiffness_kernel_t<T, n, false, true>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements);
-    else
-        hipLaunchKernelGGL((fused_stiffness_kernel_t<T, n, false, false>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements);
+    for_gather_nt_store(point_dof, [&](auto gather, auto nt) {
+        hipLaunchKernelGGL((fused_stiffness_kernel_t<T, n, decltype(gather)::value, decltype(nt)::value, false, kDiag>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements);
+    });
     FDD_LAUNCH_CHECK();
     return 0;
 }
 
-// the kDiag instances: G.g[3..5] are not passed on (never dereferenced)
-template <typename T, int n>
-int launch_fused_diag_t(T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const GPtrsT<T> &G, const int *elem_offset, int num_elements, void *stream)
-{
-    using C = FusedCfg<n>;
-    const int grid = (num_elements + C::epb - 1) / C::epb;
-    static const bool nt_store = fdd_env_int("FDD_TUNE_STIFFNESS_NT_STORE", 1) != 0;
-    if (point_dof and nt_store)
-        hipLaunchKernelGGL((fused_stiffness_kernel_t<T, n, true, true, false, true>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements);
-    else if (point_dof)
-        hipLaunchKernelGGL((fused_stiffness_kernel_t<T, n, true, false, false, true>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements);
-    else if (nt_store)
-        hipLaunchKernelGGL((fused_stiffness_kernel_t<T, n, false, true, false, true>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements);
-    else
-        hipLaunchKernelGGL((fused_stiffness_kernel_t<T, n, false, false, false, true>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements);
-    FDD_LAUNCH_CHECK();
-    return 0;
-}
-
-template <typename T>
-int fused_dispatch_diag(T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const T *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
+// six factor arrays or, kDiag, three; in double or in float (the single-precision form is used gather-on-load only: the
+// preconditioner's dof-space solve, and has no two-launch form to point to)
+template <typename T, bool kDiag = false>
+int fused_dispatch(T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const T *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
 {
     FDD_REQUIRE(num_elements >= 0);
     if (num_elements == 0) return 0;
     FDD_REQUIRE(Au != nullptr && u != nullptr && D_hat != nullptr && G != nullptr);
     GPtrsT<T> g;
-    for (int k = 0; k < FDD_NUM_GEOM_FACTS; k++) g.g[k] = nullptr;
-    for (int k = 0; k < 3; k++)
+    if constexpr (kDiag)
     {
-        FDD_REQUIRE(G[k] != nullptr);
-        g.g[k] = G[k];
+        if (int rc = fdd_three_factors(g, G)) return rc;
     }
-    switch (poly_degree + 1)
-    {
-#define FDD_DIAG_CASE(N_) \
-    case N_: return launch_fused_diag_t<T, N_>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-        FDD_DIAG_CASE(2)
-        FDD_DIAG_CASE(3)
-        FDD_DIAG_CASE(4)
-        FDD_DIAG_CASE(5)
-        FDD_DIAG_CASE(6)
-        FDD_DIAG_CASE(7)
-        FDD_DIAG_CASE(8)
-        FDD_DIAG_CASE(9)
-        FDD_DIAG_CASE(10)
-        FDD_DIAG_CASE(11)
-        FDD_DIAG_CASE(12)
-        FDD_DIAG_CASE(13)
-        FDD_DIAG_CASE(14)
-        FDD_DIAG_CASE(15)
-        FDD_DIAG_CASE(16)
-#undef FDD_DIAG_CASE
-    default:
+    else
+        for (int k = 0; k < FDD_NUM_GEOM_FACTS; k++)
+        {
+            FDD_REQUIRE(G[k] != nullptr);
+            g.g[k] = G[k];
+        }
+    int rc = 0;
+    if (fdd_for_n<2, 16>(poly_degree + 1, [&](auto n) { rc = launch_fused_t<T, decltype(n)::value, kDiag>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream); })) return rc;
+    if constexpr (sizeof(T) == 4 && !kDiag)
+        fdd_set_error("fused stiffness kernel supports poly_degree 1..15, got %d", poly_degree);
+    else
         fdd_set_error("fused stiffness kernel supports poly_degree 1..15, got %d (use the two-launch form)", poly_degree);
-        return FDD_ERR_UNSUPPORTED;
-    }
+    return FDD_ERR_UNSUPPORTED;
 }
 
 // ---------------------------------------------------------------------------
@@ -910,31 +889,60 @@ __global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restri
     }
 }
 
-template <typename T, bool kShared, int kLean = 0>
+// kShared by whether factor_elem is given
+template <typename T, int kLean>
 int launch_lines_t(T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const GPtrsT<T> &G, const int *elem_offset, const int *factor_elem, int num_elements, void *stream)
 {
     const int grid = (num_elements + LineCfg::epb - 1) / LineCfg::epb;
-    static const bool nt_store = fdd_env_int("FDD_TUNE_STIFFNESS_NT_STORE", 1) != 0;
-    if (point_dof and nt_store)
-        hipLaunchKernelGGL((line_stiffness_kernel_t<T, true, true, kShared, kLean>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem);
-    else if (point_dof)
-        hipLaunchKernelGGL((line_stiffness_kernel_t<T, true, false, kShared, kLean>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem);
-    else if (nt_store)
-        hipLaunchKernelGGL((line_stiffness_kernel_t<T, false, true, kShared, kLean>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem);
-    else
-        hipLaunchKernelGGL((line_stiffness_kernel_t<T, false, false, kShared, kLean>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem);
+    fdd_for_bool(factor_elem != nullptr, [&](auto shared) {
+        for_gather_nt_store(point_dof, [&](auto gather, auto nt) {
+            hipLaunchKernelGGL((line_stiffness_kernel_t<T, decltype(gather)::value, decltype(nt)::value, decltype(shared)::value, kLean>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem);
+        });
+    });
     FDD_LAUNCH_CHECK();
     return 0;
 }
 
-// diag = 1: three factor arrays, G[3..5] are not passed on (never dereferenced).  diag = 0: six arrays -- that form was built
-// and timed (see above), was not ahead of the slab form and is not compiled in: FDD_ERR_UNSUPPORTED
-// shared (fdd_stiffness_matrix_lines_shared[_f32]): factor_elem names the element whose factor block each element reads;
-// three arrays only
-template <typename T>
-int lines_dispatch(T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const T *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, bool shared, int num_elements, int poly_degree, int diag, void *stream)
+// A development build (-DFDD_LEAN_LINE_DEV) compiles both choices of the lean parts for both precisions and exports
+// fdd_dev_lean_line_parts to choose between them at run time, for tools/lean_line_ab.py's per-part timings.
+#ifdef FDD_LEAN_LINE_DEV
+static int g_lean_line_parts = 0; // 0: the choice of the release build
+extern "C" int fdd_dev_lean_line_parts(int parts)
 {
-    FDD_REQUIRE(num_elements >= 0 && (diag == 0 || diag == 1));
+    if (parts != 0 && parts != kLeanTerms && parts != (kLeanTerms | kLeanResident)) return FDD_ERR_UNSUPPORTED;
+    g_lean_line_parts = parts;
+    return 0;
+}
+#endif
+
+// The three entries of the line form; every refusal comes before the output is touched.
+// streamed (fdd_stiffness_matrix_lines[_f32]): diag = 1: three factor arrays, G[3..5] are not passed on (never dereferenced).
+//   diag = 0: six arrays -- that form was built and timed (see above), was not ahead of the slab form and is not compiled in
+// shared (fdd_stiffness_matrix_lines_shared[_f32]): factor_elem names the element whose factor block each element reads;
+//   three arrays only
+// lean (fdd_stiffness_matrix_lines_lean[_f32]): the kLean instances, shared where factor_elem is given and streamed where it
+//   is null; degree 7 on three arrays only.  The caller's guarantee about D_hat is in fdd_hip.h.  Double runs both parts,
+//   float kLeanTerms (see above)
+enum class LineEntry
+{
+    streamed,
+    shared,
+    lean
+};
+template <typename T>
+int lines_dispatch(LineEntry entry, T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const T *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream)
+{
+    if (entry == LineEntry::shared && diag != 1)
+    {
+        fdd_set_error("the shared-block line form of the stiffness kernel exists on three factor arrays only (diag = 1), got diag = %d", diag);
+        return FDD_ERR_UNSUPPORTED;
+    }
+    FDD_REQUIRE(num_elements >= 0 && (entry == LineEntry::lean || diag == 0 || diag == 1));
+    if (entry == LineEntry::lean && (poly_degree != 7 || diag != 1))
+    {
+        fdd_set_error("the lean line form of the stiffness kernel supports poly_degree 7 on three factor arrays (diag = 1) only, got poly_degree %d, diag = %d", poly_degree, diag);
+        return FDD_ERR_UNSUPPORTED;
+    }
     if (poly_degree != 7)
     {
         fdd_set_error("the line form of the stiffness kernel supports poly_degree 7 only, got %d", poly_degree);
@@ -947,64 +955,16 @@ int lines_dispatch(T *Au, const T *u, const int *point_dof, const double *u_scal
     }
     if (num_elements == 0) return 0;
     FDD_REQUIRE(Au != nullptr && u != nullptr && D_hat != nullptr && G != nullptr);
-    FDD_REQUIRE(not shared || factor_elem != nullptr);
+    FDD_REQUIRE(entry != LineEntry::shared || factor_elem != nullptr);
     GPtrsT<T> g;
-    for (int k = 0; k < FDD_NUM_GEOM_FACTS; k++) g.g[k] = nullptr;
-    for (int k = 0; k < 3; k++)
-    {
-        FDD_REQUIRE(G[k] != nullptr);
-        g.g[k] = G[k];
-    }
-    if (shared) return launch_lines_t<T, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, factor_elem, num_elements, stream);
-    return launch_lines_t<T, false>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, nullptr, num_elements, stream);
-}
-
-// lean (fdd_stiffness_matrix_lines_lean[_f32]): the kLean instances, shared where factor_elem is given and streamed where
-// it is null; degree 7 on three arrays only, anything else is refused before the output is touched.  The caller's
-// guarantee about D_hat is in fdd_hip.h.  Double runs both parts, float kLeanTerms (see above).  A development build
-// (-DFDD_LEAN_LINE_DEV) compiles both choices for both precisions and exports fdd_dev_lean_line_parts to choose between
-// them at run time, for tools/lean_line_ab.py's per-part timings.
-#ifdef FDD_LEAN_LINE_DEV
-static int g_lean_line_parts = 0; // 0: the choice of the release build
-extern "C" int fdd_dev_lean_line_parts(int parts)
-{
-    if (parts != 0 && parts != kLeanTerms && parts != (kLeanTerms | kLeanResident)) return FDD_ERR_UNSUPPORTED;
-    g_lean_line_parts = parts;
-    return 0;
-}
-#endif
-
-template <typename T, int kLean>
-int launch_lines_lean_t(T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const GPtrsT<T> &g, const int *elem_offset, const int *factor_elem, int num_elements, void *stream)
-{
-    if (factor_elem) return launch_lines_t<T, true, kLean>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, factor_elem, num_elements, stream);
-    return launch_lines_t<T, false, kLean>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, nullptr, num_elements, stream);
-}
-
-template <typename T>
-int lines_lean_dispatch(T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const T *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream)
-{
-    FDD_REQUIRE(num_elements >= 0);
-    if (poly_degree != 7 || diag != 1)
-    {
-        fdd_set_error("the lean line form of the stiffness kernel supports poly_degree 7 on three factor arrays (diag = 1) only, got poly_degree %d, diag = %d", poly_degree, diag);
-        return FDD_ERR_UNSUPPORTED;
-    }
-    if (num_elements == 0) return 0;
-    FDD_REQUIRE(Au != nullptr && u != nullptr && D_hat != nullptr && G != nullptr);
-    GPtrsT<T> g;
-    for (int k = 0; k < FDD_NUM_GEOM_FACTS; k++) g.g[k] = nullptr;
-    for (int k = 0; k < 3; k++)
-    {
-        FDD_REQUIRE(G[k] != nullptr);
-        g.g[k] = G[k];
-    }
+    if (int rc = fdd_three_factors(g, G)) return rc;
+    if (entry != LineEntry::lean) return launch_lines_t<T, 0>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, entry == LineEntry::shared ? factor_elem : nullptr, num_elements, stream);
     constexpr int kParts = sizeof(T) == 8 ? (kLeanTerms | kLeanResident) : kLeanTerms;
 #ifdef FDD_LEAN_LINE_DEV
     constexpr int kOther = kParts ^ kLeanResident;
-    if (g_lean_line_parts == kOther) return launch_lines_lean_t<T, kOther>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, factor_elem, num_elements, stream);
+    if (g_lean_line_parts == kOther) return launch_lines_t<T, kOther>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, factor_elem, num_elements, stream);
 #endif
-    return launch_lines_lean_t<T, kParts>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, factor_elem, num_elements, stream);
+    return launch_lines_t<T, kParts>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, factor_elem, num_elements, stream);
 }
 
 // ---- factor blocks that repeat from element to element (the kShared line instance) ----
@@ -1138,10 +1098,9 @@ int launch_fused_affine_t(T *Au, const T *u, const int *point_dof, const double 
     for (int k = 0; k < FDD_NUM_GEOM_FACTS; k++) g.g[k] = nullptr;
     g.g[0] = elem_factors;
     g.g[1] = gll_weights;
-    if (point_dof)
-        hipLaunchKernelGGL((fused_stiffness_kernel_t<T, n, true, true, true>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements);
-    else
-        hipLaunchKernelGGL((fused_stiffness_kernel_t<T, n, false, true, true>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements);
+    fdd_for_bool(point_dof != nullptr, [&](auto gather) {
+        hipLaunchKernelGGL((fused_stiffness_kernel_t<T, n, decltype(gather)::value, true, true>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements);
+    });
     FDD_LAUNCH_CHECK();
     return 0;
 }
@@ -1152,111 +1111,10 @@ int fused_dispatch_affine(T *Au, const T *u, const int *point_dof, const double 
     FDD_REQUIRE(num_elements >= 0);
     if (num_elements == 0) return 0;
     FDD_REQUIRE(Au != nullptr && u != nullptr && D_hat != nullptr && elem_factors != nullptr && gll_weights != nullptr);
-    switch (poly_degree + 1)
-    {
-#define FDD_AFFINE_CASE(N_) \
-    case N_: return launch_fused_affine_t<T, N_>(Au, u, point_dof, u_scale, D_hat, elem_factors, gll_weights, elem_offset, num_elements, stream);
-        FDD_AFFINE_CASE(2)
-        FDD_AFFINE_CASE(3)
-        FDD_AFFINE_CASE(4)
-        FDD_AFFINE_CASE(5)
-        FDD_AFFINE_CASE(6)
-        FDD_AFFINE_CASE(7)
-        FDD_AFFINE_CASE(8)
-        FDD_AFFINE_CASE(9)
-        FDD_AFFINE_CASE(10)
-        FDD_AFFINE_CASE(11)
-        FDD_AFFINE_CASE(12)
-        FDD_AFFINE_CASE(13)
-        FDD_AFFINE_CASE(14)
-        FDD_AFFINE_CASE(15)
-        FDD_AFFINE_CASE(16)
-#undef FDD_AFFINE_CASE
-    default:
-        fdd_set_error("fused stiffness kernel supports poly_degree 1..15, got %d", poly_degree);
-        return FDD_ERR_UNSUPPORTED;
-    }
-}
-
-template <int n>
-int launch_fused(double *Au, const double *u, const int *point_dof, const double *u_scale, const double *D_hat, const GPtrs &G, const int *elem_offset, int num_elements, void *stream)
-{
-    GPtrsT<double> g;
-    for (int k = 0; k < FDD_NUM_GEOM_FACTS; k++) g.g[k] = G.g[k];
-    return launch_fused_t<double, n>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-}
-
-// the single-precision form: gather-on-load only (the preconditioner's dof-space solve)
-int fused_dispatch_f32(float *Au, const float *u, const int *point_dof, const double *u_scale, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
-{
-    FDD_REQUIRE(num_elements >= 0);
-    if (num_elements == 0) return 0;
-    FDD_REQUIRE(Au != nullptr && u != nullptr && D_hat != nullptr && G != nullptr);
-    GPtrsT<float> g;
-    for (int k = 0; k < FDD_NUM_GEOM_FACTS; k++)
-    {
-        FDD_REQUIRE(G[k] != nullptr);
-        g.g[k] = G[k];
-    }
-    switch (poly_degree + 1)
-    {
-#define FDD_F32_CASE(N_) \
-    case N_: return launch_fused_t<float, N_>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-        FDD_F32_CASE(2)
-        FDD_F32_CASE(3)
-        FDD_F32_CASE(4)
-        FDD_F32_CASE(5)
-        FDD_F32_CASE(6)
-        FDD_F32_CASE(7)
-        FDD_F32_CASE(8)
-        FDD_F32_CASE(9)
-        FDD_F32_CASE(10)
-        FDD_F32_CASE(11)
-        FDD_F32_CASE(12)
-        FDD_F32_CASE(13)
-        FDD_F32_CASE(14)
-        FDD_F32_CASE(15)
-        FDD_F32_CASE(16)
-#undef FDD_F32_CASE
-    default:
-        fdd_set_error("fused stiffness kernel supports poly_degree 1..15, got %d", poly_degree);
-        return FDD_ERR_UNSUPPORTED;
-    }
-}
-
-int fused_dispatch(double *Au, const double *u, const int *point_dof, const double *u_scale, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
-{
-    FDD_REQUIRE(num_elements >= 0);
-    if (num_elements == 0) return 0;
-    FDD_REQUIRE(Au != nullptr && u != nullptr && D_hat != nullptr && G != nullptr);
-    GPtrs g;
-    for (int k = 0; k < FDD_NUM_GEOM_FACTS; k++)
-    {
-        FDD_REQUIRE(G[k] != nullptr);
-        g.g[k] = G[k];
-    }
-
-    switch (poly_degree + 1)
-    {
-    case 2: return launch_fused<2>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 3: return launch_fused<3>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 4: return launch_fused<4>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 5: return launch_fused<5>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 6: return launch_fused<6>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 7: return launch_fused<7>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 8: return launch_fused<8>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 9: return launch_fused<9>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 10: return launch_fused<10>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 11: return launch_fused<11>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 12: return launch_fused<12>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 13: return launch_fused<13>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 14: return launch_fused<14>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 15: return launch_fused<15>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 16: return launch_fused<16>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    default:
-        fdd_set_error("fused stiffness kernel supports poly_degree 1..15, got %d (use the two-launch form)", poly_degree);
-        return FDD_ERR_UNSUPPORTED;
-    }
+    int rc = 0;
+    if (fdd_for_n<2, 16>(poly_degree + 1, [&](auto n) { rc = launch_fused_affine_t<T, decltype(n)::value>(Au, u, point_dof, u_scale, D_hat, elem_factors, gll_weights, elem_offset, num_elements, stream); })) return rc;
+    fdd_set_error("fused stiffness kernel supports poly_degree 1..15, got %d", poly_degree);
+    return FDD_ERR_UNSUPPORTED;
 }
 
 // ---------------------------------------------------------------------------
@@ -1377,25 +1235,21 @@ int launch_fused_2d(double *Au, const double *u, const double *D_hat, const GPtr
 {
     constexpr int epb = kBlock / (n * n);
     const int groups = (num_elements + epb - 1) / epb;
-    static const bool nt_store = fdd_env_int("FDD_TUNE_STIFFNESS_NT_STORE", 1) != 0;
     static const int per_block = fdd_env_int("FDD_TUNE_STIFFNESS_2D_GROUPS", 4);
-#define FDD_2D_LAUNCH(K_) \
-    do \
-    { \
-        const int grid = (groups + K_ - 1) / K_; \
-        if (nt_store) \
-            hipLaunchKernelGGL((fused_stiffness_2d_kernel<n, K_, true>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, D_hat, G, elem_offset, num_elements); \
-        else \
-            hipLaunchKernelGGL((fused_stiffness_2d_kernel<n, K_, false>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, D_hat, G, elem_offset, num_elements); \
-    } while (0)
+    auto launch = [&](auto per) {
+        constexpr int K = decltype(per)::value;
+        const int grid = (groups + K - 1) / K;
+        fdd_for_bool(stiffness_nt_store(), [&](auto nt) {
+            hipLaunchKernelGGL((fused_stiffness_2d_kernel<n, K, decltype(nt)::value>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, D_hat, G, elem_offset, num_elements);
+        });
+    };
     // few elements: one group per workgroup keeps more workgroups in the launch
     if (per_block >= 4 && groups >= 4 * 2048)
-        FDD_2D_LAUNCH(4);
+        launch(std::integral_constant<int, 4>{});
     else if (per_block >= 2 && groups >= 2 * 2048)
-        FDD_2D_LAUNCH(2);
+        launch(std::integral_constant<int, 2>{});
     else
-        FDD_2D_LAUNCH(1);
-#undef FDD_2D_LAUNCH
+        launch(std::integral_constant<int, 1>{});
     FDD_LAUNCH_CHECK();
     return 0;
 }
@@ -1408,30 +1262,10 @@ int fused_dispatch_2d(double *Au, const double *u, const double *D_hat, const do
     GPtrs g;
     for (int k = 0; k < FDD_NUM_GEOM_FACTS; k++) g.g[k] = G[k]; // 2-D reads G[0] = G11, G[1] = G22, G[2] = G12 only
     FDD_REQUIRE(g.g[0] != nullptr && g.g[1] != nullptr && g.g[2] != nullptr);
-    switch (poly_degree + 1)
-    {
-#define FDD_2D_CASE(N_) \
-    case N_: return launch_fused_2d<N_>(Au, u, D_hat, g, elem_offset, num_elements, stream);
-        FDD_2D_CASE(2)
-        FDD_2D_CASE(3)
-        FDD_2D_CASE(4)
-        FDD_2D_CASE(5)
-        FDD_2D_CASE(6)
-        FDD_2D_CASE(7)
-        FDD_2D_CASE(8)
-        FDD_2D_CASE(9)
-        FDD_2D_CASE(10)
-        FDD_2D_CASE(11)
-        FDD_2D_CASE(12)
-        FDD_2D_CASE(13)
-        FDD_2D_CASE(14)
-        FDD_2D_CASE(15)
-        FDD_2D_CASE(16)
-#undef FDD_2D_CASE
-    default:
-        fdd_set_error("fused 2-D stiffness kernel supports poly_degree 1..15, got %d (use the two-launch form)", poly_degree);
-        return FDD_ERR_UNSUPPORTED;
-    }
+    int rc = 0;
+    if (fdd_for_n<2, 16>(poly_degree + 1, [&](auto n) { rc = launch_fused_2d<decltype(n)::value>(Au, u, D_hat, g, elem_offset, num_elements, stream); })) return rc;
+    fdd_set_error("fused 2-D stiffness kernel supports poly_degree 1..15, got %d (use the two-launch form)", poly_degree);
+    return FDD_ERR_UNSUPPORTED;
 }
 
 int fill_level_table(LevelTable &T, const double *const *D_hat_ptr, const int *poly_degree, int num_levels)
@@ -1485,12 +1319,12 @@ int fdd_dom_stiffness_matrix_2(double *Au, const double *const GDu[3], const dou
 
 int fdd_dom_stiffness_matrix(double *Au, const double *u, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], int num_elements, int poly_degree, void *stream)
 {
-    return fused_dispatch(Au, u, nullptr, nullptr, D_hat, G, nullptr, num_elements, poly_degree, stream);
+    return fused_dispatch<double>(Au, u, nullptr, nullptr, D_hat, G, nullptr, num_elements, poly_degree, stream);
 }
 
 int fdd_sub_stiffness_matrix(double *Au, const double *u, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
 {
-    return fused_dispatch(Au, u, nullptr, nullptr, D_hat, G, elem_offset, num_elements, poly_degree, stream);
+    return fused_dispatch<double>(Au, u, nullptr, nullptr, D_hat, G, elem_offset, num_elements, poly_degree, stream);
 }
 
 int fdd_stiffness_matrix_2d(double *Au, const double *u, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
@@ -1501,13 +1335,13 @@ int fdd_stiffness_matrix_2d(double *Au, const double *u, const double *D_hat, co
 int fdd_sub_stiffness_matrix_gather(double *Au, const double *v, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
 {
     FDD_REQUIRE(point_dof != nullptr);
-    return fused_dispatch(Au, v, point_dof, nullptr, D_hat, G, elem_offset, num_elements, poly_degree, stream);
+    return fused_dispatch<double>(Au, v, point_dof, nullptr, D_hat, G, elem_offset, num_elements, poly_degree, stream);
 }
 
 int fdd_sub_stiffness_matrix_gather_scaled(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
 {
     FDD_REQUIRE(point_dof != nullptr);
-    return fused_dispatch(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, num_elements, poly_degree, stream);
+    return fused_dispatch<double>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, num_elements, poly_degree, stream);
 }
 
 int fdd_stiffness_matrix_affine(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *elem_factors, const double *gll_weights, const int *elem_offset, int num_elements, int poly_degree, void *stream)
@@ -1517,51 +1351,42 @@ int fdd_stiffness_matrix_affine(double *Au, const double *v, const double *v_sca
 
 int fdd_stiffness_matrix_diag(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
 {
-    return fused_dispatch_diag<double>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, num_elements, poly_degree, stream);
+    return fused_dispatch<double, true>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, num_elements, poly_degree, stream);
 }
 
 int fdd_stiffness_matrix_diag_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
 {
-    return fused_dispatch_diag<float>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, num_elements, poly_degree, stream);
+    return fused_dispatch<float, true>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, num_elements, poly_degree, stream);
 }
 
 int fdd_stiffness_matrix_lines(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, int diag, void *stream)
 {
-    return lines_dispatch<double>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, nullptr, false, num_elements, poly_degree, diag, stream);
+    return lines_dispatch<double>(LineEntry::streamed, Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, nullptr, num_elements, poly_degree, diag, stream);
 }
 
 int fdd_stiffness_matrix_lines_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, int diag, void *stream)
 {
-    return lines_dispatch<float>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, nullptr, false, num_elements, poly_degree, diag, stream);
-}
-
-static int lines_shared_diag_only(int diag)
-{
-    if (diag == 1) return 0;
-    fdd_set_error("the shared-block line form of the stiffness kernel exists on three factor arrays only (diag = 1), got diag = %d", diag);
-    return FDD_ERR_UNSUPPORTED;
+    return lines_dispatch<float>(LineEntry::streamed, Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, nullptr, num_elements, poly_degree, diag, stream);
 }
 
 int fdd_stiffness_matrix_lines_shared(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream)
 {
-    if (int rc = lines_shared_diag_only(diag)) return rc;
-    return lines_dispatch<double>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, factor_elem, true, num_elements, poly_degree, diag, stream);
+    return lines_dispatch<double>(LineEntry::shared, Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, factor_elem, num_elements, poly_degree, diag, stream);
 }
 
 int fdd_stiffness_matrix_lines_shared_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream)
 {
-    if (int rc = lines_shared_diag_only(diag)) return rc;
-    return lines_dispatch<float>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, factor_elem, true, num_elements, poly_degree, diag, stream);
+    return lines_dispatch<float>(LineEntry::shared, Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, factor_elem, num_elements, poly_degree, diag, stream);
 }
 
 int fdd_stiffness_matrix_lines_lean(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream)
 {
-    return lines_lean_dispatch<double>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, factor_elem, num_elements, poly_degree, diag, stream);
+    return lines_dispatch<double>(LineEntry::lean, Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, factor_elem, num_elements, poly_degree, diag, stream);
 }
 
 int fdd_stiffness_matrix_lines_lean_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream)
 {
-    return lines_lean_dispatch<float>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, factor_elem, num_elements, poly_degree, diag, stream);
+    return lines_dispatch<float>(LineEntry::lean, Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, factor_elem, num_elements, poly_degree, diag, stream);
 }
 
 constexpr int kFactorBlockGrid = 1 << 20; // workgroups; beyond it a workgroup takes several elements in turn
@@ -1573,13 +1398,7 @@ static int factor_block_args(GPtrs &g, const double *const G[FDD_NUM_GEOM_FACTS]
         fdd_set_error("the factor-block entries support poly_degree 1..15, got %d", poly_degree);
         return FDD_ERR_UNSUPPORTED;
     }
-    for (int k = 0; k < FDD_NUM_GEOM_FACTS; k++) g.g[k] = nullptr;
-    for (int k = 0; k < 3; k++)
-    {
-        FDD_REQUIRE(G[k] != nullptr);
-        g.g[k] = G[k];
-    }
-    return 0;
+    return fdd_three_factors(g, G);
 }
 
 int fdd_stiffness_factor_block_hash(unsigned long long *out, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
@@ -1647,7 +1466,7 @@ int fdd_stiffness_matrix_affine_f32(float *Au, const float *v, const double *v_s
 int fdd_sub_stiffness_matrix_gather_scaled_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
 {
     FDD_REQUIRE(point_dof != nullptr);
-    return fused_dispatch_f32(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, num_elements, poly_degree, stream);
+    return fused_dispatch<float>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, num_elements, poly_degree, stream);
 }
 
 int fdd_sub_stiffness_matrix_1(double *const GDu[3], const double *u, const double *const *D_hat_ptr, const int *offset, const int *vert, const int *level, const int *poly_degree, int num_levels, const double *const G[FDD_NUM_GEOM_FACTS], int num_points, int dim, void *stream)

@@ -425,6 +425,16 @@ int launch_mfma(double *Au, const double *u, const int *point_dof, const double 
     return 0;
 }
 
+// the instance for the degree, after each entry's own checks
+template <bool kAffine, bool kDiag>
+int mfma_dispatch_n(double *Au, const double *u, const int *point_dof, const double *u_scale, const double *D_hat, const GPtrs &g, const int *elem_offset, int num_elements, int poly_degree, void *stream)
+{
+    int rc = 0;
+    if (fdd_for_n<9, 16>(poly_degree + 1, [&](auto n) { rc = launch_mfma<decltype(n)::value, kAffine, kDiag>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream); })) return rc;
+    fdd_set_error("fp64-MFMA stiffness kernel supports poly_degree 8..15, got %d", poly_degree);
+    return FDD_ERR_UNSUPPORTED;
+}
+
 int mfma_dispatch_affine(double *Au, const double *u, const int *point_dof, const double *u_scale, const double *D_hat, const double *elem_factors, const double *gll_weights, const int *elem_offset, int num_elements, int poly_degree, void *stream)
 {
     FDD_REQUIRE(num_elements >= 0);
@@ -434,76 +444,28 @@ int mfma_dispatch_affine(double *Au, const double *u, const int *point_dof, cons
     for (int k = 0; k < FDD_NUM_GEOM_FACTS; k++) g.g[k] = nullptr;
     g.g[0] = elem_factors;
     g.g[1] = gll_weights;
-    switch (poly_degree + 1)
-    {
-    case 9: return launch_mfma<9, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 10: return launch_mfma<10, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 11: return launch_mfma<11, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 12: return launch_mfma<12, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 13: return launch_mfma<13, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 14: return launch_mfma<14, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 15: return launch_mfma<15, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 16: return launch_mfma<16, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    default:
-        fdd_set_error("fp64-MFMA stiffness kernel supports poly_degree 8..15, got %d", poly_degree);
-        return FDD_ERR_UNSUPPORTED;
-    }
+    return mfma_dispatch_n<true, false>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, poly_degree, stream);
 }
 
-// the kDiag instances: G[3..5] are not passed on (never dereferenced)
-int mfma_dispatch_diag(double *Au, const double *u, const int *point_dof, const double *u_scale, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
-{
-    FDD_REQUIRE(num_elements >= 0);
-    if (num_elements == 0) return 0;
-    FDD_REQUIRE(Au != nullptr && u != nullptr && D_hat != nullptr && G != nullptr && Au != u);
-    GPtrs g;
-    for (int k = 0; k < FDD_NUM_GEOM_FACTS; k++) g.g[k] = nullptr;
-    for (int k = 0; k < 3; k++)
-    {
-        FDD_REQUIRE(G[k] != nullptr);
-        g.g[k] = G[k];
-    }
-    switch (poly_degree + 1)
-    {
-    case 9: return launch_mfma<9, false, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 10: return launch_mfma<10, false, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 11: return launch_mfma<11, false, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 12: return launch_mfma<12, false, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 13: return launch_mfma<13, false, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 14: return launch_mfma<14, false, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 15: return launch_mfma<15, false, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 16: return launch_mfma<16, false, true>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    default:
-        fdd_set_error("fp64-MFMA stiffness kernel supports poly_degree 8..15, got %d", poly_degree);
-        return FDD_ERR_UNSUPPORTED;
-    }
-}
-
+// kDiag: the three-array instances; G[3..5] are not passed on (never dereferenced)
+template <bool kDiag>
 int mfma_dispatch(double *Au, const double *u, const int *point_dof, const double *u_scale, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
 {
     FDD_REQUIRE(num_elements >= 0);
     if (num_elements == 0) return 0;
     FDD_REQUIRE(Au != nullptr && u != nullptr && D_hat != nullptr && G != nullptr && Au != u);
     GPtrs g;
-    for (int k = 0; k < FDD_NUM_GEOM_FACTS; k++)
+    if constexpr (kDiag)
     {
-        FDD_REQUIRE(G[k] != nullptr);
-        g.g[k] = G[k];
+        if (int rc = fdd_three_factors(g, G)) return rc;
     }
-    switch (poly_degree + 1)
-    {
-    case 9: return launch_mfma<9>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 10: return launch_mfma<10>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 11: return launch_mfma<11>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 12: return launch_mfma<12>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 13: return launch_mfma<13>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 14: return launch_mfma<14>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 15: return launch_mfma<15>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    case 16: return launch_mfma<16>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, stream);
-    default:
-        fdd_set_error("fp64-MFMA stiffness kernel supports poly_degree 8..15, got %d", poly_degree);
-        return FDD_ERR_UNSUPPORTED;
-    }
+    else
+        for (int k = 0; k < FDD_NUM_GEOM_FACTS; k++)
+        {
+            FDD_REQUIRE(G[k] != nullptr);
+            g.g[k] = G[k];
+        }
+    return mfma_dispatch_n<false, kDiag>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, num_elements, poly_degree, stream);
 }
 
 } // namespace
@@ -512,7 +474,7 @@ extern "C" {
 
 int fdd_stiffness_matrix_mfma(double *Au, const double *u, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
 {
-    return mfma_dispatch(Au, u, nullptr, nullptr, D_hat, G, elem_offset, num_elements, poly_degree, stream);
+    return mfma_dispatch<false>(Au, u, nullptr, nullptr, D_hat, G, elem_offset, num_elements, poly_degree, stream);
 }
 
 int fdd_stiffness_matrix_mfma_affine(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *elem_factors, const double *gll_weights, const int *elem_offset, int num_elements, int poly_degree, void *stream)
@@ -522,13 +484,13 @@ int fdd_stiffness_matrix_mfma_affine(double *Au, const double *v, const double *
 
 int fdd_stiffness_matrix_mfma_diag(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
 {
-    return mfma_dispatch_diag(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, num_elements, poly_degree, stream);
+    return mfma_dispatch<true>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, num_elements, poly_degree, stream);
 }
 
 int fdd_stiffness_matrix_mfma_gather(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream)
 {
     FDD_REQUIRE(point_dof != nullptr);
-    return mfma_dispatch(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, num_elements, poly_degree, stream);
+    return mfma_dispatch<false>(Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, num_elements, poly_degree, stream);
 }
 
 } // extern "C"

@@ -9,7 +9,10 @@
 #define FDD_ELEMENT_OPERATOR_HPP
 
 #include <algorithm>
+#include <array>
 #include <cstring>
+#include <stdexcept>
+#include <string>
 #include <type_traits>
 #include <unordered_map>
 #include <vector>
@@ -43,47 +46,123 @@ struct LevelList
     // float copies for the single-precision inner solve (Subdomain::prepare_single_precision); not allocated before
     memory G32[NUM_GEOM_FACTS], D_hat32;
     // affine elements (an option, set_affine_geometry): six numbers per element + the GLL weights stand for the factor arrays
-    bool affine = false;            // in use
+    bool affine = false;            // in use; only 3-D lists of degree <= 15 (detect_affine checks no other)
     double affine_deviation = -1.0; // largest relative deviation found (-1: not checked)
     memory affine_c, affine_w, affine_c32, affine_w32;
     // are the three off-diagonal factor arrays G[3..5] zero at every point of the list (detect_zero_factors, once, when the
-    // factor pointers are set)?  Then the kernel that does not stream them applies; G32 are casts of the same arrays
+    // factor pointers are set)?  Then the kernel that does not stream them applies; G32 are casts of the same arrays.
+    // Only 3-D lists of degree <= 15
     bool offdiag_zero = false;
     // do the list's elements share their G[0..2] blocks with a few representatives, bit for bit (detect_shared_blocks, once,
     // after the check above)?  factor_elem[e]: the lowest element of the list that holds element e's block; G32 are casts
-    // of the same arrays, so equal double blocks are equal float blocks and the one map serves both precisions
+    // of the same arrays, so equal double blocks are equal float blocks and the one map serves both precisions.
+    // Only with offdiag_zero
     bool shared_blocks = false;
     int factor_classes = 0; // distinct blocks found (0: not looked for)
     memory factor_elem;     // device ints, allocated only where shared_blocks holds
     // does the table behind D_hat / D_hat32 meet the lean line instance's conditions (check_lean_table, on the host array
-    // each upload is made from; each precision on its own)?
+    // each upload is made from; each precision on its own)?  Only at degree 7
     bool lean_D_hat = false, lean_D_hat32 = false;
 
     size_t num_points() const { return (size_t)num_elements * (poly_degree + 1) * (poly_degree + 1) * (dim == 3 ? poly_degree + 1 : 1); }
 };
 
-// the matrix-core kernels exist in double only, for 3-D elements of degree 11..15
-template <typename Real>
-inline bool on_matrix_cores(const LevelList &ll, bool mfma_enabled)
+// ---- the flags that choose between the stiffness kernels ----
+// One value per Domain and per Subdomain.  A flag is on by default where the loaded kernel library exports the flag's
+// entries, and set_stiffness_flag refuses to turn on one whose entries are missing: that function is the only place that
+// keeps "a flag that is on has its entries", and choose_stiffness below relies on it without asking the weak symbols.
+// None of the flags empties anything that hangs on the operator (projection basis, point-Jacobi diagonal, Chebyshev bound):
+struct StiffnessFlags
 {
-    return std::is_same<Real, double>::value and mfma_enabled and ll.dim == 3 and ll.poly_degree >= 11 and ll.poly_degree <= 15;
+    // 3-D lists of degree 11..15 run on the fp64 matrix cores, in double (tolerance-level parity, fdd_hip.h); no entry is
+    // asked for: the matrix-core six-array entries are not weak
+    bool mfma_stiffness;
+    // lists whose three off-diagonal factor arrays are zero at every point (detect_zero_factors) run the kernel that streams
+    // three arrays; 0: six arrays everywhere.  The operator's values do not change -- what is left out is the addition of
+    // exact zeros -- so the projection basis, the point-Jacobi diagonal and the Chebyshev bound stay
+    bool skip_zero_factors;
+    // the same for lists on the matrix cores: their three-array instance, while "skip_zero_factors" and "mfma_stiffness"
+    // are both on; 0: those lists stream six arrays.  The values are the six-array matrix-core kernel's, to the sign of a
+    // zero, so nothing is emptied here either
+    bool mfma_skip_zero_factors;
+    // 3-D degree-7 lists on the three-array kernel run its line form (an element is one wavefront); 0: the slab form.  The
+    // six-array line form measured no faster than the slab form in either precision (172.9 against 169.7 and 94.2 against
+    // 93.6 us per launch at 32^3 elements), so those lists keep the slab form and the kernel library compiles no six-array
+    // line instance.  Same bits either way, so nothing that hangs on the operator is emptied
+    bool line_stiffness;
+    // lists on the line form whose elements share their factor blocks bit for bit (detect_shared_blocks) read the few
+    // distinct blocks instead of streaming every copy; 0: every element streams its own.  The words read are the same, so
+    // are all bits
+    bool shared_factor_blocks;
+    // lists on the line form whose uploaded D_hat has a zero interior diagonal and is its own negated mirror image
+    // (check_lean_table) run the lean instance, which leaves out the addition of exact zeros; 0: the parent instances.  The
+    // values are the parent's, to the sign of a zero, so nothing that hangs on the operator is emptied
+    bool lean_line_stiffness;
+
+    StiffnessFlags();
+};
+
+// flag name -> member and the entries it needs, in the order in which a missing one is named
+struct StiffnessFlagRow
+{
+    const char *name;
+    bool StiffnessFlags::*member;
+    struct
+    {
+        const void *fn;
+        const char *name;
+    } entries[5]; // ends at a null name
+};
+
+inline const std::array<StiffnessFlagRow, 6> &stiffness_flag_table()
+{
+#define FDD_ENTRY(name) {(const void *)&name, #name}
+    static const std::array<StiffnessFlagRow, 6> table = {{
+        {"mfma_stiffness", &StiffnessFlags::mfma_stiffness, {}},
+        {"skip_zero_factors", &StiffnessFlags::skip_zero_factors, {FDD_ENTRY(fdd_stiffness_offdiag_zero), FDD_ENTRY(fdd_stiffness_matrix_diag), FDD_ENTRY(fdd_stiffness_matrix_diag_f32)}},
+        // with the check that sets LevelList::offdiag_zero
+        {"mfma_skip_zero_factors", &StiffnessFlags::mfma_skip_zero_factors, {FDD_ENTRY(fdd_stiffness_matrix_mfma_diag), FDD_ENTRY(fdd_stiffness_offdiag_zero), FDD_ENTRY(fdd_stiffness_matrix_diag), FDD_ENTRY(fdd_stiffness_matrix_diag_f32)}},
+        {"line_stiffness", &StiffnessFlags::line_stiffness, {FDD_ENTRY(fdd_stiffness_matrix_lines), FDD_ENTRY(fdd_stiffness_matrix_lines_f32)}},
+        // with the two entries that establish which blocks repeat
+        {"shared_factor_blocks", &StiffnessFlags::shared_factor_blocks, {FDD_ENTRY(fdd_stiffness_matrix_lines_shared), FDD_ENTRY(fdd_stiffness_matrix_lines_shared_f32), FDD_ENTRY(fdd_stiffness_factor_block_hash), FDD_ENTRY(fdd_stiffness_factor_block_verify)}},
+        {"lean_line_stiffness", &StiffnessFlags::lean_line_stiffness, {FDD_ENTRY(fdd_stiffness_matrix_lines_lean), FDD_ENTRY(fdd_stiffness_matrix_lines_lean_f32)}},
+    }};
+#undef FDD_ENTRY
+    return table;
 }
 
-// the first entry of the three-array stiffness kernel the loaded kernel library does not export, or nullptr
-inline const char *missing_zero_factor_entry()
+inline const StiffnessFlagRow *stiffness_flag_row(const std::string &flag)
 {
-    if (&fdd_stiffness_offdiag_zero == nullptr) return "fdd_stiffness_offdiag_zero";
-    if (&fdd_stiffness_matrix_diag == nullptr) return "fdd_stiffness_matrix_diag";
-    if (&fdd_stiffness_matrix_diag_f32 == nullptr) return "fdd_stiffness_matrix_diag_f32";
+    for (const StiffnessFlagRow &row : stiffness_flag_table())
+        if (flag == row.name) return &row;
     return nullptr;
 }
 
-// the entry of the matrix-core kernel on three factor arrays, where the loaded kernel library does not export it, or nullptr
-inline const char *missing_mfma_zero_factor_entry()
+// the first entry the flag needs that the loaded kernel library does not export, or nullptr
+inline const char *missing_stiffness_entry(const StiffnessFlagRow &row)
 {
-    if (&fdd_stiffness_matrix_mfma_diag == nullptr) return "fdd_stiffness_matrix_mfma_diag";
-    return missing_zero_factor_entry(); // the check that sets LevelList::offdiag_zero
+    for (const auto &e : row.entries)
+        if (e.name and e.fn == nullptr) return e.name;
+    return nullptr;
 }
+inline const char *missing_stiffness_entry(const char *flag) { return missing_stiffness_entry(*stiffness_flag_row(flag)); }
+
+inline StiffnessFlags::StiffnessFlags()
+{
+    for (const StiffnessFlagRow &row : stiffness_flag_table()) this->*row.member = missing_stiffness_entry(row) == nullptr;
+}
+
+// false: not a stiffness flag.  Throws where the flag is to be turned on and an entry it needs is missing
+inline bool set_stiffness_flag(StiffnessFlags &flags, const std::string &flag, bool on)
+{
+    const StiffnessFlagRow *row = stiffness_flag_row(flag);
+    if (not row) return false;
+    if (on)
+        if (const char *missing = missing_stiffness_entry(*row)) throw std::runtime_error(flag + " needs " + missing + ", which the loaded kernel library does not export");
+    flags.*row->member = on;
+    return true;
+}
+inline bool stiffness_flag(const StiffnessFlags &flags, const char *flag) { return flags.*stiffness_flag_row(flag)->member; }
 
 // ---- factor arrays that are identically zero (flag "skip_zero_factors") ----
 // On a mesh whose elements have orthogonal axes (every box, every rectilinear grid) G[3..5] are 0.0 at every point.
@@ -91,11 +170,11 @@ inline const char *missing_mfma_zero_factor_entry()
 // is on) the list runs the kernel that streams G[0..2] only.  Unlike the affine option the arithmetic left out is the
 // addition of exact zeros: the operator's values are the same, to the sign of a zero.  Only 3-D lists of degree <= 15 are
 // checked (the 2-D and two-launch forms keep six arrays); without the entries nothing is, and nothing switches.  A list that
-// runs on the matrix cores takes their three-array instance (on_mfma_diag_kernel, flag "mfma_skip_zero_factors").
+// runs on the matrix cores takes their three-array instance (flag "mfma_skip_zero_factors").
 inline void detect_zero_factors(LevelList &ll)
 {
     ll.offdiag_zero = false;
-    if (ll.dim != 3 or ll.poly_degree > 15 or ll.num_elements == 0 or missing_zero_factor_entry()) return;
+    if (ll.dim != 3 or ll.poly_degree > 15 or ll.num_elements == 0 or missing_stiffness_entry("skip_zero_factors")) return;
     int flags[3] = {1, 1, 1};
     memory flags_dev = dev().malloc<int>(3);
     FDD_CALL(fdd_stiffness_offdiag_zero(flags_dev.as<int>(), ll.G, nullptr, ll.num_elements, ll.poly_degree, dev().stream));
@@ -104,53 +183,7 @@ inline void detect_zero_factors(LevelList &ll)
     ll.offdiag_zero = flags[0] == 0 and flags[1] == 0 and flags[2] == 0;
 }
 
-// does the list run the three-array kernel for this precision?  (affine, where switched on, takes precedence: see the callers)
-template <typename Real>
-inline bool on_diag_kernel(const LevelList &ll, bool mfma_enabled, bool skip_zero_factors)
-{
-    return skip_zero_factors and ll.offdiag_zero and not ll.affine and not on_matrix_cores<Real>(ll, mfma_enabled);
-}
-
-// does the list run the matrix-core kernel on three factor arrays?  Both flags: "skip_zero_factors" = 0 goes on meaning six
-// arrays everywhere.  The values are those of the six-array matrix-core kernel, to the sign of a zero.
-template <typename Real>
-inline bool on_mfma_diag_kernel(const LevelList &ll, bool mfma_enabled, bool skip_zero_factors, bool mfma_skip_zero_factors)
-{
-    return on_matrix_cores<Real>(ll, mfma_enabled) and skip_zero_factors and mfma_skip_zero_factors and ll.offdiag_zero and not ll.affine and missing_mfma_zero_factor_entry() == nullptr;
-}
-
-// ---- the line form of the stiffness kernel (flag "line_stiffness") ----
-// the first entry of the line form the loaded kernel library does not export, or nullptr
-inline const char *missing_line_stiffness_entry()
-{
-    if (&fdd_stiffness_matrix_lines == nullptr) return "fdd_stiffness_matrix_lines";
-    if (&fdd_stiffness_matrix_lines_f32 == nullptr) return "fdd_stiffness_matrix_lines_f32";
-    return nullptr;
-}
-
-// does the list run the line form for this precision, in the local and in the gather form alike?  3-D, degree 7 (an element
-// is one wavefront), not affine, not on the matrix cores, entry present, flag on -- and on the three-array kernel
-// (on_diag_kernel): the six-array line form measured no faster than the slab form in either precision (172.9 against 169.7
-// and 94.2 against 93.6 us per launch at 32^3 elements), so those lists keep the slab form and the kernel library compiles
-// no six-array line instance.  The line form gives the bits of the instance it replaces, so nothing that hangs on the
-// operator changes with the flag.
-template <typename Real>
-inline bool on_line_kernel(const LevelList &ll, bool mfma_enabled, bool skip_zero_factors, bool line_stiffness)
-{
-    return line_stiffness and ll.dim == 3 and ll.poly_degree == 7 and on_diag_kernel<Real>(ll, mfma_enabled, skip_zero_factors) and missing_line_stiffness_entry() == nullptr;
-}
-
 // ---- factor blocks that repeat from element to element (flag "shared_factor_blocks") ----
-// the first entry of the shared-block line instance and its detection the loaded kernel library does not export, or nullptr
-inline const char *missing_shared_factor_entry()
-{
-    if (&fdd_stiffness_matrix_lines_shared == nullptr) return "fdd_stiffness_matrix_lines_shared";
-    if (&fdd_stiffness_matrix_lines_shared_f32 == nullptr) return "fdd_stiffness_matrix_lines_shared_f32";
-    if (&fdd_stiffness_factor_block_hash == nullptr) return "fdd_stiffness_factor_block_hash";
-    if (&fdd_stiffness_factor_block_verify == nullptr) return "fdd_stiffness_factor_block_verify";
-    return nullptr;
-}
-
 // The distinct blocks of a shared list occupy at most this many bytes (85 of them at degree 7): a quarter of the 4 MiB of
 // L2 of one XCD, so that they stay there beside the streamed vectors.  A design bound from the cache size, not a tuned value.
 constexpr size_t shared_factor_bytes_limit = (size_t)1 << 20;
@@ -168,7 +201,7 @@ inline void detect_shared_blocks(LevelList &ll)
     ll.shared_blocks = false;
     ll.factor_classes = 0;
     ll.factor_elem.free();
-    if (not ll.offdiag_zero or ll.dim != 3 or ll.poly_degree > 15 or ll.num_elements == 0 or missing_shared_factor_entry()) return;
+    if (not ll.offdiag_zero or ll.dim != 3 or ll.poly_degree > 15 or ll.num_elements == 0 or missing_stiffness_entry("shared_factor_blocks")) return;
     const size_t ne = (size_t)ll.num_elements;
     std::vector<unsigned long long> hash(ne);
     memory hash_dev = dev().malloc<unsigned long long>(ne);
@@ -196,23 +229,7 @@ inline void detect_shared_blocks(LevelList &ll)
     ll.shared_blocks = true;
 }
 
-// does the list run the shared instance of the line form?  Only where it runs the line form at all, so every flag and
-// condition on_line_kernel looks at keeps its meaning and precedence.  Same bits as the streamed instance.
-template <typename Real>
-inline bool on_shared_line_kernel(const LevelList &ll, bool mfma_enabled, bool skip_zero_factors, bool line_stiffness, bool shared_factor_blocks)
-{
-    return shared_factor_blocks and ll.shared_blocks and on_line_kernel<Real>(ll, mfma_enabled, skip_zero_factors, line_stiffness) and missing_shared_factor_entry() == nullptr;
-}
-
 // ---- the lean instances of the line form (flag "lean_line_stiffness") ----
-// the first entry of the lean line instances the loaded kernel library does not export, or nullptr
-inline const char *missing_lean_line_entry()
-{
-    if (&fdd_stiffness_matrix_lines_lean == nullptr) return "fdd_stiffness_matrix_lines_lean";
-    if (&fdd_stiffness_matrix_lines_lean_f32 == nullptr) return "fdd_stiffness_matrix_lines_lean_f32";
-    return nullptr;
-}
-
 // What fdd_stiffness_matrix_lines_lean[_f32] asks of an 8 x 8 table, bit for bit: the interior diagonal is +-0.0 (either
 // sign, each entry on its own: gll::dgll writes +0.0 on all six) and everywhere else entry 63 - m has the bits of the negation
 // of entry m.  A NaN passes only with its mirror image's payload and the other sign.
@@ -246,194 +263,216 @@ inline void check_lean_table(LevelList &ll, const std::vector<double> &D)
     if (not ll.D_hat32.ptr()) check_lean_table32(ll, D);
 }
 
-// does the list run a lean instance of the line form (shared where on_shared_line_kernel holds, streamed otherwise)?  Only
-// where it runs the line form at all and its table in this precision passed the check; a table that did not keeps the parent
-// instance.  The parent's values, to the sign of a zero.
-template <typename Real>
-inline bool on_lean_line_kernel(const LevelList &ll, bool mfma_enabled, bool skip_zero_factors, bool line_stiffness, bool lean_line_stiffness)
+// ---- which kernel a list runs ----
+enum class StiffnessForm
 {
-    return lean_line_stiffness and (std::is_same<Real, float>::value ? ll.lean_D_hat32 : ll.lean_D_hat) and on_line_kernel<Real>(ll, mfma_enabled, skip_zero_factors, line_stiffness) and missing_lean_line_entry() == nullptr;
+    local, // Au = A_L u on element-local points (apply_local; double only)
+    gather // q = A_L (Q (s v)), Q read through an index array (apply_gather; 3-D lists of degree <= 15)
+};
+
+enum class StiffnessFamily
+{
+    two_launch, // the reference's two-launch form, degree above 15
+    fused_2d,
+    fused,      // six factor arrays
+    diag,       // three factor arrays, slab form
+    lines,      // three factor arrays, line form (degree 7); the only family with the attributes shared and lean
+    mfma,       // six arrays on the matrix cores
+    mfma_diag,  // three arrays on the matrix cores
+    affine,
+    mfma_affine
+};
+
+struct StiffnessChoice
+{
+    StiffnessFamily family;
+    bool shared = false, lean = false;
+
+    // what fddh_problem_*_info counts, asked of the gather form's choice
+    bool three_arrays() const { return family == StiffnessFamily::diag or family == StiffnessFamily::lines; } // not the matrix-core instance
+    bool mfma_three_arrays() const { return family == StiffnessFamily::mfma_diag; }
+    bool lines() const { return family == StiffnessFamily::lines; }
+    bool shared_lines() const { return lines() and shared; }
+    bool lean_lines() const { return lines() and lean; }
+};
+
+// The one decision, for both forms and both precisions.  in_place: Au == u (local form only).  Launches nothing, touches no
+// device memory and asks no weak symbol (StiffnessFlags); a handful of comparisons, made again at every launch.
+inline StiffnessChoice choose_stiffness(const LevelList &ll, const StiffnessFlags &flags, bool f32, StiffnessForm form, bool in_place = false)
+{
+    using F = StiffnessFamily;
+    const bool gather = form == StiffnessForm::gather;
+    // the matrix-core kernels exist in double only, for 3-D elements of degree 11..15: a float list never runs on them
+    const bool matrix_cores = not f32 and flags.mfma_stiffness and ll.dim == 3 and ll.poly_degree >= 11 and ll.poly_degree <= 15;
+    // the gather form takes affine first, whatever the other flags say
+    if (gather and ll.affine) return {matrix_cores ? F::mfma_affine : F::affine};
+    // the local form has no affine kernel: an affine list there runs six arrays
+    const bool three_arrays = flags.skip_zero_factors and ll.offdiag_zero and not ll.affine;
+    // the local matrix-core kernels need Au != u; in place, such a list runs six arrays off the matrix cores
+    if (matrix_cores and (gather or not in_place)) return {three_arrays and flags.mfma_skip_zero_factors ? F::mfma_diag : F::mfma};
+    if (three_arrays and not matrix_cores)
+    {
+        if (not(flags.line_stiffness and ll.dim == 3 and ll.poly_degree == 7)) return {F::diag};
+        // shared or streamed, a lean list or not: the two attributes do not look at each other, and each precision's lean
+        // verdict comes from the check of its own table
+        return {F::lines, flags.shared_factor_blocks and ll.shared_blocks, flags.lean_line_stiffness and (f32 ? ll.lean_D_hat32 : ll.lean_D_hat)};
+    }
+    if (gather or (ll.dim == 3 and ll.poly_degree <= 15)) return {F::fused};
+    return {ll.dim == 2 and ll.poly_degree <= 15 ? F::fused_2d : F::two_launch};
+}
+
+// The profile label and the bytes per point of every choice: the strings and numbers bench.py's kernel table keys on.  The
+// labels of the three-array instances are not "fused_stiffness_kernel..." / "mfma_stiffness_kernel...": the committed counters
+// bench.py matches by those prefixes are the six-array kernels'.  The line form counts the bytes of the instance it replaces
+// (lean: of its parent instance); a shared list's few factor blocks stay in cache, so u and Au (index and q) are what moves.
+// The gather form adds the gathered values to its total (apply_gather).  No label: no scope (the two-launch form).
+struct StiffnessProfile
+{
+    const char *label;
+    double bytes_per_point;
+};
+inline StiffnessProfile stiffness_profile(StiffnessForm form, const StiffnessChoice &c, bool f32)
+{
+    using F = StiffnessFamily;
+    static const struct
+    {
+        StiffnessForm form;
+        F family;
+        bool shared, lean;
+        const char *label, *label32;
+        double bytes, bytes32;
+    } table[] = {
+        {StiffnessForm::local, F::mfma_diag, false, false, "mfma_diag_stiffness_kernel", nullptr, 40.0, 0.0},
+        {StiffnessForm::local, F::mfma, false, false, "mfma_stiffness_kernel", nullptr, 64.0, 0.0},
+        {StiffnessForm::local, F::lines, false, false, "line_stiffness_kernel", nullptr, 40.0, 0.0},
+        {StiffnessForm::local, F::lines, true, false, "line_stiffness_kernel<shared>", nullptr, 16.0, 0.0},
+        {StiffnessForm::local, F::lines, false, true, "line_stiffness_kernel<lean>", nullptr, 40.0, 0.0},
+        {StiffnessForm::local, F::lines, true, true, "line_stiffness_kernel<shared,lean>", nullptr, 16.0, 0.0},
+        {StiffnessForm::local, F::diag, false, false, "diag_stiffness_kernel", nullptr, 40.0, 0.0},
+        {StiffnessForm::local, F::fused, false, false, "fused_stiffness_kernel", nullptr, 64.0, 0.0},
+        {StiffnessForm::local, F::fused_2d, false, false, "fused_stiffness_2d_kernel", nullptr, 40.0, 0.0},
+        {StiffnessForm::gather, F::affine, false, false, "fused_stiffness_kernel<gather,affine>", "fused_stiffness_kernel<gather,f32,affine>", 12.0, 8.0},
+        {StiffnessForm::gather, F::mfma_affine, false, false, "mfma_stiffness_kernel<gather,affine>", nullptr, 12.0, 0.0},
+        {StiffnessForm::gather, F::mfma_diag, false, false, "mfma_diag_stiffness_kernel<gather>", nullptr, 36.0, 0.0},
+        {StiffnessForm::gather, F::lines, false, false, "line_stiffness_kernel<gather>", "line_stiffness_kernel<gather,f32>", 36.0, 20.0},
+        {StiffnessForm::gather, F::lines, true, false, "line_stiffness_kernel<gather,shared>", "line_stiffness_kernel<gather,shared,f32>", 12.0, 8.0},
+        {StiffnessForm::gather, F::lines, false, true, "line_stiffness_kernel<gather,lean>", "line_stiffness_kernel<gather,f32,lean>", 36.0, 20.0},
+        {StiffnessForm::gather, F::lines, true, true, "line_stiffness_kernel<gather,shared,lean>", "line_stiffness_kernel<gather,shared,f32,lean>", 12.0, 8.0},
+        {StiffnessForm::gather, F::diag, false, false, "diag_stiffness_kernel<gather>", "diag_stiffness_kernel<gather,f32>", 36.0, 20.0},
+        {StiffnessForm::gather, F::fused, false, false, "fused_stiffness_kernel<gather>", "fused_stiffness_kernel<gather,f32>", 60.0, 32.0},
+        {StiffnessForm::gather, F::mfma, false, false, "mfma_stiffness_kernel<gather>", nullptr, 60.0, 0.0},
+    };
+    for (const auto &row : table)
+        if (row.form == form and row.family == c.family and row.shared == c.shared and row.lean == c.lean) return {f32 ? row.label32 : row.label, f32 ? row.bytes32 : row.bytes};
+    return {nullptr, 0.0};
+}
+
+// Where a list's arrays come from, by precision: the list's own in double, the float copies in single
+template <typename Real>
+struct ListArrays
+{
+    const Real *G[NUM_GEOM_FACTS], *D_hat, *affine_c, *affine_w;
+    explicit ListArrays(const LevelList &ll)
+    {
+        if constexpr (std::is_same<Real, float>::value)
+        {
+            for (int g = 0; g < NUM_GEOM_FACTS; g++) G[g] = ll.G32[g].as<float>();
+            D_hat = ll.D_hat32.as<float>(), affine_c = ll.affine_c32.as<float>(), affine_w = ll.affine_w32.as<float>();
+        }
+        else
+        {
+            for (int g = 0; g < NUM_GEOM_FACTS; g++) G[g] = ll.G[g];
+            D_hat = ll.D_hat, affine_c = ll.affine_c.as<double>(), affine_w = ll.affine_w.as<double>();
+        }
+    }
+};
+
+// an entry of the kernel library by precision
+template <typename Real, typename Entry64, typename Entry32>
+inline auto entry_of(Entry64 *entry, Entry32 *entry_f32)
+{
+    if constexpr (std::is_same<Real, float>::value)
+        return entry_f32;
+    else
+        return entry;
+}
+
+// the families on three factor arrays take the same arguments in both forms (local: no index, no scale).  False: not one of them
+template <typename Real>
+inline bool launch_three_arrays(const StiffnessChoice &c, const LevelList &ll, Real *q, const Real *v, const double *scale_dev, const int *point_index)
+{
+    const ListArrays<Real> a(ll);
+    void *s = dev().stream;
+    const int *factor_elem = c.shared ? ll.factor_elem.as<int>() : nullptr;
+    if (c.family == StiffnessFamily::diag)
+        FDD_CALL(entry_of<Real>(fdd_stiffness_matrix_diag, fdd_stiffness_matrix_diag_f32)(q, v, scale_dev, point_index, a.D_hat, a.G, nullptr, ll.num_elements, ll.poly_degree, s));
+    else if (c.family == StiffnessFamily::mfma_diag)
+    {
+        if constexpr (std::is_same<Real, double>::value) FDD_CALL(fdd_stiffness_matrix_mfma_diag(q, v, scale_dev, point_index, a.D_hat, a.G, nullptr, ll.num_elements, ll.poly_degree, s));
+    }
+    else if (c.family != StiffnessFamily::lines)
+        return false;
+    else if (c.lean) // shared where factor_elem is given
+        FDD_CALL(entry_of<Real>(fdd_stiffness_matrix_lines_lean, fdd_stiffness_matrix_lines_lean_f32)(q, v, scale_dev, point_index, a.D_hat, a.G, nullptr, factor_elem, ll.num_elements, ll.poly_degree, 1, s));
+    else if (c.shared)
+        FDD_CALL(entry_of<Real>(fdd_stiffness_matrix_lines_shared, fdd_stiffness_matrix_lines_shared_f32)(q, v, scale_dev, point_index, a.D_hat, a.G, nullptr, factor_elem, ll.num_elements, ll.poly_degree, 1, s));
+    else
+        FDD_CALL(entry_of<Real>(fdd_stiffness_matrix_lines, fdd_stiffness_matrix_lines_f32)(q, v, scale_dev, point_index, a.D_hat, a.G, nullptr, ll.num_elements, ll.poly_degree, 1, s));
+    return true;
 }
 
 // Au = A_L u on the points of the list (Au, u: the vectors the list's first_offset counts in).  workspace: three vectors
 // of the list's points for the two-launch form above degree 15.
-inline void apply_local(const LevelList &ll, double *Au, const double *u, const std::vector<memory> &workspace, bool mfma_enabled, bool skip_zero_factors, bool line_stiffness, bool mfma_skip_zero_factors, bool shared_factor_blocks, bool lean_line_stiffness)
+inline void apply_local(const LevelList &ll, double *Au, const double *u, const std::vector<memory> &workspace, const StiffnessFlags &flags)
 {
     void *stream = dev().stream;
-    const double points = (double)ll.num_points();
     Au += ll.first_offset, u += ll.first_offset;
-    if (on_mfma_diag_kernel<double>(ll, mfma_enabled, skip_zero_factors, mfma_skip_zero_factors) and Au != u)
-    {
-        // not "mfma_stiffness_kernel...": the committed counters bench.py matches by that prefix are the six-array kernel's
-        ProfileScope prof("mfma_diag_stiffness_kernel", 40.0 * points);
-        FDD_CALL(fdd_stiffness_matrix_mfma_diag(Au, u, nullptr, nullptr, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, stream));
-    }
-    else if (on_matrix_cores<double>(ll, mfma_enabled) and Au != u)
-    {
-        // high order: the six contractions on the fp64 matrix cores (tolerance-level parity, fdd_hip.h)
-        ProfileScope prof("mfma_stiffness_kernel", 64.0 * points);
-        FDD_CALL(fdd_stiffness_matrix_mfma(Au, u, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, stream));
-    }
-    else if (on_lean_line_kernel<double>(ll, mfma_enabled, skip_zero_factors, line_stiffness, lean_line_stiffness))
-    {
-        const bool shared = on_shared_line_kernel<double>(ll, mfma_enabled, skip_zero_factors, line_stiffness, shared_factor_blocks);
-        ProfileScope prof(shared ? "line_stiffness_kernel<shared,lean>" : "line_stiffness_kernel<lean>", (shared ? 16.0 : 40.0) * points); // the bytes of the parent instance
-        FDD_CALL(fdd_stiffness_matrix_lines_lean(Au, u, nullptr, nullptr, ll.D_hat, ll.G, nullptr, shared ? ll.factor_elem.as<int>() : nullptr, ll.num_elements, ll.poly_degree, 1, stream));
-    }
-    else if (on_shared_line_kernel<double>(ll, mfma_enabled, skip_zero_factors, line_stiffness, shared_factor_blocks))
-    {
-        ProfileScope prof("line_stiffness_kernel<shared>", 16.0 * points); // u and Au; the few factor blocks stay in cache
-        FDD_CALL(fdd_stiffness_matrix_lines_shared(Au, u, nullptr, nullptr, ll.D_hat, ll.G, nullptr, ll.factor_elem.as<int>(), ll.num_elements, ll.poly_degree, 1, stream));
-    }
-    else if (on_line_kernel<double>(ll, mfma_enabled, skip_zero_factors, line_stiffness))
-    {
-        ProfileScope prof("line_stiffness_kernel", 40.0 * points); // the bytes of the three-array instance it replaces
-        FDD_CALL(fdd_stiffness_matrix_lines(Au, u, nullptr, nullptr, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, 1, stream));
-    }
-    else if (on_diag_kernel<double>(ll, mfma_enabled, skip_zero_factors)) // the gather form's predicate: one answer per list (3-D, degree <= 15: nothing else is checked)
-    {
-        // the labels of the three-array instances are not "fused_stiffness_kernel...": the committed counters bench.py
-        // matches by family are the six-array kernel's
-        ProfileScope prof("diag_stiffness_kernel", 40.0 * points);
-        FDD_CALL(fdd_stiffness_matrix_diag(Au, u, nullptr, nullptr, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, stream));
-    }
-    else if (ll.dim == 3 and ll.poly_degree <= 15)
-    {
-        ProfileScope prof("fused_stiffness_kernel", 64.0 * points);
-        FDD_CALL(fdd_sub_stiffness_matrix(Au, u, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, stream));
-    }
-    else if (ll.dim == 2 and ll.poly_degree <= 15)
-    {
-        ProfileScope prof("fused_stiffness_2d_kernel", 40.0 * points);
-        FDD_CALL(fdd_stiffness_matrix_2d(Au, u, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, stream));
-    }
-    else
+    const StiffnessChoice c = choose_stiffness(ll, flags, false, StiffnessForm::local, Au == u);
+    if (c.family == StiffnessFamily::two_launch)
     {
         // degree above 15: the reference's two-launch form (domain.tpp:605-606) on the list
         double *GDu[3] = {workspace[0].as<double>(), workspace[1].as<double>(), workspace[2].as<double>()};
         FDD_CALL(fdd_dom_stiffness_matrix_1(GDu, u, ll.D_hat, ll.G, (int)ll.num_points(), ll.poly_degree, ll.dim, stream));
         FDD_CALL(fdd_dom_stiffness_matrix_2(Au, GDu, ll.D_hat, (int)ll.num_points(), ll.poly_degree, ll.dim, stream));
+        return;
     }
-}
-
-namespace ops
-{
-// the gather entries per precision, as in precision_ops.hpp; q, point_index: at the list's first point
-inline void stiffness_gather(const LevelList &ll, double *q, const double *v, const double *scale_dev, const int *point_index, bool mfma, void *s)
-{
-    FDD_CALL((mfma ? fdd_stiffness_matrix_mfma_gather : fdd_sub_stiffness_matrix_gather_scaled)(q, v, scale_dev, point_index, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, s));
-}
-inline void stiffness_gather(const LevelList &ll, float *q, const float *v, const double *scale_dev, const int *point_index, bool, void *s)
-{
-    const float *G[NUM_GEOM_FACTS];
-    for (int g = 0; g < NUM_GEOM_FACTS; g++) G[g] = ll.G32[g].as<float>();
-    FDD_CALL(fdd_sub_stiffness_matrix_gather_scaled_f32(q, v, scale_dev, point_index, ll.D_hat32.as<float>(), G, nullptr, ll.num_elements, ll.poly_degree, s));
-}
-inline void stiffness_diag(const LevelList &ll, double *q, const double *v, const double *scale_dev, const int *point_index, void *s)
-{
-    FDD_CALL(fdd_stiffness_matrix_diag(q, v, scale_dev, point_index, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, s));
-}
-inline void stiffness_diag(const LevelList &ll, float *q, const float *v, const double *scale_dev, const int *point_index, void *s)
-{
-    const float *G[NUM_GEOM_FACTS];
-    for (int g = 0; g < NUM_GEOM_FACTS; g++) G[g] = ll.G32[g].as<float>();
-    FDD_CALL(fdd_stiffness_matrix_diag_f32(q, v, scale_dev, point_index, ll.D_hat32.as<float>(), G, nullptr, ll.num_elements, ll.poly_degree, s));
-}
-inline void stiffness_mfma_diag(const LevelList &ll, double *q, const double *v, const double *scale_dev, const int *point_index, void *s)
-{
-    FDD_CALL(fdd_stiffness_matrix_mfma_diag(q, v, scale_dev, point_index, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, s));
-}
-inline void stiffness_lines(const LevelList &ll, double *q, const double *v, const double *scale_dev, const int *point_index, void *s)
-{
-    FDD_CALL(fdd_stiffness_matrix_lines(q, v, scale_dev, point_index, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, 1, s));
-}
-inline void stiffness_lines(const LevelList &ll, float *q, const float *v, const double *scale_dev, const int *point_index, void *s)
-{
-    const float *G[NUM_GEOM_FACTS];
-    for (int g = 0; g < NUM_GEOM_FACTS; g++) G[g] = ll.G32[g].as<float>();
-    FDD_CALL(fdd_stiffness_matrix_lines_f32(q, v, scale_dev, point_index, ll.D_hat32.as<float>(), G, nullptr, ll.num_elements, ll.poly_degree, 1, s));
-}
-inline void stiffness_lines_shared(const LevelList &ll, double *q, const double *v, const double *scale_dev, const int *point_index, void *s)
-{
-    FDD_CALL(fdd_stiffness_matrix_lines_shared(q, v, scale_dev, point_index, ll.D_hat, ll.G, nullptr, ll.factor_elem.as<int>(), ll.num_elements, ll.poly_degree, 1, s));
-}
-inline void stiffness_lines_shared(const LevelList &ll, float *q, const float *v, const double *scale_dev, const int *point_index, void *s)
-{
-    const float *G[NUM_GEOM_FACTS];
-    for (int g = 0; g < NUM_GEOM_FACTS; g++) G[g] = ll.G32[g].as<float>();
-    FDD_CALL(fdd_stiffness_matrix_lines_shared_f32(q, v, scale_dev, point_index, ll.D_hat32.as<float>(), G, nullptr, ll.factor_elem.as<int>(), ll.num_elements, ll.poly_degree, 1, s));
-}
-inline void stiffness_lines_lean(const LevelList &ll, double *q, const double *v, const double *scale_dev, const int *point_index, bool shared, void *s)
-{
-    FDD_CALL(fdd_stiffness_matrix_lines_lean(q, v, scale_dev, point_index, ll.D_hat, ll.G, nullptr, shared ? ll.factor_elem.as<int>() : nullptr, ll.num_elements, ll.poly_degree, 1, s));
-}
-inline void stiffness_lines_lean(const LevelList &ll, float *q, const float *v, const double *scale_dev, const int *point_index, bool shared, void *s)
-{
-    const float *G[NUM_GEOM_FACTS];
-    for (int g = 0; g < NUM_GEOM_FACTS; g++) G[g] = ll.G32[g].as<float>();
-    FDD_CALL(fdd_stiffness_matrix_lines_lean_f32(q, v, scale_dev, point_index, ll.D_hat32.as<float>(), G, nullptr, shared ? ll.factor_elem.as<int>() : nullptr, ll.num_elements, ll.poly_degree, 1, s));
-}
-inline void stiffness_affine(const LevelList &ll, double *q, const double *v, const double *scale_dev, const int *point_index, bool mfma, void *s)
-{
-    FDD_CALL((mfma ? fdd_stiffness_matrix_mfma_affine : fdd_stiffness_matrix_affine)(q, v, scale_dev, point_index, ll.D_hat, ll.affine_c.as<double>(), ll.affine_w.as<double>(), nullptr, ll.num_elements, ll.poly_degree, s));
-}
-inline void stiffness_affine(const LevelList &ll, float *q, const float *v, const double *scale_dev, const int *point_index, bool, void *s)
-{
-    FDD_CALL(fdd_stiffness_matrix_affine_f32(q, v, scale_dev, point_index, ll.D_hat32.as<float>(), ll.affine_c32.as<float>(), ll.affine_w32.as<float>(), nullptr, ll.num_elements, ll.poly_degree, s));
-}
+    const StiffnessProfile p = stiffness_profile(StiffnessForm::local, c, false);
+    ProfileScope prof(p.label, p.bytes_per_point * (double)ll.num_points());
+    if (launch_three_arrays<double>(c, ll, Au, u, nullptr, nullptr)) return;
+    if (c.family == StiffnessFamily::mfma) // high order: the six contractions on the fp64 matrix cores (tolerance-level parity, fdd_hip.h)
+        FDD_CALL(fdd_stiffness_matrix_mfma(Au, u, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, stream));
+    else if (c.family == StiffnessFamily::fused)
+        FDD_CALL(fdd_sub_stiffness_matrix(Au, u, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, stream));
+    else
+        FDD_CALL(fdd_stiffness_matrix_2d(Au, u, ll.D_hat, ll.G, nullptr, ll.num_elements, ll.poly_degree, stream));
 }
 
 // q (points of the list) = A_L (Q (s v)): u[p] = s v[point_index[p]] on load (0 where the index is negative), s = *scale_dev
 // (null: 1).  q, point_index: the arrays the list's first_offset counts in; gathered_values: the length of v (the bytes it
 // adds to the count).  3-D lists of degree <= 15.
 template <typename Real>
-inline void apply_gather(const LevelList &ll, Real *q, const Real *v, const int *point_index, const double *scale_dev, int gathered_values, bool mfma_enabled, bool skip_zero_factors, bool line_stiffness, bool mfma_skip_zero_factors, bool shared_factor_blocks, bool lean_line_stiffness)
+inline void apply_gather(const LevelList &ll, Real *q, const Real *v, const int *point_index, const double *scale_dev, int gathered_values, const StiffnessFlags &flags)
 {
     constexpr bool f32 = std::is_same<Real, float>::value;
-    const bool mfma = on_matrix_cores<Real>(ll, mfma_enabled);
-    const double points = (double)ll.num_points(), gathered = (double)sizeof(Real) * gathered_values;
+    void *stream = dev().stream;
     q += ll.first_offset, point_index += ll.first_offset;
-    if (ll.affine)
+    const StiffnessChoice c = choose_stiffness(ll, flags, f32, StiffnessForm::gather);
+    const StiffnessProfile p = stiffness_profile(StiffnessForm::gather, c, f32);
+    ProfileScope prof(p.label, p.bytes_per_point * (double)ll.num_points() + (double)sizeof(Real) * gathered_values);
+    if (launch_three_arrays<Real>(c, ll, q, v, scale_dev, point_index)) return;
+    const ListArrays<Real> a(ll);
+    const bool matrix_cores = c.family == StiffnessFamily::mfma or c.family == StiffnessFamily::mfma_affine; // never in float (choose_stiffness)
+    if (c.family == StiffnessFamily::affine or c.family == StiffnessFamily::mfma_affine)
     {
-        ProfileScope prof(f32 ? "fused_stiffness_kernel<gather,f32,affine>" : mfma ? "mfma_stiffness_kernel<gather,affine>" : "fused_stiffness_kernel<gather,affine>", (f32 ? 8.0 : 12.0) * points + gathered);
-        ops::stiffness_affine(ll, q, v, scale_dev, point_index, mfma, dev().stream);
-        return;
+        if constexpr (f32)
+            FDD_CALL(fdd_stiffness_matrix_affine_f32(q, v, scale_dev, point_index, a.D_hat, a.affine_c, a.affine_w, nullptr, ll.num_elements, ll.poly_degree, stream));
+        else
+            FDD_CALL((matrix_cores ? fdd_stiffness_matrix_mfma_affine : fdd_stiffness_matrix_affine)(q, v, scale_dev, point_index, a.D_hat, a.affine_c, a.affine_w, nullptr, ll.num_elements, ll.poly_degree, stream));
     }
-    if constexpr (not f32) // the matrix-core kernels exist in double only
-        if (on_mfma_diag_kernel<Real>(ll, mfma_enabled, skip_zero_factors, mfma_skip_zero_factors))
-        {
-            ProfileScope prof("mfma_diag_stiffness_kernel<gather>", 36.0 * points + gathered);
-            ops::stiffness_mfma_diag(ll, q, v, scale_dev, point_index, dev().stream);
-            return;
-        }
-    if (on_lean_line_kernel<Real>(ll, mfma_enabled, skip_zero_factors, line_stiffness, lean_line_stiffness))
-    {
-        const bool shared = on_shared_line_kernel<Real>(ll, mfma_enabled, skip_zero_factors, line_stiffness, shared_factor_blocks);
-        const char *label = shared ? (f32 ? "line_stiffness_kernel<gather,shared,f32,lean>" : "line_stiffness_kernel<gather,shared,lean>") : (f32 ? "line_stiffness_kernel<gather,f32,lean>" : "line_stiffness_kernel<gather,lean>");
-        ProfileScope prof(label, (shared ? (f32 ? 8.0 : 12.0) : (f32 ? 20.0 : 36.0)) * points + gathered); // the bytes of the parent instance
-        ops::stiffness_lines_lean(ll, q, v, scale_dev, point_index, shared, dev().stream);
-        return;
-    }
-    if (on_shared_line_kernel<Real>(ll, mfma_enabled, skip_zero_factors, line_stiffness, shared_factor_blocks))
-    {
-        ProfileScope prof(f32 ? "line_stiffness_kernel<gather,shared,f32>" : "line_stiffness_kernel<gather,shared>", (f32 ? 8.0 : 12.0) * points + gathered); // index and q; the few factor blocks stay in cache
-        ops::stiffness_lines_shared(ll, q, v, scale_dev, point_index, dev().stream);
-        return;
-    }
-    if (on_line_kernel<Real>(ll, mfma_enabled, skip_zero_factors, line_stiffness))
-    {
-        ProfileScope prof(f32 ? "line_stiffness_kernel<gather,f32>" : "line_stiffness_kernel<gather>", (f32 ? 20.0 : 36.0) * points + gathered); // the bytes of the instance it replaces
-        ops::stiffness_lines(ll, q, v, scale_dev, point_index, dev().stream);
-        return;
-    }
-    if (on_diag_kernel<Real>(ll, mfma_enabled, skip_zero_factors))
-    {
-        ProfileScope prof(f32 ? "diag_stiffness_kernel<gather,f32>" : "diag_stiffness_kernel<gather>", (f32 ? 20.0 : 36.0) * points + gathered);
-        ops::stiffness_diag(ll, q, v, scale_dev, point_index, dev().stream);
-        return;
-    }
-    ProfileScope prof(f32 ? "fused_stiffness_kernel<gather,f32>" : mfma ? "mfma_stiffness_kernel<gather>" : "fused_stiffness_kernel<gather>", (f32 ? 32.0 : 60.0) * points + gathered);
-    ops::stiffness_gather(ll, q, v, scale_dev, point_index, mfma, dev().stream);
+    else if constexpr (f32)
+        FDD_CALL(fdd_sub_stiffness_matrix_gather_scaled_f32(q, v, scale_dev, point_index, a.D_hat, a.G, nullptr, ll.num_elements, ll.poly_degree, stream));
+    else
+        FDD_CALL((matrix_cores ? fdd_stiffness_matrix_mfma_gather : fdd_sub_stiffness_matrix_gather_scaled)(q, v, scale_dev, point_index, a.D_hat, a.G, nullptr, ll.num_elements, ll.poly_degree, stream));
 }
 
 // ---- affine elements (an option of this build; the reference always streams the six factor arrays) ----

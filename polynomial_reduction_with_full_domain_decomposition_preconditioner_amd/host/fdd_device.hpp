@@ -55,28 +55,28 @@
 #pragma weak fdd_csr_plan_gather_cheby
 #pragma weak fdd_csr_plan_gather_cheby_f32
 // and the stiffness kernel that does not stream factor arrays that are identically zero, with its check: without them every
-// list streams six arrays, and the flag "skip_zero_factors" refuses to be set to 1, naming the missing entry
-// (missing_zero_factor_entry, element_operator.hpp)
+// list streams six arrays, and the flag "skip_zero_factors" refuses to be set to 1, naming the missing entry (here and below:
+// set_stiffness_flag and the table of flags, element_operator.hpp)
 #pragma weak fdd_stiffness_matrix_diag
 #pragma weak fdd_stiffness_matrix_diag_f32
 #pragma weak fdd_stiffness_offdiag_zero
 // and its matrix-core instance (degree 11..15): without it those lists keep the six-array matrix-core kernel, and the flag
-// "mfma_skip_zero_factors" refuses to be set to 1 (missing_mfma_zero_factor_entry, element_operator.hpp)
+// "mfma_skip_zero_factors" refuses to be set to 1
 #pragma weak fdd_stiffness_matrix_mfma_diag
 // and the line form of the stiffness kernel at degree 7: without it those lists stay on the slab form, and the flag
-// "line_stiffness" refuses to be set to 1, naming the missing entry (missing_line_stiffness_entry, element_operator.hpp)
+// "line_stiffness" refuses to be set to 1, naming the missing entry
 #pragma weak fdd_stiffness_matrix_lines
 #pragma weak fdd_stiffness_matrix_lines_f32
 // and its instance for factor blocks that repeat from element to element, with the two entries that establish which do:
 // without them every list streams its own blocks, and the flag "shared_factor_blocks" refuses to be set to 1, naming the
-// missing entry (missing_shared_factor_entry, element_operator.hpp)
+// missing entry
 #pragma weak fdd_stiffness_matrix_lines_shared
 #pragma weak fdd_stiffness_matrix_lines_shared_f32
 #pragma weak fdd_stiffness_factor_block_hash
 #pragma weak fdd_stiffness_factor_block_verify
 // and the lean instances of the line form (a D_hat with a zero interior diagonal that is its own negated mirror image):
 // without them every list keeps the parent instance, and the flag "lean_line_stiffness" refuses to be set to 1, naming the
-// missing entry (missing_lean_line_entry, element_operator.hpp)
+// missing entry
 #pragma weak fdd_stiffness_matrix_lines_lean
 #pragma weak fdd_stiffness_matrix_lines_lean_f32
 

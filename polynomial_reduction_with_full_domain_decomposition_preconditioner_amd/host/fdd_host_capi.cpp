@@ -944,16 +944,20 @@ int fddh_problem_affine_info(fddh_problem *p, int *fine_domain_affine, int *sub_
     }
 }
 
-int fddh_problem_zero_factor_info(fddh_problem *p, int *enabled, int *fine_domain_diag, int *sub_lists_diag, int *sub_lists)
+// what the five fddh_problem_*_info entries of the stiffness flags have in common: the flag, whether the fine Domain's list and
+// how many of the Subdomain's lists run a kernel of its kind (the gather form's choice in the precision in use), and the
+// number of lists.  more(list): what an entry reports beyond that, from the fine Domain's list
+static int stiffness_info(fddh_problem *p, const char *flag, bool (fdd::StiffnessChoice::*is)() const, int *enabled, int *fine_domain, int *sub_lists_on, int *sub_lists, const std::function<void(const fdd::LevelList &)> &more = nullptr)
 {
     try
     {
         if (int rc = rank_check(p)) return rc;
         if (!p) return fail("null argument");
         Domain<SType> &dom = p->fine();
-        if (enabled) *enabled = dom.skip_zero_factors ? 1 : 0;
-        if (fine_domain_diag) *fine_domain_diag = dom.runs_diag_kernel() ? 1 : 0;
-        if (sub_lists_diag) *sub_lists_diag = p->subdomain ? p->subdomain->lists_on_diag_kernel() : 0;
+        if (enabled) *enabled = fdd::stiffness_flag(dom.stiffness, flag) ? 1 : 0;
+        if (fine_domain) *fine_domain = (dom.operator_choice().*is)() ? 1 : 0;
+        if (more) more(dom.operator_list());
+        if (sub_lists_on) *sub_lists_on = p->subdomain ? p->subdomain->count_lists(is) : 0;
         if (sub_lists) *sub_lists = p->subdomain ? (int)p->subdomain->operator_lists().size() : 0;
         return 0;
     }
@@ -961,84 +965,35 @@ int fddh_problem_zero_factor_info(fddh_problem *p, int *enabled, int *fine_domai
     {
         return fail("%s", e.what());
     }
+}
+
+int fddh_problem_zero_factor_info(fddh_problem *p, int *enabled, int *fine_domain_diag, int *sub_lists_diag, int *sub_lists)
+{
+    return stiffness_info(p, "skip_zero_factors", &fdd::StiffnessChoice::three_arrays, enabled, fine_domain_diag, sub_lists_diag, sub_lists);
 }
 
 int fddh_problem_mfma_zero_factor_info(fddh_problem *p, int *enabled, int *fine_domain_mfma_diag, int *sub_lists_mfma_diag, int *sub_lists)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p) return fail("null argument");
-        Domain<SType> &dom = p->fine();
-        if (enabled) *enabled = dom.mfma_skip_zero_factors ? 1 : 0;
-        if (fine_domain_mfma_diag) *fine_domain_mfma_diag = dom.runs_mfma_diag_kernel() ? 1 : 0;
-        if (sub_lists_mfma_diag) *sub_lists_mfma_diag = p->subdomain ? p->subdomain->lists_on_mfma_diag_kernel() : 0;
-        if (sub_lists) *sub_lists = p->subdomain ? (int)p->subdomain->operator_lists().size() : 0;
-        return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    return stiffness_info(p, "mfma_skip_zero_factors", &fdd::StiffnessChoice::mfma_three_arrays, enabled, fine_domain_mfma_diag, sub_lists_mfma_diag, sub_lists);
 }
 
 int fddh_problem_line_stiffness_info(fddh_problem *p, int *enabled, int *fine_domain_lines, int *sub_lists_lines, int *sub_lists)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p) return fail("null argument");
-        Domain<SType> &dom = p->fine();
-        if (enabled) *enabled = dom.line_stiffness ? 1 : 0;
-        if (fine_domain_lines) *fine_domain_lines = dom.runs_line_kernel() ? 1 : 0;
-        if (sub_lists_lines) *sub_lists_lines = p->subdomain ? p->subdomain->lists_on_line_kernel() : 0;
-        if (sub_lists) *sub_lists = p->subdomain ? (int)p->subdomain->operator_lists().size() : 0;
-        return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    return stiffness_info(p, "line_stiffness", &fdd::StiffnessChoice::lines, enabled, fine_domain_lines, sub_lists_lines, sub_lists);
 }
 
 int fddh_problem_shared_factor_info(fddh_problem *p, int *enabled, int *fine_domain_shared, int *fine_domain_classes, int *sub_lists_shared, int *sub_lists)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p) return fail("null argument");
-        Domain<SType> &dom = p->fine();
-        if (enabled) *enabled = dom.shared_factor_blocks ? 1 : 0;
-        if (fine_domain_shared) *fine_domain_shared = dom.runs_shared_line_kernel() ? 1 : 0;
-        if (fine_domain_classes) *fine_domain_classes = dom.operator_list().factor_classes;
-        if (sub_lists_shared) *sub_lists_shared = p->subdomain ? p->subdomain->lists_on_shared_line_kernel() : 0;
-        if (sub_lists) *sub_lists = p->subdomain ? (int)p->subdomain->operator_lists().size() : 0;
-        return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    return stiffness_info(p, "shared_factor_blocks", &fdd::StiffnessChoice::shared_lines, enabled, fine_domain_shared, sub_lists_shared, sub_lists, [&](const fdd::LevelList &list) {
+        if (fine_domain_classes) *fine_domain_classes = list.factor_classes;
+    });
 }
 
 int fddh_problem_lean_line_info(fddh_problem *p, int *enabled, int *fine_domain_table_ok, int *fine_domain_lean, int *sub_lists_lean, int *sub_lists)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p) return fail("null argument");
-        Domain<SType> &dom = p->fine();
-        if (enabled) *enabled = dom.lean_line_stiffness ? 1 : 0;
-        if (fine_domain_table_ok) *fine_domain_table_ok = dom.operator_list().lean_D_hat ? 1 : 0;
-        if (fine_domain_lean) *fine_domain_lean = dom.runs_lean_line_kernel() ? 1 : 0;
-        if (sub_lists_lean) *sub_lists_lean = p->subdomain ? p->subdomain->lists_on_lean_line_kernel() : 0;
-        if (sub_lists) *sub_lists = p->subdomain ? (int)p->subdomain->operator_lists().size() : 0;
-        return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    return stiffness_info(p, "lean_line_stiffness", &fdd::StiffnessChoice::lean_lines, enabled, fine_domain_lean, sub_lists_lean, sub_lists, [&](const fdd::LevelList &list) {
+        if (fine_domain_table_ok) *fine_domain_table_ok = list.lean_D_hat ? 1 : 0;
+    });
 }
 
 int fddh_problem_set_flag(fddh_problem *p, const char *name, int value)
@@ -1106,11 +1061,6 @@ int fddh_problem_set_flag(fddh_problem *p, const char *name, int value)
         {
             if (p->subdomain) p->subdomain->assembled_inner = value != 0;
         }
-        else if (s == "mfma_stiffness")
-        {
-            for (auto &kv : p->domains) kv.second.mfma_stiffness = value != 0;
-            if (p->subdomain) p->subdomain->mfma_stiffness = value != 0;
-        }
         else if (s == "amg_device_setup")
         {
             // build the FEM matrix and the lattice levels of the AMG hierarchy in HBM (Subdomain::amg_build); needs the
@@ -1135,56 +1085,12 @@ int fddh_problem_set_flag(fddh_problem *p, const char *name, int value)
             p->fine().projection.clear(); // the operator's arithmetic changes under the stored images
             if (p->subdomain) p->subdomain->operator_changed();
         }
-        else if (s == "skip_zero_factors")
+        else if (fdd::stiffness_flag_row(s))
         {
-            // lists whose three off-diagonal factor arrays are zero at every point (checked once, when a list's factor
-            // pointers are set) run the kernel that streams three arrays (default where the kernel library has it); 0: six
-            // arrays everywhere.  The operator's values do not change -- what is left out is the addition of exact zeros --
-            // so the projection basis, the point-Jacobi diagonal and the Chebyshev bound stay.
-            if (value != 0)
-                if (const char *missing = fdd::missing_zero_factor_entry()) return fail("skip_zero_factors needs %s, which the loaded kernel library does not export", missing);
-            for (auto &kv : p->domains) kv.second.skip_zero_factors = value != 0;
-            if (p->subdomain) p->subdomain->skip_zero_factors = value != 0;
-        }
-        else if (s == "mfma_skip_zero_factors")
-        {
-            // the same for lists on the matrix cores (degree 11..15): their three-array instance, while "skip_zero_factors"
-            // and "mfma_stiffness" are both on (default where the kernel library has it); 0: those lists stream six arrays.
-            // The values are the six-array matrix-core kernel's, to the sign of a zero, so nothing is emptied here either.
-            if (value != 0)
-                if (const char *missing = fdd::missing_mfma_zero_factor_entry()) return fail("mfma_skip_zero_factors needs %s, which the loaded kernel library does not export", missing);
-            for (auto &kv : p->domains) kv.second.mfma_skip_zero_factors = value != 0;
-            if (p->subdomain) p->subdomain->mfma_skip_zero_factors = value != 0;
-        }
-        else if (s == "line_stiffness")
-        {
-            // 3-D degree-7 lists on the three-array kernel run its line form (default where the kernel library has it); 0: the
-            // slab form.  Same bits either way, so nothing that hangs on the operator is emptied.
-            if (value != 0)
-                if (const char *missing = fdd::missing_line_stiffness_entry()) return fail("line_stiffness needs %s, which the loaded kernel library does not export", missing);
-            for (auto &kv : p->domains) kv.second.line_stiffness = value != 0;
-            if (p->subdomain) p->subdomain->line_stiffness = value != 0;
-        }
-        else if (s == "shared_factor_blocks")
-        {
-            // lists on the line form whose elements share their factor blocks bit for bit (established once, when a list's
-            // factor pointers are set) read the few distinct blocks instead of streaming every copy (default where the kernel
-            // library has the entries); 0: every element streams its own.  The words read are the same, so are all bits.
-            if (value != 0)
-                if (const char *missing = fdd::missing_shared_factor_entry()) return fail("shared_factor_blocks needs %s, which the loaded kernel library does not export", missing);
-            for (auto &kv : p->domains) kv.second.shared_factor_blocks = value != 0;
-            if (p->subdomain) p->subdomain->shared_factor_blocks = value != 0;
-        }
-        else if (s == "lean_line_stiffness")
-        {
-            // lists on the line form whose uploaded D_hat has a zero interior diagonal and is its own negated mirror image
-            // (checked on the host whenever a table is uploaded) run the lean instance, which leaves out the addition of
-            // exact zeros (default where the kernel library has the entries); 0: the parent instances.  The values are the
-            // parent's, to the sign of a zero, so nothing that hangs on the operator is emptied.
-            if (value != 0)
-                if (const char *missing = fdd::missing_lean_line_entry()) return fail("lean_line_stiffness needs %s, which the loaded kernel library does not export", missing);
-            for (auto &kv : p->domains) kv.second.lean_line_stiffness = value != 0;
-            if (p->subdomain) p->subdomain->lean_line_stiffness = value != 0;
+            // the flags that choose between the stiffness kernels: what each does, the entries it needs and why none of them
+            // empties what hangs on the operator are in element_operator.hpp (StiffnessFlags).  Refused before anything is written
+            for (auto &kv : p->domains) fdd::set_stiffness_flag(kv.second.stiffness, s, value != 0);
+            if (p->subdomain) fdd::set_stiffness_flag(p->subdomain->stiffness, s, value != 0);
         }
         else if (s == "fused_projection")
         {

@@ -931,7 +931,7 @@ class Subdomain
     template <typename Real>
     void stiffness_from_dofs(Real *q, const Real *za, const double *scale_dev = nullptr)
     {
-        for (auto &ll : subdomain_operator.level_lists) fdd::apply_gather(ll, q, za, point_dof_dev.template as<int>(), scale_dev, subdomain_operator.num_extended_dofs, mfma_stiffness, skip_zero_factors, line_stiffness, mfma_skip_zero_factors, shared_factor_blocks, lean_line_stiffness);
+        for (auto &ll : subdomain_operator.level_lists) fdd::apply_gather(ll, q, za, point_dof_dev.template as<int>(), scale_dev, subdomain_operator.num_extended_dofs, stiffness);
     }
 
     // y (dofs) = [Qt A_L Q | A_sup] (s x~): the operator of the inner iteration on a dof vector.  x~ is one of the
@@ -1407,12 +1407,7 @@ class Subdomain
         residual_history.assign(hist.begin(), hist.begin() + nh);
         history_pending = false;
     }
-    bool mfma_stiffness = true;           // N >= 11 element lists on the fp64 matrix cores
-    bool line_stiffness = fdd::missing_line_stiffness_entry() == nullptr;  // degree-7 lists on the three-array kernel run its line form (element_operator.hpp)
-    bool shared_factor_blocks = fdd::missing_shared_factor_entry() == nullptr; // lists on the line form whose factor blocks repeat from element to element read the few distinct ones (element_operator.hpp)
-    bool lean_line_stiffness = fdd::missing_lean_line_entry() == nullptr; // lists on the line form whose D_hat allows it run the instance without the zero terms (element_operator.hpp)
-    bool skip_zero_factors = fdd::missing_zero_factor_entry() == nullptr; // lists whose off-diagonal factor arrays are identically zero do not stream them (element_operator.hpp)
-    bool mfma_skip_zero_factors = fdd::missing_mfma_zero_factor_entry() == nullptr; // nor where they run on the matrix cores, while skip_zero_factors and mfma_stiffness are on
+    fdd::StiffnessFlags stiffness; // which kernel each element list runs (element_operator.hpp)
     std::vector<DType> residual_history;  // inner history of the last application
 
     int num_values = 0;
@@ -1918,7 +1913,7 @@ class Subdomain
 
         superdomain_operator.A.multiply(Au_sup, u_sup); // empty: no-op
 
-        for (auto &ll : subdomain_operator.level_lists) fdd::apply_local(ll, Au_sub_l.as<double>(), u_sub_l.as<double>(), work_dev, mfma_stiffness, skip_zero_factors, line_stiffness, mfma_skip_zero_factors, shared_factor_blocks, lean_line_stiffness);
+        for (auto &ll : subdomain_operator.level_lists) fdd::apply_local(ll, Au_sub_l.as<double>(), u_sub_l.as<double>(), work_dev, stiffness);
     }
 
     // subdomain.tpp:4161-4268
@@ -2148,45 +2143,13 @@ class Subdomain
     // factor arrays all have the form c_f(e) (w_i w_j) w_k to rounding runs on the kernel that does not stream them.
     // Returns the number of lists switched over.
     const std::vector<fdd::LevelList> &operator_lists() const { return subdomain_operator.level_lists; }
-    // how many of them run the three-array kernel in the gather form of the precision in use (flag "skip_zero_factors")
-    int lists_on_diag_kernel() const
+    // how many of them the gather form of the precision in use runs on a kernel of the given kind (fddh_problem_*_info); a float
+    // inner solve has no matrix-core kernel
+    int count_lists(bool (fdd::StiffnessChoice::*is)() const) const
     {
         int count = 0;
         for (auto &ll : subdomain_operator.level_lists)
-            if (precision == 32 ? fdd::on_diag_kernel<float>(ll, mfma_stiffness, skip_zero_factors) : fdd::on_diag_kernel<double>(ll, mfma_stiffness, skip_zero_factors)) count++;
-        return count;
-    }
-    // how many run the matrix-core kernel on three factor arrays (flag "mfma_skip_zero_factors"): none in a float inner solve,
-    // which has no matrix-core kernel
-    int lists_on_mfma_diag_kernel() const
-    {
-        int count = 0;
-        for (auto &ll : subdomain_operator.level_lists)
-            if (precision == 32 ? fdd::on_mfma_diag_kernel<float>(ll, mfma_stiffness, skip_zero_factors, mfma_skip_zero_factors) : fdd::on_mfma_diag_kernel<double>(ll, mfma_stiffness, skip_zero_factors, mfma_skip_zero_factors)) count++;
-        return count;
-    }
-    // how many on the shared instance of the line form (flag "shared_factor_blocks"), in the precision in use
-    int lists_on_shared_line_kernel() const
-    {
-        int count = 0;
-        for (auto &ll : subdomain_operator.level_lists)
-            if (precision == 32 ? fdd::on_shared_line_kernel<float>(ll, mfma_stiffness, skip_zero_factors, line_stiffness, shared_factor_blocks) : fdd::on_shared_line_kernel<double>(ll, mfma_stiffness, skip_zero_factors, line_stiffness, shared_factor_blocks)) count++;
-        return count;
-    }
-    // how many on a lean instance of the line form (flag "lean_line_stiffness"), in the precision in use
-    int lists_on_lean_line_kernel() const
-    {
-        int count = 0;
-        for (auto &ll : subdomain_operator.level_lists)
-            if (precision == 32 ? fdd::on_lean_line_kernel<float>(ll, mfma_stiffness, skip_zero_factors, line_stiffness, lean_line_stiffness) : fdd::on_lean_line_kernel<double>(ll, mfma_stiffness, skip_zero_factors, line_stiffness, lean_line_stiffness)) count++;
-        return count;
-    }
-    // and how many the line form of it (flag "line_stiffness")
-    int lists_on_line_kernel() const
-    {
-        int count = 0;
-        for (auto &ll : subdomain_operator.level_lists)
-            if (precision == 32 ? fdd::on_line_kernel<float>(ll, mfma_stiffness, skip_zero_factors, line_stiffness) : fdd::on_line_kernel<double>(ll, mfma_stiffness, skip_zero_factors, line_stiffness)) count++;
+            if ((fdd::choose_stiffness(ll, stiffness, precision == 32, fdd::StiffnessForm::gather).*is)()) count++;
         return count;
     }
     int set_affine_geometry(bool on)

@@ -1117,3 +1117,17 @@ def guarded(values, dtype, gpu):
 
 def guards_stand(whole):
     return bool((whole[:8] == GUARD).all()) and bool((whole[-8:] == GUARD).all())
+
+
+def profiled(fn, records=False):
+    """fn() with the host layer's kernel profile on: (what fn returned, the set of labels recorded), or with records the
+    whole record, label -> {"count", "ms", "bytes"} (bytes summed over the label's launches)"""
+    from polynomial_reduction_with_full_domain_decomposition_preconditioner_amd import lib
+
+    lib.host().call("fddh_profile_enable", 1)
+    out = fn()
+    buf = ctypes.create_string_buffer(1 << 16)
+    lib.host().call("fddh_profile_collect", buf, len(buf))
+    lib.host().call("fddh_profile_enable", 0)
+    record = json.loads(buf.value.decode())
+    return out, (record if records else set(record))

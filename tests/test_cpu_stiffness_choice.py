@@ -1,0 +1,59 @@
+"""The host layer's choice of stiffness kernel, exhaustively and without a GPU.  tests/stiffness_choice_dump.cpp includes
+host/element_operator.hpp, is linked against the CPU stand-in of the kernel library and prints the choice, its profile label
+and bytes per point, and what the info entries would count, for every reachable combination of list state, the six flags
+(written into the struct directly, so that the branches the stand-in has no entries for are reached), precision, form and
+Au == u.  Every row is held to the restatement in stiffness_choice_rules.py, and every family and every label has to occur."""
+import os
+import subprocess
+
+import pytest
+
+import stiffness_choice_rules as R
+import support as S
+
+SHIM_DIR = os.path.join(S.HERE, "cpu_shim")
+HOST_DIR = os.path.join(S.ROOT, "polynomial_reduction_with_full_domain_decomposition_preconditioner_amd", "host")
+
+
+@pytest.fixture(scope="module")
+def rows():
+    subprocess.check_call(["make", "-C", S.ORACLE_DIR, "-s"])
+    subprocess.check_call(["make", "-C", SHIM_DIR, "-s"])
+    build = os.path.join(SHIM_DIR, "_build")
+    exe = os.path.join(build, "stiffness_choice_dump")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I" + os.path.join(S.ROOT, "include"), "-I" + HOST_DIR, "-o", exe, os.path.join(S.HERE, "stiffness_choice_dump.cpp"),
+                           "-L" + build, "-lfdd_cpu_shim", "-ldl", "-Wl,-rpath," + build])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120, check=True).stdout
+    parsed = []
+    for line in out.splitlines():
+        lst, flags, how, choice, info = (part.split() for part in line.split("|"))
+        parsed.append((tuple(int(x) for x in lst[:2]) + tuple(x == "1" for x in lst[2:]), dict(zip(R.FLAGS, (x == "1" for x in flags))), how[0] == "1", how[1], how[2] == "1",
+                       (choice[0], choice[1] == "1", choice[2] == "1"), None if choice[3] == "-" else choice[3], float(choice[4]), dict(zip(("diag", "mfma_diag", "lines", "shared", "lean"), (x == "1" for x in info)))))
+    return parsed
+
+
+def test_every_reachable_combination_is_printed_once(rows):
+    key = lambda lst, flags, f32, form, in_place: (lst, tuple(flags[f] for f in R.FLAGS), f32, form, in_place)
+    want = [key(*c) for c in R.combinations()]
+    got = [key(*r[:5]) for r in rows]
+    assert len(got) == len(set(got)) == len(want) and set(got) == set(want), (len(got), len(want))
+
+
+def test_every_row_is_the_restatement(rows):
+    for lst, flags, f32, form, in_place, choice, label, nbytes, info in rows:
+        what = (lst, flags, f32, form, in_place)
+        want = R.choose(lst, flags, f32, form, in_place)
+        assert choice == want, (what, choice, want)
+        want_label, want_bytes = R.profile(form, want, f32)
+        assert label == want_label and nbytes == (want_bytes or 0), (what, label, nbytes, want_label, want_bytes)
+        assert info == R.info(lst, flags, f32), (what, info)
+
+
+def test_every_family_and_every_label_occurs(rows):
+    for form in ("local", "gather"):
+        families = {r[5][0] for r in rows if r[3] == form}
+        assert families == {family for f, family, _, _ in R.PROFILE if f == form}, (form, families)
+    assert {r[5][0] for r in rows} == set(R.FAMILIES)
+    assert {r[6] for r in rows if r[6]} == R.ALL_LABELS
+    for name in ("diag", "mfma_diag", "lines", "shared", "lean"):
+        assert any(r[8][name] for r in rows) and not all(r[8][name] for r in rows), name

@@ -6,7 +6,6 @@ one, and the solver-level checks of tests/chebyshev_checks.py (the recurrence ag
 fixed linear symmetric positive map, the preconditioner and both outer solvers against the oracle, two ranks on the
 composite, the refusals, the invalidation)."""
 import ctypes
-import json
 
 import numpy as np
 import pytest
@@ -32,15 +31,6 @@ def setup(gpu):
     H.comm_single()
     H.set_print(False)
     return True
-
-
-def profiled(fn):
-    lib.host().call("fddh_profile_enable", 1)
-    out = fn()
-    buf = ctypes.create_string_buffer(1 << 16)
-    lib.host().call("fddh_profile_collect", buf, len(buf))
-    lib.host().call("fddh_profile_enable", 0)
-    return out, set(json.loads(buf.value.decode()))
 
 
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
@@ -274,7 +264,7 @@ def test_same_bits_in_every_form(setup, shape):
                 for form, (kernels, fused) in {"fused": (1, 1), "step": (1, 0), "composed": (0, 0)}.items():
                     p.set_flag("chebyshev_kernels", kernels)
                     p.set_flag("fused_chebyshev", fused)
-                    got[(bits, form)], labels = profiled(lambda: p.sub_dof_solve(fa))
+                    got[(bits, form)], labels = S.profiled(lambda: p.sub_dof_solve(fa))
                     if form == "fused" and shape == "E3N7":
                         assert FUSED_LABELS & labels, sorted(labels)
                     if form == "step":

@@ -8,8 +8,6 @@ Bars of the kernel checks (the project's own for reductions and element-wise sum
 absolute values of its terms, an entry of x / b within 1e-13 x (|x_in| + sum_k |c_k row_k|) -- the start value is a term
 of the sum like the others: without it an entry whose products happen to be tiny would be held below the rounding of the
 one addition that forms it."""
-import ctypes
-import json
 
 import numpy as np
 import pytest
@@ -162,15 +160,6 @@ def setup(gpu):
     return True
 
 
-def profiled(fn):
-    lib.host().call("fddh_profile_enable", 1)
-    out = fn()
-    buf = ctypes.create_string_buffer(1 << 16)
-    lib.host().call("fddh_profile_collect", buf, len(buf))
-    lib.host().call("fddh_profile_enable", 0)
-    return out, set(json.loads(buf.value.decode()))
-
-
 def test_single_launches_agree_with_the_composed_passes(setup):
     """four right-hand sides through solve_projected at capacity 4, once with "fused_projection" 1 and once with 0, each
     from an empty basis: the same iteration counts, solutions within 1e-10 |u|_inf, bases within 1e-10 |X_k|_inf entry by
@@ -185,7 +174,7 @@ def test_single_launches_agree_with_the_composed_passes(setup):
         for flag in (1, 0):
             p.set_flag("fused_projection", flag)
             p.projection_clear()
-            sols, labels = profiled(lambda: [p.solve_projected(f, "fcg") for f in fs])
+            sols, labels = S.profiled(lambda: [p.solve_projected(f, "fcg") for f in fs])
             assert (LABELS <= labels) if flag else not (LABELS & labels), (flag, sorted(labels))
             runs[flag] = (sols, C.basis_of(p))
         p.set_flag("fused_projection", 1)
