@@ -339,6 +339,12 @@ int fdd_cheby_step(double *x, double *d, double *r_out, const double *r_in, cons
 int fdd_cheby_step_f32(float *x, float *d, float *r_out, const float *r_in, const float *q, const float *dinv, float c_d, float c_r, int first, int last, int n, void *stream);
 int fdd_csr_plan_gather_cheby(const fdd_csr_plan *plan, double *x, double *d, double *r_out, const int *Qt_ptr, const int *Qt_col, const double *u, const double *r_in, const double *dinv, double c_d, double c_r, int last, void *stream);
 int fdd_csr_plan_gather_cheby_f32(const fdd_csr_plan *plan, float *x, float *d, float *r_out, const int *Qt_ptr, const int *Qt_col, const float *u, const float *r_in, const float *dinv, float c_d, float c_r, int last, void *stream);
+/* The boolean gather on a selection of Qt's rows: the plan, ptr and col are those of a matrix that holds rows of Qt one after
+ * the other (columns still point indices), and row r's sum is stored at y[row_map[r]] (row_map: num_rows ints in device
+ * memory); the other words of y are not touched.  The sums are those of fdd_csr_plan_dssum (mode 1), bit for bit.  On the
+ * persistent pipelined kernel only, like fdd_csr_plan_gather_cheby: any other plan is FDD_ERR_INVALID_ARGUMENT.  Used with
+ * fdd_stiffness_matrix_lines_direct, which completes the rows left out. */
+int fdd_csr_plan_gather_mapped(const fdd_csr_plan *plan, double *y, const int *row_map, const int *ptr, const int *col, const double *u, void *stream);
 
 /* Scalar bookkeeping of one restart cycle of the inner flexible GMRES(m) (subdomain.tpp:4396-4477) on the device:
  * Hessenberg column + Givens rotations + residual recurrence + stopping tests per step, back-substitution at the
@@ -427,6 +433,25 @@ int fdd_stiffness_matrix_lines_shared_f32(float *Au, const float *v, const doubl
  * FDD_ERR_UNSUPPORTED otherwise, output untouched. */
 int fdd_stiffness_matrix_lines_lean(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream);
 int fdd_stiffness_matrix_lines_lean_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream);
+/* The line form that also assembles: y = Qt Au for most rows of the boolean gather Qt (points -> dofs) without the round trip
+ * through the point buffer.  point_class_dof is point_dof with the class of the point in bits 29..30 of every non-negative
+ * entry (so dofs below 2^29; a negative entry is a point without a dof, as in point_dof), the class being what Qt's own
+ * arrays say about the row of the point's dof:
+ *   0 general    the value goes to the point buffer Au as in fdd_stiffness_matrix_lines, for a gather of those rows
+ *                (fdd_csr_plan_gather_mapped on the compacted rows);
+ *   1 single     the row's only entry: y[dof] = 0 + value;
+ *   2 pair-low   point (7, j, k) of list element e, the first of the row's two entries;
+ *   3 pair-high  point (0, j, k) of list element e + 1, the second, with e / 4 == (e + 1) / 4 (the two elements are waves of
+ *                one workgroup): y[dof] = (0 + value of the pair-low point) + value.
+ * These are the gather's own statements in column order, so every word of y written here has the bits fdd_csr_plan_dssum
+ * (mode 1) writes after fdd_stiffness_matrix_lines[_shared|_lean] on the same inputs; the points of class 0 hold the same
+ * bits in Au, the other points of Au are not written.  The CALLER guarantees the classes (the entry cannot check them) and
+ * that every row of y is completed exactly once by this entry and the gather of the general rows together.  Which instance:
+ * lean != 0: that of fdd_stiffness_matrix_lines_lean (with its condition on D_hat; factor_elem may be NULL), else that of
+ * fdd_stiffness_matrix_lines_shared where factor_elem is given and of fdd_stiffness_matrix_lines where it is NULL.  Double
+ * only.  Refuses what those entries refuse (poly_degree other than 7, diag other than 1: FDD_ERR_UNSUPPORTED), before any
+ * output is touched.  FDD_TUNE_ASSEMBLE_NT_STORE=1: non-temporal stores of y (default 0). */
+int fdd_stiffness_matrix_lines_direct(double *Au, double *y, const double *v, const double *v_scale_dev, const int *point_class_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int lean, int num_elements, int poly_degree, int diag, void *stream);
 /* Which blocks repeat?  out[e] (num_elements 64-bit words in device memory) = a hash of the bit patterns of element e's block
  * of G[0], G[1], G[2] that depends on the position of every word: equal blocks give equal hashes, and two blocks that differ
  * in a single word give different ones.  3-D elements, poly_degree 1..15. */

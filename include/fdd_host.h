@@ -285,6 +285,23 @@ int fddh_problem_shared_factor_info(fddh_problem *p, int *enabled, int *fine_dom
  * The info entry: is the flag on, does the fine Domain's table pass the check, does its list run the lean instance, how many
  * of the Subdomain's level lists run it (in the precision in use), of how many.  Any argument may be NULL. */
 int fddh_problem_lean_line_info(fddh_problem *p, int *enabled, int *fine_domain_table_ok, int *fine_domain_lean, int *sub_lists_lean, int *sub_lists);
+/* Flag "assemble_in_stiffness" (default 1 where the kernel library exports fdd_stiffness_matrix_lines_direct and
+ * fdd_csr_plan_gather_mapped; setting it to 1 on a library without them is refused, naming the missing entry): in the
+ * Subdomain's operator on dof vectors (Qt A_L Q), the degree-7 line kernel stores the rows of Qt that have one entry, or two
+ * from x-neighbours of one workgroup of that kernel, straight into the dof vector, and only the other rows go through the
+ * point buffer and a gather of their own.  Which rows those are is read off Qt's own arrays after every set-up.  The sums
+ * are the gather's own statements in its order, so histories and iterates do not change with the flag, to the last bit.  It
+ * takes effect in a double-precision inner solve on a conforming region with unit norm weights all of whose lists run the line
+ * form (shared or streamed, lean or not); everything else keeps its kernels.  0: the point buffer and the whole gather.
+ * The info entry: is the flag on; is it in effect now and, if not, why (why_not, a C string of at most why_not_len bytes,
+ * empty when in effect); rows[3] = Qt's rows that are general, single, pair; points[5] = the region's points that are
+ * general, single, pair-low, pair-high, without a dof; the row blocks of the general rows' plan (0 until that plan is made,
+ * which happens where everything else holds).  Any argument may be NULL.  Needs a Subdomain.
+ * The arrays entry: the classes themselves, for checks -- point_class_dof (num_points ints: point_dof with the class 0..3
+ * in bits 29..30 of the non-negative entries, in the order above) and the general rows as a CSR of their own (ptr:
+ * num_rows + 1, col: num_nnz point indices, row_map: num_rows dofs).  Call once for the sizes, again with the arrays. */
+int fddh_problem_assembly_info(fddh_problem *p, int *enabled, int *in_effect, long long *rows, long long *points, int *reduced_row_blocks, char *why_not, size_t why_not_len);
+int fddh_problem_assembly_arrays(fddh_problem *p, int *num_points, int *num_rows, int *num_nnz, int *point_class_dof, int *ptr, int *col, int *row_map);
 int fddh_problem_set_flag(fddh_problem *p, const char *name, int value);
 
 /* Low-order AMG preconditioner of the inner solve (Subdomain::low_order_preconditioner,

@@ -85,6 +85,27 @@ struct EpiPlainT // T = float: the gather of the float preconditioner (subdomain
     __device__ T finish(T s, T, int) const { return s; }
 };
 typedef EpiPlainT<double> EpiPlain;
+// The plain row sum of a matrix whose rows are a selection of another's (the rows of the gather Qt that the stiffness kernel
+// does not complete itself, fdd_csr_plan_gather_mapped): row r is stored at row_map[r].  The map is the row's operand, so it
+// is requested with the row pointers of the next block; csr_short_pipelined_kernel only (kRowMap)
+template <typename T>
+struct EpiMappedT
+{
+    static constexpr bool kFreeOrder = false;
+    static constexpr bool kRowMap = true;
+    typedef int Opnd;
+    const int *row_map;
+    __device__ int operand(int row, const T *) const { return row_map[row]; }
+    __device__ T finish(T s, int, int) const { return s; }
+};
+template <typename Epi, typename = void>
+struct EpiRowMap : std::false_type
+{
+};
+template <typename Epi>
+struct EpiRowMap<Epi, std::enable_if_t<Epi::kRowMap>> : std::true_type
+{
+};
 struct EpiWeight
 {
     static constexpr bool kFreeOrder = false;
@@ -797,7 +818,10 @@ __global__ __launch_bounds__(kBlock) void csr_short_pipelined_kernel(T *__restri
             {
                 T s = T(0);
                 for (int j = sp[r]; j < sp[r + 1]; j++) s += x[j];
-                Au[r0 + r] = epi.finish(s, o[it], r0 + r);
+                if constexpr (EpiRowMap<Epi>::value)
+                    Au[o[it]] = epi.finish(s, o[it], r0 + r);
+                else
+                    Au[r0 + r] = epi.finish(s, o[it], r0 + r);
             }
         }
         if (!more) break; // every wave leaves here together: `more` is workgroup-uniform
@@ -1621,6 +1645,24 @@ int fdd_csr_plan_dssum(const fdd_csr_plan *plan, double *QQtu, double *t, const 
     {
         if (M) run(scatter, no, yes);
         else run(scatter, no, no);
+    }
+    FDD_LAUNCH_CHECK();
+    return 0;
+}
+
+// y[row_map[r]] = sum of u over the entries of row r, every row of a boolean matrix whose rows are a selection of the gather
+// Qt's (its compacted general rows, columns still point indices): the persistent pipelined kernel only, as
+// fdd_csr_plan_gather_cheby -- the caller asks fdd_csr_plan_pipelined first.  No value is read
+int fdd_csr_plan_gather_mapped(const fdd_csr_plan *plan, double *y, const int *row_map, const int *ptr, const int *col, const double *u, void *stream)
+{
+    FDD_REQUIRE(plan != nullptr);
+    if (plan->num_rows == 0) return 0;
+    FDD_REQUIRE(y != nullptr && row_map != nullptr && ptr != nullptr && col != nullptr && u != nullptr && (const void *)u != (const void *)y);
+    if (!(plan->value_bytes == 8 && plan->unit_values && plan->kind == 1 && plan->sell_slices == 0 &&
+          launch_short_pipelined<double>(plan, y, ptr, col, (const double *)nullptr, u, EpiMappedT<double>{row_map}, BlockRange{0, plan->num_blocks}, 0, plan->num_rows, fdd_stream(stream), true)))
+    {
+        fdd_set_error("fdd_csr_plan_gather_mapped: not a unit-value fp64 plan of the pipelined short-row kernel");
+        return FDD_ERR_INVALID_ARGUMENT;
     }
     FDD_LAUNCH_CHECK();
     return 0;

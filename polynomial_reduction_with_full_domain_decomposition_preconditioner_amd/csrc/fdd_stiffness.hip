@@ -741,11 +741,51 @@ __device__ __forceinline__ void lean_au(T (&au)[8], const T (&gdu)[8], const Lea
 // like the element's own; the factor loads are plain loads, since the few distinct blocks are meant to stay in cache
 // (a nontemporal load goes past L1).  u, point_dof and Au keep the element's own base, and nothing else differs: the same
 // words reach the same arithmetic.  factor_elem is not read by the streamed instances.
-template <typename T, bool kGather, bool kNTStore, bool kShared = false, int kLean = 0>
-__global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restrict__ Au, const T *__restrict__ u, const int *__restrict__ point_dof, const double *__restrict__ u_scale, const T *__restrict__ D_hat, GPtrsT<T> G, const int *__restrict__ elem_offset, int num_elements, const int *__restrict__ factor_elem)
+//
+// kDirect (double, gather; fdd_stiffness_matrix_lines_direct): most of the values go straight to the rows of y = Qt Au they
+// are the only or one of two entries of, instead of through the point buffer and the gather Qt.  point_dof carries, in the
+// two bits above kDirectDofBits, what the host layer found in Qt's own arrays about the row of each point's dof:
+//   general    anything else: the value goes to the point buffer Au as in the other instances, for the gather of those rows;
+//   single     the row's only entry:                            y[dof] = T(0) + v;
+//   pair-low   point (7, j, k) of element e, first of two entries: v is handed to the next wave through LDS;
+//   pair-high  point (0, j, k) of element e + 1 of the same workgroup, second entry: y[dof] = (T(0) + left) + v;
+// a negative entry is a point without a dof, which stores nothing.  The sums are the statements of the gather's row sum
+// (s = T(0); s += 1.0 * x[j] in column order), so every bit is the one csr_short_pipelined_kernel would have written.  One
+// workgroup barrier stands between the hand-over and its readers, so a wave past the last element does not leave early:
+// it skips the element and meets the others at the barrier.  kDirect: 1 plain, 2 non-temporal stores of y.
+constexpr int kDirectDofBits = 29;
+constexpr int kDirectDofMask = (1 << kDirectDofBits) - 1;
+enum : int
+{
+    kClassGeneral = 0,
+    kClassSingle = 1,
+    kClassPairLow = 2,
+    kClassPairHigh = 3
+};
+// where the kDirect instances write the rows they complete; no member, and nothing read, in the others
+template <typename T, int kDirect>
+struct LineDirect
+{
+    T *__restrict__ y;
+};
+template <typename T>
+struct LineDirect<T, 0>
+{
+};
+// the pair-low values of the workgroup's elements, by (j, k): LDS of the kDirect instances only
+template <typename T>
+__device__ __forceinline__ T *line_hand_over(int e_loc)
+{
+    __shared__ T s_h[LineCfg::epb][LineCfg::nn];
+    return s_h[e_loc];
+}
+
+template <typename T, bool kGather, bool kNTStore, bool kShared = false, int kLean = 0, int kDirect = 0>
+__global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restrict__ Au, const T *__restrict__ u, const int *__restrict__ point_dof, const double *__restrict__ u_scale, const T *__restrict__ D_hat, GPtrsT<T> G, const int *__restrict__ elem_offset, int num_elements, const int *__restrict__ factor_elem, LineDirect<T, kDirect> direct)
 {
     using C = LineCfg;
     constexpr int n = C::n, nn = C::nn;
+    static_assert(kDirect == 0 or kGather, "the classes of the points come with point_dof");
     __shared__ T s_a[C::epb][C::tile]; // u, then Au_2
     __shared__ T s_b[C::epb][C::tile]; // Au_1
 
@@ -754,138 +794,193 @@ __global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restri
     const int l = tid & 63;
     const int a = l & 7, b = l >> 3;
     const int elem = blockIdx.x * C::epb + e_loc;
-    if (elem >= num_elements) return; // wave-uniform; nothing below waits for another wave
-    const size_t base = elem_offset ? (size_t)elem_offset[elem] : (size_t)elem * C::n3;
-    size_t fbase = base; // where the element's factor block is read
-    if (kShared)
+    if constexpr (kDirect == 0)
     {
-        const int rep = factor_elem[elem];
-        fbase = elem_offset ? (size_t)elem_offset[rep] : (size_t)rep * C::n3;
+        if (elem >= num_elements) return; // wave-uniform; nothing below waits for another wave
     }
-    T *ta = s_a[e_loc], *tb = s_b[e_loc];
-    constexpr bool kTerms = (kLean & kLeanTerms) != 0, kResident = (kLean & kLeanResident) != 0;
-    static_assert(kTerms or not kResident, "the resident table does not hold the diagonal entries");
-    const LeanTable<T, kResident> Dl(D_hat);
-
-    // k-column role: u as in the slab form
-    T r_u[n];
-    if (kGather)
+    const bool active = kDirect == 0 or elem < num_elements; // kDirect: such a wave skips the element and goes to the barrier
+    int d[n];                                                // the lane's entries of point_dof (kGather)
+    T v[n];                                                  // its sums (kDirect: kept across the barrier)
+    if (active)
     {
-        const int *pd = point_dof + base;
-        int d[n];
-#pragma unroll
-        for (int k = 0; k < n; k++) d[k] = __builtin_nontemporal_load(pd + (l + k * nn));
-#pragma unroll
-        for (int k = 0; k < n; k++) r_u[k] = u[d[k] < 0 ? 0 : d[k]];
-#pragma unroll
-        for (int k = 0; k < n; k++) r_u[k] = (d[k] < 0) ? T(0) : r_u[k];
-        if (u_scale)
+        const size_t base = elem_offset ? (size_t)elem_offset[elem] : (size_t)elem * C::n3;
+        size_t fbase = base; // where the element's factor block is read
+        if (kShared)
         {
-            const T sc = (T)(*u_scale);
-#pragma unroll
-            for (int k = 0; k < n; k++) r_u[k] = sc * r_u[k];
+            const int rep = factor_elem[elem];
+            fbase = elem_offset ? (size_t)elem_offset[rep] : (size_t)rep * C::n3;
         }
-    }
-    else
-    {
-        const T *up = u + base;
-#pragma unroll
-        for (int k = 0; k < n; k++) r_u[k] = __builtin_nontemporal_load(up + (l + k * nn));
-    }
+        T *ta = s_a[e_loc], *tb = s_b[e_loc];
+        constexpr bool kTerms = (kLean & kLeanTerms) != 0, kResident = (kLean & kLeanResident) != 0;
+        static_assert(kTerms or not kResident, "the resident table does not hold the diagonal entries");
+        const LeanTable<T, kResident> Dl(D_hat);
 
-    T r_3[n];
-    if constexpr (not kTerms)
-    {
-#pragma unroll
-        for (int m = 0; m < n; m++) r_3[m] = T(0);
-    }
-
-    {
-        // the three factor lines of this lane, all requested before anything waits
-        T g0[n], g1[n], g2[n];
-#pragma unroll
-        for (int k = 0; k < n; k++) g2[k] = kShared ? G.g[2][fbase + (l + k * nn)] : __builtin_nontemporal_load(G.g[2] + fbase + (l + k * nn)); // (i, j) = (a, b), k
+        // k-column role: u as in the slab form
+        T r_u[n];
+        if (kGather)
         {
-            const T *g0p = G.g[0] + fbase + 8 * l; // (j, k) = (a, b): the row starts at 8 a + 64 b
+            const int *pd = point_dof + base;
 #pragma unroll
-            for (int p = 0; p < n; p++) g0[p] = g0p[p];
-        }
-        {
-            const T *g1p = G.g[1] + fbase + (a + nn * b); // (i, k) = (a, b): the column steps by 8
+            for (int k = 0; k < n; k++) d[k] = __builtin_nontemporal_load(pd + (l + k * nn));
 #pragma unroll
-            for (int p = 0; p < n; p++) g1[p] = kShared ? g1p[8 * p] : __builtin_nontemporal_load(g1p + 8 * p);
-        }
-
+            for (int k = 0; k < n; k++) r_u[k] = u[d[k] < 0 ? 0 : (kDirect != 0 ? (d[k] & kDirectDofMask) : d[k])];
 #pragma unroll
-        for (int k = 0; k < n; k++) ta[C::at(a, b, k)] = r_u[k];
-        element_sync<true>();
-
-        // z: registers only, Au_3(i, j, m) = sum_k D_hat[m + 8 k] * (g2_k * Du_3_k), k ascending
-#pragma unroll
-        for (int k = 0; k < n; k++)
-        {
-            if constexpr (kTerms)
+            for (int k = 0; k < n; k++) r_u[k] = (d[k] < 0) ? T(0) : r_u[k];
+            if (u_scale)
             {
-                const T *Dk = Dl.row(k);
-                T Du_3 = Dl.at(Dk, k, 0) * r_u[0];
+                const T sc = (T)(*u_scale);
 #pragma unroll
-                for (int p = 1; p < n; p++)
-                    if (not lean_zero_entry(k, p)) Du_3 += Dl.at(Dk, k, p) * r_u[p];
-                const T GDu_3 = g2[k] * Du_3;
+                for (int k = 0; k < n; k++) r_u[k] = sc * r_u[k];
+            }
+        }
+        else
+        {
+            const T *up = u + base;
 #pragma unroll
-                for (int m = 0; m < n; m++)
+            for (int k = 0; k < n; k++) r_u[k] = __builtin_nontemporal_load(up + (l + k * nn));
+        }
+
+        T r_3[n];
+        if constexpr (not kTerms)
+        {
+#pragma unroll
+            for (int m = 0; m < n; m++) r_3[m] = T(0);
+        }
+
+        {
+            // the three factor lines of this lane, all requested before anything waits
+            T g0[n], g1[n], g2[n];
+#pragma unroll
+            for (int k = 0; k < n; k++) g2[k] = kShared ? G.g[2][fbase + (l + k * nn)] : __builtin_nontemporal_load(G.g[2] + fbase + (l + k * nn)); // (i, j) = (a, b), k
+            {
+                const T *g0p = G.g[0] + fbase + 8 * l; // (j, k) = (a, b): the row starts at 8 a + 64 b
+#pragma unroll
+                for (int p = 0; p < n; p++) g0[p] = g0p[p];
+            }
+            {
+                const T *g1p = G.g[1] + fbase + (a + nn * b); // (i, k) = (a, b): the column steps by 8
+#pragma unroll
+                for (int p = 0; p < n; p++) g1[p] = kShared ? g1p[8 * p] : __builtin_nontemporal_load(g1p + 8 * p);
+            }
+
+#pragma unroll
+            for (int k = 0; k < n; k++) ta[C::at(a, b, k)] = r_u[k];
+            element_sync<true>();
+
+            // z: registers only, Au_3(i, j, m) = sum_k D_hat[m + 8 k] * (g2_k * Du_3_k), k ascending
+#pragma unroll
+            for (int k = 0; k < n; k++)
+            {
+                if constexpr (kTerms)
                 {
-                    if (k == 0)
-                        r_3[m] = Dl.at(Dk, 0, m) * GDu_3;
-                    else if (not lean_zero_entry(k, m))
-                        r_3[m] += Dl.at(Dk, k, m) * GDu_3;
+                    const T *Dk = Dl.row(k);
+                    T Du_3 = Dl.at(Dk, k, 0) * r_u[0];
+#pragma unroll
+                    for (int p = 1; p < n; p++)
+                        if (not lean_zero_entry(k, p)) Du_3 += Dl.at(Dk, k, p) * r_u[p];
+                    const T GDu_3 = g2[k] * Du_3;
+#pragma unroll
+                    for (int m = 0; m < n; m++)
+                    {
+                        if (k == 0)
+                            r_3[m] = Dl.at(Dk, 0, m) * GDu_3;
+                        else if (not lean_zero_entry(k, m))
+                            r_3[m] += Dl.at(Dk, k, m) * GDu_3;
+                    }
+                }
+                else
+                {
+                    const T *Dk = line_row(D_hat, k);
+                    T Du_3 = T(0);
+#pragma unroll
+                    for (int p = 0; p < n; p++) Du_3 += Dk[p] * r_u[p];
+                    const T GDu_3 = g2[k] * Du_3;
+#pragma unroll
+                    for (int m = 0; m < n; m++) r_3[m] += Dk[m] * GDu_3;
                 }
             }
-            else
-            {
-                const T *Dk = line_row(D_hat, k);
-                T Du_3 = T(0);
+
+            // x: the row out of the u tile, Au_1 into the other tile
+            T ul[n], w[n], au[n];
 #pragma unroll
-                for (int p = 0; p < n; p++) Du_3 += Dk[p] * r_u[p];
-                const T GDu_3 = g2[k] * Du_3;
+            for (int p = 0; p < n; p++) ul[p] = ta[C::at(p, a, b)];
+            if constexpr (kTerms) lean_du(w, ul, Dl); else line_du(w, ul, D_hat);
 #pragma unroll
-                for (int m = 0; m < n; m++) r_3[m] += Dk[m] * GDu_3;
-            }
+            for (int p = 0; p < n; p++) w[p] = g0[p] * w[p];
+            if constexpr (kTerms) lean_au(au, w, Dl); else line_au(au, w, D_hat);
+#pragma unroll
+            for (int p = 0; p < n; p++) tb[C::at(p, a, b)] = au[p];
+            // y: the column out of the u tile, Au_2 over it: every lane's row and column loads precede these stores in the
+            // wave's instruction order, which the LDS keeps
+#pragma unroll
+            for (int p = 0; p < n; p++) ul[p] = ta[C::at(a, p, b)];
+            element_sync<true>();
+            if constexpr (kTerms) lean_du(w, ul, Dl); else line_du(w, ul, D_hat);
+#pragma unroll
+            for (int p = 0; p < n; p++) w[p] = g1[p] * w[p];
+            if constexpr (kTerms) lean_au(au, w, Dl); else line_au(au, w, D_hat);
+#pragma unroll
+            for (int p = 0; p < n; p++) ta[C::at(a, p, b)] = au[p];
+            element_sync<true>();
         }
 
-        // x: the row out of the u tile, Au_1 into the other tile
-        T ul[n], w[n], au[n];
+        T *Aup = Au + base;
+        if constexpr (kDirect == 0)
+        {
 #pragma unroll
-        for (int p = 0; p < n; p++) ul[p] = ta[C::at(p, a, b)];
-        if constexpr (kTerms) lean_du(w, ul, Dl); else line_du(w, ul, D_hat);
-#pragma unroll
-        for (int p = 0; p < n; p++) w[p] = g0[p] * w[p];
-        if constexpr (kTerms) lean_au(au, w, Dl); else line_au(au, w, D_hat);
-#pragma unroll
-        for (int p = 0; p < n; p++) tb[C::at(p, a, b)] = au[p];
-        // y: the column out of the u tile, Au_2 over it: every lane's row and column loads precede these stores in the
-        // wave's instruction order, which the LDS keeps
-#pragma unroll
-        for (int p = 0; p < n; p++) ul[p] = ta[C::at(a, p, b)];
-        element_sync<true>();
-        if constexpr (kTerms) lean_du(w, ul, Dl); else line_du(w, ul, D_hat);
-#pragma unroll
-        for (int p = 0; p < n; p++) w[p] = g1[p] * w[p];
-        if constexpr (kTerms) lean_au(au, w, Dl); else line_au(au, w, D_hat);
-#pragma unroll
-        for (int p = 0; p < n; p++) ta[C::at(a, p, b)] = au[p];
-        element_sync<true>();
-    }
-
-    T *Aup = Au + base;
-#pragma unroll
-    for (int k = 0; k < n; k++)
-    {
-        const T v = (tb[C::at(a, b, k)] + ta[C::at(a, b, k)]) + r_3[k];
-        if (kNTStore)
-            __builtin_nontemporal_store(v, Aup + (l + k * nn));
+            for (int k = 0; k < n; k++)
+            {
+                v[k] = (tb[C::at(a, b, k)] + ta[C::at(a, b, k)]) + r_3[k];
+                if (kNTStore)
+                    __builtin_nontemporal_store(v[k], Aup + (l + k * nn));
+                else
+                    Aup[l + k * nn] = v[k];
+            }
+        }
         else
-            Aup[l + k * nn] = v;
+        {
+#pragma unroll
+            for (int k = 0; k < n; k++)
+            {
+                v[k] = (tb[C::at(a, b, k)] + ta[C::at(a, b, k)]) + r_3[k];
+                const int cls = d[k] >> kDirectDofBits, dof = d[k] & kDirectDofMask; // a point without a dof: cls < 0
+                if (cls == kClassGeneral)
+                {
+                    if (kNTStore)
+                        __builtin_nontemporal_store(v[k], Aup + (l + k * nn));
+                    else
+                        Aup[l + k * nn] = v[k];
+                }
+                else if (cls == kClassSingle)
+                {
+                    const T s = T(0) + v[k];
+                    if (kDirect == 2)
+                        __builtin_nontemporal_store(s, direct.y + dof);
+                    else
+                        direct.y[dof] = s;
+                }
+                else if (cls == kClassPairLow)
+                    line_hand_over<T>(e_loc)[b + 8 * k] = v[k];
+            }
+        }
+    }
+    if constexpr (kDirect != 0)
+    {
+        element_sync<false>(); // waits for the hand-over's LDS writes only: the stores above stay in flight
+        if (active)
+        {
+            const T *left = line_hand_over<T>(e_loc > 0 ? e_loc - 1 : 0); // the classification never names wave 0 pair-high
+#pragma unroll
+            for (int k = 0; k < n; k++)
+                if ((d[k] >> kDirectDofBits) == kClassPairHigh)
+                {
+                    const T s = (T(0) + left[b + 8 * k]) + v[k];
+                    if (kDirect == 2)
+                        __builtin_nontemporal_store(s, direct.y + (d[k] & kDirectDofMask));
+                    else
+                        direct.y[d[k] & kDirectDofMask] = s;
+                }
+        }
     }
 }
 
@@ -896,7 +991,32 @@ int launch_lines_t(T *Au, const T *u, const int *point_dof, const double *u_scal
     const int grid = (num_elements + LineCfg::epb - 1) / LineCfg::epb;
     fdd_for_bool(factor_elem != nullptr, [&](auto shared) {
         for_gather_nt_store(point_dof, [&](auto gather, auto nt) {
-            hipLaunchKernelGGL((line_stiffness_kernel_t<T, decltype(gather)::value, decltype(nt)::value, decltype(shared)::value, kLean>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem);
+            hipLaunchKernelGGL((line_stiffness_kernel_t<T, decltype(gather)::value, decltype(nt)::value, decltype(shared)::value, kLean>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem, LineDirect<T, 0>{});
+        });
+    });
+    FDD_LAUNCH_CHECK();
+    return 0;
+}
+
+// FDD_TUNE_ASSEMBLE_NT_STORE, read once: non-temporal stores of the rows of y the kDirect instances complete.  0: the next
+// kernels read y (the multi-dot, the update), and non-temporal stores of such vectors measured slower before (HISTORY)
+inline bool assemble_nt_store()
+{
+    static const bool nt_store = fdd_env_int("FDD_TUNE_ASSEMBLE_NT_STORE", 0) != 0;
+    return nt_store;
+}
+
+// the kDirect instances: double and gather only; kShared by whether factor_elem is given
+template <int kLean>
+int launch_lines_direct(double *Au, double *y, const double *u, const int *point_class_dof, const double *u_scale, const double *D_hat, const GPtrsT<double> &G, const int *elem_offset, const int *factor_elem, int num_elements, void *stream)
+{
+    const int grid = (num_elements + LineCfg::epb - 1) / LineCfg::epb;
+    fdd_for_bool(factor_elem != nullptr, [&](auto shared) {
+        fdd_for_bool(stiffness_nt_store(), [&](auto nt) {
+            fdd_for_bool(assemble_nt_store(), [&](auto nt_y) {
+                constexpr int kDirect = decltype(nt_y)::value ? 2 : 1;
+                hipLaunchKernelGGL((line_stiffness_kernel_t<double, true, decltype(nt)::value, decltype(shared)::value, kLean, kDirect>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_class_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem, LineDirect<double, kDirect>{y});
+            });
         });
     });
     FDD_LAUNCH_CHECK();
@@ -929,8 +1049,10 @@ enum class LineEntry
     shared,
     lean
 };
+// direct (fdd_stiffness_matrix_lines_direct): the kDirect instance of the entry's kernel, which completes rows of direct_y;
+//   double with point_dof only
 template <typename T>
-int lines_dispatch(LineEntry entry, T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const T *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream)
+int lines_dispatch(LineEntry entry, T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const T *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream, bool direct = false, T *direct_y = nullptr)
 {
     if (entry == LineEntry::shared && diag != 1)
     {
@@ -956,8 +1078,15 @@ int lines_dispatch(LineEntry entry, T *Au, const T *u, const int *point_dof, con
     if (num_elements == 0) return 0;
     FDD_REQUIRE(Au != nullptr && u != nullptr && D_hat != nullptr && G != nullptr);
     FDD_REQUIRE(entry != LineEntry::shared || factor_elem != nullptr);
+    FDD_REQUIRE(not direct || (point_dof != nullptr && direct_y != nullptr && (const void *)direct_y != (const void *)u && (const void *)direct_y != (const void *)Au));
     GPtrsT<T> g;
     if (int rc = fdd_three_factors(g, G)) return rc;
+    if constexpr (sizeof(T) == 8)
+        if (direct)
+        {
+            if (entry != LineEntry::lean) return launch_lines_direct<0>(Au, direct_y, u, point_dof, u_scale, D_hat, g, elem_offset, entry == LineEntry::shared ? factor_elem : nullptr, num_elements, stream);
+            return launch_lines_direct<(kLeanTerms | kLeanResident)>(Au, direct_y, u, point_dof, u_scale, D_hat, g, elem_offset, factor_elem, num_elements, stream);
+        }
     if (entry != LineEntry::lean) return launch_lines_t<T, 0>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, entry == LineEntry::shared ? factor_elem : nullptr, num_elements, stream);
     constexpr int kParts = sizeof(T) == 8 ? (kLeanTerms | kLeanResident) : kLeanTerms;
 #ifdef FDD_LEAN_LINE_DEV
@@ -1367,6 +1496,12 @@ int fdd_stiffness_matrix_lines(double *Au, const double *v, const double *v_scal
 int fdd_stiffness_matrix_lines_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, int diag, void *stream)
 {
     return lines_dispatch<float>(LineEntry::streamed, Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, nullptr, num_elements, poly_degree, diag, stream);
+}
+
+int fdd_stiffness_matrix_lines_direct(double *Au, double *y, const double *v, const double *v_scale_dev, const int *point_class_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int lean, int num_elements, int poly_degree, int diag, void *stream)
+{
+    const LineEntry entry = lean != 0 ? LineEntry::lean : (factor_elem != nullptr ? LineEntry::shared : LineEntry::streamed);
+    return lines_dispatch<double>(entry, Au, v, point_class_dof, v_scale_dev, D_hat, G, elem_offset, factor_elem, num_elements, poly_degree, diag, stream, true, y);
 }
 
 int fdd_stiffness_matrix_lines_shared(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream)

@@ -98,6 +98,11 @@ struct StiffnessFlags
     // (check_lean_table) run the lean instance, which leaves out the addition of exact zeros; 0: the parent instances.  The
     // values are the parent's, to the sign of a zero, so nothing that hangs on the operator is emptied
     bool lean_line_stiffness;
+    // a Subdomain whose lists all run the degree-7 line form in double has that kernel complete the rows of the gather Qt that
+    // have one entry, or two from neighbouring elements of one workgroup, and gathers the other rows alone
+    // (assembly_classes.hpp; where Subdomain::assembly_obstacle finds none); 0: the point buffer and the whole
+    // gather.  The sums are the gather's own statements, so every bit stays and nothing that hangs on the operator is emptied
+    bool assemble_in_stiffness;
 
     StiffnessFlags();
 };
@@ -114,10 +119,10 @@ struct StiffnessFlagRow
     } entries[5]; // ends at a null name
 };
 
-inline const std::array<StiffnessFlagRow, 6> &stiffness_flag_table()
+inline const std::array<StiffnessFlagRow, 7> &stiffness_flag_table()
 {
 #define FDD_ENTRY(name) {(const void *)&name, #name}
-    static const std::array<StiffnessFlagRow, 6> table = {{
+    static const std::array<StiffnessFlagRow, 7> table = {{
         {"mfma_stiffness", &StiffnessFlags::mfma_stiffness, {}},
         {"skip_zero_factors", &StiffnessFlags::skip_zero_factors, {FDD_ENTRY(fdd_stiffness_offdiag_zero), FDD_ENTRY(fdd_stiffness_matrix_diag), FDD_ENTRY(fdd_stiffness_matrix_diag_f32)}},
         // with the check that sets LevelList::offdiag_zero
@@ -126,6 +131,8 @@ inline const std::array<StiffnessFlagRow, 6> &stiffness_flag_table()
         // with the two entries that establish which blocks repeat
         {"shared_factor_blocks", &StiffnessFlags::shared_factor_blocks, {FDD_ENTRY(fdd_stiffness_matrix_lines_shared), FDD_ENTRY(fdd_stiffness_matrix_lines_shared_f32), FDD_ENTRY(fdd_stiffness_factor_block_hash), FDD_ENTRY(fdd_stiffness_factor_block_verify)}},
         {"lean_line_stiffness", &StiffnessFlags::lean_line_stiffness, {FDD_ENTRY(fdd_stiffness_matrix_lines_lean), FDD_ENTRY(fdd_stiffness_matrix_lines_lean_f32)}},
+        // with the gather of the rows the kernel leaves
+        {"assemble_in_stiffness", &StiffnessFlags::assemble_in_stiffness, {FDD_ENTRY(fdd_stiffness_matrix_lines_direct), FDD_ENTRY(fdd_csr_plan_gather_mapped)}},
     }};
 #undef FDD_ENTRY
     return table;
@@ -473,6 +480,24 @@ inline void apply_gather(const LevelList &ll, Real *q, const Real *v, const int 
         FDD_CALL(fdd_sub_stiffness_matrix_gather_scaled_f32(q, v, scale_dev, point_index, a.D_hat, a.G, nullptr, ll.num_elements, ll.poly_degree, stream));
     else
         FDD_CALL((matrix_cores ? fdd_stiffness_matrix_mfma_gather : fdd_sub_stiffness_matrix_gather_scaled)(q, v, scale_dev, point_index, a.D_hat, a.G, nullptr, ll.num_elements, ll.poly_degree, stream));
+}
+
+// ---- the line form that assembles (flag "assemble_in_stiffness") ----
+// Can the list run it?  The gather form's choice in double is the line form, whichever instance
+inline bool direct_lines_apply(const LevelList &ll, const StiffnessFlags &flags) { return flags.assemble_in_stiffness and choose_stiffness(ll, flags, false, StiffnessForm::gather).lines(); }
+
+// apply_gather with the rows of y = Qt q that the kernel completes written to y and the other points' values to q;
+// point_class_dof: point_index with the class of every point (assembly_classes.hpp).  The caller has asked direct_lines_apply.
+// The instance is the one choose_stiffness names and the launch is recorded under that instance's label, with its count:
+// every point's value is still stored once, or handed to the neighbour's store.  What tells the two paths apart in a profile
+// is the gather that follows (AssemblyClasses::gather_general)
+inline void apply_gather_direct(const LevelList &ll, double *q, double *y, const double *v, const int *point_class_dof, const double *scale_dev, int gathered_values, const StiffnessFlags &flags)
+{
+    q += ll.first_offset, point_class_dof += ll.first_offset;
+    const StiffnessChoice c = choose_stiffness(ll, flags, false, StiffnessForm::gather);
+    const StiffnessProfile p = stiffness_profile(StiffnessForm::gather, c, false);
+    ProfileScope prof(p.label, p.bytes_per_point * (double)ll.num_points() + (double)sizeof(double) * gathered_values);
+    FDD_CALL(fdd_stiffness_matrix_lines_direct(q, y, v, scale_dev, point_class_dof, ll.D_hat, ll.G, nullptr, c.shared ? ll.factor_elem.as<int>() : nullptr, c.lean ? 1 : 0, ll.num_elements, ll.poly_degree, 1, dev().stream));
 }
 
 // ---- affine elements (an option of this build; the reference always streams the six factor arrays) ----

@@ -79,6 +79,11 @@
 // missing entry
 #pragma weak fdd_stiffness_matrix_lines_lean
 #pragma weak fdd_stiffness_matrix_lines_lean_f32
+// and the line form that completes most rows of the gather Qt itself, with the gather of the rows it leaves: without them
+// every operator application keeps the point buffer and the whole gather, and the flag "assemble_in_stiffness" refuses to be
+// set to 1, naming the missing entry
+#pragma weak fdd_stiffness_matrix_lines_direct
+#pragma weak fdd_csr_plan_gather_mapped
 
 namespace fdd
 {

@@ -996,6 +996,56 @@ int fddh_problem_lean_line_info(fddh_problem *p, int *enabled, int *fine_domain_
     });
 }
 
+int fddh_problem_assembly_info(fddh_problem *p, int *enabled, int *in_effect, long long *rows, long long *points, int *reduced_row_blocks, char *why_not, size_t why_not_len)
+{
+    try
+    {
+        if (int rc = rank_check(p)) return rc;
+        if (!p) return fail("null argument");
+        if (!p->subdomain) return fail("problem was created without a Subdomain");
+        Subdomain<SType> &sub = *p->subdomain;
+        if (enabled) *enabled = sub.stiffness.assemble_in_stiffness ? 1 : 0;
+        const char *obstacle = sub.assembly_obstacle();
+        if (!sub.assembly.built) sub.assembly_build(); // the classes are reported whether they are used or not
+        if (in_effect) *in_effect = obstacle == nullptr ? 1 : 0;
+        if (rows) std::copy(sub.assembly.rows, sub.assembly.rows + 3, rows);
+        if (points) std::copy(sub.assembly.points, sub.assembly.points + 5, points);
+        if (reduced_row_blocks) *reduced_row_blocks = sub.assembly.reduced_blocks;
+        if (why_not && why_not_len > 0) snprintf(why_not, why_not_len, "%s", obstacle ? obstacle : "");
+        return 0;
+    }
+    catch (const std::exception &e)
+    {
+        return fail("%s", e.what());
+    }
+}
+
+int fddh_problem_assembly_arrays(fddh_problem *p, int *num_points, int *num_rows, int *num_nnz, int *point_class_dof, int *ptr, int *col, int *row_map)
+{
+    try
+    {
+        if (int rc = rank_check(p)) return rc;
+        if (!p) return fail("null argument");
+        if (!p->subdomain) return fail("problem was created without a Subdomain");
+        Subdomain<SType> &sub = *p->subdomain;
+        if (!sub.assembly.built) sub.assembly_build();
+        const fdd::AssemblyClasses &a = sub.assembly;
+        if (!a.unusable.empty()) return fail("no classes: %s", a.unusable.c_str());
+        if (num_points) *num_points = (int)a.point_class_dof.size();
+        if (num_rows) *num_rows = (int)a.row_map.size();
+        if (num_nnz) *num_nnz = (int)a.col.size();
+        if (point_class_dof) std::copy(a.point_class_dof.begin(), a.point_class_dof.end(), point_class_dof);
+        if (ptr) std::copy(a.ptr.begin(), a.ptr.end(), ptr);
+        if (col) std::copy(a.col.begin(), a.col.end(), col);
+        if (row_map) std::copy(a.row_map.begin(), a.row_map.end(), row_map);
+        return 0;
+    }
+    catch (const std::exception &e)
+    {
+        return fail("%s", e.what());
+    }
+}
+
 int fddh_problem_set_flag(fddh_problem *p, const char *name, int value)
 {
     try

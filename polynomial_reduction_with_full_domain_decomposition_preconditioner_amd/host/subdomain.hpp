@@ -50,6 +50,7 @@
 
 #include "amg.hpp"
 #include "amg_device_setup.hpp"
+#include "assembly_classes.hpp"
 #include "composite.hpp"
 #include "config.hpp"
 #include "csr_matrix.hpp"
@@ -934,6 +935,39 @@ class Subdomain
         for (auto &ll : subdomain_operator.level_lists) fdd::apply_gather(ll, q, za, point_dof_dev.template as<int>(), scale_dev, subdomain_operator.num_extended_dofs, stiffness);
     }
 
+  public:
+    // ---- rows of Qt completed by the stiffness kernel (flag "assemble_in_stiffness", assembly_classes.hpp) ----
+    // The classes of Qt's rows, from Qt's own arrays: made when first asked for and again after every set-up (both forms of
+    // set-up clear them where they rebuild the lists and Qt)
+    fdd::AssemblyClasses assembly;
+    void assembly_build()
+    {
+        CSR_Matrix<DType> &Qt = subdomain_operator.Qt;
+        std::vector<int> ptr((size_t)Qt.num_rows + 1, 0), col((size_t)Qt.num_nnz);
+        if (Qt.num_nnz > 0) // the host mirrors are dropped after set-up: the device arrays are the matrix
+        {
+            Qt.ptr.copyTo(ptr.data(), ptr.size() * sizeof(int));
+            Qt.col.copyTo(col.data(), col.size() * sizeof(int));
+        }
+        assembly.build(ptr.data(), col.data(), Qt.num_rows, subdomain_operator.num_points, point_dof, subdomain_operator.level_lists);
+    }
+    // Why operator_dofs keeps the point buffer and the whole gather in double (nullptr: it does not).  A handful of
+    // comparisons per call once the classes are on the device
+    const char *assembly_obstacle()
+    {
+        if (not stiffness.assemble_in_stiffness) return "the flag is off";
+        if (precision != 64) return "the inner solve runs in float";
+        if (is_composite) return "a composite region";
+        if (not norm_weight_is_one) return "the gather is weighted";
+        if (subdomain_operator.level_lists.empty() or subdomain_operator.Qt.num_nnz == 0 or subdomain_operator.Qt.num_rows != subdomain_operator.num_extended_dofs or not subdomain_operator.Qt.unit_values) return "no boolean gather over every dof";
+        for (auto &ll : subdomain_operator.level_lists)
+            if (not fdd::direct_lines_apply(ll, stiffness)) return "a list does not run the degree-7 line form";
+        if (not assembly.built) assembly_build();
+        if (not assembly.ensure_device()) return assembly.unusable.c_str();
+        return nullptr;
+    }
+
+  private:
     // y (dofs) = [Qt A_L Q | A_sup] (s x~): the operator of the inner iteration on a dof vector.  x~ is one of the
     // Krylov vectors; in a composite its allocation carries the copies and hanging values behind the dofs (W), which
     // are written here.
@@ -946,6 +980,14 @@ class Subdomain
         const int nse = subdomain_operator.num_extended_dofs;
         if (not is_composite)
         {
+            if constexpr (not f32)
+                if (y != x and assembly_obstacle() == nullptr)
+                {
+                    // the line kernel completes the single and pair rows of y itself; the general rows' points go through q
+                    for (auto &ll : subdomain_operator.level_lists) fdd::apply_gather_direct(ll, q, y, x, assembly.point_class_dof_dev.template as<int>(), scale_dev, nse, stiffness);
+                    assembly.gather_general(y, q);
+                    return;
+                }
             stiffness_from_dofs(q, x, scale_dev);
             if constexpr (f32)
                 subdomain_operator.Qt.gather(y, q, 0, nse); // the float gather takes no norm weight
@@ -1576,6 +1618,7 @@ class Subdomain
                 subdomain_operator.Q.initialize(P, max_dof);
         }
         subdomain_operator.Q.transpose(subdomain_operator.Qt);
+        assembly.clear(); // the classes of another Qt
         point_dof.assign(P, -1);
         for (int p = 0; p < P; p++)
             if (tmp[p] > 0.0) point_dof[p] = (int)tmp[p] - 1;
@@ -1739,6 +1782,7 @@ class Subdomain
         for (size_t t = 0; t < c.Q_row.size(); t++) subdomain_operator.Q.add_entry(c.Q_row[t], c.Q_col[t], c.Q_val[t]);
         subdomain_operator.Q.assemble();
         subdomain_operator.Q.transpose(subdomain_operator.Qt);
+        assembly.clear(); // the classes of another Qt
         subdomain_operator.num_dofs = c.sub_num_dofs;
         subdomain_operator.num_points = NP;
         subdomain_operator.num_extended_dofs = nse;

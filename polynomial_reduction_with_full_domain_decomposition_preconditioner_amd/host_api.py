@@ -447,6 +447,25 @@ class Problem:
         _H().call("fddh_problem_lean_line_info", self.h, ctypes.byref(on), ctypes.byref(ok), ctypes.byref(dom), ctypes.byref(lean), ctypes.byref(lists))
         return {"enabled": bool(on.value), "fine_domain_table_ok": bool(ok.value), "fine_domain": bool(dom.value), "sub_lists_lean": lean.value, "sub_lists": lists.value}
 
+    def assembly_info(self):
+        """flag "assemble_in_stiffness": is it on, is it in effect in the subdomain's dof-space operator (and why not),
+        Qt's rows and the region's points by class, the row blocks of the general rows' plan"""
+        on, eff, blocks = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        rows, points, why = (ctypes.c_longlong * 3)(), (ctypes.c_longlong * 5)(), ctypes.create_string_buffer(256)
+        _H().call("fddh_problem_assembly_info", self.h, ctypes.byref(on), ctypes.byref(eff), rows, points, ctypes.byref(blocks), why, len(why))
+        return {"enabled": bool(on.value), "in_effect": bool(eff.value), "why_not": why.value.decode(), "rows": dict(zip(("general", "single", "pair"), map(int, rows))),
+                "points": dict(zip(("general", "single", "pair_low", "pair_high", "none"), map(int, points))), "reduced_row_blocks": blocks.value}
+
+    def assembly_arrays(self):
+        """(point_class_dof, ptr, col, row_map): point_dof with the class of each point in bits 29..30, and the general rows
+        of Qt as a CSR of their own with their dofs"""
+        npts, nr, nz = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        _H().call("fddh_problem_assembly_arrays", self.h, ctypes.byref(npts), ctypes.byref(nr), ctypes.byref(nz), None, None, None, None)
+        pcd, ptr, col, rmap = np.zeros(npts.value, np.int32), np.zeros(nr.value + 1, np.int32), np.zeros(nz.value, np.int32), np.zeros(nr.value, np.int32)
+        ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        _H().call("fddh_problem_assembly_arrays", self.h, None, None, None, ip(pcd), ip(ptr), ip(col), ip(rmap))
+        return pcd, ptr, col, rmap
+
     def dssum(self, u, mask=True, weight=False):
         out = np.zeros(self.n)
         _H().call("fddh_problem_dssum", self.h, _dp(out), _dp(np.ascontiguousarray(u)), int(mask), int(weight))
