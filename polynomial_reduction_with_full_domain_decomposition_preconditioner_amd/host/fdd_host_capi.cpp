@@ -47,7 +47,7 @@ struct fddh_problem
 
     // The rank (= host thread) that built the problem: its device stream, communicator and globals are thread_local, so a
     // call from any other thread would silently run on the legacy default stream with a one-rank communicator (every
-    // collective skipped: wrong sums, or peers hanging in RCCL).  Every fddh_problem_* entry checks it (rank_check).
+    // collective skipped: wrong sums, or peers hanging in RCCL).  Every fddh_problem_* entry checks it first (on_problem).
     unsigned long long owner = 0; // device_t::rank_instance of that rank; never 0 for a finished problem
 
     // device staging vectors
@@ -70,6 +70,151 @@ static int rank_check(const fddh_problem *p = nullptr)
     return 0;
 }
 
+namespace
+{
+
+// the frame of every entry: what the body returns, or -1 with the text of what it threw
+template <typename Body>
+int guarded(Body &&body)
+{
+    try
+    {
+        return body();
+    }
+    catch (const std::exception &e)
+    {
+        return fail("%s", e.what());
+    }
+}
+
+// The opening of a fddh_problem_* entry, in this order: the calling thread is the problem's rank (rank_check); the problem
+// and the pointers the entry cannot do without are there (args_ok, which is formed before the rank is known and so must not
+// look into *p; refused with `refusal`); then the body on *p.  A test that needs *p is the body's own
+template <typename Problem, typename Body>
+int on_problem(Problem *p, bool args_ok, const char *refusal, Body &&body)
+{
+    return guarded([&] {
+        if (int rc = rank_check(p)) return rc;
+        if (!p || !args_ok) return fail("%s", refusal);
+        return body(*p);
+    });
+}
+
+template <typename Problem, typename Body>
+int on_problem(Problem *p, bool args_ok, Body &&body)
+{
+    return on_problem(p, args_ok, "null argument", body);
+}
+
+// the same for an entry that is about the Subdomain: the body gets *p and *p->subdomain
+template <typename Problem, typename Body>
+int on_subdomain(Problem *p, bool args_ok, Body &&body)
+{
+    return on_problem(p, args_ok, [&](Problem &pr) {
+        if (!pr.subdomain) return fail("problem was created without a Subdomain");
+        return body(pr, *pr.subdomain);
+    });
+}
+
+size_t fine_bytes(const fddh_problem &p) { return (size_t)p.fine().num_local_points * sizeof(double); }
+
+// a vector of the fine level's points in through p.a, op, its result out through p.b (out may be null: the result stays in p.b)
+template <typename Op>
+void fine_round_trip(fddh_problem &p, const double *in, double *out, Op &&op)
+{
+    p.a.copyFrom(in, fine_bytes(p));
+    op();
+    if (out) p.b.copyTo(out, fine_bytes(p));
+}
+
+// its counterpart for the Subdomain's vectors: in through p.sa, out through p.sb
+size_t sub_bytes(const fddh_problem &p) { return (size_t)p.subdomain->num_values * sizeof(double); }
+
+template <typename Op>
+void sub_round_trip(fddh_problem &p, const double *in, double *out, Op &&op)
+{
+    p.sa.copyFrom(in, sub_bytes(p));
+    op();
+    p.sb.copyTo(out, sub_bytes(p));
+}
+
+template <typename T>
+void copy_history(const std::vector<T> &h, double *history, int history_cap, int *num_history)
+{
+    const int nh = (int)h.size();
+    if (history)
+        for (int i = 0; i < nh && i < history_cap; i++) history[i] = h[i];
+    if (num_history) *num_history = nh;
+}
+
+// an entry that is about to run the inner solve: why the Chebyshev-Jacobi option cannot run on this problem as it is
+// configured (the flags may be set in any order, so this is looked at when a solve starts), or nullptr
+const char *inner_solver_refusal(const fddh_problem &p)
+{
+    if (!p.subdomain || !p.subdomain->chebyshev()) return nullptr;
+    return p.subdomain->chebyshev_refusal();
+}
+
+// the same for an outer solve, which runs the inner one where the preconditioner is in use
+const char *outer_solve_refusal(const fddh_problem &p)
+{
+    return p.subdomain && p.fine().use_preconditioner ? inner_solver_refusal(p) : nullptr;
+}
+
+// f(the problem's Subdomain) or f(no preconditioner): the callers differ in the test that chooses
+template <typename F>
+auto with_preconditioner(fddh_problem &p, bool use_subdomain, F &&f)
+{
+    if (use_subdomain) return f(*p.subdomain);
+    return f(p.none);
+}
+
+// fn() between finish + barrier (collective: every rank or none) and finish, the wall time into *seconds; seconds null: fn() alone
+template <typename Fn>
+void wall_timed(double *seconds, Fn &&fn)
+{
+    std::chrono::steady_clock::time_point t0;
+    if (seconds)
+    {
+        fdd::dev().finish();
+        fdd::comm().barrier();
+        t0 = std::chrono::steady_clock::now();
+    }
+    fn();
+    if (seconds)
+    {
+        fdd::dev().finish();
+        *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+}
+
+// What the outer solve entries share: the inner solver's refusal, f staged in, run(fine Domain, preconditioner) with the
+// problem's Subdomain or none -- from p.a into p.b, timed where seconds is given --, then u (where asked for) and the history out
+template <typename Run>
+int outer_solve(fddh_problem &p, const double *f, double *u, double *history, int history_cap, int *num_history, int *num_iterations, double *seconds, Run &&run)
+{
+    if (const char *why = outer_solve_refusal(p)) return fail("%s", why);
+    Domain<SType> &d = p.fine();
+    fine_round_trip(p, f, u, [&] {
+        wall_timed(seconds, [&] { with_preconditioner(p, p.subdomain != nullptr, [&](auto &preconditioner) { run(d, preconditioner); }); });
+    });
+    copy_history(d.residual_history, history, history_cap, num_history);
+    if (num_iterations) *num_iterations = d.num_iterations;
+    return 0;
+}
+
+// solver_id 0: flexible CG, else GMRES(m)
+template <typename Preconditioner>
+void krylov_solve(fddh_problem &p, Domain<SType> &d, Preconditioner &preconditioner, int solver_id)
+{
+    if (solver_id == 0)
+        d.flexible_conjugate_gradient(p.b, p.a, preconditioner);
+    else
+        d.generalized_minimum_residual(p.b, p.a, preconditioner);
+}
+
+} // namespace
+
 static std::vector<int> level_degrees(int N, int reduction)
 {
     std::vector<int> d;
@@ -90,14 +235,6 @@ static void setup_lap(const char *what, int degree, double &mark)
     const double t = setup_clock();
     if (on and fdd::comm().rank == 0) printf("setup: %-28s N = %-2d %8.3f s\n", what, degree, t - mark);
     mark = t;
-}
-
-// an entry that is about to run the inner solve: why the Chebyshev-Jacobi option cannot run on this problem as it is
-// configured (the flags may be set in any order, so this is looked at when a solve starts), or nullptr
-static const char *inner_solver_refusal(const fddh_problem *p)
-{
-    if (!p->subdomain || !p->subdomain->chebyshev()) return nullptr;
-    return p->subdomain->chebyshev_refusal();
 }
 
 static void finish_problem(fddh_problem *p, int flags, int sub_overlap, int sup_overlap)
@@ -127,14 +264,50 @@ static void finish_problem(fddh_problem *p, int flags, int sub_overlap, int sup_
     }
 }
 
+// fddh_comm_callbacks and _ex: the latter also needs, and hands on, exchange_bytes
+static int comm_callbacks(int rank, int size, void *ctx, fddh_allreduce_fn allreduce_sum_f64, fddh_allreduce_fn allreduce_max_f64, fddh_allgather_fn allgather_bytes, fddh_barrier_fn barrier, fddh_exchange_fn exchange_bytes, bool with_exchange)
+{
+    return guarded([&] {
+        if (int rc = rank_check()) return rc;
+        if (rank < 0 || size < 1 || rank >= size || !allreduce_sum_f64 || !allreduce_max_f64 || !allgather_bytes || !barrier || (with_exchange && !exchange_bytes)) return fail("bad callback set");
+        fdd::CommCallbacks cb;
+        cb.ctx = ctx;
+        cb.allreduce_sum_f64 = allreduce_sum_f64;
+        cb.allreduce_max_f64 = allreduce_max_f64;
+        cb.allgather_bytes = allgather_bytes;
+        cb.barrier = barrier;
+        cb.exchange_bytes = exchange_bytes;
+        fdd::set_comm(new fdd::CallbackComm(rank, size, cb));
+        fdd::globals().proc_id = rank;
+        fdd::globals().num_procs = size;
+        return 0;
+    });
+}
+
+// `iterations` launches of y = A x in milliseconds, timed with events on the stream after three launches to warm up
+static float spmv_ms(CSR_Matrix<SType> &A, fdd::memory &x, fdd::memory &y, int iterations)
+{
+    void *e0 = nullptr, *e1 = nullptr;
+    FDD_CALL(fdd_event_create(&e0));
+    FDD_CALL(fdd_event_create(&e1));
+    for (int i = 0; i < 3; i++) A.multiply(y, x);
+    FDD_CALL(fdd_event_record(e0, fdd::dev().stream));
+    for (int i = 0; i < iterations; i++) A.multiply(y, x);
+    FDD_CALL(fdd_event_record(e1, fdd::dev().stream));
+    float ms = 0.0f;
+    FDD_CALL(fdd_event_elapsed_ms(&ms, e0, e1));
+    FDD_CALL(fdd_event_destroy(e0));
+    FDD_CALL(fdd_event_destroy(e1));
+    return ms;
+}
+
 extern "C" {
 
 const char *fddh_last_error(void) { return g_err; }
 
 int fddh_init(int device, void *stream, int own_stream)
 {
-    try
-    {
+    return guarded([&] {
         if (fdd_set_device(device) != 0) return fail("fdd_set_device(%d): %s", device, fdd_last_error());
         if (own_stream)
         {
@@ -147,96 +320,62 @@ int fddh_init(int device, void *stream, int own_stream)
         if (!fdd::dev().initialised) fdd::dev().rank_instance = ++rank_instances; // a further fddh_init of a live rank changes its stream, not who it is
         fdd::dev().initialised = true;
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_set_print(int on)
 {
-    try
-    {
+    return guarded([&] {
         fdd::globals().print = on != 0;
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_set_timer(int on)
 {
-    try
-    {
+    return guarded([&] {
         fdd_timer().enabled = on != 0;
         if (on) fdd_timer().initialize();
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_timer_total(const char *key, double *seconds)
 {
-    try
-    {
+    return guarded([&] {
         if (!key || !seconds) return fail("null argument");
         *seconds = fdd_timer().total(key);
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_timer_total_over_ranks(const char *key, const char *aggregation, double *seconds)
 {
-    try
-    {
+    return guarded([&] {
         if (!key || !aggregation || !seconds) return fail("null argument");
         *seconds = fdd_timer().total(key, aggregation); // collective: all-reduce (max or sum) over the ranks, timer.tpp:67
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_comm_single(void)
 {
-    try
-    {
+    return guarded([&] {
         if (int rc = rank_check()) return rc;
         fdd::set_comm(new fdd::SingleComm());
         fdd::globals().proc_id = 0;
         fdd::globals().num_procs = 1;
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_local_world_create(void **world, int size)
 {
-    try
-    {
+    return guarded([&] {
         if (!world || size < 1) return fail("bad argument");
         *world = new std::shared_ptr<fdd::LocalWorld>(new fdd::LocalWorld(size));
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_local_world_destroy(void *world)
@@ -247,22 +386,16 @@ int fddh_local_world_destroy(void *world)
 
 int fddh_local_world_fail(void *world)
 {
-    try
-    {
+    return guarded([&] {
         if (!world) return fail("null argument");
         (*static_cast<std::shared_ptr<fdd::LocalWorld> *>(world))->fail();
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_rank_finalize(void)
 {
-    try
-    {
+    return guarded([&] {
         fdd::device_t &d = fdd::dev();
         if (!d.initialised) return 0;
         if (d.stream) fdd_stream_sync(d.stream);
@@ -273,17 +406,12 @@ int fddh_rank_finalize(void)
         d.initialised = false;
         d.rank_instance = 0; // the problems this rank built are nobody's now: every entry refuses them
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_comm_local(void *world, int rank)
 {
-    try
-    {
+    return guarded([&] {
         if (int rc = rank_check()) return rc;
         if (!world) return fail("null argument");
         std::shared_ptr<fdd::LocalWorld> w = *static_cast<std::shared_ptr<fdd::LocalWorld> *>(world);
@@ -292,32 +420,22 @@ int fddh_comm_local(void *world, int rank)
         fdd::globals().proc_id = rank;
         fdd::globals().num_procs = w->size;
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_comm_rccl_unique_id(char *out128)
 {
-    try
-    {
+    return guarded([&] {
         if (!out128) return fail("null argument");
         fdd::RcclComm tmp;
         tmp.unique_id(out128);
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_comm_rccl_init(const char *id128, int rank, int size)
 {
-    try
-    {
+    return guarded([&] {
         if (int rc = rank_check()) return rc;
         if (!id128 || rank < 0 || size < 1 || rank >= size) return fail("bad rank/size");
         fdd::RcclComm *c = new fdd::RcclComm();
@@ -326,67 +444,24 @@ int fddh_comm_rccl_init(const char *id128, int rank, int size)
         fdd::globals().proc_id = rank;
         fdd::globals().num_procs = size;
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_comm_callbacks(int rank, int size, void *ctx, fddh_allreduce_fn allreduce_sum_f64, fddh_allreduce_fn allreduce_max_f64, fddh_allgather_fn allgather_bytes, fddh_barrier_fn barrier)
 {
-    try
-    {
-        if (int rc = rank_check()) return rc;
-        if (rank < 0 || size < 1 || rank >= size || !allreduce_sum_f64 || !allreduce_max_f64 || !allgather_bytes || !barrier) return fail("bad callback set");
-        fdd::CommCallbacks cb;
-        cb.ctx = ctx;
-        cb.allreduce_sum_f64 = allreduce_sum_f64;
-        cb.allreduce_max_f64 = allreduce_max_f64;
-        cb.allgather_bytes = allgather_bytes;
-        cb.barrier = barrier;
-        cb.exchange_bytes = nullptr; // fddh_comm_callbacks_ex supplies it
-        fdd::set_comm(new fdd::CallbackComm(rank, size, cb));
-        fdd::globals().proc_id = rank;
-        fdd::globals().num_procs = size;
-        return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    return comm_callbacks(rank, size, ctx, allreduce_sum_f64, allreduce_max_f64, allgather_bytes, barrier, nullptr, false);
 }
 
 int fddh_comm_callbacks_ex(int rank, int size, void *ctx, fddh_allreduce_fn allreduce_sum_f64, fddh_allreduce_fn allreduce_max_f64, fddh_allgather_fn allgather_bytes, fddh_barrier_fn barrier, fddh_exchange_fn exchange_bytes)
 {
-    try
-    {
-        if (int rc = rank_check()) return rc;
-        if (rank < 0 || size < 1 || rank >= size || !allreduce_sum_f64 || !allreduce_max_f64 || !allgather_bytes || !barrier || !exchange_bytes) return fail("bad callback set");
-        fdd::CommCallbacks cb;
-        cb.ctx = ctx;
-        cb.allreduce_sum_f64 = allreduce_sum_f64;
-        cb.allreduce_max_f64 = allreduce_max_f64;
-        cb.allgather_bytes = allgather_bytes;
-        cb.barrier = barrier;
-        cb.exchange_bytes = exchange_bytes;
-        fdd::set_comm(new fdd::CallbackComm(rank, size, cb));
-        fdd::globals().proc_id = rank;
-        fdd::globals().num_procs = size;
-        return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    return comm_callbacks(rank, size, ctx, allreduce_sum_f64, allreduce_max_f64, allgather_bytes, barrier, exchange_bytes, true);
 }
 
 // Drives every collective of the active communicator once, bypassing the
 // "size == 1" shortcuts of the solver, and checks the results.
 int fddh_comm_selftest(int n)
 {
-    try
-    {
+    return guarded([&] {
         if (int rc = rank_check()) return rc;
         if (n < 1) return fail("n must be positive");
         fdd::Comm &c = fdd::comm();
@@ -475,40 +550,23 @@ int fddh_comm_selftest(int n)
         d.free();
         g.free();
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_comm_info(int *rank, int *size, char *name, size_t name_len)
 {
-    try
-    {
+    return guarded([&] {
         if (int rc = rank_check()) return rc;
         if (rank) *rank = fdd::comm().rank;
         if (size) *size = fdd::comm().size;
         if (name && name_len) snprintf(name, name_len, "%s", fdd::comm().name());
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_create_box(fddh_problem **out, const int E[3], const int P[3], int poly_degree, int poly_reduction, int with_subdomain)
 {
-    try
-    {
-        if (int rc = rank_check()) return rc;
-        return fddh_problem_create_box_ex(out, E, P, poly_degree, poly_reduction, 1, 1, with_subdomain ? FDDH_WITH_SUBDOMAIN : 0);
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    return fddh_problem_create_box_ex(out, E, P, poly_degree, poly_reduction, 1, 1, with_subdomain ? FDDH_WITH_SUBDOMAIN : 0);
 }
 
 int fddh_problem_create_box_ex(fddh_problem **out, const int E[3], const int P[3], int poly_degree, int poly_reduction, int subdomain_overlap, int superdomain_overlap, int flags)
@@ -518,8 +576,7 @@ int fddh_problem_create_box_ex(fddh_problem **out, const int E[3], const int P[3
 
 int fddh_problem_create_kershaw_ex(fddh_problem **out, const int E[3], const int P[3], int poly_degree, int poly_reduction, int subdomain_overlap, int superdomain_overlap, int flags, double eps_y, double eps_z)
 {
-    try
-    {
+    return guarded([&] {
         if (int rc = rank_check()) return rc;
         if (!(eps_y > 0.0 && eps_y <= 1.0 && eps_z > 0.0 && eps_z <= 1.0)) return fail("Kershaw eps must lie in (0, 1]");
         const int with_subdomain = flags & FDDH_WITH_SUBDOMAIN;
@@ -557,30 +614,17 @@ int fddh_problem_create_kershaw_ex(fddh_problem **out, const int E[3], const int
         finish_problem(p, flags, subdomain_overlap, superdomain_overlap);
         *out = p;
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_create_dir(fddh_problem **out, const char *directory, int poly_degree, int poly_reduction, int subdomain_overlap, int superdomain_overlap, int with_subdomain)
 {
-    try
-    {
-        if (int rc = rank_check()) return rc;
-        return fddh_problem_create_dir_ex(out, directory, poly_degree, poly_reduction, subdomain_overlap, superdomain_overlap, with_subdomain ? FDDH_WITH_SUBDOMAIN : 0);
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    return fddh_problem_create_dir_ex(out, directory, poly_degree, poly_reduction, subdomain_overlap, superdomain_overlap, with_subdomain ? FDDH_WITH_SUBDOMAIN : 0);
 }
 
 int fddh_problem_create_dir_ex(fddh_problem **out, const char *directory, int poly_degree, int poly_reduction, int subdomain_overlap, int superdomain_overlap, int flags)
 {
-    try
-    {
+    return guarded([&] {
         if (int rc = rank_check()) return rc;
         const int with_subdomain = flags & FDDH_WITH_SUBDOMAIN;
         if (!out || !directory || poly_degree < 1 || poly_reduction < 1) return fail("bad argument");
@@ -603,17 +647,12 @@ int fddh_problem_create_dir_ex(fddh_problem **out, const char *directory, int po
         finish_problem(p, flags, subdomain_overlap, superdomain_overlap);
         *out = p;
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_destroy(fddh_problem *p)
 {
-    try
-    {
+    return guarded([&] {
         if (int rc = rank_check(p)) return rc;
         // Like the reference (empty destructors, domain.tpp:24-28), device memory of
         // the host classes is released at process end; the staging vectors are freed.
@@ -626,11 +665,7 @@ int fddh_problem_destroy(fddh_problem *p)
         p->fine().projection.release();
         delete p;
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_write_box_mesh_files(const char *directory, const int E[3], const int P[3], int poly_degree, int rank)
@@ -640,8 +675,7 @@ int fddh_write_box_mesh_files(const char *directory, const int E[3], const int P
 
 int fddh_write_kershaw_mesh_files(const char *directory, const int E[3], const int P[3], int poly_degree, int rank, double eps_y, double eps_z)
 {
-    try
-    {
+    return guarded([&] {
         if (!directory || !E || !P) return fail("null argument");
         if (!(eps_y > 0.0 && eps_y <= 1.0 && eps_z > 0.0 && eps_z <= 1.0)) return fail("Kershaw eps must lie in (0, 1]");
         fdd::BoxSpec spec;
@@ -659,20 +693,13 @@ int fddh_write_kershaw_mesh_files(const char *directory, const int E[3], const i
         mkdir(sub, 0777);
         if (!Domain<SType>::write_mesh_files(directory, rank, m)) return fail("cannot write mesh files under '%s'", directory);
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_info(const fddh_problem *p, long long *info, int n)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !info) return fail("null argument");
-        const Domain<SType> &d = p->fine();
+    return on_problem(p, info != nullptr, [&](const fddh_problem &pr) {
+        const Domain<SType> &d = pr.fine();
         long long v[FDDH_INFO_COUNT];
         v[FDDH_INFO_NUM_LOCAL_POINTS] = d.num_local_points;
         v[FDDH_INFO_NUM_LOCAL_NODES] = d.num_local_nodes;
@@ -681,31 +708,22 @@ int fddh_problem_info(const fddh_problem *p, long long *info, int n)
         v[FDDH_INFO_NUM_TOTAL_NODES] = d.num_total_nodes;
         v[FDDH_INFO_NUM_TOTAL_ELEMENTS] = d.num_total_elements;
         v[FDDH_INFO_NUM_LOCAL_ELEMENTS] = d.num_local_elements;
-        v[FDDH_INFO_NUM_LEVELS] = (long long)p->degrees.size();
-        v[FDDH_INFO_SUB_NUM_VALUES] = p->subdomain ? p->subdomain->num_values : 0;
-        v[FDDH_INFO_SUB_NUM_DOFS] = p->subdomain ? p->subdomain->dofs() : 0;
+        v[FDDH_INFO_NUM_LEVELS] = (long long)pr.degrees.size();
+        v[FDDH_INFO_SUB_NUM_VALUES] = pr.subdomain ? pr.subdomain->num_values : 0;
+        v[FDDH_INFO_SUB_NUM_DOFS] = pr.subdomain ? pr.subdomain->dofs() : 0;
         v[FDDH_INFO_NUM_ITERATIONS] = d.num_iterations;
         v[FDDH_INFO_DIM] = d.mesh.dim;
         for (int i = 0; i < n && i < FDDH_INFO_COUNT; i++) info[i] = v[i];
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_sub_info(const fddh_problem *p, long long *info, int n)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !info) return fail("null argument");
-        if (!p->subdomain) return fail("problem was created without a Subdomain");
-        const Subdomain<PType> &s = *p->subdomain;
+    return on_subdomain(p, info != nullptr, [&](const fddh_problem &pr, const Subdomain<PType> &s) {
         const fdd::composite::Composite &c = s.composite_description();
         long long v[FDDH_SUB_INFO_COUNT];
-        const int own_elems = p->fine().num_local_elements, own_pts = p->fine().num_local_points;
+        const int own_elems = pr.fine().num_local_elements, own_pts = pr.fine().num_local_points;
         v[FDDH_SUB_IS_COMPOSITE] = s.composite() ? 1 : 0;
         v[FDDH_SUB_NUM_ELEMS] = s.composite() ? c.num_sub_elems : own_elems;
         v[FDDH_SUB_NUM_EXT_ELEMS] = s.composite() ? c.num_sub_ext_elems : own_elems;
@@ -722,21 +740,12 @@ int fddh_problem_sub_info(const fddh_problem *p, long long *info, int n)
         v[FDDH_SUB_NUM_PEERS] = s.composite() ? (long long)c.peers.size() : 0;
         for (int i = 0; i < n && i < FDDH_SUB_INFO_COUNT; i++) info[i] = v[i];
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_sub_region(const fddh_problem *p, int *element, int *level, int n)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !element || !level) return fail("null argument");
-        if (!p->subdomain) return fail("problem was created without a Subdomain");
-        const Subdomain<PType> &s = *p->subdomain;
+    return on_subdomain(p, element && level, [&](const fddh_problem &, const Subdomain<PType> &s) {
         if (!s.composite()) return fail("the region is the rank's own elements (no composite)");
         const fdd::composite::Composite &c = s.composite_description();
         if (n != c.num_sub_ext_elems) return fail("the region has %d elements", c.num_sub_ext_elems);
@@ -746,53 +755,33 @@ int fddh_problem_sub_region(const fddh_problem *p, int *element, int *level, int
             level[r] = c.sub[r].level;
         }
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_sub_composite_levels(const fddh_problem *p, int *kept, int n, int *num_levels)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !num_levels) return fail("null argument");
-        if (!p->subdomain) return fail("problem was created without a Subdomain");
-        const fdd::composite::Composite &c = p->subdomain->composite_description();
+    return on_subdomain(p, num_levels != nullptr, [&](const fddh_problem &, const Subdomain<PType> &s) {
+        const fdd::composite::Composite &c = s.composite_description();
         *num_levels = (int)c.comp_levels.size();
         for (int i = 0; i < n && i < *num_levels && kept; i++) kept[i] = c.comp_levels[i];
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_level_degree(const fddh_problem *p, int level, int *poly_degree)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !poly_degree || level < 0 || level >= (int)p->degrees.size()) return fail("bad level");
-        *poly_degree = p->degrees[level];
+    return on_problem(p, poly_degree != nullptr, "bad level", [&](const fddh_problem &pr) {
+        if (level < 0 || level >= (int)pr.degrees.size()) return fail("bad level");
+        *poly_degree = pr.degrees[level];
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_mesh_array(const fddh_problem *p, int level, const char *name, void *out, size_t bytes)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !name || !out || level < 0 || level >= (int)p->degrees.size()) return fail("bad argument");
-        const MeshData<SType> &m = p->domains.at(p->degrees[level]).mesh;
+    return on_problem(p, name && out, "bad argument", [&](const fddh_problem &pr) {
+        if (level < 0 || level >= (int)pr.degrees.size()) return fail("bad argument");
+        const MeshData<SType> &m = pr.domains.at(pr.degrees[level]).mesh;
         const void *src = nullptr;
         size_t have = 0;
         std::string s(name);
@@ -807,20 +796,13 @@ int fddh_problem_mesh_array(const fddh_problem *p, int level, const char *name, 
         if (bytes != have) return fail("mesh array '%s' has %zu bytes, caller gave %zu", name, have, bytes);
         memcpy(out, src, have);
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
-int fddh_problem_csr(const fddh_problem *cp, int which, int *num_rows, int *num_cols, int *num_nnz, int *ptr, int *col, double *val)
+int fddh_problem_csr(const fddh_problem *p, int which, int *num_rows, int *num_cols, int *num_nnz, int *ptr, int *col, double *val)
 {
-    try
-    {
-        if (!cp) return fail("null argument");
-        fddh_problem *p = const_cast<fddh_problem *>(cp);
-        CSR_Matrix<SType> &A = (which == 0) ? p->fine().scatter_matrix() : p->fine().gather_matrix();
+    return on_problem(const_cast<fddh_problem *>(p), true, [&](fddh_problem &pr) {
+        CSR_Matrix<SType> &A = (which == 0) ? pr.fine().scatter_matrix() : pr.fine().gather_matrix();
         if (num_rows) *num_rows = A.num_rows;
         if (num_cols) *num_cols = A.num_cols;
         if (num_nnz) *num_nnz = A.num_nnz;
@@ -828,105 +810,72 @@ int fddh_problem_csr(const fddh_problem *cp, int which, int *num_rows, int *num_
         if (col) memcpy(col, A.col_hst.data(), A.col_hst.size() * sizeof(int));
         if (val) memcpy(val, A.val_hst.data(), A.val_hst.size() * sizeof(double));
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
-int fddh_problem_assembled_weight(const fddh_problem *cp, double *out, int n)
+int fddh_problem_assembled_weight(const fddh_problem *p, double *out, int n)
 {
-    try
-    {
-        if (!cp || !out) return fail("null argument");
-        fddh_problem *p = const_cast<fddh_problem *>(cp);
-        if (n != p->fine().num_local_nodes) return fail("assembled_weight has %d entries", p->fine().num_local_nodes);
-        p->fine().assembled_weight_memory().copyTo(out, (size_t)n * sizeof(double));
+    return on_problem(const_cast<fddh_problem *>(p), out != nullptr, [&](fddh_problem &pr) {
+        if (n != pr.fine().num_local_nodes) return fail("assembled_weight has %d entries", pr.fine().num_local_nodes);
+        pr.fine().assembled_weight_memory().copyTo(out, (size_t)n * sizeof(double));
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_set_D_hat(fddh_problem *p, int level, const double *D_hat, int n)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !D_hat || level < 0 || level >= (int)p->degrees.size()) return fail("bad argument");
-        if (n != p->degrees[level] + 1) return fail("D_hat of level %d is %d x %d", level, p->degrees[level] + 1, p->degrees[level] + 1);
-        p->domains[p->degrees[level]].set_D_hat(D_hat, n);
-        p->fine().projection.clear(); // the basis and its images belong to the operator as it was
-        if (p->subdomain) p->subdomain->operator_changed(p->degrees[level], D_hat, n); // and so do the point-Jacobi diagonal and the Chebyshev bound
+    return on_problem(p, D_hat != nullptr, "bad argument", [&](fddh_problem &pr) {
+        if (level < 0 || level >= (int)pr.degrees.size()) return fail("bad argument");
+        if (n != pr.degrees[level] + 1) return fail("D_hat of level %d is %d x %d", level, pr.degrees[level] + 1, pr.degrees[level] + 1);
+        pr.domains[pr.degrees[level]].set_D_hat(D_hat, n);
+        pr.fine().projection.clear(); // the basis and its images belong to the operator as it was
+        if (pr.subdomain) pr.subdomain->operator_changed(pr.degrees[level], D_hat, n); // and so do the point-Jacobi diagonal and the Chebyshev bound
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_get_D_hat(const fddh_problem *p, int level, double *D_hat, int n)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !D_hat || level < 0 || level >= (int)p->degrees.size()) return fail("bad argument");
-        if (n != p->degrees[level] + 1) return fail("wrong size");
-        const std::vector<double> &D = p->domains.at(p->degrees[level]).D_hat_hst;
+    return on_problem(p, D_hat != nullptr, "bad argument", [&](const fddh_problem &pr) {
+        if (level < 0 || level >= (int)pr.degrees.size()) return fail("bad argument");
+        if (n != pr.degrees[level] + 1) return fail("wrong size");
+        const std::vector<double> &D = pr.domains.at(pr.degrees[level]).D_hat_hst;
         memcpy(D_hat, D.data(), D.size() * sizeof(double));
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_set_options(fddh_problem *p, int max_iterations, double tolerance, int num_vectors, int use_preconditioner, int preconditioner_type, int sub_num_vectors, int sub_max_iterations, int sub_build_tree)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p) return fail("null argument");
-        Domain<SType> &d = p->fine();
+    return on_problem(p, true, [&](fddh_problem &pr) {
+        Domain<SType> &d = pr.fine();
         if (max_iterations >= 0) d.max_iterations = max_iterations;
         if (!std::isnan(tolerance) && tolerance >= 0.0) d.tolerance = tolerance;
         if (num_vectors > 0) d.num_vectors = num_vectors;
         if (use_preconditioner >= 0)
         {
-            if (use_preconditioner && !p->subdomain) return fail("problem was created without a Subdomain");
+            if (use_preconditioner && !pr.subdomain) return fail("problem was created without a Subdomain");
             d.use_preconditioner = use_preconditioner != 0;
         }
         if (preconditioner_type >= 0) d.preconditioner_type = preconditioner_type;
-        if (p->subdomain)
+        if (pr.subdomain)
         {
-            if (sub_num_vectors > 0) p->subdomain->num_vectors = sub_num_vectors;
-            if (sub_max_iterations >= 0) p->subdomain->max_iterations = sub_max_iterations;
-            if (sub_build_tree >= 0) p->subdomain->build_tree = sub_build_tree != 0;
+            if (sub_num_vectors > 0) pr.subdomain->num_vectors = sub_num_vectors;
+            if (sub_max_iterations >= 0) pr.subdomain->max_iterations = sub_max_iterations;
+            if (sub_build_tree >= 0) pr.subdomain->build_tree = sub_build_tree != 0;
         }
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_affine_info(fddh_problem *p, int *fine_domain_affine, int *sub_lists_affine, int *sub_lists, double *max_deviation)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p) return fail("null argument");
-        Domain<SType> &dom = p->fine();
+    return on_problem(p, true, [&](fddh_problem &pr) {
+        Domain<SType> &dom = pr.fine();
         double worst = dom.operator_list().affine_deviation;
         int lists = 0, affine = 0;
-        if (p->subdomain)
-            for (auto &ll : p->subdomain->operator_lists())
+        if (pr.subdomain)
+            for (auto &ll : pr.subdomain->operator_lists())
             {
                 lists++;
                 if (ll.affine) affine++;
@@ -937,11 +886,7 @@ int fddh_problem_affine_info(fddh_problem *p, int *fine_domain_affine, int *sub_
         if (sub_lists) *sub_lists = lists;
         if (max_deviation) *max_deviation = worst;
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 // what the five fddh_problem_*_info entries of the stiffness flags have in common: the flag, whether the fine Domain's list and
@@ -949,22 +894,15 @@ int fddh_problem_affine_info(fddh_problem *p, int *fine_domain_affine, int *sub_
 // number of lists.  more(list): what an entry reports beyond that, from the fine Domain's list
 static int stiffness_info(fddh_problem *p, const char *flag, bool (fdd::StiffnessChoice::*is)() const, int *enabled, int *fine_domain, int *sub_lists_on, int *sub_lists, const std::function<void(const fdd::LevelList &)> &more = nullptr)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p) return fail("null argument");
-        Domain<SType> &dom = p->fine();
+    return on_problem(p, true, [&](fddh_problem &pr) {
+        Domain<SType> &dom = pr.fine();
         if (enabled) *enabled = fdd::stiffness_flag(dom.stiffness, flag) ? 1 : 0;
         if (fine_domain) *fine_domain = (dom.operator_choice().*is)() ? 1 : 0;
         if (more) more(dom.operator_list());
-        if (sub_lists_on) *sub_lists_on = p->subdomain ? p->subdomain->count_lists(is) : 0;
-        if (sub_lists) *sub_lists = p->subdomain ? (int)p->subdomain->operator_lists().size() : 0;
+        if (sub_lists_on) *sub_lists_on = pr.subdomain ? pr.subdomain->count_lists(is) : 0;
+        if (sub_lists) *sub_lists = pr.subdomain ? (int)pr.subdomain->operator_lists().size() : 0;
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_zero_factor_info(fddh_problem *p, int *enabled, int *fine_domain_diag, int *sub_lists_diag, int *sub_lists)
@@ -998,12 +936,7 @@ int fddh_problem_lean_line_info(fddh_problem *p, int *enabled, int *fine_domain_
 
 int fddh_problem_assembly_info(fddh_problem *p, int *enabled, int *in_effect, long long *rows, long long *points, int *reduced_row_blocks, char *why_not, size_t why_not_len)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p) return fail("null argument");
-        if (!p->subdomain) return fail("problem was created without a Subdomain");
-        Subdomain<SType> &sub = *p->subdomain;
+    return on_subdomain(p, true, [&](fddh_problem &, Subdomain<PType> &sub) {
         if (enabled) *enabled = sub.stiffness.assemble_in_stiffness ? 1 : 0;
         const char *obstacle = sub.assembly_obstacle();
         if (!sub.assembly.built) sub.assembly_build(); // the classes are reported whether they are used or not
@@ -1013,21 +946,12 @@ int fddh_problem_assembly_info(fddh_problem *p, int *enabled, int *in_effect, lo
         if (reduced_row_blocks) *reduced_row_blocks = sub.assembly.reduced_blocks;
         if (why_not && why_not_len > 0) snprintf(why_not, why_not_len, "%s", obstacle ? obstacle : "");
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_assembly_arrays(fddh_problem *p, int *num_points, int *num_rows, int *num_nnz, int *point_class_dof, int *ptr, int *col, int *row_map)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p) return fail("null argument");
-        if (!p->subdomain) return fail("problem was created without a Subdomain");
-        Subdomain<SType> &sub = *p->subdomain;
+    return on_subdomain(p, true, [&](fddh_problem &, Subdomain<PType> &sub) {
         if (!sub.assembly.built) sub.assembly_build();
         const fdd::AssemblyClasses &a = sub.assembly;
         if (!a.unusable.empty()) return fail("no classes: %s", a.unusable.c_str());
@@ -1039,232 +963,257 @@ int fddh_problem_assembly_arrays(fddh_problem *p, int *num_points, int *num_rows
         if (col) std::copy(a.col.begin(), a.col.end(), col);
         if (row_map) std::copy(a.row_map.begin(), a.row_map.end(), row_map);
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
+}
+
+// ---- fddh_problem_set_flag ----
+// Three tables, asked in this order: the flags that only switch a member on or off (here), the flags that choose between the
+// stiffness kernels (fdd::stiffness_flag_row, element_operator.hpp) and the flags that check a range, need an entry of the
+// kernel library, rebuild a hierarchy, clear the projection or refuse a problem without a Subdomain (coded_flag_row below).
+
+// flag name -> the member it assigns `value != 0` to on every Domain (or none) and on the Subdomain (or none).  A row that
+// only names a Subdomain member is accepted, and does nothing, on a problem without one
+struct PlainFlagRow
+{
+    const char *name;
+    bool Domain<SType>::*domain;
+    bool Subdomain<PType>::*subdomain;
+};
+
+static const PlainFlagRow *plain_flag_row(const std::string &flag)
+{
+    typedef Domain<SType> D;
+    typedef Subdomain<PType> S;
+    static const PlainFlagRow table[] = {
+        {"fused_dssum", &D::fused_dssum, &S::fused_dssum},
+        {"restructured_inner_solve", &D::restructured_outer, &S::restructured}, // and the same restructure of the outer GMRES
+        // gs_add on the boundary prefix as grouped sends / receives between the ranks that share nodes (default) or as
+        // the dense interface-slot all-reduce; must be set alike on every rank
+        {"neighbour_interface_exchange", &D::neighbour_interface_exchange, nullptr},
+        // the coarse level's blocks inside the ring pull's group (default) or as an all-gather of their own; alike on every rank
+        {"fold_coarse_exchange", nullptr, &S::fold_coarse_exchange},
+        {"assembled_outer_solve", &D::assembled_outer, nullptr},
+        {"shared_residual_norm", &D::shared_residual_norm, nullptr},
+        {"skip_last_basis_store", nullptr, &S::skip_last_basis_store},
+        {"early_gamma", &D::early_gamma, nullptr},
+        {"unit_stitch_in_place", &D::unit_stitch_in_place, nullptr},
+        {"fused_update_flexible_dot", &D::fused_update_flexible_dot, nullptr},
+        {"lazy_steps", &D::lazy_steps, nullptr},
+        {"device_bookkeeping", &D::device_scalars, &S::device_bookkeeping},
+        {"assembled_inner_solve", nullptr, &S::assembled_inner},
+    };
+    for (const PlainFlagRow &row : table)
+        if (flag == row.name) return &row;
+    return nullptr;
+}
+
+// build the FEM matrix and the lattice levels of the AMG hierarchy in HBM (Subdomain::amg_build); needs the
+// fdd_amg_setup_* entries of the kernel library
+static int set_amg_device_setup(fddh_problem &p, const char *, int value)
+{
+    if (value != 0)
+        if (const char *missing = fdd::missing_amg_setup_entry()) return fail("amg_device_setup needs %s, which the loaded kernel library does not export", missing);
+    p.subdomain->amg_device_setup = value != 0;
+    return 0;
+}
+
+static int set_sub_use_preconditioner(fddh_problem &p, const char *, int value)
+{
+    p.subdomain->use_preconditioner = value == 1;
+    p.subdomain->use_jacobi = value == 2;
+    return 0;
+}
+
+// an option of this build: elements that are affine images of the reference cube do not stream their factor
+// arrays (element_operator.hpp); only where the mesh's own arrays have that form (fddh_problem_affine_info)
+static int set_affine_geometry(fddh_problem &p, const char *, int value)
+{
+    for (auto &kv : p.domains) kv.second.set_affine_geometry(value != 0);
+    if (p.subdomain) p.subdomain->set_affine_geometry(value != 0);
+    p.fine().projection.clear(); // the operator's arithmetic changes under the stored images
+    if (p.subdomain) p.subdomain->operator_changed();
+    return 0;
+}
+
+// the projection's passes as single launches of csrc/fdd_projection.hip (default where the kernel library has
+// them) or composed from the multi-vector entries (projection.hpp); the basis stays
+static int set_fused_projection(fddh_problem &p, const char *, int value)
+{
+    if (value != 0)
+        if (const char *missing = fdd::missing_projection_entry()) return fail("fused_projection needs %s, which the loaded kernel library does not export", missing);
+    p.fine().projection.fused = value != 0;
+    return 0;
+}
+
+// 0: the inner FCG / GMRES(m) (set_options' preconditioner_type); 1: the Chebyshev-Jacobi iteration (an option of this
+// build, Subdomain::chebyshev_dofs), which takes the place of either.  What it cannot run on is refused when a solve starts.
+static int set_inner_solver(fddh_problem &p, const char *, int value)
+{
+    if (value != 0 && value != 1) return fail("inner_solver is 0 (FCG / GMRES) or 1 (Chebyshev-Jacobi)");
+    p.subdomain->inner_solver = value;
+    return 0;
+}
+
+static int set_inner_chebyshev_order(fddh_problem &p, const char *, int value)
+{
+    if (value < 1 || value > 16) return fail("inner_chebyshev_order must lie in 1..16, got %d", value);
+    p.subdomain->cheby.order = value;
+    return 0;
+}
+
+static int set_inner_chebyshev_lower_permille(fddh_problem &p, const char *, int value)
+{
+    if (value < 1 || value > 999) return fail("inner_chebyshev_lower_permille must lie in 1..999, got %d", value);
+    if (!(value / 1000.0 < p.subdomain->cheby.upper)) return fail("inner_chebyshev_lower_permille %d is not below the upper factor %g", value, p.subdomain->cheby.upper);
+    p.subdomain->cheby.lower = value / 1000.0;
+    return 0;
+}
+
+// chebyshev_kernels: a step of the Chebyshev-Jacobi solve as one launch of fdd_cheby_step (default where the kernel
+// library has it) or, 0, composed from vector_vector_addition / vector_diagonal_scaling_dev.  fused_chebyshev: the step
+// as the epilogue of the gather in front of it where that applies (default likewise); 0: gather, then the step.
+static int set_chebyshev_kernels(fddh_problem &p, const char *name, int value)
+{
+    const bool fused = strcmp(name, "fused_chebyshev") == 0;
+    if (value != 0)
+        if (const char *missing = fdd::missing_chebyshev_entry(fused)) return fail("%s needs %s, which the loaded kernel library does not export", name, missing);
+    (fused ? p.subdomain->cheby.fused : p.subdomain->cheby.use_kernels) = value != 0;
+    return 0;
+}
+
+static int set_amg_graph(fddh_problem &p, const char *, int value)
+{
+    if (p.subdomain) p.subdomain->amg_hierarchy.use_graph = value != 0;
+    return 0;
+}
+
+static int set_amg_fused_smoother(fddh_problem &p, const char *, int value)
+{
+    if (p.subdomain) p.subdomain->amg_hierarchy.set_fused_smoother(value != 0);
+    return 0;
+}
+
+// the interpolator of a geometric level applied from the lattice's weight table (fdd_lattice_prolong / _restrict)
+// instead of as two SpMVs; 0: the CSR interpolator on every level (the same operator, sums in the CSR order)
+static int set_amg_matrix_free_transfer(fddh_problem &p, const char *, int value)
+{
+    if (p.subdomain) p.subdomain->amg_hierarchy.set_matrix_free_transfer(value != 0);
+    return 0;
+}
+
+// the reference's PTYPE = Float (config.hpp:19-20): 64 or 32 for the whole inner solve (Krylov vectors, element
+// stiffness, gather, V-cycle)
+static int set_preconditioner_precision(fddh_problem &p, const char *, int value)
+{
+    if (p.subdomain and not p.subdomain->set_precision(value)) return fail("preconditioner_precision is 64 or 32 (32: 3-D regions on the dof-space inner solve, Chebyshev order >= 2)");
+    return 0;
+}
+
+// subdomain.hpp:236 `num_vcycles` (run.py:154 rewrites the line and rebuilds; here a run-time switch)
+static int set_amg_num_vcycles(fddh_problem &p, const char *, int value)
+{
+    if (value < 1 || value > 16) return fail("amg_num_vcycles must lie in 1..16");
+    p.subdomain->num_vcycles = value;
+    p.subdomain->amg_hierarchy.set_num_vcycles(value);
+    return 0;
+}
+
+// subdomain.hpp:237 `cheby_order` (run.py:155; clamped to 1..4 by subdomain.tpp:3477-3478).  The smoother's
+// coefficients are computed when the hierarchy is built: set it before (fddh_problem_amg_build / first solve)
+static int set_amg_cheby_order(fddh_problem &p, const char *, int value)
+{
+    if (value < 1 || value > 4) return fail("amg_cheby_order must lie in 1..4 (subdomain.tpp:3477-3478)");
+    // -- or afterwards where the hierarchy is fddh_problem_amg_build's own: it is built again with the options of that
+    // build.  One that was handed in level by level carries the caller's coefficients and cannot follow.
+    Subdomain<PType> &sub = *p.subdomain;
+    if (value == sub.cheby_order) return 0;
+    if (value < 2 && (sub.amg_hierarchy.precision == 32 || sub.precision == 32)) return fail("amg_cheby_order %d: the 32-bit V-cycle (amg_precision / preconditioner_precision 32) needs a Chebyshev order of at least 2", value);
+    if (sub.amg_hierarchy.ready() && !sub.amg_built_here) return fail("amg_cheby_order cannot change once a hierarchy has been handed in (fddh_problem_amg_add_level): its coefficients are the caller's");
+    sub.cheby_order = value;
+    if (sub.amg_hierarchy.ready()) sub.amg_rebuild();
+    return 0;
+}
+
+// AMG/config.hpp:4 `Float`: 64 (double) or 32 (float)
+static int set_amg_precision(fddh_problem &p, const char *, int value)
+{
+    if (p.subdomain and not p.subdomain->amg_hierarchy.set_precision(value)) return fail("amg_precision is 64 or 32 (32 needs a Chebyshev order of at least 2)");
+    return 0;
+}
+
+// flag name -> the function that sets it, and whether a problem without a Subdomain refuses the flag (before the function runs)
+struct CodedFlagRow
+{
+    const char *name;
+    bool needs_subdomain;
+    int (*set)(fddh_problem &p, const char *name, int value);
+};
+
+static const CodedFlagRow *coded_flag_row(const std::string &flag)
+{
+    static const CodedFlagRow table[] = {
+        {"amg_device_setup", true, set_amg_device_setup},
+        {"sub_use_preconditioner", true, set_sub_use_preconditioner},
+        {"affine_geometry", false, set_affine_geometry},
+        {"fused_projection", false, set_fused_projection},
+        {"inner_solver", true, set_inner_solver},
+        {"inner_chebyshev_order", true, set_inner_chebyshev_order},
+        {"inner_chebyshev_lower_permille", true, set_inner_chebyshev_lower_permille},
+        {"chebyshev_kernels", true, set_chebyshev_kernels},
+        {"fused_chebyshev", true, set_chebyshev_kernels},
+        {"amg_graph", false, set_amg_graph},
+        {"amg_fused_smoother", false, set_amg_fused_smoother},
+        {"amg_matrix_free_transfer", false, set_amg_matrix_free_transfer},
+        {"preconditioner_precision", false, set_preconditioner_precision},
+        {"amg_num_vcycles", true, set_amg_num_vcycles},
+        {"amg_cheby_order", true, set_amg_cheby_order},
+        {"amg_precision", false, set_amg_precision},
+    };
+    for (const CodedFlagRow &row : table)
+        if (flag == row.name) return &row;
+    return nullptr;
 }
 
 int fddh_problem_set_flag(fddh_problem *p, const char *name, int value)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !name) return fail("null argument");
+    return on_problem(p, name != nullptr, [&](fddh_problem &pr) {
         const std::string s(name);
-        if (s == "fused_dssum")
+        if (const PlainFlagRow *row = plain_flag_row(s))
         {
-            for (auto &kv : p->domains) kv.second.fused_dssum = value != 0;
-            if (p->subdomain) p->subdomain->fused_dssum = value != 0;
-        }
-        else if (s == "restructured_inner_solve")
-        {
-            if (p->subdomain) p->subdomain->restructured = value != 0;
-            for (auto &kv : p->domains) kv.second.restructured_outer = value != 0; // the same restructure of the outer GMRES
-        }
-        else if (s == "neighbour_interface_exchange")
-        {
-            // gs_add on the boundary prefix as grouped sends / receives between the ranks that share nodes (default) or as
-            // the dense interface-slot all-reduce; must be set alike on every rank
-            for (auto &kv : p->domains) kv.second.neighbour_interface_exchange = value != 0;
-        }
-        else if (s == "fold_coarse_exchange")
-        {
-            // the coarse level's blocks inside the ring pull's group (default) or as an all-gather of their own; alike on every rank
-            if (p->subdomain) p->subdomain->fold_coarse_exchange = value != 0;
-        }
-        else if (s == "assembled_outer_solve")
-        {
-            for (auto &kv : p->domains) kv.second.assembled_outer = value != 0;
-        }
-        else if (s == "shared_residual_norm")
-        {
-            for (auto &kv : p->domains) kv.second.shared_residual_norm = value != 0;
-        }
-        else if (s == "skip_last_basis_store")
-        {
-            if (p->subdomain) p->subdomain->skip_last_basis_store = value != 0;
-        }
-        else if (s == "early_gamma")
-        {
-            for (auto &kv : p->domains) kv.second.early_gamma = value != 0;
-        }
-        else if (s == "unit_stitch_in_place")
-        {
-            for (auto &kv : p->domains) kv.second.unit_stitch_in_place = value != 0;
-        }
-        else if (s == "fused_update_flexible_dot")
-        {
-            for (auto &kv : p->domains) kv.second.fused_update_flexible_dot = value != 0;
-        }
-        else if (s == "lazy_steps")
-        {
-            for (auto &kv : p->domains) kv.second.lazy_steps = value != 0;
-        }
-        else if (s == "device_bookkeeping")
-        {
-            if (p->subdomain) p->subdomain->device_bookkeeping = value != 0;
-            for (auto &kv : p->domains) kv.second.device_scalars = value != 0;
-        }
-        else if (s == "assembled_inner_solve")
-        {
-            if (p->subdomain) p->subdomain->assembled_inner = value != 0;
-        }
-        else if (s == "amg_device_setup")
-        {
-            // build the FEM matrix and the lattice levels of the AMG hierarchy in HBM (Subdomain::amg_build); needs the
-            // fdd_amg_setup_* entries of the kernel library
-            if (!p->subdomain) return fail("problem was created without a Subdomain");
-            if (value != 0)
-                if (const char *missing = fdd::missing_amg_setup_entry()) return fail("amg_device_setup needs %s, which the loaded kernel library does not export", missing);
-            p->subdomain->amg_device_setup = value != 0;
-        }
-        else if (s == "sub_use_preconditioner")
-        {
-            if (!p->subdomain) return fail("problem was created without a Subdomain");
-            p->subdomain->use_preconditioner = value == 1;
-            p->subdomain->use_jacobi = value == 2;
-        }
-        else if (s == "affine_geometry")
-        {
-            // an option of this build: elements that are affine images of the reference cube do not stream their factor
-            // arrays (element_operator.hpp); only where the mesh's own arrays have that form (fddh_problem_affine_info)
-            for (auto &kv : p->domains) kv.second.set_affine_geometry(value != 0);
-            if (p->subdomain) p->subdomain->set_affine_geometry(value != 0);
-            p->fine().projection.clear(); // the operator's arithmetic changes under the stored images
-            if (p->subdomain) p->subdomain->operator_changed();
+            if (row->domain)
+                for (auto &kv : pr.domains) kv.second.*row->domain = value != 0;
+            if (row->subdomain && pr.subdomain) (*pr.subdomain).*row->subdomain = value != 0;
         }
         else if (fdd::stiffness_flag_row(s))
         {
             // the flags that choose between the stiffness kernels: what each does, the entries it needs and why none of them
             // empties what hangs on the operator are in element_operator.hpp (StiffnessFlags).  Refused before anything is written
-            for (auto &kv : p->domains) fdd::set_stiffness_flag(kv.second.stiffness, s, value != 0);
-            if (p->subdomain) fdd::set_stiffness_flag(p->subdomain->stiffness, s, value != 0);
+            for (auto &kv : pr.domains) fdd::set_stiffness_flag(kv.second.stiffness, s, value != 0);
+            if (pr.subdomain) fdd::set_stiffness_flag(pr.subdomain->stiffness, s, value != 0);
         }
-        else if (s == "fused_projection")
+        else if (const CodedFlagRow *coded = coded_flag_row(s))
         {
-            // the projection's passes as single launches of csrc/fdd_projection.hip (default where the kernel library has
-            // them) or composed from the multi-vector entries (projection.hpp); the basis stays
-            if (value != 0)
-                if (const char *missing = fdd::missing_projection_entry()) return fail("fused_projection needs %s, which the loaded kernel library does not export", missing);
-            p->fine().projection.fused = value != 0;
-        }
-        else if (s == "inner_solver")
-        {
-            // 0: the inner FCG / GMRES(m) (set_options' preconditioner_type); 1: the Chebyshev-Jacobi iteration (an option of this
-            // build, Subdomain::chebyshev_dofs), which takes the place of either.  What it cannot run on is refused when a solve starts.
-            if (!p->subdomain) return fail("problem was created without a Subdomain");
-            if (value != 0 && value != 1) return fail("inner_solver is 0 (FCG / GMRES) or 1 (Chebyshev-Jacobi)");
-            p->subdomain->inner_solver = value;
-        }
-        else if (s == "inner_chebyshev_order")
-        {
-            if (!p->subdomain) return fail("problem was created without a Subdomain");
-            if (value < 1 || value > 16) return fail("inner_chebyshev_order must lie in 1..16, got %d", value);
-            p->subdomain->cheby.order = value;
-        }
-        else if (s == "inner_chebyshev_lower_permille")
-        {
-            if (!p->subdomain) return fail("problem was created without a Subdomain");
-            if (value < 1 || value > 999) return fail("inner_chebyshev_lower_permille must lie in 1..999, got %d", value);
-            if (!(value / 1000.0 < p->subdomain->cheby.upper)) return fail("inner_chebyshev_lower_permille %d is not below the upper factor %g", value, p->subdomain->cheby.upper);
-            p->subdomain->cheby.lower = value / 1000.0;
-        }
-        else if (s == "chebyshev_kernels" || s == "fused_chebyshev")
-        {
-            // chebyshev_kernels: a step of the Chebyshev-Jacobi solve as one launch of fdd_cheby_step (default where the kernel
-            // library has it) or, 0, composed from vector_vector_addition / vector_diagonal_scaling_dev.  fused_chebyshev: the step
-            // as the epilogue of the gather in front of it where that applies (default likewise); 0: gather, then the step.
-            if (!p->subdomain) return fail("problem was created without a Subdomain");
-            const bool fused = s == "fused_chebyshev";
-            if (value != 0)
-                if (const char *missing = fdd::missing_chebyshev_entry(fused)) return fail("%s needs %s, which the loaded kernel library does not export", name, missing);
-            (fused ? p->subdomain->cheby.fused : p->subdomain->cheby.use_kernels) = value != 0;
-        }
-        else if (s == "amg_graph")
-        {
-            if (p->subdomain) p->subdomain->amg_hierarchy.use_graph = value != 0;
-        }
-        else if (s == "amg_fused_smoother")
-        {
-            if (p->subdomain) p->subdomain->amg_hierarchy.set_fused_smoother(value != 0);
-        }
-        else if (s == "amg_matrix_free_transfer")
-        {
-            // the interpolator of a geometric level applied from the lattice's weight table (fdd_lattice_prolong / _restrict)
-            // instead of as two SpMVs; 0: the CSR interpolator on every level (the same operator, sums in the CSR order)
-            if (p->subdomain) p->subdomain->amg_hierarchy.set_matrix_free_transfer(value != 0);
-        }
-        else if (s == "preconditioner_precision")
-        {
-            // the reference's PTYPE = Float (config.hpp:19-20): 64 or 32 for the whole inner solve (Krylov vectors, element
-            // stiffness, gather, V-cycle)
-            if (p->subdomain and not p->subdomain->set_precision(value)) return fail("preconditioner_precision is 64 or 32 (32: 3-D regions on the dof-space inner solve, Chebyshev order >= 2)");
-        }
-        else if (s == "amg_num_vcycles")
-        {
-            // subdomain.hpp:236 `num_vcycles` (run.py:154 rewrites the line and rebuilds; here a run-time switch)
-            if (!p->subdomain) return fail("problem was created without a Subdomain");
-            if (value < 1 || value > 16) return fail("amg_num_vcycles must lie in 1..16");
-            p->subdomain->num_vcycles = value;
-            p->subdomain->amg_hierarchy.set_num_vcycles(value);
-        }
-        else if (s == "amg_cheby_order")
-        {
-            // subdomain.hpp:237 `cheby_order` (run.py:155; clamped to 1..4 by subdomain.tpp:3477-3478).  The smoother's
-            // coefficients are computed when the hierarchy is built: set it before (fddh_problem_amg_build / first solve)
-            if (!p->subdomain) return fail("problem was created without a Subdomain");
-            if (value < 1 || value > 4) return fail("amg_cheby_order must lie in 1..4 (subdomain.tpp:3477-3478)");
-            // -- or afterwards where the hierarchy is fddh_problem_amg_build's own: it is built again with the options of that
-            // build.  One that was handed in level by level carries the caller's coefficients and cannot follow.
-            Subdomain<PType> &sub = *p->subdomain;
-            if (value == sub.cheby_order) return 0;
-            if (value < 2 && (sub.amg_hierarchy.precision == 32 || sub.precision == 32)) return fail("amg_cheby_order %d: the 32-bit V-cycle (amg_precision / preconditioner_precision 32) needs a Chebyshev order of at least 2", value);
-            if (sub.amg_hierarchy.ready() && !sub.amg_built_here) return fail("amg_cheby_order cannot change once a hierarchy has been handed in (fddh_problem_amg_add_level): its coefficients are the caller's");
-            sub.cheby_order = value;
-            if (sub.amg_hierarchy.ready()) sub.amg_rebuild();
-        }
-        else if (s == "amg_precision")
-        {
-            // AMG/config.hpp:4 `Float`: 64 (double) or 32 (float)
-            if (p->subdomain and not p->subdomain->amg_hierarchy.set_precision(value)) return fail("amg_precision is 64 or 32 (32 needs a Chebyshev order of at least 2)");
+            if (coded->needs_subdomain && !pr.subdomain) return fail("problem was created without a Subdomain");
+            return coded->set(pr, name, value);
         }
         else
             return fail("unknown flag '%s'", name);
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_sub_point_dofs(const fddh_problem *p, int *dof, int n)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !dof) return fail("null argument");
-        if (!p->subdomain) return fail("problem was created without a Subdomain");
-        if (n != (int)p->subdomain->point_dof.size()) return fail("the subdomain region has %d points", (int)p->subdomain->point_dof.size());
-        memcpy(dof, p->subdomain->point_dof.data(), (size_t)n * sizeof(int));
+    return on_subdomain(p, dof != nullptr, [&](const fddh_problem &, const Subdomain<PType> &s) {
+        if (n != (int)s.point_dof.size()) return fail("the subdomain region has %d points", (int)s.point_dof.size());
+        memcpy(dof, s.point_dof.data(), (size_t)n * sizeof(int));
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_amg_add_level(fddh_problem *p, int n, const int *A_ptr, const int *A_col, const double *A_val, const double *D_val, const double *coefs, int num_coefs, int n_coarse, const int *P_ptr, const int *P_col, const double *P_val)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !A_ptr || !A_col || !A_val || !D_val || !coefs) return fail("null argument");
-        if (!p->subdomain) return fail("problem was created without a Subdomain");
-        Subdomain<SType> &s = *p->subdomain;
+    return on_subdomain(p, A_ptr && A_col && A_val && D_val && coefs, [&](fddh_problem &, Subdomain<PType> &s) {
         if (s.amg_hierarchy.ready()) return fail("the AMG hierarchy is already finalized");
         if (num_coefs != s.cheby_order) return fail("cheby_order is %d, got %d coefficients", s.cheby_order, num_coefs);
         if (s.amg_hierarchy.levels.empty() && n != s.dofs()) return fail("the finest AMG level must have the subdomain's %d dofs, got %d", s.dofs(), n);
@@ -1277,113 +1226,71 @@ int fddh_problem_amg_add_level(fddh_problem *p, int n, const int *A_ptr, const i
         if ((P_ptr != nullptr) != (n_coarse > 0)) return fail("n_coarse > 0 exactly when a prolongation is given");
         s.amg_add_level(n, A_ptr, A_col, A_val, D_val, coefs, n_coarse, P_ptr, P_col, P_val);
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_amg_finalize(fddh_problem *p)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p) return fail("null argument");
-        if (!p->subdomain) return fail("problem was created without a Subdomain");
-        if (p->subdomain->amg_hierarchy.levels.empty()) return fail("no AMG level was added");
-        if (p->subdomain->amg_hierarchy.levels.back().P.num_rows != 0) return fail("the last AMG level still has a prolongation: add its coarse level first");
-        p->subdomain->amg_finalize();
+    return on_subdomain(p, true, [&](fddh_problem &, Subdomain<PType> &s) {
+        if (s.amg_hierarchy.levels.empty()) return fail("no AMG level was added");
+        if (s.amg_hierarchy.levels.back().P.num_rows != 0) return fail("the last AMG level still has a prolongation: add its coarse level first");
+        s.amg_finalize();
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_amg_build(fddh_problem *p, int coarsest_size, double strength, int smooth_prolongator, int verbose, int *num_levels)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p) return fail("null argument");
-        if (!p->subdomain) return fail("problem was created without a Subdomain");
+    return on_subdomain(p, true, [&](fddh_problem &, Subdomain<PType> &s) {
         fdd::low_order::Options o;
         if (coarsest_size > 0) o.coarsest_size = coarsest_size;
         if (strength > 0.0) o.strength = strength;
         o.smooth_prolongator = smooth_prolongator != 0;
-        const int nl = p->subdomain->amg_build(o, verbose != 0);
+        const int nl = s.amg_build(o, verbose != 0);
         if (num_levels) *num_levels = nl;
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_amg_level_info(const fddh_problem *p, int level, int *n, int *nnz_A, int *n_coarse, int *nnz_P)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !p->subdomain) return fail("no Subdomain");
-        const auto &lv = p->subdomain->amg_hierarchy.levels;
+    return on_problem(p, true, "no Subdomain", [&](const fddh_problem &pr) {
+        if (!pr.subdomain) return fail("no Subdomain");
+        const auto &lv = pr.subdomain->amg_hierarchy.levels;
         if (level < 0 || level >= (int)lv.size()) return fail("the hierarchy has %d levels", (int)lv.size());
         if (n) *n = lv[level].n;
         if (nnz_A) *nnz_A = lv[level].A.num_nnz;
         if (n_coarse) *n_coarse = lv[level].P.num_cols;
         if (nnz_P) *nnz_P = lv[level].P.num_nnz;
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_amg_setup_info(const fddh_problem *p, int *levels_built_on_device, double *setup_seconds)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p) return fail("null argument");
-        if (!p->subdomain) return fail("problem was created without a Subdomain");
-        if (levels_built_on_device) *levels_built_on_device = p->subdomain->amg_levels_on_device;
-        if (setup_seconds) *setup_seconds = p->subdomain->amg_setup_seconds;
+    return on_subdomain(p, true, [&](const fddh_problem &, const Subdomain<PType> &s) {
+        if (levels_built_on_device) *levels_built_on_device = s.amg_levels_on_device;
+        if (setup_seconds) *setup_seconds = s.amg_setup_seconds;
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_amg_level_transfer(const fddh_problem *p, int level, int *matrix_free)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !p->subdomain || !matrix_free) return fail("no Subdomain");
-        const auto &H = p->subdomain->amg_hierarchy;
+    return on_problem(p, true, "no Subdomain", [&](const fddh_problem &pr) {
+        if (!pr.subdomain || !matrix_free) return fail("no Subdomain");
+        const auto &H = pr.subdomain->amg_hierarchy;
         if (level < 0 || level >= (int)H.levels.size()) return fail("the hierarchy has %d levels", (int)H.levels.size());
         *matrix_free = (H.levels[level].T.active && H.matrix_free_transfer) ? 1 : 0;
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
-int fddh_problem_amg_level_arrays(const fddh_problem *cp, int level, int *A_ptr, int *A_col, double *A_val, double *D_val, double *coefs, int *P_ptr, int *P_col, double *P_val)
+int fddh_problem_amg_level_arrays(const fddh_problem *p, int level, int *A_ptr, int *A_col, double *A_val, double *D_val, double *coefs, int *P_ptr, int *P_col, double *P_val)
 {
-    try
-    {
-        if (!cp || !cp->subdomain) return fail("no Subdomain");
-        fddh_problem *p = const_cast<fddh_problem *>(cp);
-        auto &lv = p->subdomain->amg_hierarchy.levels;
+    return on_problem(p, true, "no Subdomain", [&](const fddh_problem &pr) {
+        if (!pr.subdomain) return fail("no Subdomain");
+        auto &lv = pr.subdomain->amg_hierarchy.levels;
         if (level < 0 || level >= (int)lv.size()) return fail("the hierarchy has %d levels", (int)lv.size());
         amg::Level &L = lv[level];
         // col / val of a level built in HBM have no host copy: read from the device arrays
@@ -1409,86 +1316,45 @@ int fddh_problem_amg_level_arrays(const fddh_problem *cp, int level, int *A_ptr,
             fetch(L.P, P_col, P_val);
         }
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 // z = low_order_preconditioner(r) on level-0 subdomain points (subdomain.tpp:3987-4159)
 int fddh_problem_amg_apply(fddh_problem *p, const double *r, double *z)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !r || !z) return fail("null argument");
-        if (!p->subdomain) return fail("problem was created without a Subdomain");
-        if (!p->subdomain->amg_hierarchy.ready()) return fail("no finalized AMG hierarchy is attached");
-        const size_t bytes = (size_t)p->fine().num_local_points * sizeof(double);
-        p->a.copyFrom(r, bytes);
-        p->subdomain->apply_low_order_preconditioner(p->b, p->a);
-        p->b.copyTo(z, bytes);
+    return on_subdomain(p, r && z, [&](fddh_problem &pr, Subdomain<PType> &s) {
+        if (!s.amg_hierarchy.ready()) return fail("no finalized AMG hierarchy is attached");
+        fine_round_trip(pr, r, z, [&] { s.apply_low_order_preconditioner(pr.b, pr.a); });
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_dssum(fddh_problem *p, double *out, const double *in, int apply_mask, int apply_weight)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !out || !in) return fail("null argument");
-        Domain<SType> &d = p->fine();
-        const size_t bytes = (size_t)d.num_local_points * sizeof(double);
-        p->a.copyFrom(in, bytes);
-        d.direct_stiffness_summation(p->b, p->a, apply_mask != 0, apply_weight != 0);
-        p->b.copyTo(out, bytes);
+    return on_problem(p, out && in, [&](fddh_problem &pr) {
+        fine_round_trip(pr, in, out, [&] { pr.fine().direct_stiffness_summation(pr.b, pr.a, apply_mask != 0, apply_weight != 0); });
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_stiffness(fddh_problem *p, double *out, const double *in, int apply_dssum)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !out || !in) return fail("null argument");
-        Domain<SType> &d = p->fine();
-        const size_t bytes = (size_t)d.num_local_points * sizeof(double);
-        p->a.copyFrom(in, bytes);
-        d.stiffness_matrix(p->b, p->a, apply_dssum != 0);
-        p->b.copyTo(out, bytes);
+    return on_problem(p, out && in, [&](fddh_problem &pr) {
+        fine_round_trip(pr, in, out, [&] { pr.fine().stiffness_matrix(pr.b, pr.a, apply_dssum != 0); });
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_residual_norm(fddh_problem *p, const double *r, double *norm)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !r || !norm) return fail("null argument");
-        Domain<SType> &d = p->fine();
-        const size_t bytes = (size_t)d.num_local_points * sizeof(double);
+    return on_problem(p, r && norm, [&](fddh_problem &pr) {
+        Domain<SType> &d = pr.fine();
         // ||r|| = sqrt(<r, r>) through the public pieces (Domain::residual_norm is private, domain.hpp:71)
-        p->a.copyFrom(r, bytes);
-        d.direct_stiffness_summation(p->b, p->a);
+        pr.a.copyFrom(r, fine_bytes(pr));
+        d.direct_stiffness_summation(pr.b, pr.a);
         fdd::memory ws = fdd::dev().malloc<double>(fdd_reduce_workspace_doubles());
         fdd::memory sc = fdd::dev().malloc<double>(1);
-        FDD_CALL(fdd_dom_residual_norm(sc.as<double>(), ws.as<double>(), p->a.as<double>(), p->b.as<double>(), d.dirichlet_mask_memory().as<double>(), d.num_local_points, fdd::dev().stream));
+        FDD_CALL(fdd_dom_residual_norm(sc.as<double>(), ws.as<double>(), pr.a.as<double>(), pr.b.as<double>(), d.dirichlet_mask_memory().as<double>(), d.num_local_points, fdd::dev().stream));
         if (fdd::comm().size > 1) fdd::comm().allreduce_sum(sc.as<double>(), 1);
         double v = 0.0;
         sc.copyTo(&v, sizeof(double));
@@ -1496,411 +1362,193 @@ int fddh_problem_residual_norm(fddh_problem *p, const double *r, double *norm)
         sc.free();
         *norm = std::sqrt(v);
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_make_rhs(fddh_problem *p, int function_id, unsigned long long seed, double *u_star, double *f)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p) return fail("null argument");
-        Domain<SType> &d = p->fine();
-        const size_t bytes = (size_t)d.num_local_points * sizeof(double);
-        d.initial_function(p->a, function_id, seed); // poisson.cpp:211-213
-        d.stiffness_matrix(p->b, p->a);              // poisson.cpp:219 (no dssum)
-        if (u_star) p->a.copyTo(u_star, bytes);
-        if (f) p->b.copyTo(f, bytes);
+    return on_problem(p, true, [&](fddh_problem &pr) {
+        Domain<SType> &d = pr.fine();
+        d.initial_function(pr.a, function_id, seed); // poisson.cpp:211-213
+        d.stiffness_matrix(pr.b, pr.a);              // poisson.cpp:219 (no dssum)
+        if (u_star) pr.a.copyTo(u_star, fine_bytes(pr));
+        if (f) pr.b.copyTo(f, fine_bytes(pr));
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_make_rhs_from(fddh_problem *p, double *u_star_inout, double *f)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !u_star_inout) return fail("null argument");
-        Domain<SType> &d = p->fine();
-        const size_t bytes = (size_t)d.num_local_points * sizeof(double);
-        p->a.copyFrom(u_star_inout, bytes);
-        d.direct_stiffness_summation(p->a, p->a, true, true); // domain.tpp:579
-        d.stiffness_matrix(p->b, p->a);
-        p->a.copyTo(u_star_inout, bytes);
-        if (f) p->b.copyTo(f, bytes);
+    return on_problem(p, u_star_inout != nullptr, [&](fddh_problem &pr) {
+        Domain<SType> &d = pr.fine();
+        pr.a.copyFrom(u_star_inout, fine_bytes(pr));
+        d.direct_stiffness_summation(pr.a, pr.a, true, true); // domain.tpp:579
+        d.stiffness_matrix(pr.b, pr.a);
+        pr.a.copyTo(u_star_inout, fine_bytes(pr));
+        if (f) pr.b.copyTo(f, fine_bytes(pr));
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_solve(fddh_problem *p, int solver_id, const double *f, double *u, double *history, int history_cap, int *num_history, int *num_iterations)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !f || !u) return fail("null argument");
-        if (p->subdomain && p->fine().use_preconditioner)
-            if (const char *why = inner_solver_refusal(p)) return fail("%s", why);
-        Domain<SType> &d = p->fine();
-        const size_t bytes = (size_t)d.num_local_points * sizeof(double);
-        p->a.copyFrom(f, bytes);
-
-        if (p->subdomain)
-        {
-            if (solver_id == 0)
-                d.flexible_conjugate_gradient(p->b, p->a, *p->subdomain);
-            else
-                d.generalized_minimum_residual(p->b, p->a, *p->subdomain);
-        }
-        else
-        {
-            if (solver_id == 0)
-                d.flexible_conjugate_gradient(p->b, p->a, p->none);
-            else
-                d.generalized_minimum_residual(p->b, p->a, p->none);
-        }
-
-        p->b.copyTo(u, bytes);
-        const int nh = (int)d.residual_history.size();
-        if (history)
-            for (int i = 0; i < nh && i < history_cap; i++) history[i] = d.residual_history[i];
-        if (num_history) *num_history = nh;
-        if (num_iterations) *num_iterations = d.num_iterations;
-        return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    return on_problem(p, f && u, [&](fddh_problem &pr) {
+        return outer_solve(pr, f, u, history, history_cap, num_history, num_iterations, nullptr, [&](Domain<SType> &d, auto &preconditioner) { krylov_solve(pr, d, preconditioner, solver_id); });
+    });
 }
 
 int fddh_problem_solve_timed(fddh_problem *p, int solver_id, const double *f, double *u, double *history, int history_cap, int *num_history, int *num_iterations, double *seconds)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !f || !seconds) return fail("null argument");
-        if (p->subdomain && p->fine().use_preconditioner)
-            if (const char *why = inner_solver_refusal(p)) return fail("%s", why);
-        Domain<SType> &d = p->fine();
-        const size_t bytes = (size_t)d.num_local_points * sizeof(double);
-        p->a.copyFrom(f, bytes);
-        fdd::dev().finish();
-        fdd::comm().barrier();
-        const auto t0 = std::chrono::steady_clock::now();
-        if (p->subdomain)
-        {
-            if (solver_id == 0)
-                d.flexible_conjugate_gradient(p->b, p->a, *p->subdomain);
-            else
-                d.generalized_minimum_residual(p->b, p->a, *p->subdomain);
-        }
-        else
-        {
-            if (solver_id == 0)
-                d.flexible_conjugate_gradient(p->b, p->a, p->none);
-            else
-                d.generalized_minimum_residual(p->b, p->a, p->none);
-        }
-        fdd::dev().finish();
-        *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        if (u) p->b.copyTo(u, bytes);
-        const int nh = (int)d.residual_history.size();
-        if (history)
-            for (int i = 0; i < nh && i < history_cap; i++) history[i] = d.residual_history[i];
-        if (num_history) *num_history = nh;
-        if (num_iterations) *num_iterations = d.num_iterations;
-        return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    return on_problem(p, f && seconds, [&](fddh_problem &pr) {
+        return outer_solve(pr, f, u, history, history_cap, num_history, num_iterations, seconds, [&](Domain<SType> &d, auto &preconditioner) { krylov_solve(pr, d, preconditioner, solver_id); });
+    });
 }
 
 int fddh_problem_projection_configure(fddh_problem *p, int capacity)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p) return fail("null argument");
+    return on_problem(p, true, [&](fddh_problem &pr) {
         if (capacity < 0 || capacity > FDD_PROJECTION_MAX) return fail("capacity %d: the projection basis holds 0 (off) to %d vectors", capacity, FDD_PROJECTION_MAX);
-        Domain<SType> &d = p->fine();
+        Domain<SType> &d = pr.fine();
         d.projection.configure(capacity, d.num_local_points);
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_projection_clear(fddh_problem *p)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p) return fail("null argument");
-        p->fine().projection.clear();
+    return on_problem(p, true, [&](fddh_problem &pr) {
+        pr.fine().projection.clear();
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_projection_info(const fddh_problem *p, int *capacity, int *size, long long *restarts)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p) return fail("null argument");
-        const fdd::Projection &pj = p->fine().projection;
+    return on_problem(p, true, [&](const fddh_problem &pr) {
+        const fdd::Projection &pj = pr.fine().projection;
         if (capacity) *capacity = pj.capacity;
         if (size) *size = pj.size;
         if (restarts) *restarts = pj.restarts;
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_projection_basis(const fddh_problem *p, int k, double *x, double *Ax)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p) return fail("null argument");
-        const fdd::Projection &pj = p->fine().projection;
+    return on_problem(p, true, [&](const fddh_problem &pr) {
+        const fdd::Projection &pj = pr.fine().projection;
         if (k < 0 || k >= pj.size) return fail("k = %d: the projection basis holds %d vectors", k, pj.size);
         const size_t bytes = (size_t)pj.n * sizeof(double);
         if (x && bytes) pj.X.slice((size_t)k * pj.ld, pj.n).copyTo(x, bytes);
         if (Ax && bytes) pj.AX.slice((size_t)k * pj.ld, pj.n).copyTo(Ax, bytes);
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_solve_projected(fddh_problem *p, int solver_id, const double *f, double *u, double *history, int history_cap, int *num_history, int *num_iterations, double *projection, double *seconds)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !f || !u) return fail("null argument");
-        if (p->subdomain && p->fine().use_preconditioner)
-            if (const char *why = inner_solver_refusal(p)) return fail("%s", why);
-        Domain<SType> &d = p->fine();
-        const size_t bytes = (size_t)d.num_local_points * sizeof(double);
-        p->a.copyFrom(f, bytes);
-        std::chrono::steady_clock::time_point t0;
-        if (seconds)
-        {
-            fdd::dev().finish();
-            fdd::comm().barrier();
-            t0 = std::chrono::steady_clock::now();
-        }
+    return on_problem(p, f && u, [&](fddh_problem &pr) {
         double proj[4];
-        if (p->subdomain)
-            d.solve_projected(p->b, p->a, *p->subdomain, solver_id, proj);
-        else
-            d.solve_projected(p->b, p->a, p->none, solver_id, proj);
-        if (seconds)
-        {
-            fdd::dev().finish();
-            *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        }
-        p->b.copyTo(u, bytes);
-        const int nh = (int)d.residual_history.size();
-        if (history)
-            for (int i = 0; i < nh && i < history_cap; i++) history[i] = d.residual_history[i];
-        if (num_history) *num_history = nh;
-        if (num_iterations) *num_iterations = d.num_iterations;
+        if (int rc = outer_solve(pr, f, u, history, history_cap, num_history, num_iterations, seconds, [&](Domain<SType> &d, auto &preconditioner) { d.solve_projected(pr.b, pr.a, preconditioner, solver_id, proj); })) return rc;
         if (projection) memcpy(projection, proj, sizeof(proj));
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_precond_apply(fddh_problem *p, int type, const double *r, double *z, double *history, int history_cap, int *num_history)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !r || !z) return fail("null argument");
-        if (!p->subdomain) return fail("problem was created without a Subdomain");
-        Domain<SType> &d = p->fine();
-        if (const char *why = inner_solver_refusal(p)) return fail("%s", why);
-        const size_t bytes = (size_t)d.num_local_points * sizeof(double);
-        p->a.copyFrom(r, bytes);
-        if (type == 0)
-            p->subdomain->flexible_conjugate_gradient(p->b, p->a);
-        else
-            p->subdomain->generalized_minimum_residual(p->b, p->a);
-        p->b.copyTo(z, bytes);
-        p->subdomain->finish_history();
-        const int nh = (int)p->subdomain->residual_history.size();
-        if (history)
-            for (int i = 0; i < nh && i < history_cap; i++) history[i] = p->subdomain->residual_history[i];
-        if (num_history) *num_history = nh;
+    return on_subdomain(p, r && z, [&](fddh_problem &pr, Subdomain<PType> &s) {
+        if (const char *why = inner_solver_refusal(pr)) return fail("%s", why);
+        fine_round_trip(pr, r, z, [&] {
+            if (type == 0)
+                s.flexible_conjugate_gradient(pr.b, pr.a);
+            else
+                s.generalized_minimum_residual(pr.b, pr.a);
+        });
+        s.finish_history();
+        copy_history(s.residual_history, history, history_cap, num_history);
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_sub_op(fddh_problem *p, int op, const double *in, double *out)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !in || !out) return fail("null argument");
-        if (!p->subdomain) return fail("problem was created without a Subdomain");
-        Subdomain<PType> &s = *p->subdomain;
-        const size_t bytes = (size_t)s.num_values * sizeof(double);
+    return on_subdomain(p, in && out, [&](fddh_problem &pr, Subdomain<PType> &s) {
         if (op == 0)
         {
             // tree_operator: input is an outer (Domain) vector
-            p->a.copyFrom(in, (size_t)p->fine().num_local_points * sizeof(double));
-            s.apply_tree_operator(p->sb, p->a);
+            pr.a.copyFrom(in, fine_bytes(pr));
+            s.apply_tree_operator(pr.sb, pr.a);
+            pr.sb.copyTo(out, sub_bytes(pr));
         }
+        else if (op == 1)
+            sub_round_trip(pr, in, out, [&] { s.stiffness_matrix(pr.sb, pr.sa); });
+        else if (op == 2)
+            sub_round_trip(pr, in, out, [&] { s.direct_stiffness_summation(pr.sb, pr.sa); });
         else
-        {
-            p->sa.copyFrom(in, bytes);
-            if (op == 1)
-                s.stiffness_matrix(p->sb, p->sa);
-            else if (op == 2)
-                s.direct_stiffness_summation(p->sb, p->sa);
-            else
-                return fail("unknown subdomain op %d", op);
-        }
-        p->sb.copyTo(out, bytes);
+            return fail("unknown subdomain op %d", op);
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_sub_dof_op(fddh_problem *p, int op, const double *in, double *out, int n)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !in || !out) return fail("null argument");
-        if (!p->subdomain) return fail("problem was created without a Subdomain");
-        Subdomain<PType> &s = *p->subdomain;
+    return on_subdomain(p, in && out, [&](fddh_problem &pr, Subdomain<PType> &s) {
         if (not s.dof_space_available()) return fail("the inner iteration of this problem does not run in dof space");
         if (n != s.dof_count()) return fail("dof vectors have %d entries, got %d", s.dof_count(), n);
         if (op == 0)
             s.host_operator_dofs(out, in);
         else if (op == 1)
         {
-            p->a.copyFrom(in, (size_t)p->fine().num_local_points * sizeof(double));
-            s.host_rhs_dofs(out, p->a);
+            pr.a.copyFrom(in, fine_bytes(pr));
+            s.host_rhs_dofs(out, pr.a);
         }
         else
             return fail("unknown dof-space op %d", op);
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_sub_jacobi_diagonal(fddh_problem *p, double *out, int n)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !out) return fail("null argument");
-        if (!p->subdomain) return fail("problem was created without a Subdomain");
-        const std::vector<double> &d = p->subdomain->jacobi_diagonal();
-        if (n != p->subdomain->dofs()) return fail("the diagonal has %d entries, got %d", p->subdomain->dofs(), n);
+    return on_subdomain(p, out != nullptr, [&](fddh_problem &, Subdomain<PType> &s) {
+        const std::vector<double> &d = s.jacobi_diagonal();
+        if (n != s.dofs()) return fail("the diagonal has %d entries, got %d", s.dofs(), n);
         for (int i = 0; i < n; i++) out[i] = d[i];
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_sub_dof_solve(fddh_problem *p, const double *fa, double *ua, int n)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !fa || !ua) return fail("null argument");
-        if (!p->subdomain) return fail("problem was created without a Subdomain");
-        Subdomain<PType> &s = *p->subdomain;
-        if (const char *why = inner_solver_refusal(p)) return fail("%s", why);
+    return on_subdomain(p, fa && ua, [&](fddh_problem &pr, Subdomain<PType> &s) {
+        if (const char *why = inner_solver_refusal(pr)) return fail("%s", why);
         if (not s.dof_space_available()) return fail("the inner iteration of this problem does not run in dof space");
         if (n != s.dof_count()) return fail("dof vectors have %d entries, got %d", s.dof_count(), n);
         s.host_solve_dofs(ua, fa);
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_inner_chebyshev_configure(fddh_problem *p, int order, double lower, double upper, int power_iterations)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p) return fail("null argument");
-        if (!p->subdomain) return fail("problem was created without a Subdomain");
+    return on_subdomain(p, true, [&](fddh_problem &, Subdomain<PType> &s) {
         if (order < 1 || order > 16) return fail("the Chebyshev order must lie in 1..16, got %d", order);
         if (!(lower > 0.0) || !(upper > lower) || !std::isfinite(upper)) return fail("the Chebyshev interval needs 0 < lower < upper, got [%g, %g]", lower, upper);
         if (power_iterations < 1 || power_iterations > 10000) return fail("power_iterations must lie in 1..10000, got %d", power_iterations);
-        auto &c = p->subdomain->cheby;
+        auto &c = s.cheby;
         c.order = order;
         c.lower = lower;
         c.upper = upper;
         if (power_iterations != c.power_iterations) c.lambda = 0.0; // the estimate belongs to its iteration count; the factors do not touch it
         c.power_iterations = power_iterations;
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_inner_chebyshev_info(fddh_problem *p, int *order, double *lower, double *upper, double *lambda, int *power_iterations)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p) return fail("null argument");
-        if (!p->subdomain) return fail("problem was created without a Subdomain");
-        Subdomain<PType> &s = *p->subdomain;
+    return on_subdomain(p, true, [&](fddh_problem &, Subdomain<PType> &s) {
         if (lambda)
         {
             if (not s.dof_space_available()) return fail("the inner iteration of this problem does not run in dof space: there is no operator to bound");
@@ -1911,89 +1559,47 @@ int fddh_problem_inner_chebyshev_info(fddh_problem *p, int *order, double *lower
         if (upper) *upper = s.cheby.upper;
         if (power_iterations) *power_iterations = s.cheby.power_iterations;
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_sub_residual_norm(fddh_problem *p, const double *r, double *norm)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !r || !norm) return fail("null argument");
-        if (!p->subdomain) return fail("problem was created without a Subdomain");
-        p->sa.copyFrom(r, (size_t)p->subdomain->num_values * sizeof(double));
-        p->subdomain->compute_residual_norm(*norm, p->sa);
+    return on_subdomain(p, r && norm, [&](fddh_problem &pr, Subdomain<PType> &s) {
+        pr.sa.copyFrom(r, sub_bytes(pr));
+        s.compute_residual_norm(*norm, pr.sa);
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_pcg_begin(fddh_problem *p, const double *f)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !f) return fail("null argument");
-        if (p->subdomain && p->fine().use_preconditioner)
-            if (const char *why = inner_solver_refusal(p)) return fail("%s", why);
-        Domain<SType> &d = p->fine();
-        p->a.copyFrom(f, (size_t)d.num_local_points * sizeof(double));
-        if (p->subdomain && d.use_preconditioner)
-            d.fcg_begin(p->b, p->a, *p->subdomain);
-        else
-            d.fcg_begin(p->b, p->a, p->none);
+    return on_problem(p, f != nullptr, [&](fddh_problem &pr) {
+        if (const char *why = outer_solve_refusal(pr)) return fail("%s", why);
+        Domain<SType> &d = pr.fine();
+        pr.a.copyFrom(f, fine_bytes(pr));
+        with_preconditioner(pr, pr.subdomain && d.use_preconditioner, [&](auto &preconditioner) { d.fcg_begin(pr.b, pr.a, preconditioner); });
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_pcg_steps(fddh_problem *p, int steps, double *last_residual)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || steps < 0) return fail("bad argument");
-        if (p->subdomain && p->fine().use_preconditioner)
-            if (const char *why = inner_solver_refusal(p)) return fail("%s", why);
-        Domain<SType> &d = p->fine();
-        double r = std::numeric_limits<double>::quiet_NaN();
-        if (p->subdomain && d.use_preconditioner)
-            r = d.fcg_steps(*p->subdomain, steps);
-        else
-            r = d.fcg_steps(p->none, steps);
+    return on_problem(p, steps >= 0, "bad argument", [&](fddh_problem &pr) {
+        if (const char *why = outer_solve_refusal(pr)) return fail("%s", why);
+        Domain<SType> &d = pr.fine();
+        const double r = with_preconditioner(pr, pr.subdomain && d.use_preconditioner, [&](auto &preconditioner) { return d.fcg_steps(preconditioner, steps); });
         if (last_residual) *last_residual = r;
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_pcg_solution(fddh_problem *p, double *u)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !u) return fail("null argument");
-        p->fine().fcg_finish();
-        p->b.copyTo(u, (size_t)p->fine().num_local_points * sizeof(double));
+    return on_problem(p, u != nullptr, [&](fddh_problem &pr) {
+        pr.fine().fcg_finish();
+        pr.b.copyTo(u, fine_bytes(pr));
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 // Average launch time of the assembly SpMVs on the problem's own matrices, timed with
@@ -2001,48 +1607,28 @@ int fddh_problem_pcg_solution(fddh_problem *p, double *u)
 // (scatter, one non-zero per row), 1: Qt x (gather, 1-8 non-zeros per row).
 int fddh_problem_spmv_time(fddh_problem *p, int which, int iterations, double *avg_us, double *algorithmic_bytes)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !avg_us || !algorithmic_bytes || iterations < 1 || which < 0 || which > 1) return fail("bad argument");
-        Domain<SType> &d = p->fine();
+    return on_problem(p, avg_us && algorithmic_bytes && iterations >= 1 && which >= 0 && which <= 1, "bad argument", [&](fddh_problem &pr) {
+        Domain<SType> &d = pr.fine();
         CSR_Matrix<SType> &A = (which == 0) ? d.scatter_matrix() : d.gather_matrix();
         fdd::memory x = fdd::dev().malloc<double>(std::max(A.num_cols, 1));
         fdd::memory y = fdd::dev().malloc<double>(std::max(A.num_rows, 1));
         FDD_CALL(fdd_set_to_value(x.as<double>(), 1.0, A.num_cols, 0, fdd::dev().stream));
-        void *e0 = nullptr, *e1 = nullptr;
-        FDD_CALL(fdd_event_create(&e0));
-        FDD_CALL(fdd_event_create(&e1));
-        for (int i = 0; i < 3; i++) A.multiply(y, x);
-        FDD_CALL(fdd_event_record(e0, fdd::dev().stream));
-        for (int i = 0; i < iterations; i++) A.multiply(y, x);
-        FDD_CALL(fdd_event_record(e1, fdd::dev().stream));
-        float ms = 0.0f;
-        FDD_CALL(fdd_event_elapsed_ms(&ms, e0, e1));
-        FDD_CALL(fdd_event_destroy(e0));
-        FDD_CALL(fdd_event_destroy(e1));
+        const float ms = spmv_ms(A, x, y, iterations);
         x.free();
         y.free();
         *avg_us = 1.0e3 * ms / iterations;
         *algorithmic_bytes = A.algorithmic_bytes(false);
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_problem_comm_time(fddh_problem *p, int iterations, double *avg_us, double *bytes)
 {
-    try
-    {
-        if (int rc = rank_check(p)) return rc;
-        if (!p || !avg_us || !bytes || iterations < 1) return fail("bad argument");
+    return on_problem(p, avg_us && bytes && iterations >= 1, "bad argument", [&](fddh_problem &pr) {
         for (int k = 0; k < FDDH_COMM_TIME_COUNT; k++) avg_us[k] = bytes[k] = 0.0;
         fdd::Comm &c = fdd::comm();
         if (c.size == 1) return 0;
-        Domain<SType> &d = p->fine();
+        Domain<SType> &d = pr.fine();
         fdd::memory scal = fdd::dev().malloc<double>(4);
         FDD_CALL(fdd_memset(scal.ptr(), 0, 4 * sizeof(double), fdd::dev().stream));
         const auto clock = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -2062,28 +1648,23 @@ int fddh_problem_comm_time(fddh_problem *p, int iterations, double *avg_us, doub
         bytes[1] = 2.0 * d.interface_slots_count() * sizeof(double);
         avg_us[4] = timed([&] { d.comm_probe_interface(2, true); });
         bytes[4] = d.comm_interface_neighbour_bytes(2);
-        if (p->subdomain)
+        if (pr.subdomain)
         {
-            avg_us[2] = timed([&] { p->subdomain->comm_probe_coarse(); });
-            bytes[2] = p->subdomain->comm_coarse_bytes();
-            avg_us[3] = timed([&] { p->subdomain->comm_probe_ring(); });
-            bytes[3] = p->subdomain->comm_ring_bytes();
-            avg_us[5] = timed([&] { p->subdomain->comm_probe_ring_and_coarse(); });
-            bytes[5] = p->subdomain->comm_ring_and_coarse_bytes();
+            avg_us[2] = timed([&] { pr.subdomain->comm_probe_coarse(); });
+            bytes[2] = pr.subdomain->comm_coarse_bytes();
+            avg_us[3] = timed([&] { pr.subdomain->comm_probe_ring(); });
+            bytes[3] = pr.subdomain->comm_ring_bytes();
+            avg_us[5] = timed([&] { pr.subdomain->comm_probe_ring_and_coarse(); });
+            bytes[5] = pr.subdomain->comm_ring_and_coarse_bytes();
         }
         scal.free();
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_spmv_stencil_time(int m, int iterations, double *avg_us, double *algorithmic_bytes, long long *num_nnz)
 {
-    try
-    {
+    return guarded([&] {
         if (m < 2 || iterations < 1 || !avg_us || !algorithmic_bytes) return fail("bad argument");
         const long long n = (long long)m * m * m;
         if (n > 2000000000LL) return fail("grid too large");
@@ -2135,17 +1716,7 @@ int fddh_spmv_stencil_time(int m, int iterations, double *avg_us, double *algori
             for (long long r = 0; r < n; r++) hx[r] = 0.5 + 1.0e-3 * (double)((r * 7919) % 1009);
             x.copyFrom(hx.data(), (size_t)n * sizeof(double));
         }
-        void *e0 = nullptr, *e1 = nullptr;
-        FDD_CALL(fdd_event_create(&e0));
-        FDD_CALL(fdd_event_create(&e1));
-        for (int i = 0; i < 3; i++) A.multiply(y, x);
-        FDD_CALL(fdd_event_record(e0, fdd::dev().stream));
-        for (int i = 0; i < iterations; i++) A.multiply(y, x);
-        FDD_CALL(fdd_event_record(e1, fdd::dev().stream));
-        float ms = 0.0f;
-        FDD_CALL(fdd_event_elapsed_ms(&ms, e0, e1));
-        FDD_CALL(fdd_event_destroy(e0));
-        FDD_CALL(fdd_event_destroy(e1));
+        const float ms = spmv_ms(A, x, y, iterations);
         *avg_us = 1.0e3 * ms / iterations;
         *algorithmic_bytes = A.algorithmic_bytes(false);
         if (num_nnz) *num_nnz = total;
@@ -2155,45 +1726,30 @@ int fddh_spmv_stencil_time(int m, int iterations, double *avg_us, double *algori
         A.col.free();
         A.val.free();
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_profile_enable(int on)
 {
-    try
-    {
+    return guarded([&] {
         fdd::profiler().reset();
         fdd::profiler().enabled = on != 0;
         fdd::profiler().only.clear();
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_profile_only(const char *kernel_key)
 {
-    try
-    {
+    return guarded([&] {
         fdd::profiler().only = kernel_key ? kernel_key : "";
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_profile_collect(char *json, size_t json_len)
 {
-    try
-    {
+    return guarded([&] {
         if (!json || json_len < 3) return fail("bad buffer");
         auto stats = fdd::profiler().collect();
         std::string s = "{";
@@ -2209,39 +1765,25 @@ int fddh_profile_collect(char *json, size_t json_len)
         if (s.size() + 1 > json_len) return fail("profile JSON needs %zu bytes", s.size() + 1);
         memcpy(json, s.c_str(), s.size() + 1);
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_sync(void)
 {
-    try
-    {
+    return guarded([&] {
         fdd::dev().finish();
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 int fddh_barrier(void)
 {
-    try
-    {
+    return guarded([&] {
         fdd::dev().finish();
         fdd::comm().barrier();
         fdd::dev().finish();
         return 0;
-    }
-    catch (const std::exception &e)
-    {
-        return fail("%s", e.what());
-    }
+    });
 }
 
 } // extern "C"
