@@ -460,6 +460,22 @@ int fdd_stiffness_factor_block_hash(unsigned long long *out, const double *const
  * of element factor_elem[e] in any bit of any of the three arrays (-0.0 differs from 0.0, NaN payloads count), or whose
  * factor_elem[e] lies outside 0..num_elements-1.  0: the map is safe to hand to fdd_stiffness_matrix_lines_shared[_f32]. */
 int fdd_stiffness_factor_block_verify(int *mismatches, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, void *stream);
+/* The halves the stiffness operator is made of, as entries of their own (an option of this build; csrc/fdd_field.hip), and the
+ * diagonal mass matrix.  3-D, double, elements contiguous (element e starts at e (N+1)^3); xyz, grad and v are HOST arrays
+ * of three device pointers (the coordinates of the points; the components).  With D[i][p] = D_hat[p + i n], per point:
+ *   J[a][b] = dX_a / dr_b   D_hat applied to x, y, z along r, s, t;  I = J^-1 by cofactors over det J
+ *   mass    = w_i w_j w_k det J                                      (gll_weights: the n weights)
+ *   grad_a  = sum_b du/dr_b I[b][a]
+ *   out     = D_r^T F_r + D_s^T F_s + D_t^T F_t,  F_b = mass sum_a I[b][a] v_a:  the weak divergence, integral of
+ *             grad(phi) . v against every basis function phi, element-local and unassembled like mass and grad, so that
+ *             weak_divergence(gradient(u)) is the stiffness operator's Au
+ * The metric is formed in the kernel, no array holds it: 32 (mass), 56 (gradient) and 56 (weak divergence) B per point.
+ * A non-positive det J is not detected.  poly_degree 1..15, FDD_ERR_UNSUPPORTED otherwise; num_elements < 2^31 / (N+1)^3;
+ * no output may be one of the inputs or another output (equal pointers: FDD_ERR_INVALID_ARGUMENT).  A call that is refused
+ * touches no output; num_elements = 0 does nothing. */
+int fdd_field_mass(double *mass, const double *const xyz[3], const double *D_hat, const double *gll_weights, int num_elements, int poly_degree, void *stream);
+int fdd_field_gradient(double *const grad[3], const double *u, const double *const xyz[3], const double *D_hat, int num_elements, int poly_degree, void *stream);
+int fdd_field_weak_divergence(double *out, const double *const v[3], const double *const xyz[3], const double *D_hat, const double *gll_weights, int num_elements, int poly_degree, void *stream);
 int fdd_stiffness_matrix_affine_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *elem_factors, const float *gll_weights, const int *elem_offset, int num_elements, int poly_degree, void *stream);
 int fdd_sub_stiffness_matrix_gather_scaled_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream);
 int fdd_multi_inner_product_scaled_f32(double *out, double *ws, const float *a, const float *const *b, const double *b_scale_dev, int m, int n, void *stream); /* out[k] = sum a * (s_k b_k), k < m <= 8 */

@@ -338,6 +338,25 @@ int fddh_problem_make_rhs(fddh_problem *p, int function_id, unsigned long long s
 /* u* given on the host (e.g. a seeded vector): u* <- weighted dssum(u*), f = A_L u* */
 int fddh_problem_make_rhs_from(fddh_problem *p, double *u_star_inout, double *f);
 
+/* Mass, gradient and weak divergence of fields on the problem's fine mesh (an option of this build; fdd_hip.h: fdd_field_*,
+ * where the formulas are): what a caller who solves -laplace(u) = s, or the pressure step of a flow code, needs around the
+ * solve.  Host vectors of num_local_points, element-local like every vector of this header; 3-D problems of degree <= 15 (a
+ * 2-D problem is refused and stays usable); refused, naming the missing entry, on a kernel library without the fdd_field_*
+ * entries.  The opening is that of the fddh_problem_* entries: the calling thread must be the problem's rank.
+ *   mass             the diagonal mass matrix B = w_i w_j w_k det J, unassembled: f = B s (point by point) is the right-hand
+ *                    side of -laplace(u) = s for fddh_problem_solve
+ *   gradient         of u, per element.  average != 0: every component is replaced by its multiplicity-weighted mean over the
+ *                    copies of a node (Domain::direct_stiffness_summation without the mask, with the weight), which is
+ *                    continuous; collective on several ranks
+ *   weak_divergence  out_i = integral of grad(phi_i) . v, unassembled like the f of fddh_problem_make_rhs and handed to
+ *                    fddh_problem_solve as it is; weak_divergence(gradient(u)) = fddh_problem_stiffness(u)
+ * They read the level's current D_hat (fddh_problem_set_D_hat is followed) and a device copy of the coordinates made at the
+ * first call (24 B per point) and freed with the problem.  A non-positive Jacobian is not detected: the generated meshes are
+ * checked when they are made; for a mesh read from files, min(mass) > 0 is the caller's check. */
+int fddh_field_mass(fddh_problem *p, double *mass);
+int fddh_field_gradient(fddh_problem *p, const double *u, double *gx, double *gy, double *gz, int average);
+int fddh_field_weak_divergence(fddh_problem *p, const double *vx, const double *vy, const double *vz, double *out);
+
 /* Outer solve: solver_id 0 = flexible_conjugate_gradient, 1 = generalized_minimum_residual
  * (poisson.cpp:224-231).  history receives the residual norms the reference
  * prints (iteration 0 first). */

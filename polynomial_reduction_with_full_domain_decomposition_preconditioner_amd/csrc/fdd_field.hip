@@ -1,0 +1,377 @@
+// Mass, gradient and weak divergence of fields on the GLL points of a 3-D mesh, gfx950: the two halves the stiffness
+// operator is made of, A_L u = D^T [B J^-1 J^-T] D u = wdiv(grad u), as entries of their own, and the diagonal mass
+// matrix B = w_i w_j w_k det J.  An option of this build (the reference has no such kernels).
+//
+// No array holds the metric J^-1: it is formed per point from the coordinates.  J[a][b] = dX_a / dr_b is D_hat applied to
+// x, y, z along r, s, t; C = adj J by cofactors, det J = J[0][.] . C[.][0] -- the statements of host/box_mesh.hpp
+// (deform_isoparametric) -- and J^-1 = C / det.  Reading x, y, z costs 24 B per point where nine metric arrays would cost 72:
+//   mass  32 B/point (24 read,  8 written)   mass    = (w_i w_j) w_k det
+//   grad  56 B/point (32 read, 24 written)   grad_a  = (sum_b du/dr_b C[b][a]) / det
+//   wdiv  56 B/point (48 read,  8 written)   F_b     = (w_i w_j) w_k sum_a C[b][a] v_a  (= mass sum_a J^-1[b][a] v_a: the
+//                                            determinant cancels, so no division), out = D_r^T F_r + D_s^T F_s + D_t^T F_t
+// One division per point (grad) or none, not nine: a double division is a dozen instructions, and nine of them would be a
+// third of the kernel's arithmetic.  The contractions are written with explicit fused multiply-adds, which
+// -ffp-contract=off leaves alone: no reference arithmetic is to be matched bit for bit here (the bar is the long double
+// restatement of tests/field_checks.py), a contraction of n terms is n instructions instead of 2n, and the kernels, which
+// are bound by arithmetic and LDS reads before they are by memory, need a third fewer registers for it.
+//
+// The shape is that of fused_stiffness_kernel_t (fdd_stiffness.hip): an element of n = N+1 points per edge is owned by
+// n*n lanes, lane (i,j) marches over k.  Its k-columns of the differentiated fields (x, y, z and, for grad, u) sit in
+// registers for the t contraction; only the current k-slab of each sits in LDS (rows padded by one double, two buffers: one
+// sync per slab) for the r and s contractions.  wdiv's second half is that kernel's: F_r / F_s slabs through LDS, D_t^T F_t
+// accumulated in registers.  A column is a vector value, not an array: slab k's entry is taken out of it (and wdiv's r/s
+// part put into the accumulator) under the loop's wave-uniform k by indexed register moves, so the slab loop stays rolled
+// and nothing goes to scratch.
+#include "fdd_common.h"
+
+namespace
+{
+
+constexpr int kBlock = 256;
+
+enum FieldOp
+{
+    kMass = 0,
+    kGrad = 1,
+    kWdiv = 2
+};
+
+struct Ptrs3
+{
+    const double *p[3];
+};
+struct OutPtrs3
+{
+    double *p[3];
+};
+
+template <int n>
+struct FieldCfg
+{
+    static constexpr int nn = n * n;
+    static constexpr int epb = (kBlock / nn) > 0 ? (kBlock / nn) : 1; // elements per workgroup
+    static constexpr int ld = n + 1;                                  // padded LDS row
+    static constexpr int slab = n * ld;
+    static constexpr int vl = n <= 2 ? 2 : (n <= 4 ? 4 : (n <= 8 ? 8 : 16)); // entries of a column value
+};
+
+template <int VL>
+struct ColumnOf
+{
+    typedef double type __attribute__((ext_vector_type(VL)));
+};
+
+// fdd_stiffness.hip's: a wave-level fence where an element never straddles a wavefront, else a barrier that waits on the
+// LDS counter only (the loads requested for the next slab stay in flight)
+template <bool kWaveLocal>
+__device__ __forceinline__ void element_sync()
+{
+    if (kWaveLocal)
+    {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    else
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+
+// kMass: out.p[0] = mass.  kGrad: out.p[0..2] = grad of in.p[0].  kWdiv: out.p[0] = weak divergence of in.p[0..2].
+// w: the n GLL weights (kMass, kWdiv).  Elements are contiguous: element e starts at e * n^3.
+template <int n, int kOp>
+__global__ __launch_bounds__(kBlock) void field_kernel(OutPtrs3 out, Ptrs3 in, Ptrs3 X, const double *__restrict__ D_hat, const double *__restrict__ w, int num_elements)
+{
+    using C = FieldCfg<n>;
+    using Column = typename ColumnOf<C::vl>::type;
+    constexpr int nn = C::nn;
+    constexpr int n3 = nn * n;
+    constexpr bool kWaveLocal = (64 % nn == 0);
+    constexpr bool kDReg = (n <= 8); // the D_hat rows / columns of a lane in registers, else re-read from LDS per slab
+    constexpr int nd = kDReg ? n : 1;
+    constexpr int nF = (kOp == kGrad) ? 4 : 3; // fields differentiated: x, y, z and u
+    constexpr bool kWeights = (kOp != kGrad);
+
+    __shared__ double s_D[n * n];
+    __shared__ double s_c[2][nF][C::epb][C::slab];                                                // slab k of every field, two buffers
+    __shared__ double s_f[2][kOp == kWdiv ? C::epb : 1][kOp == kWdiv ? C::slab : 1];              // F_r / F_s of the slab
+
+    constexpr bool kWaveIsElement = (nn == 64);
+    const int tid = threadIdx.x;
+    const int e_loc = kWaveIsElement ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid / nn;
+    const int ij = tid - e_loc * nn;
+    const int j = ij / n;
+    const int i = ij - j * n;
+    const int elem = blockIdx.x * C::epb + e_loc;
+    const bool active = (e_loc < C::epb) && (elem < num_elements);
+    const size_t base = active ? (size_t)elem * n3 : 0;
+    const int el = active ? e_loc : 0;
+    const int lpos = i + j * C::ld;
+
+    // this lane's k-columns, all requested before D_hat is staged; wdiv: v of slab 0 behind them
+    Column col[nF];
+#pragma unroll
+    for (int f = 0; f < nF; f++) col[f] = (Column)(0.0);
+    double vq[3] = {0.0, 0.0, 0.0};
+    double wij = 0.0;
+    if (active)
+    {
+#pragma unroll
+        for (int f = 0; f < 3; f++)
+        {
+            const double *cp = X.p[f] + base;
+#pragma unroll
+            for (int k = 0; k < n; k++) col[f][k] = __builtin_nontemporal_load(cp + (ij + k * nn));
+        }
+        if constexpr (kOp == kGrad)
+        {
+            const double *up = in.p[0] + base;
+#pragma unroll
+            for (int k = 0; k < n; k++) col[3][k] = __builtin_nontemporal_load(up + (ij + k * nn));
+        }
+        if constexpr (kOp == kWdiv)
+        {
+#pragma unroll
+            for (int a = 0; a < 3; a++) vq[a] = __builtin_nontemporal_load(in.p[a] + base + ij);
+        }
+        if constexpr (kWeights) wij = w[i] * w[j];
+    }
+
+    for (int t = tid; t < n * n; t += kBlock) s_D[t] = D_hat[t];
+    __syncthreads(); // s_D is written across elements
+
+    double D_i[nd], D_j[nd], Dt_i[nd], Dt_j[nd];
+    if (kDReg)
+    {
+#pragma unroll
+        for (int p = 0; p < nd; p++)
+        {
+            D_i[p] = s_D[p + i * n]; // D[i][p]: d/dr
+            D_j[p] = s_D[p + j * n]; // D[j][p]: d/ds
+            if constexpr (kOp == kWdiv)
+            {
+                Dt_i[p] = s_D[i + p * n]; // D[p][i]: D_r^T
+                Dt_j[p] = s_D[j + p * n]; // D[p][j]: D_s^T
+            }
+        }
+    }
+
+    Column acc = (Column)(0.0); // wdiv: out of this lane's column
+
+    // not unrolled, as in the stiffness kernel: unrolled, the D_hat entries become loop-invariant register state
+#pragma unroll 1
+    for (int k = 0; k < n; k++)
+    {
+        double(*sc)[C::epb][C::slab] = s_c[k & 1];
+        if (active)
+        {
+#pragma unroll
+            for (int f = 0; f < nF; f++) sc[f][el][lpos] = col[f][k];
+        }
+
+        double v[3] = {vq[0], vq[1], vq[2]};
+        if constexpr (kOp == kWdiv)
+        {
+            if (active && k + 1 < n)
+            {
+#pragma unroll
+                for (int a = 0; a < 3; a++) vq[a] = __builtin_nontemporal_load(in.p[a] + base + (ij + (k + 1) * nn));
+            }
+        }
+
+        // row k of D_hat: wave-uniform address -> scalar loads
+        double Dk[n];
+#pragma unroll
+        for (int p = 0; p < n; p++) Dk[p] = D_hat[p + k * n];
+
+        element_sync<kWaveLocal>();
+
+        // d[f][b] = d field_f / d r_b at (i, j, k), summed over p = 0..n-1 from 0.0
+        double d[nF][3];
+#pragma unroll
+        for (int f = 0; f < nF; f++) d[f][0] = d[f][1] = d[f][2] = 0.0;
+#pragma unroll
+        for (int p = 0; p < n; p++)
+        {
+            const double di = kDReg ? D_i[kDReg ? p : 0] : s_D[p + i * n];
+            const double dj = kDReg ? D_j[kDReg ? p : 0] : s_D[p + j * n];
+#pragma unroll
+            for (int f = 0; f < nF; f++)
+            {
+                d[f][0] = __builtin_fma(di, sc[f][el][p + j * C::ld], d[f][0]);
+                d[f][1] = __builtin_fma(dj, sc[f][el][i + p * C::ld], d[f][1]);
+                d[f][2] = __builtin_fma(Dk[p], col[f][p], d[f][2]);
+            }
+        }
+
+        // J[a][b] = d[a][b]; Cf = adj J, I = Cf / det = J^-1 (host/box_mesh.hpp: deform_isoparametric)
+        double Cf[3][3];
+        Cf[0][0] = d[1][1] * d[2][2] - d[1][2] * d[2][1];
+        Cf[0][1] = d[0][2] * d[2][1] - d[0][1] * d[2][2];
+        Cf[0][2] = d[0][1] * d[1][2] - d[0][2] * d[1][1];
+        Cf[1][0] = d[1][2] * d[2][0] - d[1][0] * d[2][2];
+        Cf[1][1] = d[0][0] * d[2][2] - d[0][2] * d[2][0];
+        Cf[1][2] = d[0][2] * d[1][0] - d[0][0] * d[1][2];
+        Cf[2][0] = d[1][0] * d[2][1] - d[1][1] * d[2][0];
+        Cf[2][1] = d[0][1] * d[2][0] - d[0][0] * d[2][1];
+        Cf[2][2] = d[0][0] * d[1][1] - d[0][1] * d[1][0];
+
+        const int off = ij + k * nn;
+        if constexpr (kOp == kMass)
+        {
+            const double det = d[0][0] * Cf[0][0] + d[0][1] * Cf[1][0] + d[0][2] * Cf[2][0];
+            if (active) __builtin_nontemporal_store(wij * w[k] * det, out.p[0] + base + off);
+        }
+        if constexpr (kOp == kGrad)
+        {
+            const double det = d[0][0] * Cf[0][0] + d[0][1] * Cf[1][0] + d[0][2] * Cf[2][0];
+            const double rdet = 1.0 / det;
+            if (active)
+            {
+#pragma unroll
+                for (int a = 0; a < 3; a++) __builtin_nontemporal_store((d[3][0] * Cf[0][a] + d[3][1] * Cf[1][a] + d[3][2] * Cf[2][a]) * rdet, out.p[a] + base + off);
+            }
+        }
+        if constexpr (kOp == kWdiv)
+        {
+            const double w3 = wij * w[k];
+            double F[3];
+#pragma unroll
+            for (int b = 0; b < 3; b++) F[b] = w3 * (Cf[b][0] * v[0] + Cf[b][1] * v[1] + Cf[b][2] * v[2]);
+
+            // one buffer is enough: the next slab's F is written behind the sync above, which every lane reaches after its reads of this one
+            if (active)
+            {
+                s_f[0][el][lpos] = F[0];
+                s_f[1][el][lpos] = F[1];
+            }
+            element_sync<kWaveLocal>();
+
+            double o_r = 0.0, o_s = 0.0;
+#pragma unroll
+            for (int p = 0; p < n; p++)
+            {
+                const double dti = kDReg ? Dt_i[kDReg ? p : 0] : s_D[i + p * n];
+                const double dtj = kDReg ? Dt_j[kDReg ? p : 0] : s_D[j + p * n];
+                o_r = __builtin_fma(dti, s_f[0][el][p + j * C::ld], o_r);
+                o_s = __builtin_fma(dtj, s_f[1][el][i + p * C::ld], o_s);
+            }
+            acc[k] = acc[k] + (o_r + o_s);
+            // out(i,j,m) += D[k][m] F_t(i,j,k)
+#pragma unroll
+            for (int m = 0; m < n; m++) acc[m] = __builtin_fma(Dk[m], F[2], acc[m]);
+        }
+    }
+
+    if constexpr (kOp == kWdiv)
+    {
+        if (active)
+        {
+            double *op = out.p[0] + base;
+#pragma unroll
+            for (int k = 0; k < n; k++) __builtin_nontemporal_store(acc[k], op + (ij + k * nn));
+        }
+    }
+}
+
+template <int kOp>
+int launch_field(const OutPtrs3 &out, const Ptrs3 &in, const Ptrs3 &X, const double *D_hat, const double *w, int num_elements, int n, void *stream)
+{
+    fdd_for_n<2, 16>(n, [&](auto nc) {
+        using C = FieldCfg<decltype(nc)::value>;
+        const int grid = (num_elements + C::epb - 1) / C::epb;
+        hipLaunchKernelGGL((field_kernel<decltype(nc)::value, kOp>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), out, in, X, D_hat, w, num_elements);
+    });
+    FDD_LAUNCH_CHECK();
+    return 0;
+}
+
+// What the three entries check in the same order, before any arithmetic on the sizes and before any output is touched:
+// the degree (the element bound divides by (N+1)^3), then the count.  *run: there is something to launch.
+int field_sizes(int num_elements, int poly_degree, bool *run)
+{
+    *run = false;
+    if (poly_degree < 1 || poly_degree > 15)
+    {
+        fdd_set_error("field kernels support poly_degree 1..15, got %d", poly_degree);
+        return FDD_ERR_UNSUPPORTED;
+    }
+    const long long n = poly_degree + 1;
+    FDD_REQUIRE(num_elements >= 0);
+    FDD_REQUIRE(num_elements < (1LL << 31) / (n * n * n));
+    *run = num_elements > 0;
+    return 0;
+}
+
+int three_pointers(Ptrs3 &to, const double *const from[3])
+{
+    FDD_REQUIRE(from != nullptr);
+    for (int a = 0; a < 3; a++)
+    {
+        FDD_REQUIRE(from[a] != nullptr);
+        to.p[a] = from[a];
+    }
+    return 0;
+}
+
+// no output is an input, and no two outputs are the same array
+int no_alias(const OutPtrs3 &out, int num_out, const Ptrs3 &in, int num_in, const Ptrs3 &X)
+{
+    for (int o = 0; o < num_out; o++)
+    {
+        for (int a = 0; a < num_in; a++) FDD_REQUIRE(out.p[o] != in.p[a]);
+        for (int a = 0; a < 3; a++) FDD_REQUIRE(out.p[o] != X.p[a]);
+        for (int q = 0; q < o; q++) FDD_REQUIRE(out.p[o] != out.p[q]);
+    }
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int fdd_field_mass(double *mass, const double *const xyz[3], const double *D_hat, const double *gll_weights, int num_elements, int poly_degree, void *stream)
+{
+    bool run;
+    if (int rc = field_sizes(num_elements, poly_degree, &run)) return rc;
+    if (!run) return 0;
+    FDD_REQUIRE(mass != nullptr && D_hat != nullptr && gll_weights != nullptr);
+    OutPtrs3 out = {{mass, nullptr, nullptr}};
+    Ptrs3 in = {{nullptr, nullptr, nullptr}}, X;
+    if (int rc = three_pointers(X, xyz)) return rc;
+    if (int rc = no_alias(out, 1, in, 0, X)) return rc;
+    return launch_field<kMass>(out, in, X, D_hat, gll_weights, num_elements, poly_degree + 1, stream);
+}
+
+int fdd_field_gradient(double *const grad[3], const double *u, const double *const xyz[3], const double *D_hat, int num_elements, int poly_degree, void *stream)
+{
+    bool run;
+    if (int rc = field_sizes(num_elements, poly_degree, &run)) return rc;
+    if (!run) return 0;
+    FDD_REQUIRE(grad != nullptr && u != nullptr && D_hat != nullptr);
+    OutPtrs3 out;
+    for (int a = 0; a < 3; a++)
+    {
+        FDD_REQUIRE(grad[a] != nullptr);
+        out.p[a] = grad[a];
+    }
+    Ptrs3 in = {{u, nullptr, nullptr}}, X;
+    if (int rc = three_pointers(X, xyz)) return rc;
+    if (int rc = no_alias(out, 3, in, 1, X)) return rc;
+    return launch_field<kGrad>(out, in, X, D_hat, nullptr, num_elements, poly_degree + 1, stream);
+}
+
+int fdd_field_weak_divergence(double *out_, const double *const v[3], const double *const xyz[3], const double *D_hat, const double *gll_weights, int num_elements, int poly_degree, void *stream)
+{
+    bool run;
+    if (int rc = field_sizes(num_elements, poly_degree, &run)) return rc;
+    if (!run) return 0;
+    FDD_REQUIRE(out_ != nullptr && D_hat != nullptr && gll_weights != nullptr);
+    OutPtrs3 out = {{out_, nullptr, nullptr}};
+    Ptrs3 in, X;
+    if (int rc = three_pointers(in, v)) return rc;
+    if (int rc = three_pointers(X, xyz)) return rc;
+    if (int rc = no_alias(out, 1, in, 3, X)) return rc;
+    return launch_field<kWdiv>(out, in, X, D_hat, gll_weights, num_elements, poly_degree + 1, stream);
+}
+
+} // extern "C"

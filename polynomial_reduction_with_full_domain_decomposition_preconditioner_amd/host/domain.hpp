@@ -32,6 +32,7 @@
 #include "csr_matrix.hpp"
 #include "element.hpp"
 #include "element_operator.hpp"
+#include "field_ops.hpp"
 #include "gll.hpp"
 #include "gmres.hpp"
 #include "math.hpp"
@@ -482,6 +483,7 @@ class Domain
     fdd::memory D_hat;
     std::vector<double> D_hat_hst;
     fdd::memory geom_fact[NUM_GEOM_FACTS];
+    fdd::FieldGeometry field_geometry; // device copy of mesh.x / y / z and the GLL weights for the field operators (field_ops.hpp): made at first use, freed with the Domain
 
     Domain() {}
     Domain(char *directory_, int poly_degree_) { initialize(directory_, poly_degree_); }

@@ -84,9 +84,23 @@
 // set to 1, naming the missing entry
 #pragma weak fdd_stiffness_matrix_lines_direct
 #pragma weak fdd_csr_plan_gather_mapped
+// and the mass, gradient and weak divergence of fields on the fine mesh (csrc/fdd_field.hip): without them the fddh_field_*
+// entries refuse, naming the missing entry (missing_field_entry)
+#pragma weak fdd_field_mass
+#pragma weak fdd_field_gradient
+#pragma weak fdd_field_weak_divergence
 
 namespace fdd
 {
+
+// the first of the field entries the loaded kernel library does not export, or nullptr
+inline const char *missing_field_entry()
+{
+    if (&fdd_field_mass == nullptr) return "fdd_field_mass";
+    if (&fdd_field_gradient == nullptr) return "fdd_field_gradient";
+    if (&fdd_field_weak_divergence == nullptr) return "fdd_field_weak_divergence";
+    return nullptr;
+}
 
 // the first AMG setup entry the loaded kernel library does not export, or nullptr
 inline const char *missing_amg_setup_entry()

@@ -20,6 +20,7 @@
 
 #include "box_mesh.hpp"
 #include "domain.hpp"
+#include "field_ops.hpp"
 #include "subdomain.hpp"
 
 typedef double SType; // config.hpp:19 STYPE
@@ -114,6 +115,14 @@ int on_subdomain(Problem *p, bool args_ok, Body &&body)
         if (!pr.subdomain) return fail("problem was created without a Subdomain");
         return body(pr, *pr.subdomain);
     });
+}
+
+// the same for the fddh_field_* entries: the body gets *p and the field operators of its fine Domain, whose constructor
+// throws what they cannot run on (a kernel library without their entries, a 2-D problem: field_ops.hpp)
+template <typename Body>
+int on_field_ops(fddh_problem *p, bool args_ok, Body &&body)
+{
+    return on_problem(p, args_ok, [&](fddh_problem &pr) { return body(pr, fdd::FieldOps<Domain<SType>>(pr.fine())); });
 }
 
 size_t fine_bytes(const fddh_problem &p) { return (size_t)p.fine().num_local_points * sizeof(double); }
@@ -1341,6 +1350,53 @@ int fddh_problem_stiffness(fddh_problem *p, double *out, const double *in, int a
 {
     return on_problem(p, out && in, [&](fddh_problem &pr) {
         fine_round_trip(pr, in, out, [&] { pr.fine().stiffness_matrix(pr.b, pr.a, apply_dssum != 0); });
+        return 0;
+    });
+}
+
+// ---- fddh_field_*: mass, gradient and weak divergence on the fine level (field_ops.hpp) ----
+int fddh_field_mass(fddh_problem *p, double *mass)
+{
+    return on_field_ops(p, mass != nullptr, [&](fddh_problem &pr, const fdd::FieldOps<Domain<SType>> &ops) {
+        ops.mass(pr.b);
+        pr.b.copyTo(mass, fine_bytes(pr));
+        return 0;
+    });
+}
+
+int fddh_field_gradient(fddh_problem *p, const double *u, double *gx, double *gy, double *gz, int average)
+{
+    return on_field_ops(p, u && gx && gy && gz, [&](fddh_problem &pr, const fdd::FieldOps<Domain<SType>> &ops) {
+        fdd::memory third = fdd::dev().malloc<double>(pr.fine().num_local_points);
+        pr.a.copyFrom(u, fine_bytes(pr));
+        ops.gradient(pr.b, pr.c, third, pr.a);
+        fdd::memory *g[3] = {&pr.b, &pr.c, &third};
+        double *out[3] = {gx, gy, gz};
+        for (int a = 0; a < 3; a++)
+        {
+            if (average) // the multiplicity-weighted mean over the copies of a node: continuous; collective on several ranks
+            {
+                pr.fine().direct_stiffness_summation(pr.a, *g[a], false, true);
+                pr.a.copyTo(out[a], fine_bytes(pr));
+            }
+            else
+                g[a]->copyTo(out[a], fine_bytes(pr));
+        }
+        third.free();
+        return 0;
+    });
+}
+
+int fddh_field_weak_divergence(fddh_problem *p, const double *vx, const double *vy, const double *vz, double *out)
+{
+    return on_field_ops(p, vx && vy && vz && out, [&](fddh_problem &pr, const fdd::FieldOps<Domain<SType>> &ops) {
+        fdd::memory result = fdd::dev().malloc<double>(pr.fine().num_local_points);
+        pr.a.copyFrom(vx, fine_bytes(pr));
+        pr.b.copyFrom(vy, fine_bytes(pr));
+        pr.c.copyFrom(vz, fine_bytes(pr));
+        ops.weak_divergence(result, pr.a, pr.b, pr.c);
+        result.copyTo(out, fine_bytes(pr));
+        result.free();
         return 0;
     });
 }

@@ -476,6 +476,32 @@ class Problem:
         _H().call("fddh_problem_stiffness", self.h, _dp(out), _dp(np.ascontiguousarray(u)), int(dssum))
         return out
 
+    def mass(self):
+        """The diagonal mass matrix B = w_i w_j w_k det J at the fine level's points, unassembled.  The right-hand side of
+        -laplace(u) = s from the source term s at the points:
+
+            f = p.mass() * s
+            u, its, hist = p.solve(f)
+        """
+        out = np.zeros(self.n)
+        _H().call("fddh_field_mass", self.h, _dp(out))
+        return out
+
+    def gradient(self, u, average=False):
+        """(gx, gy, gz): the gradient of u, per element; average: each component replaced by its multiplicity-weighted
+        mean over the copies of a node (continuous; collective on several ranks)"""
+        g = [np.zeros(self.n) for _ in range(3)]
+        _H().call("fddh_field_gradient", self.h, _dp(np.ascontiguousarray(u, dtype=np.float64)), _dp(g[0]), _dp(g[1]), _dp(g[2]), int(average))
+        return tuple(g)
+
+    def weak_divergence(self, vx, vy, vz):
+        """out_i = integral of grad(phi_i) . v, unassembled like the f of make_rhs: weak_divergence(*gradient(u)) is
+        stiffness(u)"""
+        out = np.zeros(self.n)
+        v = [np.ascontiguousarray(c, dtype=np.float64) for c in (vx, vy, vz)]
+        _H().call("fddh_field_weak_divergence", self.h, _dp(v[0]), _dp(v[1]), _dp(v[2]), _dp(out))
+        return out
+
     def residual_norm(self, r):
         v = ctypes.c_double()
         _H().call("fddh_problem_residual_norm", self.h, _dp(np.ascontiguousarray(r)), ctypes.byref(v))
