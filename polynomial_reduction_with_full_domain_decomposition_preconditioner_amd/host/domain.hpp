@@ -45,8 +45,8 @@
 namespace fdd
 {
 // An inner solve's final update u~ = sum_k y_k (s_k v_k), described instead of launched: a caller that reads u~ next in a
-// pass of its own sets defer_final_update around one gmres_dofs call and, where pending_update.active comes back set,
-// owes the update (Domain::fcg_nodes_step_direction forms it inside the flexible dot's pass).
+// pass of its own hands one in (InnerSolveHints::defer_into) and, where `active` comes back set, owes the update
+// (Domain::fcg_nodes_step_direction forms it inside the flexible dot's pass).
 struct PendingUpdate
 {
     bool active = false;
@@ -56,12 +56,18 @@ struct PendingUpdate
     std::vector<const double *> v;
     int n = 0;
 };
+
+// What the caller of one inner solve knows about it: arguments of that call, nothing outlives it.
+struct InnerSolveHints
+{
+    const double *known_rhs_norm2 = nullptr; // |f~|^2 over the dofs, already on the device (double-precision device GMRES only)
+    bool lazy_history = false;               // a single-cycle solve does not synchronise at all; Subdomain::finish_history() fetches on demand
+    PendingUpdate *defer_into = nullptr;     // non-null: the caller can form the final update itself and receives its description here
+};
 } // namespace fdd
 
 struct NoPreconditioner
 {
-    bool defer_final_update = false;
-    fdd::PendingUpdate pending_update; // never active
     void flexible_conjugate_gradient(fdd::memory &, fdd::memory &) {}
     void generalized_minimum_residual(fdd::memory &, fdd::memory &) {}
     // the surface Domain's assembled flexible CG looks at (never taken: can_assemble() is false)
@@ -69,8 +75,7 @@ struct NoPreconditioner
     bool assembled_inner = false;
     bool can_assemble() const { return false; }
     int dofs() const { return 0; }
-    void gmres_dofs(fdd::memory &, fdd::memory &, bool = true, bool = false) {}
-    bool lazy_history = false;
+    void gmres_dofs(fdd::memory &, fdd::memory &, bool = true, bool = false, const fdd::InnerSolveHints & = {}) {}
     bool composite() const { return false; }
     bool composite_dof_space() const { return false; }
     int own_dofs() const { return 0; }
@@ -80,8 +85,7 @@ struct NoPreconditioner
     void comm_probe_ring() {}
     double comm_coarse_bytes() const { return 0.0; }
     double comm_ring_bytes() const { return 0.0; }
-    void gmres_composite_dofs(fdd::memory &, fdd::memory &, bool = true, bool = false, const double * = nullptr) {}
-    const double *known_rhs_norm2_dev = nullptr;
+    void gmres_composite_dofs(fdd::memory &, fdd::memory &, bool = true, bool = false, const double * = nullptr, const fdd::InnerSolveHints & = {}) {}
     bool unit_norm_weight() const { return false; }
     bool chebyshev() const { return false; }
 };
@@ -135,30 +139,53 @@ class Domain
     fdd::GmresScalars<DType> gmres_scalars; // H, rotations, gamma of the outer GMRES: sized per solve, shared by the point-space and the node-space form
     int gmres_point_vectors = 0; // num_vectors the point-space basis V, Z was allocated for
 
-    // state of a running flexible CG (fcg_begin / fcg_step)
-    fdd::memory fcg_u;
-    DType fcg_r_0_norm = 0.0;
-    DType fcg_gamma_k = 0.0;
-    int fcg_iter = 0;
+    // The layout of `scalars` in the node-space flexible CG (double slots).  One all-reduce carries a {next gamma, theta}
+    // pair together with the norm's two parts, whichever side of them the pair sits on, and the theta of the sequence
+    // without early_gamma together with them as well: the adjacencies below.
+    static constexpr int SLOT_GAMMA = 0;  // <z, r> from the projection kernel
+    static constexpr int SLOT_PQ = 1;     // <p, q>
+    static constexpr int SLOT_PAIR_A = 2; // {next gamma, theta}: the pair alternates between A and B (the current gamma must outlive the next)
+    static constexpr int SLOT_THETA = 3;  // theta without early_gamma (the second entry of pair A)
+    static constexpr int SLOT_NORM = 4;   // the residual norm's boundary-prefix and interior parts
+    static constexpr int SLOT_PAIR_B = 6;
+    static_assert(SLOT_PAIR_A + 2 == SLOT_NORM and SLOT_NORM + 2 == SLOT_PAIR_B, "a pair and the norm's parts are four contiguous doubles on either side");
+    static_assert(SLOT_THETA + 1 == SLOT_NORM and SLOT_THETA == SLOT_PAIR_A + 1, "theta sits right in front of the norm's parts");
+
+    // state of a running flexible CG (fcg_begin / fcg_step / fcg_steps): a fresh one per solve
+    struct FcgRun
+    {
+        fdd::memory u, u_pts; // the solution vector (point space); where fcg_finish puts the solution (node space)
+        bool nodes_active = false;
+        DType r_0_norm = 0.0, gamma_k = 0.0;
+        int iter = 0;
+        bool norm_pending = false;                 // device_scalars: the last residual norm is enqueued, not fetched
+        const double *pending_rhs_norm2 = nullptr; // what node_norm_enqueue returned for the residual the next precondition_nodes call receives
+        bool gamma_on_device = false;
+        int gamma_slot = SLOT_GAMMA; // where the current gamma sits in `scalars`
+    };
+    FcgRun fcg;
+
+    // the node residual norm in flight (node_norm_enqueue / node_norm_finish): reset where a solve starts
+    struct NormInFlight
+    {
+        int parts = 1;                  // scalars[SLOT_NORM..]: boundary-prefix and interior parts of the last enqueued norm
+        bool deferred = false;          // the saved prefix still waits for its exchange
+        bool reduce_pending = false;    // the slots still hold this rank's parts only
+        const double *source = nullptr; // the vector whose norm is being taken
+    };
+    NormInFlight norm_state;
 
     // ---- assembled flexible CG: every vector holds one value per local node ----
     // (see fcg_nodes_* below; built on first use)
     bool nodes_ready = false;
-    bool fcg_nodes_active = false;
-    bool fcg_norm_pending = false;
-    int norm_parts = 1; // scalars[4..]: boundary-prefix and interior parts of the last enqueued residual norm
     fdd::memory norm_hist;               // device-side residual history of fcg_steps
     int norm_hist_cap = 0;
-    bool norm_deferred = false;          // the saved prefix still waits for its exchange
-    bool norm_reduce_pending = false;    // scalars[4..5] still hold this rank's parts only
-    const double *norm_source = nullptr; // the vector whose norm is being taken
-    fdd::memory nprefix;                 // its boundary prefix (exchanged copy)
+    fdd::memory nprefix;                 // the boundary prefix of the norm's vector (exchanged copy)
     fdd::memory point_node_dev;           // int[num_local_points]: Q as an index array
     fdd::memory node_mask;                // Dirichlet mask per node
     fdd::memory node_stitch;              // local multiplicity * assembled weight * mask
     std::vector<DType> node_stitch_hst, node_mask_hst;
     bool norm_on_dof_slice = false;       // one rank, mask = indicator of the dof slice: the masked node norm is the slice's plain norm
-    const double *pending_rhs_norm2 = nullptr; // what node_norm_enqueue returned for the residual the next precondition_nodes call receives
     bool stitch_is_one = false;           // every weight of the dof slice is exactly 1.0 (setup_dof_maps)
     fdd::memory node_of_dof, dof_of_node; // renumbering to / from the subdomain's dofs
     int nodes_sub_dofs = -1;
@@ -170,7 +197,6 @@ class Domain
     fdd::memory nf;
     std::vector<fdd::memory> VN, ZN, VNA, VP;
     int gmres_nodes_vectors = 0;
-    fdd::memory fcg_u_pts;
     bool composite_rhs_from_nodes = true; // composite preconditioner: own part of its right-hand side = the node residual (no second gather of the own points)
     fdd::memory rp;                 // composite preconditioner: the residual on the element-local points (the degree tree and the ring / superdomain exchange start from it)
     bool composite_precond = false; // the Subdomain is a full-domain-decomposition composite driven in dof space
@@ -471,8 +497,6 @@ class Domain
     bool lazy_steps = true;      // fcg_steps: K iterations with one host synchronisation at the end
     bool shared_residual_norm = true; // one rank: the outer residual norm and the inner solve's first norm are the same sum over the dof slice, formed once (the iterates keep their bits; the recorded norm groups its terms differently)
     bool early_gamma = true;      // device scalars: the flexible dot also forms the next iteration's gamma = <z, r+> (same bits; the projection kernel is left with <p, q>)
-    bool gamma_on_device = false;
-    int gamma_slot = 0; // where the current gamma sits in `scalars`
     bool fused_update_flexible_dot = true; // one rank, z~ written in place, early_gamma: the inner solve's final update of z~ is formed inside the flexible dot's pass (same bits; 0: a kernel of its own in front of the dot)
     bool unit_stitch_in_place = true; // stitching weights of the dof slice all exactly 1 (one rank): the inner solve writes z~ in place (0: the multiplication by the ones, the reference's sequence)
     fdd::StiffnessFlags stiffness; // which kernel the element operator runs (element_operator.hpp)
@@ -984,7 +1008,7 @@ class Domain
     }
 
     // sqrt(<r, QQt r>) (domain.tpp:916-931) from r^ = Qt r: sum_n r^_n * gs(r^)_n * mask_n.
-    // Two halves: the reductions (+ all-reduce) are enqueued into scalars[4..5]; the value is
+    // Two halves: the reductions (+ all-reduce) are enqueued into scalars[SLOT_NORM..]; the value is
     // fetched when the host wants it, which may be after more work has been enqueued.
     // defer_exchange: the boundary prefix is only saved; its exchange rides with the stitching exchange of the
     // preconditioner that follows (precondition_nodes), which then finishes the norm (node_norm_finish)
@@ -998,17 +1022,17 @@ class Domain
         // prefix), so that all of them issue the same collectives
         const bool multi = fdd::comm().size > 1 and num_interface_slots > 0;
         const int nb = multi ? num_bdary_nodes : 0;
-        double *out = scalars.as<double>() + 4;
+        double *out = scalars.as<double>() + SLOT_NORM;
         if (multi)
         {
             if (not nprefix.ptr()) nprefix = fdd::dev().malloc<DType>(std::max(num_bdary_nodes, 1));
             nprefix.copyFrom(rn, (size_t)nb * sizeof(DType));
             FDD_CALL(fdd_dom_residual_norm(out + 1, reduce_ws.as<double>(), rn.as<double>() + nb, rn.as<double>() + nb, node_mask.as<double>() + nb, nn - nb, fdd::dev().stream));
-            norm_parts = 2;
-            norm_source = rn.as<double>();
+            norm_state.parts = 2;
+            norm_state.source = rn.as<double>();
             if (defer_exchange)
             {
-                norm_deferred = true;
+                norm_state.deferred = true;
                 return nullptr;
             }
             gs_add_boundary(nprefix);
@@ -1034,28 +1058,28 @@ class Domain
             const double *self[1] = {rn.as<double>()};
             FDD_CALL(fdd_multi_weighted_inner_product(out, reduce_ws.as<double>(), rn.as<double>(), self, 1, node_mask.as<double>(), nn, fdd::dev().stream));
         }
-        norm_parts = 1;
-        if (fdd::comm().size > 1) fdd::comm().allreduce_sum(out, norm_parts);
+        norm_state.parts = 1;
+        if (fdd::comm().size > 1) fdd::comm().allreduce_sum(out, norm_state.parts);
         return known;
     }
 
     // the boundary part of the norm once the saved prefix has been exchanged, then the all-reduce of both parts
     void node_norm_finish()
     {
-        double *out = scalars.as<double>() + 4;
-        FDD_CALL(fdd_dom_residual_norm(out, reduce_ws.as<double>(), norm_source, nprefix.as<double>(), node_mask.as<double>(), num_bdary_nodes, fdd::dev().stream));
-        if (norm_deferred and device_scalars)
-            norm_reduce_pending = true; // its two scalars join the all-reduce of the flexible dot (fcg_nodes_step_direction)
+        double *out = scalars.as<double>() + SLOT_NORM;
+        FDD_CALL(fdd_dom_residual_norm(out, reduce_ws.as<double>(), norm_state.source, nprefix.as<double>(), node_mask.as<double>(), num_bdary_nodes, fdd::dev().stream));
+        if (norm_state.deferred and device_scalars)
+            norm_state.reduce_pending = true; // its two scalars join the all-reduce of the flexible dot (fcg_nodes_step_direction)
         else
             fdd::comm().allreduce_sum(out, 2);
-        norm_deferred = false;
+        norm_state.deferred = false;
     }
 
     DType node_norm_fetch()
     {
         DType v[2] = {0.0, 0.0};
-        fdd::memory tail = scalars.slice(4, 2);
-        tail.copyTo(v, norm_parts * sizeof(DType));
+        fdd::memory tail = scalars.slice(SLOT_NORM, 2);
+        tail.copyTo(v, norm_state.parts * sizeof(DType));
         return std::sqrt(v[0] + v[1]);
     }
 
@@ -1067,14 +1091,15 @@ class Domain
     }
 
     // z~ = M^-1 r^ and the stitching (domain.tpp:639-645, 697-706)
-    // rhs_norm2: device address of |rn's dof slice|^2 if the caller has just formed it from this very rn (node_norm_enqueue's
-    // return value), else nullptr
-    // may_defer_update: the caller reads zn next in a pass of its own and can form the inner solve's final update there: where
-    // the inner solve agrees (subdomain.pending_update.active on return) zn's dof slice is still to be written
+    // hints.known_rhs_norm2: device address of |rn's dof slice|^2 if the caller has just formed it from this very rn
+    // (node_norm_enqueue's return value), else nullptr
+    // hints.defer_into: the caller reads zn next in a pass of its own and can form the inner solve's final update there: where
+    // the inner solve agrees (defer_into->active on return) zn's dof slice is still to be written
     template <typename PType>
-    void precondition_nodes(fdd::memory &zn, fdd::memory &rn, PType &subdomain, const double *rhs_norm2 = nullptr, bool may_defer_update = false)
+    void precondition_nodes(fdd::memory &zn, fdd::memory &rn, PType &subdomain, const fdd::InnerSolveHints &hints = {})
     {
         void *stream = fdd::dev().stream;
+        fdd::InnerSolveHints inner{nullptr, hints.lazy_history}; // what this call's inner solve is told: the norm and the deferral only where they hold below
         if (use_preconditioner)
         {
             fdd_timer().start("subdomain.solver");
@@ -1084,7 +1109,7 @@ class Domain
                 // ring pull, coarse all-gather: Subdomain::tree_operator) and returns the composite's dof vector,
                 // whose leading entries are this rank's nodes
                 // (the own points' part of the right-hand side is the node residual itself when the dofs are a slice of the nodes)
-                subdomain.gmres_composite_dofs(sub_u, rp, true, false, (dof_shift >= 0 and composite_rhs_from_nodes) ? rn.as<double>() + dof_shift : nullptr);
+                subdomain.gmres_composite_dofs(sub_u, rp, true, false, (dof_shift >= 0 and composite_rhs_from_nodes) ? rn.as<double>() + dof_shift : nullptr, inner);
             }
             else if (dof_shift >= 0)
             {
@@ -1093,24 +1118,21 @@ class Domain
                 // place as well: the multiplication below would be x * 1.0
                 fdd::memory f_slice = rn.slice(dof_shift, nodes_sub_dofs);
                 // the norm of this very slice was formed a moment ago (node_norm_enqueue): the inner solve starts from it
-                subdomain.known_rhs_norm2_dev = rhs_norm2;
+                inner.known_rhs_norm2 = hints.known_rhs_norm2;
                 if (stitch_is_one and unit_stitch_in_place)
                 {
                     fdd::memory z_slice = zn.slice(dof_shift, nodes_sub_dofs);
                     // nothing stands between the in-place update and the caller's pass: one rank, no exchange below
-                    // (an update still owed from an earlier solve is an error there: gmres_dofs refuses to start)
-                    subdomain.defer_final_update = may_defer_update and fdd::comm().size == 1;
-                    subdomain.gmres_dofs(z_slice, f_slice);
-                    subdomain.defer_final_update = false;
+                    if (fdd::comm().size == 1) inner.defer_into = hints.defer_into;
+                    subdomain.gmres_dofs(z_slice, f_slice, true, false, inner);
                 }
                 else
-                    subdomain.gmres_dofs(sub_u, f_slice);
-                subdomain.known_rhs_norm2_dev = nullptr;
+                    subdomain.gmres_dofs(sub_u, f_slice, true, false, inner);
             }
             else
             {
                 FDD_CALL(fdd_gather_indexed(sub_f.as<double>(), rn.as<double>(), node_of_dof.as<int>(), nullptr, nodes_sub_dofs, stream));
-                subdomain.gmres_dofs(sub_u, sub_f);
+                subdomain.gmres_dofs(sub_u, sub_f, true, false, inner);
             }
             fdd_timer().stop("subdomain.solver");
 
@@ -1127,7 +1149,7 @@ class Domain
             }
             else
                 FDD_CALL(fdd_gather_indexed(zn.as<double>(), sub_u.as<double>(), dof_of_node.as<int>(), node_stitch.as<double>(), num_local_nodes, stream));
-            if (norm_deferred)
+            if (norm_state.deferred)
             {
                 gs_add_boundary_pair(zn, nprefix);
                 node_norm_finish();
@@ -1139,7 +1161,7 @@ class Domain
         else
         {
             nt.copyFrom(rn, (size_t)num_local_nodes * sizeof(DType));
-            if (norm_deferred)
+            if (norm_state.deferred)
             {
                 gs_add_boundary_pair(nt, nprefix);
                 node_norm_finish();
@@ -1155,21 +1177,21 @@ class Domain
     {
         setup_nodes();
         if (use_preconditioner) setup_dof_maps(subdomain);
-        fcg_u_pts = u;
-        fcg_nodes_active = true;
+        fcg.u_pts = u;
+        fcg.nodes_active = true;
 
         gather_nodes(nr, f);
         if (use_preconditioner and composite_precond) rp.copyFrom(f, (size_t)num_local_points * sizeof(DType)); // r = f on the points as well
         FDD_CALL(fdd_set_to_value(nu.as<double>(), 0.0, num_local_nodes, 0, fdd::dev().stream));
         FDD_CALL(fdd_set_to_value(nz.as<double>(), 0.0, num_local_nodes, 0, fdd::dev().stream));
 
-        const double *r0_norm2 = node_norm(fcg_r_0_norm, nr);
-        residual_history.push_back(fcg_r_0_norm);
-        rstdout("Iter %2d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", 0, fcg_r_0_norm, 1.0);
+        const double *r0_norm2 = node_norm(fcg.r_0_norm, nr);
+        residual_history.push_back(fcg.r_0_norm);
+        rstdout("Iter %2d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", 0, fcg.r_0_norm, 1.0);
 
-        precondition_nodes(nz, nr, subdomain, r0_norm2);
+        precondition_nodes(nz, nr, subdomain, {r0_norm2});
         np.copyFrom(nz, (size_t)num_local_nodes * sizeof(DType));
-        gamma_on_device = false; // the first iteration's projection kernel forms gamma itself
+        // (fcg.gamma_on_device is clear: the first iteration's projection kernel forms gamma itself)
     }
 
     DType fcg_nodes_step_residual()
@@ -1183,12 +1205,12 @@ class Domain
         gather_nodes(nq, q_k);
         fdd_timer().stop("domain.operator_application");
 
-        if (device_scalars and gamma_on_device and early_gamma)
+        if (device_scalars and fcg.gamma_on_device and early_gamma)
         {
-            // gamma = <z, r> already sits in scalars[0]: the flexible dot of the previous iteration formed it from the
+            // gamma = <z, r> already sits in scalars[fcg.gamma_slot]: the flexible dot of the previous iteration formed it from the
             // vectors it was reading anyway (fcg_nodes_step_direction); <p, q> is what is left of domain.okl:140-184
-            FDD_CALL(fdd_sub_inner_product(scalars.as<double>() + 1, reduce_ws.as<double>(), np.as<double>(), nq.as<double>(), nn, stream));
-            if (fdd::comm().size > 1) fdd::comm().allreduce_sum(scalars.as<double>() + 1, 1);
+            FDD_CALL(fdd_sub_inner_product(scalars.as<double>() + SLOT_PQ, reduce_ws.as<double>(), np.as<double>(), nq.as<double>(), nn, stream));
+            if (fdd::comm().size > 1) fdd::comm().allreduce_sum(scalars.as<double>() + SLOT_PQ, 1);
         }
         else
         {
@@ -1197,25 +1219,25 @@ class Domain
         }
         if (device_scalars)
         {
-            // gamma = scalars[gamma_slot] (kept for beta), theta = scalars[1]: alpha never visits the host
-            if (not(gamma_on_device and early_gamma)) gamma_slot = 0; // the projection kernel has just written it
-            FDD_CALL(fdd_dom_solution_and_residual_update_dev(nu.as<double>(), nr1.as<double>(), nr.as<double>(), np.as<double>(), nq.as<double>(), scalars.as<double>() + gamma_slot, scalars.as<double>() + 1, nn, stream));
+            // gamma = scalars[fcg.gamma_slot] (kept for beta), theta = scalars[SLOT_PQ]: alpha never visits the host
+            if (not(fcg.gamma_on_device and early_gamma)) fcg.gamma_slot = 0; // the projection kernel has just written it
+            FDD_CALL(fdd_dom_solution_and_residual_update_dev(nu.as<double>(), nr1.as<double>(), nr.as<double>(), np.as<double>(), nq.as<double>(), scalars.as<double>() + fcg.gamma_slot, scalars.as<double>() + SLOT_PQ, nn, stream));
             if (use_preconditioner and composite_precond) // r+ = r - alpha q on the points too (domain.okl:191), alpha from device memory
-                FDD_CALL(fdd_xmay_ratio_dev(rp.as<double>(), rp.as<double>(), scalars.as<double>() + gamma_slot, scalars.as<double>() + 1, q_k.as<double>(), num_local_points, stream));
-            pending_rhs_norm2 = node_norm_enqueue(nr1, /*defer_exchange=*/true); // finished inside the preconditioner's exchange
-            fcg_norm_pending = true;
+                FDD_CALL(fdd_xmay_ratio_dev(rp.as<double>(), rp.as<double>(), scalars.as<double>() + fcg.gamma_slot, scalars.as<double>() + SLOT_PQ, q_k.as<double>(), num_local_points, stream));
+            fcg.pending_rhs_norm2 = node_norm_enqueue(nr1, /*defer_exchange=*/true); // finished inside the preconditioner's exchange
+            fcg.norm_pending = true;
             return std::numeric_limits<DType>::quiet_NaN(); // fcg_nodes_norm() has the value
         }
         fetch_scalars(values, 2);
-        fcg_gamma_k = values[0];
-        const DType alpha_k = fcg_gamma_k / values[1];
+        fcg.gamma_k = values[0];
+        const DType alpha_k = fcg.gamma_k / values[1];
 
         FDD_CALL(fdd_dom_solution_and_residual_update(nu.as<double>(), nr1.as<double>(), nr.as<double>(), np.as<double>(), nq.as<double>(), alpha_k, nn, stream));
         if (use_preconditioner and composite_precond) FDD_CALL(fdd_vector_vector_addition(rp.as<double>(), 1.0, rp.as<double>(), -alpha_k, q_k.as<double>(), num_local_points, stream));
 
-        pending_rhs_norm2 = node_norm(r_norm, nr1);
+        fcg.pending_rhs_norm2 = node_norm(r_norm, nr1);
         residual_history.push_back(r_norm);
-        rstdout("Iter %2d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", fcg_iter + 1, r_norm, r_norm / fcg_r_0_norm);
+        rstdout("Iter %2d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", fcg.iter + 1, r_norm, r_norm / fcg.r_0_norm);
         return r_norm;
     }
 
@@ -1223,38 +1245,39 @@ class Domain
     DType fcg_nodes_norm()
     {
         const DType r_norm = node_norm_fetch();
-        fcg_norm_pending = false;
+        fcg.norm_pending = false;
         residual_history.push_back(r_norm);
-        rstdout("Iter %2d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", fcg_iter + 1, r_norm, r_norm / fcg_r_0_norm);
+        rstdout("Iter %2d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", fcg.iter + 1, r_norm, r_norm / fcg.r_0_norm);
         return r_norm;
     }
 
     template <typename PType>
-    void fcg_nodes_step_direction(PType &subdomain)
+    void fcg_nodes_step_direction(PType &subdomain, bool lazy_history = false)
     {
         const int nn = num_local_nodes;
         DType theta_k;
         // the inner solve's final update of z~ may ride in the flexible dot's pass below, which reads z~ first
         const bool fuse_update = fused_update_flexible_dot and device_scalars and early_gamma and &fdd_dom_lincomb_flexible_gamma != nullptr;
-        precondition_nodes(nz, nr1, subdomain, pending_rhs_norm2, fuse_update); // nr1 is untouched since its norm was enqueued (fcg_nodes_step_residual)
-        pending_rhs_norm2 = nullptr;
+        fdd::PendingUpdate pu; // owed from the inner solve's return to the flexible dot below
+        // nr1 is untouched since its norm was enqueued (fcg_nodes_step_residual)
+        precondition_nodes(nz, nr1, subdomain, {fcg.pending_rhs_norm2, lazy_history, fuse_update ? &pu : nullptr});
+        fcg.pending_rhs_norm2 = nullptr;
         if (device_scalars)
         {
-            // beta = scalars[3] / scalars[0] (theta / gamma), read by the update kernel; the residual norm's two
-            // parts sit right behind it (scalars[4..5]) and are summed over the ranks in the same collective
-            int theta_at = 3;
+            // beta = theta / gamma, read by the update kernel; the residual norm's two parts sit right behind theta
+            // (SLOT_THETA, SLOT_NORM) and are summed over the ranks in the same collective
+            int theta_at = SLOT_THETA;
             if (early_gamma)
             {
                 // {<z, r+> (the next iteration's gamma), theta} from one pass over r, r+, z.  The pair alternates between
-                // scalars[2..3] and scalars[6..7] (the current gamma must outlive it: beta reads it below), either side of
-                // the norm's two parts in scalars[4..5], so that one all-reduce still carries all four
-                const int next = (gamma_slot == 2) ? 6 : 2;
+                // SLOT_PAIR_A and SLOT_PAIR_B (the current gamma must outlive it: beta reads it below), either side of
+                // the norm's two parts, so that one all-reduce still carries all four
+                const int next = (fcg.gamma_slot == SLOT_PAIR_A) ? SLOT_PAIR_B : SLOT_PAIR_A;
                 theta_at = next + 1;
-                if (use_preconditioner and subdomain.pending_update.active)
+                if (pu.active)
                 {
                     // z~'s dof slice is formed here, by the statement the inner solve would have launched, and enters the two
                     // sums without a trip through memory; the inner right-hand side (r+'s slice) is read once for both
-                    auto &pu = subdomain.pending_update;
                     pu.active = false;
                     if (pu.q != nz.as<double>() + dof_shift or pu.n > nodes_sub_dofs)
                     {
@@ -1270,43 +1293,49 @@ class Domain
                     FDD_CALL(fdd_dom_inner_product_flexible_gamma(scalars.as<double>() + next, reduce_ws.as<double>(), nr.as<double>(), nr1.as<double>(), nz.as<double>(), nn, fdd::dev().stream));
                 if (fdd::comm().size > 1)
                 {
-                    if (norm_reduce_pending)
-                        fdd::comm().allreduce_sum(scalars.as<double>() + (next == 2 ? 2 : 4), 4);
+                    if (norm_state.reduce_pending)
+                        fdd::comm().allreduce_sum(scalars.as<double>() + std::min(next, SLOT_NORM), 4); // pair A + norm, or norm + pair B
                     else
                         fdd::comm().allreduce_sum(scalars.as<double>() + next, 2);
                 }
-                norm_reduce_pending = false;
+                norm_state.reduce_pending = false;
                 // p = z + beta p; "r = r+" (domain.okl:226-233) is a swap of the two node vectors, not a copy
-                FDD_CALL(fdd_xpby_ratio_dev(np.as<double>(), nz.as<double>(), scalars.as<double>() + theta_at, scalars.as<double>() + gamma_slot, np.as<double>(), nn, fdd::dev().stream));
-                gamma_slot = next;
+                FDD_CALL(fdd_xpby_ratio_dev(np.as<double>(), nz.as<double>(), scalars.as<double>() + theta_at, scalars.as<double>() + fcg.gamma_slot, np.as<double>(), nn, fdd::dev().stream));
+                fcg.gamma_slot = next;
             }
             else
             {
-                FDD_CALL(fdd_dom_inner_product_flexible(scalars.as<double>() + 3, reduce_ws.as<double>(), nr.as<double>(), nr1.as<double>(), nz.as<double>(), nn, fdd::dev().stream));
-                if (fdd::comm().size > 1) fdd::comm().allreduce_sum(scalars.as<double>() + 3, norm_reduce_pending ? 3 : 1);
-                norm_reduce_pending = false;
-                FDD_CALL(fdd_xpby_ratio_dev(np.as<double>(), nz.as<double>(), scalars.as<double>() + 3, scalars.as<double>() + gamma_slot, np.as<double>(), nn, fdd::dev().stream));
+                FDD_CALL(fdd_dom_inner_product_flexible(scalars.as<double>() + SLOT_THETA, reduce_ws.as<double>(), nr.as<double>(), nr1.as<double>(), nz.as<double>(), nn, fdd::dev().stream));
+                if (fdd::comm().size > 1) fdd::comm().allreduce_sum(scalars.as<double>() + SLOT_THETA, norm_state.reduce_pending ? 3 : 1);
+                norm_state.reduce_pending = false;
+                FDD_CALL(fdd_xpby_ratio_dev(np.as<double>(), nz.as<double>(), scalars.as<double>() + SLOT_THETA, scalars.as<double>() + fcg.gamma_slot, np.as<double>(), nn, fdd::dev().stream));
             }
-            gamma_on_device = early_gamma;
+            fcg.gamma_on_device = early_gamma;
             std::swap(nr, nr1);
         }
         else
         {
-            gamma_on_device = false;
+            fcg.gamma_on_device = false;
             FDD_CALL(fdd_dom_inner_product_flexible(scalars.as<double>(), reduce_ws.as<double>(), nr.as<double>(), nr1.as<double>(), nz.as<double>(), nn, fdd::dev().stream));
             fetch_scalars(&theta_k, 1);
-            const DType beta_k = theta_k / fcg_gamma_k;
+            const DType beta_k = theta_k / fcg.gamma_k;
             FDD_CALL(fdd_dom_residual_and_search_update(np.as<double>(), nr.as<double>(), nz.as<double>(), nr1.as<double>(), beta_k, nn, fdd::dev().stream));
         }
+        if (pu.active)
+        {
+            // the inner solve left its final update to this function and no branch above formed it: z~ was never written
+            fprintf(stderr, "ERROR: an inner solve's deferred final update was dropped\n");
+            exit(EXIT_FAILURE);
+        }
         num_iterations++;
-        fcg_iter++;
+        fcg.iter++;
     }
 
     // u = Q u~: hand the solution back on the element-local points
     void fcg_finish()
     {
-        if (not fcg_nodes_active) return;
-        Q.multiply(fcg_u_pts, nu);
+        if (not fcg.nodes_active) return;
+        Q.multiply(fcg.u_pts, nu);
     }
 
     // domain.tpp:611-725.  The loop body is exposed as fcg_begin / fcg_step so
@@ -1317,40 +1346,37 @@ class Domain
     {
         residual_history.clear();
         num_iterations = 0;
-        fcg_iter = 0;
-        fcg_nodes_active = false;
+        fcg = FcgRun();
+        norm_state = NormInFlight();
         if (can_fcg_nodes(subdomain))
         {
             fcg_nodes_begin(u, f, subdomain);
             return;
         }
-        fcg_u = u;
+        fcg.u = u;
 
         fdd_timer().start("domain.vector_operations");
-        FDD_CALL(fdd_dom_initialize_arrays(fcg_u.as<double>(), r_k.as<double>(), f.as<double>(), num_local_points, fdd::dev().stream));
+        FDD_CALL(fdd_dom_initialize_arrays(u.as<double>(), r_k.as<double>(), f.as<double>(), num_local_points, fdd::dev().stream));
         fdd_timer().stop("domain.vector_operations");
 
         fdd_timer().start("domain.residual_norm");
-        residual_norm(fcg_r_0_norm, r_k);
+        residual_norm(fcg.r_0_norm, r_k);
         fdd_timer().stop("domain.residual_norm");
 
-        residual_history.push_back(fcg_r_0_norm);
-        rstdout("Iter %2d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", 0, fcg_r_0_norm, 1.0);
+        residual_history.push_back(fcg.r_0_norm);
+        rstdout("Iter %2d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", 0, fcg.r_0_norm, 1.0);
 
         apply_preconditioner(z_k, r_k, subdomain);
 
         fdd_timer().start("domain.vector_operations");
         p_k.copyFrom(z_k, (size_t)num_local_points * sizeof(DType));
         fdd_timer().stop("domain.vector_operations");
-
-        num_iterations = 0;
-        fcg_iter = 0;
     }
 
     // first half of an iteration: q = A p, alpha, u += alpha p, r+ = r - alpha q, ||r+||
     DType fcg_step_residual()
     {
-        if (fcg_nodes_active) return fcg_nodes_step_residual();
+        if (fcg.nodes_active) return fcg_nodes_step_residual();
         DType theta_k, r_norm;
 
         fdd_timer().start("domain.operator_application");
@@ -1358,13 +1384,13 @@ class Domain
         fdd_timer().stop("domain.operator_application");
 
         fdd_timer().start("domain.inner_products");
-        projection_inner_products(fcg_gamma_k, theta_k, z_k, r_k, p_k, q_k);
+        projection_inner_products(fcg.gamma_k, theta_k, z_k, r_k, p_k, q_k);
         fdd_timer().stop("domain.inner_products");
 
-        const DType alpha_k = fcg_gamma_k / theta_k;
+        const DType alpha_k = fcg.gamma_k / theta_k;
 
         fdd_timer().start("domain.vector_operations");
-        solution_and_residual_update(fcg_u, r_kp1, r_k, p_k, q_k, alpha_k);
+        solution_and_residual_update(fcg.u, r_kp1, r_k, p_k, q_k, alpha_k);
         fdd_timer().stop("domain.vector_operations");
 
         fdd_timer().start("domain.residual_norm");
@@ -1372,7 +1398,7 @@ class Domain
         fdd_timer().stop("domain.residual_norm");
 
         residual_history.push_back(r_norm);
-        rstdout("Iter %2d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", fcg_iter + 1, r_norm, r_norm / fcg_r_0_norm);
+        rstdout("Iter %2d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", fcg.iter + 1, r_norm, r_norm / fcg.r_0_norm);
         return r_norm;
     }
 
@@ -1380,7 +1406,7 @@ class Domain
     template <typename PType>
     void fcg_step_direction(PType &subdomain)
     {
-        if (fcg_nodes_active)
+        if (fcg.nodes_active)
         {
             fcg_nodes_step_direction(subdomain);
             return;
@@ -1393,14 +1419,14 @@ class Domain
         inner_product_flexible(theta_k, r_k, r_kp1, z_k);
         fdd_timer().stop("domain.inner_products");
 
-        const DType beta_k = theta_k / fcg_gamma_k;
+        const DType beta_k = theta_k / fcg.gamma_k;
 
         fdd_timer().start("domain.vector_operations");
         residual_and_search_update(p_k, r_k, z_k, r_kp1, beta_k);
         fdd_timer().stop("domain.vector_operations");
 
         num_iterations++;
-        fcg_iter++;
+        fcg.iter++;
     }
 
     // one full PCG iteration without stopping tests (what bench.py calls a step)
@@ -1408,14 +1434,14 @@ class Domain
     DType fcg_step(PType &subdomain)
     {
         DType r_norm = fcg_step_residual();
-        if (fcg_norm_pending)
+        if (fcg.norm_pending)
         {
             // the norm's reductions are in the queue; the preconditioner is enqueued behind them
             // before the host waits for the value (the inner solve synchronises at its end anyway)
             fcg_step_direction(subdomain);
-            fcg_iter--; // the history line belongs to the iteration just counted
+            fcg.iter--; // the history line belongs to the iteration just counted
             r_norm = fcg_nodes_norm();
-            fcg_iter++;
+            fcg.iter++;
             return r_norm;
         }
         fcg_step_direction(subdomain);
@@ -1424,13 +1450,13 @@ class Domain
 
     // K iterations without stopping tests (what bench.py times).  In the node-space / device-scalar mode nothing
     // in an iteration needs the host: the norms go to a device-side history and are read once at the end, the
-    // inner solves run without their end-of-cycle read (Subdomain::lazy_history).  Same arithmetic, same order.
+    // inner solves run without their end-of-cycle read (InnerSolveHints::lazy_history).  Same arithmetic, same order.
     template <typename PType>
     DType fcg_steps(PType &subdomain, int K)
     {
         DType r_norm = std::numeric_limits<DType>::quiet_NaN();
         if (K <= 0) return r_norm;
-        if (not(fcg_nodes_active and device_scalars and lazy_steps))
+        if (not(fcg.nodes_active and device_scalars and lazy_steps))
         {
             for (int s = 0; s < K; s++) r_norm = fcg_step(subdomain);
             return r_norm;
@@ -1441,22 +1467,19 @@ class Domain
             norm_hist = fdd::dev().malloc<DType>(K);
             norm_hist_cap = K;
         }
-        const bool saved = subdomain.lazy_history;
-        subdomain.lazy_history = true;
         for (int s = 0; s < K; s++)
         {
             fcg_nodes_step_residual();
-            fcg_nodes_step_direction(subdomain);
-            FDD_CALL(fdd_sqrt_sum_dev(norm_hist.as<double>() + s, scalars.as<double>() + 4, norm_parts, fdd::dev().stream));
-            fcg_norm_pending = false;
+            fcg_nodes_step_direction(subdomain, /*lazy_history=*/true);
+            FDD_CALL(fdd_sqrt_sum_dev(norm_hist.as<double>() + s, scalars.as<double>() + SLOT_NORM, norm_state.parts, fdd::dev().stream));
+            fcg.norm_pending = false;
         }
-        subdomain.lazy_history = saved;
         std::vector<DType> h(K);
         norm_hist.copyTo(h.data(), (size_t)K * sizeof(DType)); // the one synchronisation of the K iterations
         for (int s = 0; s < K; s++)
         {
             residual_history.push_back(h[s]);
-            rstdout("Iter %2d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", fcg_iter - K + s + 1, h[s], h[s] / fcg_r_0_norm);
+            rstdout("Iter %2d: | residual_norm = %24.16g | relative_residual_norm = %24.16g | \n", fcg.iter - K + s + 1, h[s], h[s] / fcg.r_0_norm);
         }
         return h[K - 1];
     }
@@ -1470,26 +1493,26 @@ class Domain
         {
             DType r_norm = fcg_step_residual();
             bool direction_done = false;
-            if (fcg_norm_pending)
+            if (fcg.norm_pending)
             {
                 // device_scalars: the second half of the iteration is enqueued before the host reads
                 // the norm.  If the tests below stop the solve, that half was speculative: it touched
                 // z, p, r only, never the solution, and its iteration count is taken back.
                 fcg_step_direction(subdomain);
                 direction_done = true;
-                fcg_iter--;
+                fcg.iter--;
                 r_norm = fcg_nodes_norm();
-                fcg_iter++;
+                fcg.iter++;
             }
 
-            bool stop = use_relative ? (r_norm / fcg_r_0_norm < tolerance) : (r_norm < tolerance);
+            bool stop = use_relative ? (r_norm / fcg.r_0_norm < tolerance) : (r_norm < tolerance);
             if (std::isnan(r_norm)) stop = true;
             if (stop)
             {
                 if (direction_done)
                 {
                     num_iterations--;
-                    fcg_iter--;
+                    fcg.iter--;
                 }
                 break;
             }
@@ -1548,6 +1571,7 @@ class Domain
             gmres_nodes_vectors = m;
         }
         residual_history.clear();
+        norm_state = NormInFlight();
 
         // the assembled copy <., .> reads: gs over the ranks on the interface prefix, nothing to do on one rank
         auto assembled = [&](int i) -> fdd::memory & {

@@ -1033,6 +1033,12 @@ class Subdomain
     }
 
   private:
+    // a new inner solve starts
+    void begin_inner_solve()
+    {
+        residual_history.clear();
+        history_pending = false; // a lazy solve before this one (pcg_steps) may have left its history on the device: it is not this solve's
+    }
 
   public:
     bool composite_dof_space() const { return is_composite and comp_dofs_ready and assembled_inner and device_bookkeeping and num_vectors <= FDD_MULTI_MAX; }
@@ -1041,13 +1047,13 @@ class Subdomain
     // z~ = M^-1 r for the node-space outer solve: r is the outer residual on the rank's own points (the degree tree
     // and the ring / superdomain exchange start from it), the result the dof-space correction (its leading own_dofs()
     // entries follow the Domain's node order)
-    void gmres_composite_dofs(fdd::memory &ua_out, fdd::memory &r_pts, bool print_history = true, bool use_relative = false, const double *own_assembled = nullptr)
+    void gmres_composite_dofs(fdd::memory &ua_out, fdd::memory &r_pts, bool print_history = true, bool use_relative = false, const double *own_assembled = nullptr, const fdd::InnerSolveHints &hints = {})
     {
         fdd::memory &fa = krylov64.fa;
         if (not fa.ptr()) fa = fdd::dev().malloc<DType>(std::max(dof_alloc_size(), 1));
         tree_operator(f, r_pts);
         composite_rhs_dofs(fa, f, own_assembled);
-        gmres_dofs_device(ua_out, fa, print_history, use_relative);
+        gmres_dofs_device(ua_out, fa, print_history, use_relative, hints);
     }
     fdd::memory new_dof_vector() { return fdd::dev().malloc<DType>(std::max(dof_alloc_size(), 1)); }
     // the two exchanges of tree_operator alone, on their buffers' current contents (bench.py's communication timings)
@@ -1429,15 +1435,9 @@ class Subdomain
     bool assembled_inner = true;          // inner GMRES on vectors over the dofs: Q fused into the stiffness load, no point-space Krylov basis
     bool device_bookkeeping = true;       // assembled inner GMRES: Givens / stopping tests in one-thread kernels, one host sync per cycle
     bool unit_norm_weight() const { return norm_weight_is_one; }
-    const double *known_rhs_norm2_dev = nullptr; // set by the caller around one solve: |f~|^2 over the dofs, already on the device (double-precision device GMRES only)
     bool fold_coarse_exchange = true;     // the coarse level's blocks travel inside the ring pull's group (false: an all-gather of their own)
     bool skip_last_basis_store = true;    // device GMRES: the last Arnoldi step of a cycle forms the norm of its vector without storing it (nobody reads it)
-    bool lazy_history = false;            // single-cycle inner solves do not synchronise at all; finish_history() fetches on demand
-    bool history_pending = false;
-    // the lazy single cycle's final update, described instead of launched (fdd::PendingUpdate, domain.hpp): only the
-    // double-precision device GMRES on its lazy branch defers; every other solve leaves `active` clear and has updated u~
-    bool defer_final_update = false;
-    fdd::PendingUpdate pending_update;
+    bool history_pending = false;         // the last solve ran with InnerSolveHints::lazy_history and its history is still on the device
 
     // residual_history of the last lazy solve (one blocking read of the device state)
     void finish_history()
@@ -1964,8 +1964,7 @@ class Subdomain
     void flexible_conjugate_gradient(fdd::memory &u_l, fdd::memory &f_l, bool print_history = true, bool use_relative = false)
     {
         if (inner_solver == 1) return generalized_minimum_residual(u_l, f_l, print_history, use_relative); // Chebyshev-Jacobi takes the place of either Krylov solve
-        residual_history.clear();
-        history_pending = false; // a lazy solve before this one (pcg_steps) may have left its history on the device: it is not this solve's
+        begin_inner_solve();
         tree_operator(r_k, f_l);
 
         fdd_timer().start("subdomain.vector_operations");
@@ -2095,8 +2094,7 @@ class Subdomain
         krylov64.ensure(num_vectors, std::max(nd, 1), false);
         std::vector<fdd::memory> &VA = krylov64.VA;
         fdd::memory &qa = krylov64.qa;
-        residual_history.clear();
-        history_pending = false; // a lazy solve before this one (pcg_steps) may have left its history on the device: it is not this solve's
+        begin_inner_solve();
 
         tree_operator(f, f_l);
         initialize_arrays(u_k, r_k, f);
@@ -2243,19 +2241,19 @@ class Subdomain
     // synchronises ONCE per cycle, to read the history and the stopping column.  A stop
     // inside a cycle is recorded, not acted on: the remaining steps run on vectors
     // nobody uses and the update takes the columns the reference would have taken.
-    void gmres_dofs_device(fdd::memory &ua, fdd::memory &fa, bool print_history, bool use_relative)
+    void gmres_dofs_device(fdd::memory &ua, fdd::memory &fa, bool print_history, bool use_relative, const fdd::InnerSolveHints &hints = {})
     {
         if (inner_solver == 1) return chebyshev_dofs(ua, fa);
         if (precision == 32)
-            gmres_dofs_device_t(krylov32, ua, fa, print_history, use_relative);
+            gmres_dofs_device_t(krylov32, ua, fa, print_history, use_relative, hints);
         else
-            gmres_dofs_device_t(krylov64, ua, fa, print_history, use_relative);
+            gmres_dofs_device_t(krylov64, ua, fa, print_history, use_relative, hints);
     }
 
     // Real = float is the reference's PTYPE = Float: the same recurrences and the same device bookkeeping on float vectors
     // (prepare_single_precision), with the casts of subdomain.okl:268-282 at the two ends; ua_io / fa_io are double either way.
     template <typename Real>
-    void gmres_dofs_device_t(DofKrylov<Real> &K, fdd::memory &ua_io, fdd::memory &fa_io, bool print_history, bool use_relative)
+    void gmres_dofs_device_t(DofKrylov<Real> &K, fdd::memory &ua_io, fdd::memory &fa_io, bool print_history, bool use_relative, const fdd::InnerSolveHints &hints = {})
     {
         constexpr bool f32 = std::is_same<Real, float>::value;
         namespace ops = fdd::ops;
@@ -2276,7 +2274,7 @@ class Subdomain
         }
         Real *ua = (f32 ? K.ua : ua_io).template as<Real>(), *fa = (f32 ? K.fa : fa_io).template as<Real>(), *qa = K.qa.template as<Real>();
         if (not gmres_state.ptr()) gmres_state = fdd::dev().malloc<char>(fdd_gmres_state_bytes());
-        residual_history.clear();
+        begin_inner_solve();
         double *sc = scalars.as<double>();
         double *ws = reduce_ws.as<double>();
         // NULL: unit weights, not read (the composite iterates on its unique dofs: all weights 1; the float reductions take none)
@@ -2311,8 +2309,7 @@ class Subdomain
         // u~ starts at 0 (subdomain.tpp:4270-4275); the first update writes it without reading it
         int iter = 0;
         bool first_cycle = true;
-        history_pending = false;
-        const bool lazy = lazy_history and max_iterations <= m and fdd::globals().pstdout_file == nullptr;
+        const bool lazy = hints.lazy_history and max_iterations <= m and fdd::globals().pstdout_file == nullptr;
         std::vector<Real *> W(m + 1), ptrs(m + 1);
         std::vector<double> hist(FDD_MULTI_MAX + 1);
 
@@ -2327,8 +2324,8 @@ class Subdomain
                 W[0] = K.VA[0].template as<Real>();
                 ops::vector_vector_addition(W[0], 1, fa, -1, qa, nd, stream);
             }
-            if (not f32 and first_cycle and known_rhs_norm2_dev and nw == nullptr)
-                FDD_CALL(fdd_gmres_begin_dev(st, known_rhs_norm2_dev, 1, stream)); // the caller has just formed |f~|^2 with this very call (Domain::node_norm_enqueue)
+            if (not f32 and first_cycle and hints.known_rhs_norm2 and nw == nullptr)
+                FDD_CALL(fdd_gmres_begin_dev(st, hints.known_rhs_norm2, 1, stream)); // the caller has just formed |f~|^2 with this very call (Domain::node_norm_enqueue)
             else
             {
                 ops::multi_dot(sc, ws, W[0], W.data(), nullptr, 1, nw, nd, stream);
@@ -2372,17 +2369,13 @@ class Subdomain
                 FDD_CALL(fdd_gmres_last_column(st, &last_dev));
                 bool deferred = false;
                 if constexpr (not f32)
-                    if (defer_final_update)
+                    if (fdd::PendingUpdate *pu = hints.defer_into)
                     {
                         // the caller launches it, inside the pass that reads u~ first (Domain::fcg_nodes_step_direction)
-                        pending_update.active = deferred = true;
-                        pending_update.q = ua;
-                        pending_update.q_is_zero = 1;
-                        pending_update.coeffs_dev = y_dev;
-                        pending_update.scales_dev = scales;
-                        pending_update.last_dev = last_dev;
-                        pending_update.v.assign(ptrs.begin(), ptrs.begin() + m);
-                        pending_update.n = nd;
+                        pu->active = deferred = true;
+                        pu->q = ua, pu->q_is_zero = 1, pu->n = nd;
+                        pu->coeffs_dev = y_dev, pu->scales_dev = scales, pu->last_dev = last_dev;
+                        pu->v.assign(ptrs.begin(), ptrs.begin() + m);
                     }
                 if (not deferred) ops::lincomb_limited(ua, 1, y_dev, ptrs.data(), scales, last_dev, m, nd, stream);
                 history_pending = true;
@@ -2430,8 +2423,8 @@ class Subdomain
     // symmetric, linear operator.  The coefficients are formed here in double and passed by value.  One pass per step
     // (fdd_cheby_step), in a conforming region as the epilogue of the gather Qt that ends the operator application
     // (fdd_csr_plan_gather_cheby), or composed from vector_vector_addition / diagonal_scaling where the kernel library
-    // has neither: the same bits in all three.  The history stays empty; known_rhs_norm2_dev and defer_final_update are
-    // not looked at (x is written in place, no update is left pending).
+    // has neither: the same bits in all three.  The history stays empty; the caller's InnerSolveHints are not looked
+    // at (x is written in place, no update is left pending).
     // ------------------------------------------------------------------
     // why this problem cannot run it, or nullptr
     const char *chebyshev_refusal() const
@@ -2510,8 +2503,7 @@ class Subdomain
         Real *x = (f32 ? C.x : ua_io).template as<Real>(), *d = C.d.template as<Real>(), *r = C.r.template as<Real>(), *q = C.q.template as<Real>(), *t = C.t.template as<Real>();
         const Real *f = (f32 ? C.f : fa_io).template as<Real>();
         const Real *dinv = (f32 ? jacobi_dinv_f32 : jacobi_dinv).template as<Real>();
-        residual_history.clear();
-        history_pending = false;
+        begin_inner_solve();
 
         const bool kernels = cheby.use_kernels and fdd::missing_chebyshev_entry(false) == nullptr;
         // the float gather takes no norm weight; the double one may: then the separate pass stays
@@ -2589,18 +2581,12 @@ class Subdomain
     }
 
     // the solve itself, dof vectors in and out (callers that already hold assembled data skip Qt / Q)
-    void gmres_dofs(fdd::memory &ua, fdd::memory &fa, bool print_history = true, bool use_relative = false)
+    void gmres_dofs(fdd::memory &ua, fdd::memory &fa, bool print_history = true, bool use_relative = false, const fdd::InnerSolveHints &hints = {})
     {
-        if (pending_update.active)
-        {
-            // a caller asked for the last solve's final update to be deferred and never formed it: that u~ was never written
-            fprintf(stderr, "ERROR: an inner solve's deferred final update was dropped\n");
-            exit(EXIT_FAILURE);
-        }
         if (inner_solver == 1) return chebyshev_dofs(ua, fa);
         if (device_bookkeeping and num_vectors <= FDD_MULTI_MAX)
         {
-            gmres_dofs_device(ua, fa, print_history, use_relative);
+            gmres_dofs_device(ua, fa, print_history, use_relative, hints);
             return;
         }
         const int nd = subdomain_operator.num_extended_dofs;
@@ -2612,8 +2598,7 @@ class Subdomain
         krylov64.ensure(m, std::max(nd, 1), pre);
         std::vector<fdd::memory> &VA = krylov64.VA, &ZA = krylov64.ZA;
         fdd::memory &qa = krylov64.qa;
-        residual_history.clear();
-        history_pending = false; // a lazy solve before this one (pcg_steps) may have left its history on the device: it is not this solve's
+        begin_inner_solve();
         double *sc = scalars.as<double>();
         double *ws = reduce_ws.as<double>();
         const double *nw = norm_weight_is_one ? nullptr : norm_weight.as<double>(); // NULL: unit weights, not read
@@ -2707,8 +2692,7 @@ class Subdomain
         }
 
         if ((int)Z.size() != num_vectors) allocate_krylov();
-        residual_history.clear();
-        history_pending = false; // a lazy solve before this one (pcg_steps) may have left its history on the device: it is not this solve's
+        begin_inner_solve();
 
         tree_operator(f, f_l);
 

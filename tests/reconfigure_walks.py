@@ -15,7 +15,9 @@ already relies on run-to-run repeatability; the control (two fresh(ck) runs) is 
 A walk is a named list of (label, changes) steps; changes are relative to the step before.  A failure names the walk,
 the step and its label, i.e. the transition.
 
-Run as a program (the CPU test does): reconfigure_walks.py <libfdd_host_cpu.so> <walk name>.
+Besides the walks: a stepwise run abandoned while it is live, then other solves (ABANDONED, run_abandoned_stepwise).
+
+Run as a program (the CPU test does): reconfigure_walks.py <libfdd_host_cpu.so> <walk name, or a name of ABANDONED>.
 """
 import sys
 
@@ -420,6 +422,50 @@ def run_walk(driver, name):
         p.close()
 
 
+# ---- a stepwise run abandoned while it is live: an order no walk runs (their pcg_begin / pcg_steps always end in pcg_solution
+# and nothing follows inside the step).  The two one-rank boxes whose dof slice ends at an odd and at an even node
+# (test_gpu_fused_passes.py), with the V-cycle inside the inner solve.
+ABANDONED = {
+    "abandoned_stepwise_odd_slice_end": ("box", (4, 4, 4), 3, 2),
+    "abandoned_stepwise_even_slice_end": ("box", (4, 3, 3), 5, 4),
+}
+
+
+def run_abandoned_stepwise(driver, name):
+    """pcg_begin, pcg_steps(2) and no pcg_solution -- the inner solve's lazy history is still on the device and the outer
+    solver's run state is that of iteration 2 -- then solve(fcg), solve(gmres) and precond_apply(gmres) with another
+    right-hand side: the bits (vectors, histories, iteration counts) of a fresh problem given the same three calls."""
+    S = driver.S
+    mesh = ABANDONED[name]
+    c = dict(BASE, amg="host", sub_use_preconditioner=1)
+
+    def three_calls(p):
+        r = S.seeded_uniform(p.n, 16) - 0.5
+        _, f2 = p.make_rhs_from(S.seeded_uniform(p.n, 1235))
+        out = {}
+        for method in ("fcg", "gmres"):
+            out[method + ".u"], out[method + ".iterations"], out[method + ".history"] = p.solve(f2, method)
+        out["precond.z"], out["precond.history"] = p.precond_apply(r, "gmres")
+        return out
+
+    outs = []
+    for abandon in (True, False):
+        p = driver.build(mesh)
+        try:
+            driver.apply(p, c, {})
+            if abandon:
+                _, f1 = p.make_rhs_from(S.seeded_uniform(p.n, 1234))
+                p.pcg_begin(f1)
+                assert np.isfinite(p.pcg_steps(2))
+            outs.append(three_calls(p))
+        finally:
+            p.close()
+    bad = differences(outs[0], outs[1])
+    print("  %s: %s" % (name, "same bits as a fresh problem" if not bad else bad))
+    assert outs[1]["fcg.iterations"] > 2 and outs[1]["gmres.iterations"] > 2 and len(outs[1]["precond.history"]) > 1
+    assert not bad, "%s: after an abandoned stepwise run the problem differs from a fresh one: %s" % (name, "; ".join(bad))
+
+
 def families_have_an_oracle_walk():
     return {f: [n for n, w in WALKS.items() if w["family"] == f and w.get("oracle")] for f in FAMILIES}
 
@@ -439,5 +485,5 @@ if __name__ == "__main__":
     H.init(0, use_torch_stream=False)
     H.comm_single()
     H.set_print(False)
-    run_walk(Driver(H, S, lib), walk)
+    (run_abandoned_stepwise if walk in ABANDONED else run_walk)(Driver(H, S, lib), walk)
     print("ok")

@@ -52,3 +52,11 @@ def test_the_walk_tables_cover_what_they_claim():
 def test_reconfigured_problem_equals_a_fresh_one(cpu_host_lib, walk):
     out = subprocess.run([sys.executable, os.path.join(S.HERE, "reconfigure_walks.py"), cpu_host_lib, walk], capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0 and out.stdout.rstrip().endswith("ok"), out.stdout[-4000:] + out.stderr[-4000:]
+
+
+@pytest.mark.parametrize("name", sorted(R.ABANDONED))
+def test_an_abandoned_stepwise_run_leaves_nothing_behind(cpu_host_lib, name):
+    """reconfigure_walks.run_abandoned_stepwise: pcg_begin and pcg_steps(2) without pcg_solution, then two solves and a
+    preconditioner application with another right-hand side, against a fresh problem given the same three calls"""
+    out = subprocess.run([sys.executable, os.path.join(S.HERE, "reconfigure_walks.py"), cpu_host_lib, name], capture_output=True, text=True, timeout=1500)
+    assert out.returncode == 0 and out.stdout.rstrip().endswith("ok"), out.stdout[-4000:] + out.stderr[-4000:]

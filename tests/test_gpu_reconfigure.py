@@ -30,5 +30,10 @@ def test_reconfigured_problem_equals_a_fresh_one(own_stream, walk):
     R.run_walk(R.Driver(H, S, lib), walk)
 
 
+@pytest.mark.parametrize("name", sorted(R.ABANDONED))
+def test_an_abandoned_stepwise_run_leaves_nothing_behind(own_stream, name):
+    R.run_abandoned_stepwise(R.Driver(H, S, lib), name)
+
+
 def test_the_device_built_hierarchy_is_walked_here():
     assert "vcycle_device" in R.walk_names(cpu=False) and R.WALKS["vcycle_device"]["base"]["amg"] == "device"
