@@ -4,8 +4,13 @@ as device-to-device copies / rank-ordered sums between the ranks' buffers).  2x2
 ranks, 2x2x2 the corner shared by eight, through the HIP kernels and Comm::exchange on device buffers -- the pool
 allows at most 6 processes on a GPU, so eight ranks cannot be eight processes there.
 
+CASES are the composites with three or more polynomial levels (rings at N - r, N - 2r, ... between the rank's own
+elements and the degree-1 far field), overlaps other than 1, the strip of three ranks and the Kershaw mesh: each
+states the number of levels it expects, and every rank's Subdomain is held to one kernel choice per level list.
+
 Used by tests/test_gpu_comm.py on the GPU (product libraries) and, with the CPU stand-in of the kernel C-ABI, by
-tests/test_cpu_multirank.py as `python tests/local_world_checks.py --cpu-shim <world> <Ex,Ey,Ez> <N> <red>`.
+tests/test_cpu_multirank.py as `python tests/local_world_checks.py --cpu-shim <world> <Ex,Ey,Ez> <N> <red>`, followed
+by any of `overlaps=a,b kershaw=1 outer_cap=K levels=L composite_levels=L amg_method=gmres no_superdomain=r,...`.
 """
 import os
 import sys
@@ -16,16 +21,61 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.dirname(HERE))
 
+RESTART = 20  # the outer GMRES restart length of both sides (the host layer's default, OracleWorld.solve's default)
+# A capped outer solve runs max_iterations = cap with tolerance 0 on both sides.  The cap is the smallest multiple of RESTART
+# that is >= 20: between restarts the Domain loop runs one step more than it counts.  Next to each capped case: the largest
+# |history - oracle history| / r0 (bar 1e-8) and |u - oracle u| / max|u| (bar 1e-8, Kershaw 1e-6) over the capped solves of
+# all ranks, oracle against the CPU stand-in at that cap.
+CAP = 20
+CASES = {
+    "four_levels": dict(world=2, E=(10, 2, 2), N=7, red=2, levels=4),  # 7, 5, 3, 1: a line list next to three slab-form lists
+    "four_levels_wide_superdomain": dict(world=2, E=(12, 2, 2), N=7, red=2, overlaps=(1, 2), levels=4, outer_cap=CAP),  # 5.0e-16, 7.0e-15
+    "reduction_one": dict(world=2, E=(16, 4, 4), N=3, red=1, overlaps=(1, 2), levels=3),  # 3, 2, 1
+    "three_levels_four_ranks": dict(world=4, E=(8, 8, 2), N=5, red=2, levels=3),  # 5, 3, 1
+    "strip_of_three": dict(world=3, E=(9, 2, 2), N=5, red=2, levels=3, no_superdomain=(1,)),  # the middle rank's rings reach both ends
+    "kershaw_four_levels": dict(world=2, E=(10, 2, 2), N=7, red=2, kershaw=True, levels=4, outer_cap=CAP),  # 3.0e-14, 7.9e-13
+    # the reference's own developer run (Kershaw, 8 ranks, N = 2, reduction 1, overlaps 1 / 1, outer GMRES, V-cycle on) on fewer
+    # elements than its 16^3, whose superdomain is coarsened in three composite levels (1694, 200, 18 kept dofs on rank 0).
+    # 8^3 has one composite level (343 kept dofs: nothing is aggregated), so the case runs (16, 8, 8), which has two (588, 22):
+    # 1.6e-14, 2.0e-14.  (32, 4, 4) has as many elements as 8^3 and the three composite levels (180, 18, 9): 6.4e-14, 2.7e-13
+    "reference_developer_run": dict(world=8, E=(16, 8, 8), N=2, red=1, kershaw=True, levels=2, composite_levels=2, outer_cap=CAP, amg_method="gmres"),
+    "developer_run_three_composite_levels": dict(world=8, E=(32, 4, 4), N=2, red=1, kershaw=True, levels=2, composite_levels=3, outer_cap=CAP, amg_method="gmres"),
+}
 
-def run(world, E, N, red, amg=True):
+
+def command_line(case):
+    """the arguments after [--cpu-shim] that run a case of CASES"""
+    case = dict(case)
+    args = [str(case.pop("world")), ",".join(map(str, case.pop("E"))), str(case.pop("N")), str(case.pop("red"))]
+    text = lambda v: ",".join(map(str, v)) if isinstance(v, tuple) else str(int(v)) if isinstance(v, bool) else str(v)
+    return args + ["%s=%s" % (name, text(value)) for name, value in case.items()]
+
+
+def run(world, E, N, red, amg=True, overlaps=(1, 1), kershaw=False, outer_cap=None, levels=None, composite_levels=None, amg_method="fcg", no_superdomain=None, product=True):
+    """levels: the number of polynomial levels the region of every rank must hold (None: more than one);
+    composite_levels: the length of every rank's list of composite levels; no_superdomain: exactly these ranks have no
+    superdomain dof; outer_cap: every outer solve of both sides runs that many steps with tolerance 0;
+    product: the kernel library is the product's (every optional stiffness entry present), not the CPU stand-in (none)."""
+    import stiffness_choice_rules as R
     import support as S
     from polynomial_reduction_with_full_domain_decomposition_preconditioner_amd import host_api as H
     from polynomial_reduction_with_full_domain_decomposition_preconditioner_amd import lib
 
+    assert outer_cap is None or (outer_cap > 0 and outer_cap % RESTART == 0), outer_cap
+    capped = dict(max_iterations=outer_cap, tolerance=0.0, num_vectors=RESTART) if outer_cap else {}
     Pg = S.rank_grid(world)
-    meshes = [S.BoxMesh(E, N, Pg, r) for r in range(world)]
+    degrees = S.level_degrees(N, red)
+    if kershaw:  # the reference's experiment geometry, generated by the host layer; the oracle's world gets the host layer's bits
+        import tempfile
+
+        kdir = tempfile.mkdtemp(prefix="fdd_kershaw_")
+        level_meshes = [[S.kershaw_mesh_of_the_host_layer(lib.host(), kdir, E, d, 0.3, Pg, r) for d in degrees] for r in range(world)]
+        meshes = [row[0] for row in level_meshes]
+        F = S.OracleFdd(E, N, red, Pg, overlaps[0], overlaps[1], meshes=level_meshes)
+    else:
+        meshes = [S.BoxMesh(E, N, Pg, r) for r in range(world)]
+        F = S.OracleFdd(E, N, red, Pg, overlaps[0], overlaps[1])
     W = S.OracleWorld(meshes, N)
-    F = S.OracleFdd(E, N, red, Pg)
     us = [np.sin(3 * mm.x + 1) * np.cos(2 * mm.y) + mm.z * mm.x for mm in meshes]
     # every oracle result up front, on this thread (the oracle's world is one mutable object)
     o_f = W.stiffness(W.dssum(us, True, True))
@@ -44,14 +94,27 @@ def run(world, E, N, red, amg=True):
                 z[k][:] = out[k]
 
         for method in (("fcg", "gmres") if mode == 0 else ("fcg",)):
-            solves[(mode, method)] = W.solve(o_f, method, precond=pre)
+            solves[(mode, method)] = W.solve(o_f, method, precond=pre, **capped)
     regions = [F.region(r) for r in range(world)]
-    levels = [F.composite_levels(r) for r in range(world)]
+    comp_levels = [F.composite_levels(r) for r in range(world)]
+    if no_superdomain is not None:  # the mesh still produces the ranks without a superdomain that the case is about
+        assert [r for r in range(world) if F.info[r]["sup_dofs"] == 0] == sorted(no_superdomain), [F.info[r]["sup_dofs"] for r in range(world)]
+    u_bar = 1e-6 if kershaw else 1e-8
+    margins = {"history": 0.0, "solution": 0.0}
+    # what was established about a level list of this mesh (stiffness_choice_rules): a box has zero off-diagonal factor arrays
+    # and one factor block for all its elements, the Kershaw map neither; the lean verdicts are the rule on the uploaded table
+    lean = {f32: R.lean_table_ok(S.gll(7)[2], f32) for f32 in (False, True)}
+    flags = {name: product or name == "mfma_stiffness" for name in R.FLAGS}  # "mfma_stiffness" needs no entry of its own
+    info_keys = (("zero_factor_info", "diag", "skip_zero_factors", "sub_lists_diag"), ("mfma_zero_factor_info", "mfma_diag", "mfma_skip_zero_factors", "sub_lists_mfma_diag"),
+                 ("line_stiffness_info", "lines", "line_stiffness", "sub_lists_lines"), ("shared_factor_info", "shared", "shared_factor_blocks", "sub_lists_shared"),
+                 ("lean_line_info", "lean", "lean_line_stiffness", "sub_lists_lean"))
 
     def body(rank, size):
         lib.host().call("fddh_comm_selftest", 1000)
-        p = H.Problem.box(E, Pg, N, red, True)
+        p = H.Problem.kershaw(E, Pg, N, red, 0.3, True, overlaps[0], overlaps[1]) if kershaw else H.Problem.box(E, Pg, N, red, True, overlaps[0], overlaps[1])
         p.set_flag("sub_use_preconditioner", 0)
+        if capped:
+            p.set_options(**capped)
         for lvl in range(p.info["num_levels"]):
             p.set_D_hat(lvl, S.gll(p.level_degree(lvl))[2])
         _, f = p.make_rhs_from(us[rank])
@@ -61,15 +124,64 @@ def run(world, E, N, red, amg=True):
         for a, b in (("num_elems", "sub_elems"), ("num_ext_elems", "sub_ext_elems"), ("num_points", "points"), ("sub_dofs", "sub_dofs"), ("sub_ext_dofs", "sub_ext_dofs"), ("interface_dofs", "interface_dofs"),
                      ("sup_dofs", "sup_dofs"), ("sup_ext_dofs", "sup_ext_dofs"), ("unique_dofs", "unique_dofs"), ("coarse_dofs", "coarse_dofs"), ("num_values", "num_values")):
             assert si[a] == oi[b], (a, si[a], oi[b])
+        if no_superdomain is not None:
+            assert (si["sup_dofs"] == 0) == (rank in no_superdomain), (rank, si["sup_dofs"])
         ids, lv = p.sub_region()
-        assert np.array_equal(ids, regions[rank][0]) and np.array_equal(lv, regions[rank][1]) and len(set(lv.tolist())) > 1
-        assert p.sub_composite_levels() == levels[rank]
+        region_levels = sorted(set(lv.tolist()))
+        assert np.array_equal(ids, regions[rank][0]) and np.array_equal(lv, regions[rank][1])
+        if levels is None:
+            assert len(region_levels) > 1
+        else:  # every polynomial level of the chain N, N - r, ..., 1 has elements in this rank's region
+            assert len(region_levels) == levels == len(degrees), (region_levels, levels, degrees)
+        assert p.sub_composite_levels() == comp_levels[rank]
+        if composite_levels is not None:
+            assert len(comp_levels[rank]) == composite_levels, comp_levels[rank]
+
+        # one kernel choice per level list: the info entries count the region's lists, and of each family as many as the
+        # rules give for the lists' states (the gather form in the precision in use), summed
+        lists = [(3, degrees[l], False, not kershaw, not kershaw, degrees[l] == 7 and lean[False], degrees[l] == 7 and lean[True]) for l in region_levels]
+        assert all(R.reachable(*lst) for lst in lists)
+
+        def check_choice(f32):
+            want = R.composite_info(lists, flags, f32)
+            for entry, kind, flag, key in info_keys:
+                answer = getattr(p, entry)()
+                assert (answer["enabled"], answer[key], answer["sub_lists"]) == (flags[flag], want[kind], len(lists)), (f32, flag, answer, want)
+            if N == 7:  # the host layer's verdict on the uploaded degree-7 table is the rule's
+                assert p.lean_line_info()["fine_domain_table_ok"] == lean[False]
+            if kershaw:  # six arrays on every list whatever the flags say
+                assert want["diag"] == 0 and p.zero_factor_info()["sub_lists_diag"] == 0
+            elif product:
+                assert want["diag"] == len(lists), want
+                if N == 7:  # one operator application runs a line instance and slab-form instances together
+                    assert 1 <= p.line_stiffness_info()["sub_lists_lines"] < len(lists)
+                    assert want["lines"] == want["shared"] == want["lean"] == 1, want
+
+        check_choice(False)
+        answer = p.affine_info()
+        assert (answer["sub_lists_affine"], answer["sub_lists"]) == (0, len(lists)), answer
+
         for op in ("stiffness", "dssum"):
             got = p.sub_op(op, ref["v"][rank])
             assert np.abs(got - ref[op][rank]).max() <= 1e-12 * np.abs(ref[op][rank]).max(), op
         assert abs(p.sub_residual_norm(ref["v"][rank]) - ref["norm"][rank]) <= 1e-12 * ref["norm"][rank]
         got = p.sub_op("tree", us[rank])  # ring pull by Comm::exchange + coarse all-gather on the ranks' device buffers
         assert np.abs(got - ref["tree"][rank]).max() <= 1e-12 * np.abs(ref["tree"][rank]).max()
+
+        # the flag "assemble_in_stiffness" leaves every bit alone: on a composite it does not engage, and says why
+        def with_assembly_flag(value, why):
+            if product:
+                p.set_flag("assemble_in_stiffness", value)
+            ai = p.assembly_info()
+            assert (ai["enabled"], ai["in_effect"], ai["why_not"]) == (bool(value), False, why), ai
+            return (p.sub_op("stiffness", ref["v"][rank]),) + p.precond_apply(us[rank], "gmres")
+
+        off = with_assembly_flag(0, "the flag is off")
+        if product:  # the stand-in has no entry to turn the flag on with
+            on = with_assembly_flag(1, "a composite region")
+            assert all(np.array_equal(a, b) for a, b in zip(on, off))
+
+        mine = {}
         for mode in (0, 2):
             p.set_flag("sub_use_preconditioner", mode)
             for method in ("gmres", "fcg"):
@@ -80,37 +192,54 @@ def run(world, E, N, red, amg=True):
             for method in (("fcg", "gmres") if mode == 0 else ("fcg",)):
                 u, its, hist = p.solve(f, method)
                 ou, oits, ohist = solves[(mode, method)]
-                assert its == oits, (mode, method, its, oits)
-                assert np.abs(hist - ohist).max() <= 1e-8 * ohist[0]
-                assert np.abs(u - ou[rank]).max() <= 1e-8 * np.abs(ou[rank]).max()
+                assert its == oits and (not capped or its == outer_cap), (mode, method, its, oits)
+                d_hist, d_u = np.abs(hist - ohist).max() / ohist[0], np.abs(u - ou[rank]).max() / np.abs(ou[rank]).max()
+                margins["history"], margins["solution"] = max(margins["history"], d_hist), max(margins["solution"], d_u)
+                assert d_hist <= 1e-8, (mode, method, d_hist)
+                assert d_u <= u_bar, (mode, method, d_u)
+                mine[(mode, method)] = (u, its, hist)
         p.set_flag("sub_use_preconditioner", 0)
-        its64 = solves[(0, "fcg")][1]
+        u64, its64, h64 = mine[(0, "fcg")]
+
+        def ends_well(its, hist):
+            """a float solve: converged to 1e-7, or, capped, all its steps taken and the residual below where it began"""
+            return (its == outer_cap and np.isfinite(hist).all() and hist[-1] < hist[0]) if capped else hist[-1] <= 1e-7 * hist[0] * 1.0001
+
         # the whole inner solve in single precision (PTYPE = Float = float) on the composite
         p.set_flag("preconditioner_precision", 32)
+        check_choice(True)
         u32, its32, h32 = p.solve(f, "fcg")
-        assert abs(its32 - its64) <= 1 and h32[-1] <= 1e-7 * h32[0] * 1.0001
+        assert abs(its32 - its64) <= 1 and ends_well(its32, h32), (its32, its64, h32[-1] / h32[0])
         p.set_flag("preconditioner_precision", 64)
-        # the affine-elements option on the composite: every level list of the region (own elements, rings at their reduced
-        # degrees, the degree-1 far field) is checked on its own and runs without streaming its factor arrays
         p.set_flag("affine_geometry", 1)
         info = p.affine_info()
-        assert info["fine_domain"] and info["sub_lists_affine"] == info["sub_lists"] >= 2 and info["max_deviation"] <= 64 * np.finfo(float).eps, info
         ua, itsa, ha = p.solve(f, "fcg")
-        assert itsa == its64 and np.abs(ua - solves[(0, "fcg")][0][rank]).max() <= 1e-8 * np.abs(ua).max()
+        if kershaw:
+            # the option leaves a mesh whose factor arrays are not of the affine form alone: no list switches over, every bit stays
+            assert not info["fine_domain"] and (info["sub_lists_affine"], info["sub_lists"]) == (0, len(lists)), info
+            assert itsa == its64 and np.array_equal(ua, u64) and np.array_equal(ha, h64)
+        else:
+            # the affine-elements option on the composite: every level list of the region (own elements, rings at their reduced
+            # degrees, the degree-1 far field) is checked on its own and runs without streaming its factor arrays
+            assert info["fine_domain"] and info["sub_lists_affine"] == info["sub_lists"] == len(lists) >= 2 and info["max_deviation"] <= 64 * np.finfo(float).eps, info
+            assert itsa == its64 and np.abs(ua - solves[(0, "fcg")][0][rank]).max() <= 1e-8 * np.abs(ua).max()
         p.set_flag("affine_geometry", 0)
         its_amg = None
         if amg:
             # the reference's default: the low-order V-cycle inside every inner step, hierarchy built by the host layer
             p.set_flag("sub_use_preconditioner", 1)
             assert p.amg_build(coarsest_size=40) >= 2
-            u, its_amg, hist = p.solve(f, "fcg")
-            assert hist[-1] <= 1e-7 * hist[0] and its_amg < its64
-            assert np.abs(u - solves[(0, "fcg")][0][rank]).max() <= 1e-5 * np.abs(u).max()
+            u, its_amg, hist = p.solve(f, amg_method)
+            if capped:  # after the same number of steps the residual with the V-cycle lies below the one without it
+                assert its_amg == outer_cap and hist[-1] < mine[(0, amg_method)][2][-1], (hist[-1], mine[(0, amg_method)][2][-1])
+            else:
+                assert hist[-1] <= 1e-7 * hist[0] and its_amg < mine[(0, amg_method)][1]
+                assert np.abs(u - solves[(0, amg_method)][0][rank]).max() <= 1e-5 * np.abs(u).max()
             # and the whole preconditioner in float: every rank builds its f32 plans and captures its f32 V-cycle graph
             # while its peers are somewhere else in theirs (setup copies must not touch the legacy default stream)
             p.set_flag("preconditioner_precision", 32)
-            u32a, its32a, h32a = p.solve(f, "fcg")
-            assert abs(its32a - its_amg) <= 1 and h32a[-1] <= 1e-7 * h32a[0] * 1.0001
+            u32a, its32a, h32a = p.solve(f, amg_method)
+            assert abs(its32a - its_amg) <= 1 and ends_well(its32a, h32a), (its32a, its_amg, h32a[-1] / h32a[0])
             p.set_flag("preconditioner_precision", 64)
         ct = p.comm_time(2)
         assert ct["ring_exchange"]["bytes"] > 0 and ct["coarse_allgather"]["bytes"] > 0
@@ -121,17 +250,23 @@ def run(world, E, N, red, amg=True):
     W.close()
     F.close()
     assert len(set(out)) == 1, out  # every rank saw the same iteration counts
+    print("largest differences to the oracle over the outer solves: history %.2e r0, solution %.2e max|u|" % (margins["history"], margins["solution"]))
     return out[0]
 
 
 if __name__ == "__main__":
     args = sys.argv[1:]
+    product = True
     if args and args[0] == "--cpu-shim":
         from polynomial_reduction_with_full_domain_decomposition_preconditioner_amd import lib
 
         # test-only: serve include/fdd_host.h from the CPU build of the host layer (tests/cpu_shim)
         lib._host = lib._Lib(os.path.join(HERE, "cpu_shim", "_build", "libfdd_host_cpu.so"), os.path.join(lib.INCLUDE_DIR, "fdd_host.h"), "fddh_last_error")
-        args = args[1:]
-    world = int(args[0])
-    E = tuple(int(x) for x in args[1].split(","))
-    print("local world ok:", run(world, E, int(args[2]), int(args[3])))
+        args, product = args[1:], False
+    ints = lambda text: tuple(int(x) for x in text.split(","))
+    read = {"overlaps": ints, "kershaw": lambda t: bool(int(t)), "outer_cap": int, "levels": int, "composite_levels": int, "amg_method": str, "no_superdomain": ints}
+    options = {}
+    for arg in args[4:]:
+        name, _, text = arg.partition("=")
+        options[name] = read[name](text)
+    print("local world ok:", run(int(args[0]), ints(args[1]), int(args[2]), int(args[3]), product=product, **options))

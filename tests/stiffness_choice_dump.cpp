@@ -12,7 +12,7 @@ int main()
 {
     using namespace fdd;
     const char *family_name[] = {"two_launch", "fused_2d", "fused", "diag", "lines", "mfma", "mfma_diag", "affine", "mfma_affine"};
-    const int degrees[] = {1, 7, 8, 11, 15, 16};
+    const int degrees[] = {1, 2, 3, 5, 7, 8, 11, 15, 16};
     for (int dim = 2; dim <= 3; dim++)
         for (int degree : degrees)
             for (int state = 0; state < 32; state++)

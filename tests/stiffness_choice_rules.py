@@ -7,6 +7,7 @@ test_gpu_stiffness_choice.py holds a real solve's profile labels and info answer
 A list: dim, degree, and what was established about its arrays -- affine (in use), offdiag_zero, shared_blocks, and the lean
 verdicts on its double and float derivative tables.  Flags: a dict name -> bool."""
 import itertools
+import struct
 
 FLAGS = ("mfma_stiffness", "skip_zero_factors", "line_stiffness", "mfma_skip_zero_factors", "shared_factor_blocks", "lean_line_stiffness")
 FAMILIES = ("two_launch", "fused_2d", "fused", "diag", "lines", "mfma", "mfma_diag", "affine", "mfma_affine")
@@ -87,9 +88,35 @@ def info(lst, flags, f32):
     return {"diag": family in ("diag", "lines"), "mfma_diag": family == "mfma_diag", "lines": family == "lines", "shared": family == "lines" and shared, "lean": family == "lines" and lean}
 
 
+def composite_info(lists, flags, f32):
+    """what the entries say of a Subdomain with several level lists (a composite region: the rank's own elements at degree N,
+    rings at the reduced degrees, the degree-1 far field): every list is chosen for on its own, from its own degree and
+    arrays, and an entry counts the lists of its kind -- a degree-7 line list stands next to slab lists at 5, 3 and 1"""
+    each = [info(lst, flags, f32) for lst in lists]
+    return {kind: sum(one[kind] for one in each) for kind in ("diag", "mfma_diag", "lines", "shared", "lean")}
+
+
+def lean_table_ok(D, f32=False):
+    """the lean line instance's conditions on an 8 x 8 derivative table (the flag's description), bit for bit: the interior
+    diagonal is +-0.0 and everywhere else entry 63 - m has the bits of the negation of entry m; f32: on the table cast to
+    float, which is the one the float lists read"""
+    code, sign = ("<f", 1 << 31) if f32 else ("<d", 1 << 63)
+    values = [float(x) for row in D for x in (row if hasattr(row, "__len__") else [row])]
+    if len(values) != 64:
+        return False
+    w = [int.from_bytes(struct.pack(code, x), "little") for x in values]
+    if any(w[9 * i] & ~sign for i in range(1, 7)):
+        return False
+    return all(w[63 - m] == w[m] ^ sign for m in range(32) if m not in (9, 18, 27))
+
+
+# 2, 3 and 5: the intermediate degrees of the composites tests/local_world_checks.py runs (7, 5, 3, 1; 5, 3, 1; 3, 2, 1)
+DEGREES = (1, 2, 3, 5, 7, 8, 11, 15, 16)
+
+
 def combinations():
     """every reachable (list, flags, f32, form, in_place)"""
-    for dim, degree in itertools.product((2, 3), (1, 7, 8, 11, 15, 16)):
+    for dim, degree in itertools.product((2, 3), DEGREES):
         for state in itertools.product((False, True), repeat=5):
             lst = (dim, degree) + state
             if not reachable(*lst):

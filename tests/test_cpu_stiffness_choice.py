@@ -49,6 +49,32 @@ def test_every_row_is_the_restatement(rows):
         assert info == R.info(lst, flags, f32), (what, info)
 
 
+def test_the_lean_table_rule():
+    """lean_table_ok, which local_world_checks.py states a composite's degree-7 list with: the GLL table passes in both
+    precisions; a last-bit change breaks the double verdict and not the float one (the cast drops it); the interior diagonal
+    may be -0.0 and nothing else; a table of another size fails"""
+    import numpy as np
+
+    D = np.array(S.gll(7)[2], dtype=np.float64).reshape(64)
+    assert R.lean_table_ok(D) and R.lean_table_ok(D, True) and R.lean_table_ok(D.reshape(8, 8))
+    bad = D.copy()
+    bad[0] = np.nextafter(bad[0], 0.0)
+    assert not R.lean_table_ok(bad) and R.lean_table_ok(bad, True)
+    bad[0] = D[0] * (1 + 2.0**-20)
+    assert not R.lean_table_ok(bad, True)
+    signed = D.copy()
+    signed[9] = -0.0
+    assert R.lean_table_ok(signed) and R.lean_table_ok(signed, True)
+    signed[9] = 5e-324
+    assert not R.lean_table_ok(signed) and R.lean_table_ok(signed, True)  # the cast to float rounds it to zero
+    assert not R.lean_table_ok(np.array(S.gll(3)[2]))
+    lists = [(3, d, False, True, True, d == 7, d == 7) for d in (7, 5, 3, 1)]
+    on = {name: True for name in R.FLAGS}
+    assert R.composite_info(lists, on, False) == R.composite_info(lists, on, True) == {"diag": 4, "mfma_diag": 0, "lines": 1, "shared": 1, "lean": 1}
+    assert R.composite_info(lists, dict(on, line_stiffness=False), False) == {"diag": 4, "mfma_diag": 0, "lines": 0, "shared": 0, "lean": 0}
+    assert sum(R.composite_info([(3, d, False, False, False, d == 7, d == 7) for d in (7, 5, 3, 1)], on, False).values()) == 0  # Kershaw
+
+
 def test_every_family_and_every_label_occurs(rows):
     for form in ("local", "gather"):
         families = {r[5][0] for r in rows if r[3] == form}
