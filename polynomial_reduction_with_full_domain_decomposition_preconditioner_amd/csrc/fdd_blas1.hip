@@ -2,34 +2,37 @@
 // updates of domain.okl / subdomain.okl, the precision-cast copies and the
 // element-wise AMG smoother kernels of AMG/kernels.cu.
 //
-// One template drives them all: every lane moves 16 B per access (double2),
-// the grid is capped at 2048 workgroups of 256 lanes and strides over the
-// vector, so a 134 MB vector is 16 passes of fully coalesced 1 KiB
-// wave-accesses.  Pointers that are not 16-B aligned (occa::memory::slice
-// offsets, math.okl's `offset`) take the scalar 8-B path.
+// One template drives them all: every op states its loads, arithmetic and stores
+// once, in at(), over a lane accessor (fdd_stream.h).  Where every pointer the op
+// names allows it, a lane moves a pair (16 B of doubles) per access; the grid is
+// capped and strides over the vector, so a 134 MB vector is fully coalesced 1 KiB
+// wave-accesses.  Pointers that are not aligned for pairs (occa::memory::slice
+// offsets, math.okl's `offset`) and the odd last element take one element per lane.
 //
 // Compiled with -ffp-contract=off: a*x + b*y is two multiplies and one add in
 // source order, bit-identical to the OCCA-Serial arithmetic.
-#include "fdd_common.h"
+#include "fdd_stream.h"
 
 namespace
 {
 
 constexpr int kBlock = 256;
+using Single = fdd_lanes<1>;
+using Pair = fdd_lanes<2>;
 
 template <typename Op>
 __global__ __launch_bounds__(kBlock) void ew_vec2_kernel(Op op, long long n2, long long n)
 {
     const long long stride = (long long)gridDim.x * kBlock;
-    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n2; i += stride) op.vec2(i);
-    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) op.one(n - 1);
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n2; i += stride) op.at(Pair{}, i);
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) op.at(Single{}, n - 1);
 }
 
 template <typename Op>
 __global__ __launch_bounds__(kBlock) void ew_scalar_kernel(Op op, long long n)
 {
     const long long stride = (long long)gridDim.x * kBlock;
-    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) op.one(i);
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) op.at(Single{}, i);
 }
 
 // Element-wise kernels have no per-workgroup epilogue: at C2 sizes a grid of one pair of doubles per lane (21 k workgroups)
@@ -38,10 +41,10 @@ __global__ __launch_bounds__(kBlock) void ew_scalar_kernel(Op op, long long n)
 constexpr int kEwMaxBlocks = 32768;
 
 template <typename Op>
-int launch_ew(const Op &op, long long n, bool aligned, void *stream)
+int launch_ew(const Op &op, long long n, void *stream)
 {
     if (n <= 0) return 0;
-    if (aligned && n >= 2)
+    if (fdd_lanes_fit<Pair>(op) && n >= 2)
     {
         long long n2 = n / 2;
         int grid = fdd_stream_grid(n2, kBlock, kEwMaxBlocks);
@@ -56,34 +59,27 @@ int launch_ew(const Op &op, long long n, bool aligned, void *stream)
     return 0;
 }
 
-// 16-byte streaming loads are non-temporal: these kernels read every byte once per launch
-// and the operands are far larger than the caches (measured +10-15 % on the multi-stream ops)
-typedef double fdd_v2f64 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ double2 ld2(const double *p, long long i)
-{
-    const fdd_v2f64 v = __builtin_nontemporal_load(reinterpret_cast<const fdd_v2f64 *>(p) + i);
-    return make_double2(v.x, v.y);
-}
-__device__ __forceinline__ void st2(double *p, long long i, double2 v) { reinterpret_cast<double2 *>(p)[i] = v; } // default policy: the next kernel usually reads it
+// Every op: at(a, i) is the operation on element i of accessor a (all loads before the first store: the vectors may be
+// one another), pointers(f) names the vectors it touches.
 
 // ---------------------------------------------------------------- math.okl
 struct SetOp // math.okl:5-11
 {
     double *u;
     double alpha;
-    __device__ void vec2(long long i) const { st2(u, i, make_double2(alpha, alpha)); }
-    __device__ void one(long long i) const { u[i] = alpha; }
+    template <typename A>
+    __device__ void at(A a, long long i) const { a.st(u, i, a.all(alpha)); }
+    template <typename F>
+    void pointers(F f) const { f(u); }
 };
 
 struct InvertOp // math.okl:13-19
 {
     double *u;
-    __device__ void vec2(long long i) const
-    {
-        double2 a = ld2(u, i);
-        st2(u, i, make_double2(1.0 / a.x, 1.0 / a.y));
-    }
-    __device__ void one(long long i) const { u[i] = 1.0 / u[i]; }
+    template <typename A>
+    __device__ void at(A a, long long i) const { a.st(u, i, 1.0 / a.ld(u, i)); }
+    template <typename F>
+    void pointers(F f) const { f(u); }
 };
 
 struct AxpbyOp // math.okl:21-27
@@ -92,12 +88,10 @@ struct AxpbyOp // math.okl:21-27
     const double *u;
     const double *v;
     double alpha, beta;
-    __device__ void vec2(long long i) const
-    {
-        double2 a = ld2(u, i), b = ld2(v, i);
-        st2(uv, i, make_double2(alpha * a.x + beta * b.x, alpha * a.y + beta * b.y));
-    }
-    __device__ void one(long long i) const { uv[i] = alpha * u[i] + beta * v[i]; }
+    template <typename A>
+    __device__ void at(A a, long long i) const { a.st(uv, i, alpha * a.ld(u, i) + beta * a.ld(v, i)); }
+    template <typename F>
+    void pointers(F f) const { f(uv), f(u), f(v); }
 };
 
 // x = (1 / sqrt(*s2)) * u with the squared norm still on the device
@@ -107,13 +101,10 @@ struct ScaleRsqrtDevOp
     double *au;
     const double *u;
     const double *s2;
-    __device__ void vec2(long long i) const
-    {
-        const double alpha = 1.0 / sqrt(*s2);
-        double2 a = ld2(u, i);
-        st2(au, i, make_double2(alpha * a.x, alpha * a.y));
-    }
-    __device__ void one(long long i) const { au[i] = (1.0 / sqrt(*s2)) * u[i]; }
+    template <typename A>
+    __device__ void at(A a, long long i) const { a.st(au, i, (1.0 / sqrt(*s2)) * a.ld(u, i)); }
+    template <typename F>
+    void pointers(F f) const { f(au), f(u); }
 };
 
 // au = (*scale) * u: math.okl:29-35 with the factor read from device memory
@@ -122,13 +113,10 @@ struct ScaleDevOp
     double *au;
     const double *u;
     const double *scale;
-    __device__ void vec2(long long i) const
-    {
-        const double alpha = *scale;
-        double2 a = ld2(u, i);
-        st2(au, i, make_double2(alpha * a.x, alpha * a.y));
-    }
-    __device__ void one(long long i) const { au[i] = (*scale) * u[i]; }
+    template <typename A>
+    __device__ void at(A a, long long i) const { a.st(au, i, (*scale) * a.ld(u, i)); }
+    template <typename F>
+    void pointers(F f) const { f(au), f(u); }
 };
 
 // z = d .* ((*scale) * u): the point-Jacobi preconditioner of the inner solve applied to a Krylov vector kept
@@ -139,13 +127,14 @@ struct DiagScaleDevOp
     const double *d;
     const double *u;
     const double *scale; // may be null: z = d .* u
-    __device__ void vec2(long long i) const
+    template <typename A>
+    __device__ void at(A a, long long i) const
     {
-        const double alpha = scale ? *scale : 1.0;
-        const double2 a = ld2(u, i), dd = ld2(d, i);
-        st2(z, i, scale ? make_double2(dd.x * (alpha * a.x), dd.y * (alpha * a.y)) : make_double2(dd.x * a.x, dd.y * a.y));
+        const auto uu = a.ld(u, i), dd = a.ld(d, i);
+        a.st(z, i, scale ? dd * ((*scale) * uu) : dd * uu);
     }
-    __device__ void one(long long i) const { z[i] = scale ? d[i] * ((*scale) * u[i]) : d[i] * u[i]; }
+    template <typename F>
+    void pointers(F f) const { f(z), f(u), f(d); }
 };
 
 // out = x + (*num / *den) * y: the p = z + beta*p half of residual_and_search_update (domain.okl:218-233)
@@ -154,13 +143,10 @@ struct XpbyRatioDevOp
 {
     double *out;
     const double *x, *y, *num, *den;
-    __device__ void vec2(long long i) const
-    {
-        const double beta = *num / *den;
-        const double2 a = ld2(x, i), b = ld2(y, i);
-        st2(out, i, make_double2(a.x + beta * b.x, a.y + beta * b.y));
-    }
-    __device__ void one(long long i) const { out[i] = x[i] + (*num / *den) * y[i]; }
+    template <typename A>
+    __device__ void at(A a, long long i) const { a.st(out, i, a.ld(x, i) + (*num / *den) * a.ld(y, i)); }
+    template <typename F>
+    void pointers(F f) const { f(out), f(x), f(y); }
 };
 
 // out = x - (*num / *den) * y: the r+ = r - alpha*q half of solution_and_residual_update (domain.okl:186-193) on
@@ -169,58 +155,27 @@ struct XmayRatioDevOp
 {
     double *out;
     const double *x, *y, *num, *den;
-    __device__ void vec2(long long i) const
-    {
-        const double alpha = *num / *den;
-        const double2 a = ld2(x, i), b = ld2(y, i);
-        st2(out, i, make_double2(a.x - alpha * b.x, a.y - alpha * b.y));
-    }
-    __device__ void one(long long i) const { out[i] = x[i] - (*num / *den) * y[i]; }
+    template <typename A>
+    __device__ void at(A a, long long i) const { a.st(out, i, a.ld(x, i) - (*num / *den) * a.ld(y, i)); }
+    template <typename F>
+    void pointers(F f) const { f(out), f(x), f(y); }
 };
 
-// One step of the Chebyshev-Jacobi inner solve (host/subdomain.hpp, chebyshev_dofs) as one pass.  The statements are those
-// of the entries the step can also be composed from, in their order -- vector_vector_addition (AxpbyOp) and
-// vector_diagonal_scaling_dev (DiagScaleDevOp) above -- so the bits are the same either way:
-//   first : t = dinv .* r_in;  d = c_r*t + 0*t;                                x = d
-//   later : r = 1*r_in + (-1)*q;  t = dinv .* r;  d = c_d*d + c_r*t;            x = 1*x + 1*d
-// r_in is the right-hand side at the second step (never written) and r_out itself afterwards; the last step stores x only.
-// f64 bytes per dof: first 32, middle 64, last 48.
-struct ChebyStepOp
+struct ChebyStepOp // fdd_cheby_step_at (fdd_stream.h)
 {
     double *x, *d, *r_out;
     const double *r_in, *q, *dinv;
     double c_d, c_r;
     int first, last;
-    __device__ double direction(double rv, double dv, double di) const
+    template <typename A>
+    __device__ void at(A a, long long i) const { fdd_cheby_step_at(a, i, x, d, r_out, r_in, q, dinv, c_d, c_r, first, last); }
+    template <typename F>
+    void pointers(F f) const // the vectors this step touches: a pointer it leaves alone may be anything
     {
-        const double t = di * rv;
-        return first ? c_r * t + 0.0 * t : c_d * dv + c_r * t;
-    }
-    __device__ void vec2(long long i) const
-    {
-        const double2 di = ld2(dinv, i);
-        double2 r = ld2(r_in, i), dv = make_double2(0.0, 0.0), xv = dv;
-        if (!first)
-        {
-            const double2 qv = ld2(q, i);
-            dv = ld2(d, i);
-            xv = ld2(x, i);
-            r = make_double2(1.0 * r.x + (-1.0) * qv.x, 1.0 * r.y + (-1.0) * qv.y);
-        }
-        dv = make_double2(direction(r.x, dv.x, di.x), direction(r.y, dv.y, di.y));
-        st2(x, i, first ? dv : make_double2(1.0 * xv.x + 1.0 * dv.x, 1.0 * xv.y + 1.0 * dv.y));
-        if (last) return;
-        st2(d, i, dv);
-        if (!first) st2(r_out, i, r);
-    }
-    __device__ void one(long long i) const
-    {
-        const double r = first ? r_in[i] : 1.0 * r_in[i] + (-1.0) * q[i];
-        const double dn = direction(r, first ? 0.0 : d[i], dinv[i]);
-        x[i] = first ? dn : 1.0 * x[i] + 1.0 * dn;
-        if (last) return;
-        d[i] = dn;
-        if (!first) r_out[i] = r;
+        f(x), f(r_in), f(dinv);
+        if (!last) f(d);
+        if (!first) f(q), f(d);
+        if (!first && !last) f(r_out);
     }
 };
 
@@ -239,12 +194,10 @@ struct ScaleOp // math.okl:29-35
     double *au;
     const double *u;
     double alpha;
-    __device__ void vec2(long long i) const
-    {
-        double2 a = ld2(u, i);
-        st2(au, i, make_double2(alpha * a.x, alpha * a.y));
-    }
-    __device__ void one(long long i) const { au[i] = alpha * u[i]; }
+    template <typename A>
+    __device__ void at(A a, long long i) const { a.st(au, i, alpha * a.ld(u, i)); }
+    template <typename F>
+    void pointers(F f) const { f(au), f(u); }
 };
 
 // ------------------------------------------------- domain.okl / subdomain.okl
@@ -253,17 +206,15 @@ struct InitOp // domain.okl:100-107, subdomain.okl:211-218
     double *u_k;
     double *r_k;
     const double *f;
-    __device__ void vec2(long long i) const
+    template <typename A>
+    __device__ void at(A a, long long i) const
     {
-        double2 a = ld2(f, i);
-        st2(u_k, i, make_double2(0.0, 0.0));
-        st2(r_k, i, a);
+        const auto fv = a.ld(f, i);
+        a.st(u_k, i, a.all(0.0));
+        a.st(r_k, i, fv);
     }
-    __device__ void one(long long i) const
-    {
-        u_k[i] = 0.0;
-        r_k[i] = f[i];
-    }
+    template <typename F>
+    void pointers(F fn) const { fn(u_k), fn(r_k), fn(f); }
 };
 
 // alpha either by value or as num/den read from device memory
@@ -288,21 +239,16 @@ struct UpdateUROp // domain.okl:186-193, subdomain.okl:220-227
     const double *p_k;
     const double *q_k;
     S alpha;
-    __device__ void vec2(long long i) const
+    template <typename A>
+    __device__ void at(A a, long long i) const
     {
-        const double a = alpha.get();
-        double2 u = ld2(u_k, i), r = ld2(r_k, i), p = ld2(p_k, i), q = ld2(q_k, i);
-        u.x += a * p.x;
-        u.y += a * p.y;
-        st2(u_k, i, u);
-        st2(r_kp1, i, make_double2(r.x - a * q.x, r.y - a * q.y));
+        const double al = alpha.get();
+        const auto u = a.ld(u_k, i), r = a.ld(r_k, i), p = a.ld(p_k, i), q = a.ld(q_k, i);
+        a.st(u_k, i, u + al * p);
+        a.st(r_kp1, i, r - al * q);
     }
-    __device__ void one(long long i) const
-    {
-        const double a = alpha.get();
-        u_k[i] += a * p_k[i];
-        r_kp1[i] = r_k[i] - a * q_k[i];
-    }
+    template <typename F>
+    void pointers(F f) const { f(u_k), f(r_kp1), f(r_k), f(p_k), f(q_k); }
 };
 
 template <typename S>
@@ -313,51 +259,36 @@ struct UpdatePROp // domain.okl:226-233, subdomain.okl:259-266
     const double *z_k;
     const double *r_kp1;
     S beta;
-    __device__ void vec2(long long i) const
+    template <typename A>
+    __device__ void at(A a, long long i) const
     {
         const double b = beta.get();
-        double2 z = ld2(z_k, i), p = ld2(p_k, i), r = ld2(r_kp1, i);
-        st2(p_k, i, make_double2(z.x + b * p.x, z.y + b * p.y));
-        st2(r_k, i, r);
+        const auto z = a.ld(z_k, i), p = a.ld(p_k, i), r = a.ld(r_kp1, i);
+        a.st(p_k, i, z + b * p);
+        a.st(r_k, i, r);
     }
-    __device__ void one(long long i) const
-    {
-        const double b = beta.get();
-        p_k[i] = z_k[i] + b * p_k[i];
-        r_k[i] = r_kp1[i];
-    }
+    template <typename F>
+    void pointers(F f) const { f(p_k), f(r_k), f(z_k), f(r_kp1); }
 };
 
-struct CopyOp // subdomain.okl:268-282 with DType = EType = double
+template <typename TO, typename FROM>
+struct CopyAs // subdomain.okl:268-282: DType = EType = double, and the two casts of DType = float
 {
-    double *u;
-    const double *v;
-    __device__ void vec2(long long i) const { st2(u, i, ld2(v, i)); }
-    __device__ void one(long long i) const { u[i] = v[i]; }
+    TO *u;
+    const FROM *v;
+    template <typename A>
+    __device__ void at(A a, long long i) const { a.st(u, i, A::template to<TO>(a.ld(v, i))); }
+    template <typename F>
+    void pointers(F f) const { f(u), f(v); }
 };
-
-struct CopyF32F64Op // subdomain.okl:268-274, DType = float
+struct CopyOp : CopyAs<double, double> // subdomain.okl:268-282 with DType = EType = double
 {
-    float *u;
-    const double *v;
-    __device__ void vec2(long long i) const
-    {
-        double2 a = ld2(v, i);
-        reinterpret_cast<float2 *>(u)[i] = make_float2((float)a.x, (float)a.y);
-    }
-    __device__ void one(long long i) const { u[i] = (float)v[i]; }
 };
-
-struct CopyF64F32Op // subdomain.okl:276-282, DType = float
+struct CopyF32F64Op : CopyAs<float, double> // subdomain.okl:268-274, DType = float
 {
-    double *u;
-    const float *v;
-    __device__ void vec2(long long i) const
-    {
-        float2 a = reinterpret_cast<const float2 *>(v)[i];
-        st2(u, i, make_double2((double)a.x, (double)a.y));
-    }
-    __device__ void one(long long i) const { u[i] = (double)v[i]; }
+};
+struct CopyF64F32Op : CopyAs<double, float> // subdomain.okl:276-282, DType = float
+{
 };
 
 // q <- (...((1.0*q + c_0 v_0) + c_1 v_1)...) + c_{M-1} v_{M-1}: the M successive
@@ -371,24 +302,19 @@ struct MultiAxpyOp
     double *q;
     const double *v[M];
     double c[M];
-    __device__ void vec2(long long i) const
+    template <typename A>
+    __device__ void at(A a, long long i) const
     {
-        double2 x = ld2(q, i);
+        auto x = a.ld(q, i);
 #pragma unroll
-        for (int k = 0; k < M; k++)
-        {
-            const double2 b = ld2(v[k], i);
-            x.x = 1.0 * x.x + c[k] * b.x;
-            x.y = 1.0 * x.y + c[k] * b.y;
-        }
-        st2(q, i, x);
+        for (int k = 0; k < M; k++) x = 1.0 * x + c[k] * a.ld(v[k], i);
+        a.st(q, i, x);
     }
-    __device__ void one(long long i) const
+    template <typename F>
+    void pointers(F f) const
     {
-        double x = q[i];
-#pragma unroll
-        for (int k = 0; k < M; k++) x = 1.0 * x + c[k] * v[k][i];
-        q[i] = x;
+        f(q);
+        for (int k = 0; k < M; k++) f(v[k]);
     }
 };
 
@@ -397,17 +323,15 @@ int launch_multi_axpy(double *q, const double *coeffs, const double *const *v, i
 {
     MultiAxpyOp<M> op;
     op.q = q;
-    bool al = fdd_aligned16(q);
     for (int k = 0; k < M; k++)
     {
         op.v[k] = v[k];
         op.c[k] = coeffs[k];
-        al = al && fdd_aligned16(v[k]);
     }
-    return launch_ew(op, n, al, stream);
+    return launch_ew(op, n, stream);
 }
 
-// the same with the coefficients read from device memory (the output of fdd_gmres_finish_dev)
+// the same with the coefficients read from device memory (the output of fdd_gmres_finish_dev): fdd_lincomb (fdd_stream.h)
 template <int M>
 struct MultiAxpyDevOp
 {
@@ -417,35 +341,17 @@ struct MultiAxpyDevOp
     const double *vs; // optional per-vector scales: v_k stands for vs[k] * v_k
     bool from_zero;   // q is known to be 0 (it was just cleared): it is not read, 1.0*0 + c*v is c*v all the same
     const double *last; // optional: only vectors 0..(int)*last enter (a count that never left the device)
-    __device__ void vec2(long long i) const
+    template <typename A>
+    __device__ void at(A a, long long i) const
     {
-        double2 x = from_zero ? make_double2(0.0, 0.0) : ld2(q, i);
-        const int kmax = last ? (int)*last : M - 1;
-#pragma unroll
-        for (int k = 0; k < M; k++)
-        {
-            if (k > kmax) break;
-            const double ck = c[k];
-            double2 b = ld2(v[k], i);
-            if (vs)
-            {
-                const double sk = vs[k];
-                b.x = sk * b.x;
-                b.y = sk * b.y;
-            }
-            x.x = 1.0 * x.x + ck * b.x;
-            x.y = 1.0 * x.y + ck * b.y;
-        }
-        st2(q, i, x);
+        const auto x = from_zero ? a.all(0.0) : a.ld(q, i);
+        a.st(q, i, fdd_lincomb<M>(x, last ? (int)*last : M - 1, c, vs, [&](int k) { return a.ld(v[k], i); }));
     }
-    __device__ void one(long long i) const
+    template <typename F>
+    void pointers(F f) const
     {
-        double x = from_zero ? 0.0 : q[i];
-        const int kmax = last ? (int)*last : M - 1;
-#pragma unroll
-        for (int k = 0; k < M; k++)
-            if (k <= kmax) x = 1.0 * x + c[k] * (vs ? vs[k] * v[k][i] : v[k][i]);
-        q[i] = x;
+        f(q);
+        for (int k = 0; k < M; k++) f(v[k]);
     }
 };
 
@@ -458,13 +364,8 @@ int launch_multi_axpy_dev(double *q, const double *coeffs_dev, const double *con
     op.vs = v_scale_dev;
     op.from_zero = from_zero;
     op.last = last_dev;
-    bool al = fdd_aligned16(q);
-    for (int k = 0; k < M; k++)
-    {
-        op.v[k] = v[k];
-        al = al && fdd_aligned16(v[k]);
-    }
-    return launch_ew(op, n, al, stream);
+    for (int k = 0; k < M; k++) op.v[k] = v[k];
+    return launch_ew(op, n, stream);
 }
 
 // ------------------------------------------------------------ AMG/kernels.cu
@@ -475,49 +376,49 @@ struct ScaledResidualOp // AMG/kernels.cu:25-41
     const double *f_m_Au;
     const double *S;
     double alpha;
-    __device__ void vec2(long long i) const
+    template <typename A>
+    __device__ void at(A a, long long i) const
     {
-        double2 s = ld2(S, i), r = ld2(f_m_Au, i);
-        double2 sr = make_double2(s.x * r.x, s.y * r.y);
-        st2(Sr, i, sr);
-        st2(w, i, make_double2(alpha * sr.x, alpha * sr.y));
+        const auto sr = a.ld(S, i) * a.ld(f_m_Au, i);
+        a.st(Sr, i, sr);
+        a.st(w, i, alpha * sr);
     }
-    __device__ void one(long long i) const
-    {
-        Sr[i] = S[i] * f_m_Au[i];
-        w[i] = alpha * Sr[i];
-    }
+    template <typename F>
+    void pointers(F f) const { f(Sr), f(w), f(f_m_Au), f(S); }
 };
 
-struct SmoothStartOp // scaled_residual from u = 0 (f - A u is f) followed by vector_multiplication: Sr = S*f, work = D*(alpha*Sr)
+// scaled_residual from u = 0 (f - A u is f) followed by vector_multiplication: Sr = S*f, work = D*(alpha*Sr); T = double or float
+template <typename A, typename T>
+__device__ __forceinline__ void smooth_start_at(A a, long long i, T *work, T *Sr, const T *f, const T *S, T alpha)
+{
+    const auto s = a.ld(S, i), sr = s * a.ld(f, i);
+    a.st(Sr, i, sr);
+    a.st(work, i, s * (alpha * sr));
+}
+
+struct SmoothStartOp
 {
     double *work;
     double *Sr;
     const double *f;
     const double *S;
     double alpha;
-    __device__ void vec2(long long i) const
-    {
-        double2 s = ld2(S, i), r = ld2(f, i);
-        double2 sr = make_double2(s.x * r.x, s.y * r.y);
-        st2(Sr, i, sr);
-        st2(work, i, make_double2(s.x * (alpha * sr.x), s.y * (alpha * sr.y)));
-    }
-    __device__ void one(long long i) const
-    {
-        const double sr = S[i] * f[i];
-        Sr[i] = sr;
-        work[i] = S[i] * (alpha * sr);
-    }
+    template <typename A>
+    __device__ void at(A a, long long i) const { smooth_start_at(a, i, work, Sr, f, S, alpha); }
+    template <typename F>
+    void pointers(F fn) const { fn(work), fn(Sr), fn(f), fn(S); }
 };
 
-// ---- Float = float (AMG/config.hpp:4): the two element-wise kernels the fused f32 V-cycle launches ----
+// ---- Float = float (AMG/config.hpp:4): the two element-wise kernels the fused f32 V-cycle launches.  Their pairs are
+// 8 bytes, but the entries have always asked 16 of their pointers before they walk them in pairs, and still do ----
 struct SetF32Op // AMG/kernels.cu:11-23
 {
     float *data;
     float value;
-    __device__ void vec2(long long i) const { reinterpret_cast<float2 *>(data)[i] = make_float2(value, value); }
-    __device__ void one(long long i) const { data[i] = value; }
+    template <typename A>
+    __device__ void at(A a, long long i) const { a.st(data, i, a.all(value)); }
+    template <typename F>
+    void pointers(F f) const { f(data, 16); }
 };
 
 struct SmoothStartF32Op // SmoothStartOp in f32
@@ -527,19 +428,10 @@ struct SmoothStartF32Op // SmoothStartOp in f32
     const float *f;
     const float *S;
     float alpha;
-    __device__ void vec2(long long i) const
-    {
-        const float2 s = reinterpret_cast<const float2 *>(S)[i], r = reinterpret_cast<const float2 *>(f)[i];
-        const float2 sr = make_float2(s.x * r.x, s.y * r.y);
-        reinterpret_cast<float2 *>(Sr)[i] = sr;
-        reinterpret_cast<float2 *>(work)[i] = make_float2(s.x * (alpha * sr.x), s.y * (alpha * sr.y));
-    }
-    __device__ void one(long long i) const
-    {
-        const float sr = S[i] * f[i];
-        Sr[i] = sr;
-        work[i] = S[i] * (alpha * sr);
-    }
+    template <typename A>
+    __device__ void at(A a, long long i) const { smooth_start_at(a, i, work, Sr, f, S, alpha); }
+    template <typename F>
+    void pointers(F fn) const { fn(work, 16), fn(Sr, 16), fn(f, 16), fn(S, 16); }
 };
 
 struct PolyEvalOp // AMG/kernels.cu:43-59
@@ -549,19 +441,15 @@ struct PolyEvalOp // AMG/kernels.cu:43-59
     const double *r;
     const double *D_val;
     double alpha;
-    __device__ void vec2(long long i) const
+    template <typename A>
+    __device__ void at(A a, long long i) const
     {
-        double2 vv = ld2(v, i), d = ld2(D_val, i), rr = ld2(r, i);
-        vv.x *= d.x;
-        vv.y *= d.y;
-        st2(v, i, vv);
-        st2(w, i, make_double2(alpha * rr.x + vv.x, alpha * rr.y + vv.y));
+        const auto vv = a.ld(v, i) * a.ld(D_val, i), rr = a.ld(r, i);
+        a.st(v, i, vv);
+        a.st(w, i, alpha * rr + vv);
     }
-    __device__ void one(long long i) const
-    {
-        v[i] *= D_val[i];
-        w[i] = alpha * r[i] + v[i];
-    }
+    template <typename F>
+    void pointers(F f) const { f(w), f(v), f(r), f(D_val); }
 };
 
 struct UpdateFieldOp // AMG/kernels.cu:61-76
@@ -569,14 +457,10 @@ struct UpdateFieldOp // AMG/kernels.cu:61-76
     double *u;
     const double *w;
     const double *D_val;
-    __device__ void vec2(long long i) const
-    {
-        double2 uu = ld2(u, i), ww = ld2(w, i), d = ld2(D_val, i);
-        uu.x += d.x * ww.x;
-        uu.y += d.y * ww.y;
-        st2(u, i, uu);
-    }
-    __device__ void one(long long i) const { u[i] += D_val[i] * w[i]; }
+    template <typename A>
+    __device__ void at(A a, long long i) const { a.st(u, i, a.ld(u, i) + a.ld(D_val, i) * a.ld(w, i)); }
+    template <typename F>
+    void pointers(F f) const { f(u), f(w), f(D_val); }
 };
 
 struct VMulOp // AMG/kernels.cu:79-94
@@ -584,12 +468,10 @@ struct VMulOp // AMG/kernels.cu:79-94
     double *uv;
     const double *u;
     const double *v;
-    __device__ void vec2(long long i) const
-    {
-        double2 a = ld2(u, i), b = ld2(v, i);
-        st2(uv, i, make_double2(a.x * b.x, a.y * b.y));
-    }
-    __device__ void one(long long i) const { uv[i] = u[i] * v[i]; }
+    template <typename A>
+    __device__ void at(A a, long long i) const { a.st(uv, i, a.ld(u, i) * a.ld(v, i)); }
+    template <typename F>
+    void pointers(F f) const { f(uv), f(u), f(v); }
 };
 
 static int initialize_arrays(double *u_k, double *r_k, const double *f, int n, void *stream)
@@ -597,7 +479,7 @@ static int initialize_arrays(double *u_k, double *r_k, const double *f, int n, v
     FDD_REQUIRE(n >= 0);
     if (n == 0) return 0;
     FDD_REQUIRE(u_k != nullptr && r_k != nullptr && f != nullptr);
-    return launch_ew(InitOp{u_k, r_k, f}, n, fdd_aligned16(u_k) && fdd_aligned16(r_k) && fdd_aligned16(f), stream);
+    return launch_ew(InitOp{u_k, r_k, f}, n, stream);
 }
 
 template <typename S>
@@ -606,8 +488,7 @@ static int update_ur(double *u_k, double *r_kp1, const double *r_k, const double
     FDD_REQUIRE(n >= 0);
     if (n == 0) return 0;
     FDD_REQUIRE(u_k != nullptr && r_kp1 != nullptr && r_k != nullptr && p_k != nullptr && q_k != nullptr);
-    bool al = fdd_aligned16(u_k) && fdd_aligned16(r_kp1) && fdd_aligned16(r_k) && fdd_aligned16(p_k) && fdd_aligned16(q_k);
-    return launch_ew(UpdateUROp<S>{u_k, r_kp1, r_k, p_k, q_k, alpha}, n, al, stream);
+    return launch_ew(UpdateUROp<S>{u_k, r_kp1, r_k, p_k, q_k, alpha}, n, stream);
 }
 
 template <typename S>
@@ -616,8 +497,7 @@ static int update_pr(double *p_k, double *r_k, const double *z_k, const double *
     FDD_REQUIRE(n >= 0);
     if (n == 0) return 0;
     FDD_REQUIRE(p_k != nullptr && r_k != nullptr && z_k != nullptr && r_kp1 != nullptr);
-    bool al = fdd_aligned16(p_k) && fdd_aligned16(r_k) && fdd_aligned16(z_k) && fdd_aligned16(r_kp1);
-    return launch_ew(UpdatePROp<S>{p_k, r_k, z_k, r_kp1, beta}, n, al, stream);
+    return launch_ew(UpdatePROp<S>{p_k, r_k, z_k, r_kp1, beta}, n, stream);
 }
 
 } // namespace
@@ -630,7 +510,7 @@ int fdd_set_to_value(double *u, double alpha, int n, int offset, void *stream)
     if (n == 0) return 0;
     FDD_REQUIRE(u != nullptr);
     double *p = u + offset;
-    return launch_ew(SetOp{p, alpha}, n, fdd_aligned16(p), stream);
+    return launch_ew(SetOp{p, alpha}, n, stream);
 }
 
 int fdd_invert_vector_elements(double *u, int n, void *stream)
@@ -638,7 +518,7 @@ int fdd_invert_vector_elements(double *u, int n, void *stream)
     FDD_REQUIRE(n >= 0);
     if (n == 0) return 0;
     FDD_REQUIRE(u != nullptr);
-    return launch_ew(InvertOp{u}, n, fdd_aligned16(u), stream);
+    return launch_ew(InvertOp{u}, n, stream);
 }
 
 int fdd_vector_vector_addition(double *uv, double alpha, const double *u, double beta, const double *v, int n, void *stream)
@@ -646,7 +526,7 @@ int fdd_vector_vector_addition(double *uv, double alpha, const double *u, double
     FDD_REQUIRE(n >= 0);
     if (n == 0) return 0;
     FDD_REQUIRE(uv != nullptr && u != nullptr && v != nullptr);
-    return launch_ew(AxpbyOp{uv, u, v, alpha, beta}, n, fdd_aligned16(uv) && fdd_aligned16(u) && fdd_aligned16(v), stream);
+    return launch_ew(AxpbyOp{uv, u, v, alpha, beta}, n, stream);
 }
 
 int fdd_vector_scaling(double *au, double alpha, const double *u, int n, void *stream)
@@ -654,7 +534,7 @@ int fdd_vector_scaling(double *au, double alpha, const double *u, int n, void *s
     FDD_REQUIRE(n >= 0);
     if (n == 0) return 0;
     FDD_REQUIRE(au != nullptr && u != nullptr);
-    return launch_ew(ScaleOp{au, u, alpha}, n, fdd_aligned16(au) && fdd_aligned16(u), stream);
+    return launch_ew(ScaleOp{au, u, alpha}, n, stream);
 }
 
 int fdd_sqrt_sum_dev(double *out, const double *parts_dev, int nparts, void *stream)
@@ -670,7 +550,7 @@ int fdd_xpby_ratio_dev(double *out, const double *x, const double *num_dev, cons
     FDD_REQUIRE(n >= 0);
     if (n == 0) return 0;
     FDD_REQUIRE(out != nullptr && x != nullptr && y != nullptr && num_dev != nullptr && den_dev != nullptr);
-    return launch_ew(XpbyRatioDevOp{out, x, y, num_dev, den_dev}, n, fdd_aligned16(out) && fdd_aligned16(x) && fdd_aligned16(y), stream);
+    return launch_ew(XpbyRatioDevOp{out, x, y, num_dev, den_dev}, n, stream);
 }
 
 int fdd_xmay_ratio_dev(double *out, const double *x, const double *num_dev, const double *den_dev, const double *y, int n, void *stream)
@@ -678,7 +558,7 @@ int fdd_xmay_ratio_dev(double *out, const double *x, const double *num_dev, cons
     FDD_REQUIRE(n >= 0);
     if (n == 0) return 0;
     FDD_REQUIRE(out != nullptr && x != nullptr && y != nullptr && num_dev != nullptr && den_dev != nullptr);
-    return launch_ew(XmayRatioDevOp{out, x, y, num_dev, den_dev}, n, fdd_aligned16(out) && fdd_aligned16(x) && fdd_aligned16(y), stream);
+    return launch_ew(XmayRatioDevOp{out, x, y, num_dev, den_dev}, n, stream);
 }
 
 int fdd_vector_scaling_dev(double *au, const double *scale_dev, const double *u, int n, void *stream)
@@ -686,7 +566,7 @@ int fdd_vector_scaling_dev(double *au, const double *scale_dev, const double *u,
     FDD_REQUIRE(n >= 0);
     if (n == 0) return 0;
     FDD_REQUIRE(au != nullptr && u != nullptr && scale_dev != nullptr);
-    return launch_ew(ScaleDevOp{au, u, scale_dev}, n, fdd_aligned16(au) && fdd_aligned16(u), stream);
+    return launch_ew(ScaleDevOp{au, u, scale_dev}, n, stream);
 }
 
 int fdd_vector_diagonal_scaling_dev(double *z, const double *d, const double *scale_dev, const double *u, int n, void *stream)
@@ -694,7 +574,7 @@ int fdd_vector_diagonal_scaling_dev(double *z, const double *d, const double *sc
     FDD_REQUIRE(n >= 0);
     if (n == 0) return 0;
     FDD_REQUIRE(z != nullptr && u != nullptr && d != nullptr);
-    return launch_ew(DiagScaleDevOp{z, d, u, scale_dev}, n, fdd_aligned16(z) && fdd_aligned16(u) && fdd_aligned16(d), stream);
+    return launch_ew(DiagScaleDevOp{z, d, u, scale_dev}, n, stream);
 }
 
 int fdd_cheby_step(double *x, double *d, double *r_out, const double *r_in, const double *q, const double *dinv, double c_d, double c_r, int first, int last, int n, void *stream)
@@ -704,8 +584,7 @@ int fdd_cheby_step(double *x, double *d, double *r_out, const double *r_in, cons
     FDD_REQUIRE(x != nullptr && r_in != nullptr && dinv != nullptr);
     FDD_REQUIRE(last || d != nullptr);
     FDD_REQUIRE(first || (q != nullptr && d != nullptr && (last || r_out != nullptr)));
-    const bool al = fdd_aligned16(x) && fdd_aligned16(r_in) && fdd_aligned16(dinv) && (last || fdd_aligned16(d)) && (first || (fdd_aligned16(q) && fdd_aligned16(d) && (last || fdd_aligned16(r_out))));
-    return launch_ew(ChebyStepOp{x, d, r_out, r_in, q, dinv, c_d, c_r, first ? 1 : 0, last ? 1 : 0}, n, al, stream);
+    return launch_ew(ChebyStepOp{x, d, r_out, r_in, q, dinv, c_d, c_r, first ? 1 : 0, last ? 1 : 0}, n, stream);
 }
 
 int fdd_vector_scaling_rsqrt_dev(double *au, const double *norm2_dev, const double *u, int n, void *stream)
@@ -713,7 +592,7 @@ int fdd_vector_scaling_rsqrt_dev(double *au, const double *norm2_dev, const doub
     FDD_REQUIRE(n >= 0);
     if (n == 0) return 0;
     FDD_REQUIRE(au != nullptr && u != nullptr && norm2_dev != nullptr);
-    return launch_ew(ScaleRsqrtDevOp{au, u, norm2_dev}, n, fdd_aligned16(au) && fdd_aligned16(u), stream);
+    return launch_ew(ScaleRsqrtDevOp{au, u, norm2_dev}, n, stream);
 }
 
 int fdd_dom_initialize_arrays(double *u_k, double *r_k, const double *f, int num_points, void *stream)
@@ -763,7 +642,7 @@ int fdd_sub_copy_f64_f64(double *u, const double *v, int num_points, void *strea
     FDD_REQUIRE(num_points >= 0);
     if (num_points == 0) return 0;
     FDD_REQUIRE(u != nullptr && v != nullptr);
-    return launch_ew(CopyOp{u, v}, num_points, fdd_aligned16(u) && fdd_aligned16(v), stream);
+    return launch_ew(CopyOp{u, v}, num_points, stream);
 }
 
 int fdd_sub_copy_f32_f64(float *u, const double *v, int num_points, void *stream)
@@ -771,8 +650,7 @@ int fdd_sub_copy_f32_f64(float *u, const double *v, int num_points, void *stream
     FDD_REQUIRE(num_points >= 0);
     if (num_points == 0) return 0;
     FDD_REQUIRE(u != nullptr && v != nullptr);
-    bool al = fdd_aligned16(v) && ((reinterpret_cast<uintptr_t>(u) & 7u) == 0);
-    return launch_ew(CopyF32F64Op{u, v}, num_points, al, stream);
+    return launch_ew(CopyF32F64Op{u, v}, num_points, stream);
 }
 
 int fdd_sub_copy_f64_f32(double *u, const float *v, int num_points, void *stream)
@@ -780,8 +658,7 @@ int fdd_sub_copy_f64_f32(double *u, const float *v, int num_points, void *stream
     FDD_REQUIRE(num_points >= 0);
     if (num_points == 0) return 0;
     FDD_REQUIRE(u != nullptr && v != nullptr);
-    bool al = fdd_aligned16(u) && ((reinterpret_cast<uintptr_t>(v) & 7u) == 0);
-    return launch_ew(CopyF64F32Op{u, v}, num_points, al, stream);
+    return launch_ew(CopyF64F32Op{u, v}, num_points, stream);
 }
 
 int fdd_multi_axpy(double *q, const double *coeffs, const double *const *v, int m, int n, void *stream)
@@ -848,8 +725,7 @@ int fdd_amg_main_scaled_residual(double *Sr, double *w, const double *f_m_Au, co
     FDD_REQUIRE(size >= 0);
     if (size == 0) return 0;
     FDD_REQUIRE(Sr != nullptr && w != nullptr && f_m_Au != nullptr && S != nullptr);
-    bool al = fdd_aligned16(Sr) && fdd_aligned16(w) && fdd_aligned16(f_m_Au) && fdd_aligned16(S);
-    return launch_ew(ScaledResidualOp{Sr, w, f_m_Au, S, alpha}, size, al, stream);
+    return launch_ew(ScaledResidualOp{Sr, w, f_m_Au, S, alpha}, size, stream);
 }
 
 int fdd_amg_smooth_start(double *work, double *Sr, const double *f, const double *D_val, double coef, int size, void *stream)
@@ -857,8 +733,7 @@ int fdd_amg_smooth_start(double *work, double *Sr, const double *f, const double
     FDD_REQUIRE(size >= 0);
     if (size == 0) return 0;
     FDD_REQUIRE(work != nullptr && Sr != nullptr && f != nullptr && D_val != nullptr);
-    bool al = fdd_aligned16(work) && fdd_aligned16(Sr) && fdd_aligned16(f) && fdd_aligned16(D_val);
-    return launch_ew(SmoothStartOp{work, Sr, f, D_val, coef}, size, al, stream);
+    return launch_ew(SmoothStartOp{work, Sr, f, D_val, coef}, size, stream);
 }
 
 int fdd_amg_vector_set_to_value_f32(float *data, float value, int size, void *stream)
@@ -866,7 +741,7 @@ int fdd_amg_vector_set_to_value_f32(float *data, float value, int size, void *st
     FDD_REQUIRE(size >= 0);
     if (size == 0) return 0;
     FDD_REQUIRE(data != nullptr);
-    return launch_ew(SetF32Op{data, value}, size, fdd_aligned16(data), stream);
+    return launch_ew(SetF32Op{data, value}, size, stream);
 }
 
 int fdd_amg_smooth_start_f32(float *work, float *Sr, const float *f, const float *D_val, float coef, int size, void *stream)
@@ -874,8 +749,7 @@ int fdd_amg_smooth_start_f32(float *work, float *Sr, const float *f, const float
     FDD_REQUIRE(size >= 0);
     if (size == 0) return 0;
     FDD_REQUIRE(work != nullptr && Sr != nullptr && f != nullptr && D_val != nullptr);
-    bool al = fdd_aligned16(work) && fdd_aligned16(Sr) && fdd_aligned16(f) && fdd_aligned16(D_val);
-    return launch_ew(SmoothStartF32Op{work, Sr, f, D_val, coef}, size, al, stream);
+    return launch_ew(SmoothStartF32Op{work, Sr, f, D_val, coef}, size, stream);
 }
 
 int fdd_amg_main_polynomial_evaluation(double *w, double *v, const double *r, const double *D_val, double alpha, int size, void *stream)
@@ -883,8 +757,7 @@ int fdd_amg_main_polynomial_evaluation(double *w, double *v, const double *r, co
     FDD_REQUIRE(size >= 0);
     if (size == 0) return 0;
     FDD_REQUIRE(w != nullptr && v != nullptr && r != nullptr && D_val != nullptr);
-    bool al = fdd_aligned16(w) && fdd_aligned16(v) && fdd_aligned16(r) && fdd_aligned16(D_val);
-    return launch_ew(PolyEvalOp{w, v, r, D_val, alpha}, size, al, stream);
+    return launch_ew(PolyEvalOp{w, v, r, D_val, alpha}, size, stream);
 }
 
 int fdd_amg_main_update_field(double *u, const double *w, const double *D_val, int size, void *stream)
@@ -892,8 +765,7 @@ int fdd_amg_main_update_field(double *u, const double *w, const double *D_val, i
     FDD_REQUIRE(size >= 0);
     if (size == 0) return 0;
     FDD_REQUIRE(u != nullptr && w != nullptr && D_val != nullptr);
-    bool al = fdd_aligned16(u) && fdd_aligned16(w) && fdd_aligned16(D_val);
-    return launch_ew(UpdateFieldOp{u, w, D_val}, size, al, stream);
+    return launch_ew(UpdateFieldOp{u, w, D_val}, size, stream);
 }
 
 int fdd_amg_vector_multiplication(double *uv, const double *u, const double *v, int size, void *stream)
@@ -901,8 +773,7 @@ int fdd_amg_vector_multiplication(double *uv, const double *u, const double *v, 
     FDD_REQUIRE(size >= 0);
     if (size == 0) return 0;
     FDD_REQUIRE(uv != nullptr && u != nullptr && v != nullptr);
-    bool al = fdd_aligned16(uv) && fdd_aligned16(u) && fdd_aligned16(v);
-    return launch_ew(VMulOp{uv, u, v}, size, al, stream);
+    return launch_ew(VMulOp{uv, u, v}, size, stream);
 }
 
 } // extern "C"

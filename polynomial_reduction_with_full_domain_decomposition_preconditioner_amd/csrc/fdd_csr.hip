@@ -34,7 +34,7 @@
 //    gather matrix Qt, and its weighted norm, on the plan's row blocks.
 #include <type_traits>
 
-#include "fdd_common.h"
+#include "fdd_stream.h" // wave_sum
 
 #include <algorithm>
 #include <cstdlib>
@@ -268,20 +268,6 @@ __global__ __launch_bounds__(kBlock) void csr_row_kernel(double *__restrict__ Au
 #pragma unroll
     for (int r = 0; r < NPT; r++)
         if (row[r] < row_end) Au[row[r]] = epi.finish(s[r], epi.operand(row[r], Au), row[r]);
-}
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = FDD_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, FDD_WAVE);
-    return v;
-}
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = FDD_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, FDD_WAVE);
-    return v;
 }
 
 // T: the value type of the matrix and of both vectors (double everywhere except the Float = float V-cycle, AMG/config.hpp:4)

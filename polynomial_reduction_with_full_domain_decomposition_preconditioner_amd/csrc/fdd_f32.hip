@@ -4,9 +4,7 @@
 // Storage is float; device-resident scalars (Gram-Schmidt coefficients, 1/norm scales, the Givens state) stay
 // double, as do the accumulators of the reductions (fdd_reduce.hip).  The stiffness kernel is the float
 // instantiation of the fused kernel (fdd_stiffness.hip), the V-cycle the f32 cycle of host/amg.hpp.
-#include <cstdint>
-
-#include "fdd_common.h"
+#include "fdd_stream.h"
 
 namespace
 {
@@ -39,54 +37,25 @@ __global__ __launch_bounds__(kBlock) void axpby_f32_kernel(float *uv, float alph
     for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) uv[i] = alpha * u[i] + beta * v[i];
 }
 
-// One step of the Chebyshev-Jacobi inner solve on float vectors: the statements of ChebyStepOp (fdd_blas1.hip), which are
-// those of axpby_f32_kernel and diag_scale_dev_f32_kernel above.  16 bytes per lane where every pointer allows it.
+// One step of the Chebyshev-Jacobi inner solve on float vectors: fdd_cheby_step_at (fdd_stream.h), whose statements are
+// those of axpby_f32_kernel and diag_scale_dev_f32_kernel above.  Four floats per lane where all six pointers allow it
+// (an absent one is NULL and does).
 struct ChebyStepF32
 {
     float *x, *d, *r_out;
     const float *r_in, *q, *dinv;
     float c_d, c_r;
     int first, last;
-    __device__ void one(float &xv, float &dv, float &rv, float qv, float di) const
-    {
-        if (!first) rv = 1.0f * rv + (-1.0f) * qv;
-        const float t = di * rv;
-        dv = first ? c_r * t + 0.0f * t : c_d * dv + c_r * t;
-        xv = first ? dv : 1.0f * xv + 1.0f * dv;
-    }
+    template <typename A>
+    __device__ void at(A l, long long i) const { fdd_cheby_step_at(l, i, x, d, r_out, r_in, q, dinv, c_d, c_r, first, last); }
+    template <typename F>
+    void pointers(F f) const { f(x), f(r_in), f(dinv), f(d), f(r_out), f(q); }
 };
 __global__ __launch_bounds__(kBlock) void cheby_step_f32_kernel(ChebyStepF32 a, long long n4, long long n)
 {
-    const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (long long)gridDim.x * kBlock)
-    {
-        const float4 di = reinterpret_cast<const float4 *>(a.dinv)[i];
-        float4 r = reinterpret_cast<const float4 *>(a.r_in)[i], qv = zero, dv = zero, xv = zero;
-        if (!a.first)
-        {
-            qv = reinterpret_cast<const float4 *>(a.q)[i];
-            dv = reinterpret_cast<const float4 *>(a.d)[i];
-            xv = reinterpret_cast<const float4 *>(a.x)[i];
-        }
-        a.one(xv.x, dv.x, r.x, qv.x, di.x);
-        a.one(xv.y, dv.y, r.y, qv.y, di.y);
-        a.one(xv.z, dv.z, r.z, qv.z, di.z);
-        a.one(xv.w, dv.w, r.w, qv.w, di.w);
-        reinterpret_cast<float4 *>(a.x)[i] = xv;
-        if (a.last) continue;
-        reinterpret_cast<float4 *>(a.d)[i] = dv;
-        if (!a.first) reinterpret_cast<float4 *>(a.r_out)[i] = r;
-    }
-    // the tail behind the last whole float4 (n4 = 0: every value, for pointers that are not 16-byte aligned)
-    for (long long i = 4 * n4 + (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock)
-    {
-        float r = a.r_in[i], dv = a.first ? 0.0f : a.d[i], xv = a.first ? 0.0f : a.x[i];
-        a.one(xv, dv, r, a.first ? 0.0f : a.q[i], a.dinv[i]);
-        a.x[i] = xv;
-        if (a.last) continue;
-        a.d[i] = dv;
-        if (!a.first) a.r_out[i] = r;
-    }
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n4; i += (long long)gridDim.x * kBlock) a.at(fdd_lanes<4>{}, i);
+    // the tail behind the last whole quad (n4 = 0: every value, for pointers that are not 16-byte aligned)
+    for (long long i = 4 * n4 + (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += (long long)gridDim.x * kBlock) a.at(fdd_lanes<1>{}, i);
 }
 
 // q (+)= sum_k c[k] * (s[k] *) v_k, k < min(m, *last + 1): the solution update of the inner GMRES from device coefficients
@@ -185,10 +154,9 @@ int fdd_cheby_step_f32(float *x, float *d, float *r_out, const float *r_in, cons
     FDD_REQUIRE(x != nullptr && r_in != nullptr && dinv != nullptr);
     FDD_REQUIRE(last || d != nullptr);
     FDD_REQUIRE(first || (q != nullptr && d != nullptr && (last || r_out != nullptr)));
-    const auto al = [](const void *p) { return p == nullptr || ((uintptr_t)p & 15) == 0; };
-    const bool aligned = al(x) && al(r_in) && al(dinv) && al(d) && al(r_out) && al(q);
-    const long long n4 = aligned ? n / 4 : 0;
-    hipLaunchKernelGGL(cheby_step_f32_kernel, dim3(grid_for(n4 > 0 ? n4 : n)), dim3(kBlock), 0, fdd_stream(stream), ChebyStepF32{x, d, r_out, r_in, q, dinv, c_d, c_r, first ? 1 : 0, last ? 1 : 0}, n4, (long long)n);
+    const ChebyStepF32 op{x, d, r_out, r_in, q, dinv, c_d, c_r, first ? 1 : 0, last ? 1 : 0};
+    const long long n4 = fdd_lanes_fit<fdd_lanes<4>>(op) ? n / 4 : 0;
+    hipLaunchKernelGGL(cheby_step_f32_kernel, dim3(grid_for(n4 > 0 ? n4 : n)), dim3(kBlock), 0, fdd_stream(stream), op, n4, (long long)n);
     FDD_LAUNCH_CHECK();
     return 0;
 }

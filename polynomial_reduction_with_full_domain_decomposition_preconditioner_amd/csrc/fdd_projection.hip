@@ -12,7 +12,7 @@
 // non-temporal loads, private sums per lane, a wavefront __shfl_down tree, one partial per workgroup and value, and
 // one final workgroup.  Results are deterministic for given n and K (fixed grid, fixed tree).  The workspace is the
 // common one of fdd_reduce_workspace_doubles(): the dots' grid is capped so that K * grid partials fit in it.
-#include "fdd_common.h"
+#include "fdd_stream.h"
 
 namespace
 {
@@ -21,19 +21,6 @@ constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / FDD_WAVE;
 constexpr int kWsDoubles = FDD_MULTI_MAX * FDD_REDUCE_MAX_BLOCKS; // fdd_reduce_workspace_doubles()
 
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = FDD_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, FDD_WAVE);
-    return v;
-}
-
-typedef double fdd_v2f64 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ double2 ld2(const double *p, long long i) // non-temporal: read once per launch
-{
-    const fdd_v2f64 v = __builtin_nontemporal_load(reinterpret_cast<const fdd_v2f64 *>(p) + i);
-    return make_double2(v.x, v.y);
-}
 __device__ __forceinline__ double ld1(const double *p, long long i) { return __builtin_nontemporal_load(p + i); }
 
 // one partial per workgroup and value: ws[k * gridDim.x + blockIdx.x]

@@ -11,20 +11,18 @@
 // for a given n (fixed grid, fixed tree) but its summation order differs from
 // the reference's 128-wide tree + serial block sum: parity is
 // tolerance-based (tests/).
-#include "fdd_common.h"
+//
+// Every op states its terms once, in at(), over a lane accessor (fdd_stream.h): a
+// pair adds its first element's term and then its second's to the lane's sum.
+#include "fdd_stream.h"
 
 namespace
 {
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / FDD_WAVE;
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = FDD_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, FDD_WAVE);
-    return v;
-}
+using Single = fdd_lanes<1>;
+using Pair = fdd_lanes<2>;
 
 // NV values per element (1 or 2 simultaneous sums)
 template <int NV>
@@ -68,8 +66,8 @@ __global__ __launch_bounds__(kBlock) void reduce_vec2_kernel(Op op, double *ws, 
     for (int k = 0; k < Op::NV; k++) a.v[k] = 0.0;
 
     const long long stride = (long long)gridDim.x * kBlock;
-    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n2; i += stride) op.vec2(i, a);
-    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) op.one(n - 1, a);
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n2; i += stride) op.at(Pair{}, i, a);
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) op.at(Single{}, n - 1, a);
 
     block_reduce_store<Op::NV>(a, ws, FDD_REDUCE_MAX_BLOCKS);
 }
@@ -82,7 +80,7 @@ __global__ __launch_bounds__(kBlock) void reduce_scalar_kernel(Op op, double *ws
     for (int k = 0; k < Op::NV; k++) a.v[k] = 0.0;
 
     const long long stride = (long long)gridDim.x * kBlock;
-    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) op.one(i, a);
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) op.at(Single{}, i, a);
 
     block_reduce_store<Op::NV>(a, ws, FDD_REDUCE_MAX_BLOCKS);
 }
@@ -132,7 +130,7 @@ __global__ __launch_bounds__(kBlock) void reduce_final_kernel(double *out, const
 }
 
 template <typename Op>
-int launch_reduce(const Op &op, double *out, double *ws, long long n, bool aligned, void *stream)
+int launch_reduce(const Op &op, double *out, double *ws, long long n, void *stream)
 {
     hipStream_t s = fdd_stream(stream);
     if (n <= 0)
@@ -142,7 +140,7 @@ int launch_reduce(const Op &op, double *out, double *ws, long long n, bool align
     }
 
     int grid;
-    if (aligned && n >= 2)
+    if (fdd_lanes_fit<Pair>(op) && n >= 2)
     {
         long long n2 = n / 2;
         grid = fdd_stream_grid(n2, kBlock);
@@ -159,88 +157,70 @@ int launch_reduce(const Op &op, double *out, double *ws, long long n, bool align
     return 0;
 }
 
-typedef double fdd_v2f64 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ double2 ld2(const double *p, long long i) // non-temporal: read once per launch
-{
-    const fdd_v2f64 v = __builtin_nontemporal_load(reinterpret_cast<const fdd_v2f64 *>(p) + i);
-    return make_double2(v.x, v.y);
-}
+// Every op: at(l, i, acc) adds the terms of element i of accessor l to the lane's sums, pointers(f) names the vectors it touches.
 
 struct Dot2Op // subdomain.okl:103-132 / cublasDdot
 {
     static constexpr int NV = 1;
     const double *u, *v;
-    __device__ void vec2(long long i, Acc<1> &a) const
-    {
-        double2 x = ld2(u, i), y = ld2(v, i);
-        a.v[0] += x.x * y.x;
-        a.v[0] += x.y * y.y;
-    }
-    __device__ void one(long long i, Acc<1> &a) const { a.v[0] += u[i] * v[i]; }
+    template <typename A>
+    __device__ void at(A l, long long i, Acc<1> &acc) const { l.add(acc.v[0], l.ld(u, i) * l.ld(v, i)); }
+    template <typename F>
+    void pointers(F f) const { f(u), f(v); }
 };
 
 struct Dot3Op // domain.okl:109-138 (r*QQt_r*mask), :235-264 (u*v*mask), subdomain.okl:134-163 (u*v*w)
 {
     static constexpr int NV = 1;
     const double *u, *v, *w;
-    __device__ void vec2(long long i, Acc<1> &a) const
-    {
-        double2 x = ld2(u, i), y = ld2(v, i), z = ld2(w, i);
-        a.v[0] += x.x * y.x * z.x;
-        a.v[0] += x.y * y.y * z.y;
-    }
-    __device__ void one(long long i, Acc<1> &a) const { a.v[0] += u[i] * v[i] * w[i]; }
+    template <typename A>
+    __device__ void at(A l, long long i, Acc<1> &acc) const { l.add(acc.v[0], l.ld(u, i) * l.ld(v, i) * l.ld(w, i)); }
+    template <typename F>
+    void pointers(F f) const { f(u), f(v), f(w); }
 };
 
 struct ProjOp // domain.okl:140-184
 {
     static constexpr int NV = 2;
     const double *z, *r, *p, *q;
-    __device__ void vec2(long long i, Acc<2> &a) const
+    template <typename A>
+    __device__ void at(A l, long long i, Acc<2> &acc) const
     {
-        double2 zz = ld2(z, i), rr = ld2(r, i), pp = ld2(p, i), qq = ld2(q, i);
-        a.v[0] += zz.x * rr.x;
-        a.v[0] += zz.y * rr.y;
-        a.v[1] += pp.x * qq.x;
-        a.v[1] += pp.y * qq.y;
+        const auto zz = l.ld(z, i), rr = l.ld(r, i), pp = l.ld(p, i), qq = l.ld(q, i);
+        l.add(acc.v[0], zz * rr);
+        l.add(acc.v[1], pp * qq);
     }
-    __device__ void one(long long i, Acc<2> &a) const
-    {
-        a.v[0] += z[i] * r[i];
-        a.v[1] += p[i] * q[i];
-    }
+    template <typename F>
+    void pointers(F f) const { f(z), f(r), f(p), f(q); }
 };
 
 struct ProjWOp // subdomain.okl:165-209
 {
     static constexpr int NV = 2;
     const double *z, *r, *p, *q, *w;
-    __device__ void vec2(long long i, Acc<2> &a) const
+    template <typename A>
+    __device__ void at(A l, long long i, Acc<2> &acc) const
     {
-        double2 zz = ld2(z, i), rr = ld2(r, i), pp = ld2(p, i), qq = ld2(q, i), ww = ld2(w, i);
-        a.v[0] += zz.x * rr.x * ww.x;
-        a.v[0] += zz.y * rr.y * ww.y;
-        a.v[1] += pp.x * qq.x * ww.x;
-        a.v[1] += pp.y * qq.y * ww.y;
+        const auto zz = l.ld(z, i), rr = l.ld(r, i), pp = l.ld(p, i), qq = l.ld(q, i), ww = l.ld(w, i);
+        l.add(acc.v[0], zz * rr * ww);
+        l.add(acc.v[1], pp * qq * ww);
     }
-    __device__ void one(long long i, Acc<2> &a) const
-    {
-        a.v[0] += z[i] * r[i] * w[i];
-        a.v[1] += p[i] * q[i] * w[i];
-    }
+    template <typename F>
+    void pointers(F f) const { f(z), f(r), f(p), f(q), f(w); }
 };
 
 struct FlexOp // domain.okl:195-224
 {
     static constexpr int NV = 1;
     const double *r, *r1, *z;
-    __device__ void vec2(long long i, Acc<1> &a) const
+    template <typename A>
+    __device__ void at(A l, long long i, Acc<1> &acc) const
     {
-        double2 a0 = ld2(r, i), a1 = ld2(r1, i), zz = ld2(z, i);
-        a.v[0] += (a1.x - a0.x) * zz.x;
-        a.v[0] += (a1.y - a0.y) * zz.y;
+        const auto a0 = l.ld(r, i), a1 = l.ld(r1, i), zz = l.ld(z, i);
+        l.add(acc.v[0], (a1 - a0) * zz);
     }
-    __device__ void one(long long i, Acc<1> &a) const { a.v[0] += (r1[i] - r[i]) * z[i]; }
+    template <typename F>
+    void pointers(F f) const { f(r), f(r1), f(z); }
 };
 
 // the flexible dot and, from the same three streams, the NEXT iteration's gamma = <z, r+> (domain.okl:140-184's first sum one
@@ -249,27 +229,25 @@ struct FlexGammaOp
 {
     static constexpr int NV = 2;
     const double *r, *r1, *z;
-    __device__ void vec2(long long i, Acc<2> &a) const
+    // the two sums' terms, given the values of r, r+ and z
+    template <typename A, typename V>
+    static __device__ __forceinline__ void add(A l, Acc<2> &acc, V a0, V a1, V zz)
     {
-        double2 a0 = ld2(r, i), a1 = ld2(r1, i), zz = ld2(z, i);
-        a.v[0] += zz.x * a1.x;
-        a.v[0] += zz.y * a1.y;
-        a.v[1] += (a1.x - a0.x) * zz.x;
-        a.v[1] += (a1.y - a0.y) * zz.y;
+        l.add(acc.v[0], zz * a1);
+        l.add(acc.v[1], (a1 - a0) * zz);
     }
-    __device__ void one(long long i, Acc<2> &a) const
-    {
-        a.v[0] += z[i] * r1[i];
-        a.v[1] += (r1[i] - r[i]) * z[i];
-    }
+    template <typename A>
+    __device__ void at(A l, long long i, Acc<2> &acc) const { add(l, acc, l.ld(r, i), l.ld(r1, i), l.ld(z, i)); }
+    template <typename F>
+    void pointers(F f) const { f(r), f(r1), f(z); }
 };
 
 // FlexGammaOp with z's slice [lo, hi) not read but FORMED on the way: z[i] = (z[i] or 0) + sum_{k <= *last} c_k (vs_k v_k[i - lo]),
-// the statement of MultiAxpyDevOp (fdd_blas1.hip), stored, and entered into the two sums where the stored value would
-// have been loaded.  The traversal (pairs, accumulators, expressions, their order) is FlexGammaOp's, so z and both sums
-// have the bits of fdd_multi_lincomb_limited_dev followed by fdd_dom_inner_product_flexible_gamma -- without writing z
-// and reading it back, and, where v_0 is r1's own slice (the inner solve's right-hand side read in place), without
-// reading that twice.
+// the statement of MultiAxpyDevOp (fdd_blas1.hip; fdd_lincomb, fdd_stream.h), stored, and entered into the two sums where
+// the stored value would have been loaded.  The traversal (pairs, accumulators, expressions, their order) is FlexGammaOp's,
+// so z and both sums have the bits of fdd_multi_lincomb_limited_dev followed by fdd_dom_inner_product_flexible_gamma --
+// without writing z and reading it back, and, where v_0 is r1's own slice (the inner solve's right-hand side read in place),
+// without reading that twice.  A pair can lie astride a slice end, so the two accessors have a body each here.
 template <int M>
 struct LincombFlexGammaOp
 {
@@ -283,74 +261,49 @@ struct LincombFlexGammaOp
     const double *last; // optional: only vectors 0..(int)*last enter
     bool from_zero;     // z's slice is taken as 0 and not read
     bool v0_is_r1;      // v[0] == r1 + lo: its entries are the ones this pass loads from r1 anyway
-    bool v_pairs;       // lo is even and every v[k] is 16-byte aligned: a pair inside the slice is one 16-byte load per vector
+    bool v_pairs;       // lo is even and every v[k] is aligned for pairs: a pair inside the slice is one 16-byte load per vector
 
+    __device__ __forceinline__ int kmax() const { return last ? (int)*last : M - 1; }
     __device__ __forceinline__ double form(long long i, double r1_i, int kmax) const
     {
-        double x = from_zero ? 0.0 : z[i];
-#pragma unroll
-        for (int k = 0; k < M; k++)
-            if (k <= kmax)
-            {
-                const double b = (k == 0 && v0_is_r1) ? r1_i : v[k][i - lo];
-                x = 1.0 * x + c[k] * (vs ? vs[k] * b : b);
-            }
+        const double x = fdd_lincomb<M>(from_zero ? 0.0 : z[i], kmax, c, vs, [&](int k) { return (k == 0 && v0_is_r1) ? r1_i : v[k][i - lo]; });
         z[i] = x;
         return x;
     }
-    __device__ void vec2(long long i, Acc<2> &a) const
+    __device__ void at(Pair l, long long i, Acc<2> &acc) const
     {
-        const double2 a0 = ld2(r, i), a1 = ld2(r1, i);
+        using V = Pair::value<double>;
+        const V a0 = l.ld(r, i), a1 = l.ld(r1, i);
         const long long g = 2 * i;
         const bool in0 = g >= lo && g < hi, in1 = g + 1 >= lo && g + 1 < hi;
-        double2 zz;
+        V zz;
         if (in0 && in1)
         {
-            const int kmax = last ? (int)*last : M - 1;
-            zz = from_zero ? make_double2(0.0, 0.0) : ld2(z, i);
-#pragma unroll
-            for (int k = 0; k < M; k++)
-            {
-                if (k > kmax) break;
-                const double ck = c[k];
-                double2 b;
-                if (k == 0 && v0_is_r1)
-                    b = a1;
-                else if (v_pairs)
-                    b = ld2(v[k], (g - lo) >> 1);
-                else
-                    b = make_double2(__builtin_nontemporal_load(v[k] + (g - lo)), __builtin_nontemporal_load(v[k] + (g - lo) + 1));
-                if (vs)
-                {
-                    const double sk = vs[k];
-                    b.x = sk * b.x;
-                    b.y = sk * b.y;
-                }
-                zz.x = 1.0 * zz.x + ck * b.x;
-                zz.y = 1.0 * zz.y + ck * b.y;
-            }
-            reinterpret_cast<double2 *>(z)[i] = zz; // default policy: the direction update reads it next
+            zz = fdd_lincomb<M>(from_zero ? l.all(0.0) : l.ld(z, i), kmax(), c, vs, [&](int k) -> V {
+                if (k == 0 && v0_is_r1) return a1;
+                if (v_pairs) return l.ld(v[k], (g - lo) >> 1);
+                return {__builtin_nontemporal_load(v[k] + (g - lo)), __builtin_nontemporal_load(v[k] + (g - lo) + 1)};
+            });
+            l.st(z, i, zz); // default policy: the direction update reads it next
         }
         else if (in0 || in1) // a pair astride a slice end: per component
         {
-            const int kmax = last ? (int)*last : M - 1;
-            zz.x = in0 ? form(g, a1.x, kmax) : z[g];
-            zz.y = in1 ? form(g + 1, a1.y, kmax) : z[g + 1];
+            const int km = kmax();
+            zz.c[0] = in0 ? form(g, a1.c[0], km) : z[g];
+            zz.c[1] = in1 ? form(g + 1, a1.c[1], km) : z[g + 1];
         }
         else
-            zz = ld2(z, i);
-        a.v[0] += zz.x * a1.x;
-        a.v[0] += zz.y * a1.y;
-        a.v[1] += (a1.x - a0.x) * zz.x;
-        a.v[1] += (a1.y - a0.y) * zz.y;
+            zz = l.ld(z, i);
+        FlexGammaOp::add(l, acc, a0, a1, zz);
     }
-    __device__ void one(long long i, Acc<2> &a) const
+    __device__ void at(Single l, long long i, Acc<2> &acc) const
     {
         const double r1_i = r1[i];
-        const double zi = (i >= lo && i < hi) ? form(i, r1_i, last ? (int)*last : M - 1) : z[i];
-        a.v[0] += zi * r1_i;
-        a.v[1] += (r1_i - r[i]) * zi;
+        FlexGammaOp::add(l, acc, r[i], r1_i, (i >= lo && i < hi) ? form(i, r1_i, kmax()) : z[i]);
     }
+    // the same selection as fdd_dom_inner_product_flexible_gamma's: the pairing of the sums is that entry's
+    template <typename F>
+    void pointers(F f) const { f(r), f(r1), f(z); }
 };
 
 template <int M>
@@ -371,26 +324,24 @@ int launch_lincomb_flex_gamma(double *out2, double *ws, const double *r, const d
     for (int k = 0; k < M; k++)
     {
         op.v[k] = v[k];
-        op.v_pairs = op.v_pairs && fdd_aligned16(v[k]);
+        op.v_pairs = op.v_pairs && fdd_aligned(v[k], Pair::bytes<double>);
     }
-    // the same selection as fdd_dom_inner_product_flexible_gamma's: the pairing of the sums is that entry's
-    return launch_reduce(op, out2, ws, n, fdd_aligned16(r) && fdd_aligned16(r1) && fdd_aligned16(z), stream);
+    return launch_reduce(op, out2, ws, n, stream);
 }
 
 struct FlexWOp // subdomain.okl:229-258
 {
     static constexpr int NV = 1;
     const double *r, *r1, *z, *w;
-    __device__ void vec2(long long i, Acc<1> &a) const
+    template <typename A>
+    __device__ void at(A l, long long i, Acc<1> &acc) const
     {
-        double2 a0 = ld2(r, i), a1 = ld2(r1, i), zz = ld2(z, i), ww = ld2(w, i);
-        a.v[0] += (a1.x - a0.x) * zz.x * ww.x;
-        a.v[0] += (a1.y - a0.y) * zz.y * ww.y;
+        const auto a0 = l.ld(r, i), a1 = l.ld(r1, i), zz = l.ld(z, i), ww = l.ld(w, i);
+        l.add(acc.v[0], (a1 - a0) * zz * ww);
     }
-    __device__ void one(long long i, Acc<1> &a) const { a.v[0] += (r1[i] - r[i]) * z[i] * w[i]; }
+    template <typename F>
+    void pointers(F f) const { f(r), f(r1), f(z), f(w); }
 };
-
-inline bool al2(const void *a, const void *b) { return fdd_aligned16(a) && fdd_aligned16(b); }
 
 // out[i] = sum a * b_i * w for i < M: `a` and `w` are read once for all M dots
 // (the reference launches weighted_inner_product once per pair, subdomain.tpp:4389-4394)
@@ -401,27 +352,23 @@ struct MultiDotWOp
     const double *a, *w;
     const double *b[M];
     const double *bs; // optional: b_k stands for bs[k] * b_k (a Krylov basis kept unnormalised, its 1/norm on the device)
-    __device__ void vec2(long long i, Acc<M> &acc) const
+    template <typename A>
+    __device__ void at(A l, long long i, Acc<M> &acc) const
     {
-        const double2 aa = ld2(a, i), ww = w ? ld2(w, i) : make_double2(1.0, 1.0); // w == NULL: unit weights, not read (x * 1.0 is x)
+        const auto aa = l.ld(a, i), ww = w ? l.ld(w, i) : l.all(1.0); // w == NULL: unit weights, not read (x * 1.0 is x)
 #pragma unroll
         for (int k = 0; k < M; k++)
         {
-            double2 bb = (b[k] == a) ? aa : ld2(b[k], i); // <a, a>: one stream, not two
-            if (bs)
-            {
-                const double sk = bs[k];
-                bb.x = sk * bb.x;
-                bb.y = sk * bb.y;
-            }
-            acc.v[k] += aa.x * bb.x * ww.x;
-            acc.v[k] += aa.y * bb.y * ww.y;
+            auto bb = (b[k] == a) ? aa : l.ld(b[k], i); // <a, a>: one stream, not two
+            if (bs) bb = bs[k] * bb;
+            l.add(acc.v[k], aa * bb * ww);
         }
     }
-    __device__ void one(long long i, Acc<M> &acc) const
+    template <typename F>
+    void pointers(F f) const
     {
-#pragma unroll
-        for (int k = 0; k < M; k++) acc.v[k] += a[i] * (bs ? bs[k] * b[k][i] : b[k][i]) * (w ? w[i] : 1.0);
+        f(a), f(w);
+        for (int k = 0; k < M; k++) f(b[k]);
     }
 };
 
@@ -432,13 +379,8 @@ int launch_multi_dot(double *out, double *ws, const double *a, const double *con
     op.a = a;
     op.w = w;
     op.bs = b_scale_dev;
-    bool al = al2(a, w); // NULL counts as aligned
-    for (int k = 0; k < M; k++)
-    {
-        op.b[k] = b[k];
-        al = al && fdd_aligned16(b[k]);
-    }
-    return launch_reduce(op, out, ws, n, al, stream);
+    for (int k = 0; k < M; k++) op.b[k] = b[k];
+    return launch_reduce(op, out, ws, n, stream);
 }
 
 // Gram-Schmidt update and the norm of its result in one pass:
@@ -454,35 +396,27 @@ struct MultiAxpyNormOp
     const double *x[M];
     const double *xs; // optional per-vector scales: x_k stands for xs[k] * x_k
     double sign;
-    __device__ void vec2(long long i, Acc<1> &acc) const
+    template <typename A>
+    __device__ void at(A l, long long i, Acc<1> &acc) const
     {
-        double2 yy = ld2(y, i);
-        const double2 ww = w ? ld2(w, i) : make_double2(1.0, 1.0);
+        auto yy = l.ld(y, i);
+        const auto ww = w ? l.ld(w, i) : l.all(1.0);
 #pragma unroll
         for (int k = 0; k < M; k++)
         {
             const double ck = sign * c[k];
-            double2 b = ld2(x[k], i);
-            if (xs)
-            {
-                const double sk = xs[k];
-                b.x = sk * b.x;
-                b.y = sk * b.y;
-            }
-            yy.x = 1.0 * yy.x + ck * b.x;
-            yy.y = 1.0 * yy.y + ck * b.y;
+            auto b = l.ld(x[k], i);
+            if (xs) b = xs[k] * b;
+            yy = 1.0 * yy + ck * b;
         }
-        if (dst) reinterpret_cast<double2 *>(dst)[i] = yy; // dst == NULL: only the norm is wanted (the last Arnoldi step of a cycle)
-        acc.v[0] += yy.x * yy.x * ww.x;
-        acc.v[0] += yy.y * yy.y * ww.y;
+        if (dst) l.st(dst, i, yy); // dst == NULL: only the norm is wanted (the last Arnoldi step of a cycle)
+        l.add(acc.v[0], yy * yy * ww);
     }
-    __device__ void one(long long i, Acc<1> &acc) const
+    template <typename F>
+    void pointers(F f) const
     {
-        double v = y[i];
-#pragma unroll
-        for (int k = 0; k < M; k++) v = 1.0 * v + (sign * c[k]) * (xs ? xs[k] * x[k][i] : x[k][i]);
-        if (dst) dst[i] = v;
-        acc.v[0] += v * v * (w ? w[i] : 1.0);
+        f(y), f(w), f(dst);
+        for (int k = 0; k < M; k++) f(x[k]);
     }
 };
 
@@ -496,13 +430,8 @@ int launch_multi_axpy_norm(double *out, double *ws, double *dst, const double *y
     op.c = c;
     op.xs = x_scale_dev;
     op.sign = sign;
-    bool al = al2(y, w) && fdd_aligned16(dst);
-    for (int k = 0; k < M; k++)
-    {
-        op.x[k] = x[k];
-        al = al && fdd_aligned16(x[k]);
-    }
-    return launch_reduce(op, out, ws, n, al, stream);
+    for (int k = 0; k < M; k++) op.x[k] = x[k];
+    return launch_reduce(op, out, ws, n, stream);
 }
 
 // ||Qt_w u||^2 in one pass: per assembled node s = (sum_j 1.0*u[col_j]) * w,
@@ -544,8 +473,6 @@ __global__ __launch_bounds__(kBlock) void gather_norm2_kernel(double *ws, const 
 // float vectors.  Storage is float; products and sums are carried in double (the partial sums of a 10^7-term float
 // dot would lose half their digits in float), the Gram-Schmidt update is rounded to float where it is stored.
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float2 ld2f(const float *p, long long i) { return reinterpret_cast<const float2 *>(p)[i]; }
-
 template <int M>
 struct MultiDotOpF
 {
@@ -553,22 +480,23 @@ struct MultiDotOpF
     const float *a;
     const float *b[M];
     const double *bs;
-    __device__ void vec2(long long i, Acc<M> &acc) const
+    template <typename A>
+    __device__ void at(A l, long long i, Acc<M> &acc) const
     {
-        const float2 aa = ld2f(a, i);
+        const auto aa = l.ld(a, i);
 #pragma unroll
         for (int k = 0; k < M; k++)
         {
-            const float2 bb = (b[k] == a) ? aa : ld2f(b[k], i);
+            const auto bb = (b[k] == a) ? aa : l.ld(b[k], i);
             const double sk = bs ? bs[k] : 1.0;
-            acc.v[k] += (double)aa.x * (sk * (double)bb.x);
-            acc.v[k] += (double)aa.y * (sk * (double)bb.y);
+            l.add(acc.v[k], A::template to<double>(aa) * (sk * A::template to<double>(bb)));
         }
     }
-    __device__ void one(long long i, Acc<M> &acc) const
+    template <typename F>
+    void pointers(F f) const
     {
-#pragma unroll
-        for (int k = 0; k < M; k++) acc.v[k] += (double)a[i] * ((bs ? bs[k] : 1.0) * (double)b[k][i]);
+        f(a);
+        for (int k = 0; k < M; k++) f(b[k]);
     }
 };
 
@@ -578,13 +506,8 @@ int launch_multi_dot_f32(double *out, double *ws, const float *a, const float *c
     MultiDotOpF<M> op;
     op.a = a;
     op.bs = b_scale_dev;
-    bool al = (((uintptr_t)a) & 7) == 0;
-    for (int k = 0; k < M; k++)
-    {
-        op.b[k] = b[k];
-        al = al && ((((uintptr_t)b[k]) & 7) == 0);
-    }
-    return launch_reduce(op, out, ws, n, al, stream);
+    for (int k = 0; k < M; k++) op.b[k] = b[k];
+    return launch_reduce(op, out, ws, n, stream);
 }
 
 template <int M>
@@ -597,31 +520,27 @@ struct MultiAxpyNormOpF
     const double *c;  // coefficients on the device
     const double *xs; // optional scales of the x_k
     double sign;
-    __device__ void vec2(long long i, Acc<1> &acc) const
+    template <typename A>
+    __device__ void at(A l, long long i, Acc<1> &acc) const
     {
-        const float2 yy = ld2f(y, i);
-        double v0 = yy.x, v1 = yy.y;
+        auto v = A::template to<double>(l.ld(y, i));
 #pragma unroll
         for (int k = 0; k < M; k++)
         {
-            const float2 b = ld2f(x[k], i);
+            const auto b = l.ld(x[k], i);
             const double ck = sign * c[k] * (xs ? xs[k] : 1.0);
-            v0 += ck * (double)b.x;
-            v1 += ck * (double)b.y;
+            v = v + ck * A::template to<double>(b);
         }
-        const float2 r = make_float2((float)v0, (float)v1);
-        if (dst) reinterpret_cast<float2 *>(dst)[i] = r;
-        acc.v[0] += (double)r.x * (double)r.x;
-        acc.v[0] += (double)r.y * (double)r.y;
+        const auto rf = A::template to<float>(v);
+        if (dst) l.st(dst, i, rf);
+        const auto rd = A::template to<double>(rf);
+        l.add(acc.v[0], rd * rd);
     }
-    __device__ void one(long long i, Acc<1> &acc) const
+    template <typename F>
+    void pointers(F f) const
     {
-        double v = y[i];
-#pragma unroll
-        for (int k = 0; k < M; k++) v += sign * c[k] * (xs ? xs[k] : 1.0) * (double)x[k][i];
-        const float r = (float)v;
-        if (dst) dst[i] = r;
-        acc.v[0] += (double)r * (double)r;
+        f(y), f(dst);
+        for (int k = 0; k < M; k++) f(x[k]);
     }
 };
 
@@ -634,13 +553,8 @@ int launch_multi_axpy_norm_f32(double *out, double *ws, float *dst, const float 
     op.c = c;
     op.xs = x_scale_dev;
     op.sign = sign;
-    bool al = ((((uintptr_t)y) | ((uintptr_t)dst)) & 7) == 0;
-    for (int k = 0; k < M; k++)
-    {
-        op.x[k] = x[k];
-        al = al && ((((uintptr_t)x[k]) & 7) == 0);
-    }
-    return launch_reduce(op, out, ws, n, al, stream);
+    for (int k = 0; k < M; k++) op.x[k] = x[k];
+    return launch_reduce(op, out, ws, n, stream);
 }
 
 } // namespace
@@ -653,35 +567,35 @@ int fdd_dom_residual_norm(double *out, double *ws, const double *r_k, const doub
 {
     FDD_REQUIRE(out != nullptr && ws != nullptr && num_points >= 0);
     FDD_REQUIRE(num_points == 0 || (r_k != nullptr && QQt_r_k != nullptr && dirichlet_mask != nullptr));
-    return launch_reduce(Dot3Op{r_k, QQt_r_k, dirichlet_mask}, out, ws, num_points, al2(r_k, QQt_r_k) && fdd_aligned16(dirichlet_mask), stream);
+    return launch_reduce(Dot3Op{r_k, QQt_r_k, dirichlet_mask}, out, ws, num_points, stream);
 }
 
 int fdd_dom_inner_product(double *out, double *ws, const double *u_k, const double *v_k, const double *dirichlet_mask, int num_points, void *stream)
 {
     FDD_REQUIRE(out != nullptr && ws != nullptr && num_points >= 0);
     FDD_REQUIRE(num_points == 0 || (u_k != nullptr && v_k != nullptr && dirichlet_mask != nullptr));
-    return launch_reduce(Dot3Op{u_k, v_k, dirichlet_mask}, out, ws, num_points, al2(u_k, v_k) && fdd_aligned16(dirichlet_mask), stream);
+    return launch_reduce(Dot3Op{u_k, v_k, dirichlet_mask}, out, ws, num_points, stream);
 }
 
 int fdd_dom_projection_inner_products(double *out2, double *ws, const double *z_k, const double *r_k, const double *p_k, const double *q_k, int num_points, void *stream)
 {
     FDD_REQUIRE(out2 != nullptr && ws != nullptr && num_points >= 0);
     FDD_REQUIRE(num_points == 0 || (z_k != nullptr && r_k != nullptr && p_k != nullptr && q_k != nullptr));
-    return launch_reduce(ProjOp{z_k, r_k, p_k, q_k}, out2, ws, num_points, al2(z_k, r_k) && al2(p_k, q_k), stream);
+    return launch_reduce(ProjOp{z_k, r_k, p_k, q_k}, out2, ws, num_points, stream);
 }
 
 int fdd_dom_inner_product_flexible(double *out, double *ws, const double *r_k, const double *r_kp1, const double *z_k, int num_points, void *stream)
 {
     FDD_REQUIRE(out != nullptr && ws != nullptr && num_points >= 0);
     FDD_REQUIRE(num_points == 0 || (r_k != nullptr && r_kp1 != nullptr && z_k != nullptr));
-    return launch_reduce(FlexOp{r_k, r_kp1, z_k}, out, ws, num_points, al2(r_k, r_kp1) && fdd_aligned16(z_k), stream);
+    return launch_reduce(FlexOp{r_k, r_kp1, z_k}, out, ws, num_points, stream);
 }
 
 int fdd_dom_inner_product_flexible_gamma(double *out2, double *ws, const double *r_k, const double *r_kp1, const double *z_k, int num_points, void *stream)
 {
     FDD_REQUIRE(out2 != nullptr && ws != nullptr && num_points >= 0);
     FDD_REQUIRE(num_points == 0 || (r_k != nullptr && r_kp1 != nullptr && z_k != nullptr));
-    return launch_reduce(FlexGammaOp{r_k, r_kp1, z_k}, out2, ws, num_points, al2(r_k, r_kp1) && fdd_aligned16(z_k), stream);
+    return launch_reduce(FlexGammaOp{r_k, r_kp1, z_k}, out2, ws, num_points, stream);
 }
 
 int fdd_dom_lincomb_flexible_gamma(double *out2, double *ws, const double *r_k, const double *r_kp1, double *z_k, int num_points, int slice_begin, int slice_size, int z_is_zero, const double *coeffs_dev, const double *const *v, const double *v_scale_dev, const double *last_dev, int m, void *stream)
@@ -690,7 +604,7 @@ int fdd_dom_lincomb_flexible_gamma(double *out2, double *ws, const double *r_k, 
     FDD_REQUIRE(slice_begin >= 0 && slice_size >= 0 && (long long)slice_begin + slice_size <= num_points);
     FDD_REQUIRE(num_points == 0 || (r_k != nullptr && r_kp1 != nullptr && z_k != nullptr));
     FDD_REQUIRE(slice_size == 0 || (coeffs_dev != nullptr && v != nullptr));
-    if (slice_size == 0) return launch_reduce(FlexGammaOp{r_k, r_kp1, z_k}, out2, ws, num_points, al2(r_k, r_kp1) && fdd_aligned16(z_k), stream);
+    if (slice_size == 0) return launch_reduce(FlexGammaOp{r_k, r_kp1, z_k}, out2, ws, num_points, stream);
     for (int k = 0; k < m; k++) FDD_REQUIRE(v[k] != nullptr && v[k] != z_k + slice_begin);
     const bool zero = z_is_zero != 0;
     switch (m)
@@ -710,35 +624,35 @@ int fdd_sub_inner_product(double *out, double *ws, const double *u, const double
 {
     FDD_REQUIRE(out != nullptr && ws != nullptr && num_values >= 0);
     FDD_REQUIRE(num_values == 0 || (u != nullptr && v != nullptr));
-    return launch_reduce(Dot2Op{u, v}, out, ws, num_values, al2(u, v), stream);
+    return launch_reduce(Dot2Op{u, v}, out, ws, num_values, stream);
 }
 
 int fdd_sub_weighted_inner_product(double *out, double *ws, const double *u, const double *v, const double *w, int num_values, void *stream)
 {
     FDD_REQUIRE(out != nullptr && ws != nullptr && num_values >= 0);
     FDD_REQUIRE(num_values == 0 || (u != nullptr && v != nullptr && w != nullptr));
-    return launch_reduce(Dot3Op{u, v, w}, out, ws, num_values, al2(u, v) && fdd_aligned16(w), stream);
+    return launch_reduce(Dot3Op{u, v, w}, out, ws, num_values, stream);
 }
 
 int fdd_sub_projection_inner_products(double *out2, double *ws, const double *z_k, const double *r_k, const double *p_k, const double *q_k, const double *weight, int num_values, void *stream)
 {
     FDD_REQUIRE(out2 != nullptr && ws != nullptr && num_values >= 0);
     FDD_REQUIRE(num_values == 0 || (z_k != nullptr && r_k != nullptr && p_k != nullptr && q_k != nullptr && weight != nullptr));
-    return launch_reduce(ProjWOp{z_k, r_k, p_k, q_k, weight}, out2, ws, num_values, al2(z_k, r_k) && al2(p_k, q_k) && fdd_aligned16(weight), stream);
+    return launch_reduce(ProjWOp{z_k, r_k, p_k, q_k, weight}, out2, ws, num_values, stream);
 }
 
 int fdd_sub_search_update_inner_product(double *out, double *ws, const double *r_k, const double *r_kp1, const double *z_k, const double *weight, int num_points, void *stream)
 {
     FDD_REQUIRE(out != nullptr && ws != nullptr && num_points >= 0);
     FDD_REQUIRE(num_points == 0 || (r_k != nullptr && r_kp1 != nullptr && z_k != nullptr && weight != nullptr));
-    return launch_reduce(FlexWOp{r_k, r_kp1, z_k, weight}, out, ws, num_points, al2(r_k, r_kp1) && al2(z_k, weight), stream);
+    return launch_reduce(FlexWOp{r_k, r_kp1, z_k, weight}, out, ws, num_points, stream);
 }
 
 int fdd_amg_dot(double *out, double *ws, const double *x, const double *y, int size, void *stream)
 {
     FDD_REQUIRE(out != nullptr && ws != nullptr && size >= 0);
     FDD_REQUIRE(size == 0 || (x != nullptr && y != nullptr));
-    return launch_reduce(Dot2Op{x, y}, out, ws, size, al2(x, y), stream);
+    return launch_reduce(Dot2Op{x, y}, out, ws, size, stream);
 }
 
 int fdd_multi_weighted_inner_product(double *out, double *ws, const double *a, const double *const *b, int m, const double *w, int n, void *stream)
