@@ -180,6 +180,16 @@ int fdd_dom_residual_and_search_update(double *p_k, double *r_k, const double *z
  *   alpha = num[0] / den[0];   beta = num[0] / den[0]. */
 int fdd_dom_solution_and_residual_update_dev(double *u_k, double *r_kp1, const double *r_k, const double *p_k, const double *q_k, const double *alpha_num, const double *alpha_den, int num_points, void *stream);
 int fdd_dom_residual_and_search_update_dev(double *p_k, double *r_k, const double *z_k, const double *r_kp1, const double *beta_num, const double *beta_den, int num_points, void *stream);
+/* The residual half of fdd_dom_solution_and_residual_update_dev alone, r_kp1 = r_k - alpha q_k over all num_points, and of
+ * the values it stores the sum of squares over the slice [slice_begin, slice_begin + slice_size), in ONE pass: out[0] has
+ * the bits of fdd_multi_weighted_inner_product_scaled(out, ws, r_kp1 + slice_begin, {r_kp1 + slice_begin}, NULL, 1, NULL,
+ * slice_size) run afterwards (its grid, its choice of path by the alignment of r_kp1 + slice_begin, its lanes counted
+ * from the slice start), without r_kp1 being read back.  r_kp1 may be r_k. */
+int fdd_dom_residual_update_norm2_dev(double *out, double *ws, double *r_kp1, const double *r_k, const double *q_k, const double *alpha_num, const double *alpha_den, int num_points, int slice_begin, int slice_size, void *stream);
+/* The solution half of fdd_dom_solution_and_residual_update_dev and fdd_xpby_ratio_dev(p_k, z_k, beta_num, beta_den, p_k)
+ * with p_k loaded once: u_k += alpha p_k, then p_k = z_k + beta p_k, both from the old p_k.  Same bits as the two entries.
+ * u_k, p_k and z_k are distinct vectors. */
+int fdd_dom_solution_direction_update_dev(double *u_k, double *p_k, const double *z_k, const double *alpha_num, const double *alpha_den, const double *beta_num, const double *beta_den, int num_points, void *stream);
 
 /* ------------------------------------------------------------------ */
 /* subdomain.okl -- FDD local-solve kernels                             */

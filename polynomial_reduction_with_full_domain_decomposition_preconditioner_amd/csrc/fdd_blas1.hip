@@ -161,6 +161,25 @@ struct XmayRatioDevOp
     void pointers(F f) const { f(out), f(x), f(y); }
 };
 
+// u = u + (*a_num / *a_den) * p and p = z + (*b_num / *b_den) * p with p loaded once: the solution update of UpdateUROp
+// (domain.okl:186-193), which nothing reads before the end of a solve, carried by the direction update that reads p anyway
+// (XpbyRatioDevOp above, out == y == p).  Both expressions are those ops' own, so u and p keep their bits.
+struct SolutionDirectionDevOp
+{
+    double *u, *p;
+    const double *z, *a_num, *a_den, *b_num, *b_den;
+    template <typename A>
+    __device__ void at(A a, long long i) const
+    {
+        const double al = a_num[0] / a_den[0];
+        const auto uu = a.ld(u, i), pp = a.ld(p, i), zz = a.ld(z, i);
+        a.st(u, i, uu + al * pp);
+        a.st(p, i, zz + (*b_num / *b_den) * pp);
+    }
+    template <typename F>
+    void pointers(F f) const { f(u), f(p), f(z); }
+};
+
 struct ChebyStepOp // fdd_cheby_step_at (fdd_stream.h)
 {
     double *x, *d, *r_out;
@@ -559,6 +578,14 @@ int fdd_xmay_ratio_dev(double *out, const double *x, const double *num_dev, cons
     if (n == 0) return 0;
     FDD_REQUIRE(out != nullptr && x != nullptr && y != nullptr && num_dev != nullptr && den_dev != nullptr);
     return launch_ew(XmayRatioDevOp{out, x, y, num_dev, den_dev}, n, stream);
+}
+
+int fdd_dom_solution_direction_update_dev(double *u_k, double *p_k, const double *z_k, const double *alpha_num, const double *alpha_den, const double *beta_num, const double *beta_den, int num_points, void *stream)
+{
+    FDD_REQUIRE(num_points >= 0);
+    if (num_points == 0) return 0;
+    FDD_REQUIRE(u_k != nullptr && p_k != nullptr && z_k != nullptr && u_k != p_k && alpha_num != nullptr && alpha_den != nullptr && beta_num != nullptr && beta_den != nullptr);
+    return launch_ew(SolutionDirectionDevOp{u_k, p_k, z_k, alpha_num, alpha_den, beta_num, beta_den}, num_points, stream);
 }
 
 int fdd_vector_scaling_dev(double *au, const double *scale_dev, const double *u, int n, void *stream)

@@ -434,6 +434,64 @@ int launch_multi_axpy_norm(double *out, double *ws, double *dst, const double *y
     return launch_reduce(op, out, ws, n, stream);
 }
 
+// r1 = r - (*num / *den) * q over all n nodes (UpdateUROp's residual statement, fdd_blas1.hip) and, of the values it stores,
+// the sum of squares over the slice [lo, lo + nd): MultiDotWOp<1> with b[0] == a and unit weights on r1 + lo, without
+// reading r1 back.  Unlike LincombFlexGammaOp, whose pairs are the whole vector's, the traversal here is the SLICE's: the
+// sum has the bits of launch_reduce(MultiDotWOp<1>{r1 + lo, ...}, nd) only if grid, path (pairs where r1 + lo is aligned
+// for them and nd >= 2) and lane-to-element assignment are that launch's, counted from the slice start.  at() is the
+// operation on element i of accessor l of the vectors `from` elements further on; it returns what it stored.
+struct ResidualUpdateNormOp
+{
+    double *r1;
+    const double *r, *q, *num, *den;
+    template <typename A>
+    __device__ typename A::template value<double> at(A l, long long from, long long i, bool wide_loads = true) const
+    {
+        const double al = num[0] / den[0];
+        typename A::template value<double> rr, qq;
+        if constexpr (std::is_same<A, Pair>::value)
+        {
+            if (wide_loads)
+                rr = l.ld(r + from, i), qq = l.ld(q + from, i);
+            else // r or q is not aligned for pairs where r1 is: the same two elements, loaded one by one
+            {
+                rr = {__builtin_nontemporal_load(r + from + 2 * i), __builtin_nontemporal_load(r + from + 2 * i + 1)};
+                qq = {__builtin_nontemporal_load(q + from + 2 * i), __builtin_nontemporal_load(q + from + 2 * i + 1)};
+            }
+        }
+        else
+            rr = l.ld(r + from, i), qq = l.ld(q + from, i);
+        const auto v = rr - al * qq;
+        l.st(r1 + from, i, v);
+        return v;
+    }
+    template <typename A, typename V>
+    static __device__ __forceinline__ void add(A l, Acc<1> &acc, V v) { l.add(acc.v[0], v * v * l.all(1.0)); }
+};
+
+template <bool PAIRS>
+__global__ __launch_bounds__(kBlock) void residual_update_norm_kernel(ResidualUpdateNormOp op, double *ws, long long lo, long long nd, long long n, bool wide_loads)
+{
+    Acc<1> a;
+    a.v[0] = 0.0;
+    const long long stride = (long long)gridDim.x * kBlock;
+    const long long first = (long long)blockIdx.x * kBlock + threadIdx.x;
+    // the slice, as reduce_vec2_kernel / reduce_scalar_kernel walk a vector that starts at lo
+    if constexpr (PAIRS)
+    {
+        const long long nd2 = nd / 2;
+        for (long long i = first; i < nd2; i += stride) ResidualUpdateNormOp::add(Pair{}, a, op.at(Pair{}, lo, i, wide_loads));
+        if ((nd & 1) && first == 0) ResidualUpdateNormOp::add(Single{}, a, op.at(Single{}, lo, nd - 1));
+    }
+    else
+        for (long long i = first; i < nd; i += stride) ResidualUpdateNormOp::add(Single{}, a, op.at(Single{}, lo, i));
+    // the nodes in front of and behind the slice: updated, in no sum
+    for (long long i = first; i < lo; i += stride) op.at(Single{}, 0, i);
+    for (long long i = lo + nd + first; i < n; i += stride) op.at(Single{}, 0, i);
+
+    block_reduce_store<1>(a, ws, FDD_REDUCE_MAX_BLOCKS);
+}
+
 // ||Qt_w u||^2 in one pass: per assembled node s = (sum_j 1.0*u[col_j]) * w,
 // accumulate s*s*w -- the gather of multiply_weight (csr_matrix.okl:35-48) and
 // the weighted_inner_product (subdomain.okl:134-163) of Subdomain::residual_norm
@@ -618,6 +676,36 @@ int fdd_dom_lincomb_flexible_gamma(double *out2, double *ws, const double *r_k, 
     case 7: return launch_lincomb_flex_gamma<7>(out2, ws, r_k, r_kp1, z_k, num_points, slice_begin, slice_size, zero, coeffs_dev, v, v_scale_dev, last_dev, stream);
     default: return launch_lincomb_flex_gamma<8>(out2, ws, r_k, r_kp1, z_k, num_points, slice_begin, slice_size, zero, coeffs_dev, v, v_scale_dev, last_dev, stream);
     }
+}
+
+int fdd_dom_residual_update_norm2_dev(double *out, double *ws, double *r_kp1, const double *r_k, const double *q_k, const double *alpha_num, const double *alpha_den, int num_points, int slice_begin, int slice_size, void *stream)
+{
+    FDD_REQUIRE(out != nullptr && ws != nullptr && num_points >= 0);
+    FDD_REQUIRE(slice_begin >= 0 && slice_size >= 0 && (long long)slice_begin + slice_size <= num_points);
+    FDD_REQUIRE(num_points == 0 || (r_kp1 != nullptr && r_k != nullptr && q_k != nullptr && alpha_num != nullptr && alpha_den != nullptr));
+    hipStream_t s = fdd_stream(stream);
+    const ResidualUpdateNormOp op{r_kp1, r_k, q_k, alpha_num, alpha_den};
+    const long long lo = slice_begin, nd = slice_size, n = num_points;
+    // the norm's own launch on r_kp1 + lo (launch_reduce): path, grid, and an empty sum as a cleared scalar
+    const bool pairs = nd >= 2 && fdd_aligned(r_kp1 + lo, Pair::bytes<double>);
+    const bool wide_loads = fdd_aligned(r_k + lo, Pair::bytes<double>) && fdd_aligned(q_k + lo, Pair::bytes<double>);
+    if (nd == 0)
+    {
+        if (hipError_t e = hipMemsetAsync(out, 0, sizeof(double), s)) return (int)e;
+        if (n == 0) return 0;
+        hipLaunchKernelGGL(residual_update_norm_kernel<false>, dim3(fdd_stream_grid(n, kBlock)), dim3(kBlock), 0, s, op, ws, lo, nd, n, wide_loads);
+        FDD_LAUNCH_CHECK();
+        return 0;
+    }
+    const int grid = fdd_stream_grid(pairs ? nd / 2 : nd, kBlock);
+    if (pairs)
+        hipLaunchKernelGGL(residual_update_norm_kernel<true>, dim3(grid), dim3(kBlock), 0, s, op, ws, lo, nd, n, wide_loads);
+    else
+        hipLaunchKernelGGL(residual_update_norm_kernel<false>, dim3(grid), dim3(kBlock), 0, s, op, ws, lo, nd, n, wide_loads);
+    FDD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(reduce_final_kernel<1>, dim3(1), dim3(kBlock), 0, s, out, ws, grid);
+    FDD_LAUNCH_CHECK();
+    return 0;
 }
 
 int fdd_sub_inner_product(double *out, double *ws, const double *u, const double *v, int num_values, void *stream)

@@ -162,6 +162,15 @@ class Domain
         const double *pending_rhs_norm2 = nullptr; // what node_norm_enqueue returned for the residual the next precondition_nodes call receives
         bool gamma_on_device = false;
         int gamma_slot = SLOT_GAMMA; // where the current gamma sits in `scalars`
+        // u~ += alpha p~ of the iteration whose residual half ran last, not launched yet (solution_in_direction_pass): the
+        // direction half carries it in the pass that reads p~ anyway, and whatever reads u~ before that flushes it first
+        // (fcg_flush_solution_update).  alpha = *num / *den, both still in `scalars` until the direction half has run
+        struct OwedSolutionUpdate
+        {
+            bool active = false;
+            const double *num = nullptr, *den = nullptr;
+        };
+        OwedSolutionUpdate owed_u;
     };
     FcgRun fcg;
 
@@ -498,6 +507,8 @@ class Domain
     bool shared_residual_norm = true; // one rank: the outer residual norm and the inner solve's first norm are the same sum over the dof slice, formed once (the iterates keep their bits; the recorded norm groups its terms differently)
     bool early_gamma = true;      // device scalars: the flexible dot also forms the next iteration's gamma = <z, r+> (same bits; the projection kernel is left with <p, q>)
     bool fused_update_flexible_dot = true; // one rank, z~ written in place, early_gamma: the inner solve's final update of z~ is formed inside the flexible dot's pass (same bits; 0: a kernel of its own in front of the dot)
+    bool fused_residual_norm = true; // one rank, the norm is the dof slice's plain sum (shared_residual_norm): r+ = r - alpha q sums the squares of what it stores (same bits; 0: the norm reads r+ back)
+    bool solution_in_direction_pass = true; // device scalars: u~ += alpha p~ rides in the pass of p~ = z~ + beta p~, which loads p~ once for both (same bits; 0: in the residual update's pass)
     bool unit_stitch_in_place = true; // stitching weights of the dof slice all exactly 1 (one rank): the inner solve writes z~ in place (0: the multiplication by the ones, the reference's sequence)
     fdd::StiffnessFlags stiffness; // which kernel the element operator runs (element_operator.hpp)
     DType tolerance = 1.0e-07;
@@ -1007,6 +1018,15 @@ class Domain
         fdd::apply_gather(list, q.as<double>(), pn.as<double>(), point_node_dev.as<int>(), nullptr, num_local_nodes, stiffness);
     }
 
+    // whether node_norm_enqueue forms the norm as the plain sum over the dof slice (and returns its address)
+    bool norm_is_slice_sum() const
+    {
+        const bool multi = fdd::comm().size > 1 and num_interface_slots > 0;
+        // (only with the inner solve to share it with: without a preconditioner the norm keeps its masked form, whether or not
+        // an earlier solve of this problem set the dof maps up)
+        return not multi and norm_on_dof_slice and shared_residual_norm and use_preconditioner;
+    }
+
     // sqrt(<r, QQt r>) (domain.tpp:916-931) from r^ = Qt r: sum_n r^_n * gs(r^)_n * mask_n.
     // Two halves: the reductions (+ all-reduce) are enqueued into scalars[SLOT_NORM..]; the value is
     // fetched when the host wants it, which may be after more work has been enqueued.
@@ -1040,9 +1060,7 @@ class Domain
             return nullptr;
         }
         const double *known = nullptr;
-        // (only with the inner solve to share it with: without a preconditioner the norm keeps its masked form, whether or not
-        // an earlier solve of this problem set the dof maps up)
-        if (norm_on_dof_slice and shared_residual_norm and use_preconditioner)
+        if (norm_is_slice_sum())
         {
             // One rank, mask = 1 on the dof slice and 0 elsewhere: the masked sum over the nodes IS the plain sum over the
             // slice -- the sum the inner solve forms first (its right-hand side is this slice, read in place).  Formed once,
@@ -1061,6 +1079,18 @@ class Domain
         norm_state.parts = 1;
         if (fdd::comm().size > 1) fdd::comm().allreduce_sum(out, norm_state.parts);
         return known;
+    }
+
+    // rn1 = rn - (*num / *den) qn with node_norm_enqueue(rn1)'s slice sum formed from the values as they are stored (flag
+    // "fused_residual_norm"): that call's sum to the bit, without its pass over rn1.  Only where norm_is_slice_sum().
+    const double *residual_update_and_norm_enqueue(fdd::memory &rn1, fdd::memory &rn, fdd::memory &qn, const double *num, const double *den)
+    {
+        const int nn = num_local_nodes;
+        double *out = scalars.as<double>() + SLOT_NORM;
+        fdd::ProfileScope prof("residual_update_norm_kernel", 24.0 * nn);
+        FDD_CALL(fdd_dom_residual_update_norm2_dev(out, reduce_ws.as<double>(), rn1.as<double>(), rn.as<double>(), qn.as<double>(), num, den, nn, dof_shift, nodes_sub_dofs, fdd::dev().stream));
+        norm_state.parts = 1;
+        return out;
     }
 
     // the boundary part of the norm once the saved prefix has been exchanged, then the all-reduce of both parts
@@ -1200,6 +1230,8 @@ class Domain
         void *stream = fdd::dev().stream;
         DType values[2], r_norm;
 
+        fcg_flush_solution_update(); // a residual half that follows another: alpha's operands are about to be overwritten
+
         fdd_timer().start("domain.operator_application");
         stiffness_from_nodes(q_k, np);
         gather_nodes(nq, q_k);
@@ -1221,10 +1253,28 @@ class Domain
         {
             // gamma = scalars[fcg.gamma_slot] (kept for beta), theta = scalars[SLOT_PQ]: alpha never visits the host
             if (not(fcg.gamma_on_device and early_gamma)) fcg.gamma_slot = 0; // the projection kernel has just written it
-            FDD_CALL(fdd_dom_solution_and_residual_update_dev(nu.as<double>(), nr1.as<double>(), nr.as<double>(), np.as<double>(), nq.as<double>(), scalars.as<double>() + fcg.gamma_slot, scalars.as<double>() + SLOT_PQ, nn, stream));
+            const double *a_num = scalars.as<double>() + fcg.gamma_slot, *a_den = scalars.as<double>() + SLOT_PQ;
+            // u~ += alpha p~ is left to the direction half, which reads p~ anyway (nothing reads u~ before the solve ends)
+            const bool defer_u = solution_in_direction_pass and &fdd_dom_solution_direction_update_dev != nullptr;
+            // the norm of r+ over the dof slice is summed where r+ is stored
+            const bool fuse_norm = fused_residual_norm and &fdd_dom_residual_update_norm2_dev != nullptr and norm_is_slice_sum();
+            if (not defer_u and not fuse_norm)
+                FDD_CALL(fdd_dom_solution_and_residual_update_dev(nu.as<double>(), nr1.as<double>(), nr.as<double>(), np.as<double>(), nq.as<double>(), a_num, a_den, nn, stream));
+            else
+            {
+                // the two statements of that kernel, each where it costs least
+                if (defer_u)
+                    fcg.owed_u = {true, a_num, a_den};
+                else
+                    FDD_CALL(fdd_xpby_ratio_dev(nu.as<double>(), nu.as<double>(), a_num, a_den, np.as<double>(), nn, stream));
+                if (fuse_norm)
+                    fcg.pending_rhs_norm2 = residual_update_and_norm_enqueue(nr1, nr, nq, a_num, a_den);
+                else
+                    FDD_CALL(fdd_xmay_ratio_dev(nr1.as<double>(), nr.as<double>(), a_num, a_den, nq.as<double>(), nn, stream));
+            }
             if (use_preconditioner and composite_precond) // r+ = r - alpha q on the points too (domain.okl:191), alpha from device memory
-                FDD_CALL(fdd_xmay_ratio_dev(rp.as<double>(), rp.as<double>(), scalars.as<double>() + fcg.gamma_slot, scalars.as<double>() + SLOT_PQ, q_k.as<double>(), num_local_points, stream));
-            fcg.pending_rhs_norm2 = node_norm_enqueue(nr1, /*defer_exchange=*/true); // finished inside the preconditioner's exchange
+                FDD_CALL(fdd_xmay_ratio_dev(rp.as<double>(), rp.as<double>(), a_num, a_den, q_k.as<double>(), num_local_points, stream));
+            if (not fuse_norm) fcg.pending_rhs_norm2 = node_norm_enqueue(nr1, /*defer_exchange=*/true); // finished inside the preconditioner's exchange
             fcg.norm_pending = true;
             return std::numeric_limits<DType>::quiet_NaN(); // fcg_nodes_norm() has the value
         }
@@ -1300,7 +1350,7 @@ class Domain
                 }
                 norm_state.reduce_pending = false;
                 // p = z + beta p; "r = r+" (domain.okl:226-233) is a swap of the two node vectors, not a copy
-                FDD_CALL(fdd_xpby_ratio_dev(np.as<double>(), nz.as<double>(), scalars.as<double>() + theta_at, scalars.as<double>() + fcg.gamma_slot, np.as<double>(), nn, fdd::dev().stream));
+                direction_update_dev(scalars.as<double>() + theta_at, scalars.as<double>() + fcg.gamma_slot);
                 fcg.gamma_slot = next;
             }
             else
@@ -1308,7 +1358,7 @@ class Domain
                 FDD_CALL(fdd_dom_inner_product_flexible(scalars.as<double>() + SLOT_THETA, reduce_ws.as<double>(), nr.as<double>(), nr1.as<double>(), nz.as<double>(), nn, fdd::dev().stream));
                 if (fdd::comm().size > 1) fdd::comm().allreduce_sum(scalars.as<double>() + SLOT_THETA, norm_state.reduce_pending ? 3 : 1);
                 norm_state.reduce_pending = false;
-                FDD_CALL(fdd_xpby_ratio_dev(np.as<double>(), nz.as<double>(), scalars.as<double>() + SLOT_THETA, scalars.as<double>() + fcg.gamma_slot, np.as<double>(), nn, fdd::dev().stream));
+                direction_update_dev(scalars.as<double>() + SLOT_THETA, scalars.as<double>() + fcg.gamma_slot);
             }
             fcg.gamma_on_device = early_gamma;
             std::swap(nr, nr1);
@@ -1316,6 +1366,7 @@ class Domain
         else
         {
             fcg.gamma_on_device = false;
+            fcg_flush_solution_update(); // (device_scalars was cleared between the halves: p~ changes below)
             FDD_CALL(fdd_dom_inner_product_flexible(scalars.as<double>(), reduce_ws.as<double>(), nr.as<double>(), nr1.as<double>(), nz.as<double>(), nn, fdd::dev().stream));
             fetch_scalars(&theta_k, 1);
             const DType beta_k = theta_k / fcg.gamma_k;
@@ -1331,10 +1382,35 @@ class Domain
         fcg.iter++;
     }
 
+    // p~ = z~ + beta p~, beta = *b_num / *b_den, and with it the solution update the residual half left owed
+    void direction_update_dev(const double *b_num, const double *b_den)
+    {
+        const int nn = num_local_nodes;
+        if (fcg.owed_u.active)
+        {
+            // alpha's operands (the current gamma and <p, q>) are still in their slots: gamma_slot only advances behind this pass
+            fdd::ProfileScope prof("ew_kernel<SolutionDirectionDev>", 40.0 * nn);
+            FDD_CALL(fdd_dom_solution_direction_update_dev(nu.as<double>(), np.as<double>(), nz.as<double>(), fcg.owed_u.num, fcg.owed_u.den, b_num, b_den, nn, fdd::dev().stream));
+            fcg.owed_u.active = false;
+        }
+        else
+            FDD_CALL(fdd_xpby_ratio_dev(np.as<double>(), nz.as<double>(), b_num, b_den, np.as<double>(), nn, fdd::dev().stream));
+    }
+
+    // the owed solution update as a launch of its own (the statement of the kernel it was taken out of): in front of whatever
+    // reads u~, or overwrites p~ or alpha's operands, while it is owed
+    void fcg_flush_solution_update()
+    {
+        if (not fcg.owed_u.active) return;
+        FDD_CALL(fdd_xpby_ratio_dev(nu.as<double>(), nu.as<double>(), fcg.owed_u.num, fcg.owed_u.den, np.as<double>(), num_local_nodes, fdd::dev().stream));
+        fcg.owed_u.active = false;
+    }
+
     // u = Q u~: hand the solution back on the element-local points
     void fcg_finish()
     {
         if (not fcg.nodes_active) return;
+        fcg_flush_solution_update();
         Q.multiply(fcg.u_pts, nu);
     }
 
@@ -1497,7 +1573,9 @@ class Domain
             {
                 // device_scalars: the second half of the iteration is enqueued before the host reads
                 // the norm.  If the tests below stop the solve, that half was speculative: it touched
-                // z, p, r only, never the solution, and its iteration count is taken back.
+                // z, p, r and, of the solution, only the update it owed to the iteration whose residual
+                // has just been tested (solution_in_direction_pass) -- the solution returned is that
+                // iteration's either way -- and its iteration count is taken back.
                 fcg_step_direction(subdomain);
                 direction_done = true;
                 fcg.iter--;
@@ -1590,6 +1668,7 @@ class Domain
 
         fdd_timer().start("domain.vector_operations");
         gather_nodes(nf, f); // f^ = Qt f
+        fcg.owed_u.active = false; // u~ is this solve's from here on
         FDD_CALL(fdd_set_to_value(nu.as<double>(), 0.0, nn, 0, stream));
         nr.copyFrom(nf, (size_t)nn * sizeof(DType));
         if (points_too) VP[0].copyFrom(f, (size_t)num_local_points * sizeof(DType));

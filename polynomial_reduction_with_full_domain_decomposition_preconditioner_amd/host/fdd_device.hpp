@@ -42,6 +42,10 @@
 #pragma weak fdd_amg_setup_memory_info
 // likewise the fused update-and-dot entry: without it the update and the dot stay two launches (Domain::fcg_nodes_step_direction)
 #pragma weak fdd_dom_lincomb_flexible_gamma
+// and the two passes of the outer step that carry a neighbour's work: without them the residual update, its norm, the solution
+// update and the direction update stay the launches they were (Domain::fcg_nodes_step_residual / _direction)
+#pragma weak fdd_dom_residual_update_norm2_dev
+#pragma weak fdd_dom_solution_direction_update_dev
 // and the projection passes: without them the same steps are composed from the multi-vector entries (projection.hpp), and the
 // flag "fused_projection" refuses to be set to 1, naming the missing entry (missing_projection_entry)
 #pragma weak fdd_projection_dots

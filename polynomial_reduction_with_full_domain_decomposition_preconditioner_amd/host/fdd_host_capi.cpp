@@ -1007,6 +1007,10 @@ static const PlainFlagRow *plain_flag_row(const std::string &flag)
         {"early_gamma", &D::early_gamma, nullptr},
         {"unit_stitch_in_place", &D::unit_stitch_in_place, nullptr},
         {"fused_update_flexible_dot", &D::fused_update_flexible_dot, nullptr},
+        // the outer step's passes that carry a neighbour's work (Domain::fcg_nodes_step_residual / _direction); each falls back
+        // to the launches it replaces where the kernel library lacks its entry or its conditions do not hold
+        {"fused_residual_norm", &D::fused_residual_norm, nullptr},
+        {"solution_in_direction_pass", &D::solution_in_direction_pass, nullptr},
         {"lazy_steps", &D::lazy_steps, nullptr},
         {"device_bookkeeping", &D::device_scalars, &S::device_bookkeeping},
         {"assembled_inner_solve", nullptr, &S::assembled_inner},
