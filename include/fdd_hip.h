@@ -486,6 +486,17 @@ int fdd_stiffness_factor_block_verify(int *mismatches, const double *const G[FDD
 int fdd_field_mass(double *mass, const double *const xyz[3], const double *D_hat, const double *gll_weights, int num_elements, int poly_degree, void *stream);
 int fdd_field_gradient(double *const grad[3], const double *u, const double *const xyz[3], const double *D_hat, int num_elements, int poly_degree, void *stream);
 int fdd_field_weak_divergence(double *out, const double *const v[3], const double *const xyz[3], const double *D_hat, const double *gll_weights, int num_elements, int poly_degree, void *stream);
+/* The zeroth-order term of -laplace(u) + lambda u on assembled vectors (an option of this build; csrc/fdd_helmholtz.hip):
+ *   y[i] = y[i] + c[i] * x[i]          x[i] standing for (*scale_dev) * x[i] where scale_dev is given (the _f32 entry rounds
+ *                                      the factor to float first, as fdd_vector_scaling_dev_f32 does)
+ * behind the operator application that formed y; multiply, then add, at every width.  The inner-product entry stores the
+ * same update and returns sum x[i] * y_new[i] through the reduction workspace (fdd_reduce_workspace_doubles): what
+ * fdd_sub_inner_product(x, y) would read back.  16-byte lanes where y, c and x are all 16-byte aligned, one element per
+ * lane otherwise; deterministic for given n and alignment.  y must overlap neither c nor x (FDD_ERR_INVALID_ARGUMENT);
+ * a call that is refused touches no output; n = 0 stores nothing (the sum is 0). */
+int fdd_shift_add(double *y, const double *c, const double *scale_dev, const double *x, int n, void *stream);
+int fdd_shift_add_f32(float *y, const float *c, const double *scale_dev, const float *x, int n, void *stream);
+int fdd_shift_add_inner_product(double *out, double *ws, double *y, const double *c, const double *x, int n, void *stream);
 int fdd_stiffness_matrix_affine_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *elem_factors, const float *gll_weights, const int *elem_offset, int num_elements, int poly_degree, void *stream);
 int fdd_sub_stiffness_matrix_gather_scaled_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream);
 int fdd_multi_inner_product_scaled_f32(double *out, double *ws, const float *a, const float *const *b, const double *b_scale_dev, int m, int n, void *stream); /* out[k] = sum a * (s_k b_k), k < m <= 8 */

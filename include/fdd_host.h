@@ -357,6 +357,29 @@ int fddh_field_mass(fddh_problem *p, double *mass);
 int fddh_field_gradient(fddh_problem *p, const double *u, double *gx, double *gy, double *gz, int average);
 int fddh_field_weak_divergence(fddh_problem *p, const double *vx, const double *vy, const double *vz, double *out);
 
+/* ---- Helmholtz solves: (-laplace + lambda) u = f (an option of this build; the reference solves the Poisson problem) ----
+ * A shift is a constant lambda >= 0 or, lambda_points != NULL, a value >= 0 per point of the fine level (all finite).  It is
+ * kept as one node vector, cbar[n] = sum over the copies p of node n of lambda_p * B_p (B: fddh_field_mass; the products in
+ * double on the host, summed in the column order of the row of the gather matrix, fddh_problem_csr(1)), which the outer
+ * solve adds behind its operator application (q^ += cbar .* p~) and the inner solve, renumbered to its dofs, behind its
+ * own; the exact diagonal of the inner operator, the Chebyshev-Jacobi bound and a hierarchy built by fddh_problem_amg_build
+ * (built again, on the host, with cbar on the diagonal of its level-0 matrix) follow, a hierarchy that was handed in does
+ * not.  An all-zero shift switches the term off: every solve then has the bits it had before a shift was ever set.
+ * fddh_problem_solve / _solve_timed / _pcg_* / _precond_apply / _sub_dof_op / _sub_jacobi_diagonal / _sub_dof_solve follow a
+ * set shift; the right-hand side of a manufactured solution is stiffness(u*) + lambda B u*, formed by the caller.
+ * Refused, the problem staying usable: more than one rank, a composite Subdomain, a 2-D problem, poly_degree > 15, a kernel
+ * library without fdd_shift_add / _f32 / _inner_product or fdd_field_mass (naming the entry); and, when it starts, a solve
+ * that would not run the node-space outer loops and the dof-space inner operator (point-space outer forms, the inner FCG,
+ * assembled_inner_solve = 0, device_bookkeeping = 0), and fddh_problem_solve_projected.
+ *   info           whether a shift is set, and the smallest and largest lambda it was made from
+ *   shift          cbar on the rank's nodes (zeros when none is set)
+ *   node_operator  q^ = (Qt A_L Q + diag(cbar)) v~ on node vectors and vq = <v~, q^>: the launches of the outer flexible CG's
+ *                  operator application and of the dot behind it (gather-form stiffness, gather, fused shift-and-dot) */
+int fddh_helmholtz_set(fddh_problem *p, double lambda, const double *lambda_points /* NULL: the constant */);
+int fddh_helmholtz_info(fddh_problem *p, int *active, double *min, double *max);
+int fddh_helmholtz_shift(fddh_problem *p, double *cbar_nodes, int n);
+int fddh_helmholtz_node_operator(fddh_problem *p, const double *v_nodes, double *q_nodes, int n, double *vq);
+
 /* Outer solve: solver_id 0 = flexible_conjugate_gradient, 1 = generalized_minimum_residual
  * (poisson.cpp:224-231).  history receives the residual norms the reference
  * prints (iteration 0 first). */

@@ -1018,6 +1018,60 @@ class Domain
         fdd::apply_gather(list, q.as<double>(), pn.as<double>(), point_node_dev.as<int>(), nullptr, num_local_nodes, stiffness);
     }
 
+    // ---- Helmholtz shift: the node-space outer operator is Qt A_L Q + diag(c) -- a LABELLED OPTION of this build ----
+    // c[n] = sum over the copies p of node n of lambda_p B_p (B: the diagonal mass matrix, fdd_field_mass): the products in
+    // double on the host, summed in the column order of Qt's row.  Like r^ and q^ it is this rank's partial sum; p~ is
+    // continuous, so q^ += c .* p~ behind the gather is the whole term (one rank: the C API refuses the others).  Not inside
+    // the stiffness kernels: there the term would be lambda_p B_p u_p per point, two more streams in the kernel that is
+    // closest to its register and LDS limits, in every instance of it; on the assembled vectors it is one stream and no
+    // stiffness kernel changes.  lambda_B == nullptr or all zero: off.
+    std::vector<DType> shift_nodes_hst;
+    fdd::memory shift_nodes;
+    bool shift_active() const { return not shift_nodes_hst.empty(); }
+    void set_shift(const DType *lambda_B)
+    {
+        shift_nodes.free();
+        shift_nodes_hst.clear();
+        if (lambda_B == nullptr) return;
+        std::vector<DType> c((size_t)num_local_nodes, 0.0);
+        bool any = false;
+        for (int n = 0; n < num_local_nodes; n++)
+        {
+            DType s = 0.0;
+            for (int t = Qt.ptr_hst[n]; t < Qt.ptr_hst[n + 1]; t++) s += lambda_B[Qt.col_hst[t]];
+            c[n] = s;
+            any = any or s != 0.0;
+        }
+        if (not any) return;
+        shift_nodes_hst = std::move(c);
+        shift_nodes = fdd::dev().malloc<DType>(shift_nodes_hst.size());
+        shift_nodes.copyFrom(shift_nodes_hst.data(), shift_nodes_hst.size() * sizeof(DType));
+    }
+    // q^ += c .* p~ behind stiffness_from_nodes + gather_nodes
+    void shift_add_nodes(fdd::memory &qn, fdd::memory &pn)
+    {
+        if (shift_active()) FDD_CALL(fdd_shift_add(qn.as<double>(), shift_nodes.as<double>(), nullptr, pn.as<double>(), num_local_nodes, fdd::dev().stream));
+    }
+
+    // q^ = (Qt A_L Q + diag(c)) v~ on the caller's node vectors and <v~, q^>: the launches of fcg_nodes_step_residual's
+    // operator application and of the dot behind it, in their order (a test sees what the outer step computes)
+    DType node_operator(fdd::memory &qn, fdd::memory &vn)
+    {
+        setup_nodes();
+        fcg_flush_solution_update(); // a stepwise solve in progress may still owe an update whose alpha sits in the slot written below
+        void *stream = fdd::dev().stream;
+        double *out = scalars.as<double>() + SLOT_PQ;
+        stiffness_from_nodes(q_k, vn);
+        gather_nodes(qn, q_k);
+        if (shift_active())
+            FDD_CALL(fdd_shift_add_inner_product(out, reduce_ws.as<double>(), qn.as<double>(), shift_nodes.as<double>(), vn.as<double>(), num_local_nodes, stream));
+        else
+            FDD_CALL(fdd_sub_inner_product(out, reduce_ws.as<double>(), vn.as<double>(), qn.as<double>(), num_local_nodes, stream));
+        DType vq = 0.0;
+        scalars.slice(SLOT_PQ, 1).copyTo(&vq, sizeof(DType));
+        return vq;
+    }
+
     // whether node_norm_enqueue forms the norm as the plain sum over the dof slice (and returns its address)
     bool norm_is_slice_sum() const
     {
@@ -1241,11 +1295,16 @@ class Domain
         {
             // gamma = <z, r> already sits in scalars[fcg.gamma_slot]: the flexible dot of the previous iteration formed it from the
             // vectors it was reading anyway (fcg_nodes_step_direction); <p, q> is what is left of domain.okl:140-184
-            FDD_CALL(fdd_sub_inner_product(scalars.as<double>() + SLOT_PQ, reduce_ws.as<double>(), np.as<double>(), nq.as<double>(), nn, stream));
+            // (with a Helmholtz shift the same pass first completes q^ += c .* p~ and sums the values it stores)
+            if (shift_active())
+                FDD_CALL(fdd_shift_add_inner_product(scalars.as<double>() + SLOT_PQ, reduce_ws.as<double>(), nq.as<double>(), shift_nodes.as<double>(), np.as<double>(), nn, stream));
+            else
+                FDD_CALL(fdd_sub_inner_product(scalars.as<double>() + SLOT_PQ, reduce_ws.as<double>(), np.as<double>(), nq.as<double>(), nn, stream));
             if (fdd::comm().size > 1) fdd::comm().allreduce_sum(scalars.as<double>() + SLOT_PQ, 1);
         }
         else
         {
+            shift_add_nodes(nq, np);
             FDD_CALL(fdd_dom_projection_inner_products(scalars.as<double>(), reduce_ws.as<double>(), nz.as<double>(), nr.as<double>(), np.as<double>(), nq.as<double>(), nn, stream));
             if (device_scalars and fdd::comm().size > 1) fdd::comm().allreduce_sum(scalars.as<double>(), 2);
         }
@@ -1682,6 +1741,7 @@ class Domain
             fdd_timer().start("domain.operator_application");
             stiffness_from_nodes(q_k, nu);
             gather_nodes(nq, q_k);
+            shift_add_nodes(nq, nu);
             fdd_timer().stop("domain.operator_application");
             fdd_timer().start("domain.vector_operations");
             FDD_CALL(fdd_vector_vector_addition(nr.as<double>(), 1.0, nf.as<double>(), -1.0, nq.as<double>(), nn, stream));
@@ -1703,6 +1763,7 @@ class Domain
             fdd_timer().start("domain.operator_application");
             stiffness_from_nodes(q_k, ZN[j]);
             gather_nodes(nq, q_k);
+            shift_add_nodes(nq, ZN[j]);
             fdd_timer().stop("domain.operator_application");
 
             // classical Gram-Schmidt: every H[i][j] from the same q (domain.tpp:810-815), then the updates

@@ -93,9 +93,25 @@
 #pragma weak fdd_field_mass
 #pragma weak fdd_field_gradient
 #pragma weak fdd_field_weak_divergence
+// and the zeroth-order term of a Helmholtz operator (csrc/fdd_helmholtz.hip): without them fddh_helmholtz_set refuses, naming
+// the missing entry (missing_helmholtz_entry)
+#pragma weak fdd_shift_add
+#pragma weak fdd_shift_add_f32
+#pragma weak fdd_shift_add_inner_product
 
 namespace fdd
 {
+
+// the first entry a Helmholtz shift needs that the loaded kernel library does not export (the mass matrix it is made from
+// among them), or nullptr
+inline const char *missing_helmholtz_entry()
+{
+    if (&fdd_shift_add == nullptr) return "fdd_shift_add";
+    if (&fdd_shift_add_f32 == nullptr) return "fdd_shift_add_f32";
+    if (&fdd_shift_add_inner_product == nullptr) return "fdd_shift_add_inner_product";
+    if (&fdd_field_mass == nullptr) return "fdd_field_mass";
+    return nullptr;
+}
 
 // the first of the field entries the loaded kernel library does not export, or nullptr
 inline const char *missing_field_entry()

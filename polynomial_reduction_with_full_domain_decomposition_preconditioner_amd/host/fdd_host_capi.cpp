@@ -55,6 +55,8 @@ struct fddh_problem
     fdd::memory a, b, c;
     fdd::memory sa, sb; // subdomain-sized
 
+    double helmholtz_min = 0.0, helmholtz_max = 0.0; // of the lambda a set Helmholtz shift was made from (fddh_helmholtz_set)
+
     Domain<SType> &fine() { return domains[poly_degree]; }
     const Domain<SType> &fine() const { return domains.at(poly_degree); }
 };
@@ -176,6 +178,24 @@ auto with_preconditioner(fddh_problem &p, bool use_subdomain, F &&f)
 {
     if (use_subdomain) return f(*p.subdomain);
     return f(p.none);
+}
+
+// With a Helmholtz shift set (fddh_helmholtz_set): why a solve would not carry it, or nullptr.  The term lives in the
+// node-space outer loops and in Subdomain::operator_dofs and nowhere else, so whatever would run another loop is refused
+// when it starts (the flags may be set in any order).  inner: the inner solve alone; outer_gmres: the outer GMRES, else FCG
+const char *helmholtz_inner_refusal(fddh_problem &p)
+{
+    if (!p.fine().shift_active() || !p.subdomain) return nullptr;
+    return p.subdomain->helmholtz_refusal();
+}
+
+const char *helmholtz_outer_refusal(fddh_problem &p, bool outer_gmres)
+{
+    Domain<SType> &d = p.fine();
+    if (!d.shift_active()) return nullptr;
+    const bool nodes = with_preconditioner(p, p.subdomain != nullptr, [&](auto &preconditioner) { return d.can_fcg_nodes(preconditioner); });
+    if (!nodes || (outer_gmres && !d.restructured_outer)) return "a Helmholtz shift needs the node-space outer solve (assembled_outer_solve = 1, restructured_inner_solve = 1, the inner GMRES or Chebyshev-Jacobi in dof space): the point-space outer loops do not carry the term";
+    return d.use_preconditioner ? helmholtz_inner_refusal(p) : nullptr;
 }
 
 // fn() between finish + barrier (collective: every rank or none) and finish, the wall time into *seconds; seconds null: fn() alone
@@ -1405,6 +1425,92 @@ int fddh_field_weak_divergence(fddh_problem *p, const double *vx, const double *
     });
 }
 
+// ---- fddh_helmholtz_*: -laplace(u) + lambda u through the node-space outer solve and the dof-space inner solve ----
+int fddh_helmholtz_set(fddh_problem *p, double lambda, const double *lambda_points)
+{
+    return on_problem(p, true, [&](fddh_problem &pr) {
+        Domain<SType> &d = pr.fine();
+        if (const char *missing = fdd::missing_helmholtz_entry()) return fail("a Helmholtz shift needs %s, which the loaded kernel library does not export", missing);
+        if (fdd::comm().size > 1) return fail("a Helmholtz shift is supported on one rank: this communicator has %d", fdd::comm().size);
+        if (d.mesh.dim != 3) return fail("a Helmholtz shift is 3-D only: this problem is %d-D", d.mesh.dim);
+        if (d.poly_degree > 15) return fail("a Helmholtz shift supports poly_degree 1..15, got %d", d.poly_degree);
+        if (pr.subdomain && pr.subdomain->composite()) return fail("a Helmholtz shift needs a conforming region: this problem's Subdomain is a composite");
+        if (pr.subdomain && (int)pr.subdomain->point_dof.size() != d.num_local_points) return fail("a Helmholtz shift needs a Subdomain over the rank's own points");
+        const size_t np = (size_t)d.num_local_points;
+        double lo = lambda, hi = lambda;
+        for (size_t q = 0; lambda_points && q < np; q++)
+        {
+            const double v = lambda_points[q];
+            if (!std::isfinite(v) || v < 0.0) return fail("lambda must be finite and >= 0 at every point: point %zu has %g", q, v);
+            lo = q == 0 ? v : std::min(lo, v);
+            hi = q == 0 ? v : std::max(hi, v);
+        }
+        if (!lambda_points && (!std::isfinite(lambda) || lambda < 0.0)) return fail("lambda must be finite and >= 0, got %g", lambda);
+
+        std::vector<double> lambda_B;
+        if (hi > 0.0)
+        {
+            fdd::FieldOps<Domain<SType>>(d).mass(pr.b);
+            lambda_B.resize(np);
+            pr.b.copyTo(lambda_B.data(), fine_bytes(pr));
+            for (size_t q = 0; q < np; q++) lambda_B[q] = (lambda_points ? lambda_points[q] : lambda) * lambda_B[q];
+        }
+        const bool was_active = d.shift_active();
+        d.set_shift(hi > 0.0 ? lambda_B.data() : nullptr);
+        if (was_active || d.shift_active()) d.projection.clear(); // the operator changes under the stored images
+        pr.helmholtz_min = d.shift_active() ? lo : 0.0;
+        pr.helmholtz_max = d.shift_active() ? hi : 0.0;
+        if (pr.subdomain)
+        {
+            // the same values in the Subdomain's dof numbering: a dof sits on the node of any of its points
+            Subdomain<PType> &s = *pr.subdomain;
+            std::vector<double> c_dofs((size_t)std::max(s.dof_count(), 1), 0.0);
+            const CSR_Matrix<SType> &Q = d.scatter_matrix();
+            for (size_t q = 0; d.shift_active() && q < np; q++)
+                if (s.point_dof[q] >= 0 && s.point_dof[q] < s.dof_count()) c_dofs[s.point_dof[q]] = d.shift_nodes_hst[Q.col_hst[q]];
+            s.set_shift(d.shift_active() ? c_dofs.data() : nullptr, s.dof_count());
+        }
+        return 0;
+    });
+}
+
+int fddh_helmholtz_info(fddh_problem *p, int *active, double *min, double *max)
+{
+    return on_problem(p, true, [&](fddh_problem &pr) {
+        if (active) *active = pr.fine().shift_active() ? 1 : 0;
+        if (min) *min = pr.helmholtz_min;
+        if (max) *max = pr.helmholtz_max;
+        return 0;
+    });
+}
+
+int fddh_helmholtz_shift(fddh_problem *p, double *cbar_nodes, int n)
+{
+    return on_problem(p, cbar_nodes != nullptr, [&](fddh_problem &pr) {
+        const Domain<SType> &d = pr.fine();
+        if (n != d.num_local_nodes) return fail("the shift has %d entries (the rank's nodes), got %d", d.num_local_nodes, n);
+        for (int i = 0; i < n; i++) cbar_nodes[i] = d.shift_active() ? d.shift_nodes_hst[i] : 0.0;
+        return 0;
+    });
+}
+
+int fddh_helmholtz_node_operator(fddh_problem *p, const double *v_nodes, double *q_nodes, int n, double *vq)
+{
+    return on_problem(p, v_nodes && q_nodes, [&](fddh_problem &pr) {
+        Domain<SType> &d = pr.fine();
+        if (d.mesh.dim != 3 || d.poly_degree > 15 || !d.gather_matrix().unit_values) return fail("the node-space operator needs a 3-D problem of degree 1..15 with a boolean gather");
+        if (n != d.num_local_nodes) return fail("node vectors have %d entries, got %d", d.num_local_nodes, n);
+        fdd::memory vn = fdd::dev().malloc<double>(std::max(n, 1)), qn = fdd::dev().malloc<double>(std::max(n, 1));
+        vn.copyFrom(v_nodes, (size_t)n * sizeof(double));
+        const double dot = d.node_operator(qn, vn);
+        qn.copyTo(q_nodes, (size_t)n * sizeof(double));
+        if (vq) *vq = dot;
+        vn.free();
+        qn.free();
+        return 0;
+    });
+}
+
 int fddh_problem_residual_norm(fddh_problem *p, const double *r, double *norm)
 {
     return on_problem(p, r && norm, [&](fddh_problem &pr) {
@@ -1453,6 +1559,7 @@ int fddh_problem_make_rhs_from(fddh_problem *p, double *u_star_inout, double *f)
 int fddh_problem_solve(fddh_problem *p, int solver_id, const double *f, double *u, double *history, int history_cap, int *num_history, int *num_iterations)
 {
     return on_problem(p, f && u, [&](fddh_problem &pr) {
+        if (const char *why = helmholtz_outer_refusal(pr, solver_id != 0)) return fail("%s", why);
         return outer_solve(pr, f, u, history, history_cap, num_history, num_iterations, nullptr, [&](Domain<SType> &d, auto &preconditioner) { krylov_solve(pr, d, preconditioner, solver_id); });
     });
 }
@@ -1460,6 +1567,7 @@ int fddh_problem_solve(fddh_problem *p, int solver_id, const double *f, double *
 int fddh_problem_solve_timed(fddh_problem *p, int solver_id, const double *f, double *u, double *history, int history_cap, int *num_history, int *num_iterations, double *seconds)
 {
     return on_problem(p, f && seconds, [&](fddh_problem &pr) {
+        if (const char *why = helmholtz_outer_refusal(pr, solver_id != 0)) return fail("%s", why);
         return outer_solve(pr, f, u, history, history_cap, num_history, num_iterations, seconds, [&](Domain<SType> &d, auto &preconditioner) { krylov_solve(pr, d, preconditioner, solver_id); });
     });
 }
@@ -1508,6 +1616,7 @@ int fddh_problem_projection_basis(const fddh_problem *p, int k, double *x, doubl
 int fddh_problem_solve_projected(fddh_problem *p, int solver_id, const double *f, double *u, double *history, int history_cap, int *num_history, int *num_iterations, double *projection, double *seconds)
 {
     return on_problem(p, f && u, [&](fddh_problem &pr) {
+        if (pr.fine().shift_active()) return fail("solve_projected while a Helmholtz shift is set: the basis and its stored images belong to the operator without the term (clear the shift, or use solve)");
         double proj[4];
         if (int rc = outer_solve(pr, f, u, history, history_cap, num_history, num_iterations, seconds, [&](Domain<SType> &d, auto &preconditioner) { d.solve_projected(pr.b, pr.a, preconditioner, solver_id, proj); })) return rc;
         if (projection) memcpy(projection, proj, sizeof(proj));
@@ -1519,6 +1628,8 @@ int fddh_problem_precond_apply(fddh_problem *p, int type, const double *r, doubl
 {
     return on_subdomain(p, r && z, [&](fddh_problem &pr, Subdomain<PType> &s) {
         if (const char *why = inner_solver_refusal(pr)) return fail("%s", why);
+        if (const char *why = helmholtz_inner_refusal(pr)) return fail("%s", why);
+        if (pr.fine().shift_active() && type == 0) return fail("a Helmholtz shift needs the inner GMRES or Chebyshev-Jacobi in dof space: the inner FCG does not go through operator_dofs");
         fine_round_trip(pr, r, z, [&] {
             if (type == 0)
                 s.flexible_conjugate_gradient(pr.b, pr.a);
@@ -1583,6 +1694,7 @@ int fddh_problem_sub_dof_solve(fddh_problem *p, const double *fa, double *ua, in
 {
     return on_subdomain(p, fa && ua, [&](fddh_problem &pr, Subdomain<PType> &s) {
         if (const char *why = inner_solver_refusal(pr)) return fail("%s", why);
+        if (const char *why = helmholtz_inner_refusal(pr)) return fail("%s", why);
         if (not s.dof_space_available()) return fail("the inner iteration of this problem does not run in dof space");
         if (n != s.dof_count()) return fail("dof vectors have %d entries, got %d", s.dof_count(), n);
         s.host_solve_dofs(ua, fa);
@@ -1635,6 +1747,7 @@ int fddh_problem_pcg_begin(fddh_problem *p, const double *f)
 {
     return on_problem(p, f != nullptr, [&](fddh_problem &pr) {
         if (const char *why = outer_solve_refusal(pr)) return fail("%s", why);
+        if (const char *why = helmholtz_outer_refusal(pr, false)) return fail("%s", why);
         Domain<SType> &d = pr.fine();
         pr.a.copyFrom(f, fine_bytes(pr));
         with_preconditioner(pr, pr.subdomain && d.use_preconditioner, [&](auto &preconditioner) { d.fcg_begin(pr.b, pr.a, preconditioner); });
@@ -1646,6 +1759,7 @@ int fddh_problem_pcg_steps(fddh_problem *p, int steps, double *last_residual)
 {
     return on_problem(p, steps >= 0, "bad argument", [&](fddh_problem &pr) {
         if (const char *why = outer_solve_refusal(pr)) return fail("%s", why);
+        if (const char *why = helmholtz_outer_refusal(pr, false)) return fail("%s", why);
         Domain<SType> &d = pr.fine();
         const double r = with_preconditioner(pr, pr.subdomain && d.use_preconditioner, [&](auto &preconditioner) { return d.fcg_steps(preconditioner, steps); });
         if (last_residual) *last_residual = r;

@@ -41,6 +41,17 @@ inline void cheby_step(float *x, float *d, float *r_out, const float *r_in, cons
     ProfileScope prof("cheby_step_f32_kernel", 4.0 * n * (first ? 4 : (last ? 6 : 8)));
     FDD_CALL(fdd_cheby_step_f32(x, d, r_out, r_in, q, dinv, (float)c_d, (float)c_r, first ? 1 : 0, last ? 1 : 0, n, s));
 }
+// y += c .* (scale x): the zeroth-order term of a Helmholtz operator behind the operator application that formed y
+inline void shift_add(double *y, const double *c, const double *scale_dev, const double *x, int n, void *s)
+{
+    ProfileScope prof("shift_add_kernel<f64>", 8.0 * n * 4);
+    FDD_CALL(fdd_shift_add(y, c, scale_dev, x, n, s));
+}
+inline void shift_add(float *y, const float *c, const double *scale_dev, const float *x, int n, void *s)
+{
+    ProfileScope prof("shift_add_kernel<f32>", 4.0 * n * 4);
+    FDD_CALL(fdd_shift_add_f32(y, c, scale_dev, x, n, s));
+}
 
 // ---- the Arnoldi step's reductions: out[k] = <a, s_k b_k>, and dst = y + sign sum c_k (s_k x_k) with |dst|^2 ----
 // w: the norm weight of the dofs (null: 1 everywhere, not read).  The float entries take none.

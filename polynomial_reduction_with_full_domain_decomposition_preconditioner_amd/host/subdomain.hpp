@@ -622,6 +622,7 @@ class Subdomain
         // subdomain's extended dofs among them) take their rows of A (operator_dofs / subdomain.tpp:3951)
         jacobi_diag_hst.assign(std::max(num_dofs, 1), 1.0);
         for (int d = 0; d < std::min(ns, num_dofs); d++) jacobi_diag_hst[d] = diag_ext[d];
+        for (size_t d = 0; d < std::min(shift_dofs_hst.size(), jacobi_diag_hst.size()); d++) jacobi_diag_hst[d] += shift_dofs_hst[d]; // the Helmholtz term is diagonal
         if (superdomain_operator.num_extended_dofs > 0)
         {
             const CSR_Matrix<DType> &A = superdomain_operator.A;
@@ -970,9 +971,17 @@ class Subdomain
   private:
     // y (dofs) = [Qt A_L Q | A_sup] (s x~): the operator of the inner iteration on a dof vector.  x~ is one of the
     // Krylov vectors; in a composite its allocation carries the copies and hanging values behind the dofs (W), which
-    // are written here.
+    // are written here.  With a Helmholtz shift set (set_shift; conforming regions only) the zeroth-order term follows:
+    // y += c .* (s x~), one more pass over the dofs.
     template <typename Real>
     void operator_dofs(Real *y, Real *x, const double *scale_dev = nullptr)
+    {
+        stiffness_operator_dofs(y, x, scale_dev);
+        if (shift_active()) fdd::ops::shift_add(y, (std::is_same<Real, float>::value ? shift_dofs_f32 : shift_dofs).template as<Real>(), scale_dev, x, dof_space_size(), fdd::dev().stream);
+    }
+
+    template <typename Real>
+    void stiffness_operator_dofs(Real *y, Real *x, const double *scale_dev)
     {
         constexpr bool f32 = std::is_same<Real, float>::value;
         void *stream = fdd::dev().stream;
@@ -1124,6 +1133,46 @@ class Subdomain
         operator_generation++;
     }
 
+    // ---- Helmholtz shift: the inner operator is Qt A_L Q + diag(c), c >= 0 over the dofs -- a LABELLED OPTION of this build ----
+    // c is the Domain's node vector (Domain::set_shift) in this class's dof numbering, kept in both precisions and on the
+    // host (the exact diagonal and the low-order matrix take it from there).  cbar == nullptr: off.  An operator change:
+    // the diagonal and the Chebyshev bound are made again at their next use, a hierarchy that amg_build made is built again
+    // now, with the term on the diagonal of its level-0 matrix; one that was handed in is the caller's and stays.
+    std::vector<double> shift_dofs_hst;
+    fdd::memory shift_dofs, shift_dofs_f32;
+    bool shift_active() const { return not shift_dofs_hst.empty(); }
+    void set_shift(const double *cbar, int n)
+    {
+        const bool was_active = shift_active();
+        if (cbar == nullptr and not was_active) return;
+        shift_dofs.free();
+        shift_dofs_f32.free();
+        shift_dofs_hst.clear();
+        if (cbar != nullptr and n > 0)
+        {
+            shift_dofs_hst.assign(cbar, cbar + n);
+            shift_dofs = fdd::dev().malloc<DType>((size_t)n);
+            shift_dofs.copyFrom(shift_dofs_hst.data(), (size_t)n * sizeof(DType));
+            shift_dofs_f32 = fdd::to_float(shift_dofs_hst);
+        }
+        operator_changed();
+        if (amg_hierarchy.ready() and amg_built_here)
+        {
+            const int nl = amg_build(amg_build_options);
+            rstdout("Low-order preconditioner assembled again (Helmholtz shift %s): %d levels, %.3f s\n", shift_active() ? "set" : "cleared", nl, amg_setup_seconds);
+        }
+    }
+
+    // why a solve of this problem would not carry the shift (it enters through operator_dofs alone), or nullptr
+    const char *helmholtz_refusal() const
+    {
+        if (is_composite) return "a Helmholtz shift needs a conforming region: this Subdomain is a composite";
+        if (not dof_space_available()) return "a Helmholtz shift needs the dof-space inner solve: a 3-D region with assembled_inner_solve = 1";
+        if (not norm_weight_is_one) return "a Helmholtz shift needs an unweighted gather in the inner operator";
+        if (not chebyshev() and not(device_bookkeeping and num_vectors <= FDD_MULTI_MAX)) return "a Helmholtz shift needs the inner GMRES with its bookkeeping on the device: the host-bookkeeping loop does not go through operator_dofs";
+        return nullptr;
+    }
+
     // ---- Chebyshev-Jacobi inner solve (chebyshev_dofs below): a LABELLED OPTION of this build, off by default ----
     int inner_solver = 0; // 0: the inner FCG / GMRES(m) as in the reference; 1: a fixed Chebyshev polynomial in D^-1 A
     bool chebyshev() const { return inner_solver == 1; }
@@ -1242,7 +1291,8 @@ class Subdomain
         static const bool timing = getenv("FDD_SETUP_TIMING") != nullptr;
         const auto clock = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         const double t0 = clock();
-        const bool on_device = amg_device_setup and not is_composite;
+        const bool on_device = amg_device_setup and not is_composite and not shift_active();
+        if (amg_device_setup and shift_active()) rstdout("amg_device_setup: with a Helmholtz shift set the low-order hierarchy is built on the host\n");
         if (amg_device_setup and is_composite) rstdout("amg_device_setup: a composite region builds its low-order hierarchy on the host\n");
         // the lattice the level-0 dofs sit on (the GLL points of the degree-N elements): the leading levels of the
         // hierarchy coarsen it geometrically (low_order.hpp); the device build also takes its point -> dof rows
@@ -1388,7 +1438,13 @@ class Subdomain
                 A = fdd::composite::assemble_low_order(comp, nodes, D_hat[num_levels - 1].first, (double)epsilon);
             }
             else
+            {
                 A = fdd::low_order::assemble_fem(fine_mesh->x.data(), fine_mesh->y.data(), fine_mesh->z.data(), point_dof.data(), num_dofs, poly_degree[0], fine_mesh->num_local_elements, epsilon);
+                // the Helmholtz term on the diagonal of the level-0 matrix: the coarse operators are Galerkin products of it
+                for (int d = 0; d < std::min((int)shift_dofs_hst.size(), A.rows); d++)
+                    for (int t = A.ptr[d]; t < A.ptr[d + 1]; t++)
+                        if (A.col[t] == d) A.val[t] += shift_dofs_hst[d];
+            }
             t1 = clock();
         }
         std::vector<fdd::low_order::Level> lv = fdd::low_order::build(std::move(A), options, verbose, std::move(lattice), first_host_level, geometric_done);
@@ -2506,8 +2562,9 @@ class Subdomain
         begin_inner_solve();
 
         const bool kernels = cheby.use_kernels and fdd::missing_chebyshev_entry(false) == nullptr;
-        // the float gather takes no norm weight; the double one may: then the separate pass stays
-        const bool fused = kernels and cheby.fused and not is_composite and (f32 or norm_weight_is_one) and subdomain_operator.Qt.num_rows == nd and subdomain_operator.Qt.gather_cheby_applies();
+        // the float gather takes no norm weight; the double one may: then the separate pass stays.  So it does with a Helmholtz
+        // shift: the gather's epilogue would take q before the term is added (operator_dofs adds it)
+        const bool fused = kernels and cheby.fused and not is_composite and not shift_active() and (f32 or norm_weight_is_one) and subdomain_operator.Qt.num_rows == nd and subdomain_operator.Qt.gather_cheby_applies();
         const double a = cheby.lower * lambda, b = cheby.upper * lambda, theta = 0.5 * (a + b), delta = 0.5 * (b - a), sigma = theta / delta;
         double rho = 1.0 / sigma;
 

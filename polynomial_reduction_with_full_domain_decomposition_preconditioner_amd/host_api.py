@@ -502,6 +502,41 @@ class Problem:
         _H().call("fddh_field_weak_divergence", self.h, _dp(v[0]), _dp(v[1]), _dp(v[2]), _dp(out))
         return out
 
+    # --- Helmholtz solves (an addition of this build, include/fdd_host.h) ---
+    def helmholtz(self, lam):
+        """Solve (-laplace + lam) u = f from here on: lam a constant >= 0 or an array >= 0 over the fine level's points; 0
+        switches the term off.  One rank, conforming region, 3-D.  A manufactured right-hand side:
+
+            f = p.stiffness(u_star) + lam * p.mass() * u_star
+        """
+        if np.ndim(lam) == 0:
+            _H().call("fddh_helmholtz_set", self.h, ctypes.c_double(float(lam)), None)
+        else:
+            lam = np.ascontiguousarray(lam, dtype=np.float64)
+            if lam.shape != (self.n,):
+                raise ValueError("lam has one value per point of the fine level (%d), got shape %s" % (self.n, lam.shape))
+            _H().call("fddh_helmholtz_set", self.h, ctypes.c_double(0.0), _dp(lam))
+
+    def helmholtz_info(self):
+        """{"active", "min", "max"}: whether a shift is set and the range of the lam it was made from"""
+        on, lo, hi = ctypes.c_int(), ctypes.c_double(), ctypes.c_double()
+        _H().call("fddh_helmholtz_info", self.h, ctypes.byref(on), ctypes.byref(lo), ctypes.byref(hi))
+        return {"active": bool(on.value), "min": lo.value, "max": hi.value}
+
+    def helmholtz_shift(self):
+        """cbar on the rank's nodes: the sums of lam * mass() over the copies of every node (zeros when no shift is set)"""
+        out = np.zeros(self.info["num_local_nodes"])
+        _H().call("fddh_helmholtz_shift", self.h, _dp(out), len(out))
+        return out
+
+    def helmholtz_node_operator(self, v):
+        """(q, <v, q>) with q = (Qt A_L Q + diag(cbar)) v on node vectors: the outer step's operator application and its dot"""
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        q = np.zeros(len(v))
+        vq = ctypes.c_double()
+        _H().call("fddh_helmholtz_node_operator", self.h, _dp(v), _dp(q), len(v), ctypes.byref(vq))
+        return q, vq.value
+
     def residual_norm(self, r):
         v = ctypes.c_double()
         _H().call("fddh_problem_residual_norm", self.h, _dp(np.ascontiguousarray(r)), ctypes.byref(v))
