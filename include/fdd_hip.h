@@ -462,6 +462,24 @@ int fdd_stiffness_matrix_lines_lean_f32(float *Au, const float *v, const double 
  * only.  Refuses what those entries refuse (poly_degree other than 7, diag other than 1: FDD_ERR_UNSUPPORTED), before any
  * output is touched.  FDD_TUNE_ASSEMBLE_NT_STORE=1: non-temporal stores of y (default 0). */
 int fdd_stiffness_matrix_lines_direct(double *Au, double *y, const double *v, const double *v_scale_dev, const int *point_class_dof, const double *D_hat, const double *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int lean, int num_elements, int poly_degree, int diag, void *stream);
+/* The coefficient instances of the line form: the operator D^T [kappa G] D on a list whose UNSCALED factor blocks repeat,
+ * kappa one double per point, without streaming the scaled arrays kappa G.  blocks: a HOST array of three device pointers
+ * to the distinct unscaled blocks of G[0], G[1], G[2] in compact form (block c starts at c * 512 doubles);
+ * block_of_elem[e] (device ints): the block of element e, in any order; coef: one double per point, read at the element's
+ * own offset (elem_offset[e], or e * 512 where elem_offset is NULL), three times per element -- once in each role of the
+ * lane -- of which the second and third are expected to come from cache: 8 B per point beside the 12 of the shared instance
+ * (derived, not measured).  Per point and array the kernel forms g = coef * block as one IEEE double product, the
+ * statement G'[g][p] = G[g][p] * kappa[p] of the caller that makes the scaled arrays; coef and blocks are double in both
+ * precisions and the float entry rounds the double product once, to the float cast of G'.  Everything else is the body of
+ * fdd_stiffness_matrix_lines[_f32]: every output bit is that entry's on G' (lean != 0: fdd_stiffness_matrix_lines_lean's,
+ * with its condition on D_hat and up to the sign of a zero).  point_dof NULL: the local form.  _direct: the arguments and
+ * the classes of fdd_stiffness_matrix_lines_direct.  Refused before anything is touched, the degree first: poly_degree
+ * other than 7 and diag other than 1 (FDD_ERR_UNSUPPORTED); a NULL coef, blocks, blocks[g] or block_of_elem; an output
+ * (Au, y) that is one of the inputs, or an input that starts inside the points of Au where elem_offset is NULL
+ * (FDD_ERR_INVALID_ARGUMENT): Au may NOT alias v here. */
+int fdd_stiffness_matrix_lines_coef(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *coef, const double *const blocks[3], const int *block_of_elem, const int *elem_offset, int lean, int num_elements, int poly_degree, int diag, void *stream);
+int fdd_stiffness_matrix_lines_coef_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const double *coef, const double *const blocks[3], const int *block_of_elem, const int *elem_offset, int lean, int num_elements, int poly_degree, int diag, void *stream);
+int fdd_stiffness_matrix_lines_coef_direct(double *Au, double *y, const double *v, const double *v_scale_dev, const int *point_class_dof, const double *D_hat, const double *coef, const double *const blocks[3], const int *block_of_elem, const int *elem_offset, int lean, int num_elements, int poly_degree, int diag, void *stream);
 /* Which blocks repeat?  out[e] (num_elements 64-bit words in device memory) = a hash of the bit patterns of element e's block
  * of G[0], G[1], G[2] that depends on the position of every word: equal blocks give equal hashes, and two blocks that differ
  * in a single word give different ones.  3-D elements, poly_degree 1..15. */

@@ -380,6 +380,30 @@ int fddh_helmholtz_info(fddh_problem *p, int *active, double *min, double *max);
 int fddh_helmholtz_shift(fddh_problem *p, double *cbar_nodes, int n);
 int fddh_helmholtz_node_operator(fddh_problem *p, const double *v_nodes, double *q_nodes, int n, double *vq);
 
+/* ---- Variable diffusivity: -div(kappa grad u) + lambda u = f (an option of this build; the reference solves the Poisson problem) ----
+ * kappa_points: one double per point of the fine level, element-major like fddh_problem_mesh_array("x"), every value
+ * finite and > 0; continuity across elements is not asked for (a jump along element faces is legal).  The local operator
+ * becomes D^T [kappa G] D: the scaled factor arrays G'[g][p] = mesh g[g][p] * kappa[p] (one IEEE double product per entry,
+ * on the host, all six g) replace the mesh's in the device buffers every stiffness kernel reads; the mesh's own arrays are
+ * not written (fddh_problem_mesh_array("g_1".."g_6") keeps returning them), and setting again or clearing (NULL) starts
+ * from them.  What is derived from the factor arrays is derived again: the zero-factor, shared-block and (where that option
+ * is on) affine verdicts, the float copies, the exact diagonal of the inner operator, the Chebyshev-Jacobi bound, and a
+ * hierarchy built by fddh_problem_amg_build (built again on the host, each tetrahedron of the low-order matrix scaled by the
+ * mean of kappa at its four vertices); a hierarchy that was handed in stays.  The projection basis is cleared;
+ * fddh_problem_solve_projected stays allowed.  A Helmholtz shift is independent and keeps the unscaled mass.
+ * fddh_problem_stiffness / _make_rhs_from / _solve* / _pcg_* / _precond_apply / _sub_dof_op / _sub_jacobi_diagonal /
+ * _sub_dof_solve / _amg_build and fddh_helmholtz_node_operator follow a set kappa; fddh_field_* are geometry and do not.
+ * Flag "coefficient_in_kernel" (fddh_problem_set_flag; refused where the kernel library lacks
+ * fdd_stiffness_matrix_lines_coef[_f32|_direct]): a 3-D degree-7 list whose UNSCALED factor blocks repeat runs the
+ * coefficient instance of the line kernel, which reads the shared unscaled block and kappa and forms the product itself
+ * instead of streaming G'; the same bits either way.  Default 1 where the entries are (measured faster: DESIGN section 14).
+ * Refused, nothing touched and the problem staying usable: more than one rank, a composite Subdomain, a 2-D problem, n other
+ * than the number of fine-level points, a value that is not finite or not > 0 (the first such point is named).
+ *   info   whether a kappa is set, its smallest and largest value, and -- as the other fddh_problem_*_info entries count --
+ *          whether the fine Domain's list and how many of the Subdomain's lists run the coefficient instance */
+int fddh_diffusivity_set(fddh_problem *p, const double *kappa_points /* NULL clears */, int n);
+int fddh_diffusivity_info(fddh_problem *p, int *active, double *min, double *max, int *fine_domain_in_kernel, int *sub_lists_in_kernel, int *sub_lists);
+
 /* Outer solve: solver_id 0 = flexible_conjugate_gradient, 1 = generalized_minimum_residual
  * (poisson.cpp:224-231).  history receives the residual norms the reference
  * prints (iteration 0 first). */

@@ -772,6 +772,40 @@ template <typename T>
 struct LineDirect<T, 0>
 {
 };
+// kCoef (fdd_stiffness_matrix_lines_coef[_f32|_direct]): the factor arrays of a list whose unscaled blocks repeat, scaled by a
+// coefficient per point, without streaming the scaled arrays.  Element e reads its three unscaled factor lines from block
+// factor_elem[e] of three compact arrays (block c starts at c * 512; the lookup is wave-uniform and the loads are plain, as
+// in kShared) and the coefficient at its own base, in each of the lane's three roles; g = coef * block is one IEEE double
+// product, the statement the host made the scaled arrays with, rounded once to float in the float instance.  So the same
+// words reach the same arithmetic as in the streamed instance on the scaled arrays.  coef and the blocks are double in both
+// precisions; G is not read.  The lines are staged role by role -- the next role's two lines are requested before the
+// current role's arithmetic and multiplied after it -- since all six raw lines at once do not fit beside the sums at
+// four waves per SIMD.  No member, and nothing read, in the other instances
+template <bool kCoef>
+struct LineCoef
+{
+    const double *__restrict__ coef;
+    const double *__restrict__ blk[3];
+};
+template <>
+struct LineCoef<false>
+{
+};
+// one role's raw lines, and their products
+__device__ __forceinline__ void coef_line_load(double (&c)[8], double (&b)[8], const double *cp, const double *bp, int stride)
+{
+#pragma unroll
+    for (int p = 0; p < 8; p++) c[p] = cp[stride * p];
+#pragma unroll
+    for (int p = 0; p < 8; p++) b[p] = bp[stride * p];
+}
+template <typename T>
+__device__ __forceinline__ void coef_line_product(T (&g)[8], const double (&c)[8], const double (&b)[8])
+{
+#pragma unroll
+    for (int p = 0; p < 8; p++) g[p] = (T)(c[p] * b[p]);
+}
+
 // the pair-low values of the workgroup's elements, by (j, k): LDS of the kDirect instances only
 template <typename T>
 __device__ __forceinline__ T *line_hand_over(int e_loc)
@@ -780,9 +814,10 @@ __device__ __forceinline__ T *line_hand_over(int e_loc)
     return s_h[e_loc];
 }
 
-template <typename T, bool kGather, bool kNTStore, bool kShared = false, int kLean = 0, int kDirect = 0>
-__global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restrict__ Au, const T *__restrict__ u, const int *__restrict__ point_dof, const double *__restrict__ u_scale, const T *__restrict__ D_hat, GPtrsT<T> G, const int *__restrict__ elem_offset, int num_elements, const int *__restrict__ factor_elem, LineDirect<T, kDirect> direct)
+template <typename T, bool kGather, bool kNTStore, bool kShared = false, int kLean = 0, int kDirect = 0, bool kCoef = false>
+__global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restrict__ Au, const T *__restrict__ u, const int *__restrict__ point_dof, const double *__restrict__ u_scale, const T *__restrict__ D_hat, GPtrsT<T> G, const int *__restrict__ elem_offset, int num_elements, const int *__restrict__ factor_elem, LineDirect<T, kDirect> direct, LineCoef<kCoef> cf = {})
 {
+    static_assert(not(kCoef and kShared), "kCoef has its own way of addressing the shared blocks");
     using C = LineCfg;
     constexpr int n = C::n, nn = C::nn;
     static_assert(kDirect == 0 or kGather, "the classes of the points come with point_dof");
@@ -810,6 +845,7 @@ __global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restri
             const int rep = factor_elem[elem];
             fbase = elem_offset ? (size_t)elem_offset[rep] : (size_t)rep * C::n3;
         }
+        if (kCoef) fbase = (size_t)factor_elem[elem] * C::n3; // the compact arrays hold the distinct blocks one after another
         T *ta = s_a[e_loc], *tb = s_b[e_loc];
         constexpr bool kTerms = (kLean & kLeanTerms) != 0, kResident = (kLean & kLeanResident) != 0;
         static_assert(kTerms or not kResident, "the resident table does not hold the diagonal entries");
@@ -850,17 +886,27 @@ __global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restri
         {
             // the three factor lines of this lane, all requested before anything waits
             T g0[n], g1[n], g2[n];
-#pragma unroll
-            for (int k = 0; k < n; k++) g2[k] = kShared ? G.g[2][fbase + (l + k * nn)] : __builtin_nontemporal_load(G.g[2] + fbase + (l + k * nn)); // (i, j) = (a, b), k
+            double cl[n], bl[n]; // kCoef: the raw lines of the role after the current one
+            if constexpr (kCoef)
             {
-                const T *g0p = G.g[0] + fbase + 8 * l; // (j, k) = (a, b): the row starts at 8 a + 64 b
-#pragma unroll
-                for (int p = 0; p < n; p++) g0[p] = g0p[p];
+                coef_line_load(cl, bl, cf.coef + base + l, cf.blk[2] + fbase + l, nn); // (i, j) = (a, b), k
+                coef_line_product(g2, cl, bl);
+                coef_line_load(cl, bl, cf.coef + base + 8 * l, cf.blk[0] + fbase + 8 * l, 1); // (j, k) = (a, b): the row
             }
+            else
             {
-                const T *g1p = G.g[1] + fbase + (a + nn * b); // (i, k) = (a, b): the column steps by 8
 #pragma unroll
-                for (int p = 0; p < n; p++) g1[p] = kShared ? g1p[8 * p] : __builtin_nontemporal_load(g1p + 8 * p);
+                for (int k = 0; k < n; k++) g2[k] = kShared ? G.g[2][fbase + (l + k * nn)] : __builtin_nontemporal_load(G.g[2] + fbase + (l + k * nn)); // (i, j) = (a, b), k
+                {
+                    const T *g0p = G.g[0] + fbase + 8 * l; // (j, k) = (a, b): the row starts at 8 a + 64 b
+#pragma unroll
+                    for (int p = 0; p < n; p++) g0[p] = g0p[p];
+                }
+                {
+                    const T *g1p = G.g[1] + fbase + (a + nn * b); // (i, k) = (a, b): the column steps by 8
+#pragma unroll
+                    for (int p = 0; p < n; p++) g1[p] = kShared ? g1p[8 * p] : __builtin_nontemporal_load(g1p + 8 * p);
+                }
             }
 
 #pragma unroll
@@ -900,6 +946,11 @@ __global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restri
                 }
             }
 
+            if constexpr (kCoef)
+            {
+                coef_line_product(g0, cl, bl);
+                coef_line_load(cl, bl, cf.coef + base + (a + nn * b), cf.blk[1] + fbase + (a + nn * b), 8); // (i, k) = (a, b): the column
+            }
             // x: the row out of the u tile, Au_1 into the other tile
             T ul[n], w[n], au[n];
 #pragma unroll
@@ -915,6 +966,7 @@ __global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restri
 #pragma unroll
             for (int p = 0; p < n; p++) ul[p] = ta[C::at(a, p, b)];
             element_sync<true>();
+            if constexpr (kCoef) coef_line_product(g1, cl, bl);
             if constexpr (kTerms) lean_du(w, ul, Dl); else line_du(w, ul, D_hat);
 #pragma unroll
             for (int p = 0; p < n; p++) w[p] = g1[p] * w[p];
@@ -1021,6 +1073,78 @@ int launch_lines_direct(double *Au, double *y, const double *u, const int *point
     });
     FDD_LAUNCH_CHECK();
     return 0;
+}
+
+// the kCoef instances: block_of_elem goes where factor_elem does, G is not read.  direct_y given: the kDirect instance
+// (double with point_dof only, which the entry has checked)
+template <typename T, int kLean>
+int launch_lines_coef(T *Au, T *direct_y, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const LineCoef<true> &cf, const int *elem_offset, const int *block_of_elem, int num_elements, void *stream)
+{
+    const int grid = (num_elements + LineCfg::epb - 1) / LineCfg::epb;
+    if constexpr (sizeof(T) == 8)
+        if (direct_y != nullptr)
+        {
+            fdd_for_bool(stiffness_nt_store(), [&](auto nt) {
+                fdd_for_bool(assemble_nt_store(), [&](auto nt_y) {
+                    constexpr int kDirect = decltype(nt_y)::value ? 2 : 1;
+                    hipLaunchKernelGGL((line_stiffness_kernel_t<double, true, decltype(nt)::value, false, kLean, kDirect, true>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, GPtrsT<double>{}, elem_offset, num_elements, block_of_elem, LineDirect<double, kDirect>{direct_y}, cf);
+                });
+            });
+            FDD_LAUNCH_CHECK();
+            return 0;
+        }
+    for_gather_nt_store(point_dof, [&](auto gather, auto nt) {
+        hipLaunchKernelGGL((line_stiffness_kernel_t<T, decltype(gather)::value, decltype(nt)::value, false, kLean, 0, true>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, GPtrsT<T>{}, elem_offset, num_elements, block_of_elem, LineDirect<T, 0>{}, cf);
+    });
+    FDD_LAUNCH_CHECK();
+    return 0;
+}
+
+// The three entries of the coefficient form (fdd_stiffness_matrix_lines_coef[_f32|_direct]); every refusal comes before
+// anything is touched, the degree first.  An output may not be one of the inputs: not the same address, and where the
+// elements lie one after another (elem_offset null) no input may start inside the points Au covers
+template <typename T>
+int lines_coef_dispatch(T *Au, T *direct_y, bool direct, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const double *coef, const double *const blocks[3], const int *block_of_elem, const int *elem_offset, int lean, int num_elements, int poly_degree, int diag, void *stream)
+{
+    if (poly_degree != 7)
+    {
+        fdd_set_error("the coefficient line form of the stiffness kernel supports poly_degree 7 only, got %d", poly_degree);
+        return FDD_ERR_UNSUPPORTED;
+    }
+    if (diag != 1)
+    {
+        fdd_set_error("the coefficient line form of the stiffness kernel exists on three factor arrays only (diag = 1), got diag = %d", diag);
+        return FDD_ERR_UNSUPPORTED;
+    }
+    FDD_REQUIRE(num_elements >= 0);
+    FDD_REQUIRE(coef != nullptr && blocks != nullptr && blocks[0] != nullptr && blocks[1] != nullptr && blocks[2] != nullptr && block_of_elem != nullptr);
+    FDD_REQUIRE(Au != nullptr && u != nullptr && D_hat != nullptr);
+    FDD_REQUIRE(not direct || (point_dof != nullptr && direct_y != nullptr));
+    {
+        const char *lo = (const char *)Au, *hi = lo + (elem_offset ? sizeof(T) : (size_t)num_elements * LineCfg::n3 * sizeof(T));
+        const void *inputs[] = {u, point_dof, u_scale, D_hat, coef, blocks[0], blocks[1], blocks[2], block_of_elem, elem_offset};
+        for (const void *in : inputs)
+        {
+            const bool in_Au = (const char *)in >= lo && (const char *)in < hi;
+            if (in != nullptr && (in_Au || (direct && in == (const void *)direct_y)))
+            {
+                fdd_set_error("the coefficient line form of the stiffness kernel: an output overlaps an input");
+                return FDD_ERR_INVALID_ARGUMENT;
+            }
+        }
+        if (direct && (const char *)direct_y >= lo && (const char *)direct_y < hi)
+        {
+            fdd_set_error("the coefficient line form of the stiffness kernel: y overlaps Au");
+            return FDD_ERR_INVALID_ARGUMENT;
+        }
+    }
+    if (num_elements == 0) return 0;
+    LineCoef<true> cf;
+    cf.coef = coef;
+    for (int g = 0; g < 3; g++) cf.blk[g] = blocks[g];
+    constexpr int kParts = sizeof(T) == 8 ? (kLeanTerms | kLeanResident) : kLeanTerms; // the lean entries' parts
+    if (lean != 0) return launch_lines_coef<T, kParts>(Au, direct ? direct_y : nullptr, u, point_dof, u_scale, D_hat, cf, elem_offset, block_of_elem, num_elements, stream);
+    return launch_lines_coef<T, 0>(Au, direct ? direct_y : nullptr, u, point_dof, u_scale, D_hat, cf, elem_offset, block_of_elem, num_elements, stream);
 }
 
 // A development build (-DFDD_LEAN_LINE_DEV) compiles both choices of the lean parts for both precisions and exports
@@ -1522,6 +1646,21 @@ int fdd_stiffness_matrix_lines_lean(double *Au, const double *v, const double *v
 int fdd_stiffness_matrix_lines_lean_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream)
 {
     return lines_dispatch<float>(LineEntry::lean, Au, v, point_dof, v_scale_dev, D_hat, G, elem_offset, factor_elem, num_elements, poly_degree, diag, stream);
+}
+
+int fdd_stiffness_matrix_lines_coef(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *coef, const double *const blocks[3], const int *block_of_elem, const int *elem_offset, int lean, int num_elements, int poly_degree, int diag, void *stream)
+{
+    return lines_coef_dispatch<double>(Au, nullptr, false, v, point_dof, v_scale_dev, D_hat, coef, blocks, block_of_elem, elem_offset, lean, num_elements, poly_degree, diag, stream);
+}
+
+int fdd_stiffness_matrix_lines_coef_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const double *coef, const double *const blocks[3], const int *block_of_elem, const int *elem_offset, int lean, int num_elements, int poly_degree, int diag, void *stream)
+{
+    return lines_coef_dispatch<float>(Au, nullptr, false, v, point_dof, v_scale_dev, D_hat, coef, blocks, block_of_elem, elem_offset, lean, num_elements, poly_degree, diag, stream);
+}
+
+int fdd_stiffness_matrix_lines_coef_direct(double *Au, double *y, const double *v, const double *v_scale_dev, const int *point_class_dof, const double *D_hat, const double *coef, const double *const blocks[3], const int *block_of_elem, const int *elem_offset, int lean, int num_elements, int poly_degree, int diag, void *stream)
+{
+    return lines_coef_dispatch<double>(Au, y, true, v, point_class_dof, v_scale_dev, D_hat, coef, blocks, block_of_elem, elem_offset, lean, num_elements, poly_degree, diag, stream);
 }
 
 constexpr int kFactorBlockGrid = 1 << 20; // workgroups; beyond it a workgroup takes several elements in turn

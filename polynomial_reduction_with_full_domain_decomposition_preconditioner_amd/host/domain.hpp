@@ -30,6 +30,7 @@
 
 #include "config.hpp"
 #include "csr_matrix.hpp"
+#include "diffusivity.hpp"
 #include "element.hpp"
 #include "element_operator.hpp"
 #include "field_ops.hpp"
@@ -1008,8 +1009,29 @@ class Domain
     fdd::StiffnessChoice operator_choice() const { return fdd::choose_stiffness(list, stiffness, false, fdd::StiffnessForm::gather); } // what the fddh_problem_*_info entries report
     bool set_affine_geometry(bool on)
     {
+        list.affine_requested = on;
         list.affine = on and fdd::detect_affine(list);
         return list.affine or not on;
+    }
+
+    // ---- a diffusivity per point: -div(kappa grad u), diffusivity.hpp -- a LABELLED OPTION of this build ----
+    // kappa over the fine level's points (the caller has checked it, fdd::diffusivity::refusal); nullptr clears.  The scaled
+    // arrays G' = mesh.g * kappa go into the buffers the list -- and the Subdomain's level-0 list, which aliases them -- already
+    // reads, what is derived from a list's arrays is derived again, and a list whose unscaled blocks repeat gets the members of
+    // the coefficient line instance.  mesh.g is never written: setting again or clearing starts from it.  The caller clears
+    // the projection basis and tells the Subdomain (Subdomain::set_diffusivity).
+    bool diffusivity_is_set = false; // the Subdomain keeps the values (its hierarchy is built from them)
+    fdd::diffusivity::UnscaledBlocks unscaled_blocks;
+    bool diffusivity_active() const { return diffusivity_is_set; }
+    void set_diffusivity(const DType *kappa)
+    {
+        if (kappa == nullptr and not diffusivity_active()) return;
+        unscaled_blocks.remember(list); // the first time: the list's arrays are still the mesh's own
+        diffusivity_is_set = kappa != nullptr;
+        for (int g = 0; g < NUM_GEOM_FACTS; g++) fdd::diffusivity::upload_scaled(geom_fact[g], mesh.g[g], kappa);
+        fdd::diffusivity::refresh_list(list);
+        const std::vector<DType> *g[3] = {&mesh.g[0], &mesh.g[1], &mesh.g[2]};
+        fdd::diffusivity::fill_coef(list, unscaled_blocks, kappa, g);
     }
 
     // q (points) = A_local (Q p~)

@@ -47,6 +47,7 @@ struct LevelList
     memory G32[NUM_GEOM_FACTS], D_hat32;
     // affine elements (an option, set_affine_geometry): six numbers per element + the GLL weights stand for the factor arrays
     bool affine = false;            // in use; only 3-D lists of degree <= 15 (detect_affine checks no other)
+    bool affine_requested = false;  // the option as last asked for: a list whose arrays are rewritten is checked again (diffusivity.hpp)
     double affine_deviation = -1.0; // largest relative deviation found (-1: not checked)
     memory affine_c, affine_w, affine_c32, affine_w32;
     // are the three off-diagonal factor arrays G[3..5] zero at every point of the list (detect_zero_factors, once, when the
@@ -63,6 +64,12 @@ struct LevelList
     // does the table behind D_hat / D_hat32 meet the lean line instance's conditions (check_lean_table, on the host array
     // each upload is made from; each precision on its own)?  Only at degree 7
     bool lean_D_hat = false, lean_D_hat32 = false;
+    // a diffusivity per point is set (diffusivity.hpp): G and G32 then hold the scaled arrays kappa G, which every kernel
+    // reads as it reads the mesh's own.  Where the list is 3-D of degree 7 and its UNSCALED arrays shared blocks (the verdict
+    // of detect_shared_blocks on the mesh's arrays, kept by diffusivity.hpp), the coefficient line instance can form kappa G
+    // itself (flag "coefficient_in_kernel"): coef, device doubles per point; coef_blocks, the distinct unscaled blocks of
+    // G[0..2] in compact form (block c at c (N+1)^3); coef_block_of_elem, device ints per element.  Not allocated otherwise
+    memory coef, coef_blocks[3], coef_block_of_elem;
 
     size_t num_points() const { return (size_t)num_elements * (poly_degree + 1) * (poly_degree + 1) * (dim == 3 ? poly_degree + 1 : 1); }
 };
@@ -103,6 +110,13 @@ struct StiffnessFlags
     // (assembly_classes.hpp; where Subdomain::assembly_obstacle finds none); 0: the point buffer and the whole
     // gather.  The sums are the gather's own statements, so every bit stays and nothing that hangs on the operator is emptied
     bool assemble_in_stiffness;
+    // lists on the line form that carry a coefficient (LevelList::coef: a diffusivity on a list whose unscaled factor
+    // blocks repeat) run the coefficient instance, which reads the shared unscaled block and one coefficient per point and
+    // forms the scaled factor itself; 0: they stream the scaled arrays.  The product is the statement that made the scaled
+    // arrays, so the bits are the streamed instance's and nothing that hangs on the operator is emptied.  On by default where
+    // its entries are, like the flags above (measured faster than streaming the scaled arrays); the
+    // initialiser is what a kernel library without the entries leaves
+    bool coefficient_in_kernel = false;
 
     StiffnessFlags();
 };
@@ -119,10 +133,10 @@ struct StiffnessFlagRow
     } entries[5]; // ends at a null name
 };
 
-inline const std::array<StiffnessFlagRow, 7> &stiffness_flag_table()
+inline const std::array<StiffnessFlagRow, 8> &stiffness_flag_table()
 {
 #define FDD_ENTRY(name) {(const void *)&name, #name}
-    static const std::array<StiffnessFlagRow, 7> table = {{
+    static const std::array<StiffnessFlagRow, 8> table = {{
         {"mfma_stiffness", &StiffnessFlags::mfma_stiffness, {}},
         {"skip_zero_factors", &StiffnessFlags::skip_zero_factors, {FDD_ENTRY(fdd_stiffness_offdiag_zero), FDD_ENTRY(fdd_stiffness_matrix_diag), FDD_ENTRY(fdd_stiffness_matrix_diag_f32)}},
         // with the check that sets LevelList::offdiag_zero
@@ -133,6 +147,7 @@ inline const std::array<StiffnessFlagRow, 7> &stiffness_flag_table()
         {"lean_line_stiffness", &StiffnessFlags::lean_line_stiffness, {FDD_ENTRY(fdd_stiffness_matrix_lines_lean), FDD_ENTRY(fdd_stiffness_matrix_lines_lean_f32)}},
         // with the gather of the rows the kernel leaves
         {"assemble_in_stiffness", &StiffnessFlags::assemble_in_stiffness, {FDD_ENTRY(fdd_stiffness_matrix_lines_direct), FDD_ENTRY(fdd_csr_plan_gather_mapped)}},
+        {"coefficient_in_kernel", &StiffnessFlags::coefficient_in_kernel, {FDD_ENTRY(fdd_stiffness_matrix_lines_coef), FDD_ENTRY(fdd_stiffness_matrix_lines_coef_f32), FDD_ENTRY(fdd_stiffness_matrix_lines_coef_direct)}},
     }};
 #undef FDD_ENTRY
     return table;
@@ -294,6 +309,7 @@ struct StiffnessChoice
 {
     StiffnessFamily family;
     bool shared = false, lean = false;
+    bool coef = false; // the coefficient instance of the line form; never together with shared (it names the blocks itself)
 
     // what fddh_problem_*_info counts, asked of the gather form's choice
     bool three_arrays() const { return family == StiffnessFamily::diag or family == StiffnessFamily::lines; } // not the matrix-core instance
@@ -301,6 +317,7 @@ struct StiffnessChoice
     bool lines() const { return family == StiffnessFamily::lines; }
     bool shared_lines() const { return lines() and shared; }
     bool lean_lines() const { return lines() and lean; }
+    bool coef_lines() const { return lines() and coef; }
 };
 
 // The one decision, for both forms and both precisions.  in_place: Au == u (local form only).  Launches nothing, touches no
@@ -322,7 +339,10 @@ inline StiffnessChoice choose_stiffness(const LevelList &ll, const StiffnessFlag
         if (not(flags.line_stiffness and ll.dim == 3 and ll.poly_degree == 7)) return {F::diag};
         // shared or streamed, a lean list or not: the two attributes do not look at each other, and each precision's lean
         // verdict comes from the check of its own table
-        return {F::lines, flags.shared_factor_blocks and ll.shared_blocks, flags.lean_line_stiffness and (f32 ? ll.lean_D_hat32 : ll.lean_D_hat)};
+        const bool lean = flags.lean_line_stiffness and (f32 ? ll.lean_D_hat32 : ll.lean_D_hat);
+        // a list that carries a coefficient, while the flag is on: the coefficient instance (its entries refuse Au == u)
+        if (ll.coef.ptr() and flags.coefficient_in_kernel and not in_place) return {F::lines, false, lean, true};
+        return {F::lines, flags.shared_factor_blocks and ll.shared_blocks, lean};
     }
     if (gather or (ll.dim == 3 and ll.poly_degree <= 15)) return {F::fused};
     return {ll.dim == 2 and ll.poly_degree <= 15 ? F::fused_2d : F::two_launch};
@@ -369,6 +389,23 @@ inline StiffnessProfile stiffness_profile(StiffnessForm form, const StiffnessCho
         {StiffnessForm::gather, F::fused, false, false, "fused_stiffness_kernel<gather>", "fused_stiffness_kernel<gather,f32>", 60.0, 32.0},
         {StiffnessForm::gather, F::mfma, false, false, "mfma_stiffness_kernel<gather>", nullptr, 60.0, 0.0},
     };
+    // the coefficient instances: the shared instance's bytes plus one double per point for the coefficient, in both
+    // precisions (its second and third read per element are expected to come from cache: derived)
+    static const struct
+    {
+        StiffnessForm form;
+        bool lean;
+        const char *label, *label32;
+        double bytes, bytes32;
+    } coef_table[] = {
+        {StiffnessForm::local, false, "line_stiffness_kernel<coef>", nullptr, 24.0, 0.0},
+        {StiffnessForm::local, true, "line_stiffness_kernel<coef,lean>", nullptr, 24.0, 0.0},
+        {StiffnessForm::gather, false, "line_stiffness_kernel<gather,coef>", "line_stiffness_kernel<gather,coef,f32>", 20.0, 16.0},
+        {StiffnessForm::gather, true, "line_stiffness_kernel<gather,coef,lean>", "line_stiffness_kernel<gather,coef,f32,lean>", 20.0, 16.0},
+    };
+    if (c.coef_lines())
+        for (const auto &row : coef_table)
+            if (row.form == form and row.lean == c.lean) return {f32 ? row.label32 : row.label, f32 ? row.bytes32 : row.bytes};
     for (const auto &row : table)
         if (row.form == form and row.family == c.family and row.shared == c.shared and row.lean == c.lean) return {f32 ? row.label32 : row.label, f32 ? row.bytes32 : row.bytes};
     return {nullptr, 0.0};
@@ -419,6 +456,11 @@ inline bool launch_three_arrays(const StiffnessChoice &c, const LevelList &ll, R
     }
     else if (c.family != StiffnessFamily::lines)
         return false;
+    else if (c.coef) // the coefficient and the blocks are double in both precisions; the table is the precision's own
+    {
+        const double *blocks[3] = {ll.coef_blocks[0].as<double>(), ll.coef_blocks[1].as<double>(), ll.coef_blocks[2].as<double>()};
+        FDD_CALL(entry_of<Real>(fdd_stiffness_matrix_lines_coef, fdd_stiffness_matrix_lines_coef_f32)(q, v, scale_dev, point_index, a.D_hat, ll.coef.as<double>(), blocks, ll.coef_block_of_elem.as<int>(), nullptr, c.lean ? 1 : 0, ll.num_elements, ll.poly_degree, 1, s));
+    }
     else if (c.lean) // shared where factor_elem is given
         FDD_CALL(entry_of<Real>(fdd_stiffness_matrix_lines_lean, fdd_stiffness_matrix_lines_lean_f32)(q, v, scale_dev, point_index, a.D_hat, a.G, nullptr, factor_elem, ll.num_elements, ll.poly_degree, 1, s));
     else if (c.shared)
@@ -497,6 +539,12 @@ inline void apply_gather_direct(const LevelList &ll, double *q, double *y, const
     const StiffnessChoice c = choose_stiffness(ll, flags, false, StiffnessForm::gather);
     const StiffnessProfile p = stiffness_profile(StiffnessForm::gather, c, false);
     ProfileScope prof(p.label, p.bytes_per_point * (double)ll.num_points() + (double)sizeof(double) * gathered_values);
+    if (c.coef)
+    {
+        const double *blocks[3] = {ll.coef_blocks[0].as<double>(), ll.coef_blocks[1].as<double>(), ll.coef_blocks[2].as<double>()};
+        FDD_CALL(fdd_stiffness_matrix_lines_coef_direct(q, y, v, scale_dev, point_class_dof, ll.D_hat, ll.coef.as<double>(), blocks, ll.coef_block_of_elem.as<int>(), nullptr, c.lean ? 1 : 0, ll.num_elements, ll.poly_degree, 1, dev().stream));
+        return;
+    }
     FDD_CALL(fdd_stiffness_matrix_lines_direct(q, y, v, scale_dev, point_class_dof, ll.D_hat, ll.G, nullptr, c.shared ? ll.factor_elem.as<int>() : nullptr, c.lean ? 1 : 0, ll.num_elements, ll.poly_degree, 1, dev().stream));
 }
 

@@ -88,6 +88,12 @@
 // set to 1, naming the missing entry
 #pragma weak fdd_stiffness_matrix_lines_direct
 #pragma weak fdd_csr_plan_gather_mapped
+// and the coefficient instances of the line form (a diffusivity per point on a list whose unscaled factor blocks repeat,
+// host/diffusivity.hpp): without them such a list streams its scaled arrays, and the flag "coefficient_in_kernel" refuses to be
+// set to 1, naming the missing entry
+#pragma weak fdd_stiffness_matrix_lines_coef
+#pragma weak fdd_stiffness_matrix_lines_coef_f32
+#pragma weak fdd_stiffness_matrix_lines_coef_direct
 // and the mass, gradient and weak divergence of fields on the fine mesh (csrc/fdd_field.hip): without them the fddh_field_*
 // entries refuse, naming the missing entry (missing_field_entry)
 #pragma weak fdd_field_mass

@@ -56,6 +56,7 @@ struct fddh_problem
     fdd::memory sa, sb; // subdomain-sized
 
     double helmholtz_min = 0.0, helmholtz_max = 0.0; // of the lambda a set Helmholtz shift was made from (fddh_helmholtz_set)
+    double diffusivity_min = 0.0, diffusivity_max = 0.0; // of the kappa that is set (fddh_diffusivity_set; 0: none)
 
     Domain<SType> &fine() { return domains[poly_degree]; }
     const Domain<SType> &fine() const { return domains.at(poly_degree); }
@@ -1507,6 +1508,41 @@ int fddh_helmholtz_node_operator(fddh_problem *p, const double *v_nodes, double 
         if (vq) *vq = dot;
         vn.free();
         qn.free();
+        return 0;
+    });
+}
+
+// ---- fddh_diffusivity_*: -div(kappa grad u), kappa per point of the fine level (host/diffusivity.hpp) ----
+int fddh_diffusivity_set(fddh_problem *p, const double *kappa_points, int n)
+{
+    return on_problem(p, true, [&](fddh_problem &pr) {
+        Domain<SType> &d = pr.fine();
+        const std::string why = fdd::diffusivity::refusal(kappa_points, n, d.num_local_points, d.mesh.dim, fdd::comm().size, pr.subdomain && pr.subdomain->composite());
+        if (!why.empty()) return fail("%s", why.c_str());
+        if (pr.subdomain && (int)pr.subdomain->point_dof.size() != d.num_local_points) return fail("a diffusivity needs a Subdomain over the rank's own points");
+        if (kappa_points == nullptr && !d.diffusivity_active()) return 0;
+        d.set_diffusivity(kappa_points);
+        // the basis belongs to the operator as it was; solve_projected stays allowed: the images stored from here on are this operator's
+        d.projection.clear();
+        if (pr.subdomain) pr.subdomain->set_diffusivity(kappa_points, (size_t)d.num_local_points, d.operator_list());
+        pr.diffusivity_min = pr.diffusivity_max = 0.0;
+        if (kappa_points)
+        {
+            pr.diffusivity_min = *std::min_element(kappa_points, kappa_points + n);
+            pr.diffusivity_max = *std::max_element(kappa_points, kappa_points + n);
+        }
+        return 0;
+    });
+}
+
+int fddh_diffusivity_info(fddh_problem *p, int *active, double *min, double *max, int *fine_domain_in_kernel, int *sub_lists_in_kernel, int *sub_lists)
+{
+    int enabled = 0;
+    if (int rc = stiffness_info(p, "coefficient_in_kernel", &fdd::StiffnessChoice::coef_lines, &enabled, fine_domain_in_kernel, sub_lists_in_kernel, sub_lists)) return rc;
+    return on_problem(p, true, [&](fddh_problem &pr) {
+        if (active) *active = pr.fine().diffusivity_active() ? 1 : 0;
+        if (min) *min = pr.diffusivity_min;
+        if (max) *max = pr.diffusivity_max;
         return 0;
     });
 }

@@ -183,7 +183,9 @@ inline HostCSR from_triplets(int rows, int cols, std::vector<int> &ti, std::vect
 
 // subdomain.tpp:2823-3060: P1 stiffness of the 6 tetrahedra of every GLL sub-cell, summed on the dofs.
 // x, y, z: coordinates of the level-0 points (element-major, x fastest); point_dof[p] < 0: no dof (Dirichlet).
-inline HostCSR assemble_fem(const double *x, const double *y, const double *z, const int *point_dof, int num_dofs, int poly_degree, int num_elements, double epsilon = 1.0e-12)
+// kappa (an option of this build, diffusivity.hpp; nullptr: the statements of the reference): a diffusivity per point; a
+// tetrahedron's matrix is scaled by the mean of its four vertices' values, summed in the vertex order of tets[t].
+inline HostCSR assemble_fem(const double *x, const double *y, const double *z, const int *point_dof, int num_dofs, int poly_degree, int num_elements, double epsilon = 1.0e-12, const double *kappa = nullptr)
 {
     // vertex offsets (i, j, k) of the 6 tetrahedra of a cell (subdomain.tpp:2878-2885)
     static const int tets[6][4][3] = {
@@ -243,6 +245,7 @@ inline HostCSR assemble_fem(const double *x, const double *y, const double *z, c
                                 for (int k = 0; k < 3; k++) g += (det / 24.0) * iH[m * 3 + k] * iH[nn * 3 + k];
                                 G[m][nn] = g;
                             }
+                        const double kt = kappa ? 0.25 * (((kappa[loc[0]] + kappa[loc[1]]) + kappa[loc[2]]) + kappa[loc[3]]) : 1.0;
                         // A_tet = sum_mn D_m^T G_mn D_n over the 4 (identical) quadrature points (subdomain.tpp:3009-3027)
                         // Dref's entries are 0 and +-1 (row m: +1 in column m, -1 in column 3): the terms with a zero factor
                         // add +-0 and are skipped, the others are +-G_mn exactly, added in the reference's order (m, n, q)
@@ -259,7 +262,7 @@ inline HostCSR assemble_fem(const double *x, const double *y, const double *z, c
                                         const double g = minus ? -G[m][nn] : G[m][nn];
                                         for (int q = 0; q < 4; q++) a += g;
                                     }
-                                At[i][j] = a;
+                                At[i][j] = kappa ? kt * a : a;
                             }
                         for (int i = 0; i < 4; i++)
                         {

@@ -1163,6 +1163,36 @@ class Subdomain
         }
     }
 
+    // ---- a diffusivity per point (diffusivity.hpp): the inner operator is Qt D^T [kappa G] D Q -- a LABELLED OPTION of this build ----
+    // On one rank without a composite the inner operator is the fine level's own list on the Domain's own arrays, which
+    // Domain::set_diffusivity has just rewritten: what this class derived from them is derived again (the list's verdicts and
+    // float copies now; the diagonal, its inverses, the Chebyshev bound and the first-step scaling at their next use), the
+    // list takes the Domain's members of the coefficient instance as views, and a hierarchy that amg_build made is built
+    // again with kappa in its level-0 matrix; one that was handed in is the caller's and stays.  The classes of the rows of
+    // Qt (assembly) do not depend on the factors or on the kernel's instance and stay.  A Helmholtz shift is independent of
+    // all this and keeps the unscaled mass.  kappa == nullptr: cleared.
+    std::vector<double> diffusivity_hst;
+    bool diffusivity_active() const { return not diffusivity_hst.empty(); }
+    void set_diffusivity(const double *kappa, size_t n, const fdd::LevelList &domain_list)
+    {
+        if (kappa == nullptr and not diffusivity_active()) return;
+        if (kappa != nullptr)
+            diffusivity_hst.assign(kappa, kappa + n);
+        else
+            diffusivity_hst.clear();
+        for (auto &ll : subdomain_operator.level_lists)
+        {
+            fdd::diffusivity::refresh_list(ll);
+            fdd::diffusivity::share_coef(ll, domain_list);
+        }
+        operator_changed();
+        if (amg_hierarchy.ready() and amg_built_here)
+        {
+            const int nl = amg_build(amg_build_options);
+            rstdout("Low-order preconditioner assembled again (diffusivity %s): %d levels, %.3f s\n", diffusivity_active() ? "set" : "cleared", nl, amg_setup_seconds);
+        }
+    }
+
     // why a solve of this problem would not carry the shift (it enters through operator_dofs alone), or nullptr
     const char *helmholtz_refusal() const
     {
@@ -1291,8 +1321,9 @@ class Subdomain
         static const bool timing = getenv("FDD_SETUP_TIMING") != nullptr;
         const auto clock = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         const double t0 = clock();
-        const bool on_device = amg_device_setup and not is_composite and not shift_active();
+        const bool on_device = amg_device_setup and not is_composite and not shift_active() and not diffusivity_active();
         if (amg_device_setup and shift_active()) rstdout("amg_device_setup: with a Helmholtz shift set the low-order hierarchy is built on the host\n");
+        if (amg_device_setup and diffusivity_active()) rstdout("amg_device_setup: with a diffusivity set the low-order hierarchy is built on the host\n");
         if (amg_device_setup and is_composite) rstdout("amg_device_setup: a composite region builds its low-order hierarchy on the host\n");
         // the lattice the level-0 dofs sit on (the GLL points of the degree-N elements): the leading levels of the
         // hierarchy coarsen it geometrically (low_order.hpp); the device build also takes its point -> dof rows
@@ -1439,7 +1470,7 @@ class Subdomain
             }
             else
             {
-                A = fdd::low_order::assemble_fem(fine_mesh->x.data(), fine_mesh->y.data(), fine_mesh->z.data(), point_dof.data(), num_dofs, poly_degree[0], fine_mesh->num_local_elements, epsilon);
+                A = fdd::low_order::assemble_fem(fine_mesh->x.data(), fine_mesh->y.data(), fine_mesh->z.data(), point_dof.data(), num_dofs, poly_degree[0], fine_mesh->num_local_elements, epsilon, diffusivity_active() ? diffusivity_hst.data() : nullptr);
                 // the Helmholtz term on the diagonal of the level-0 matrix: the coarse operators are Galerkin products of it
                 for (int d = 0; d < std::min((int)shift_dofs_hst.size(), A.rows); d++)
                     for (int t = A.ptr[d]; t < A.ptr[d + 1]; t++)
@@ -2255,6 +2286,7 @@ class Subdomain
         int count = 0;
         for (auto &ll : subdomain_operator.level_lists)
         {
+            ll.affine_requested = on;
             ll.affine = on and fdd::detect_affine(ll);
             fdd::affine_float_copies(ll); // of a checked list, for the single-precision inner solve
             if (ll.affine) count++;

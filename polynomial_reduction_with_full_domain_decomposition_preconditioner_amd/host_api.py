@@ -537,6 +537,30 @@ class Problem:
         _H().call("fddh_helmholtz_node_operator", self.h, _dp(v), _dp(q), len(v), ctypes.byref(vq))
         return q, vq.value
 
+    # --- variable diffusivity (an addition of this build, include/fdd_host.h) ---
+    def diffusivity(self, kappa):
+        """Solve -div(kappa grad u) (+ lam u) = f from here on: kappa > 0 a scalar (broadcast) or an array over the fine
+        level's points, element-major like mesh_array("x"); None clears.  One rank, conforming region, 3-D.  stiffness,
+        make_rhs_from, the solves, the inner operator and its diagonal and amg_build follow; mass, gradient and
+        weak_divergence are geometry and do not."""
+        if kappa is None:
+            _H().call("fddh_diffusivity_set", self.h, None, 0)
+            return
+        if np.ndim(kappa) == 0:
+            kappa = np.full(self.n, float(kappa))
+        kappa = np.ascontiguousarray(kappa, dtype=np.float64)
+        if kappa.ndim != 1:
+            raise ValueError("kappa has one value per point of the fine level (%d), got shape %s" % (self.n, kappa.shape))
+        _H().call("fddh_diffusivity_set", self.h, _dp(kappa), len(kappa))
+
+    def diffusivity_info(self):
+        """{"active", "min", "max"}: whether a kappa is set and its range; flag "coefficient_in_kernel": does the fine
+        domain's list run the coefficient instance of the line kernel, and how many of the subdomain's lists do, of how many"""
+        on, lo, hi = ctypes.c_int(0), ctypes.c_double(0.0), ctypes.c_double(0.0)
+        dom, inside, lists = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        _H().call("fddh_diffusivity_info", self.h, ctypes.byref(on), ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(dom), ctypes.byref(inside), ctypes.byref(lists))
+        return {"active": bool(on.value), "min": lo.value, "max": hi.value, "fine_domain_in_kernel": bool(dom.value), "sub_lists_in_kernel": inside.value, "sub_lists": lists.value}
+
     def residual_norm(self, r):
         v = ctypes.c_double()
         _H().call("fddh_problem_residual_norm", self.h, _dp(np.ascontiguousarray(r)), ctypes.byref(v))
