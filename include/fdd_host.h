@@ -216,10 +216,15 @@ int fddh_problem_set_options(fddh_problem *p, int max_iterations, double toleran
  *                              that sets them in that other order is refused: not covered by the walks
  *   "preconditioner_precision" sets the V-cycle's precision too once a hierarchy exists: set "amg_precision" after it
  *   "amg_precision" / "preconditioner_precision" 32 need a Chebyshev order of at least 2 at the time they are set
- * What changes the operator under a live projection basis (fddh_problem_projection_configure) empties the basis, since its
- * stored images A X would no longer be the operator's: fddh_problem_set_D_hat (any level) and the flag "affine_geometry".
- * The same two drop the point-Jacobi diagonal and the Chebyshev-Jacobi eigenvalue bound, which are made again at next use.
- * Solver options and the other flags leave it alone.
+ * What changes the operator of a live problem: fddh_problem_set_D_hat (any level), the flag "affine_geometry",
+ * fddh_helmholtz_set and fddh_diffusivity_set (below).  All four end in one place, operator_changed in
+ * host/fdd_host_capi.cpp, which says what each reaches.  Every one of them empties a live projection basis
+ * (fddh_problem_projection_configure), since its stored images A X would no longer be the operator's, and drops the
+ * point-Jacobi diagonal, its inverses, the Chebyshev-Jacobi eigenvalue bound and the first step's scaling, which are made
+ * again at next use; a table also replaces the inner solve's host and float copies of it and their lean verdicts; the
+ * shift and kappa also rebuild a hierarchy that fddh_problem_amg_build made (one that was handed in is the caller's and
+ * stays).  A shift of zero on a problem that has none changes nothing and empties nothing.  Solver options and the other
+ * flags leave all of it alone.
  * Refused on a live problem, with an error that names the option, the option keeping its value (the closed list of
  * refused transitions; tests/reconfigure_walks.py REFUSED matches it line for line):
  *   "amg_cheby_order"          a new value once a hierarchy has been handed in (fddh_problem_amg_add_level): its
@@ -362,9 +367,9 @@ int fddh_field_weak_divergence(fddh_problem *p, const double *vx, const double *
  * kept as one node vector, cbar[n] = sum over the copies p of node n of lambda_p * B_p (B: fddh_field_mass; the products in
  * double on the host, summed in the column order of the row of the gather matrix, fddh_problem_csr(1)), which the outer
  * solve adds behind its operator application (q^ += cbar .* p~) and the inner solve, renumbered to its dofs, behind its
- * own; the exact diagonal of the inner operator, the Chebyshev-Jacobi bound and a hierarchy built by fddh_problem_amg_build
- * (built again, on the host, with cbar on the diagonal of its level-0 matrix) follow, a hierarchy that was handed in does
- * not.  An all-zero shift switches the term off: every solve then has the bits it had before a shift was ever set.
+ * own; what hangs on the operator follows as said once at fddh_problem_set_flag (operator_changed): a hierarchy built by
+ * fddh_problem_amg_build is built again, on the host, with cbar on the diagonal of its level-0 matrix, one that was handed
+ * in is not.  An all-zero shift switches the term off: every solve then has the bits it had before a shift was ever set.
  * fddh_problem_solve / _solve_timed / _pcg_* / _precond_apply / _sub_dof_op / _sub_jacobi_diagonal / _sub_dof_solve follow a
  * set shift; the right-hand side of a manufactured solution is stiffness(u*) + lambda B u*, formed by the caller.
  * Refused, the problem staying usable: more than one rank, a composite Subdomain, a 2-D problem, poly_degree > 15, a kernel
@@ -387,9 +392,10 @@ int fddh_helmholtz_node_operator(fddh_problem *p, const double *v_nodes, double 
  * on the host, all six g) replace the mesh's in the device buffers every stiffness kernel reads; the mesh's own arrays are
  * not written (fddh_problem_mesh_array("g_1".."g_6") keeps returning them), and setting again or clearing (NULL) starts
  * from them.  What is derived from the factor arrays is derived again: the zero-factor, shared-block and (where that option
- * is on) affine verdicts, the float copies, the exact diagonal of the inner operator, the Chebyshev-Jacobi bound, and a
- * hierarchy built by fddh_problem_amg_build (built again on the host, each tetrahedron of the low-order matrix scaled by the
- * mean of kappa at its four vertices); a hierarchy that was handed in stays.  The projection basis is cleared;
+ * is on) affine verdicts and the float copies where the arrays are rewritten; the rest of what hangs on the operator as said
+ * once at fddh_problem_set_flag (operator_changed): a hierarchy built by fddh_problem_amg_build is built again on the host,
+ * each tetrahedron of the low-order matrix scaled by the mean of kappa at its four vertices; a hierarchy that was handed in
+ * stays.  The projection basis is cleared by every accepted call that sets kappa or clears one that was set;
  * fddh_problem_solve_projected stays allowed.  A Helmholtz shift is independent and keeps the unscaled mass.
  * fddh_problem_stiffness / _make_rhs_from / _solve* / _pcg_* / _precond_apply / _sub_dof_op / _sub_jacobi_diagonal /
  * _sub_dof_solve / _amg_build and fddh_helmholtz_node_operator follow a set kappa; fddh_field_* are geometry and do not.

@@ -1036,20 +1036,6 @@ __global__ __launch_bounds__(kBlock, 4) void line_stiffness_kernel_t(T *__restri
     }
 }
 
-// kShared by whether factor_elem is given
-template <typename T, int kLean>
-int launch_lines_t(T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const GPtrsT<T> &G, const int *elem_offset, const int *factor_elem, int num_elements, void *stream)
-{
-    const int grid = (num_elements + LineCfg::epb - 1) / LineCfg::epb;
-    fdd_for_bool(factor_elem != nullptr, [&](auto shared) {
-        for_gather_nt_store(point_dof, [&](auto gather, auto nt) {
-            hipLaunchKernelGGL((line_stiffness_kernel_t<T, decltype(gather)::value, decltype(nt)::value, decltype(shared)::value, kLean>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem, LineDirect<T, 0>{});
-        });
-    });
-    FDD_LAUNCH_CHECK();
-    return 0;
-}
-
 // FDD_TUNE_ASSEMBLE_NT_STORE, read once: non-temporal stores of the rows of y the kDirect instances complete.  0: the next
 // kernels read y (the multi-dot, the update), and non-temporal stores of such vectors measured slower before (HISTORY)
 inline bool assemble_nt_store()
@@ -1058,93 +1044,34 @@ inline bool assemble_nt_store()
     return nt_store;
 }
 
-// the kDirect instances: double and gather only; kShared by whether factor_elem is given
-template <int kLean>
-int launch_lines_direct(double *Au, double *y, const double *u, const int *point_class_dof, const double *u_scale, const double *D_hat, const GPtrsT<double> &G, const int *elem_offset, const int *factor_elem, int num_elements, void *stream)
+// The one launcher of the degree-7 line kernel: which instance the run-time arguments name.
+//   factor_elem given -> kShared -- never with kCoef, whose block_of_elem goes where factor_elem does and whose G is not read
+//   direct_y given    -> kDirect 1 or 2 by assemble_nt_store(): double and gather only, which the dispatcher has checked
+//   kLean, kCoef      -> the caller's; kDirectToo = false compiles no kDirect instance of this kLean
+template <typename T, int kLean, bool kCoef, bool kDirectToo = true>
+int launch_lines(T *Au, T *direct_y, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const GPtrsT<T> &G, const LineCoef<kCoef> &cf, const int *elem_offset, const int *factor_elem, int num_elements, void *stream)
 {
     const int grid = (num_elements + LineCfg::epb - 1) / LineCfg::epb;
-    fdd_for_bool(factor_elem != nullptr, [&](auto shared) {
+    auto launch = [&](auto gather, auto nt, auto shared, auto direct_kind) {
+        constexpr int kDirect = decltype(direct_kind)::value;
+        LineDirect<T, kDirect> direct;
+        if constexpr (kDirect != 0) direct.y = direct_y;
+        hipLaunchKernelGGL((line_stiffness_kernel_t<T, decltype(gather)::value, decltype(nt)::value, decltype(shared)::value, kLean, kDirect, kCoef>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem, direct, cf);
+    };
+    auto with_shared = [&](auto shared) {
         fdd_for_bool(stiffness_nt_store(), [&](auto nt) {
-            fdd_for_bool(assemble_nt_store(), [&](auto nt_y) {
-                constexpr int kDirect = decltype(nt_y)::value ? 2 : 1;
-                hipLaunchKernelGGL((line_stiffness_kernel_t<double, true, decltype(nt)::value, decltype(shared)::value, kLean, kDirect>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_class_dof, u_scale, D_hat, G, elem_offset, num_elements, factor_elem, LineDirect<double, kDirect>{y});
-            });
+            if constexpr (sizeof(T) == 8 and kDirectToo)
+                if (direct_y != nullptr)
+                    return fdd_for_bool(assemble_nt_store(), [&](auto nt_y) { launch(std::true_type{}, nt, shared, std::integral_constant<int, decltype(nt_y)::value ? 2 : 1>{}); });
+            fdd_for_bool(point_dof != nullptr, [&](auto gather) { launch(gather, nt, shared, std::integral_constant<int, 0>{}); });
         });
-    });
+    };
+    if constexpr (kCoef)
+        with_shared(std::false_type{});
+    else
+        fdd_for_bool(factor_elem != nullptr, with_shared);
     FDD_LAUNCH_CHECK();
     return 0;
-}
-
-// the kCoef instances: block_of_elem goes where factor_elem does, G is not read.  direct_y given: the kDirect instance
-// (double with point_dof only, which the entry has checked)
-template <typename T, int kLean>
-int launch_lines_coef(T *Au, T *direct_y, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const LineCoef<true> &cf, const int *elem_offset, const int *block_of_elem, int num_elements, void *stream)
-{
-    const int grid = (num_elements + LineCfg::epb - 1) / LineCfg::epb;
-    if constexpr (sizeof(T) == 8)
-        if (direct_y != nullptr)
-        {
-            fdd_for_bool(stiffness_nt_store(), [&](auto nt) {
-                fdd_for_bool(assemble_nt_store(), [&](auto nt_y) {
-                    constexpr int kDirect = decltype(nt_y)::value ? 2 : 1;
-                    hipLaunchKernelGGL((line_stiffness_kernel_t<double, true, decltype(nt)::value, false, kLean, kDirect, true>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, GPtrsT<double>{}, elem_offset, num_elements, block_of_elem, LineDirect<double, kDirect>{direct_y}, cf);
-                });
-            });
-            FDD_LAUNCH_CHECK();
-            return 0;
-        }
-    for_gather_nt_store(point_dof, [&](auto gather, auto nt) {
-        hipLaunchKernelGGL((line_stiffness_kernel_t<T, decltype(gather)::value, decltype(nt)::value, false, kLean, 0, true>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), Au, u, point_dof, u_scale, D_hat, GPtrsT<T>{}, elem_offset, num_elements, block_of_elem, LineDirect<T, 0>{}, cf);
-    });
-    FDD_LAUNCH_CHECK();
-    return 0;
-}
-
-// The three entries of the coefficient form (fdd_stiffness_matrix_lines_coef[_f32|_direct]); every refusal comes before
-// anything is touched, the degree first.  An output may not be one of the inputs: not the same address, and where the
-// elements lie one after another (elem_offset null) no input may start inside the points Au covers
-template <typename T>
-int lines_coef_dispatch(T *Au, T *direct_y, bool direct, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const double *coef, const double *const blocks[3], const int *block_of_elem, const int *elem_offset, int lean, int num_elements, int poly_degree, int diag, void *stream)
-{
-    if (poly_degree != 7)
-    {
-        fdd_set_error("the coefficient line form of the stiffness kernel supports poly_degree 7 only, got %d", poly_degree);
-        return FDD_ERR_UNSUPPORTED;
-    }
-    if (diag != 1)
-    {
-        fdd_set_error("the coefficient line form of the stiffness kernel exists on three factor arrays only (diag = 1), got diag = %d", diag);
-        return FDD_ERR_UNSUPPORTED;
-    }
-    FDD_REQUIRE(num_elements >= 0);
-    FDD_REQUIRE(coef != nullptr && blocks != nullptr && blocks[0] != nullptr && blocks[1] != nullptr && blocks[2] != nullptr && block_of_elem != nullptr);
-    FDD_REQUIRE(Au != nullptr && u != nullptr && D_hat != nullptr);
-    FDD_REQUIRE(not direct || (point_dof != nullptr && direct_y != nullptr));
-    {
-        const char *lo = (const char *)Au, *hi = lo + (elem_offset ? sizeof(T) : (size_t)num_elements * LineCfg::n3 * sizeof(T));
-        const void *inputs[] = {u, point_dof, u_scale, D_hat, coef, blocks[0], blocks[1], blocks[2], block_of_elem, elem_offset};
-        for (const void *in : inputs)
-        {
-            const bool in_Au = (const char *)in >= lo && (const char *)in < hi;
-            if (in != nullptr && (in_Au || (direct && in == (const void *)direct_y)))
-            {
-                fdd_set_error("the coefficient line form of the stiffness kernel: an output overlaps an input");
-                return FDD_ERR_INVALID_ARGUMENT;
-            }
-        }
-        if (direct && (const char *)direct_y >= lo && (const char *)direct_y < hi)
-        {
-            fdd_set_error("the coefficient line form of the stiffness kernel: y overlaps Au");
-            return FDD_ERR_INVALID_ARGUMENT;
-        }
-    }
-    if (num_elements == 0) return 0;
-    LineCoef<true> cf;
-    cf.coef = coef;
-    for (int g = 0; g < 3; g++) cf.blk[g] = blocks[g];
-    constexpr int kParts = sizeof(T) == 8 ? (kLeanTerms | kLeanResident) : kLeanTerms; // the lean entries' parts
-    if (lean != 0) return launch_lines_coef<T, kParts>(Au, direct ? direct_y : nullptr, u, point_dof, u_scale, D_hat, cf, elem_offset, block_of_elem, num_elements, stream);
-    return launch_lines_coef<T, 0>(Au, direct ? direct_y : nullptr, u, point_dof, u_scale, D_hat, cf, elem_offset, block_of_elem, num_elements, stream);
 }
 
 // A development build (-DFDD_LEAN_LINE_DEV) compiles both choices of the lean parts for both precisions and exports
@@ -1159,7 +1086,7 @@ extern "C" int fdd_dev_lean_line_parts(int parts)
 }
 #endif
 
-// The three entries of the line form; every refusal comes before the output is touched.
+// The entries of the line form; every refusal comes before the output is touched.
 // streamed (fdd_stiffness_matrix_lines[_f32]): diag = 1: three factor arrays, G[3..5] are not passed on (never dereferenced).
 //   diag = 0: six arrays -- that form was built and timed (see above), was not ahead of the slab form and is not compiled in
 // shared (fdd_stiffness_matrix_lines_shared[_f32]): factor_elem names the element whose factor block each element reads;
@@ -1167,31 +1094,75 @@ extern "C" int fdd_dev_lean_line_parts(int parts)
 // lean (fdd_stiffness_matrix_lines_lean[_f32]): the kLean instances, shared where factor_elem is given and streamed where it
 //   is null; degree 7 on three arrays only.  The caller's guarantee about D_hat is in fdd_hip.h.  Double runs both parts,
 //   float kLeanTerms (see above)
+// coef (fdd_stiffness_matrix_lines_coef[_f32|_direct]): the kCoef instances, lean where the entry's `lean` says so; G is null,
+//   cf holds the coefficient and the unscaled blocks, factor_elem is block_of_elem.  These entries refuse the degree first
+//   and an empty list last, and an output may not be one of the inputs: not the same address, and where the elements lie one
+//   after another (elem_offset null) no input may start inside the points Au covers.  The others allow Au == u
 enum class LineEntry
 {
     streamed,
     shared,
-    lean
+    lean,
+    coef
 };
-// direct (fdd_stiffness_matrix_lines_direct): the kDirect instance of the entry's kernel, which completes rows of direct_y;
-//   double with point_dof only
-template <typename T>
-int lines_dispatch(LineEntry entry, T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const T *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream, bool direct = false, T *direct_y = nullptr)
+// what the coefficient entries bring besides: the coefficient per point, the distinct unscaled blocks, and whether to run lean
+struct LineCoefArgs
 {
-    if (entry == LineEntry::shared && diag != 1)
+    const double *coef;
+    const double *const *blocks;
+    int lean;
+};
+// the coefficient entries' own checks of their pointers, in their order; block_of_elem goes where factor_elem does
+template <typename T>
+int lines_coef_check(const LineCoefArgs &ca, T *Au, T *direct_y, bool direct, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const int *block_of_elem, const int *elem_offset, int num_elements)
+{
+    FDD_REQUIRE(ca.coef != nullptr && ca.blocks != nullptr && ca.blocks[0] != nullptr && ca.blocks[1] != nullptr && ca.blocks[2] != nullptr && block_of_elem != nullptr);
+    FDD_REQUIRE(Au != nullptr && u != nullptr && D_hat != nullptr);
+    FDD_REQUIRE(not direct || (point_dof != nullptr && direct_y != nullptr));
+    const char *lo = (const char *)Au, *hi = lo + (elem_offset ? sizeof(T) : (size_t)num_elements * LineCfg::n3 * sizeof(T));
+    const void *inputs[] = {u, point_dof, u_scale, D_hat, ca.coef, ca.blocks[0], ca.blocks[1], ca.blocks[2], block_of_elem, elem_offset};
+    for (const void *in : inputs)
     {
-        fdd_set_error("the shared-block line form of the stiffness kernel exists on three factor arrays only (diag = 1), got diag = %d", diag);
+        const bool in_Au = (const char *)in >= lo && (const char *)in < hi;
+        if (in != nullptr && (in_Au || (direct && in == (const void *)direct_y)))
+        {
+            fdd_set_error("the coefficient line form of the stiffness kernel: an output overlaps an input");
+            return FDD_ERR_INVALID_ARGUMENT;
+        }
+    }
+    if (direct && (const char *)direct_y >= lo && (const char *)direct_y < hi)
+    {
+        fdd_set_error("the coefficient line form of the stiffness kernel: y overlaps Au");
+        return FDD_ERR_INVALID_ARGUMENT;
+    }
+    return 0;
+}
+// direct (fdd_stiffness_matrix_lines_direct, _coef_direct): the kDirect instance of the entry's kernel, which completes rows of
+//   direct_y; double with point_dof only.  ca: the coefficient entries' and only theirs
+template <typename T>
+int lines_dispatch(LineEntry entry, T *Au, const T *u, const int *point_dof, const double *u_scale, const T *D_hat, const T *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, const int *factor_elem, int num_elements, int poly_degree, int diag, void *stream, bool direct = false, T *direct_y = nullptr, const LineCoefArgs &ca = {})
+{
+    static const char *const names[] = {"the line form", "the shared-block line form", "the lean line form", "the coefficient line form"};
+    const bool coef = entry == LineEntry::coef;
+    if (poly_degree != 7 && coef)
+    {
+        fdd_set_error("%s of the stiffness kernel supports poly_degree 7 only, got %d", names[(int)entry], poly_degree);
+        return FDD_ERR_UNSUPPORTED;
+    }
+    if ((entry == LineEntry::shared || coef) && diag != 1)
+    {
+        fdd_set_error("%s of the stiffness kernel exists on three factor arrays only (diag = 1), got diag = %d", names[(int)entry], diag);
         return FDD_ERR_UNSUPPORTED;
     }
     FDD_REQUIRE(num_elements >= 0 && (entry == LineEntry::lean || diag == 0 || diag == 1));
     if (entry == LineEntry::lean && (poly_degree != 7 || diag != 1))
     {
-        fdd_set_error("the lean line form of the stiffness kernel supports poly_degree 7 on three factor arrays (diag = 1) only, got poly_degree %d, diag = %d", poly_degree, diag);
+        fdd_set_error("%s of the stiffness kernel supports poly_degree 7 on three factor arrays (diag = 1) only, got poly_degree %d, diag = %d", names[(int)entry], poly_degree, diag);
         return FDD_ERR_UNSUPPORTED;
     }
     if (poly_degree != 7)
     {
-        fdd_set_error("the line form of the stiffness kernel supports poly_degree 7 only, got %d", poly_degree);
+        fdd_set_error("%s of the stiffness kernel supports poly_degree 7 only, got %d", names[0], poly_degree);
         return FDD_ERR_UNSUPPORTED;
     }
     if (diag == 0)
@@ -1199,25 +1170,31 @@ int lines_dispatch(LineEntry entry, T *Au, const T *u, const int *point_dof, con
         fdd_set_error("the line form of the stiffness kernel on six factor arrays measured no faster than the slab form and is not compiled in (diag = 0)");
         return FDD_ERR_UNSUPPORTED;
     }
-    if (num_elements == 0) return 0;
-    FDD_REQUIRE(Au != nullptr && u != nullptr && D_hat != nullptr && G != nullptr);
-    FDD_REQUIRE(entry != LineEntry::shared || factor_elem != nullptr);
-    FDD_REQUIRE(not direct || (point_dof != nullptr && direct_y != nullptr && (const void *)direct_y != (const void *)u && (const void *)direct_y != (const void *)Au));
-    GPtrsT<T> g;
-    if (int rc = fdd_three_factors(g, G)) return rc;
-    if constexpr (sizeof(T) == 8)
-        if (direct)
-        {
-            if (entry != LineEntry::lean) return launch_lines_direct<0>(Au, direct_y, u, point_dof, u_scale, D_hat, g, elem_offset, entry == LineEntry::shared ? factor_elem : nullptr, num_elements, stream);
-            return launch_lines_direct<(kLeanTerms | kLeanResident)>(Au, direct_y, u, point_dof, u_scale, D_hat, g, elem_offset, factor_elem, num_elements, stream);
-        }
-    if (entry != LineEntry::lean) return launch_lines_t<T, 0>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, entry == LineEntry::shared ? factor_elem : nullptr, num_elements, stream);
-    constexpr int kParts = sizeof(T) == 8 ? (kLeanTerms | kLeanResident) : kLeanTerms;
+    GPtrsT<T> g{};
+    if (coef)
+    {
+        if (int rc = lines_coef_check<T>(ca, Au, direct_y, direct, u, point_dof, u_scale, D_hat, factor_elem, elem_offset, num_elements)) return rc;
+        if (num_elements == 0) return 0;
+    }
+    else
+    {
+        if (num_elements == 0) return 0;
+        FDD_REQUIRE(Au != nullptr && u != nullptr && D_hat != nullptr && G != nullptr);
+        FDD_REQUIRE(entry != LineEntry::shared || factor_elem != nullptr);
+        FDD_REQUIRE(not direct || (point_dof != nullptr && direct_y != nullptr && (const void *)direct_y != (const void *)u && (const void *)direct_y != (const void *)Au));
+        if (int rc = fdd_three_factors(g, G)) return rc;
+    }
+    const LineCoef<true> cf = coef ? LineCoef<true>{ca.coef, {ca.blocks[0], ca.blocks[1], ca.blocks[2]}} : LineCoef<true>{};
+    T *y = direct ? direct_y : nullptr;
+    constexpr int kParts = sizeof(T) == 8 ? (kLeanTerms | kLeanResident) : kLeanTerms; // the lean entries' parts
+    if (coef && ca.lean != 0) return launch_lines<T, kParts, true>(Au, y, u, point_dof, u_scale, D_hat, g, cf, elem_offset, factor_elem, num_elements, stream);
+    if (coef) return launch_lines<T, 0, true>(Au, y, u, point_dof, u_scale, D_hat, g, cf, elem_offset, factor_elem, num_elements, stream);
+    if (entry != LineEntry::lean) return launch_lines<T, 0, false>(Au, y, u, point_dof, u_scale, D_hat, g, {}, elem_offset, entry == LineEntry::shared ? factor_elem : nullptr, num_elements, stream);
 #ifdef FDD_LEAN_LINE_DEV
     constexpr int kOther = kParts ^ kLeanResident;
-    if (g_lean_line_parts == kOther) return launch_lines_t<T, kOther>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, factor_elem, num_elements, stream);
+    if (y == nullptr && g_lean_line_parts == kOther) return launch_lines<T, kOther, false, false>(Au, y, u, point_dof, u_scale, D_hat, g, {}, elem_offset, factor_elem, num_elements, stream);
 #endif
-    return launch_lines_t<T, kParts>(Au, u, point_dof, u_scale, D_hat, g, elem_offset, factor_elem, num_elements, stream);
+    return launch_lines<T, kParts, false>(Au, y, u, point_dof, u_scale, D_hat, g, {}, elem_offset, factor_elem, num_elements, stream);
 }
 
 // ---- factor blocks that repeat from element to element (the kShared line instance) ----
@@ -1650,17 +1627,17 @@ int fdd_stiffness_matrix_lines_lean_f32(float *Au, const float *v, const double 
 
 int fdd_stiffness_matrix_lines_coef(double *Au, const double *v, const double *v_scale_dev, const int *point_dof, const double *D_hat, const double *coef, const double *const blocks[3], const int *block_of_elem, const int *elem_offset, int lean, int num_elements, int poly_degree, int diag, void *stream)
 {
-    return lines_coef_dispatch<double>(Au, nullptr, false, v, point_dof, v_scale_dev, D_hat, coef, blocks, block_of_elem, elem_offset, lean, num_elements, poly_degree, diag, stream);
+    return lines_dispatch<double>(LineEntry::coef, Au, v, point_dof, v_scale_dev, D_hat, nullptr, elem_offset, block_of_elem, num_elements, poly_degree, diag, stream, false, nullptr, {coef, blocks, lean});
 }
 
 int fdd_stiffness_matrix_lines_coef_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const double *coef, const double *const blocks[3], const int *block_of_elem, const int *elem_offset, int lean, int num_elements, int poly_degree, int diag, void *stream)
 {
-    return lines_coef_dispatch<float>(Au, nullptr, false, v, point_dof, v_scale_dev, D_hat, coef, blocks, block_of_elem, elem_offset, lean, num_elements, poly_degree, diag, stream);
+    return lines_dispatch<float>(LineEntry::coef, Au, v, point_dof, v_scale_dev, D_hat, nullptr, elem_offset, block_of_elem, num_elements, poly_degree, diag, stream, false, nullptr, {coef, blocks, lean});
 }
 
 int fdd_stiffness_matrix_lines_coef_direct(double *Au, double *y, const double *v, const double *v_scale_dev, const int *point_class_dof, const double *D_hat, const double *coef, const double *const blocks[3], const int *block_of_elem, const int *elem_offset, int lean, int num_elements, int poly_degree, int diag, void *stream)
 {
-    return lines_coef_dispatch<double>(Au, y, true, v, point_class_dof, v_scale_dev, D_hat, coef, blocks, block_of_elem, elem_offset, lean, num_elements, poly_degree, diag, stream);
+    return lines_dispatch<double>(LineEntry::coef, Au, v, point_class_dof, v_scale_dev, D_hat, nullptr, elem_offset, block_of_elem, num_elements, poly_degree, diag, stream, true, y, {coef, blocks, lean});
 }
 
 constexpr int kFactorBlockGrid = 1 << 20; // workgroups; beyond it a workgroup takes several elements in turn

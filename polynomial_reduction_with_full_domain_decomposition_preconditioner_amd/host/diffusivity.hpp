@@ -33,34 +33,26 @@ namespace fdd
 namespace diffusivity
 {
 
+// a refusal's text with its numbers in it
+template <typename... Args>
+inline std::string formatted(const char *format, Args... args)
+{
+    char msg[256];
+    snprintf(msg, sizeof(msg), format, args...);
+    return msg;
+}
+
 // Why a kappa of n values cannot be set on a problem of num_points fine-level points, or "": nothing is touched before this
 // has passed.  The first offending point is named.
 inline std::string refusal(const double *kappa, long long n, long long num_points, int dim, int ranks, bool composite)
 {
-    char msg[256];
-    if (ranks > 1)
-    {
-        snprintf(msg, sizeof(msg), "a diffusivity is supported on one rank: this communicator has %d", ranks);
-        return msg;
-    }
+    if (ranks > 1) return formatted("a diffusivity is supported on one rank: this communicator has %d", ranks);
     if (composite) return "a diffusivity needs a conforming region: this problem's Subdomain is a composite (its rings would need the neighbours' kappa at reduced degree)";
-    if (dim != 3)
-    {
-        snprintf(msg, sizeof(msg), "a diffusivity is 3-D only: this problem is %d-D", dim);
-        return msg;
-    }
+    if (dim != 3) return formatted("a diffusivity is 3-D only: this problem is %d-D", dim);
     if (kappa == nullptr) return "";
-    if (n != num_points)
-    {
-        snprintf(msg, sizeof(msg), "kappa has one value per point of the fine level (%lld), got %lld", num_points, n);
-        return msg;
-    }
+    if (n != num_points) return formatted("kappa has one value per point of the fine level (%lld), got %lld", num_points, n);
     for (long long p = 0; p < n; p++)
-        if (not std::isfinite(kappa[p]) or not(kappa[p] > 0.0))
-        {
-            snprintf(msg, sizeof(msg), "kappa must be finite and > 0 at every point: point %lld has %g", p, kappa[p]);
-            return msg;
-        }
+        if (not std::isfinite(kappa[p]) or not(kappa[p] > 0.0)) return formatted("kappa must be finite and > 0 at every point: point %lld has %g", p, kappa[p]);
     return "";
 }
 

@@ -1018,8 +1018,8 @@ class Domain
     // kappa over the fine level's points (the caller has checked it, fdd::diffusivity::refusal); nullptr clears.  The scaled
     // arrays G' = mesh.g * kappa go into the buffers the list -- and the Subdomain's level-0 list, which aliases them -- already
     // reads, what is derived from a list's arrays is derived again, and a list whose unscaled blocks repeat gets the members of
-    // the coefficient line instance.  mesh.g is never written: setting again or clearing starts from it.  The caller clears
-    // the projection basis and tells the Subdomain (Subdomain::set_diffusivity).
+    // the coefficient line instance.  mesh.g is never written: setting again or clearing starts from it.  The caller tells
+    // the Subdomain (Subdomain::set_diffusivity) and ends in the C API's operator_changed.
     bool diffusivity_is_set = false; // the Subdomain keeps the values (its hierarchy is built from them)
     fdd::diffusivity::UnscaledBlocks unscaled_blocks;
     bool diffusivity_active() const { return diffusivity_is_set; }

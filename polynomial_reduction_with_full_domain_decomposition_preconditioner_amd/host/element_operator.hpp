@@ -270,7 +270,8 @@ inline bool lean_table_ok(const Real *D)
 }
 
 // The float table is the cast to_float makes of the double one when the single-precision inner solve is prepared
-// (Subdomain::prepare_single_precision) and is not remade afterwards: the verdict on it follows the same rule.
+// (Subdomain::prepare_single_precision) and again when the table changes under it (Subdomain::operator_changed): the verdict
+// on it is made wherever the cast is.
 inline void check_lean_table32(LevelList &ll, const std::vector<double> &D)
 {
     const std::vector<float> D32(D.begin(), D.end());
@@ -365,49 +366,38 @@ inline StiffnessProfile stiffness_profile(StiffnessForm form, const StiffnessCho
     {
         StiffnessForm form;
         F family;
-        bool shared, lean;
+        bool shared, lean, coef;
         const char *label, *label32;
         double bytes, bytes32;
     } table[] = {
-        {StiffnessForm::local, F::mfma_diag, false, false, "mfma_diag_stiffness_kernel", nullptr, 40.0, 0.0},
-        {StiffnessForm::local, F::mfma, false, false, "mfma_stiffness_kernel", nullptr, 64.0, 0.0},
-        {StiffnessForm::local, F::lines, false, false, "line_stiffness_kernel", nullptr, 40.0, 0.0},
-        {StiffnessForm::local, F::lines, true, false, "line_stiffness_kernel<shared>", nullptr, 16.0, 0.0},
-        {StiffnessForm::local, F::lines, false, true, "line_stiffness_kernel<lean>", nullptr, 40.0, 0.0},
-        {StiffnessForm::local, F::lines, true, true, "line_stiffness_kernel<shared,lean>", nullptr, 16.0, 0.0},
-        {StiffnessForm::local, F::diag, false, false, "diag_stiffness_kernel", nullptr, 40.0, 0.0},
-        {StiffnessForm::local, F::fused, false, false, "fused_stiffness_kernel", nullptr, 64.0, 0.0},
-        {StiffnessForm::local, F::fused_2d, false, false, "fused_stiffness_2d_kernel", nullptr, 40.0, 0.0},
-        {StiffnessForm::gather, F::affine, false, false, "fused_stiffness_kernel<gather,affine>", "fused_stiffness_kernel<gather,f32,affine>", 12.0, 8.0},
-        {StiffnessForm::gather, F::mfma_affine, false, false, "mfma_stiffness_kernel<gather,affine>", nullptr, 12.0, 0.0},
-        {StiffnessForm::gather, F::mfma_diag, false, false, "mfma_diag_stiffness_kernel<gather>", nullptr, 36.0, 0.0},
-        {StiffnessForm::gather, F::lines, false, false, "line_stiffness_kernel<gather>", "line_stiffness_kernel<gather,f32>", 36.0, 20.0},
-        {StiffnessForm::gather, F::lines, true, false, "line_stiffness_kernel<gather,shared>", "line_stiffness_kernel<gather,shared,f32>", 12.0, 8.0},
-        {StiffnessForm::gather, F::lines, false, true, "line_stiffness_kernel<gather,lean>", "line_stiffness_kernel<gather,f32,lean>", 36.0, 20.0},
-        {StiffnessForm::gather, F::lines, true, true, "line_stiffness_kernel<gather,shared,lean>", "line_stiffness_kernel<gather,shared,f32,lean>", 12.0, 8.0},
-        {StiffnessForm::gather, F::diag, false, false, "diag_stiffness_kernel<gather>", "diag_stiffness_kernel<gather,f32>", 36.0, 20.0},
-        {StiffnessForm::gather, F::fused, false, false, "fused_stiffness_kernel<gather>", "fused_stiffness_kernel<gather,f32>", 60.0, 32.0},
-        {StiffnessForm::gather, F::mfma, false, false, "mfma_stiffness_kernel<gather>", nullptr, 60.0, 0.0},
+        {StiffnessForm::local, F::mfma_diag, false, false, false, "mfma_diag_stiffness_kernel", nullptr, 40.0, 0.0},
+        {StiffnessForm::local, F::mfma, false, false, false, "mfma_stiffness_kernel", nullptr, 64.0, 0.0},
+        {StiffnessForm::local, F::lines, false, false, false, "line_stiffness_kernel", nullptr, 40.0, 0.0},
+        {StiffnessForm::local, F::lines, true, false, false, "line_stiffness_kernel<shared>", nullptr, 16.0, 0.0},
+        {StiffnessForm::local, F::lines, false, true, false, "line_stiffness_kernel<lean>", nullptr, 40.0, 0.0},
+        {StiffnessForm::local, F::lines, true, true, false, "line_stiffness_kernel<shared,lean>", nullptr, 16.0, 0.0},
+        // the coefficient instances: the shared instance's bytes plus one double per point for the coefficient, in both
+        // precisions (its second and third read per element are expected to come from cache: derived)
+        {StiffnessForm::local, F::lines, false, false, true, "line_stiffness_kernel<coef>", nullptr, 24.0, 0.0},
+        {StiffnessForm::local, F::lines, false, true, true, "line_stiffness_kernel<coef,lean>", nullptr, 24.0, 0.0},
+        {StiffnessForm::local, F::diag, false, false, false, "diag_stiffness_kernel", nullptr, 40.0, 0.0},
+        {StiffnessForm::local, F::fused, false, false, false, "fused_stiffness_kernel", nullptr, 64.0, 0.0},
+        {StiffnessForm::local, F::fused_2d, false, false, false, "fused_stiffness_2d_kernel", nullptr, 40.0, 0.0},
+        {StiffnessForm::gather, F::affine, false, false, false, "fused_stiffness_kernel<gather,affine>", "fused_stiffness_kernel<gather,f32,affine>", 12.0, 8.0},
+        {StiffnessForm::gather, F::mfma_affine, false, false, false, "mfma_stiffness_kernel<gather,affine>", nullptr, 12.0, 0.0},
+        {StiffnessForm::gather, F::mfma_diag, false, false, false, "mfma_diag_stiffness_kernel<gather>", nullptr, 36.0, 0.0},
+        {StiffnessForm::gather, F::lines, false, false, false, "line_stiffness_kernel<gather>", "line_stiffness_kernel<gather,f32>", 36.0, 20.0},
+        {StiffnessForm::gather, F::lines, true, false, false, "line_stiffness_kernel<gather,shared>", "line_stiffness_kernel<gather,shared,f32>", 12.0, 8.0},
+        {StiffnessForm::gather, F::lines, false, true, false, "line_stiffness_kernel<gather,lean>", "line_stiffness_kernel<gather,f32,lean>", 36.0, 20.0},
+        {StiffnessForm::gather, F::lines, true, true, false, "line_stiffness_kernel<gather,shared,lean>", "line_stiffness_kernel<gather,shared,f32,lean>", 12.0, 8.0},
+        {StiffnessForm::gather, F::lines, false, false, true, "line_stiffness_kernel<gather,coef>", "line_stiffness_kernel<gather,coef,f32>", 20.0, 16.0},
+        {StiffnessForm::gather, F::lines, false, true, true, "line_stiffness_kernel<gather,coef,lean>", "line_stiffness_kernel<gather,coef,f32,lean>", 20.0, 16.0},
+        {StiffnessForm::gather, F::diag, false, false, false, "diag_stiffness_kernel<gather>", "diag_stiffness_kernel<gather,f32>", 36.0, 20.0},
+        {StiffnessForm::gather, F::fused, false, false, false, "fused_stiffness_kernel<gather>", "fused_stiffness_kernel<gather,f32>", 60.0, 32.0},
+        {StiffnessForm::gather, F::mfma, false, false, false, "mfma_stiffness_kernel<gather>", nullptr, 60.0, 0.0},
     };
-    // the coefficient instances: the shared instance's bytes plus one double per point for the coefficient, in both
-    // precisions (its second and third read per element are expected to come from cache: derived)
-    static const struct
-    {
-        StiffnessForm form;
-        bool lean;
-        const char *label, *label32;
-        double bytes, bytes32;
-    } coef_table[] = {
-        {StiffnessForm::local, false, "line_stiffness_kernel<coef>", nullptr, 24.0, 0.0},
-        {StiffnessForm::local, true, "line_stiffness_kernel<coef,lean>", nullptr, 24.0, 0.0},
-        {StiffnessForm::gather, false, "line_stiffness_kernel<gather,coef>", "line_stiffness_kernel<gather,coef,f32>", 20.0, 16.0},
-        {StiffnessForm::gather, true, "line_stiffness_kernel<gather,coef,lean>", "line_stiffness_kernel<gather,coef,f32,lean>", 20.0, 16.0},
-    };
-    if (c.coef_lines())
-        for (const auto &row : coef_table)
-            if (row.form == form and row.lean == c.lean) return {f32 ? row.label32 : row.label, f32 ? row.bytes32 : row.bytes};
     for (const auto &row : table)
-        if (row.form == form and row.family == c.family and row.shared == c.shared and row.lean == c.lean) return {f32 ? row.label32 : row.label, f32 ? row.bytes32 : row.bytes};
+        if (row.form == form and row.family == c.family and row.shared == c.shared and row.lean == c.lean and row.coef == c.coef) return {f32 ? row.label32 : row.label, f32 ? row.bytes32 : row.bytes};
     return {nullptr, 0.0};
 }
 
@@ -429,6 +419,14 @@ struct ListArrays
             D_hat = ll.D_hat, affine_c = ll.affine_c.as<double>(), affine_w = ll.affine_w.as<double>();
         }
     }
+};
+
+// the arguments of the coefficient entries that come from the list: double in both precisions
+struct CoefArrays
+{
+    const double *coef, *blocks[3];
+    const int *block_of_elem;
+    explicit CoefArrays(const LevelList &ll) : coef(ll.coef.as<double>()), blocks{ll.coef_blocks[0].as<double>(), ll.coef_blocks[1].as<double>(), ll.coef_blocks[2].as<double>()}, block_of_elem(ll.coef_block_of_elem.as<int>()) {}
 };
 
 // an entry of the kernel library by precision
@@ -456,10 +454,10 @@ inline bool launch_three_arrays(const StiffnessChoice &c, const LevelList &ll, R
     }
     else if (c.family != StiffnessFamily::lines)
         return false;
-    else if (c.coef) // the coefficient and the blocks are double in both precisions; the table is the precision's own
+    else if (c.coef) // the table is the precision's own
     {
-        const double *blocks[3] = {ll.coef_blocks[0].as<double>(), ll.coef_blocks[1].as<double>(), ll.coef_blocks[2].as<double>()};
-        FDD_CALL(entry_of<Real>(fdd_stiffness_matrix_lines_coef, fdd_stiffness_matrix_lines_coef_f32)(q, v, scale_dev, point_index, a.D_hat, ll.coef.as<double>(), blocks, ll.coef_block_of_elem.as<int>(), nullptr, c.lean ? 1 : 0, ll.num_elements, ll.poly_degree, 1, s));
+        const CoefArrays k(ll);
+        FDD_CALL(entry_of<Real>(fdd_stiffness_matrix_lines_coef, fdd_stiffness_matrix_lines_coef_f32)(q, v, scale_dev, point_index, a.D_hat, k.coef, k.blocks, k.block_of_elem, nullptr, c.lean ? 1 : 0, ll.num_elements, ll.poly_degree, 1, s));
     }
     else if (c.lean) // shared where factor_elem is given
         FDD_CALL(entry_of<Real>(fdd_stiffness_matrix_lines_lean, fdd_stiffness_matrix_lines_lean_f32)(q, v, scale_dev, point_index, a.D_hat, a.G, nullptr, factor_elem, ll.num_elements, ll.poly_degree, 1, s));
@@ -541,8 +539,8 @@ inline void apply_gather_direct(const LevelList &ll, double *q, double *y, const
     ProfileScope prof(p.label, p.bytes_per_point * (double)ll.num_points() + (double)sizeof(double) * gathered_values);
     if (c.coef)
     {
-        const double *blocks[3] = {ll.coef_blocks[0].as<double>(), ll.coef_blocks[1].as<double>(), ll.coef_blocks[2].as<double>()};
-        FDD_CALL(fdd_stiffness_matrix_lines_coef_direct(q, y, v, scale_dev, point_class_dof, ll.D_hat, ll.coef.as<double>(), blocks, ll.coef_block_of_elem.as<int>(), nullptr, c.lean ? 1 : 0, ll.num_elements, ll.poly_degree, 1, dev().stream));
+        const CoefArrays k(ll);
+        FDD_CALL(fdd_stiffness_matrix_lines_coef_direct(q, y, v, scale_dev, point_class_dof, ll.D_hat, k.coef, k.blocks, k.block_of_elem, nullptr, c.lean ? 1 : 0, ll.num_elements, ll.poly_degree, 1, dev().stream));
         return;
     }
     FDD_CALL(fdd_stiffness_matrix_lines_direct(q, y, v, scale_dev, point_class_dof, ll.D_hat, ll.G, nullptr, c.shared ? ll.factor_elem.as<int>() : nullptr, c.lean ? 1 : 0, ll.num_elements, ll.poly_degree, 1, dev().stream));

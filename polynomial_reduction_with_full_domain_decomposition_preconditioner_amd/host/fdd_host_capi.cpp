@@ -21,6 +21,7 @@
 #include "box_mesh.hpp"
 #include "domain.hpp"
 #include "field_ops.hpp"
+#include "helmholtz.hpp"
 #include "subdomain.hpp"
 
 typedef double SType; // config.hpp:19 STYPE
@@ -183,11 +184,13 @@ auto with_preconditioner(fddh_problem &p, bool use_subdomain, F &&f)
 
 // With a Helmholtz shift set (fddh_helmholtz_set): why a solve would not carry it, or nullptr.  The term lives in the
 // node-space outer loops and in Subdomain::operator_dofs and nowhere else, so whatever would run another loop is refused
-// when it starts (the flags may be set in any order).  inner: the inner solve alone; outer_gmres: the outer GMRES, else FCG
-const char *helmholtz_inner_refusal(fddh_problem &p)
+// when it starts (the flags may be set in any order).  inner: the inner solve alone (inner_fcg: called as the inner FCG);
+// outer_gmres: the outer GMRES, else FCG
+const char *helmholtz_inner_refusal(fddh_problem &p, bool inner_fcg = false)
 {
     if (!p.fine().shift_active() || !p.subdomain) return nullptr;
-    return p.subdomain->helmholtz_refusal();
+    if (const char *why = p.subdomain->helmholtz_refusal()) return why;
+    return inner_fcg ? "a Helmholtz shift needs the inner GMRES or Chebyshev-Jacobi in dof space: the inner FCG does not go through operator_dofs" : nullptr;
 }
 
 const char *helmholtz_outer_refusal(fddh_problem &p, bool outer_gmres)
@@ -197,6 +200,43 @@ const char *helmholtz_outer_refusal(fddh_problem &p, bool outer_gmres)
     const bool nodes = with_preconditioner(p, p.subdomain != nullptr, [&](auto &preconditioner) { return d.can_fcg_nodes(preconditioner); });
     if (!nodes || (outer_gmres && !d.restructured_outer)) return "a Helmholtz shift needs the node-space outer solve (assembled_outer_solve = 1, restructured_inner_solve = 1, the inner GMRES or Chebyshev-Jacobi in dof space): the point-space outer loops do not carry the term";
     return d.use_preconditioner ? helmholtz_inner_refusal(p) : nullptr;
+}
+
+// ---- an operator change: every entry that changes the operator of a live problem ends here ----
+// What hangs on the operator: (1) the projection basis and its images; in the Subdomain (2) the host copy of a level's table,
+// the lists' lean verdicts and the float table, (3) the exact Jacobi diagonal, its two inverses, the Chebyshev bound
+// cheby.lambda and operator_generation, with it the first step's scaling ChebyVectors::w, (4) the per-list verdicts, float
+// copies and coefficient members, (5) a hierarchy that amg_build made (one that was handed in is the caller's and stays).
+// (4) is read from arrays only kappa rewrites and is made again where they are rewritten (Domain::set_diffusivity,
+// Subdomain::set_diffusivity); the rest is emptied here, by what changed:
+struct OperatorChange
+{
+    enum Kind
+    {
+        table,      // a level's D_hat: (1) (2) (3).  The low-order matrix is assembled from the mesh, not from D_hat: (5) stays
+        arithmetic, // the element kernels' arithmetic (affine_geometry): (1) (3).  The values move by rounding only: (5) stays
+        shift,      // the Helmholtz term: (1) (3) (5), the term sits on the diagonal of the level-0 matrix.  A shift that was and stays off changes nothing
+        factors     // the factor arrays (kappa): (1) (3) (5), kappa scales the level-0 matrix
+    } kind;
+    int degree = -1; // table: the level's degree, the table, its size
+    const double *D = nullptr;
+    int n = 0;
+    bool was_active = false; // shift: was one set before the call
+
+    static OperatorChange of_table(int degree, const double *D, int n) { return {table, degree, D, n}; }
+    static OperatorChange of_shift(bool was_active) { return {shift, -1, nullptr, 0, was_active}; }
+};
+
+static void operator_changed(fddh_problem &p, const OperatorChange &c)
+{
+    Domain<SType> &d = p.fine();
+    if (c.kind == OperatorChange::shift && !c.was_active && !d.shift_active()) return;
+    d.projection.clear(); // (1): the basis and its images belong to the operator as it was
+    if (!p.subdomain) return;
+    const char *low_order_term = nullptr; // (5): what the printed line says was set or cleared
+    if (c.kind == OperatorChange::shift) low_order_term = d.shift_active() ? "Helmholtz shift set" : "Helmholtz shift cleared";
+    if (c.kind == OperatorChange::factors) low_order_term = d.diffusivity_active() ? "diffusivity set" : "diffusivity cleared";
+    p.subdomain->operator_changed(c.degree, c.D, c.n, low_order_term); // (2) where a table is given, (3) always
 }
 
 // fn() between finish + barrier (collective: every rank or none) and finish, the wall time into *seconds; seconds null: fn() alone
@@ -858,8 +898,7 @@ int fddh_problem_set_D_hat(fddh_problem *p, int level, const double *D_hat, int 
         if (level < 0 || level >= (int)pr.degrees.size()) return fail("bad argument");
         if (n != pr.degrees[level] + 1) return fail("D_hat of level %d is %d x %d", level, pr.degrees[level] + 1, pr.degrees[level] + 1);
         pr.domains[pr.degrees[level]].set_D_hat(D_hat, n);
-        pr.fine().projection.clear(); // the basis and its images belong to the operator as it was
-        if (pr.subdomain) pr.subdomain->operator_changed(pr.degrees[level], D_hat, n); // and so do the point-Jacobi diagonal and the Chebyshev bound
+        operator_changed(pr, OperatorChange::of_table(pr.degrees[level], D_hat, n));
         return 0;
     });
 }
@@ -1064,8 +1103,7 @@ static int set_affine_geometry(fddh_problem &p, const char *, int value)
 {
     for (auto &kv : p.domains) kv.second.set_affine_geometry(value != 0);
     if (p.subdomain) p.subdomain->set_affine_geometry(value != 0);
-    p.fine().projection.clear(); // the operator's arithmetic changes under the stored images
-    if (p.subdomain) p.subdomain->operator_changed();
+    operator_changed(p, {OperatorChange::arithmetic});
     return 0;
 }
 
@@ -1431,46 +1469,26 @@ int fddh_helmholtz_set(fddh_problem *p, double lambda, const double *lambda_poin
 {
     return on_problem(p, true, [&](fddh_problem &pr) {
         Domain<SType> &d = pr.fine();
-        if (const char *missing = fdd::missing_helmholtz_entry()) return fail("a Helmholtz shift needs %s, which the loaded kernel library does not export", missing);
-        if (fdd::comm().size > 1) return fail("a Helmholtz shift is supported on one rank: this communicator has %d", fdd::comm().size);
-        if (d.mesh.dim != 3) return fail("a Helmholtz shift is 3-D only: this problem is %d-D", d.mesh.dim);
-        if (d.poly_degree > 15) return fail("a Helmholtz shift supports poly_degree 1..15, got %d", d.poly_degree);
-        if (pr.subdomain && pr.subdomain->composite()) return fail("a Helmholtz shift needs a conforming region: this problem's Subdomain is a composite");
-        if (pr.subdomain && (int)pr.subdomain->point_dof.size() != d.num_local_points) return fail("a Helmholtz shift needs a Subdomain over the rank's own points");
         const size_t np = (size_t)d.num_local_points;
-        double lo = lambda, hi = lambda;
-        for (size_t q = 0; lambda_points && q < np; q++)
-        {
-            const double v = lambda_points[q];
-            if (!std::isfinite(v) || v < 0.0) return fail("lambda must be finite and >= 0 at every point: point %zu has %g", q, v);
-            lo = q == 0 ? v : std::min(lo, v);
-            hi = q == 0 ? v : std::max(hi, v);
-        }
-        if (!lambda_points && (!std::isfinite(lambda) || lambda < 0.0)) return fail("lambda must be finite and >= 0, got %g", lambda);
-
+        const std::string why = fdd::helmholtz::refusal(fdd::missing_helmholtz_entry(), fdd::comm().size, d.mesh.dim, d.poly_degree, pr.subdomain && pr.subdomain->composite(), pr.subdomain ? (long long)pr.subdomain->point_dof.size() : -1, lambda, lambda_points, (long long)np);
+        if (!why.empty()) return fail("%s", why.c_str());
+        const auto range = lambda_points && np ? std::minmax_element(lambda_points, lambda_points + np) : std::make_pair(&lambda, &lambda);
+        const double lo = *range.first, hi = *range.second;
         std::vector<double> lambda_B;
         if (hi > 0.0)
         {
             fdd::FieldOps<Domain<SType>>(d).mass(pr.b);
             lambda_B.resize(np);
             pr.b.copyTo(lambda_B.data(), fine_bytes(pr));
-            for (size_t q = 0; q < np; q++) lambda_B[q] = (lambda_points ? lambda_points[q] : lambda) * lambda_B[q];
+            fdd::helmholtz::scale_mass(lambda_B, lambda, lambda_points);
         }
         const bool was_active = d.shift_active();
         d.set_shift(hi > 0.0 ? lambda_B.data() : nullptr);
-        if (was_active || d.shift_active()) d.projection.clear(); // the operator changes under the stored images
         pr.helmholtz_min = d.shift_active() ? lo : 0.0;
         pr.helmholtz_max = d.shift_active() ? hi : 0.0;
-        if (pr.subdomain)
-        {
-            // the same values in the Subdomain's dof numbering: a dof sits on the node of any of its points
-            Subdomain<PType> &s = *pr.subdomain;
-            std::vector<double> c_dofs((size_t)std::max(s.dof_count(), 1), 0.0);
-            const CSR_Matrix<SType> &Q = d.scatter_matrix();
-            for (size_t q = 0; d.shift_active() && q < np; q++)
-                if (s.point_dof[q] >= 0 && s.point_dof[q] < s.dof_count()) c_dofs[s.point_dof[q]] = d.shift_nodes_hst[Q.col_hst[q]];
-            s.set_shift(d.shift_active() ? c_dofs.data() : nullptr, s.dof_count());
-        }
+        if (Subdomain<PType> *s = pr.subdomain.get())
+            s->set_shift(d.shift_active() ? fdd::helmholtz::dofs_of_nodes(d.shift_nodes_hst, d.scatter_matrix().col_hst.data(), s->point_dof.data(), np, s->dof_count()) : std::vector<double>());
+        operator_changed(pr, OperatorChange::of_shift(was_active));
         return 0;
     });
 }
@@ -1522,15 +1540,10 @@ int fddh_diffusivity_set(fddh_problem *p, const double *kappa_points, int n)
         if (pr.subdomain && (int)pr.subdomain->point_dof.size() != d.num_local_points) return fail("a diffusivity needs a Subdomain over the rank's own points");
         if (kappa_points == nullptr && !d.diffusivity_active()) return 0;
         d.set_diffusivity(kappa_points);
-        // the basis belongs to the operator as it was; solve_projected stays allowed: the images stored from here on are this operator's
-        d.projection.clear();
         if (pr.subdomain) pr.subdomain->set_diffusivity(kappa_points, (size_t)d.num_local_points, d.operator_list());
-        pr.diffusivity_min = pr.diffusivity_max = 0.0;
-        if (kappa_points)
-        {
-            pr.diffusivity_min = *std::min_element(kappa_points, kappa_points + n);
-            pr.diffusivity_max = *std::max_element(kappa_points, kappa_points + n);
-        }
+        operator_changed(pr, {OperatorChange::factors}); // solve_projected stays allowed: the images stored from here on are this operator's
+        pr.diffusivity_min = kappa_points ? *std::min_element(kappa_points, kappa_points + n) : 0.0;
+        pr.diffusivity_max = kappa_points ? *std::max_element(kappa_points, kappa_points + n) : 0.0;
         return 0;
     });
 }
@@ -1664,8 +1677,7 @@ int fddh_problem_precond_apply(fddh_problem *p, int type, const double *r, doubl
 {
     return on_subdomain(p, r && z, [&](fddh_problem &pr, Subdomain<PType> &s) {
         if (const char *why = inner_solver_refusal(pr)) return fail("%s", why);
-        if (const char *why = helmholtz_inner_refusal(pr)) return fail("%s", why);
-        if (pr.fine().shift_active() && type == 0) return fail("a Helmholtz shift needs the inner GMRES or Chebyshev-Jacobi in dof space: the inner FCG does not go through operator_dofs");
+        if (const char *why = helmholtz_inner_refusal(pr, type == 0)) return fail("%s", why);
         fine_round_trip(pr, r, z, [&] {
             if (type == 0)
                 s.flexible_conjugate_gradient(pr.b, pr.a);

@@ -1101,6 +1101,14 @@ class Subdomain
     fdd::memory tree_points() { return f.slice(0, own_points); }
 
   private:
+    // A hierarchy that amg_build made is built again after a change that reaches the low-order matrix (operator_changed,
+    // amg_rebuild); one that was handed in is the caller's and stays.  A sweep's reader sees what the change costs
+    void rebuild_own_hierarchy(const char *change)
+    {
+        if (not(amg_hierarchy.ready() and amg_built_here)) return;
+        const int nl = amg_build(amg_build_options);
+        rstdout("Low-order preconditioner assembled again (%s): %d levels, %.3f s\n", change, nl, amg_setup_seconds);
+    }
 
   public:
     const char *data_type = "double";
@@ -1117,79 +1125,67 @@ class Subdomain
         return jacobi_diag_hst;
     }
 
-    // The operator under the diagonal has changed (a level's D_hat, the arithmetic of the element kernels): the diagonal, its
-    // inverses and the eigenvalue bound of the Chebyshev inner solve are made again at their next use.  D != nullptr: the
+    // The operator under the diagonal has changed: the diagonal, its inverses and the eigenvalue bound of the Chebyshev inner
+    // solve are made again at their next use, and the first step's scaling with them (operator_generation).  Which change
+    // brings which arguments is said once, in fdd_host_capi.cpp (operator_changed there, the only caller).  D != nullptr: the
     // table of the level of that degree, whose host copy this class keeps (the device table is the Domain's own).
-    void operator_changed(int degree = -1, const double *D = nullptr, int n = 0)
+    // low_order_term != nullptr: the change reaches the low-order matrix, and a hierarchy that amg_build made is built again
+    // now; the text names the change in the printed line.
+    void operator_changed(int degree = -1, const double *D = nullptr, int n = 0, const char *low_order_term = nullptr)
     {
         for (int l = 0; D != nullptr and l < num_levels; l++)
             if (poly_degree[l] == degree) D_hat[l].first.assign(D, D + (size_t)n * n);
         for (auto &ll : subdomain_operator.level_lists)
-            if (D != nullptr and poly_degree[ll.level] == degree) fdd::check_lean_table(ll, D_hat[ll.level].first); // the Domain has uploaded this table
+            if (D != nullptr and poly_degree[ll.level] == degree)
+            {
+                fdd::check_lean_table(ll, D_hat[ll.level].first); // the Domain has uploaded this table
+                if (not ll.D_hat32.ptr()) continue;
+                ll.D_hat32.free(); // the float solve was prepared under the table as it was: its copy and its verdict follow
+                ll.D_hat32 = fdd::to_float(D_hat[ll.level].first);
+                fdd::check_lean_table32(ll, D_hat[ll.level].first);
+            }
         jacobi_dinv.free();
         jacobi_dinv_f32.free();
         jacobi_diag_hst.clear();
         cheby.lambda = 0.0;
         operator_generation++;
+        if (low_order_term != nullptr) rebuild_own_hierarchy(low_order_term);
     }
 
     // ---- Helmholtz shift: the inner operator is Qt A_L Q + diag(c), c >= 0 over the dofs -- a LABELLED OPTION of this build ----
     // c is the Domain's node vector (Domain::set_shift) in this class's dof numbering, kept in both precisions and on the
-    // host (the exact diagonal and the low-order matrix take it from there).  cbar == nullptr: off.  An operator change:
-    // the diagonal and the Chebyshev bound are made again at their next use, a hierarchy that amg_build made is built again
-    // now, with the term on the diagonal of its level-0 matrix; one that was handed in is the caller's and stays.
+    // host (the exact diagonal and the low-order matrix take it from there).  An empty c: off.  The caller follows with
+    // operator_changed.
     std::vector<double> shift_dofs_hst;
     fdd::memory shift_dofs, shift_dofs_f32;
     bool shift_active() const { return not shift_dofs_hst.empty(); }
-    void set_shift(const double *cbar, int n)
+    void set_shift(const std::vector<double> &c)
     {
-        const bool was_active = shift_active();
-        if (cbar == nullptr and not was_active) return;
         shift_dofs.free();
         shift_dofs_f32.free();
-        shift_dofs_hst.clear();
-        if (cbar != nullptr and n > 0)
-        {
-            shift_dofs_hst.assign(cbar, cbar + n);
-            shift_dofs = fdd::dev().malloc<DType>((size_t)n);
-            shift_dofs.copyFrom(shift_dofs_hst.data(), (size_t)n * sizeof(DType));
-            shift_dofs_f32 = fdd::to_float(shift_dofs_hst);
-        }
-        operator_changed();
-        if (amg_hierarchy.ready() and amg_built_here)
-        {
-            const int nl = amg_build(amg_build_options);
-            rstdout("Low-order preconditioner assembled again (Helmholtz shift %s): %d levels, %.3f s\n", shift_active() ? "set" : "cleared", nl, amg_setup_seconds);
-        }
+        shift_dofs_hst = c;
+        if (c.empty()) return;
+        shift_dofs = fdd::dev().malloc<DType>(c.size());
+        shift_dofs.copyFrom(c.data(), c.size() * sizeof(DType));
+        shift_dofs_f32 = fdd::to_float(c);
     }
 
     // ---- a diffusivity per point (diffusivity.hpp): the inner operator is Qt D^T [kappa G] D Q -- a LABELLED OPTION of this build ----
     // On one rank without a composite the inner operator is the fine level's own list on the Domain's own arrays, which
     // Domain::set_diffusivity has just rewritten: what this class derived from them is derived again (the list's verdicts and
-    // float copies now; the diagonal, its inverses, the Chebyshev bound and the first-step scaling at their next use), the
-    // list takes the Domain's members of the coefficient instance as views, and a hierarchy that amg_build made is built
-    // again with kappa in its level-0 matrix; one that was handed in is the caller's and stays.  The classes of the rows of
+    // float copies), the list takes the Domain's members of the coefficient instance as views, and the values are kept for
+    // the low-order matrix; the caller follows with operator_changed.  The classes of the rows of
     // Qt (assembly) do not depend on the factors or on the kernel's instance and stay.  A Helmholtz shift is independent of
     // all this and keeps the unscaled mass.  kappa == nullptr: cleared.
     std::vector<double> diffusivity_hst;
     bool diffusivity_active() const { return not diffusivity_hst.empty(); }
     void set_diffusivity(const double *kappa, size_t n, const fdd::LevelList &domain_list)
     {
-        if (kappa == nullptr and not diffusivity_active()) return;
-        if (kappa != nullptr)
-            diffusivity_hst.assign(kappa, kappa + n);
-        else
-            diffusivity_hst.clear();
+        diffusivity_hst.assign(kappa, kappa + (kappa != nullptr ? n : 0));
         for (auto &ll : subdomain_operator.level_lists)
         {
             fdd::diffusivity::refresh_list(ll);
             fdd::diffusivity::share_coef(ll, domain_list);
-        }
-        operator_changed();
-        if (amg_hierarchy.ready() and amg_built_here)
-        {
-            const int nl = amg_build(amg_build_options);
-            rstdout("Low-order preconditioner assembled again (diffusivity %s): %d levels, %.3f s\n", diffusivity_active() ? "set" : "cleared", nl, amg_setup_seconds);
         }
     }
 
@@ -1500,12 +1496,7 @@ class Subdomain
     // the hierarchy in place is amg_build's own (not handed in through amg_add_level): it can be made again
     bool amg_built_here = false;
     fdd::low_order::Options amg_build_options;
-    int amg_rebuild()
-    {
-        const int nl = amg_build(amg_build_options);
-        rstdout("Low-order preconditioner assembled again (amg_cheby_order %d): %d levels, %.3f s\n", cheby_order, nl, amg_setup_seconds); // a sweep's reader sees what a change of the order costs
-        return nl;
-    }
+    void amg_rebuild() { rebuild_own_hierarchy(("amg_cheby_order " + std::to_string(cheby_order)).c_str()); }
     bool amg_device_setup = false; // "amg_device_setup": amg_build makes the FEM matrix and the lattice levels in HBM (conforming regions)
     int amg_levels_on_device = 0;  // of the last amg_build: the levels whose matrix A was computed on the device
     double amg_setup_seconds = 0.0;

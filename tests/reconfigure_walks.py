@@ -1,12 +1,22 @@
 """Reconfiguring a live problem equals building a fresh one: the walk tables and the `fresh` / `walked` drivers shared by
 test_cpu_reconfigure.py (the CPU build of the host layer, tests/cpu_shim, in a child process) and test_gpu_reconfigure.py.
 
-A configuration is a complete set of options (fddh_problem_set_options), flags (fddh_problem_set_flag) and three keys of
+A configuration is a complete set of options (fddh_problem_set_options), flags (fddh_problem_set_flag) and six keys of
 this module: "amg" (how the low-order hierarchy comes to be: None = the problem never has one, "first_use" = the
 inner solve builds it, "host" / "device" = fddh_problem_amg_build with "amg_device_setup" 0 / 1, "attached" = handed in
-level by level), "inner" (the method precond_apply is called with) and "pcg_steps" (K > 0: pcg_begin / pcg_steps(K) /
-pcg_solution join the workload).  `apply` sets every key, always in the same order, so that fresh(c) and the last step
-of walked(..., c) differ in one thing only: what the problem did before.
+level by level), "inner" (the method precond_apply is called with), "pcg_steps" (K > 0: pcg_begin / pcg_steps(K) /
+pcg_solution join the workload) and the operator's terms: "D_hat" (None = the GLL table `build` sets, "perturbed" = a table
+of the fine level that fails lean_table_ok), "helmholtz" (None, a constant, or "field": seeded, >= 0, with exact zeros) and
+"diffusivity" (None, "smooth", or "jump": 1 : 1000 across an element face, diffusivity_checks.kappa_jump).  `apply` sets
+every key, always in the same order, so that fresh(c) and the last step of walked(..., c) differ in one thing only: what
+the problem did before.  Two exceptions, the table and the flag "affine_geometry": every call of either empties all that
+hangs on the operator (basis, diagonal, Chebyshev bound), made again only at the next use, so a call at every step would
+stand in for whatever the shift or kappa owe at that step.  `apply` therefore sets these two only where they differ from
+what the problem holds (`build`'s GLL table and the library's affine_geometry = 0 on a new problem; the driver keeps
+track), and no step of a walk changes the table together with another term.  The shift and kappa are set at every step, in that order, after the flags: clearing one
+that is not set returns before it touches anything, and one that is set is set again ("set twice in a row" is every such
+pair of steps), which empties again -- so the walks change the affine flag and the shift also at steps where no kappa
+is set, and kappa, set last, is never followed by another emptying.
 
 The property (every step, not only the last): the outputs of step i of walked(c0, ..., ck) equal those of fresh(ci) bit
 for bit -- vectors, residual histories, iteration counts.  Both sides run the same code on the same inputs and the suite
@@ -17,11 +27,20 @@ the step and its label, i.e. the transition.
 
 Besides the walks: a stepwise run abandoned while it is live, then other solves (ABANDONED, run_abandoned_stepwise).
 
+The CPU build: the walk whose hierarchy is built on the device is left out by name (CPU_LEFT_OUT).  The stand-in of the
+kernel library also has no fdd_shift_add* and no coefficient instance of the line kernel, so fddh_helmholtz_set answers
+"does not export" for any value and "coefficient_in_kernel" = 1 is refused.  No walk is left out for that: there every
+walk runs with "helmholtz" None and "coefficient_in_kernel" 0 at every step (CPU_SUBSTITUTED, on_cpu), i.e. the table,
+kappa and affine transitions of the family "operator" on a problem without a shift, and each step's printed label says so;
+the shift's transitions are test_gpu_reconfigure.py's alone.
+
 Run as a program (the CPU test does): reconfigure_walks.py <libfdd_host_cpu.so> <walk name, or a name of ABANDONED>.
 """
 import sys
 
 import numpy as np
+
+import diffusivity_checks as K
 
 # every option and flag a configuration sets, in the order `apply` sets them (values: the library's defaults, except the
 # iteration cap, which keeps the solves short, and "sub_use_preconditioner", off where the walk has no hierarchy)
@@ -47,6 +66,8 @@ BASE = {
     "lazy_steps": 1,
     "mfma_stiffness": 1,
     "affine_geometry": 0,
+    "coefficient_in_kernel": 1,
+    "inner_solver": 0,
     # the V-cycle
     "sub_use_preconditioner": 0,
     "amg_cheby_order": 2,
@@ -60,16 +81,38 @@ BASE = {
     "amg": None,
     "inner": "gmres",
     "pcg_steps": 0,
+    "D_hat": None,
+    "helmholtz": None,
+    "diffusivity": None,
 }
 OPTION_KEYS = ("max_iterations", "tolerance", "num_vectors", "use_preconditioner", "preconditioner_type", "sub_num_vectors", "sub_max_iterations")
-MODULE_KEYS = ("amg", "inner", "pcg_steps")
+MODULE_KEYS = ("amg", "inner", "pcg_steps", "D_hat", "helmholtz", "diffusivity")
 FLAG_KEYS = tuple(k for k in BASE if k not in OPTION_KEYS and k not in MODULE_KEYS)
 
 # The CPU stand-in of the kernel library has no fdd_amg_setup_* entry: the host layer refuses "amg_device_setup" = 1 there
 # (test_cpu_amg_device_setup.py), so walks whose hierarchy is built on the device are left out of the CPU file by name.
 # "mfma_stiffness" and "amg_graph" are accepted there (one stiffness routine serves both kernels; a capture that the
 # stand-in declines runs the same launches eagerly) and stay in.
+# "affine_geometry" empties all that hangs on the operator at every call, whatever the value (like fddh_problem_set_D_hat, the
+# module's docstring): `apply` sets it only where it differs from what the problem holds (BASE's 0, the library's default, on a
+# new problem)
+SET_ON_CHANGE = ("affine_geometry",)
+
 CPU_LEFT_OUT = {"amg": ("device",)}
+# Nor has it fdd_shift_add* or the coefficient instance of the line kernel: no walk is left out for that, these keys take the
+# value given here at every step of every walk, and the label of a step they change says so (cpu_label).
+CPU_SUBSTITUTED = {"helmholtz": None, "coefficient_in_kernel": 0}
+
+
+def on_cpu(c):
+    return dict(c, **CPU_SUBSTITUTED)
+
+
+def cpu_label(label, changes):
+    """the label of a step as the CPU build runs it: what the step asks for and the stand-in cannot do is named"""
+    dropped = [k for k in CPU_SUBSTITUTED if k in changes]
+    return label + (" [CPU build: without its change of %s]" % ", ".join(dropped) if dropped else "")
+
 
 # Transitions the library refuses, as (walk, step label, option): a closed list, matched line for line by include/fdd_host.h
 # (the comment on fddh_problem_set_flag).  The error text must name the option, the option keeps its earlier value and the
@@ -214,24 +257,72 @@ WALKS = {
         ("none", {"use_preconditioner": 0}),
         ("inner FCG, point space", {"use_preconditioner": 1, "preconditioner_type": 0, "inner": "fcg", "assembled_outer_solve": 0}),
     ]),
+    # ---- the operator's terms: shift, kappa, a level's table and the affine arithmetic, set, changed, stacked and cleared
+    "operator_terms_n7": dict(mesh=BOX_N7, family="operator", oracle=True, base={"amg": "host", "sub_use_preconditioner": 1, "max_iterations": 5, "sub_num_vectors": 2, "sub_max_iterations": 2}, steps=[
+        ("Poisson", {}),
+        ("lambda constant", {"helmholtz": 10.0}),
+        ("lambda field", {"helmholtz": "field"}),
+        ("kappa smooth on top of lambda", {"diffusivity": "smooth"}),
+        ("kappa jump", {"diffusivity": "jump"}),
+        ("kappa jump set again, streamed scaled arrays", {"coefficient_in_kernel": 0}),
+        ("kappa cleared, lambda stays", {"diffusivity": None, "coefficient_in_kernel": 1}),
+        ("all cleared, identity in the inner solve: the oracle's configuration", {"helmholtz": None, "sub_use_preconditioner": 0, "sub_num_vectors": 4, "sub_max_iterations": 4}),
+    ]),
+    "operator_terms_attached": dict(mesh=BOX_SMALL, family="operator", base={"amg": "attached", "sub_use_preconditioner": 1, "max_iterations": 5}, steps=[
+        ("lambda on", {"helmholtz": 2.0}),
+        ("kappa on", {"diffusivity": "smooth"}),
+        ("both off, cap 4", {"helmholtz": None, "diffusivity": None, "max_iterations": 4}),
+    ]),
+    "operator_terms_first_use": dict(mesh=BOX_SMALL, family="operator", base={"amg": "first_use", "sub_use_preconditioner": 1, "max_iterations": 5}, steps=[
+        ("kappa smooth, set before anything is built", {"diffusivity": "smooth"}),
+        ("a solve more, cap 4", {"max_iterations": 4}),
+        ("kappa jump", {"diffusivity": "jump"}),
+        ("lambda on", {"helmholtz": 3.0}),
+        ("affine on", {"affine_geometry": 1}),
+        ("all off", {"diffusivity": None, "helmholtz": None, "affine_geometry": 0}),
+    ]),
+    # point-Jacobi in the inner GMRES reads the exact diagonal, which the shift sits on (the Chebyshev walks below leave the shift out)
+    "operator_terms_jacobi": dict(mesh=BOX_SMALL, family="operator", base={"sub_use_preconditioner": 2, "max_iterations": 5}, steps=[
+        ("Poisson", {}),
+        ("lambda constant", {"helmholtz": 10.0}),
+        ("lambda field", {"helmholtz": "field"}),
+        ("lambda cleared, cap 4", {"helmholtz": None, "max_iterations": 4}),
+    ]),
 }
-FAMILIES = ("outer", "inner", "vcycle", "kernels", "caps", "precond")
+# the Chebyshev-Jacobi inner solve keeps cheby.lambda, the Jacobi inverses and the first step's scaling (w_generation) across
+# solves: each kind of change but the shift (the fused gather epilogue steps aside under one), in both precisions
+for _name, _precision in (("operator_terms_chebyshev", 64), ("operator_terms_chebyshev_f32", 32)):
+    WALKS[_name] = dict(mesh=BOX_N7, family="operator", base={"inner_solver": 1, "preconditioner_precision": _precision, "max_iterations": 5}, steps=[
+        ("Poisson", {}),
+        ("D_hat perturbed", {"D_hat": "perturbed"}),
+        ("D_hat back", {"D_hat": None}),
+        ("kappa on", {"diffusivity": "smooth"}),
+        ("affine on with kappa", {"affine_geometry": 1}),
+        ("kappa off", {"diffusivity": None}),
+        ("affine off, no kappa set", {"affine_geometry": 0, "max_iterations": 4}),
+    ])
+FAMILIES = ("outer", "inner", "vcycle", "kernels", "caps", "precond", "operator")
 
 
 def walk_names(cpu):
     return [n for n, w in WALKS.items() if not (cpu and w.get("base", {}).get("amg") in CPU_LEFT_OUT["amg"])]
 
 
-def configurations(walk, name=None):
+def configurations(walk, name=None, cpu=False):
     """The complete configuration of every step as (requested, in force): they differ in the options the library refuses at
-    that step (REFUSED), which keep their value; the next step starts from what is in force."""
+    that step (REFUSED), which keep their value; the next step starts from what is in force.  cpu: as the CPU build runs it
+    (on_cpu)."""
     c = dict(BASE)
     c.update(walk.get("base", {}))
     out = []
     for label, changes in walk["steps"]:
         assert set(changes) <= set(BASE), set(changes) - set(BASE)
+        assert "D_hat" not in changes or not {"affine_geometry", "helmholtz", "diffusivity"} & set(changes), "a step changes the table alone: the call would empty what the other change owes"
         requested = dict(c)
         requested.update(changes)
+        assert requested["helmholtz"] is None or requested["inner"] == "gmres", "the inner FCG is refused under a shift"
+        if cpu:
+            requested = on_cpu(requested)
         in_force = dict(requested)
         for w, at, option in REFUSED:
             if w == name and at == label:
@@ -250,8 +341,8 @@ def bits(a):
 class Driver:
     """H: host_api, S: support, lib: the package's lib module (all bound to the library under test by the caller)"""
 
-    def __init__(self, H, S, lib):
-        self.H, self.S, self.lib = H, S, lib
+    def __init__(self, H, S, lib, cpu=False):
+        self.H, self.S, self.lib, self.cpu = H, S, lib, cpu
 
     def build(self, mesh):
         kind, E, N, red = mesh
@@ -262,6 +353,7 @@ class Driver:
             p = H.Problem.box(E, (1, 1, 1), N, red, True, force_composite=(kind == "composite"))
         for lvl in range(p.info["num_levels"]):
             p.set_D_hat(lvl, S.gll(p.level_degree(lvl))[2])
+        p.takes_terms = kind != "composite"  # a composite refuses fddh_helmholtz_set and fddh_diffusivity_set whatever the value (capi_refusals.py)
         return p
 
     def apply(self, p, c, state, refusals=()):
@@ -270,6 +362,8 @@ class Driver:
         in_force = dict(c)
         p.set_options(**{k: c[k] for k in OPTION_KEYS})
         for k in FLAG_KEYS:
+            if k in SET_ON_CHANGE and c[k] == state.get("in_force", BASE)[k]:
+                continue
             try:
                 p.set_flag(k, c[k])
             except self.lib.FddError as exc:
@@ -287,8 +381,38 @@ class Driver:
             m = self.S.ArrayMesh.from_problem(p)
             p.amg_attach(self.S.low_order_hierarchy(m, p.sub_point_dofs(), p.info["sub_num_dofs"]))
             state["amg"] = "attached"
+        self.set_operator_terms(p, c, state)
         state["in_force"] = in_force
         return in_force
+
+    def set_operator_terms(self, p, c, state):
+        """state["D_hat"]: the table this problem holds (absent: the GLL table `build` set)"""
+        S = self.S
+        assert c["D_hat"] in (None, "perturbed")
+        if c["D_hat"] != state.get("D_hat"):  # only a change: the call empties everything (the module's docstring)
+            D = S.gll(p.level_degree(0))[2].copy()
+            if c["D_hat"] == "perturbed":
+                D.flat[1] *= 1.0 + 2.0**-10  # entry 62 is no longer the negation of entry 1
+            p.set_D_hat(0, D)
+            state["D_hat"] = c["D_hat"]
+        if not p.takes_terms:
+            assert c["helmholtz"] is None and c["diffusivity"] is None
+            return
+        if not self.cpu:  # the stand-in's fddh_helmholtz_set answers "does not export" for any value
+            lam = c["helmholtz"]
+            if lam == "field":
+                lam = np.where(S.seeded_uniform(p.n, 78) < 0.25, 0.0, 50.0 * S.seeded_uniform(p.n, 77))
+            p.helmholtz(0.0 if lam is None else lam)
+        else:
+            assert c["helmholtz"] is None
+        kappa = c["diffusivity"]
+        if kappa == "smooth":
+            kappa = K.kappa_smooth(*(p.mesh_array(a) for a in "xyz"))
+        elif kappa == "jump":
+            kappa = K.kappa_jump(p.mesh_array("x"), (p.level_degree(0) + 1) ** 3, 1000.0)
+        else:
+            assert kappa is None
+        p.diffusivity(kappa)
 
     def workload(self, p, c, step):
         """The inputs depend on the step: state kept from the step before (a cached basis, a history, a right-hand side on the
@@ -392,8 +516,8 @@ def run_walk(driver, name):
     every transition whose outputs differ."""
     walk = WALKS[name]
     mesh = walk["mesh"]
-    configs = configurations(walk, name)
-    labels = [s[0] for s in walk["steps"]]
+    configs = configurations(walk, name, driver.cpu)
+    labels = [cpu_label(*s) if driver.cpu else s[0] for s in walk["steps"]]
     last = configs[-1][1]
 
     k = len(configs) - 1
@@ -438,6 +562,8 @@ def run_abandoned_stepwise(driver, name):
     S = driver.S
     mesh = ABANDONED[name]
     c = dict(BASE, amg="host", sub_use_preconditioner=1)
+    if driver.cpu:
+        c = on_cpu(c)
 
     def three_calls(p):
         r = S.seeded_uniform(p.n, 16) - 0.5
@@ -485,5 +611,5 @@ if __name__ == "__main__":
     H.init(0, use_torch_stream=False)
     H.comm_single()
     H.set_print(False)
-    (run_abandoned_stepwise if walk in ABANDONED else run_walk)(Driver(H, S, lib), walk)
+    (run_abandoned_stepwise if walk in ABANDONED else run_walk)(Driver(H, S, lib, cpu=True), walk)
     print("ok")
