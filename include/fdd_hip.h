@@ -515,6 +515,26 @@ int fdd_field_weak_divergence(double *out, const double *const v[3], const doubl
 int fdd_shift_add(double *y, const double *c, const double *scale_dev, const double *x, int n, void *stream);
 int fdd_shift_add_f32(float *y, const float *c, const double *scale_dev, const float *x, int n, void *stream);
 int fdd_shift_add_inner_product(double *out, double *ws, double *y, const double *c, const double *x, int n, void *stream);
+/* The same statement on the support of a c that is zero on most of the vector (a Robin term lives on the boundary nodes):
+ *   y[index[k]] = y[index[k]] + c_values[k] * x[index[k]],  k < m        x standing for (*scale_dev) * x as above
+ * index: m distinct, ascending ints in 0..n-1 (device memory); nothing else of y is touched, so where the dense entry's
+ * y + 0 * x turns a -0.0 into +0.0 this one leaves it.  On the support the bits are the dense entry's.  An index outside
+ * 0..n-1 is skipped.  m <= n; y must overlap neither c_values, index nor x (FDD_ERR_INVALID_ARGUMENT); a call that is
+ * refused touches no output; m = 0 does nothing. */
+int fdd_shift_add_indexed(double *y, const double *c_values, const int *index, int m, const double *scale_dev, const double *x, int n, void *stream);
+int fdd_shift_add_indexed_f32(float *y, const float *c_values, const int *index, int m, const double *scale_dev, const float *x, int n, void *stream);
+/* Surface weights and unit normals of listed element faces (an option of this build; csrc/fdd_field.hip).  Face f of the list
+ * is side face_side[f] = 2 axis + upper (0..5: r-, r+, s-, s+, t-, t+) of element face_elem[f] (device arrays of num_faces
+ * ints, which the CALLER validates: a face whose element or side is out of range is skipped, its outputs stay).  Its n^2
+ * points are stored at f n^2 + a + n b with (a, b) = (j, k) on r-faces, (i, k) on s-faces, (i, j) on t-faces.  With X_r, X_s,
+ * X_t the derivatives of (x, y, z) along the in-face directions (D_hat applied to the face's own points):
+ *   Nvec   = X_s x X_t on r-faces, X_t x X_r on s-faces, X_r x X_s on t-faces
+ *   area   = w_a w_b |Nvec|                         the quadrature weight of the surface integral over the face
+ *   normal = +- Nvec / |Nvec|, + on the upper side  outward where det J > 0; normal may be NULL (not computed)
+ * area and normal[0..2] have num_faces n^2 entries; xyz and normal are HOST arrays of three device pointers.
+ * poly_degree 1..15 (checked first), FDD_ERR_UNSUPPORTED otherwise; num_elements < 2^31 / (N+1)^3, num_faces < 2^31 / (N+1)^2;
+ * no output may be an input or another output; a refused call touches nothing; num_faces = 0 does nothing. */
+int fdd_field_surface(double *area, double *const normal[3], const double *const xyz[3], const double *D_hat, const double *gll_weights, const int *face_elem, const int *face_side, int num_faces, int num_elements, int poly_degree, void *stream);
 int fdd_stiffness_matrix_affine_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *elem_factors, const float *gll_weights, const int *elem_offset, int num_elements, int poly_degree, void *stream);
 int fdd_sub_stiffness_matrix_gather_scaled_f32(float *Au, const float *v, const double *v_scale_dev, const int *point_dof, const float *D_hat, const float *const G[FDD_NUM_GEOM_FACTS], const int *elem_offset, int num_elements, int poly_degree, void *stream);
 int fdd_multi_inner_product_scaled_f32(double *out, double *ws, const float *a, const float *const *b, const double *b_scale_dev, int m, int n, void *stream); /* out[k] = sum a * (s_k b_k), k < m <= 8 */

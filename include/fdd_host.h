@@ -94,6 +94,13 @@ int fddh_write_box_mesh_files(const char *directory, const int E[3], const int P
  * non-zero (host/box_mesh.hpp). */
 int fddh_problem_create_kershaw_ex(fddh_problem **out, const int E[3], const int P[3], int poly_degree, int poly_reduction, int subdomain_overlap, int superdomain_overlap, int flags, double eps_y, double eps_z);
 int fddh_write_kershaw_mesh_files(const char *directory, const int E[3], const int P[3], int poly_degree, int rank, double eps_y, double eps_z);
+/* The same meshes with a boundary condition per face of the cube (an option of this build; the block "Neumann and Robin
+ * faces" below): faces = six characters for x-, x+, y-, y+, z-, z+, 'D' Dirichlet (the points of the face are masked) or 'N'
+ * natural (they are unknowns).  A point is masked iff it lies on at least one 'D' face: an edge between a 'D' and an 'N' face
+ * is Dirichlet.  The same codes at every level's degree; the Kershaw map keeps the faces; eps 1.0 is the uniform box.  Mesh
+ * data, accepted for any rank grid.  Another character or length is refused.  The entries above are these with "DDDDDD". */
+int fddh_problem_create_box_faces(fddh_problem **out, const int E[3], const int P[3], int poly_degree, int poly_reduction, int subdomain_overlap, int superdomain_overlap, int flags, double eps_y, double eps_z, const char *faces);
+int fddh_write_box_faces_mesh_files(const char *directory, const int E[3], const int P[3], int poly_degree, int rank, double eps_y, double eps_z, const char *faces);
 
 enum
 {
@@ -384,6 +391,44 @@ int fddh_helmholtz_set(fddh_problem *p, double lambda, const double *lambda_poin
 int fddh_helmholtz_info(fddh_problem *p, int *active, double *min, double *max);
 int fddh_helmholtz_shift(fddh_problem *p, double *cbar_nodes, int n);
 int fddh_helmholtz_node_operator(fddh_problem *p, const double *v_nodes, double *q_nodes, int n, double *vq);
+
+/* ---- Neumann and Robin faces (an option of this build; every problem of the reference is homogeneous Dirichlet) ----
+ * A problem made by fddh_problem_create_box_faces knows its faces: the face list is every face of the rank's elements that
+ * lies on the surface of the box, sorted by (side, element), side = 2 axis + upper; face f has (N+1)^2 points, point (a, b) at
+ * f (N+1)^2 + a + (N+1) b with (a, b) = (j, k) on x-faces, (i, k) on y-faces, (i, j) on z-faces (fdd_hip.h: fdd_field_surface,
+ * where the formulas are).  A problem made from mesh files has no face list: faces, surface and robin_set refuse it and say
+ * so (which covers every 2-D problem); info answers with empty codes and num_faces = -1.
+ *   info       the six codes (faces_out: 7 chars, NUL-terminated), the length of the face list, whether a Robin coefficient
+ *              is set and the smallest and largest alpha it was made from, the number of non-zero entries of the node shift
+ *              cbar (0 when none is set), the flag "indexed_shift", and in bit 0 / bit 1 whether the outer / the inner
+ *              operator adds cbar by fdd_shift_add_indexed as things stand.  Any pointer may be NULL
+ *   faces      the list: element (local) and side of every face, m = num_faces
+ *   surface    area = w_a w_b |Nvec|, the weight of the surface integral at every face point, and the unit outward normal
+ *              (nx, ny, nz all NULL: not computed); count = num_faces (N+1)^2.  Degree <= 15; refused, naming the entry, on
+ *              a kernel library without fdd_field_surface.  Works on any rank grid (each rank its own faces)
+ *   robin_set  the condition kappa du/dn + alpha u = g on natural faces: alpha per face point, finite and >= 0, and 0 on every
+ *              masked point (a positive alpha on a point of a 'D' face is refused, naming the first such point); NULL clears.
+ *              The term is diagonal: r[q] = sum of alpha * area over the face entries at point q, in face-list order from
+ *              0.0, joins the products of a Helmholtz shift per point -- lambda_q B_q where a lambda is set, else 0.0, then
+ *              + r[q] -- and the sums over the copies of a node are cbar as described at fddh_helmholtz_set, with everything
+ *              that follows a set shift there (the outer and inner operators, the exact diagonal, the level-0 matrix of a
+ *              hierarchy built here, the refusal of fddh_problem_solve_projected).  fddh_helmholtz_info keeps reporting
+ *              lambda's range and whether a lambda is set; fddh_helmholtz_shift returns the whole cbar.  The refusals are
+ *              those of fddh_helmholtz_set (one rank, a conforming region, 3-D, degree <= 15, the kernel entries); the
+ *              problem stays usable.  An all-zero alpha is no coefficient.
+ * The data of the conditions go into the right-hand side, formed by the caller (host_api.py: Problem.boundary_rhs):
+ * f - A_L u_D - lambda B u_D + scatter(area * flux), the solution being solve(f') + u_D.
+ * Flag "indexed_shift" (fddh_problem_set_flag; refused where the kernel library lacks fdd_shift_add_indexed[_f32]): where at
+ * most 1/16 of the entries of cbar are non-zero -- a Robin term alone -- the passes that only add the term run over its
+ * support; the same values.  Default 1 where the entries are (measured faster: DESIGN section 15).  The fused shift-and-dot of
+ * the outer CG step reads both vectors anyway and stays dense.
+ * A problem whose faces are all 'N' and that has no zeroth-order term is singular (the constants): it can be created, since a
+ * shift may follow, but fddh_problem_solve / _solve_timed / _solve_projected / _pcg_begin / _precond_apply refuse it, naming
+ * the remedies. */
+int fddh_boundary_info(fddh_problem *p, char *faces_out, int *num_faces, int *robin_active, double *alpha_min, double *alpha_max, long long *shift_support, int *indexed_shift, int *indexed_in_use);
+int fddh_boundary_faces(fddh_problem *p, int *elem, int *side, int m);
+int fddh_boundary_surface(fddh_problem *p, double *area, double *nx, double *ny, double *nz, long long count);
+int fddh_boundary_robin_set(fddh_problem *p, const double *alpha_face_points /* NULL clears */);
 
 /* ---- Variable diffusivity: -div(kappa grad u) + lambda u = f (an option of this build; the reference solves the Poisson problem) ----
  * kappa_points: one double per point of the fine level, element-major like fddh_problem_mesh_array("x"), every value

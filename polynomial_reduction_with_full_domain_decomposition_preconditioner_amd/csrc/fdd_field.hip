@@ -325,9 +325,119 @@ int no_alias(const OutPtrs3 &out, int num_out, const Ptrs3 &in, int num_in, cons
     return 0;
 }
 
+// ---- surface weights and outward normals of listed element faces (fdd_field_surface) ----
+// One workgroup per listed face, n*n active lanes: lane (a, b) owns the face point a + n b.  The face slab of x, y, z is
+// staged in LDS (rows padded by one double), the two in-face derivatives X_a, X_b are D_hat contracted along a and b
+// (explicit fused multiply-adds, as above), Nvec is their cross product in the order that points along the face's own
+// reference direction, and |Nvec| w_a w_b is the surface weight.  The derivative across the face is not needed.
+// 24 B read and 8 (area) + 24 (normal) B written per face point.
+template <int n>
+struct SurfaceCfg
+{
+    static constexpr int nn = n * n;
+    static constexpr int block = ((nn + FDD_WAVE - 1) / FDD_WAVE) * FDD_WAVE;
+    static constexpr int ld = n + 1;
+};
+
+template <int n>
+__global__ __launch_bounds__(SurfaceCfg<n>::block) void field_surface_kernel(double *__restrict__ area, OutPtrs3 normal, Ptrs3 X, const double *__restrict__ D_hat, const double *__restrict__ w, const int *__restrict__ face_elem,
+                                                                              const int *__restrict__ face_side, int num_elements)
+{
+    using C = SurfaceCfg<n>;
+    constexpr int nn = C::nn;
+    constexpr int n3 = nn * n;
+    __shared__ double s_D[n * C::ld]; // rows padded like the slab's: lane (a, b) reads rows a and b
+    __shared__ double s_x[3][n * C::ld];
+
+    const int face = blockIdx.x;
+    const int elem = face_elem[face], side = face_side[face];
+    // the host layer validates the list; a face outside the arrays is left alone rather than read
+    if (elem < 0 || elem >= num_elements || side < 0 || side > 5) return;
+    const int axis = side >> 1, upper = side & 1;
+    const int tid = threadIdx.x;
+    const bool active = tid < nn;
+    const int b = active ? tid / n : 0;
+    const int a = active ? tid - b * n : 0;
+    const int fixed = upper ? n - 1 : 0;
+    // (a, b) = (j, k) on r-faces, (i, k) on s-faces, (i, j) on t-faces
+    const int point = axis == 0 ? fixed + n * (a + n * b) : (axis == 1 ? a + n * (fixed + n * b) : a + n * (b + n * fixed));
+    const size_t at = (size_t)elem * n3 + point;
+
+    if (active)
+    {
+#pragma unroll
+        for (int c = 0; c < 3; c++) s_x[c][a + b * C::ld] = X.p[c][at];
+        s_D[a + b * C::ld] = D_hat[tid]; // D[b][a]
+    }
+    __syncthreads();
+
+    double da[3] = {0.0, 0.0, 0.0}, db[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int p = 0; p < n; p++)
+    {
+        const double Da = s_D[p + a * C::ld], Db = s_D[p + b * C::ld];
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+        {
+            da[c] = __builtin_fma(Da, s_x[c][p + b * C::ld], da[c]);
+            db[c] = __builtin_fma(Db, s_x[c][a + p * C::ld], db[c]);
+        }
+    }
+    // Nvec = X_s x X_t (r-faces), X_t x X_r (s-faces), X_r x X_s (t-faces): X_a x X_b, on s-faces X_b x X_a
+    // (the negation is exact)
+    const double flip = axis == 1 ? -1.0 : 1.0;
+    const double N[3] = {flip * (da[1] * db[2] - da[2] * db[1]), flip * (da[2] * db[0] - da[0] * db[2]), flip * (da[0] * db[1] - da[1] * db[0])};
+    const double mag = sqrt(N[0] * N[0] + N[1] * N[1] + N[2] * N[2]);
+    if (!active) return;
+    const size_t o = (size_t)face * nn + tid;
+    area[o] = (w[a] * w[b]) * mag;
+    if (normal.p[0] != nullptr)
+    {
+        const double sign = upper ? 1.0 : -1.0;
+#pragma unroll
+        for (int c = 0; c < 3; c++) normal.p[c][o] = sign * N[c] / mag;
+    }
+}
+
 } // namespace
 
 extern "C" {
+
+int fdd_field_surface(double *area, double *const normal[3], const double *const xyz[3], const double *D_hat, const double *gll_weights, const int *face_elem, const int *face_side, int num_faces, int num_elements, int poly_degree, void *stream)
+{
+    bool run;
+    if (int rc = field_sizes(num_elements, poly_degree, &run)) return rc;
+    const long long n = poly_degree + 1;
+    FDD_REQUIRE(num_faces >= 0);
+    FDD_REQUIRE(num_faces < (1LL << 31) / (n * n));
+    if (num_faces == 0) return 0;
+    FDD_REQUIRE(run); // faces of no element
+    FDD_REQUIRE(area != nullptr && D_hat != nullptr && gll_weights != nullptr && face_elem != nullptr && face_side != nullptr);
+    OutPtrs3 nrm = {{nullptr, nullptr, nullptr}};
+    Ptrs3 X;
+    if (int rc = three_pointers(X, xyz)) return rc;
+    const void *outs[4] = {area, nullptr, nullptr, nullptr};
+    int num_out = 1;
+    if (normal != nullptr)
+        for (int a = 0; a < 3; a++)
+        {
+            FDD_REQUIRE(normal[a] != nullptr);
+            outs[num_out++] = nrm.p[a] = normal[a];
+        }
+    // no output is an input, and no two outputs are the same array
+    const void *const ins[7] = {X.p[0], X.p[1], X.p[2], D_hat, gll_weights, face_elem, face_side};
+    for (int o = 0; o < num_out; o++)
+    {
+        for (const void *in : ins) FDD_REQUIRE(outs[o] != in);
+        for (int q = 0; q < o; q++) FDD_REQUIRE(outs[o] != outs[q]);
+    }
+    fdd_for_n<2, 16>((int)n, [&](auto nc) {
+        constexpr int nv = decltype(nc)::value;
+        hipLaunchKernelGGL((field_surface_kernel<nv>), dim3(num_faces), dim3(SurfaceCfg<nv>::block), 0, fdd_stream(stream), area, nrm, X, D_hat, gll_weights, face_elem, face_side, num_elements);
+    });
+    FDD_LAUNCH_CHECK();
+    return 0;
+}
 
 int fdd_field_mass(double *mass, const double *const xyz[3], const double *D_hat, const double *gll_weights, int num_elements, int poly_degree, void *stream)
 {

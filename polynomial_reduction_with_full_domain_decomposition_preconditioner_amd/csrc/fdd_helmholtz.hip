@@ -132,9 +132,47 @@ int shift_add(T *y, const T *c, const double *scale_dev, const T *x, int n, void
     return 0;
 }
 
+// The same statement on the support of c alone, for a c that is zero on most of the vector (a Robin term lives on the
+// boundary nodes): entry k of the compressed values belongs to element index[k].  The indices are distinct and ascending,
+// so no two lanes meet and nothing but y[index[k]] is written; one entry per lane -- its three accesses are scattered, there
+// is nothing to widen.  An index outside 0..n-1 (the host layer builds the list; a caller's mistake) is skipped, not followed.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void shift_add_indexed_kernel(T *__restrict__ y, const T *__restrict__ c_values, const int *__restrict__ index, long long m, const double *scale, const T *__restrict__ x, int n)
+{
+    const long long stride = (long long)gridDim.x * kBlock;
+    for (long long k = (long long)blockIdx.x * kBlock + threadIdx.x; k < m; k += stride)
+    {
+        const int i = index[k];
+        if (i < 0 || i >= n) continue;
+        T xx = x[i];
+        if (scale) xx = (T)(*scale) * xx;
+        y[i] = y[i] + c_values[k] * xx;
+    }
+}
+
+template <typename T>
+int shift_add_indexed(T *y, const T *c_values, const int *index, int m, const double *scale_dev, const T *x, int n, void *stream)
+{
+    FDD_REQUIRE(n >= 0 && m >= 0 && m <= n);
+    if (m == 0) return 0;
+    FDD_REQUIRE(y != nullptr && c_values != nullptr && index != nullptr && x != nullptr);
+    FDD_REQUIRE(!overlap(y, x, n));
+    const uintptr_t y0 = reinterpret_cast<uintptr_t>(y), y1 = y0 + (uintptr_t)n * sizeof(T);
+    const uintptr_t c0 = reinterpret_cast<uintptr_t>(c_values), i0 = reinterpret_cast<uintptr_t>(index);
+    FDD_REQUIRE(!(y0 < c0 + (uintptr_t)m * sizeof(T) && c0 < y1));
+    FDD_REQUIRE(!(y0 < i0 + (uintptr_t)m * sizeof(int) && i0 < y1));
+    hipLaunchKernelGGL((shift_add_indexed_kernel<T>), dim3(fdd_stream_grid(m, kBlock, kEwMaxBlocks)), dim3(kBlock), 0, fdd_stream(stream), y, c_values, index, (long long)m, scale_dev, x, n);
+    FDD_LAUNCH_CHECK();
+    return 0;
+}
+
 } // namespace
 
 extern "C" {
+
+int fdd_shift_add_indexed(double *y, const double *c_values, const int *index, int m, const double *scale_dev, const double *x, int n, void *stream) { return shift_add_indexed(y, c_values, index, m, scale_dev, x, n, stream); }
+
+int fdd_shift_add_indexed_f32(float *y, const float *c_values, const int *index, int m, const double *scale_dev, const float *x, int n, void *stream) { return shift_add_indexed(y, c_values, index, m, scale_dev, x, n, stream); }
 
 int fdd_shift_add(double *y, const double *c, const double *scale_dev, const double *x, int n, void *stream) { return shift_add(y, c, scale_dev, x, n, stream); }
 

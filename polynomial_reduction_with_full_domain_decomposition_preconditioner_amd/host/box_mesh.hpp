@@ -30,6 +30,16 @@ struct BoxSpec
     // a Nek5000 "Kershaw" export with eps = 0.3).  1.0 = the uniform box.
     double kershaw_eps[2] = {1.0, 1.0}; // eps_y, eps_z in (0, 1]
     bool deformed() const { return kershaw_eps[0] != 1.0 || kershaw_eps[1] != 1.0; }
+    // the boundary condition of the faces x-, x+, y-, y+, z-, z+ of the cube (host/boundary.hpp): 'D' Dirichlet, the points
+    // of the face are masked; 'N' natural, they are unknowns.  A point is masked iff it lies on at least one 'D' face, so an
+    // edge between a 'D' and an 'N' face is Dirichlet.  The same at every level's degree; the Kershaw map keeps the faces.
+    char faces[6] = {'D', 'D', 'D', 'D', 'D', 'D'};
+    bool all_dirichlet() const
+    {
+        for (char c : faces)
+            if (c != 'D') return false;
+        return true;
+    }
 };
 
 // The generalized Kershaw map of the unit cube onto itself (D. Kershaw, J. Comput. Phys. 39 (1981) 375-395, in the 3-D
@@ -206,7 +216,9 @@ MeshData<DType> make_box_mesh(const BoxSpec &spec, int N, int rank)
                             else
                                 m.glo_num[p] = V + 1 + gi + Gx * (gj + Gy * gk);
                             m.node_degree[p] = mult(gi, Gx) * mult(gj, Gy) * mult(gk, Gz);
-                            const bool bd = gi == 0 || gi == Gx - 1 || gj == 0 || gj == Gy - 1 || gk == 0 || gk == Gz - 1;
+                            const bool on_face[6] = {gi == 0, gi == Gx - 1, gj == 0, gj == Gy - 1, gk == 0, gk == Gz - 1};
+                            bool bd = false;
+                            for (int s = 0; s < 6; s++) bd = bd || (on_face[s] && spec.faces[s] == 'D');
                             m.p_mask[p] = bd ? 0.0 : 1.0;
                             m.x[p] = (EX + 0.5 * (zg[i] + 1.0)) * hx;
                             m.y[p] = (EY + 0.5 * (zg[j] + 1.0)) * hy;

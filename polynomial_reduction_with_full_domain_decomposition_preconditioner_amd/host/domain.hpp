@@ -28,6 +28,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "boundary.hpp"
 #include "config.hpp"
 #include "csr_matrix.hpp"
 #include "diffusivity.hpp"
@@ -37,6 +38,7 @@
 #include "gll.hpp"
 #include "gmres.hpp"
 #include "math.hpp"
+#include "precision_ops.hpp"
 #include "projection.hpp"
 #include "timer.hpp"
 
@@ -1047,13 +1049,19 @@ class Domain
     // the stiffness kernels: there the term would be lambda_p B_p u_p per point, two more streams in the kernel that is
     // closest to its register and LDS limits, in every instance of it; on the assembled vectors it is one stream and no
     // stiffness kernel changes.  lambda_B == nullptr or all zero: off.
+    // A c that is zero on most nodes (a Robin term alone: boundary.hpp) is also kept compressed, and the pass that only adds
+    // the term runs on its support (flag "indexed_shift"); the fused shift-and-dot reads both vectors anyway and stays.
     std::vector<DType> shift_nodes_hst;
     fdd::memory shift_nodes;
+    fdd::boundary::ShiftSupport shift_support;
+    bool indexed_shift = fdd::missing_indexed_shift_entry() == nullptr; // on where the entries are: measured faster
+    bool shift_indexed() const { return shift_active() and shift_support.applies(indexed_shift, num_local_nodes); }
     bool shift_active() const { return not shift_nodes_hst.empty(); }
     void set_shift(const DType *lambda_B)
     {
         shift_nodes.free();
         shift_nodes_hst.clear();
+        shift_support.release();
         if (lambda_B == nullptr) return;
         std::vector<DType> c((size_t)num_local_nodes, 0.0);
         bool any = false;
@@ -1068,11 +1076,15 @@ class Domain
         shift_nodes_hst = std::move(c);
         shift_nodes = fdd::dev().malloc<DType>(shift_nodes_hst.size());
         shift_nodes.copyFrom(shift_nodes_hst.data(), shift_nodes_hst.size() * sizeof(DType));
+        shift_support.build(shift_nodes_hst);
     }
     // q^ += c .* p~ behind stiffness_from_nodes + gather_nodes
     void shift_add_nodes(fdd::memory &qn, fdd::memory &pn)
     {
-        if (shift_active()) FDD_CALL(fdd_shift_add(qn.as<double>(), shift_nodes.as<double>(), nullptr, pn.as<double>(), num_local_nodes, fdd::dev().stream));
+        if (shift_indexed())
+            fdd::ops::shift_add_indexed(qn.as<double>(), shift_support.values.as<double>(), shift_support.index.as<int>(), shift_support.count, nullptr, pn.as<double>(), num_local_nodes, fdd::dev().stream);
+        else if (shift_active())
+            FDD_CALL(fdd_shift_add(qn.as<double>(), shift_nodes.as<double>(), nullptr, pn.as<double>(), num_local_nodes, fdd::dev().stream));
     }
 
     // q^ = (Qt A_L Q + diag(c)) v~ on the caller's node vectors and <v~, q^>: the launches of fcg_nodes_step_residual's

@@ -104,9 +104,30 @@
 #pragma weak fdd_shift_add
 #pragma weak fdd_shift_add_f32
 #pragma weak fdd_shift_add_inner_product
+// and the surface weights of boundary faces (csrc/fdd_field.hip): without it fddh_boundary_surface and fddh_boundary_robin_set
+// refuse, naming the missing entry (missing_boundary_entry)
+#pragma weak fdd_field_surface
+// and the shift on the support of c alone: without them every shift runs the dense pass, and the flag "indexed_shift" refuses
+// to be set to 1, naming the missing entry (missing_indexed_shift_entry)
+#pragma weak fdd_shift_add_indexed
+#pragma weak fdd_shift_add_indexed_f32
 
 namespace fdd
 {
+
+// the first entry a Robin coefficient needs beyond a Helmholtz shift's that the loaded kernel library does not export, or nullptr
+inline const char *missing_boundary_entry()
+{
+    if (&fdd_field_surface == nullptr) return "fdd_field_surface";
+    return nullptr;
+}
+
+inline const char *missing_indexed_shift_entry()
+{
+    if (&fdd_shift_add_indexed == nullptr) return "fdd_shift_add_indexed";
+    if (&fdd_shift_add_indexed_f32 == nullptr) return "fdd_shift_add_indexed_f32";
+    return nullptr;
+}
 
 // the first entry a Helmholtz shift needs that the loaded kernel library does not export (the mass matrix it is made from
 // among them), or nullptr

@@ -18,6 +18,7 @@
 #include <functional>
 #include <vector>
 
+#include "boundary.hpp"
 #include "box_mesh.hpp"
 #include "domain.hpp"
 #include "field_ops.hpp"
@@ -58,6 +59,17 @@ struct fddh_problem
 
     double helmholtz_min = 0.0, helmholtz_max = 0.0; // of the lambda a set Helmholtz shift was made from (fddh_helmholtz_set)
     double diffusivity_min = 0.0, diffusivity_max = 0.0; // of the kappa that is set (fddh_diffusivity_set; 0: none)
+
+    // The two terms the shift is rebuilt from (rebuild_shift), per point of the fine level, each empty while it is off: the
+    // products lambda_q B_q of a set Helmholtz shift and the sums r[q] of a set Robin coefficient (boundary.hpp)
+    std::vector<double> lambda_B, robin_r;
+    double robin_min = 0.0, robin_max = 0.0; // of the alpha that is set (fddh_boundary_robin_set; 0: none)
+    // a generated mesh: its spec (the face codes among it) and the faces of the rank's elements on the surface of the box,
+    // on the host and, from the first fddh_boundary_surface on, on the device.  A problem made from files has neither
+    bool generated = false;
+    fdd::BoxSpec spec;
+    fdd::boundary::FaceList faces;
+    fdd::memory face_elem_dev, face_side_dev;
 
     Domain<SType> &fine() { return domains[poly_degree]; }
     const Domain<SType> &fine() const { return domains.at(poly_degree); }
@@ -193,6 +205,17 @@ const char *helmholtz_inner_refusal(fddh_problem &p, bool inner_fcg = false)
     return inner_fcg ? "a Helmholtz shift needs the inner GMRES or Chebyshev-Jacobi in dof space: the inner FCG does not go through operator_dofs" : nullptr;
 }
 
+// Every face natural and no zeroth-order term: the operator has the constants in its null space, and a solve would converge
+// in the residual to a solution that is off by a constant (the V-cycle returns values of no meaning).  Creating such a problem
+// is allowed, because a shift may follow; what would solve with it is refused when it starts.
+const char *singular_refusal(fddh_problem &p)
+{
+    if (!p.generated || p.fine().shift_active()) return nullptr;
+    for (char c : p.spec.faces)
+        if (c == 'D') return nullptr;
+    return "this problem is singular: every face is natural ('N') and no zeroth-order term is set, so the constants are in the operator's null space; give it a 'D' face, a Helmholtz shift (fddh_helmholtz_set) or a Robin coefficient (fddh_boundary_robin_set)";
+}
+
 const char *helmholtz_outer_refusal(fddh_problem &p, bool outer_gmres)
 {
     Domain<SType> &d = p.fine();
@@ -264,6 +287,7 @@ template <typename Run>
 int outer_solve(fddh_problem &p, const double *f, double *u, double *history, int history_cap, int *num_history, int *num_iterations, double *seconds, Run &&run)
 {
     if (const char *why = outer_solve_refusal(p)) return fail("%s", why);
+    if (const char *why = singular_refusal(p)) return fail("%s", why);
     Domain<SType> &d = p.fine();
     fine_round_trip(p, f, u, [&] {
         wall_timed(seconds, [&] { with_preconditioner(p, p.subdomain != nullptr, [&](auto &preconditioner) { run(d, preconditioner); }); });
@@ -646,8 +670,15 @@ int fddh_problem_create_box_ex(fddh_problem **out, const int E[3], const int P[3
 
 int fddh_problem_create_kershaw_ex(fddh_problem **out, const int E[3], const int P[3], int poly_degree, int poly_reduction, int subdomain_overlap, int superdomain_overlap, int flags, double eps_y, double eps_z)
 {
+    return fddh_problem_create_box_faces(out, E, P, poly_degree, poly_reduction, subdomain_overlap, superdomain_overlap, flags, eps_y, eps_z, "DDDDDD");
+}
+
+int fddh_problem_create_box_faces(fddh_problem **out, const int E[3], const int P[3], int poly_degree, int poly_reduction, int subdomain_overlap, int superdomain_overlap, int flags, double eps_y, double eps_z, const char *faces)
+{
     return guarded([&] {
         if (int rc = rank_check()) return rc;
+        const std::string bad_faces = fdd::boundary::faces_refusal(faces);
+        if (!bad_faces.empty()) return fail("%s", bad_faces.c_str());
         if (!(eps_y > 0.0 && eps_y <= 1.0 && eps_z > 0.0 && eps_z <= 1.0)) return fail("Kershaw eps must lie in (0, 1]");
         const int with_subdomain = flags & FDDH_WITH_SUBDOMAIN;
         if (!out || !E || !P || poly_degree < 1 || poly_reduction < 1) return fail("bad argument");
@@ -668,6 +699,10 @@ int fddh_problem_create_kershaw_ex(fddh_problem **out, const int E[3], const int
         }
         spec.kershaw_eps[0] = eps_y;
         spec.kershaw_eps[1] = eps_z;
+        memcpy(spec.faces, faces, 6);
+        p->generated = true;
+        p->spec = spec;
+        p->faces = fdd::boundary::box_faces(spec, fdd::comm().rank);
 
         for (int deg : p->degrees)
         {
@@ -732,6 +767,8 @@ int fddh_problem_destroy(fddh_problem *p)
         p->c.free();
         p->sa.free();
         p->sb.free();
+        p->face_elem_dev.free();
+        p->face_side_dev.free();
         p->fine().projection.release();
         delete p;
         return 0;
@@ -745,8 +782,15 @@ int fddh_write_box_mesh_files(const char *directory, const int E[3], const int P
 
 int fddh_write_kershaw_mesh_files(const char *directory, const int E[3], const int P[3], int poly_degree, int rank, double eps_y, double eps_z)
 {
+    return fddh_write_box_faces_mesh_files(directory, E, P, poly_degree, rank, eps_y, eps_z, "DDDDDD");
+}
+
+int fddh_write_box_faces_mesh_files(const char *directory, const int E[3], const int P[3], int poly_degree, int rank, double eps_y, double eps_z, const char *faces)
+{
     return guarded([&] {
         if (!directory || !E || !P) return fail("null argument");
+        const std::string bad_faces = fdd::boundary::faces_refusal(faces);
+        if (!bad_faces.empty()) return fail("%s", bad_faces.c_str());
         if (!(eps_y > 0.0 && eps_y <= 1.0 && eps_z > 0.0 && eps_z <= 1.0)) return fail("Kershaw eps must lie in (0, 1]");
         fdd::BoxSpec spec;
         for (int d = 0; d < 3; d++)
@@ -756,6 +800,7 @@ int fddh_write_kershaw_mesh_files(const char *directory, const int E[3], const i
         }
         spec.kershaw_eps[0] = eps_y;
         spec.kershaw_eps[1] = eps_z;
+        memcpy(spec.faces, faces, 6);
         MeshData<SType> m = fdd::make_box_mesh<SType>(spec, poly_degree, rank);
         char sub[4096];
         mkdir(directory, 0777);
@@ -1117,6 +1162,17 @@ static int set_fused_projection(fddh_problem &p, const char *, int value)
     return 0;
 }
 
+// a shift whose support is a small share of its vector (a Robin term alone) as a pass over the support
+// (fdd_shift_add_indexed, boundary.hpp: kIndexedShiftShare) or, 0, as the dense pass; the same values either way
+static int set_indexed_shift(fddh_problem &p, const char *, int value)
+{
+    if (value != 0)
+        if (const char *missing = fdd::missing_indexed_shift_entry()) return fail("indexed_shift needs %s, which the loaded kernel library does not export", missing);
+    for (auto &kv : p.domains) kv.second.indexed_shift = value != 0;
+    if (p.subdomain) p.subdomain->indexed_shift = value != 0;
+    return 0;
+}
+
 // 0: the inner FCG / GMRES(m) (set_options' preconditioner_type); 1: the Chebyshev-Jacobi iteration (an option of this
 // build, Subdomain::chebyshev_dofs), which takes the place of either.  What it cannot run on is refused when a solve starts.
 static int set_inner_solver(fddh_problem &p, const char *, int value)
@@ -1228,6 +1284,7 @@ static const CodedFlagRow *coded_flag_row(const std::string &flag)
         {"sub_use_preconditioner", true, set_sub_use_preconditioner},
         {"affine_geometry", false, set_affine_geometry},
         {"fused_projection", false, set_fused_projection},
+        {"indexed_shift", false, set_indexed_shift},
         {"inner_solver", true, set_inner_solver},
         {"inner_chebyshev_order", true, set_inner_chebyshev_order},
         {"inner_chebyshev_lower_permille", true, set_inner_chebyshev_lower_permille},
@@ -1464,6 +1521,28 @@ int fddh_field_weak_divergence(fddh_problem *p, const double *vx, const double *
     });
 }
 
+// The zeroth-order term of the operator from the two terms a caller sets, for both setters (fddh_helmholtz_set,
+// fddh_boundary_robin_set): per point the product lambda_q B_q where a lambda is set, otherwise 0.0, then + r[q] where a
+// Robin coefficient is set; Domain::set_shift sums the points into nodes, the Subdomain takes the node vector in its dofs, and
+// what hangs on the operator is emptied.  With no Robin coefficient the statements are those of a Helmholtz shift alone.
+static void rebuild_shift(fddh_problem &pr)
+{
+    Domain<SType> &d = pr.fine();
+    const size_t np = (size_t)d.num_local_points;
+    const bool was_active = d.shift_active();
+    if (pr.robin_r.empty())
+        d.set_shift(pr.lambda_B.empty() ? nullptr : pr.lambda_B.data());
+    else
+    {
+        std::vector<double> c = pr.lambda_B.empty() ? std::vector<double>(np, 0.0) : pr.lambda_B;
+        for (size_t q = 0; q < np; q++) c[q] = c[q] + pr.robin_r[q];
+        d.set_shift(c.data());
+    }
+    if (Subdomain<PType> *s = pr.subdomain.get())
+        s->set_shift(d.shift_active() ? fdd::helmholtz::dofs_of_nodes(d.shift_nodes_hst, d.scatter_matrix().col_hst.data(), s->point_dof.data(), np, s->dof_count()) : std::vector<double>());
+    operator_changed(pr, OperatorChange::of_shift(was_active));
+}
+
 // ---- fddh_helmholtz_*: -laplace(u) + lambda u through the node-space outer solve and the dof-space inner solve ----
 int fddh_helmholtz_set(fddh_problem *p, double lambda, const double *lambda_points)
 {
@@ -1482,13 +1561,10 @@ int fddh_helmholtz_set(fddh_problem *p, double lambda, const double *lambda_poin
             pr.b.copyTo(lambda_B.data(), fine_bytes(pr));
             fdd::helmholtz::scale_mass(lambda_B, lambda, lambda_points);
         }
-        const bool was_active = d.shift_active();
-        d.set_shift(hi > 0.0 ? lambda_B.data() : nullptr);
-        pr.helmholtz_min = d.shift_active() ? lo : 0.0;
-        pr.helmholtz_max = d.shift_active() ? hi : 0.0;
-        if (Subdomain<PType> *s = pr.subdomain.get())
-            s->set_shift(d.shift_active() ? fdd::helmholtz::dofs_of_nodes(d.shift_nodes_hst, d.scatter_matrix().col_hst.data(), s->point_dof.data(), np, s->dof_count()) : std::vector<double>());
-        operator_changed(pr, OperatorChange::of_shift(was_active));
+        pr.lambda_B = std::move(lambda_B);
+        pr.helmholtz_min = hi > 0.0 ? lo : 0.0;
+        pr.helmholtz_max = hi > 0.0 ? hi : 0.0;
+        rebuild_shift(pr);
         return 0;
     });
 }
@@ -1496,7 +1572,7 @@ int fddh_helmholtz_set(fddh_problem *p, double lambda, const double *lambda_poin
 int fddh_helmholtz_info(fddh_problem *p, int *active, double *min, double *max)
 {
     return on_problem(p, true, [&](fddh_problem &pr) {
-        if (active) *active = pr.fine().shift_active() ? 1 : 0;
+        if (active) *active = pr.lambda_B.empty() ? 0 : 1;
         if (min) *min = pr.helmholtz_min;
         if (max) *max = pr.helmholtz_max;
         return 0;
@@ -1526,6 +1602,144 @@ int fddh_helmholtz_node_operator(fddh_problem *p, const double *v_nodes, double 
         if (vq) *vq = dot;
         vn.free();
         qn.free();
+        return 0;
+    });
+}
+
+// ---- fddh_boundary_*: Neumann and Robin faces of the generated meshes (host/boundary.hpp) ----
+// why the face entries cannot run on this problem, or nullptr
+static const char *face_list_refusal(const fddh_problem &pr)
+{
+    if (!pr.generated) return "this problem was made from mesh files and has no face list: the boundary entries know the faces of the generated box meshes only";
+    if (pr.fine().mesh.dim != 3) return "the boundary entries are 3-D only";
+    return nullptr;
+}
+
+// area (and, where normal[0] is given, the three components of the normal) of every point of the problem's face list, on the host
+static int face_surface(fddh_problem &pr, double *area, double *const normal[3])
+{
+    Domain<SType> &d = pr.fine();
+    if (const char *missing = fdd::missing_boundary_entry()) return fail("the surface weights need %s, which the loaded kernel library does not export", missing);
+    if (d.poly_degree < 1 || d.poly_degree > 15) return fail("the surface weights support poly_degree 1..15, got %d", d.poly_degree);
+    const int m = pr.faces.size(), n = d.poly_degree + 1;
+    if (m == 0) return 0;
+    const size_t count = (size_t)m * n * n;
+    if (pr.face_elem_dev.size() == 0)
+    {
+        pr.face_elem_dev = fdd::dev().malloc<int>(m);
+        pr.face_elem_dev.copyFrom(pr.faces.elem.data(), m * sizeof(int));
+        pr.face_side_dev = fdd::dev().malloc<int>(m);
+        pr.face_side_dev.copyFrom(pr.faces.side.data(), m * sizeof(int));
+    }
+    d.field_geometry.upload(d.mesh, d.poly_degree);
+    const double *X[3];
+    for (int a = 0; a < 3; a++) X[a] = d.field_geometry.xyz[a].as<double>();
+    // the temporaries are freed however this function is left: a kernel entry or a copy that throws leaves the problem usable
+    struct Outputs
+    {
+        fdd::memory m[4];
+        ~Outputs()
+        {
+            for (fdd::memory &x : m)
+                try
+                {
+                    x.free();
+                }
+                catch (...) // nothing may leave a destructor; what threw on the way here is the error the caller sees
+                {
+                }
+        }
+    } outputs;
+    fdd::memory *const out = outputs.m;
+    const int num_out = normal ? 4 : 1;
+    for (int o = 0; o < num_out; o++) out[o] = fdd::dev().malloc<double>(count);
+    double *const nrm[3] = {out[1].as<double>(), out[2].as<double>(), out[3].as<double>()};
+    FDD_CALL(fdd_field_surface(out[0].as<double>(), normal ? nrm : nullptr, X, d.D_hat.as<double>(), d.field_geometry.weights.as<double>(), pr.face_elem_dev.as<int>(), pr.face_side_dev.as<int>(), m, d.num_local_elements,
+                               d.poly_degree, fdd::dev().stream));
+    out[0].copyTo(area, count * sizeof(double));
+    for (int a = 0; normal && a < 3; a++) out[1 + a].copyTo(normal[a], count * sizeof(double));
+    return 0;
+}
+
+int fddh_boundary_info(fddh_problem *p, char *faces_out, int *num_faces, int *robin_active, double *alpha_min, double *alpha_max, long long *shift_support, int *indexed_shift, int *indexed_in_use)
+{
+    return on_problem(p, true, [&](fddh_problem &pr) {
+        Domain<SType> &d = pr.fine();
+        if (faces_out)
+        {
+            memcpy(faces_out, pr.generated ? pr.spec.faces : "\0\0\0\0\0\0", 6);
+            faces_out[6] = '\0';
+        }
+        if (num_faces) *num_faces = pr.generated ? pr.faces.size() : -1;
+        if (robin_active) *robin_active = pr.robin_r.empty() ? 0 : 1;
+        if (alpha_min) *alpha_min = pr.robin_min;
+        if (alpha_max) *alpha_max = pr.robin_max;
+        if (shift_support) *shift_support = d.shift_active() ? d.shift_support.count : 0;
+        if (indexed_shift) *indexed_shift = d.indexed_shift ? 1 : 0;
+        if (indexed_in_use) *indexed_in_use = (d.shift_indexed() ? 1 : 0) | (pr.subdomain && pr.subdomain->shift_indexed() ? 2 : 0);
+        return 0;
+    });
+}
+
+int fddh_boundary_faces(fddh_problem *p, int *elem, int *side, int m)
+{
+    return on_problem(p, elem && side, [&](fddh_problem &pr) {
+        if (const char *why = face_list_refusal(pr)) return fail("%s", why);
+        if (m != pr.faces.size()) return fail("the face list has %d entries, got %d", pr.faces.size(), m);
+        for (int f = 0; f < m; f++)
+        {
+            elem[f] = pr.faces.elem[f];
+            side[f] = pr.faces.side[f];
+        }
+        return 0;
+    });
+}
+
+int fddh_boundary_surface(fddh_problem *p, double *area, double *nx, double *ny, double *nz, long long count)
+{
+    return on_problem(p, area != nullptr && (bool(nx) == bool(ny)) && (bool(ny) == bool(nz)), [&](fddh_problem &pr) {
+        if (const char *why = face_list_refusal(pr)) return fail("%s", why);
+        const long long n = pr.poly_degree + 1, want = (long long)pr.faces.size() * n * n;
+        if (count != want) return fail("the surface arrays have %lld entries (faces x (N+1)^2), got %lld", want, count);
+        double *const normal[3] = {nx, ny, nz};
+        return face_surface(pr, area, nx ? normal : nullptr);
+    });
+}
+
+int fddh_boundary_robin_set(fddh_problem *p, const double *alpha_face_points)
+{
+    return on_problem(p, true, [&](fddh_problem &pr) {
+        if (const char *why = face_list_refusal(pr)) return fail("%s", why);
+        Domain<SType> &d = pr.fine();
+        if (alpha_face_points == nullptr)
+        {
+            if (pr.robin_r.empty()) return 0;
+            pr.robin_r.clear();
+            pr.robin_min = pr.robin_max = 0.0;
+            rebuild_shift(pr);
+            return 0;
+        }
+        if (const char *missing = fdd::missing_boundary_entry()) return fail("a Robin coefficient needs %s, which the loaded kernel library does not export", missing);
+        const size_t np = (size_t)d.num_local_points;
+        std::string why = fdd::helmholtz::refusal(fdd::missing_helmholtz_entry(), fdd::comm().size, d.mesh.dim, d.poly_degree, pr.subdomain && pr.subdomain->composite(), pr.subdomain ? (long long)pr.subdomain->point_dof.size() : -1, 0.0, nullptr, (long long)np);
+        const int n = d.poly_degree + 1;
+        if (why.empty()) why = fdd::boundary::robin_refusal(alpha_face_points, pr.faces, n, d.mesh.p_mask);
+        if (!why.empty()) return fail("%s", why.c_str());
+        const size_t count = (size_t)pr.faces.size() * n * n;
+        const auto range = count ? std::minmax_element(alpha_face_points, alpha_face_points + count) : std::make_pair(alpha_face_points, alpha_face_points);
+        const double lo = count ? *range.first : 0.0, hi = count ? *range.second : 0.0;
+        std::vector<double> r;
+        if (hi > 0.0)
+        {
+            std::vector<double> area(count);
+            if (int rc = face_surface(pr, area.data(), nullptr)) return rc;
+            r = fdd::boundary::robin_points(alpha_face_points, area.data(), pr.faces, n, np);
+        }
+        if (r.empty() && pr.robin_r.empty()) return 0; // an all-zero alpha on a problem without one: nothing changes
+        pr.robin_r = std::move(r);
+        pr.robin_min = hi > 0.0 ? lo : 0.0;
+        pr.robin_max = hi > 0.0 ? hi : 0.0;
+        rebuild_shift(pr);
         return 0;
     });
 }
@@ -1678,6 +1892,7 @@ int fddh_problem_precond_apply(fddh_problem *p, int type, const double *r, doubl
     return on_subdomain(p, r && z, [&](fddh_problem &pr, Subdomain<PType> &s) {
         if (const char *why = inner_solver_refusal(pr)) return fail("%s", why);
         if (const char *why = helmholtz_inner_refusal(pr, type == 0)) return fail("%s", why);
+        if (const char *why = singular_refusal(pr)) return fail("%s", why);
         fine_round_trip(pr, r, z, [&] {
             if (type == 0)
                 s.flexible_conjugate_gradient(pr.b, pr.a);
@@ -1796,6 +2011,7 @@ int fddh_problem_pcg_begin(fddh_problem *p, const double *f)
     return on_problem(p, f != nullptr, [&](fddh_problem &pr) {
         if (const char *why = outer_solve_refusal(pr)) return fail("%s", why);
         if (const char *why = helmholtz_outer_refusal(pr, false)) return fail("%s", why);
+        if (const char *why = singular_refusal(pr)) return fail("%s", why);
         Domain<SType> &d = pr.fine();
         pr.a.copyFrom(f, fine_bytes(pr));
         with_preconditioner(pr, pr.subdomain && d.use_preconditioner, [&](auto &preconditioner) { d.fcg_begin(pr.b, pr.a, preconditioner); });

@@ -53,6 +53,19 @@ inline void shift_add(float *y, const float *c, const double *scale_dev, const f
     FDD_CALL(fdd_shift_add_f32(y, c, scale_dev, x, n, s));
 }
 
+// the same on the m entries of c's support (host/boundary.hpp: ShiftSupport); an entry moves two values of y, one of x, one of
+// c and its index, each scattered access a line of its own at worst
+inline void shift_add_indexed(double *y, const double *c_values, const int *index, int m, const double *scale_dev, const double *x, int n, void *s)
+{
+    ProfileScope prof("shift_add_indexed_kernel<f64>", (8.0 * 4 + 4.0) * m);
+    FDD_CALL(fdd_shift_add_indexed(y, c_values, index, m, scale_dev, x, n, s));
+}
+inline void shift_add_indexed(float *y, const float *c_values, const int *index, int m, const double *scale_dev, const float *x, int n, void *s)
+{
+    ProfileScope prof("shift_add_indexed_kernel<f32>", (4.0 * 4 + 4.0) * m);
+    FDD_CALL(fdd_shift_add_indexed_f32(y, c_values, index, m, scale_dev, x, n, s));
+}
+
 // ---- the Arnoldi step's reductions: out[k] = <a, s_k b_k>, and dst = y + sign sum c_k (s_k x_k) with |dst|^2 ----
 // w: the norm weight of the dofs (null: 1 everywhere, not read).  The float entries take none.
 inline void multi_dot(double *out, double *ws, const double *a, const double *const *b, const double *b_scale, int m, const double *w, int n, void *s)

@@ -977,7 +977,10 @@ class Subdomain
     void operator_dofs(Real *y, Real *x, const double *scale_dev = nullptr)
     {
         stiffness_operator_dofs(y, x, scale_dev);
-        if (shift_active()) fdd::ops::shift_add(y, (std::is_same<Real, float>::value ? shift_dofs_f32 : shift_dofs).template as<Real>(), scale_dev, x, dof_space_size(), fdd::dev().stream);
+        if (shift_indexed())
+            fdd::ops::shift_add_indexed(y, (std::is_same<Real, float>::value ? shift_support.values_f32 : shift_support.values).template as<Real>(), shift_support.index.template as<int>(), shift_support.count, scale_dev, x, dof_space_size(), fdd::dev().stream);
+        else if (shift_active())
+            fdd::ops::shift_add(y, (std::is_same<Real, float>::value ? shift_dofs_f32 : shift_dofs).template as<Real>(), scale_dev, x, dof_space_size(), fdd::dev().stream);
     }
 
     template <typename Real>
@@ -1158,13 +1161,18 @@ class Subdomain
     // operator_changed.
     std::vector<double> shift_dofs_hst;
     fdd::memory shift_dofs, shift_dofs_f32;
+    fdd::boundary::ShiftSupport shift_support; // the entries of c that are not zero (boundary.hpp); flag "indexed_shift"
+    bool indexed_shift = fdd::missing_indexed_shift_entry() == nullptr;
     bool shift_active() const { return not shift_dofs_hst.empty(); }
+    bool shift_indexed() const { return shift_active() and shift_support.applies(indexed_shift, dof_space_size()); }
     void set_shift(const std::vector<double> &c)
     {
         shift_dofs.free();
         shift_dofs_f32.free();
+        shift_support.release();
         shift_dofs_hst = c;
         if (c.empty()) return;
+        shift_support.build(c);
         shift_dofs = fdd::dev().malloc<DType>(c.size());
         shift_dofs.copyFrom(c.data(), c.size() * sizeof(DType));
         shift_dofs_f32 = fdd::to_float(c);

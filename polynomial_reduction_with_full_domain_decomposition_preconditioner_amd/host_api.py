@@ -302,20 +302,19 @@ class Problem:
         return (WITH_SUBDOMAIN if with_subdomain else 0) | (BLOCK_LOCAL if block_local else 0) | (FORCE_COMPOSITE if force_composite else 0)
 
     @classmethod
-    def box(cls, E, P=(1, 1, 1), poly_degree=7, poly_reduction=2, with_subdomain=True, subdomain_overlap=1, superdomain_overlap=1, block_local=False, force_composite=False):
+    def box(cls, E, P=(1, 1, 1), poly_degree=7, poly_reduction=2, with_subdomain=True, subdomain_overlap=1, superdomain_overlap=1, block_local=False, force_composite=False, faces="DDDDDD"):
         """With more than one rank the Subdomain is the full-domain-decomposition composite (own elements, rings at
-        reduced degree, coarsened superdomain); block_local keeps the rank's own elements only."""
-        h = vp()
-        _H().call("fddh_problem_create_box_ex", ctypes.byref(h), _arr3(E), _arr3(P), poly_degree, poly_reduction, subdomain_overlap, superdomain_overlap, cls._flags(with_subdomain, block_local, force_composite))
-        return cls(h)
+        reduced degree, coarsened superdomain); block_local keeps the rank's own elements only.  faces: the boundary
+        condition of x-, x+, y-, y+, z-, z+, 'D' Dirichlet (masked) or 'N' natural; see robin and boundary_rhs."""
+        return cls.kershaw(E, P, poly_degree, poly_reduction, 1.0, with_subdomain, subdomain_overlap, superdomain_overlap, block_local, force_composite, faces=faces)
 
     @classmethod
-    def kershaw(cls, E, P=(1, 1, 1), poly_degree=7, poly_reduction=2, eps=0.3, with_subdomain=True, subdomain_overlap=1, superdomain_overlap=1, block_local=False, force_composite=False, eps_z=None):
+    def kershaw(cls, E, P=(1, 1, 1), poly_degree=7, poly_reduction=2, eps=0.3, with_subdomain=True, subdomain_overlap=1, superdomain_overlap=1, block_local=False, force_composite=False, eps_z=None, faces="DDDDDD"):
         """The box under the generalized Kershaw map (the reference's experiment geometry, run.py:25-47: eps = 0.3); all
-        six geometric factors are non-zero.  eps = 1 is the uniform box."""
+        six geometric factors are non-zero.  eps = 1 is the uniform box.  faces: as in box (the map keeps the faces)."""
         h = vp()
-        _H().call("fddh_problem_create_kershaw_ex", ctypes.byref(h), _arr3(E), _arr3(P), poly_degree, poly_reduction, subdomain_overlap, superdomain_overlap,
-                  cls._flags(with_subdomain, block_local, force_composite), ctypes.c_double(eps), ctypes.c_double(eps if eps_z is None else eps_z))
+        _H().call("fddh_problem_create_box_faces", ctypes.byref(h), _arr3(E), _arr3(P), poly_degree, poly_reduction, subdomain_overlap, superdomain_overlap,
+                  cls._flags(with_subdomain, block_local, force_composite), ctypes.c_double(eps), ctypes.c_double(eps if eps_z is None else eps_z), str(faces).encode())
         return cls(h)
 
     @classmethod
@@ -536,6 +535,86 @@ class Problem:
         vq = ctypes.c_double()
         _H().call("fddh_helmholtz_node_operator", self.h, _dp(v), _dp(q), len(v), ctypes.byref(vq))
         return q, vq.value
+
+    # --- Neumann and Robin faces (an addition of this build, include/fdd_host.h) ---
+    def boundary_info(self):
+        """{"faces", "num_faces", "robin_active", "alpha_min", "alpha_max", "shift_support", "indexed_shift",
+        "indexed_outer", "indexed_inner"}: the face codes ("" and -1 faces for a problem made from files), the range of a
+        set Robin coefficient, the non-zero entries of the node shift and which shift kernel the operators run"""
+        codes = ctypes.create_string_buffer(7)
+        m, on, flag, use = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        lo, hi, support = ctypes.c_double(), ctypes.c_double(), ctypes.c_longlong()
+        _H().call("fddh_boundary_info", self.h, codes, ctypes.byref(m), ctypes.byref(on), ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(support), ctypes.byref(flag), ctypes.byref(use))
+        return {"faces": codes.value.decode(), "num_faces": m.value, "robin_active": bool(on.value), "alpha_min": lo.value, "alpha_max": hi.value, "shift_support": support.value,
+                "indexed_shift": bool(flag.value), "indexed_outer": bool(use.value & 1), "indexed_inner": bool(use.value & 2)}
+
+    def surface(self, normal=True):
+        """The faces of the rank's elements on the surface of the box, sorted by (side, element): {"elem", "side"} (m each;
+        side = 2 axis + upper), "points" (m, n, n): the index of every face point in a point vector, [f, b, a] with (a, b) =
+        (j, k) on x-faces, (i, k) on y-faces, (i, j) on z-faces, "area" (m, n, n): the weight of the surface integral, and
+        "normal" (3, m, n, n): the unit outward normal (None with normal=False).  The integral of g over the surface is
+        (area * g[points]).sum(); the flux du/dn is sum_a normal[a] * gradient(u)[a][points]."""
+        m, n = self.boundary_info()["num_faces"], self.level_degree(0) + 1
+        elem, side = np.zeros(max(m, 0), np.int32), np.zeros(max(m, 0), np.int32)
+        ip = ctypes.POINTER(ctypes.c_int)
+        _H().call("fddh_boundary_faces", self.h, elem.ctypes.data_as(ip), side.ctypes.data_as(ip), m)
+        area = np.zeros((m, n, n))
+        nrm = np.zeros((3, m, n, n)) if normal else None
+        _H().call("fddh_boundary_surface", self.h, _dp(area), *([_dp(nrm[a]) for a in range(3)] if normal else [None] * 3), ctypes.c_longlong(area.size))
+        b, a = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
+        fixed = np.where(side % 2 == 1, n - 1, 0)[:, None, None]
+        axis = (side // 2)[:, None, None]
+        in_elem = np.where(axis == 0, fixed + n * (a + n * b), np.where(axis == 1, a + n * (fixed + n * b), a + n * (b + n * fixed)))
+        return {"elem": elem, "side": side, "points": elem.astype(np.int64)[:, None, None] * n**3 + in_elem, "area": area, "normal": nrm}
+
+    def robin(self, alpha):
+        """The condition kappa du/dn + alpha u = g on natural faces from here on: alpha None (clears), {side: value} (a
+        constant on every face of those sides, 0 elsewhere; masked points -- the edges shared with a 'D' face -- are left
+        at 0) or an (m, n, n) array over surface()["points"], >= 0 and 0 on masked points.  One rank, conforming region.
+        The datum g enters the right-hand side as a flux (boundary_rhs)."""
+        if alpha is None:
+            _H().call("fddh_boundary_robin_set", self.h, None)
+            return
+        if isinstance(alpha, dict):
+            s = self.surface(normal=False)
+            free = self.mesh_array("p_mask")[s["points"]] != 0.0
+            values = np.zeros(s["area"].shape)
+            for side, value in alpha.items():
+                if int(side) not in range(6):
+                    raise ValueError("a side is 0..5 (x-, x+, y-, y+, z-, z+), got %r" % (side,))
+                values[s["side"] == int(side)] = float(value)
+            alpha = values * free
+        alpha = np.ascontiguousarray(alpha, dtype=np.float64)
+        m, n = self.boundary_info()["num_faces"], self.level_degree(0) + 1
+        if alpha.shape != (m, n, n):
+            raise ValueError("alpha has one value per face point, shape %s, got %s" % ((m, n, n), alpha.shape))
+        _H().call("fddh_boundary_robin_set", self.h, _dp(alpha))
+
+    def boundary_rhs(self, f, dirichlet=None, flux=None, lam=0.0):
+        """The right-hand side of a problem with boundary data, f' = f - A_L u_D - lam * B * u_D + scatter(area * flux):
+          dirichlet  the prescribed values, an array over the points (read at the masked points only) or a scalar; u_D is
+                     that on the masked points and 0 elsewhere
+          flux       the natural datum per face point, (m, n, n) over surface()["points"]: the Neumann datum or the g of a
+                     Robin condition.  Under a diffusivity it is kappa du/dn, not du/dn
+          lam        the lam handed to helmholtz()
+        A_L is stiffness(), so a set diffusivity is followed.  The solution is solve(f')[0] + u_D, u_D formed by the caller
+        as here (the solve leaves the masked points at 0).  Numpy on the host:
+        the data are formed once per right-hand side."""
+        out = np.array(f, dtype=np.float64, copy=True)
+        u_D = np.zeros(self.n)
+        if dirichlet is not None:
+            masked = self.mesh_array("p_mask") == 0.0
+            u_D[masked] = np.broadcast_to(np.asarray(dirichlet, dtype=np.float64), (self.n,))[masked]
+            out -= self.stiffness(u_D)
+            if np.any(np.asarray(lam) != 0.0):
+                out -= lam * self.mass() * u_D
+        if flux is not None:
+            s = self.surface(normal=False)
+            flux = np.asarray(flux, dtype=np.float64)
+            if flux.shape != s["area"].shape:
+                raise ValueError("flux has one value per face point, shape %s, got %s" % (s["area"].shape, flux.shape))
+            np.add.at(out, s["points"].reshape(-1), (s["area"] * flux).reshape(-1))
+        return out
 
     # --- variable diffusivity (an addition of this build, include/fdd_host.h) ---
     def diffusivity(self, kappa):

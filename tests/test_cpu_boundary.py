@@ -1,0 +1,160 @@
+"""Neumann and Robin faces on the CPU: the face codes of the generated meshes through the writer, the dense reference of
+tests/boundary_checks.py on its own, and -- on the CPU build of the host layer (tests/cpu_shim), one child process per check,
+as tests/test_cpu_diffusivity.py runs its own -- solves with inhomogeneous Dirichlet and Neumann data, the refusal of the
+singular problem, and the refusals that name the kernel entries the stand-in lacks.
+
+Figures (each check prints its own).  The dense solve's error against u = sin(4x + 3y + 2z + 0.3) on the 2^3 box, DNDNDN:
+1.8768e-3, 5.1931e-6, 1.1418e-8 at N = 3, 5, 7 without a Robin coefficient and 1.8895e-3, 5.1837e-6, 1.1418e-8 with alpha = 2
+on x+ (pinned to 2 %).  On the stand-in the three preconditioner settings and both outer methods leave a true residual of at
+most 0.96 tau |f^| (bound 10) and an error of at most 1.00002 x the dense solve's own (bound 1.05); iterations at N = 3 / 5:
+35 / 58 unpreconditioned, 19 / 38 with Jacobi, 5 / 5 with the V-cycle (FCG).  The closed-surface sum of the restatement is printed by its test (bound for asking the
+kernel for it in tests/test_gpu_field_surface.py: 1e-12)."""
+import filecmp
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import boundary_checks as B
+import support as S
+from polynomial_reduction_with_full_domain_decomposition_preconditioner_amd import lib
+
+SHIM_DIR = os.path.join(S.HERE, "cpu_shim")
+HOST_CPU_SO = os.path.join(SHIM_DIR, "_build", "libfdd_host_cpu.so")
+
+# measured with this file (test_dense_reference_converges prints them)
+DENSE_ERRORS = {(3, False): 1.8768e-3, (5, False): 5.1931e-6, (7, False): 1.1418e-8, (3, True): 1.8895e-3, (5, True): 5.1837e-6, (7, True): 1.1418e-8}
+
+
+@pytest.fixture(scope="module")
+def cpu_host_lib():
+    subprocess.check_call(["make", "-C", S.ORACLE_DIR, "-s"])
+    subprocess.check_call(["make", "-C", SHIM_DIR, "-s"])
+    assert os.path.exists(HOST_CPU_SO)
+    return HOST_CPU_SO
+
+
+@pytest.fixture(scope="module")
+def writer(cpu_host_lib):
+    """(return code, error text) of the host layer's mesh writer in a child process (the stand-in library must not stay
+    loaded in the test process); faces None: the writer that was there before the codes"""
+
+    def write(directory, E, P, N, rank, faces=None, eps=1.0):
+        csv = lambda v: ",".join(str(t) for t in v)
+        out = subprocess.run([sys.executable, os.path.join(S.HERE, "boundary_checks.py"), cpu_host_lib, "write", str(directory), csv(E), csv(P), str(N), str(rank), "-" if faces is None else "'%s'" % faces, repr(eps)],
+                             capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+        rc, text = out.stdout.rstrip("\n").splitlines()[-1].split("\t")
+        return int(rc), text
+
+    return write
+
+
+@pytest.mark.parametrize("P,rank", [((1, 1, 1), 0), ((2, 1, 1), 0), ((2, 1, 1), 1)])
+def test_codes_DDNNNN_are_the_rod(writer, tmp_path, P, rank):
+    """the written mesh against support.RodMesh: the mask and the integer arrays exactly.  The coordinates and factors of the
+    generator and of the numpy statement differ in the last bit (their GLL points come from different tables: the bound
+    support.kershaw_mesh_of_the_host_layer uses, 1e-13), so those are held bit for bit to the files of the writer that was
+    there before the codes, which differ from these in the mask alone"""
+    E, N = (4, 2, 2), 3
+    rc, text = writer(tmp_path / "rod", E, P, N, rank, "DDNNNN")
+    assert rc == 0, text
+    assert writer(tmp_path / "box", E, P, N, rank)[0] == 0
+    got, box, rod = S.read_mesh_arrays(str(tmp_path / "rod"), N, rank), S.read_mesh_arrays(str(tmp_path / "box"), N, rank), S.RodMesh(E, N, P, rank)
+    assert got["p_mask"].min() == 0.0 and got["p_mask"].max() == 1.0
+    for name, ref in (("glo_num", rod.glo_num), ("node_degree", rod.node_degree), ("p_mask", rod.p_mask)):
+        assert np.array_equal(got[name], ref), name
+    gmax = max(np.abs(g).max() for g in rod.g)
+    for name, ref in [("x", rod.x), ("y", rod.y), ("z", rod.z)] + [("g_%d" % (k + 1), rod.g[k]) for k in range(6)]:
+        assert np.array_equal(got[name].view(np.uint64), box[name].view(np.uint64)), name
+        assert np.abs(got[name] - ref).max() <= 1e-13 * (gmax if name.startswith("g_") else 1.0), name
+    assert not np.array_equal(got["p_mask"], box["p_mask"])
+
+
+@pytest.mark.parametrize("eps", (1.0, 0.3))
+def test_default_codes_write_the_same_files(writer, tmp_path, eps):
+    E, P, N = (6, 2, 2), (2, 1, 1), 3
+    a, b = tmp_path / "a", tmp_path / "b"
+    for rank in range(2):
+        assert writer(str(a), E, P, N, rank, None, eps)[0] == 0 and writer(str(b), E, P, N, rank, "DDDDDD", eps)[0] == 0
+    names = sorted(os.listdir(a / "lx1_4"))
+    assert len(names) == 2 * 13 and names == sorted(os.listdir(b / "lx1_4"))
+    match, mismatch, errors = filecmp.cmpfiles(a / "lx1_4", b / "lx1_4", names, shallow=False)
+    assert len(match) == len(names) and not mismatch and not errors
+
+
+def test_kershaw_keeps_the_faces(writer, tmp_path):
+    """the codes mask the same points under the Kershaw map, whose image of every face of the cube is that face"""
+    E, N, faces = (6, 2, 2), 3, "DNNDND"
+    assert writer(str(tmp_path / "k"), E, (1, 1, 1), N, 0, faces, 0.3)[0] == 0 and writer(str(tmp_path / "b"), E, (1, 1, 1), N, 0, faces, 1.0)[0] == 0
+    k, b = S.read_mesh_arrays(str(tmp_path / "k"), N), S.read_mesh_arrays(str(tmp_path / "b"), N)
+    mesh = S.ArrayMesh(N, 24, k)
+    assert np.array_equal(k["p_mask"], b["p_mask"]) and np.array_equal(k["p_mask"], B.face_mask(mesh, faces))
+
+
+@pytest.mark.parametrize("faces", ("DDDDD", "DDDDDDD", "DDNNNX", "dnnnnn", ""))
+def test_other_codes_are_refused(writer, tmp_path, faces):
+    rc, text = writer(str(tmp_path), (2, 2, 2), (1, 1, 1), 2, 0, faces)
+    assert rc != 0 and "face code" in text and not os.path.exists(tmp_path / "lx1_3"), (rc, text)
+
+
+@pytest.mark.parametrize("robin", (False, True))
+def test_dense_reference_converges(robin):
+    """the reference the solves are held to, alone: spectral convergence to the exact solution with Dirichlet, Neumann and
+    Robin data on DNDNDN, pinned to 2 % of the recorded figures"""
+    for N in (3, 5, 7):
+        err = B.dense_error(N, "DNDNDN", {1: 2.0} if robin else None)
+        print("dense reference N = %d%s: %.4e" % (N, ", alpha = 2 on x+" if robin else "", err))
+        assert abs(err / DENSE_ERRORS[(N, robin)] - 1.0) <= 0.02, (N, robin, err)
+
+
+SURFACE_MESHES = [("box", (3, 3, 1), 7), ("box", (2, 2, 2), 4)] + [("kershaw", (2, 2, 2) if N in (2, 4, 6, 10, 14) else (2, 1, 1), N) for N in (1, 2, 3, 7, 8, 15)]
+
+
+@pytest.mark.parametrize("kind,E,N", SURFACE_MESHES)
+def test_surface_restatement_closes_and_sums_to_the_faces(kind, E, N):
+    """in long double: each side's areas sum to 1, sum area normal = 0 over the closed surface (to 1e-12: the condition under
+    which tests/test_gpu_field_surface.py asks the kernel for it), unit normals, float64 agrees to 1e-13, and on a box the
+    normals are +-e to 1e-13 (the coordinates are doubles: their derivative across a flat face is rounding, not zero)"""
+    import field_checks as F
+
+    mesh = F.mesh_of(kind, E, N)
+    s = B.restated_surface(mesh)
+    assert len(s["elem"]) == 2 * (E[0] * E[1] + E[1] * E[2] + E[0] * E[2])
+    closed = max(abs(float((s["area"] * s["normal"][c]).sum())) for c in range(3))
+    sides = max(abs(float(s["area"][s["side"] == k].sum()) - 1.0) for k in range(6))
+    unit = float(np.abs(sum(s["normal"][c] ** 2 for c in range(3)) - 1).max())
+    d = B.restated_surface(mesh, np.float64)
+    double = float(np.abs(d["area"] / s["area"] - 1).max())
+    print("surface %s %s N = %d: closed %.1e, sides %.1e, unit %.1e, float64 %.1e" % (kind, E, N, closed, sides, unit, double))
+    assert closed <= 1e-12 and sides <= 1e-12 and unit <= 1e-15 and double <= 1e-13
+    if kind == "box":
+        want = np.zeros((3,) + s["area"].shape)
+        for f, side in enumerate(s["side"]):
+            want[side // 2, f] = 1.0 if side % 2 else -1.0
+        assert np.abs(s["normal"] - want).max() <= 1e-13
+
+
+# ---- on the CPU build of the host layer, one child process per check ----
+def run_check(lib_path, name):
+    out = subprocess.run([sys.executable, os.path.join(S.HERE, "boundary_checks.py"), lib_path, name], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and out.stdout.rstrip().endswith("ok"), out.stdout[-6000:] + out.stderr[-4000:]
+    return out.stdout
+
+
+@pytest.mark.parametrize("N", (3, 5))
+def test_solves_with_dirichlet_and_neumann_data(cpu_host_lib, N):
+    out = run_check(cpu_host_lib, "solves_N%d" % N)
+    assert out.count("true residual") == 3 * 2
+
+
+def test_singular_problem_is_created_and_refused(cpu_host_lib):
+    out = run_check(cpu_host_lib, "singular")
+    assert out.count("refused:") == 6 and "singular:" in out
+
+
+def test_missing_kernel_entries_are_named(cpu_host_lib):
+    out = run_check(cpu_host_lib, "missing_entries")
+    assert out.count("refused:") == 3
