@@ -53,6 +53,12 @@ int fdd_get_device(int *device);
 int fdd_device_name(char *buf, size_t buf_len);
 int fdd_malloc(void **ptr, size_t bytes);       /* occa::device::malloc<T>(n) */
 int fdd_free(void *ptr);                        /* occa::memory::free() */
+/* What the library has handed out and not got back, for tests of ownership (the card's free memory is other processes'
+ * too).  Fills the first n of: live fdd_malloc blocks, their bytes, the high-water mark of those bytes since
+ * fdd_live_objects_reset_peak, live plans (fdd_csr_plan_create / _f32), live captured graphs (fdd_graph_end_capture), the
+ * count of fdd_malloc calls that returned a block, ever.  Process-wide: ranks are threads. */
+int fdd_live_objects(long long *out, int n);
+int fdd_live_objects_reset_peak(void);
 int fdd_memcpy_h2d(void *dst, const void *src, size_t bytes, void *stream); /* occa::memory::copyFrom(host): blocking */
 int fdd_memcpy_d2h(void *dst, const void *src, size_t bytes, void *stream); /* occa::memory::copyTo(host): blocking */
 int fdd_memcpy_d2d(void *dst, const void *src, size_t bytes, void *stream); /* occa::memory::copyFrom/To(mem): async */

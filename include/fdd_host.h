@@ -85,6 +85,8 @@ enum
 };
 int fddh_problem_create_box_ex(fddh_problem **out, const int E[3], const int P[3], int poly_degree, int poly_reduction, int subdomain_overlap, int superdomain_overlap, int flags);
 int fddh_problem_create_dir_ex(fddh_problem **out, const char *directory, int poly_degree, int poly_reduction, int subdomain_overlap, int superdomain_overlap, int flags);
+/* frees every device block, plan and captured graph the problem took; refused (and then nothing is freed) from a thread that
+ * is not the rank that built it, or after that rank's fddh_rank_finalize */
 int fddh_problem_destroy(fddh_problem *p);
 /* write the box mesh of this rank as the reference's file set under `directory` */
 int fddh_write_box_mesh_files(const char *directory, const int E[3], const int P[3], int poly_degree, int rank);

@@ -16,6 +16,7 @@
 #define FDD_CU_COUNT 256
 
 void fdd_set_error(const char *fmt, ...);
+void fdd_count_plan(int delta); // fdd_live_objects: a plan was created (+1) or destroyed (-1)
 
 #define FDD_HIP_CHECK(expr)                                                                         \
     do                                                                                              \

@@ -1334,6 +1334,7 @@ static int plan_create(fdd_csr_plan **plan, const int *A_ptr_host, int num_rows,
         for (int i = 0; one && i < num_rows; i++) one = (A_ptr_host[i + 1] == i + 1);
         p->one_per_row = (one && fdd_env_int("FDD_TUNE_CSR_ONE_PER_ROW", 1)) ? 1 : 0;
         *plan = p;
+        fdd_count_plan(+1);
         return 0;
     }
 
@@ -1382,6 +1383,7 @@ static int plan_create(fdd_csr_plan **plan, const int *A_ptr_host, int num_rows,
     }
 
     *plan = p;
+    fdd_count_plan(+1);
     return 0;
 }
 
@@ -1394,6 +1396,7 @@ int fdd_csr_plan_destroy(fdd_csr_plan *plan)
     if (plan->block_meta_dev) (void)hipFree(plan->block_meta_dev);
     release_sell(plan);
     delete plan;
+    fdd_count_plan(-1);
     return 0;
 }
 

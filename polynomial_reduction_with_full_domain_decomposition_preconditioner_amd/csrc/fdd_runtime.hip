@@ -3,8 +3,11 @@
 // in SURVEY.md section 8(b)).
 #include "fdd_common.h"
 
+#include <atomic>
 #include <cstdarg>
 #include <cstring>
+#include <mutex>
+#include <unordered_map>
 
 static thread_local char g_last_error[512] = "";
 
@@ -15,6 +18,26 @@ void fdd_set_error(const char *fmt, ...)
     vsnprintf(g_last_error, sizeof(g_last_error), fmt, ap);
     va_end(ap);
 }
+
+// What fdd_live_objects reports.  Ranks are threads, so the blocks are kept under a mutex.  The map is never destroyed: a
+// free at process exit must still find it.
+namespace
+{
+struct LiveBlocks
+{
+    std::mutex lock;
+    std::unordered_map<void *, size_t> size;
+    long long bytes = 0, peak = 0, mallocs = 0;
+};
+LiveBlocks &live_blocks()
+{
+    static LiveBlocks *b = new LiveBlocks();
+    return *b;
+}
+std::atomic<long long> g_live_plans{0}, g_live_graphs{0};
+} // namespace
+
+void fdd_count_plan(int delta) { g_live_plans += delta; }
 
 extern "C" {
 
@@ -59,6 +82,12 @@ int fdd_malloc(void **ptr, size_t bytes)
     *ptr = nullptr;
     if (bytes == 0) return 0;
     FDD_HIP_CHECK(hipMalloc(ptr, bytes));
+    LiveBlocks &b = live_blocks();
+    std::lock_guard<std::mutex> guard(b.lock);
+    b.size[*ptr] = bytes;
+    b.bytes += (long long)bytes;
+    if (b.bytes > b.peak) b.peak = b.bytes;
+    b.mallocs++;
     return 0;
 }
 
@@ -66,6 +95,32 @@ int fdd_free(void *ptr)
 {
     if (ptr == nullptr) return 0;
     FDD_HIP_CHECK(hipFree(ptr));
+    LiveBlocks &b = live_blocks();
+    std::lock_guard<std::mutex> guard(b.lock);
+    const auto it = b.size.find(ptr);
+    if (it != b.size.end())
+    {
+        b.bytes -= (long long)it->second;
+        b.size.erase(it);
+    }
+    return 0;
+}
+
+int fdd_live_objects(long long *out, int n)
+{
+    FDD_REQUIRE(out != nullptr && n >= 0);
+    LiveBlocks &b = live_blocks();
+    std::lock_guard<std::mutex> guard(b.lock);
+    const long long all[6] = {(long long)b.size.size(), b.bytes, b.peak, g_live_plans.load(), g_live_graphs.load(), b.mallocs};
+    for (int i = 0; i < n && i < 6; i++) out[i] = all[i];
+    return 0;
+}
+
+int fdd_live_objects_reset_peak(void)
+{
+    LiveBlocks &b = live_blocks();
+    std::lock_guard<std::mutex> guard(b.lock);
+    b.peak = b.bytes;
     return 0;
 }
 
@@ -171,6 +226,7 @@ int fdd_graph_end_capture(void *stream, void **graph_exec)
         return (int)err;
     }
     *graph_exec = reinterpret_cast<void *>(exec);
+    g_live_graphs++;
     return 0;
 }
 
@@ -185,6 +241,7 @@ int fdd_graph_destroy(void *graph_exec)
 {
     if (graph_exec == nullptr) return 0;
     FDD_HIP_CHECK(hipGraphExecDestroy(reinterpret_cast<hipGraphExec_t>(graph_exec)));
+    g_live_graphs--;
     return 0;
 }
 

@@ -21,6 +21,7 @@
 
 #include <chrono>
 #include <map>
+#include <memory>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -38,7 +39,7 @@ namespace amg
 struct Csr32
 {
     fdd::memory val;
-    fdd_csr_plan *plan = nullptr;
+    fdd::csr_plan plan;
 };
 
 // matrix-free form of a geometric level's interpolator (fdd_lattice_prolong / _restrict, csrc/fdd_transfer.hip): the maps
@@ -105,17 +106,17 @@ struct View<float>
     static void spmv(CSR_Matrix<double> &M, Csr32 &M32, fdd::memory &y, const float *y_in, fdd::memory &x, float alpha, float beta)
     {
         fdd::ProfileScope prof("csr_block_kernel<f32>", 8.0 * M.num_nnz + 8.0 * M.num_rows + 4.0 * M.num_cols + (beta != 0.0f ? 4.0 * M.num_rows : 0.0));
-        FDD_CALL(fdd_csr_plan_matvec_to_f32(M32.plan, y.as<float>(), y_in, M.ptr.as<int>(), M.col.as<int>(), M32.val.as<float>(), x.as<float>(), alpha, beta, fdd::dev().stream));
+        FDD_CALL(fdd_csr_plan_matvec_to_f32(M32.plan.get(), y.as<float>(), y_in, M.ptr.as<int>(), M.col.as<int>(), M32.val.as<float>(), x.as<float>(), alpha, beta, fdd::dev().stream));
     }
     static void matvec(CSR_Matrix<double> &M, Csr32 &M32, fdd::memory &y, fdd::memory &x, float alpha, float beta) { spmv(M, M32, y, beta != 0.0f ? y.as<float>() : nullptr, x, alpha, beta); }
     static void matvec_to(CSR_Matrix<double> &M, Csr32 &M32, fdd::memory &y, fdd::memory &y_in, fdd::memory &x, float alpha, float beta) { spmv(M, M32, y, y_in.as<float>(), x, alpha, beta); }
     const int *ptr() const { return L.A.ptr.as<int>(); }
     const int *col() const { return L.A.col.as<int>(); }
     const float *val() const { return L.s.A.val.as<float>(); }
-    void smooth_residual(fdd::memory &out, float coef) { FDD_CALL(fdd_amg_smooth_residual_matvec_f32(L.s.A.plan, out.as<float>(), r.as<float>(), ptr(), col(), val(), u.as<float>(), f.as<float>(), D.as<float>(), coef, fdd::dev().stream)); }
-    void smooth_polynomial(fdd::memory &out, fdd::memory &in, float coef) { FDD_CALL(fdd_amg_smooth_polynomial_matvec_f32(L.s.A.plan, out.as<float>(), ptr(), col(), val(), in.as<float>(), r.as<float>(), D.as<float>(), coef, fdd::dev().stream)); }
-    void smooth_update(fdd::memory &in, float coef) { FDD_CALL(fdd_amg_smooth_update_matvec_f32(L.s.A.plan, u.as<float>(), ptr(), col(), val(), in.as<float>(), r.as<float>(), D.as<float>(), coef, fdd::dev().stream)); }
-    void smooth_update_from_zero(fdd::memory &in, float coef) { FDD_CALL(fdd_amg_smooth_update_matvec_from_zero_f32(L.s.A.plan, u.as<float>(), ptr(), col(), val(), in.as<float>(), r.as<float>(), D.as<float>(), coef, fdd::dev().stream)); }
+    void smooth_residual(fdd::memory &out, float coef) { FDD_CALL(fdd_amg_smooth_residual_matvec_f32(L.s.A.plan.get(), out.as<float>(), r.as<float>(), ptr(), col(), val(), u.as<float>(), f.as<float>(), D.as<float>(), coef, fdd::dev().stream)); }
+    void smooth_polynomial(fdd::memory &out, fdd::memory &in, float coef) { FDD_CALL(fdd_amg_smooth_polynomial_matvec_f32(L.s.A.plan.get(), out.as<float>(), ptr(), col(), val(), in.as<float>(), r.as<float>(), D.as<float>(), coef, fdd::dev().stream)); }
+    void smooth_update(fdd::memory &in, float coef) { FDD_CALL(fdd_amg_smooth_update_matvec_f32(L.s.A.plan.get(), u.as<float>(), ptr(), col(), val(), in.as<float>(), r.as<float>(), D.as<float>(), coef, fdd::dev().stream)); }
+    void smooth_update_from_zero(fdd::memory &in, float coef) { FDD_CALL(fdd_amg_smooth_update_matvec_from_zero_f32(L.s.A.plan.get(), u.as<float>(), ptr(), col(), val(), in.as<float>(), r.as<float>(), D.as<float>(), coef, fdd::dev().stream)); }
 };
 
 class Hierarchy
@@ -124,15 +125,14 @@ class Hierarchy
     bool finalized = false;
     // one captured graph per OUTPUT vector of the cycle (vcycle_into: the caller's Krylov vectors stand in for
     // levels[0].u, so that the correction is written where it is wanted instead of being copied there)
-    std::map<const void *, void *> graphs;
+    struct graph_deleter
+    {
+        void operator()(void *g) const { (void)fdd_graph_destroy(g); }
+    };
+    std::map<const void *, std::unique_ptr<void, graph_deleter>> graphs;
     bool graph_failed = false;
 
-    void destroy_graphs()
-    {
-        for (auto &kv : graphs)
-            if (kv.second != nullptr) (void)fdd_graph_destroy(kv.second);
-        graphs.clear();
-    }
+    void destroy_graphs() { graphs.clear(); }
     CSR_Matrix<double> coarse_inverse;
 
 
@@ -263,9 +263,9 @@ class Hierarchy
     {
         M32.val = M.host_mirrors() ? to_f32(M.val_hst) : to_f32_device(M.val, (size_t)M.num_nnz);
         if (M.num_rows == 0 or M.num_cols == 0 or M.ptr_hst.empty()) return;
-        FDD_CALL(fdd_csr_plan_create_f32(&M32.plan, M.ptr_hst.data(), M.num_rows, M.num_cols, M.num_nnz));
+        M32.plan = fdd::make_csr_plan(M.ptr_hst.data(), M.num_rows, M.num_cols, M.num_nnz, true);
         int attached = 0;
-        if (M.num_nnz > M.num_rows) FDD_CALL(fdd_csr_plan_attach_sell(M32.plan, M.ptr_hst.data(), M.ptr.as<int>(), M.col.as<int>(), M32.val.ptr(), 1.3, &attached, fdd::dev().stream));
+        if (M.num_nnz > M.num_rows) FDD_CALL(fdd_csr_plan_attach_sell(M32.plan.get(), M.ptr_hst.data(), M.ptr.as<int>(), M.col.as<int>(), M32.val.ptr(), 1.3, &attached, fdd::dev().stream));
     }
 
     void prepare32()
@@ -292,6 +292,12 @@ class Hierarchy
     }
 
   public:
+    Hierarchy() = default;
+    Hierarchy(Hierarchy &&) = default;
+    Hierarchy &operator=(Hierarchy &&) = default; // `graphs` is declared, and so replaced, before the levels
+    // a graph must not outlive a buffer it names, and `graphs`, declared before the levels, would be destroyed after them
+    ~Hierarchy() { destroy_graphs(); }
+
     int cheby_order = 2; // subdomain.hpp:237
     int num_vcycles = 1; // subdomain.hpp:236
     bool use_graph = true; // AMG/config.hpp:6 USE_CUDA_GRAPH
@@ -361,8 +367,6 @@ class Hierarchy
         destroy_graphs();
     }
 
-    void release_graphs() { destroy_graphs(); } // before the hierarchy is replaced (Subdomain::amg_build)
-
     // a captured graph holds one launch sequence
     void set_fused_smoother(bool on)
     {
@@ -429,7 +433,6 @@ class Hierarchy
 
     Level &new_level(int n)
     {
-        if (levels.capacity() < 32) levels.reserve(32); // a growing vector would copy every level built so far, host mirrors included
         levels.emplace_back();
         levels.back().n = n;
         return levels.back();
@@ -503,7 +506,7 @@ class Hierarchy
         if (f32) prepare32();
         if (use_graph and not graph_failed)
         {
-            void *&graph = graphs[(f32 and f32_io) ? levels[0].s.u.ptr() : levels[0].u.ptr()];
+            auto &graph = graphs[(f32 and f32_io) ? levels[0].s.u.ptr() : levels[0].u.ptr()];
             if (graph == nullptr)
             {
                 // captured once on a private stream (the caller's may be the default stream, which
@@ -519,7 +522,8 @@ class Hierarchy
                         vcycle_launches();
                         fdd::dev().stream = s;
                         fdd::profiler().enabled = profiling;
-                        if (fdd_graph_end_capture(cs, &graph) != 0) graph = nullptr;
+                        void *captured = nullptr;
+                        if (fdd_graph_end_capture(cs, &captured) == 0) graph.reset(captured);
                     }
                     (void)fdd_stream_destroy(cs);
                 }
@@ -528,7 +532,7 @@ class Hierarchy
             if (graph != nullptr)
             {
                 fdd::ProfileScope prof(f32 ? "amg_vcycle<hipGraph,f32>" : "amg_vcycle<hipGraph>", spmv_bytes(f32));
-                FDD_CALL(fdd_graph_launch(graph, s));
+                FDD_CALL(fdd_graph_launch(graph.get(), s));
                 return;
             }
         }

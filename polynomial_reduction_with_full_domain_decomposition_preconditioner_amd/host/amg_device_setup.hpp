@@ -32,11 +32,7 @@ struct DeviceCSR
     std::vector<int> ptr_hst;
     memory ptr, col, val;
     long long nnz() const { return ptr_hst.empty() ? 0 : ptr_hst.back(); }
-    void free()
-    {
-        for (memory *m : {&ptr, &col, &val}) m->free();
-        std::vector<int>().swap(ptr_hst);
-    }
+    void free() { *this = DeviceCSR(); } // before the end of a scope: bounds the peak of a build
 };
 
 // the least free device memory seen at the sample points of a build (FDD_SETUP_TIMING: its peak)
@@ -115,7 +111,6 @@ inline DeviceCSR multiply(const DeviceCSR &A, const DeviceCSR &B)
     row_pointers(C, len);
     FDD_CALL(fdd_amg_setup_spgemm_fill(C.col.as<int>(), C.val.as<double>(), cursor.as<int>(), C.ptr.as<int>(), A.ptr.as<int>(), A.col.as<int>(), A.val.as<double>(), B.ptr.as<int>(), B.col.as<int>(), B.val.as<double>(), A.rows,
                                        B.rows, dev().stream));
-    cursor.free();
     return C;
 }
 
@@ -133,8 +128,6 @@ inline DeviceCSR transpose(const DeviceCSR &A, double drop_tol = -1.0)
     memory cursor = dev().malloc<int>(std::max(A.cols, 1)), src = dev().malloc<int>(std::max<size_t>((size_t)T.nnz(), 1));
     FDD_CALL(fdd_amg_setup_transpose_fill(T.col.as<int>(), val ? T.val.as<double>() : nullptr, cursor.as<int>(), src.as<int>(), T.ptr.as<int>(), A.ptr.as<int>(), A.col.as<int>(), val, A.rows, A.cols, (int)T.nnz(), drop_tol,
                                           dev().stream));
-    cursor.free();
-    src.free();
     return T;
 }
 
@@ -151,7 +144,7 @@ inline DeviceCSR assemble_fem(const double *x, const double *y, const double *z,
     memory K = dev().malloc<double>(np * 27), mask = dev().malloc<unsigned int>(np);
     note_memory();
     FDD_CALL(fdd_amg_setup_fem_stencils(K.as<double>(), mask.as<unsigned int>(), dx.as<double>(), dy.as<double>(), dz.as<double>(), pdof.as<int>(), poly_degree, num_elements, epsilon, dev().stream));
-    for (memory *m : {&dx, &dy, &dz}) m->free();
+    dx = dy = dz = memory(); // bounds the peak
     // dof -> its points in ascending order: the transpose of the point -> dof map
     DeviceCSR P = upload(points, false);
     DeviceCSR Pt = transpose(P);
@@ -163,8 +156,6 @@ inline DeviceCSR assemble_fem(const double *x, const double *y, const double *z,
     row_pointers(A, len);
     note_memory();
     FDD_CALL(fdd_amg_setup_fem_fill(A.col.as<int>(), A.val.as<double>(), A.ptr.as<int>(), Pt.ptr.as<int>(), Pt.col.as<int>(), mask.as<unsigned int>(), K.as<double>(), pdof.as<int>(), poly_degree, num_dofs, dev().stream));
-    for (memory *m : {&K, &mask}) m->free();
-    Pt.free();
     return A;
 }
 
@@ -274,7 +265,6 @@ inline DeviceCSR geometric_level(const DeviceLattice &fine, int num_dofs, Device
         transfer.coarse_dof.resize((size_t)kept_points);
         coarse.point_dof.copyTo(transfer.coarse_dof.data(), (size_t)kept_points * sizeof(int));
     }
-    for (memory *mm : {&first, &kept, &cmap, &owner, &unplaced}) mm->free();
     return P;
 }
 

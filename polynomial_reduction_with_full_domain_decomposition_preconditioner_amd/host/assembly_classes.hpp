@@ -49,12 +49,10 @@ struct AssemblyClasses
     // device copies and the plan of the general rows, made when first used
     bool on_device = false;
     memory point_class_dof_dev, ptr_dev, col_dev, row_map_dev;
-    fdd_csr_plan *plan = nullptr;
+    csr_plan plan;
 
     void clear()
     {
-        for (memory *m : {&point_class_dof_dev, &ptr_dev, &col_dev, &row_map_dev}) m->free();
-        if (plan) FDD_CALL(fdd_csr_plan_destroy(plan));
         *this = AssemblyClasses();
     }
 
@@ -144,15 +142,14 @@ struct AssemblyClasses
         const size_t nr = row_map.size();
         if (nr > 0)
         {
-            FDD_CALL(fdd_csr_plan_create(&plan, ptr.data(), (int)nr, (int)point_class_dof.size(), (int)col.size()));
-            FDD_CALL(fdd_csr_plan_set_unit_values(plan, 1));
+            plan = make_csr_plan(ptr.data(), (int)nr, (int)point_class_dof.size(), (int)col.size());
+            FDD_CALL(fdd_csr_plan_set_unit_values(plan.get(), 1));
             int pipelined = 0;
-            FDD_CALL(fdd_csr_plan_pipelined(plan, &pipelined));
-            FDD_CALL(fdd_csr_plan_num_blocks(plan, &reduced_blocks));
+            FDD_CALL(fdd_csr_plan_pipelined(plan.get(), &pipelined));
+            FDD_CALL(fdd_csr_plan_num_blocks(plan.get(), &reduced_blocks));
             if (not pipelined)
             {
-                FDD_CALL(fdd_csr_plan_destroy(plan));
-                plan = nullptr;
+                plan.reset();
                 unusable = "the plan of the general rows does not run on the pipelined short-row kernel";
                 return false;
             }
@@ -173,7 +170,7 @@ struct AssemblyClasses
         if (row_map.empty()) return;
         // per row: pointer 4, row map 4, y 8; per entry: column 4, value 8; the last pointer
         ProfileScope prof("csr_short_pipelined_kernel<gather, mapped>", 16.0 * (double)row_map.size() + 12.0 * (double)col.size() + 4.0);
-        FDD_CALL(fdd_csr_plan_gather_mapped(plan, y, row_map_dev.as<int>(), ptr_dev.as<int>(), col_dev.as<int>(), q, dev().stream));
+        FDD_CALL(fdd_csr_plan_gather_mapped(plan.get(), y, row_map_dev.as<int>(), ptr_dev.as<int>(), col_dev.as<int>(), q, dev().stream));
     }
 };
 

@@ -137,9 +137,7 @@ struct ShiftSupport
 
     void release()
     {
-        index.free();
-        values.free();
-        values_f32.free();
+        index = values = values_f32 = memory();
         count = 0;
         compressed = false;
     }

@@ -130,9 +130,7 @@ class Comm
             {
                 in[op.peer].resize(op.recv_bytes);
                 rbuf[op.peer].copyTo(in[op.peer].data(), op.recv_bytes);
-                rbuf[op.peer].free();
             }
-            if (op.send_bytes) sbuf[op.peer].free();
         }
         return in;
     }
@@ -145,7 +143,6 @@ class Comm
         tmp.copyFrom(v, n * sizeof(double));
         allreduce_sum(tmp.as<double>(), n);
         tmp.copyTo(v, n * sizeof(double));
-        tmp.free();
     }
 
     void allreduce_max_host(double *v, size_t n)
@@ -155,7 +152,6 @@ class Comm
         tmp.copyFrom(v, n * sizeof(double));
         allreduce_max(tmp.as<double>(), n);
         tmp.copyTo(v, n * sizeof(double));
-        tmp.free();
     }
 
     // MPI_Allgatherv of int64 lists: returns the concatenation in rank order
@@ -188,8 +184,6 @@ class Comm
         allgather(send.ptr(), recv.ptr(), max_count * sizeof(long long));
         std::vector<long long> all(max_count * size);
         recv.copyTo(all.data(), all.size() * sizeof(long long));
-        send.free();
-        recv.free();
 
         std::vector<long long> out;
         for (int p = 0; p < size; p++) out.insert(out.end(), all.begin() + p * max_count, all.begin() + p * max_count + counts[p]);
@@ -466,7 +460,6 @@ class LocalComm : public Comm
     {
         if (n > tmp_n_)
         {
-            tmp_.free();
             tmp_ = dev().malloc<double>(n);
             tmp_n_ = n;
         }

@@ -32,8 +32,8 @@ class CSR_Matrix
     int is_initialized = false;
     DType sparse_tolerance = 1.0e-12;
     std::vector<std::tuple<int, int, DType>> entries;
-    fdd_csr_plan *plan = nullptr;
-    fdd_csr_plan *plan_f32 = nullptr; // the same row blocks as a plan of the f32 entries (prepare_gather_cheby_f32)
+    fdd::csr_plan plan;
+    fdd::csr_plan plan_f32; // the same row blocks as a plan of the f32 entries (prepare_gather_cheby_f32)
     int plan_kind = 0;
     bool plan_pipelined = false; // a short-row plan served by the persistent pipelined kernel (profile labels name the kernel that runs)
     bool lazy_identity = false; // initialize_identity(): the arrays do not exist yet
@@ -65,7 +65,6 @@ class CSR_Matrix
 
     CSR_Matrix() {}
     CSR_Matrix(int num_rows_, int num_cols_) { initialize(num_rows_, num_cols_); }
-    ~CSR_Matrix() {}
 
     void initialize(int num_rows_, int num_cols_)
     {
@@ -194,11 +193,7 @@ class CSR_Matrix
     void adopt_device(int num_rows_, int num_cols_, std::vector<int> &&ptr_, fdd::memory ptr_dev, fdd::memory col_dev, fdd::memory val_dev)
     {
         initialize(num_rows_, num_cols_);
-        if ((num_rows == 0) or (num_cols == 0) or (ptr_[num_rows] == 0))
-        {
-            for (fdd::memory *m : {&ptr_dev, &col_dev, &val_dev}) m->free();
-            return;
-        }
+        if ((num_rows == 0) or (num_cols == 0) or (ptr_[num_rows] == 0)) return;
         ptr_hst = std::move(ptr_);
         col_hst.clear();
         val_hst.clear();
@@ -211,7 +206,6 @@ class CSR_Matrix
             int unit = 0;
             FDD_CALL(fdd_amg_setup_unit_values(flag.as<int>(), val.as<double>(), (long long)num_nnz, fdd::dev().stream));
             flag.copyTo(&unit, sizeof(int));
-            flag.free();
             unit_values = unit != 0;
         }
         is_identity = unit_values and (num_rows == num_cols) and (num_nnz == num_rows);
@@ -233,7 +227,7 @@ class CSR_Matrix
         if ((num_rows == 0) or (num_cols == 0)) return;
         initialization_check();
         fdd::ProfileScope prof(sell ? "sell_kernel<EpiAxpby>" : plan_kind == 0 ? "csr_row_kernel<EpiAxpby>" : (plan_pipelined ? "csr_short_pipelined_kernel<EpiAxpby>" : "csr_block_kernel<EpiAxpby>"), algorithmic_bytes(beta != 0.0));
-        FDD_CALL(fdd_csr_plan_matvec(plan, y.as<double>(), ptr.as<int>(), col.as<int>(), val.as<double>(), x.as<double>(), alpha, beta, fdd::dev().stream));
+        FDD_CALL(fdd_csr_plan_matvec(plan.get(), y.as<double>(), ptr.as<int>(), col.as<int>(), val.as<double>(), x.as<double>(), alpha, beta, fdd::dev().stream));
     }
 
     // y = alpha*A*x + beta*y_in: the copy "y = y_in" that precedes the SpMV in the reference (subdomain.tpp:34-36) folded in
@@ -243,7 +237,7 @@ class CSR_Matrix
         if ((num_rows == 0) or (num_cols == 0)) return;
         initialization_check();
         fdd::ProfileScope prof(sell ? "sell_kernel<EpiAxpby>" : plan_kind == 0 ? "csr_row_kernel<EpiAxpby>" : (plan_pipelined ? "csr_short_pipelined_kernel<EpiAxpby>" : "csr_block_kernel<EpiAxpby>"), algorithmic_bytes(beta != 0.0));
-        FDD_CALL(fdd_csr_plan_matvec_to(plan, y.as<double>(), y_in.as<double>(), ptr.as<int>(), col.as<int>(), val.as<double>(), x.as<double>(), alpha, beta, fdd::dev().stream));
+        FDD_CALL(fdd_csr_plan_matvec_to(plan.get(), y.as<double>(), y_in.as<double>(), ptr.as<int>(), col.as<int>(), val.as<double>(), x.as<double>(), alpha, beta, fdd::dev().stream));
     }
 
     // --- the Chebyshev smoother's element-wise kernels as epilogues of this SpMV (subdomain.tpp:19-83) ---
@@ -253,7 +247,7 @@ class CSR_Matrix
         if ((num_rows == 0) or (num_cols == 0)) return;
         initialization_check();
         fdd::ProfileScope prof(sell ? "sell_kernel<EpiSmoothResidual>" : plan_kind == 0 ? "csr_row_kernel<EpiSmoothResidual>" : "csr_block_kernel<EpiSmoothResidual>", algorithmic_bytes(true) + 16.0 * num_rows);
-        FDD_CALL(fdd_amg_smooth_residual_matvec(plan, work.as<double>(), Sr.as<double>(), ptr.as<int>(), col.as<int>(), val.as<double>(), u.as<double>(), f.as<double>(), D.as<double>(), coef, fdd::dev().stream));
+        FDD_CALL(fdd_amg_smooth_residual_matvec(plan.get(), work.as<double>(), Sr.as<double>(), ptr.as<int>(), col.as<int>(), val.as<double>(), u.as<double>(), f.as<double>(), D.as<double>(), coef, fdd::dev().stream));
     }
 
     // work_out = D*(coef*Sr + D*(A work_in))
@@ -262,7 +256,7 @@ class CSR_Matrix
         if ((num_rows == 0) or (num_cols == 0)) return;
         initialization_check();
         fdd::ProfileScope prof(sell ? "sell_kernel<EpiSmoothPoly>" : plan_kind == 0 ? "csr_row_kernel<EpiSmoothPoly>" : "csr_block_kernel<EpiSmoothPoly>", algorithmic_bytes(true) + 8.0 * num_rows);
-        FDD_CALL(fdd_amg_smooth_polynomial_matvec(plan, work_out.as<double>(), ptr.as<int>(), col.as<int>(), val.as<double>(), work_in.as<double>(), Sr.as<double>(), D.as<double>(), coef, fdd::dev().stream));
+        FDD_CALL(fdd_amg_smooth_polynomial_matvec(plan.get(), work_out.as<double>(), ptr.as<int>(), col.as<int>(), val.as<double>(), work_in.as<double>(), Sr.as<double>(), D.as<double>(), coef, fdd::dev().stream));
     }
 
     // u += D*(coef*Sr + D*(A work_in))
@@ -271,7 +265,7 @@ class CSR_Matrix
         if ((num_rows == 0) or (num_cols == 0)) return;
         initialization_check();
         fdd::ProfileScope prof(sell ? "sell_kernel<EpiSmoothUpdate>" : plan_kind == 0 ? "csr_row_kernel<EpiSmoothUpdate>" : "csr_block_kernel<EpiSmoothUpdate>", algorithmic_bytes(true) + 16.0 * num_rows);
-        FDD_CALL(fdd_amg_smooth_update_matvec(plan, u.as<double>(), ptr.as<int>(), col.as<int>(), val.as<double>(), work_in.as<double>(), Sr.as<double>(), D.as<double>(), coef, fdd::dev().stream));
+        FDD_CALL(fdd_amg_smooth_update_matvec(plan.get(), u.as<double>(), ptr.as<int>(), col.as<int>(), val.as<double>(), work_in.as<double>(), Sr.as<double>(), D.as<double>(), coef, fdd::dev().stream));
     }
 
     // the same from u = 0, which is not read (pre-smoothing)
@@ -280,7 +274,7 @@ class CSR_Matrix
         if ((num_rows == 0) or (num_cols == 0)) return;
         initialization_check();
         fdd::ProfileScope prof(sell ? "sell_kernel<EpiSmoothUpdate>" : plan_kind == 0 ? "csr_row_kernel<EpiSmoothUpdate>" : "csr_block_kernel<EpiSmoothUpdate>", algorithmic_bytes(true) + 8.0 * num_rows);
-        FDD_CALL(fdd_amg_smooth_update_matvec_from_zero(plan, u.as<double>(), ptr.as<int>(), col.as<int>(), val.as<double>(), work_in.as<double>(), Sr.as<double>(), D.as<double>(), coef, fdd::dev().stream));
+        FDD_CALL(fdd_amg_smooth_update_matvec_from_zero(plan.get(), u.as<double>(), ptr.as<int>(), col.as<int>(), val.as<double>(), work_in.as<double>(), Sr.as<double>(), D.as<double>(), coef, fdd::dev().stream));
     }
 
   private:
@@ -313,20 +307,18 @@ class CSR_Matrix
     // the SpMV plan of the device arrays (from the host row pointers)
     void make_plan()
     {
-        if (plan) FDD_CALL(fdd_csr_plan_destroy(plan));
-        if (plan_f32) FDD_CALL(fdd_csr_plan_destroy(plan_f32));
-        plan_f32 = nullptr;
-        FDD_CALL(fdd_csr_plan_create(&plan, ptr_hst.data(), num_rows, num_cols, num_nnz));
-        FDD_CALL(fdd_csr_plan_kind(plan, &plan_kind));
+        plan_f32.reset();
+        plan = fdd::make_csr_plan(ptr_hst.data(), num_rows, num_cols, num_nnz);
+        FDD_CALL(fdd_csr_plan_kind(plan.get(), &plan_kind));
         {
             int pipelined = 0;
-            FDD_CALL(fdd_csr_plan_pipelined(plan, &pipelined));
+            FDD_CALL(fdd_csr_plan_pipelined(plan.get(), &pipelined));
             plan_pipelined = pipelined != 0;
         }
-        FDD_CALL(fdd_csr_plan_set_unit_values(plan, unit_values ? 1 : 0));
+        FDD_CALL(fdd_csr_plan_set_unit_values(plan.get(), unit_values ? 1 : 0));
         // short, even rows (AMG levels, interpolators): a sliced-ELL copy the SpMV entries then run on
         sell = 0;
-        if (not unit_values and num_nnz > num_rows) FDD_CALL(fdd_csr_plan_attach_sell(plan, ptr_hst.data(), ptr.as<int>(), col.as<int>(), val.ptr(), 1.3, &sell, fdd::dev().stream));
+        if (not unit_values and num_nnz > num_rows) FDD_CALL(fdd_csr_plan_attach_sell(plan.get(), ptr_hst.data(), ptr.as<int>(), col.as<int>(), val.ptr(), 1.3, &sell, fdd::dev().stream));
     }
 
   public:
@@ -430,7 +422,7 @@ class CSR_Matrix
         const char *key = (plan_kind == 0) ? (mode == 0 ? "dssum_kernel<fused>" : mode == 1 ? "dssum_kernel<gather>" : "dssum_kernel<scatter>")
                                            : (mode == 0 ? "dssum_block_kernel<fused>" : mode == 1 ? ((plan_pipelined and not node_weight) ? "csr_short_pipelined_kernel<gather>" : "dssum_block_kernel<gather>") : "dssum_block_kernel<scatter>");
         fdd::ProfileScope prof(key, bytes);
-        FDD_CALL(fdd_csr_plan_dssum(plan, out, t, ptr.as<int>(), col.as<int>(), u, node_weight, point_mask, row_lo, row_hi, mode, fdd::dev().stream));
+        FDD_CALL(fdd_csr_plan_dssum(plan.get(), out, t, ptr.as<int>(), col.as<int>(), u, node_weight, point_mask, row_lo, row_hi, mode, fdd::dev().stream));
     }
 
     // t[row] = (sum of u over the row's entries) * node_weight[row]: the gather half alone, on double or on float vectors
@@ -440,7 +432,7 @@ class CSR_Matrix
     {
         if (row_hi <= row_lo or num_nnz == 0) return;
         fdd::ProfileScope prof((plan_pipelined ? "csr_short_pipelined_kernel<gather, f32>" : "dssum_block_kernel<gather, f32>"), 8.0 * (row_hi - row_lo) + 8.0 * num_nnz * ((double)(row_hi - row_lo) / std::max(num_rows, 1)));
-        FDD_CALL(fdd_csr_plan_gather_f32(plan, t, ptr.as<int>(), col.as<int>(), u, row_lo, row_hi, fdd::dev().stream));
+        FDD_CALL(fdd_csr_plan_gather_f32(plan.get(), t, ptr.as<int>(), col.as<int>(), u, row_lo, row_hi, fdd::dev().stream));
     }
 
     // A later step of the Chebyshev-Jacobi inner solve with this gather as the kernel's front half (fdd_csr_plan_gather_cheby,
@@ -450,7 +442,7 @@ class CSR_Matrix
     void gather_cheby(double *x, double *d, double *r_out, const double *u, const double *r_in, const double *dinv, double c_d, double c_r, bool last)
     {
         fdd::ProfileScope prof("csr_short_pipelined_kernel<gather, ChebyStep>", 4.0 * num_rows + 12.0 * num_nnz + 8.0 * num_rows * (last ? 5.0 : 7.0));
-        FDD_CALL(fdd_csr_plan_gather_cheby(plan, x, d, r_out, ptr.as<int>(), col.as<int>(), u, r_in, dinv, c_d, c_r, last ? 1 : 0, fdd::dev().stream));
+        FDD_CALL(fdd_csr_plan_gather_cheby(plan.get(), x, d, r_out, ptr.as<int>(), col.as<int>(), u, r_in, dinv, c_d, c_r, last ? 1 : 0, fdd::dev().stream));
     }
     // The float entry takes a plan of the f32 entries: made here, once, before the first float step (the row pointers come
     // back from the device where release_host() dropped the host's).
@@ -463,21 +455,21 @@ class CSR_Matrix
             fetched.resize((size_t)num_rows + 1);
             ptr.copyTo(fetched.data(), fetched.size() * sizeof(int));
         }
-        FDD_CALL(fdd_csr_plan_create_f32(&plan_f32, (ptr_hst.empty() ? fetched : ptr_hst).data(), num_rows, num_cols, num_nnz));
-        FDD_CALL(fdd_csr_plan_set_unit_values(plan_f32, 1));
+        plan_f32 = fdd::make_csr_plan((ptr_hst.empty() ? fetched : ptr_hst).data(), num_rows, num_cols, num_nnz, true);
+        FDD_CALL(fdd_csr_plan_set_unit_values(plan_f32.get(), 1));
     }
     void gather_cheby(float *x, float *d, float *r_out, const float *u, const float *r_in, const float *dinv, double c_d, double c_r, bool last)
     {
         prepare_gather_cheby_f32();
         fdd::ProfileScope prof("csr_short_pipelined_kernel<gather, ChebyStep, f32>", 4.0 * num_rows + 8.0 * num_nnz + 4.0 * num_rows * (last ? 5.0 : 7.0));
-        FDD_CALL(fdd_csr_plan_gather_cheby_f32(plan_f32, x, d, r_out, ptr.as<int>(), col.as<int>(), u, r_in, dinv, (float)c_d, (float)c_r, last ? 1 : 0, fdd::dev().stream));
+        FDD_CALL(fdd_csr_plan_gather_cheby_f32(plan_f32.get(), x, d, r_out, ptr.as<int>(), col.as<int>(), u, r_in, dinv, (float)c_d, (float)c_r, last ? 1 : 0, fdd::dev().stream));
     }
 
     // out_dev[0] = sum_rows s*s*w with s = (this u)[row]*w[row]
     void gather_weighted_norm2(double *out_dev, double *ws, const double *u, const double *node_weight)
     {
         fdd::ProfileScope prof(plan_kind == 0 ? "gather_norm2_kernel" : "gather_norm2_block_kernel", 4.0 * num_rows + 12.0 * num_nnz + 8.0 * num_rows);
-        FDD_CALL(fdd_csr_plan_gather_weighted_norm2(plan, out_dev, ws, ptr.as<int>(), col.as<int>(), u, node_weight, fdd::dev().stream));
+        FDD_CALL(fdd_csr_plan_gather_weighted_norm2(plan.get(), out_dev, ws, ptr.as<int>(), col.as<int>(), u, node_weight, fdd::dev().stream));
     }
 
     void multiply(fdd::memory &Au, fdd::memory &u) { multiply(Au.as<double>(), u.as<double>()); }
@@ -492,7 +484,7 @@ class CSR_Matrix
             return;
         }
         fdd::ProfileScope prof(plan_kind == 0 ? "csr_row_kernel<EpiPlain>" : "csr_block_kernel<EpiPlain>", algorithmic_bytes(false));
-        FDD_CALL(fdd_csr_plan_multiply(plan, Au, ptr.as<int>(), col.as<int>(), val.as<double>(), u, nullptr, fdd::dev().stream));
+        FDD_CALL(fdd_csr_plan_multiply(plan.get(), Au, ptr.as<int>(), col.as<int>(), val.as<double>(), u, nullptr, fdd::dev().stream));
     }
 
     void multiply_range(fdd::memory &Au, fdd::memory &u, int row_start, int row_end)
@@ -520,7 +512,7 @@ class CSR_Matrix
             return;
         }
         fdd::ProfileScope prof(plan_kind == 0 ? "csr_row_kernel<EpiWeight>" : "csr_block_kernel<EpiWeight>", algorithmic_bytes(true));
-        FDD_CALL(fdd_csr_plan_multiply(plan, Au.as<double>(), ptr.as<int>(), col.as<int>(), val.as<double>(), u.as<double>(), weight.as<double>(), fdd::dev().stream));
+        FDD_CALL(fdd_csr_plan_multiply(plan.get(), Au.as<double>(), ptr.as<int>(), col.as<int>(), val.as<double>(), u.as<double>(), weight.as<double>(), fdd::dev().stream));
     }
 };
 

@@ -87,11 +87,10 @@ struct UnscaledBlocks
     }
 };
 
-inline void free_coef(LevelList &ll)
+inline void clear_coef(LevelList &ll)
 {
-    ll.coef.free();
-    for (memory &m : ll.coef_blocks) m.free();
-    ll.coef_block_of_elem.free();
+    ll.coef = ll.coef_block_of_elem = memory();
+    for (memory &m : ll.coef_blocks) m = memory();
 }
 
 // The members of the coefficient instance, for a 3-D degree-7 list whose unscaled arrays share blocks: kappa on the
@@ -99,7 +98,7 @@ inline void free_coef(LevelList &ll)
 // of the element that holds them, and every element's block.  Nothing where the list is another
 inline void fill_coef(LevelList &ll, const UnscaledBlocks &ub, const double *kappa, const std::vector<double> *const g[3])
 {
-    free_coef(ll);
+    clear_coef(ll);
     if (kappa == nullptr or not ub.shared or ll.dim != 3 or ll.poly_degree != 7 or ll.num_elements == 0) return;
     const size_t ne = (size_t)ll.num_elements, n3 = 512, base = (size_t)ll.first_offset;
     std::vector<int> reps(ub.factor_elem);
@@ -123,7 +122,7 @@ inline void fill_coef(LevelList &ll, const UnscaledBlocks &ub, const double *kap
 // the same members as views of another list's over the same elements (the Subdomain's level-0 list on the Domain's): not owned
 inline void share_coef(LevelList &ll, const LevelList &owner)
 {
-    free_coef(ll);
+    clear_coef(ll);
     if (not owner.coef.ptr()) return;
     ll.coef = owner.coef.slice(0, owner.coef.size());
     for (int f = 0; f < 3; f++) ll.coef_blocks[f] = owner.coef_blocks[f].slice(0, owner.coef_blocks[f].size());
@@ -139,7 +138,7 @@ inline void refresh_list(LevelList &ll)
     detect_shared_blocks(ll);
     const bool had_float_affine = ll.affine_c32.ptr() != nullptr;
     ll.affine_deviation = -1.0;
-    for (memory *m : {&ll.affine_c, &ll.affine_w, &ll.affine_c32, &ll.affine_w32}) m->free();
+    ll.affine_c = ll.affine_w = ll.affine_c32 = ll.affine_w32 = memory();
     ll.affine = ll.affine_requested and detect_affine(ll);
     if (had_float_affine) affine_float_copies(ll);
     const size_t np = ll.num_points();

@@ -420,7 +420,6 @@ class Domain
     {
         if ((int)VA.size() != num_vectors + 1)
         {
-            for (auto &m : VA) m.free();
             VA.resize(num_vectors + 1);
             for (auto &m : VA) m = fdd::dev().malloc<DType>(num_local_points);
             va_valid = 0;
@@ -433,11 +432,7 @@ class Domain
     void allocate_gmres()
     {
         if (gmres_point_vectors == num_vectors) return;
-        for (auto *set : {&V, &Z})
-        {
-            for (auto &v : *set) v.free();
-            set->clear();
-        }
+        for (auto *set : {&V, &Z}) set->clear();
         V.resize(num_vectors + 1);
         for (int i = 0; i < num_vectors + 1; i++) V[i] = fdd::dev().malloc<DType>(num_local_points);
         Z.resize(num_vectors);
@@ -525,7 +520,6 @@ class Domain
 
     Domain() {}
     Domain(char *directory_, int poly_degree_) { initialize(directory_, poly_degree_); }
-    ~Domain() {}
 
     int boundary_nodes_count() const { return num_bdary_nodes; }
     int interface_slots_count() const { return num_interface_slots; }
@@ -1059,7 +1053,7 @@ class Domain
     bool shift_active() const { return not shift_nodes_hst.empty(); }
     void set_shift(const DType *lambda_B)
     {
-        shift_nodes.free();
+        shift_nodes = fdd::memory();
         shift_nodes_hst.clear();
         shift_support.release();
         if (lambda_B == nullptr) return;
@@ -1632,7 +1626,6 @@ class Domain
         }
         if (norm_hist_cap < K)
         {
-            norm_hist.free();
             norm_hist = fdd::dev().malloc<DType>(K);
             norm_hist_cap = K;
         }
@@ -1714,12 +1707,7 @@ class Domain
         const bool points_too = use_preconditioner and composite_precond;
         if (gmres_nodes_vectors != m or (multi and VNA.empty()) or (points_too and VP.empty()))
         {
-            for (auto *set : {&VN, &ZN, &VNA, &VP})
-            {
-                for (auto &v : *set) v.free();
-                set->clear();
-            }
-            nf.free();
+            for (auto *set : {&VN, &ZN, &VNA, &VP}) set->clear();
             nf = fdd::dev().malloc<DType>(std::max(nn, 1));
             VN.resize(m + 1);
             for (auto &v : VN) v = fdd::dev().malloc<DType>(std::max(nn, 1));

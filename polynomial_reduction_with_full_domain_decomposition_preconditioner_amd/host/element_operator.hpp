@@ -201,7 +201,6 @@ inline void detect_zero_factors(LevelList &ll)
     memory flags_dev = dev().malloc<int>(3);
     FDD_CALL(fdd_stiffness_offdiag_zero(flags_dev.as<int>(), ll.G, nullptr, ll.num_elements, ll.poly_degree, dev().stream));
     flags_dev.copyTo(flags, sizeof(flags));
-    flags_dev.free();
     ll.offdiag_zero = flags[0] == 0 and flags[1] == 0 and flags[2] == 0;
 }
 
@@ -222,14 +221,13 @@ inline void detect_shared_blocks(LevelList &ll)
 {
     ll.shared_blocks = false;
     ll.factor_classes = 0;
-    ll.factor_elem.free();
+    ll.factor_elem = memory();
     if (not ll.offdiag_zero or ll.dim != 3 or ll.poly_degree > 15 or ll.num_elements == 0 or missing_stiffness_entry("shared_factor_blocks")) return;
     const size_t ne = (size_t)ll.num_elements;
     std::vector<unsigned long long> hash(ne);
     memory hash_dev = dev().malloc<unsigned long long>(ne);
     FDD_CALL(fdd_stiffness_factor_block_hash(hash_dev.as<unsigned long long>(), ll.G, nullptr, ll.num_elements, ll.poly_degree, dev().stream));
     hash_dev.copyTo(hash.data(), ne * sizeof(unsigned long long));
-    hash_dev.free();
     std::vector<int> rep(ne);
     std::unordered_map<unsigned long long, int> first; // elements in ascending order: the first of a group is its lowest
     for (size_t e = 0; e < ne; e++) rep[e] = first.emplace(hash[e], (int)e).first->second;
@@ -241,12 +239,7 @@ inline void detect_shared_blocks(LevelList &ll)
     rep_dev.copyFrom(rep.data(), ne * sizeof(int));
     FDD_CALL(fdd_stiffness_factor_block_verify(mismatches_dev.as<int>(), ll.G, nullptr, rep_dev.as<int>(), ll.num_elements, ll.poly_degree, dev().stream));
     mismatches_dev.copyTo(&mismatches, sizeof(int));
-    mismatches_dev.free();
-    if (mismatches != 0)
-    {
-        rep_dev.free();
-        return;
-    }
+    if (mismatches != 0) return;
     ll.factor_elem = rep_dev;
     ll.shared_blocks = true;
 }
@@ -566,7 +559,6 @@ inline bool detect_affine(LevelList &ll)
         memory dev_dev = dev().malloc<double>(ll.num_elements);
         FDD_CALL(fdd_stiffness_affine_detect(ll.affine_c.as<double>(), dev_dev.as<double>(), ll.G, nullptr, ll.affine_w.as<double>(), ll.num_elements, ll.poly_degree, dev().stream));
         dev_dev.copyTo(dev_hst.data(), dev_hst.size() * sizeof(double));
-        dev_dev.free();
         ll.affine_deviation = 0.0;
         for (double x : dev_hst) ll.affine_deviation = (x == x) ? std::max(ll.affine_deviation, x) : 1.0;
     }

@@ -4,7 +4,7 @@
  * fdd::memory mirrors the slice of occa::memory the reference's host classes
  * use (copyFrom / copyTo / slice / ptr / free; usage inventory in SURVEY.md
  * section 8(b)) and fdd::device_t mirrors occa::device (malloc<T>, finish),
- * both over the C-ABI of include/fdd_hip.h.  Slices are pointer arithmetic.
+ * both over the C-ABI of include/fdd_hip.h.  Slices are pointer arithmetic on a shared block.
  * A failing C-ABI call prints and exits, the reference's own error style
  * (csr_matrix.tpp:72-76).
  */
@@ -14,6 +14,7 @@
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -212,17 +213,30 @@ inline device_t &dev()
     return d;
 }
 
+// A block of fdd_malloc, given back when its last handle goes.  The deleter runs in destructors: a failed free prints one
+// line and returns (FDD_CALL would exit).
+inline std::shared_ptr<void> own_block(void *p)
+{
+    return std::shared_ptr<void>(p, [](void *q) {
+        if (q != nullptr and fdd_free(q) != 0) fprintf(stderr, "WARNING: fdd_free failed: %s\n", fdd_last_error());
+    });
+}
+
+// Shared ownership, as occa::memory: copies and slices share the block, so no view outlives its storage; free() means "this
+// handle lets go".  A handle made from a raw pointer (owner = false) owns nothing.
 class memory
 {
   private:
+    std::shared_ptr<void> block_;
     char *base_ = nullptr;
     size_t count_ = 0; // elements
     size_t elem_ = 1;  // bytes per element
-    bool owner_ = false;
+
+    memory(std::shared_ptr<void> block, char *base, size_t count, size_t elem) : block_(std::move(block)), base_(base), count_(count), elem_(elem) {}
 
   public:
     memory() {}
-    memory(void *p, size_t count, size_t elem, bool owner) : base_((char *)p), count_(count), elem_(elem), owner_(owner) {}
+    memory(void *p, size_t count, size_t elem, bool owner) : block_(owner ? own_block(p) : nullptr), base_((char *)p), count_(count), elem_(elem) {}
 
     void *ptr() const { return base_; }
     template <typename T>
@@ -246,18 +260,12 @@ class memory
             FDD_CALL(fdd_memcpy_d2h(dst, base_, bytes, dev().stream));
     }
     // device -> device
-    void copyTo(memory dst, size_t bytes) const { FDD_CALL(fdd_memcpy_d2d(dst.base_, base_, bytes, dev().stream)); }
+    void copyTo(const memory &dst, size_t bytes) const { FDD_CALL(fdd_memcpy_d2d(dst.base_, base_, bytes, dev().stream)); }
 
     // element units, as occa::memory::slice(offset, count) (subdomain.tpp:3945-3946)
-    memory slice(size_t offset, size_t count) const { return memory(base_ + offset * elem_, count, elem_, false); }
+    memory slice(size_t offset, size_t count) const { return memory(block_, base_ + offset * elem_, count, elem_); }
 
-    void free()
-    {
-        if (owner_ && base_) FDD_CALL(fdd_free(base_));
-        base_ = nullptr;
-        count_ = 0;
-        owner_ = false;
-    }
+    void free() { *this = memory(); }
 };
 
 template <typename T>
@@ -266,6 +274,22 @@ inline memory device_t::malloc(size_t n)
     void *p = nullptr;
     FDD_CALL(fdd_malloc(&p, n * sizeof(T)));
     return memory(p, n, sizeof(T), true);
+}
+
+// the one owner of a plan of fdd_csr_plan_create / _create_f32
+struct csr_plan_deleter
+{
+    void operator()(fdd_csr_plan *p) const
+    {
+        if (fdd_csr_plan_destroy(p) != 0) fprintf(stderr, "WARNING: fdd_csr_plan_destroy failed: %s\n", fdd_last_error());
+    }
+};
+using csr_plan = std::unique_ptr<fdd_csr_plan, csr_plan_deleter>;
+inline csr_plan make_csr_plan(const int *ptr_hst, int num_rows, int num_cols, int num_nnz, bool f32 = false)
+{
+    fdd_csr_plan *p = nullptr;
+    FDD_CALL((f32 ? fdd_csr_plan_create_f32 : fdd_csr_plan_create)(&p, ptr_hst, num_rows, num_cols, num_nnz));
+    return csr_plan(p);
 }
 
 // Per-kernel timing with HIP events on the rank's own stream (what bench.py's

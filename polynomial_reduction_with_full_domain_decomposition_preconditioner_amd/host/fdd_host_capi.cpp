@@ -45,7 +45,7 @@ struct fddh_problem
     int poly_reduction = 1;
     std::vector<int> degrees; // N, N-r, ..., 1
     std::unordered_map<int, Domain<SType>> domains;
-    std::unique_ptr<Subdomain<PType>> subdomain;
+    std::unique_ptr<Subdomain<PType>> subdomain; // declared after `domains`, so destroyed first: its lists view the Domain's factor arrays
     NoPreconditioner none;
 
     // The rank (= host thread) that built the problem: its device stream, communicator and globals are thread_local, so a
@@ -626,8 +626,6 @@ int fddh_comm_selftest(int n)
                 rb[k].copyTo(got.data(), got.size() * sizeof(double));
                 for (int i = 0; i < n; i++)
                     if (got[i] != (double)(peers[k] + 1) * (i + 1) + 1000.0 * me) return fail("exchange: element %d from rank %d is %g", i, peers[k], got[i]);
-                sb[k].free();
-                rb[k].free();
             }
             std::vector<std::vector<char>> out(R);
             for (int p = 0; p < R; p++) out[p].assign((size_t)(3 + me + 2 * p), (char)(17 * me + p));
@@ -641,8 +639,6 @@ int fddh_comm_selftest(int n)
         }
 
         c.barrier();
-        d.free();
-        g.free();
         return 0;
     });
 }
@@ -759,18 +755,7 @@ int fddh_problem_destroy(fddh_problem *p)
 {
     return guarded([&] {
         if (int rc = rank_check(p)) return rc;
-        // Like the reference (empty destructors, domain.tpp:24-28), device memory of
-        // the host classes is released at process end; the staging vectors are freed.
-        if (!p) return 0;
-        p->a.free();
-        p->b.free();
-        p->c.free();
-        p->sa.free();
-        p->sb.free();
-        p->face_elem_dev.free();
-        p->face_side_dev.free();
-        p->fine().projection.release();
-        delete p;
+        delete p; // every member owns what it holds
         return 0;
     });
 }
@@ -1502,7 +1487,6 @@ int fddh_field_gradient(fddh_problem *p, const double *u, double *gx, double *gy
             else
                 g[a]->copyTo(out[a], fine_bytes(pr));
         }
-        third.free();
         return 0;
     });
 }
@@ -1516,7 +1500,6 @@ int fddh_field_weak_divergence(fddh_problem *p, const double *vx, const double *
         pr.c.copyFrom(vz, fine_bytes(pr));
         ops.weak_divergence(result, pr.a, pr.b, pr.c);
         result.copyTo(out, fine_bytes(pr));
-        result.free();
         return 0;
     });
 }
@@ -1600,8 +1583,6 @@ int fddh_helmholtz_node_operator(fddh_problem *p, const double *v_nodes, double 
         const double dot = d.node_operator(qn, vn);
         qn.copyTo(q_nodes, (size_t)n * sizeof(double));
         if (vq) *vq = dot;
-        vn.free();
-        qn.free();
         return 0;
     });
 }
@@ -1634,23 +1615,7 @@ static int face_surface(fddh_problem &pr, double *area, double *const normal[3])
     d.field_geometry.upload(d.mesh, d.poly_degree);
     const double *X[3];
     for (int a = 0; a < 3; a++) X[a] = d.field_geometry.xyz[a].as<double>();
-    // the temporaries are freed however this function is left: a kernel entry or a copy that throws leaves the problem usable
-    struct Outputs
-    {
-        fdd::memory m[4];
-        ~Outputs()
-        {
-            for (fdd::memory &x : m)
-                try
-                {
-                    x.free();
-                }
-                catch (...) // nothing may leave a destructor; what threw on the way here is the error the caller sees
-                {
-                }
-        }
-    } outputs;
-    fdd::memory *const out = outputs.m;
+    fdd::memory out[4];
     const int num_out = normal ? 4 : 1;
     for (int o = 0; o < num_out; o++) out[o] = fdd::dev().malloc<double>(count);
     double *const nrm[3] = {out[1].as<double>(), out[2].as<double>(), out[3].as<double>()};
@@ -1787,8 +1752,6 @@ int fddh_problem_residual_norm(fddh_problem *p, const double *r, double *norm)
         if (fdd::comm().size > 1) fdd::comm().allreduce_sum(sc.as<double>(), 1);
         double v = 0.0;
         sc.copyTo(&v, sizeof(double));
-        ws.free();
-        sc.free();
         *norm = std::sqrt(v);
         return 0;
     });
@@ -2052,8 +2015,6 @@ int fddh_problem_spmv_time(fddh_problem *p, int which, int iterations, double *a
         fdd::memory y = fdd::dev().malloc<double>(std::max(A.num_rows, 1));
         FDD_CALL(fdd_set_to_value(x.as<double>(), 1.0, A.num_cols, 0, fdd::dev().stream));
         const float ms = spmv_ms(A, x, y, iterations);
-        x.free();
-        y.free();
         *avg_us = 1.0e3 * ms / iterations;
         *algorithmic_bytes = A.algorithmic_bytes(false);
         return 0;
@@ -2095,7 +2056,6 @@ int fddh_problem_comm_time(fddh_problem *p, int iterations, double *avg_us, doub
             avg_us[5] = timed([&] { pr.subdomain->comm_probe_ring_and_coarse(); });
             bytes[5] = pr.subdomain->comm_ring_and_coarse_bytes();
         }
-        scal.free();
         return 0;
     });
 }
@@ -2158,11 +2118,6 @@ int fddh_spmv_stencil_time(int m, int iterations, double *avg_us, double *algori
         *avg_us = 1.0e3 * ms / iterations;
         *algorithmic_bytes = A.algorithmic_bytes(false);
         if (num_nnz) *num_nnz = total;
-        x.free();
-        y.free();
-        A.ptr.free();
-        A.col.free();
-        A.val.free();
         return 0;
     });
 }

@@ -30,7 +30,6 @@ struct FieldGeometry
     FieldGeometry() {}
     FieldGeometry(const FieldGeometry &) = delete;
     FieldGeometry &operator=(const FieldGeometry &) = delete;
-    ~FieldGeometry() { release(); }
 
     template <typename Mesh>
     void upload(const Mesh &mesh, int poly_degree)
@@ -48,13 +47,6 @@ struct FieldGeometry
         weights = dev().malloc<double>(n);
         weights.copyFrom(w.data(), n * sizeof(double));
         uploaded = true;
-    }
-
-    void release()
-    {
-        for (memory &m : xyz) m.free();
-        weights.free();
-        uploaded = false;
     }
 };
 

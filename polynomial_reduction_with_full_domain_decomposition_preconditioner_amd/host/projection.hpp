@@ -59,7 +59,7 @@ class Projection
 
     void release()
     {
-        for (memory *m : {&X, &AX, &x0, &d, &w, &c}) m->free();
+        X = AX = x0 = d = w = c = memory();
         capacity = size = n = ld = 0;
         restarts = 0;
     }

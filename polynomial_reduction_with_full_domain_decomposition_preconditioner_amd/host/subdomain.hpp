@@ -141,15 +141,12 @@ class Subdomain
         {
             if ((int)VA.size() != m + 1)
             {
-                for (auto &v : VA) v.free();
                 VA.resize(m + 1);
                 for (auto &v : VA) v = fdd::dev().malloc<Real>(na);
-                qa.free();
                 qa = fdd::dev().malloc<Real>(na);
             }
             if (keep_Z and (int)ZA.size() != m)
             {
-                for (auto &v : ZA) v.free();
                 ZA.resize(m);
                 for (auto &v : ZA) v = fdd::dev().malloc<Real>(na);
             }
@@ -767,7 +764,6 @@ class Subdomain
             slave_vals = fdd::dev().malloc<DType>(std::max(n_slaves, 1));
         }
         // every region point through one index array into W
-        point_dof_dev.free();
         point_dof_dev = fdd::dev().malloc<int>(std::max(NP, 1));
         point_dof_dev.copyFrom(index.data(), (size_t)NP * sizeof(int));
         // boolean gather: row d < nse collects the points of dof d, row nse + h is hanging point h
@@ -907,7 +903,7 @@ class Subdomain
         auto plan32 = [](amg::Csr32 &M32, CSR_Matrix<DType> &M) {
             if (M.num_rows == 0 or M.num_nnz == 0) return;
             M32.val = fdd::to_float(M.val_hst);
-            FDD_CALL(fdd_csr_plan_create_f32(&M32.plan, M.ptr_hst.data(), M.num_rows, M.num_cols, M.num_nnz));
+            M32.plan = fdd::make_csr_plan(M.ptr_hst.data(), M.num_rows, M.num_cols, M.num_nnz, true);
         };
         if (is_composite)
         {
@@ -925,7 +921,7 @@ class Subdomain
     static void multiply(CSR_Matrix<DType> &M, amg::Csr32 &, double *y, const double *x) { M.multiply(y, x); }
     static void multiply(CSR_Matrix<DType> &M, amg::Csr32 &M32, float *y, const float *x)
     {
-        if (M32.plan) FDD_CALL(fdd_csr_plan_matvec_to_f32(M32.plan, y, nullptr, M.ptr.template as<int>(), M.col.template as<int>(), M32.val.template as<float>(), x, 1.0f, 0.0f, fdd::dev().stream));
+        if (M32.plan) FDD_CALL(fdd_csr_plan_matvec_to_f32(M32.plan.get(), y, nullptr, M.ptr.template as<int>(), M.col.template as<int>(), M32.val.template as<float>(), x, 1.0f, 0.0f, fdd::dev().stream));
     }
 
     // q (points) = A_local (Q (s z~)), s = *scale_dev when given (a basis vector kept unnormalised): one launch per level
@@ -1143,12 +1139,10 @@ class Subdomain
             {
                 fdd::check_lean_table(ll, D_hat[ll.level].first); // the Domain has uploaded this table
                 if (not ll.D_hat32.ptr()) continue;
-                ll.D_hat32.free(); // the float solve was prepared under the table as it was: its copy and its verdict follow
-                ll.D_hat32 = fdd::to_float(D_hat[ll.level].first);
+                ll.D_hat32 = fdd::to_float(D_hat[ll.level].first); // the float solve was prepared under the table as it was: its copy and its verdict follow
                 fdd::check_lean_table32(ll, D_hat[ll.level].first);
             }
-        jacobi_dinv.free();
-        jacobi_dinv_f32.free();
+        jacobi_dinv = jacobi_dinv_f32 = fdd::memory();
         jacobi_diag_hst.clear();
         cheby.lambda = 0.0;
         operator_generation++;
@@ -1167,8 +1161,7 @@ class Subdomain
     bool shift_indexed() const { return shift_active() and shift_support.applies(indexed_shift, dof_space_size()); }
     void set_shift(const std::vector<double> &c)
     {
-        shift_dofs.free();
-        shift_dofs_f32.free();
+        shift_dofs = shift_dofs_f32 = fdd::memory();
         shift_support.release();
         shift_dofs_hst = c;
         if (c.empty()) return;
@@ -1266,9 +1259,7 @@ class Subdomain
         val.copyFrom(M.val.data(), nnz * sizeof(double));
         Dd.copyFrom(D.data(), (size_t)n * sizeof(double));
         if (timing and n > 100000) printf("low_order:   lambda_max on the device: matrix up %.3f s\n", clock() - t0);
-        const double lambda = device_lambda_max(n, M.ptr, ptr, col, val, Dd, iterations);
-        for (fdd::memory *m : {&ptr, &col, &val, &Dd}) m->free();
-        return lambda;
+        return device_lambda_max(n, M.ptr, ptr, col, val, Dd, iterations);
     }
     // the same on a matrix and a D that are in HBM already (ptr_hst: the host's copy of the row pointers)
     double device_lambda_max(int n, const std::vector<int> &ptr_hst, const fdd::memory &ptr, const fdd::memory &col, const fdd::memory &val, const fdd::memory &Dd, int iterations)
@@ -1280,31 +1271,43 @@ class Subdomain
         static const bool timing = getenv("FDD_SETUP_TIMING") != nullptr;
         const auto clock = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         const double t1 = clock();
-        fdd_csr_plan *plan = nullptr;
-        FDD_CALL(fdd_csr_plan_create(&plan, ptr_hst.data(), n, n, (int)nnz));
+        const fdd::csr_plan plan = fdd::make_csr_plan(ptr_hst.data(), n, n, (int)nnz);
         const double t2 = clock();
-        fdd::memory v = dv.malloc<double>(n), vn = dv.malloc<double>(n), t = dv.malloc<double>(n), w = dv.malloc<double>(n);
+        const double lambda = device_power_iteration(n, 0, Dd, iterations, [&](fdd::memory &w, fdd::memory &t) {
+            FDD_CALL(fdd_csr_plan_matvec(plan.get(), w.as<double>(), ptr.as<int>(), col.as<int>(), val.as<double>(), t.as<double>(), 1.0, 0.0, stream));
+        });
+        if (timing and n > 100000) printf("low_order:   lambda_max on the device: plan %.3f s, vectors and %d iterations %.3f s\n", t2 - t1, iterations, clock() - t2);
+        return lambda;
+    }
+    // The Rayleigh quotient of S A S after `iterations` steps of low_order::max_eigenvalue_scaled's power iteration (same start
+    // vector) on the device: six launches a step around apply(w, t), w = A t.  S: the diagonal scaling, n entries.  padded > 0:
+    // t and w have that many entries (>= n) and t is cleared first, for an operator that reads behind the n.  One scalar
+    // comes back at the end.
+    template <typename Apply>
+    static double device_power_iteration(int n, int padded, const fdd::memory &S, int iterations, Apply &&apply)
+    {
+        fdd::device_t &dv = fdd::dev();
+        void *stream = dv.stream;
+        const int nt = padded > 0 ? padded : n;
+        fdd::memory v = dv.malloc<double>(n), vn = dv.malloc<double>(n), t = dv.malloc<double>(nt), w = dv.malloc<double>(nt);
         fdd::memory ws = dv.malloc<double>(fdd_reduce_workspace_doubles()), sc = dv.malloc<double>(2);
         {
             const std::vector<double> start = fdd::low_order::power_iteration_start(n);
             v.copyFrom(start.data(), (size_t)n * sizeof(double));
         }
+        if (padded > 0) FDD_CALL(fdd_set_to_value(t.as<double>(), 0.0, nt, 0, stream));
         double *scp = sc.as<double>();
-        const double t3 = clock();
         for (int it = 0; it < iterations; it++)
         {
             FDD_CALL(fdd_sub_inner_product(scp, ws.as<double>(), v.as<double>(), v.as<double>(), n, stream));
-            FDD_CALL(fdd_vector_scaling_rsqrt_dev(vn.as<double>(), scp, v.as<double>(), n, stream));                 // vn = v / |v|
-            FDD_CALL(fdd_vector_diagonal_scaling_dev(t.as<double>(), Dd.as<double>(), nullptr, vn.as<double>(), n, stream)); // t = D vn
-            FDD_CALL(fdd_csr_plan_matvec(plan, w.as<double>(), ptr.as<int>(), col.as<int>(), val.as<double>(), t.as<double>(), 1.0, 0.0, stream));
-            FDD_CALL(fdd_vector_diagonal_scaling_dev(v.as<double>(), Dd.as<double>(), nullptr, w.as<double>(), n, stream)); // v = D A D vn
+            FDD_CALL(fdd_vector_scaling_rsqrt_dev(vn.as<double>(), scp, v.as<double>(), n, stream));                        // vn = v / |v|
+            FDD_CALL(fdd_vector_diagonal_scaling_dev(t.as<double>(), S.as<double>(), nullptr, vn.as<double>(), n, stream)); // t = S vn
+            apply(w, t);
+            FDD_CALL(fdd_vector_diagonal_scaling_dev(v.as<double>(), S.as<double>(), nullptr, w.as<double>(), n, stream)); // v = S A S vn
             FDD_CALL(fdd_sub_inner_product(scp + 1, ws.as<double>(), v.as<double>(), vn.as<double>(), n, stream));
         }
         double lambda = 1.0;
         sc.slice(1, 1).copyTo(&lambda, sizeof(double));
-        if (timing and n > 100000) printf("low_order:   lambda_max on the device: plan %.3f s, vectors %.3f s, %d iterations %.3f s\n", t2 - t1, t3 - t2, iterations, clock() - t3);
-        FDD_CALL(fdd_csr_plan_destroy(plan));
-        for (fdd::memory *m : {&v, &vn, &t, &w, &ws, &sc}) m->free();
         return lambda;
     }
 
@@ -1365,7 +1368,6 @@ class Subdomain
             // use, or again) keeps what fddh_problem_set_flag stored
             const bool graph = amg_hierarchy.use_graph, fused = amg_hierarchy.fused_smoother, matrix_free = amg_hierarchy.matrix_free_transfer;
             const int bits = amg_hierarchy.precision;
-            amg_hierarchy.release_graphs();
             amg_hierarchy = amg::Hierarchy();
             amg_hierarchy.use_graph = graph;
             amg_hierarchy.fused_smoother = fused;
@@ -1422,7 +1424,6 @@ class Subdomain
                 S::DeviceLattice next;
                 fdd::low_order::Transfer transfer;
                 S::DeviceCSR Pd = S::geometric_level(DL, n, next, transfer);
-                DL.point_dof.free();
                 DL = std::move(next);
                 if (verbose) printf("low_order: level %d coarsened on the lattice: %d -> %d rows, %d nodes per direction and element left\n", l, n, Pd.cols, DL.n);
                 lap("interpolator", l);
@@ -1442,9 +1443,7 @@ class Subdomain
                 Ad = Ac;
             }
             A = S::download(Ad);
-            Ad.free();
             if (use_lattice) lattice = DL.host(true); // small by now (C2 / C3: the degree-1 lattice)
-            DL.point_dof.free();
             lap("hand-off download", l);
             S::note_memory();
             if (timing)
@@ -1549,8 +1548,6 @@ class Subdomain
     {
         initialize(domains, poly_degree_, poly_reduction_, subdomain_overlap_, superdomain_overlap_);
     }
-
-    ~Subdomain() {}
 
     int levels_count() const { return num_levels; }
     const std::vector<int> &level_degrees() const { return poly_degree; }
@@ -1842,7 +1839,6 @@ class Subdomain
         setup_timing.lap("region geometry to the device");
         // level-sorted element lists (subdomain.tpp:1603-1630 sorted by level): the region is ordered by level, so
         // every degree is one contiguous run of elements
-        for (auto &ll : subdomain_operator.level_lists) ll.factor_elem.free();
         subdomain_operator.level_lists.clear();
         for (int l = 0; l < num_levels; l++)
         {
@@ -1995,8 +1991,6 @@ class Subdomain
 
     void allocate_krylov()
     {
-        for (auto &m : V) m.free();
-        for (auto &m : Z) m.free();
         V.resize(num_vectors + 1);
         for (int i = 0; i < num_vectors + 1; i++) V[i] = fdd::dev().malloc<DType>(num_values);
         Z.resize(num_vectors);
@@ -2521,8 +2515,8 @@ class Subdomain
         return nullptr;
     }
 
-    // lambda: the Rayleigh quotient after cheby.power_iterations steps of the power iteration on S A S, S = 1/sqrt(diag) -- the
-    // launch sequence of device_lambda_max with operator_dofs in place of the SpMV.  The region is the rank's own operator: no
+    // lambda: the Rayleigh quotient after cheby.power_iterations steps of the power iteration on S A S, S = 1/sqrt(diag)
+    // (device_power_iteration, with operator_dofs as the operator).  The region is the rank's own operator: no
     // communication.  Kept until the operator changes (operator_changed) or the iteration count does.
     double chebyshev_lambda()
     {
@@ -2530,31 +2524,11 @@ class Subdomain
         ensure_jacobi();
         const int nd = dof_space_size(), na = std::max(dof_alloc_size(), 1);
         if (nd <= 0 or cheby.power_iterations <= 0) return cheby.lambda = 1.0;
-        fdd::device_t &dv = fdd::dev();
-        void *stream = dv.stream;
         std::vector<double> s_hst(nd);
         for (int i = 0; i < nd; i++) s_hst[i] = 1.0 / std::sqrt(jacobi_diag_hst[i]);
-        fdd::memory S = dv.malloc<double>(nd), v = dv.malloc<double>(nd), vn = dv.malloc<double>(nd), t = dv.malloc<double>(na), w = dv.malloc<double>(na);
-        fdd::memory ws = dv.malloc<double>(fdd_reduce_workspace_doubles()), sc = dv.malloc<double>(2);
+        fdd::memory S = fdd::dev().malloc<double>(nd);
         S.copyFrom(s_hst.data(), (size_t)nd * sizeof(double));
-        {
-            const std::vector<double> start = fdd::low_order::power_iteration_start(nd);
-            v.copyFrom(start.data(), (size_t)nd * sizeof(double));
-        }
-        FDD_CALL(fdd_set_to_value(t.as<double>(), 0.0, na, 0, stream));
-        double *scp = sc.as<double>();
-        for (int it = 0; it < cheby.power_iterations; it++)
-        {
-            FDD_CALL(fdd_sub_inner_product(scp, ws.as<double>(), v.as<double>(), v.as<double>(), nd, stream));
-            FDD_CALL(fdd_vector_scaling_rsqrt_dev(vn.as<double>(), scp, v.as<double>(), nd, stream));                          // vn = v / |v|
-            FDD_CALL(fdd_vector_diagonal_scaling_dev(t.as<double>(), S.as<double>(), nullptr, vn.as<double>(), nd, stream)); // t = S vn
-            operator_dofs(w.as<double>(), t.as<double>());
-            FDD_CALL(fdd_vector_diagonal_scaling_dev(v.as<double>(), S.as<double>(), nullptr, w.as<double>(), nd, stream)); // v = S A S vn
-            FDD_CALL(fdd_sub_inner_product(scp + 1, ws.as<double>(), v.as<double>(), vn.as<double>(), nd, stream));
-        }
-        double lambda = 1.0;
-        sc.slice(1, 1).copyTo(&lambda, sizeof(double));
-        for (fdd::memory *m : {&S, &v, &vn, &t, &w, &ws, &sc}) m->free();
+        const double lambda = device_power_iteration(nd, na, S, cheby.power_iterations, [this](fdd::memory &w, fdd::memory &t) { operator_dofs(w.as<double>(), t.as<double>()); });
         if (not(lambda > 0.0) or not std::isfinite(lambda)) throw std::runtime_error("Chebyshev-Jacobi inner solve: the power iteration gave no positive eigenvalue estimate");
         return cheby.lambda = lambda;
     }
@@ -2580,7 +2554,7 @@ class Subdomain
         if constexpr (f32) prepare_single_precision();
         if (C.na != na)
         {
-            for (fdd::memory *v : {&C.d, &C.r, &C.q, &C.t, &C.x, &C.f, &C.w}) v->free();
+            C.w = fdd::memory(); // made again below, at the new size
             for (fdd::memory *v : {&C.d, &C.r, &C.q, &C.t}) *v = fdd::dev().malloc<Real>(na); // d is an operator input: in a composite the copies and hanging values sit behind its dofs
             if (f32) C.x = fdd::dev().malloc<Real>(na), C.f = fdd::dev().malloc<Real>(na);
             ops::set_to_zero(C.d.template as<Real>(), na, stream);
@@ -2664,8 +2638,6 @@ class Subdomain
             gmres_dofs(ua, fa, false, false);
         finish_history();
         ua.copyTo(ua_hst, (size_t)nd * sizeof(DType));
-        fa.free();
-        ua.free();
     }
 
     // the solve itself, dof vectors in and out (callers that already hold assembled data skip Qt / Q)
@@ -2879,8 +2851,6 @@ class Subdomain
         xa.copyFrom(x, (size_t)nd * sizeof(DType));
         operator_dofs(ya.as<double>(), xa.as<double>());
         ya.copyTo(y, (size_t)nd * sizeof(DType));
-        xa.free();
-        ya.free();
     }
     void host_rhs_dofs(double *y, fdd::memory &r_pts)
     {
@@ -2892,7 +2862,6 @@ class Subdomain
         else
             gather_weighted(ya, f);
         ya.copyTo(y, (size_t)nd * sizeof(DType));
-        ya.free();
     }
 
     // test hook: tree_operator is private in the reference too

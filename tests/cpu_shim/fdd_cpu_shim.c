@@ -11,6 +11,7 @@
  * without it.  In effect this is the reference's OCCA "Serial" mode.
  */
 #include <math.h>
+#include <pthread.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -36,8 +37,67 @@ int fdd_device_count(int *count) { *count = 1; return 0; }
 int fdd_set_device(int device) { (void)device; return 0; }
 int fdd_get_device(int *device) { *device = 0; return 0; }
 int fdd_device_name(char *buf, size_t n) { snprintf(buf, n, "cpu-shim"); return 0; }
-int fdd_malloc(void **ptr, size_t bytes) { *ptr = bytes ? calloc(1, bytes) : NULL; return (bytes && !*ptr) ? 2 : 0; }
-int fdd_free(void *ptr) { free(ptr); return 0; }
+
+/* fdd_live_objects: pointer -> size of every live block, under a mutex (ranks are threads) */
+static pthread_mutex_t g_live_lock = PTHREAD_MUTEX_INITIALIZER;
+static struct live_block { void *ptr; size_t bytes; } *g_live = NULL;
+static long long g_live_count = 0, g_live_capacity = 0, g_live_bytes = 0, g_live_peak = 0, g_mallocs = 0, g_live_plans = 0;
+int fdd_malloc(void **ptr, size_t bytes)
+{
+    *ptr = bytes ? calloc(1, bytes) : NULL;
+    if (!bytes) return 0;
+    if (!*ptr) return 2;
+    pthread_mutex_lock(&g_live_lock);
+    if (g_live_count == g_live_capacity)
+    {
+        g_live_capacity = g_live_capacity ? 2 * g_live_capacity : 256;
+        g_live = (struct live_block *)realloc(g_live, (size_t)g_live_capacity * sizeof(*g_live));
+    }
+    g_live[g_live_count].ptr = *ptr;
+    g_live[g_live_count++].bytes = bytes;
+    g_live_bytes += (long long)bytes;
+    if (g_live_bytes > g_live_peak) g_live_peak = g_live_bytes;
+    g_mallocs++;
+    pthread_mutex_unlock(&g_live_lock);
+    return 0;
+}
+int fdd_free(void *ptr)
+{
+    if (!ptr) return 0;
+    pthread_mutex_lock(&g_live_lock);
+    for (long long i = g_live_count - 1; i >= 0; i--)
+        if (g_live[i].ptr == ptr)
+        {
+            g_live_bytes -= (long long)g_live[i].bytes;
+            g_live[i] = g_live[--g_live_count];
+            break;
+        }
+    if (g_live_count == 0)
+    {
+        free(g_live); /* nothing of the table outlives the last block */
+        g_live = NULL;
+        g_live_capacity = 0;
+    }
+    pthread_mutex_unlock(&g_live_lock);
+    free(ptr);
+    return 0;
+}
+int fdd_live_objects(long long *out, int n)
+{
+    REQ(out != NULL && n >= 0);
+    pthread_mutex_lock(&g_live_lock);
+    const long long all[6] = {g_live_count, g_live_bytes, g_live_peak, g_live_plans, 0, g_mallocs};
+    for (int i = 0; i < n && i < 6; i++) out[i] = all[i];
+    pthread_mutex_unlock(&g_live_lock);
+    return 0;
+}
+int fdd_live_objects_reset_peak(void)
+{
+    pthread_mutex_lock(&g_live_lock);
+    g_live_peak = g_live_bytes;
+    pthread_mutex_unlock(&g_live_lock);
+    return 0;
+}
 int fdd_memcpy_h2d(void *d, const void *s, size_t b, void *st) { (void)st; if (b) memmove(d, s, b); return 0; }
 int fdd_memcpy_d2h(void *d, const void *s, size_t b, void *st) { (void)st; if (b) memmove(d, s, b); return 0; }
 int fdd_fetch_scalars(void *d, const void *s, size_t b, void *st) { (void)st; if (b) memmove(d, s, b); return 0; }
@@ -74,9 +134,15 @@ int fdd_csr_plan_create(fdd_csr_plan **plan, const int *ptr, int rows, int cols,
     (void)ptr;
     *plan = (fdd_csr_plan *)calloc(1, sizeof(fdd_csr_plan));
     (*plan)->num_rows = rows; (*plan)->num_cols = cols; (*plan)->num_nnz = nnz;
+    __atomic_add_fetch(&g_live_plans, 1, __ATOMIC_RELAXED);
     return 0;
 }
-int fdd_csr_plan_destroy(fdd_csr_plan *plan) { free(plan); return 0; }
+int fdd_csr_plan_destroy(fdd_csr_plan *plan)
+{
+    if (plan) __atomic_sub_fetch(&g_live_plans, 1, __ATOMIC_RELAXED);
+    free(plan);
+    return 0;
+}
 int fdd_csr_plan_num_blocks(const fdd_csr_plan *plan, int *nb) { (void)plan; *nb = 0; return 0; }
 int fdd_csr_plan_kind(const fdd_csr_plan *plan, int *kind) { (void)plan; *kind = 0; return 0; }
 int fdd_csr_plan_pipelined(const fdd_csr_plan *plan, int *pipelined) { (void)plan; *pipelined = 0; return 0; }
