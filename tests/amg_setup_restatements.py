@@ -266,6 +266,17 @@ def assemble_fem_ref(x, y, z, point_dof, num_dofs, N, epsilon=1.0e-12):
     return K, mask, (ptr, col, val), dets
 
 
+def add_diagonal_ref(ptr, col, val, shift):
+    """Subdomain::amg_build after assemble_fem: the diagonal entry of row d plus shift[d], once, one double sum (the
+    Helmholtz and Robin terms of the level-0 matrix; the coarse operators are Galerkin products of it)"""
+    ptr, col, val = np.asarray(ptr), np.asarray(col), np.array(val, np.float64)
+    rows = np.repeat(np.arange(len(ptr) - 1), np.diff(ptr))
+    on = np.nonzero(rows == col)[0]
+    assert np.array_equal(rows[on], np.arange(len(ptr) - 1)), "a row without a diagonal entry"
+    val[on] = val[on] + np.asarray(shift, np.float64)
+    return val
+
+
 def dof_points_ref(point_dof, num_dofs):
     """dof_ptr / dof_points: the ascending points of every dof, the transpose of point_dof"""
     point_dof = np.asarray(point_dof, np.int64)

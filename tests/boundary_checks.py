@@ -12,6 +12,10 @@ Restatements
                            (scipy sparse; dense below 3 000 nodes), the solve with Dirichlet and flux data, and the maps between
                            point and node vectors.  Nodes are the distinct glo_num, in ascending order
 The manufactured solution is u = sin(4x + 3y + 2z + 0.3): no symmetry of the box, no face on which u or its flux vanishes.
+
+The preconditioner's pieces on natural faces (check_inner_operator, check_level0_matrix, check_against_oracle, further down)
+are held to Reference.K_free(), to the restatements of tests/amg_setup_restatements.py and to the oracle; the GPU runs them
+with every term (tests/test_gpu_boundary_preconditioner.py), the CPU stand-in without lambda and alpha.
 """
 import os
 import sys
@@ -341,7 +345,221 @@ def check_missing_entries():
         p.close()
 
 
+# ---------------------------------------------------------------- the preconditioner's pieces on natural faces
+# Shared by tests/test_gpu_boundary_preconditioner.py (all of a case) and, as child processes on the CPU stand-in, by
+# tests/test_cpu_boundary.py (standin=True: that kernel library has neither fdd_shift_add nor fdd_field_surface, so lambda
+# and alpha are left out on both sides; the face codes and kappa stay).  Every bound is one the project already had.
+ROBIN = dict(kappa="smooth", lam=10.0, alpha={1: 2.0, 3: 0.5})
+OPERATOR_CASES = {
+    "box_N3_DNNNDN_all_terms": dict(kind="box", N=3, faces="DNNNDN", **ROBIN),
+    "kershaw_N5_DNNNDN_all_terms": dict(kind="kershaw", N=5, faces="DNNNDN", **ROBIN),
+    "box_N7_DNNNDN_all_terms": dict(kind="box", N=7, faces="DNNNDN", **ROBIN),
+    "box_N7_NNDDDN": dict(kind="box", N=7, faces="NNDDDN"),  # natural x-faces: the line kernel with assemble_in_stiffness
+    "box_N11_DNDNDN": dict(kind="box", N=11, faces="DNDNDN"),
+    "box_N4_NNNNNN_robin": dict(kind="box", N=4, faces="NNNNNN", alpha={1: 2.0}),  # no masked point at all
+}
+HIERARCHY_CASES = {
+    "box_N3_DNNDND": dict(kind="box", N=3, faces="DNNDND", device=True),
+    "box_N4_DNNNNN_robin": dict(kind="box", N=4, faces="DNNNNN", alpha={1: 2.0}),
+    "kershaw_N4_NNNNNN_shift": dict(kind="kershaw", N=4, faces="NNNNNN", lam=10.0),
+    "box_N4_DNNDNN_kappa_robin": dict(kind="box", N=4, faces="DNNDNN", kappa="random", alpha={1: 2.0, 4: 0.5}),
+    # degree 7: level 0 is coarsened on the lattice (8 -> 4 nodes per direction and element), whose end planes now carry dofs
+    "box_N7_DNNDND_lattice": dict(kind="box", N=7, faces="DNNDND", device=True, lattice=True),
+}
+ORACLE_CASES = {
+    "product_N7_DNNDND": dict(E=(3, 2, 2), N=7, faces="DNNDND", builder="product"),  # reaches the matrix-free transfer
+    "product_N3_NDNNND": dict(E=(4, 4, 4), N=3, faces="NDNNND", builder="product"),
+    "scipy_N5_DNNNNN": dict(E=(3, 2, 2), N=5, faces="DNNNNN", builder="scipy"),
+    "float_N5_DNNNNN": dict(E=(3, 2, 2), N=5, faces="DNNNNN", builder="float"),
+}
+
+
+def set_coefficients(p, mesh, spec, standin):
+    """kappa, lambda and alpha of the case on the problem; returns (kappa, lam, alpha, restated surface) as Reference takes
+    them.  alpha is only returned: the caller sets it through p.robin where its check wants it (before or after a build)"""
+    import diffusivity_checks as DC
+
+    kappa = {None: None, "smooth": kappa_smooth(mesh.x, mesh.y, mesh.z), "random": DC.kappa_random(p.n, 5)}[spec.get("kappa")]
+    lam = 0.0 if standin else spec.get("lam", 0.0)
+    sides = None if standin else spec.get("alpha")
+    if kappa is not None:
+        p.diffusivity(kappa)
+    if lam:
+        p.helmholtz(lam)
+    rs = restated_surface(mesh) if sides else None
+    alpha = side_alpha(rs, mesh.p_mask, sides) if sides else None
+    return kappa, lam, alpha, rs
+
+
+def reference_order_of_dofs(p, ref):
+    """perm[d] = the row of ref.K_free() that dof d of the Subdomain is.  One rank: the region is the rank's own points, so
+    point q of the Subdomain is point q of the mesh; a point has a dof exactly where its node is free, and all points of a
+    node share the dof"""
+    dof, nd = p.sub_point_dofs(), p.sub_info()["unique_dofs"]
+    assert len(dof) == len(ref.node) and nd == int(ref.free.sum()) == dof.max() + 1
+    has = dof >= 0
+    assert np.array_equal(has, ref.free[ref.node])
+    row = np.cumsum(ref.free) - 1
+    perm = np.full(nd, -1, np.int64)
+    perm[dof[has]] = row[ref.node[has]]
+    assert np.array_equal(perm[dof[has]], row[ref.node[has]]) and np.array_equal(np.sort(perm), np.arange(nd))
+    return perm
+
+
+def shift_on_dofs(p):
+    """cbar in the Subdomain's dof order (helmholtz::dofs_of_nodes): the node vector through Q's column of a dof's points"""
+    dof = p.sub_point_dofs()
+    _, _, qcol, _ = p.csr(0)
+    c = np.zeros(p.sub_info()["unique_dofs"])
+    c[dof[dof >= 0]] = p.helmholtz_shift()[qcol[dof >= 0]]
+    return c
+
+
+def check_inner_operator(case, standin=False):
+    """Qt A_L Q + diag(c) over the dofs is Reference.K_free() in the numbering of sub_point_dofs: sub_dof_operator within
+    1e-12 max|want| and sub_jacobi_diagonal within 1e-12 relative (the bounds of test_node_operator_is_the_matrix and
+    diffusivity_checks.check_operator), under preconditioner_precision 64 and 32 -- neither entry takes the flag (both run
+    the double operator, tests/test_gpu_helmholtz.py), so both settings are held to the double bound and to each other"""
+    S, _, _ = api()
+    spec = OPERATOR_CASES[case]
+    p = new_problem((2, 2, 2), spec["N"], spec["faces"], spec["kind"])
+    try:
+        mesh = S.ArrayMesh.from_problem(p)
+        assert np.array_equal(mesh.p_mask, face_mask(mesh, spec["faces"]))
+        kappa, lam, alpha, rs = set_coefficients(p, mesh, spec, standin)
+        if alpha is not None:
+            p.robin(spec["alpha"])
+        ref = Reference(mesh, kappa, lam, alpha, rs)
+        perm = reference_order_of_dofs(p, ref)
+        K = ref.K_free()[perm][:, perm].tocsr()
+        natural = int((ref.free & (np.bincount(ref.node, weights=on_surface(mesh), minlength=ref.nn) > 0)).sum())
+        assert natural > 0  # dofs on the surface: what a Dirichlet box does not have
+        x = S.seeded_uniform(len(perm), 17) - 0.5
+        want, dwant = K @ x, K.diagonal()
+        out = {}
+        for bits in (64, 32):
+            p.set_flag("preconditioner_precision", bits)
+            y, d = p.sub_dof_operator(x), p.sub_jacobi_diagonal()
+            e_op, e_diag = float(np.abs(y - want).max() / np.abs(want).max()), float((np.abs(d - dwant) / dwant).max())
+            print("inner operator %s, precision %d: operator %.3e, diagonal %.3e (%d dofs, %d on natural faces)%s" % (case, bits, e_op, e_diag, len(perm), natural, " [lambda, alpha left out]" if standin and (spec.get("lam") or spec.get("alpha")) else ""))
+            assert e_op <= 1e-12 and e_diag <= 1e-12, (case, bits, e_op, e_diag)
+            out[bits] = (y, d)
+        assert np.array_equal(out[32][0], out[64][0]) and np.array_equal(out[32][1], out[64][1])
+        p.set_flag("preconditioner_precision", 64)
+    finally:
+        p.close()
+
+
+def on_surface(mesh):
+    """1.0 at the points on the surface of the unit cube"""
+    on = np.zeros(len(mesh.x), bool)
+    for c in (mesh.x, mesh.y, mesh.z):
+        on |= (c == 0.0) | (c == 1.0)
+    return on.astype(np.float64)
+
+
+def check_level0_matrix(case, standin=False):
+    """level-0 A of the host-built hierarchy is the restatement of low_order::assemble_fem on the problem's point -> dof
+    array plus cbar on the diagonal (amg_setup_restatements.add_diagonal_ref), pattern and bits, as
+    diffusivity_checks.check_hierarchy_matrix; it has unique_dofs rows, more than the all-Dirichlet twin by the free nodes on
+    the surface; robin(None) gives back the bits of the hierarchy that never saw alpha; where nothing makes the device build
+    step aside (no shift, no kappa) the device build gives the same levels; at degree 7 level-0 P is the restatement of
+    low_order::geometric_level on that array, as bits, with the coarse dofs counted by hand"""
+    import amg_setup_restatements as R
+    import diffusivity_checks as DC
+
+    S, _, _ = api()
+    spec = HIERARCHY_CASES[case]
+    E, N = (2, 2, 2), spec["N"]
+    p = new_problem(E, N, spec["faces"], spec["kind"])
+    try:
+        mesh = S.ArrayMesh.from_problem(p)
+        kappa, lam, alpha, _ = set_coefficients(p, mesh, spec, standin)
+        if standin and spec["faces"] == "NNNNNN" and not lam:
+            raise AssertionError("%s has no twin on the stand-in: without its shift the matrix is singular" % case)
+        p.amg_build(device=False)
+        never = p.amg_levels()
+        if alpha is not None:
+            p.robin(spec["alpha"])  # a hierarchy that amg_build made is built again
+        assert p.amg_setup_info()["levels_built_on_device"] == 0
+        levels = p.amg_levels()
+        A = levels[0]["A"]
+        pd, nd = p.sub_point_dofs(), p.sub_info()["unique_dofs"]
+        assert nd == p.info["sub_num_dofs"] == A.shape[0] == A.shape[1]
+        if kappa is None:
+            ptr, col, val = R.assemble_fem_ref(mesh.x, mesh.y, mesh.z, pd, nd, N)[2]
+        else:
+            ptr, col, val = DC.assemble_fem_kappa(mesh.x, mesh.y, mesh.z, pd, nd, N, kappa)
+        c = shift_on_dofs(p)
+        assert c.any() == bool(lam or alpha is not None)
+        if c.any():
+            val = R.add_diagonal_ref(ptr, col, val, c)
+        assert np.array_equal(ptr, A.indptr) and np.array_equal(col, A.indices), "pattern of A"
+        assert np.array_equal(DC.bits(val), DC.bits(A.data)), "values of A: %d of %d differ" % ((DC.bits(val) != DC.bits(A.data)).sum(), len(val))
+        twin = new_problem(E, N, "DDDDDD", spec["kind"])
+        try:
+            nd_twin = twin.sub_info()["unique_dofs"]
+        finally:
+            twin.close()
+        node = np.unique(mesh.glo_num, return_inverse=True)[1]
+        free = np.bincount(node, weights=mesh.p_mask) > 0
+        natural = int((free & (np.bincount(node, weights=on_surface(mesh)) > 0)).sum())
+        print("level-0 matrix %s: %d rows (%d in the all-Dirichlet twin, %d free nodes on the surface), %d entries, as bits%s" % (case, nd, nd_twin, natural, len(val), " [lambda, alpha left out]" if standin and (spec.get("lam") or spec.get("alpha")) else ""))
+        assert natural > 0 and nd == nd_twin + natural
+        if spec.get("lattice"):
+            # low_order::geometric_level on the same point -> dof array (test_cpu_amg_setup_restatements.py holds it to the
+            # all-Dirichlet boxes): P as bits; the coarse lattice has 3 E + 1 = 7 nodes per direction, each direction loses the
+            # one on its single 'D' face: 6^3 coarse dofs, where the all-Dirichlet twin has 5^3; applied matrix-free
+            n = N + 1
+            keep = R.coarse_nodes_ref(n, S.gll(N)[0])
+            g = R.geometric_level_ref(pd, nd, n, keep, *R.interp_tables_ref(S.gll(N)[0], keep))
+            P = levels[0]["P"]
+            assert spec["faces"] == "DNNDND" and not g["refused"] and g["unplaced"] == 0 and P.shape == (nd, g["num_coarse"]) == (nd, 6**3)
+            assert np.array_equal(g["P"][0], P.indptr) and np.array_equal(g["P"][1], P.indices), "pattern of P"
+            assert np.array_equal(DC.bits(g["P"][2]), DC.bits(P.data)), "values of P"
+            assert p.amg_level_transfer(0)
+            print("level-0 matrix %s: P %d x %d on the lattice, as bits" % (case, nd, P.shape[1]))
+        if alpha is not None:
+            assert not np.array_equal(DC.bits(A.data), DC.bits(never[0]["A"].data))
+            p.robin(None)
+            DC.same_levels(p.amg_levels(), never)
+        if spec.get("device") and not standin:
+            p.amg_build(device=True)
+            built = p.amg_setup_info()["levels_built_on_device"]
+            print("level-0 matrix %s: %d level(s) built on the device" % (case, built))
+            assert built >= 1
+            DC.same_levels(p.amg_levels(), levels)
+    finally:
+        p.close()
+
+
+def check_against_oracle(case):
+    """amg_checks.check_amg / check_amg_f32 as they stand on a problem with natural faces (the oracle reads p_mask from the
+    mesh it is given): V-cycle 1e-11, inner histories 1e-9, outer history 1e-8, the oracle's iteration count, the matrix-free
+    transfer against the CSR one 1e-13 / 2e-5.  Prints the count (no cap: equality with the oracle's is the condition)"""
+    import amg_checks
+
+    spec = ORACLE_CASES[case]
+    p = new_problem(spec["E"], spec["N"], spec["faces"])
+    try:
+        p.set_flag("sub_use_preconditioner", 0)  # switched on by the checks once the hierarchy under test is attached
+        if spec["builder"] == "float":
+            its = amg_checks.check_amg_f32(p, spec["N"], 2)
+            print("oracle %s: %d outer iterations with the float cycle (within one of the double cycle's)" % (case, its))
+        else:
+            its = amg_checks.check_amg(p, spec["N"], 2, builder=spec["builder"])
+            assert its is not None
+            print("oracle %s: %d outer iterations, product and oracle" % (case, its))
+            if spec["builder"] == "product":
+                assert p.amg_level_transfer(0) == (spec["N"] == 7)
+    finally:
+        p.close()
+
+
 CHECKS = {"solves_N3": lambda: check_solves(3), "solves_N5": lambda: check_solves(5), "singular": check_singular, "missing_entries": check_missing_entries}
+CHECKS.update({"operator_" + c: (lambda c=c: check_inner_operator(c, standin=True)) for c in OPERATOR_CASES})
+CHECKS.update({"level0_" + c: (lambda c=c: check_level0_matrix(c, standin=True)) for c in HIERARCHY_CASES})
+CHECKS.update({"oracle_" + c: (lambda c=c: check_against_oracle(c)) for c in ORACLE_CASES})
 
 
 def write_files(L, directory, E, P, N, rank, faces, eps):

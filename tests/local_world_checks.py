@@ -10,7 +10,7 @@ states the number of levels it expects, and every rank's Subdomain is held to on
 
 Used by tests/test_gpu_comm.py on the GPU (product libraries) and, with the CPU stand-in of the kernel C-ABI, by
 tests/test_cpu_multirank.py as `python tests/local_world_checks.py --cpu-shim <world> <Ex,Ey,Ez> <N> <red>`, followed
-by any of `overlaps=a,b kershaw=1 outer_cap=K levels=L composite_levels=L amg_method=gmres no_superdomain=r,...`.
+by any of `overlaps=a,b kershaw=1 outer_cap=K levels=L composite_levels=L amg_method=gmres no_superdomain=r,... faces=DNNDND`.
 """
 import os
 import sys
@@ -38,6 +38,10 @@ CASES = {
     # elements than its 16^3, whose superdomain is coarsened in three composite levels (1694, 200, 18 kept dofs on rank 0).
     # 8^3 has one composite level (343 kept dofs: nothing is aggregated), so the case runs (16, 8, 8), which has two (588, 22):
     # 1.6e-14, 2.0e-14.  (32, 4, 4) has as many elements as 8^3 and the three composite levels (180, 18, 9): 6.4e-14, 2.7e-13
+    # natural faces, no coefficient (a Robin term and a shift are one-rank features): the ends of the strip, where the outer
+    # ranks' own elements and the middle rank's degree-1 far field carry boundary dofs, and three sides of the reduction-1 box
+    "strip_of_three_natural_ends": dict(world=3, E=(9, 2, 2), N=5, red=2, levels=3, no_superdomain=(1,), faces="NNDDDD"),
+    "reduction_one_natural": dict(world=2, E=(16, 4, 4), N=3, red=1, overlaps=(1, 2), levels=3, faces="DNNDND"),
     "reference_developer_run": dict(world=8, E=(16, 8, 8), N=2, red=1, kershaw=True, levels=2, composite_levels=2, outer_cap=CAP, amg_method="gmres"),
     "developer_run_three_composite_levels": dict(world=8, E=(32, 4, 4), N=2, red=1, kershaw=True, levels=2, composite_levels=3, outer_cap=CAP, amg_method="gmres"),
 }
@@ -51,8 +55,9 @@ def command_line(case):
     return args + ["%s=%s" % (name, text(value)) for name, value in case.items()]
 
 
-def run(world, E, N, red, amg=True, overlaps=(1, 1), kershaw=False, outer_cap=None, levels=None, composite_levels=None, amg_method="fcg", no_superdomain=None, product=True):
-    """levels: the number of polynomial levels the region of every rank must hold (None: more than one);
+def run(world, E, N, red, amg=True, overlaps=(1, 1), kershaw=False, outer_cap=None, levels=None, composite_levels=None, amg_method="fcg", no_superdomain=None, product=True, faces="DDDDDD"):
+    """faces: the codes of x-, x+, y-, y+, z-, z+ ('D' masked, 'N' natural) the product's generator is given; the oracle's
+    meshes get boundary_checks.face_mask of them as p_mask at every level; levels: the number of polynomial levels the region of every rank must hold (None: more than one);
     composite_levels: the length of every rank's list of composite levels; no_superdomain: exactly these ranks have no
     superdomain dof; outer_cap: every outer solve of both sides runs that many steps with tolerance 0;
     product: the kernel library is the product's (every optional stiffness entry present), not the CPU stand-in (none)."""
@@ -70,11 +75,16 @@ def run(world, E, N, red, amg=True, overlaps=(1, 1), kershaw=False, outer_cap=No
 
         kdir = tempfile.mkdtemp(prefix="fdd_kershaw_")
         level_meshes = [[S.kershaw_mesh_of_the_host_layer(lib.host(), kdir, E, d, 0.3, Pg, r) for d in degrees] for r in range(world)]
-        meshes = [row[0] for row in level_meshes]
-        F = S.OracleFdd(E, N, red, Pg, overlaps[0], overlaps[1], meshes=level_meshes)
     else:
-        meshes = [S.BoxMesh(E, N, Pg, r) for r in range(world)]
-        F = S.OracleFdd(E, N, red, Pg, overlaps[0], overlaps[1])
+        level_meshes = [[S.BoxMesh(E, d, Pg, r) for d in degrees] for r in range(world)]
+    if faces != "DDDDDD":
+        import boundary_checks as B
+
+        for mm in (m for row in level_meshes for m in row):
+            assert np.array_equal(mm.p_mask, B.face_mask(mm, "DDDDDD"))  # the faces of the cube are exact in these coordinates
+            mm.p_mask = B.face_mask(mm, faces)
+    meshes = [row[0] for row in level_meshes]
+    F = S.OracleFdd(E, N, red, Pg, overlaps[0], overlaps[1], meshes=level_meshes)
     W = S.OracleWorld(meshes, N)
     us = [np.sin(3 * mm.x + 1) * np.cos(2 * mm.y) + mm.z * mm.x for mm in meshes]
     # every oracle result up front, on this thread (the oracle's world is one mutable object)
@@ -111,7 +121,8 @@ def run(world, E, N, red, amg=True, overlaps=(1, 1), kershaw=False, outer_cap=No
 
     def body(rank, size):
         lib.host().call("fddh_comm_selftest", 1000)
-        p = H.Problem.kershaw(E, Pg, N, red, 0.3, True, overlaps[0], overlaps[1]) if kershaw else H.Problem.box(E, Pg, N, red, True, overlaps[0], overlaps[1])
+        p = H.Problem.kershaw(E, Pg, N, red, 0.3, True, overlaps[0], overlaps[1], faces=faces) if kershaw else H.Problem.box(E, Pg, N, red, True, overlaps[0], overlaps[1], faces=faces)
+        assert np.array_equal(p.mesh_array("p_mask"), meshes[rank].p_mask)
         p.set_flag("sub_use_preconditioner", 0)
         if capped:
             p.set_options(**capped)
@@ -251,6 +262,7 @@ def run(world, E, N, red, amg=True, overlaps=(1, 1), kershaw=False, outer_cap=No
     F.close()
     assert len(set(out)) == 1, out  # every rank saw the same iteration counts
     print("largest differences to the oracle over the outer solves: history %.2e r0, solution %.2e max|u|" % (margins["history"], margins["solution"]))
+    print("outer FCG iterations, product and oracle: %d; with the V-cycle inside (%s, product alone): %s" % (out[0][0], amg_method, out[0][1]))
     return out[0]
 
 
@@ -264,7 +276,7 @@ if __name__ == "__main__":
         lib._host = lib._Lib(os.path.join(HERE, "cpu_shim", "_build", "libfdd_host_cpu.so"), os.path.join(lib.INCLUDE_DIR, "fdd_host.h"), "fddh_last_error")
         args, product = args[1:], False
     ints = lambda text: tuple(int(x) for x in text.split(","))
-    read = {"overlaps": ints, "kershaw": lambda t: bool(int(t)), "outer_cap": int, "levels": int, "composite_levels": int, "amg_method": str, "no_superdomain": ints}
+    read = {"overlaps": ints, "kershaw": lambda t: bool(int(t)), "outer_cap": int, "levels": int, "composite_levels": int, "amg_method": str, "no_superdomain": ints, "faces": str}
     options = {}
     for arg in args[4:]:
         name, _, text = arg.partition("=")

@@ -1,13 +1,15 @@
 """Reconfiguring a live problem equals building a fresh one: the walk tables and the `fresh` / `walked` drivers shared by
 test_cpu_reconfigure.py (the CPU build of the host layer, tests/cpu_shim, in a child process) and test_gpu_reconfigure.py.
 
-A configuration is a complete set of options (fddh_problem_set_options), flags (fddh_problem_set_flag) and six keys of
+A configuration is a complete set of options (fddh_problem_set_options), flags (fddh_problem_set_flag) and seven keys of
 this module: "amg" (how the low-order hierarchy comes to be: None = the problem never has one, "first_use" = the
 inner solve builds it, "host" / "device" = fddh_problem_amg_build with "amg_device_setup" 0 / 1, "attached" = handed in
 level by level), "inner" (the method precond_apply is called with), "pcg_steps" (K > 0: pcg_begin / pcg_steps(K) /
 pcg_solution join the workload) and the operator's terms: "D_hat" (None = the GLL table `build` sets, "perturbed" = a table
 of the fine level that fails lean_table_ok), "helmholtz" (None, a constant, or "field": seeded, >= 0, with exact zeros) and
-"diffusivity" (None, "smooth", or "jump": 1 : 1000 across an element face, diffusivity_checks.kappa_jump).  `apply` sets
+"diffusivity" (None, "smooth", or "jump": 1 : 1000 across an element face, diffusivity_checks.kappa_jump), and, on a mesh
+with natural faces (a fifth entry of the mesh tuple: the face codes), "robin" (None or {side: alpha}, set after the shift
+and before kappa at every step; on the other meshes the entry is never called).  `apply` sets
 every key, always in the same order, so that fresh(c) and the last step of walked(..., c) differ in one thing only: what
 the problem did before.  Two exceptions, the table and the flag "affine_geometry": every call of either empties all that
 hangs on the operator (basis, diagonal, Chebyshev bound), made again only at the next use, so a call at every step would
@@ -83,10 +85,11 @@ BASE = {
     "pcg_steps": 0,
     "D_hat": None,
     "helmholtz": None,
+    "robin": None,
     "diffusivity": None,
 }
 OPTION_KEYS = ("max_iterations", "tolerance", "num_vectors", "use_preconditioner", "preconditioner_type", "sub_num_vectors", "sub_max_iterations")
-MODULE_KEYS = ("amg", "inner", "pcg_steps", "D_hat", "helmholtz", "diffusivity")
+MODULE_KEYS = ("amg", "inner", "pcg_steps", "D_hat", "helmholtz", "robin", "diffusivity")
 FLAG_KEYS = tuple(k for k in BASE if k not in OPTION_KEYS and k not in MODULE_KEYS)
 
 # The CPU stand-in of the kernel library has no fdd_amg_setup_* entry: the host layer refuses "amg_device_setup" = 1 there
@@ -101,7 +104,7 @@ SET_ON_CHANGE = ("affine_geometry",)
 CPU_LEFT_OUT = {"amg": ("device",)}
 # Nor has it fdd_shift_add* or the coefficient instance of the line kernel: no walk is left out for that, these keys take the
 # value given here at every step of every walk, and the label of a step they change says so (cpu_label).
-CPU_SUBSTITUTED = {"helmholtz": None, "coefficient_in_kernel": 0}
+CPU_SUBSTITUTED = {"helmholtz": None, "robin": None, "coefficient_in_kernel": 0}  # "robin": nor has it fdd_field_surface
 
 
 def on_cpu(c):
@@ -127,6 +130,7 @@ BOX_N7 = ("box", (3, 3, 3), 7, 6)
 BOX_N11 = ("box", (2, 2, 2), 11, 5)    # degrees 11, 6, 1: the fine level's stiffness runs on the matrix cores when "mfma_stiffness" is on
 KERSHAW = ("kershaw", (4, 4, 4), 3, 2)
 COMPOSITE = ("composite", (4, 4, 4), 3, 2)  # FDDH_FORCE_COMPOSITE on one rank
+BOX_N7_NATURAL = ("box", (2, 2, 2), 7, 6, "DNNNDN")  # face codes: x+, y-, y+ and z+ natural, their end points are dofs
 
 ADVICE = "the sequence of ADVICE.md: point-space GMRES(20), node-space GMRES(10), point-space GMRES(20)"
 
@@ -301,6 +305,24 @@ for _name, _precision in (("operator_terms_chebyshev", 64), ("operator_terms_che
         ("kappa off", {"diffusivity": None}),
         ("affine off, no kappa set", {"affine_geometry": 0, "max_iterations": 4}),
     ])
+# Neumann and Robin faces: the Robin term is the shift's second source (rebuild_shift), on boundary dofs only -- the indexed
+# shift kernel -- and on the diagonal of the level-0 matrix; with the hierarchy built on first use, and under the float
+# Chebyshev-Jacobi inner solve, whose Jacobi inverses and eigenvalue bound carry it
+_ROBIN_STEPS = [
+    ("alpha set", {"robin": {1: 2.0, 3: 0.5}}),
+    ("alpha changed", {"robin": {1: 0.25, 5: 4.0}}),
+    ("lambda stacked on alpha", {"helmholtz": 10.0}),
+    ("kappa stacked on both", {"diffusivity": "smooth"}),
+    ("alpha cleared, lambda and kappa stay", {"robin": None}),
+]
+# after "all cleared" the oracle has every term that is left: the V-cycle of the hierarchy as the rebuilds left it is held to
+# the oracle's on the mesh with its natural faces (check_vcycle_against_oracle, 1e-11)
+WALKS["operator_terms_natural_faces_first_use"] = dict(mesh=BOX_N7_NATURAL, family="operator", oracle_vcycle_step=len(_ROBIN_STEPS), base={"amg": "first_use", "sub_use_preconditioner": 1, "max_iterations": 5}, steps=_ROBIN_STEPS + [
+    ("all cleared, cap 4", {"helmholtz": None, "diffusivity": None, "max_iterations": 4}),
+])
+WALKS["operator_terms_natural_faces_chebyshev_f32"] = dict(mesh=BOX_N7_NATURAL, family="operator", base={"inner_solver": 1, "preconditioner_precision": 32, "max_iterations": 5}, steps=_ROBIN_STEPS + [
+    ("all cleared, cap 4", {"helmholtz": None, "diffusivity": None, "max_iterations": 4}),
+])
 FAMILIES = ("outer", "inner", "vcycle", "kernels", "caps", "precond", "operator")
 
 
@@ -345,12 +367,14 @@ class Driver:
         self.H, self.S, self.lib, self.cpu = H, S, lib, cpu
 
     def build(self, mesh):
-        kind, E, N, red = mesh
+        kind, E, N, red = mesh[:4]
+        faces = mesh[4] if len(mesh) > 4 else "DDDDDD"
         H, S = self.H, self.S
         if kind == "kershaw":
-            p = H.Problem.kershaw(E, (1, 1, 1), N, red, 0.3, True)
+            p = H.Problem.kershaw(E, (1, 1, 1), N, red, 0.3, True, faces=faces)
         else:
-            p = H.Problem.box(E, (1, 1, 1), N, red, True, force_composite=(kind == "composite"))
+            p = H.Problem.box(E, (1, 1, 1), N, red, True, force_composite=(kind == "composite"), faces=faces)
+        p.natural_faces = "N" in faces  # only then is fddh_boundary_robin_set called at all
         for lvl in range(p.info["num_levels"]):
             p.set_D_hat(lvl, S.gll(p.level_degree(lvl))[2])
         p.takes_terms = kind != "composite"  # a composite refuses fddh_helmholtz_set and fddh_diffusivity_set whatever the value (capi_refusals.py)
@@ -405,6 +429,10 @@ class Driver:
             p.helmholtz(0.0 if lam is None else lam)
         else:
             assert c["helmholtz"] is None
+        if p.natural_faces and not self.cpu:  # the stand-in's fddh_boundary_robin_set answers "does not export"
+            p.robin(c["robin"])
+        else:
+            assert c["robin"] is None
         kappa = c["diffusivity"]
         if kappa == "smooth":
             kappa = K.kappa_smooth(*(p.mesh_array(a) for a in "xyz"))
@@ -462,7 +490,7 @@ def check_against_oracle(driver, p, c, mesh):
     its 1e-9 bars): the inner GMRES without the V-cycle, in double, on this very problem after everything it went through."""
     S = driver.S
     assert c["inner"] == "gmres" and c["sub_use_preconditioner"] == 0 and c["preconditioner_precision"] == 64, "a walk marked oracle=True ends on the oracle's configuration"
-    _, _, N, red = mesh
+    _, _, N, red = mesh[:4]
     meshes = [S.ArrayMesh.from_problem(p, lvl) for lvl in range(p.info["num_levels"])]
     sd = S.OracleSubdomain(None, N, red, meshes=meshes)
     try:
@@ -486,7 +514,7 @@ def check_vcycle_against_oracle(driver, p, c, mesh):
 
     S = driver.S
     assert c["amg_precision"] == 64 and c["preconditioner_precision"] == 64 and c["amg"] in ("host", "first_use")
-    _, _, N, red = mesh
+    _, _, N, red = mesh[:4]
     meshes = [S.ArrayMesh.from_problem(p, lvl) for lvl in range(p.info["num_levels"])]
     sd = S.OracleSubdomain(None, N, red, meshes=meshes)
     try:

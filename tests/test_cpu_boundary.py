@@ -8,7 +8,12 @@ Figures (each check prints its own).  The dense solve's error against u = sin(4x
 on x+ (pinned to 2 %).  On the stand-in the three preconditioner settings and both outer methods leave a true residual of at
 most 0.96 tau |f^| (bound 10) and an error of at most 1.00002 x the dense solve's own (bound 1.05); iterations at N = 3 / 5:
 35 / 58 unpreconditioned, 19 / 38 with Jacobi, 5 / 5 with the V-cycle (FCG).  The closed-surface sum of the restatement is printed by its test (bound for asking the
-kernel for it in tests/test_gpu_field_surface.py: 1e-12)."""
+kernel for it in tests/test_gpu_field_surface.py: 1e-12).
+
+The preconditioner's pieces on natural faces (the last three tests; tests/README.md has their table): the inner operator and
+its exact diagonal against the assembled matrix at 1.8e-16 .. 9.9e-16 (bound 1e-12), the level-0 low-order matrix and, at
+degree 7, the lattice interpolator as bits of their restatements, and amg_checks against the oracle on meshes with natural
+faces, 3 or 4 outer iterations on both sides."""
 import filecmp
 import os
 import subprocess
@@ -158,3 +163,25 @@ def test_singular_problem_is_created_and_refused(cpu_host_lib):
 def test_missing_kernel_entries_are_named(cpu_host_lib):
     out = run_check(cpu_host_lib, "missing_entries")
     assert out.count("refused:") == 3
+
+
+# ---- the preconditioner's pieces on natural faces: the twins of tests/test_gpu_boundary_preconditioner.py.  The stand-in has
+# ---- no shift and no surface entry, so lambda and alpha are left out on both sides (the printed line says so); the face
+# ---- codes, kappa and every bound stay
+@pytest.mark.parametrize("case", list(B.OPERATOR_CASES))
+def test_inner_operator_and_its_diagonal_are_the_matrix(cpu_host_lib, case):
+    out = run_check(cpu_host_lib, "operator_" + case)
+    assert out.count("inner operator") == 2
+
+
+# kershaw_N4_NNNNNN_shift has no twin: without its shift, which the stand-in refuses, the matrix is singular
+@pytest.mark.parametrize("case", [c for c in B.HIERARCHY_CASES if "NNNNNN" not in c])
+def test_level0_matrix_is_its_restatement_as_bits(cpu_host_lib, case):
+    out = run_check(cpu_host_lib, "level0_" + case)
+    assert "as bits" in out
+
+
+@pytest.mark.parametrize("case", list(B.ORACLE_CASES))
+def test_vcycle_and_solves_are_the_oracles(cpu_host_lib, case):
+    out = run_check(cpu_host_lib, "oracle_" + case)
+    assert "outer iterations" in out

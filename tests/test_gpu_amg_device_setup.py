@@ -161,15 +161,15 @@ def test_row_pointer_overflow_is_an_error(own_stream):
 # ----------------------------------------------------------------------------------------------------------------------
 # hierarchies: device build against host build
 # ----------------------------------------------------------------------------------------------------------------------
-def make_box(E, N, red=2):
-    p = H.Problem.box(E, (1, 1, 1), N, red, True)
+def make_box(E, N, red=2, faces="DDDDDD"):
+    p = H.Problem.box(E, (1, 1, 1), N, red, True, faces=faces)
     for lvl in range(p.info["num_levels"]):
         p.set_D_hat(lvl, S.gll(p.level_degree(lvl))[2])
     return p
 
 
-def make_kershaw(E, N, eps, red=2):
-    p = H.Problem.kershaw(E, (1, 1, 1), N, red, eps)
+def make_kershaw(E, N, eps, red=2, faces="DDDDDD"):
+    p = H.Problem.kershaw(E, (1, 1, 1), N, red, eps, faces=faces)
     for lvl in range(p.info["num_levels"]):
         p.set_D_hat(lvl, S.gll(p.level_degree(lvl))[2])
     return p
@@ -228,6 +228,43 @@ def test_device_hierarchy_is_the_host_hierarchy(own_stream, E, N, device_min_lev
             assert pd.amg_setup_info()["levels_built_on_device"] == 1  # no lattice level: the device FEM matrix is handed over at level 0
         r = S.seeded_uniform(ph.n, 5) - 0.5
         assert np.array_equal(bits(ph.amg_apply(r)), bits(pd.amg_apply(r)))
+    finally:
+        ph.close()
+        pd.close()
+
+
+@pytest.mark.parametrize(
+    "kind,E,N,faces,device_min_levels",
+    [("box", (4, 3, 5), 7, "DNNDND", 3), ("box", (3, 3, 3), 3, "NDNNNN", 1), ("kershaw", (3, 3, 3), 7, "DNDDND", 1)],
+    ids=["box435_N7_DNNDND", "box3_N3_NDNNNN_handoff_at_0", "kershaw3_N7_DNDDND"],
+)
+def test_device_hierarchy_is_the_host_hierarchy_with_natural_faces(own_stream, kind, E, N, faces, device_min_levels):
+    """Face codes alone do not make the device build step aside (Subdomain::amg_build: only a shift, a kappa or a composite
+    do): the end points of the lattice lines are dofs, the dof lattice has a plane more per natural face and the node order
+    changes.  The same levels as the host build, as bits, the same number of device levels as the all-Dirichlet mesh of
+    that size, the same bits from a V-cycle in double and in float"""
+    make = (lambda f: make_box(E, N, faces=f)) if kind == "box" else (lambda f: make_kershaw(E, N, 0.3, faces=f))
+    ph, pd = build_pair(lambda: make(faces), device_min_levels)
+    try:
+        twin = make("DDDDDD")
+        try:
+            twin.amg_build(device=True)
+            twin_built, twin_rows = twin.amg_setup_info()["levels_built_on_device"], twin.amg_levels()[0]["A"].shape[0]
+        finally:
+            twin.close()
+        built = pd.amg_setup_info()["levels_built_on_device"]
+        print("%s %s N = %d %s: %d levels built on the device (%d on the all-Dirichlet mesh), %d rows (%d)" % (kind, E, N, faces, built, twin_built, pd.amg_levels()[0]["A"].shape[0], twin_rows))
+        assert built == twin_built and pd.amg_levels()[0]["A"].shape[0] > twin_rows
+        if N == 3:
+            assert built == 1  # no lattice level: the device FEM matrix is handed over at level 0
+        assert_same_hierarchy(ph, pd)
+        r = S.seeded_uniform(ph.n, 5) - 0.5
+        zh, zd = ph.amg_apply(r), pd.amg_apply(r)
+        assert np.array_equal(bits(zh), bits(zd)) and np.abs(zh).max() > 0.0
+        for p in (ph, pd):
+            p.set_flag("amg_precision", 32)
+        zh32, zd32 = ph.amg_apply(r), pd.amg_apply(r)
+        assert np.array_equal(bits(zh32), bits(zd32)) and np.abs(zh32).max() > 0.0 and not np.array_equal(zh32, zh)
     finally:
         ph.close()
         pd.close()
