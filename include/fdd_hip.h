@@ -510,6 +510,26 @@ int fdd_stiffness_factor_block_verify(int *mismatches, const double *const G[FDD
 int fdd_field_mass(double *mass, const double *const xyz[3], const double *D_hat, const double *gll_weights, int num_elements, int poly_degree, void *stream);
 int fdd_field_gradient(double *const grad[3], const double *u, const double *const xyz[3], const double *D_hat, int num_elements, int poly_degree, void *stream);
 int fdd_field_weak_divergence(double *out, const double *const v[3], const double *const xyz[3], const double *D_hat, const double *gll_weights, int num_elements, int poly_degree, void *stream);
+/* The convection term c . grad u on the same mesh, pointwise and as an over-integrated weak form (an option of this build;
+ * csrc/fdd_field.hip).  c is a HOST array of three device pointers (the components of the velocity at the points); the
+ * notation is that of the block above, C = adj J.  Per point of the GLL grid:
+ *   chat_b  = sum_a C[b][a] c_a                        the velocity in reference space times det J; no division
+ *   convect       out = (sum_b chat_b du/dr_b) / det J     = c . grad u at the point: the strong form, one division a point
+ * The weak form integrates on M = (3n + 1) / 2 (integer division) Gauss-Legendre points zeta_q per direction with weights
+ * omega_q (gl_weights), the 3/2 rule: P[q][i] = P[i + q n] = l_i(zeta_q) interpolates from the GLL points to them (M x n),
+ * Pd = P D is the derivative of the interpolant there.  Per fine point q = (q_r, q_s, q_t):
+ *   chat_b(q) = (P x P x P) chat_b                     the GLL-point values of chat_b, interpolated
+ *   u,_r(q)   = (P_t x P_s x Pd_r) u,  u,_s and u,_t likewise with Pd in the s / t slot
+ *   s(q)      = omega_qr omega_qs omega_qt sum_b chat_b(q) u,_b(q)
+ *   weak_convect  out = (P^T x P^T x P^T) s            element-local and unassembled like the weak divergence
+ * det J cancels: the weak form divides nowhere.  On an element with an affine map this is the integral of phi_i (c_h . grad
+ * u_h) exactly for c_h, u_h of degree N (the integrand has degree 3N per direction, the rule is exact to 2M - 1 >= 3N).  On
+ * a deformed element chat_b has degree 3N and is represented by its GLL interpolant: the aliasing of the geometry that
+ * Nek5000's set_convect_new accepts too.  A non-positive det J is not detected.  56 B read and 8 B written per point.
+ * poly_degree 1..15, checked first (FDD_ERR_UNSUPPORTED otherwise); num_quad must be (3n + 1) / 2; num_elements <
+ * 2^31 / (N+1)^3; out may be none of the inputs; a call that is refused touches nothing; num_elements = 0 does nothing. */
+int fdd_field_convect(double *out, const double *const c[3], const double *u, const double *const xyz[3], const double *D_hat, int num_elements, int poly_degree, void *stream);
+int fdd_field_weak_convect(double *out, const double *const c[3], const double *u, const double *const xyz[3], const double *D_hat, const double *P, const double *Pd, const double *gl_weights, int num_quad, int num_elements, int poly_degree, void *stream);
 /* The zeroth-order term of -laplace(u) + lambda u on assembled vectors (an option of this build; csrc/fdd_helmholtz.hip):
  *   y[i] = y[i] + c[i] * x[i]          x[i] standing for (*scale_dev) * x[i] where scale_dev is given (the _f32 entry rounds
  *                                      the factor to float first, as fdd_vector_scaling_dev_f32 does)

@@ -371,6 +371,26 @@ int fddh_field_mass(fddh_problem *p, double *mass);
 int fddh_field_gradient(fddh_problem *p, const double *u, double *gx, double *gy, double *gz, int average);
 int fddh_field_weak_divergence(fddh_problem *p, const double *vx, const double *vy, const double *vz, double *out);
 
+/* The convection term c . grad u of a velocity c = (cx, cy, cz) and a field u on the same mesh (an option of this build;
+ * fdd_hip.h: fdd_field_convect and fdd_field_weak_convect, where the formulas are): the one term of an advection-diffusion
+ * or flow step that mass, gradient and weak divergence do not give.  Host vectors of num_local_points as above, the same
+ * opening, the same refusals (a 2-D problem, a degree above 15; the problem stays usable), and on a kernel library without
+ * the two kernel entries both refuse, naming the first missing one.  A diffusivity that is set is not applied: like
+ * fddh_field_*, these are geometry.  They stand outside the fddh_field_* names because that set is the three entries above,
+ * every one of which needs the fdd_field_mass family; fddh_convect_quadrature needs no kernel at all.
+ *   convect       out = c . grad u at every point (collocated, strong form)
+ *   weak_convect  out_i = integral of phi_i (c . grad u) on (3n+1)/2 Gauss-Legendre points per direction, n = N+1 (the 3/2
+ *                 rule, which does not alias the product on an affine element), element-local and unassembled like
+ *                 weak_divergence and the f of fddh_problem_make_rhs.  Every degree 1..15 has a kernel instance
+ *   quadrature    the host tables of that rule: *num_quad = M = (3n+1)/2, z and w (M Gauss-Legendre points and weights), P
+ *                 (M x n, P[i + q n] = l_i(z_q): the interpolation from the GLL points) and Pd = P D_hat (the derivative of
+ *                 the interpolant at z_q).  Any of the pointers may be NULL (not written); ask for num_quad first.
+ * Pd is made from the fine level's current D_hat and made again after fddh_problem_set_D_hat, so both operators follow a
+ * changed table as the gradient does. */
+int fddh_convect(fddh_problem *p, const double *cx, const double *cy, const double *cz, const double *u, double *out);
+int fddh_weak_convect(fddh_problem *p, const double *cx, const double *cy, const double *cz, const double *u, double *out);
+int fddh_convect_quadrature(fddh_problem *p, int *num_quad, double *z, double *w, double *P, double *Pd);
+
 /* ---- Helmholtz solves: (-laplace + lambda) u = f (an option of this build; the reference solves the Poisson problem) ----
  * A shift is a constant lambda >= 0 or, lambda_points != NULL, a value >= 0 per point of the fine level (all finite).  It is
  * kept as one node vector, cbar[n] = sum over the copies p of node n of lambda_p * B_p (B: fddh_field_mass; the products in

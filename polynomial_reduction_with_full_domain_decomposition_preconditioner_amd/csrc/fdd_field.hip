@@ -22,6 +22,9 @@
 // accumulated in registers.  A column is a vector value, not an array: slab k's entry is taken out of it (and wdiv's r/s
 // part put into the accumulator) under the loop's wave-uniform k by indexed register moves, so the slab loop stays rolled
 // and nothing goes to scratch.
+//
+// Further down: the surface weights of listed faces (fdd_field_surface) and the convection term c . grad u, pointwise and
+// over-integrated (fdd_field_convect, fdd_field_weak_convect), each with its own account.
 #include "fdd_common.h"
 
 namespace
@@ -399,9 +402,365 @@ __global__ __launch_bounds__(SurfaceCfg<n>::block) void field_surface_kernel(dou
     }
 }
 
+// ---- the convection term c . grad u (fdd_field_convect, fdd_field_weak_convect; the formulas are in fdd_hip.h) ----
+// Both begin as the gradient kernel does: the k-columns of x, y, z (and, strong form, u) in registers, slab k of each in LDS,
+// J and C = adj J per point.  With c of the slab (read per slab, the next one requested a slab ahead, as wdiv's v is)
+// chat_b = sum_a C[b][a] c_a.  The strong form stores (sum_b chat_b du/dr_b) / det: 56 B read and 8 B written per point.
+//
+// The weak form keeps chat_r, chat_s, chat_t as three more register columns and then streams over the M = (3n+1)/2 fine
+// t-slabs; the fine element (M^3 points a field) never exists.  Per fine slab q_t, with P (M x n) the interpolation to the
+// Gauss points and P' = P D its derivative, both staged in LDS with rows padded by one double:
+//   1. lane (i, j) contracts its columns along t: chat_b and u with row q_t of P, u with row q_t of P' (rows at a
+//      wave-uniform address: scalar loads); five n x n slabs S in LDS
+//   2. along r to M x n: T = P S for the five and T = P' S for u; item (q_r, j) = lane's ij + m n^2, m < ceil(M n / n^2) <= 2
+//   3. along s to M x M: chat_b(q), u,_t = P T(P'_t u), u,_r = P T(P'_r u), u,_s = P' T(u); item (q_r, q_s), <= 3 a lane;
+//      Y = w_qr w_qs w_qt sum_b chat_b(q) u,_b(q)
+//   4. back along s, Z = P^T Y (M x n), and along r, v = P^T Z (n x n): one value per lane
+//   5. acc[k] += P[q_t][k] v for the n entries of the lane's output column, stored once behind the last slab
+// Four element syncs a slab; each buffer is written a sync behind its last read.  The phase that forms chat uses the front of
+// the same LDS (its two slab buffers of x, y, z are smaller than S).  The x, y, z columns are dead when the u column is
+// read, so at most six columns are live (n = 16: 192 registers).
+enum ConvectForm
+{
+    kStrong = 0,
+    kWeak = 1
+};
+
+template <int n>
+struct ConvectCfg
+{
+    using F = FieldCfg<n>;
+    static constexpr int nn = n * n;
+    static constexpr int M = (3 * n + 1) / 2;                 // Gauss points per direction
+    static constexpr int r1 = (M * n + nn - 1) / nn;          // (q_r, j) items a lane
+    static constexpr int r2 = (M * M + nn - 1) / nn;          // (q_r, q_s) items a lane
+    static constexpr int ldp = n + 1;                         // padded row of P and P' in LDS
+    static constexpr int oT = 5 * F::slab, oY = oT + 6 * M * n, oZ = oY + M * M;
+    static constexpr int weak_doubles = oZ + M * n;           // S, T, Y, Z of an element
+    static constexpr int strong_doubles = 2 * 4 * F::slab;    // two buffers of the slabs of x, y, z, u
+};
+
+template <int n, int kForm>
+__global__ __launch_bounds__(kBlock) void convect_kernel(double *__restrict__ out, Ptrs3 cv, const double *__restrict__ u, Ptrs3 X, const double *__restrict__ D_hat, const double *__restrict__ P, const double *__restrict__ Pd,
+                                                         const double *__restrict__ gw, int num_elements)
+{
+    using C = FieldCfg<n>;
+    using W = ConvectCfg<n>;
+    using Column = typename ColumnOf<C::vl>::type;
+    constexpr int nn = C::nn;
+    constexpr int n3 = nn * n;
+    constexpr int M = W::M;
+    constexpr bool kWaveLocal = (64 % nn == 0);
+    constexpr int nF = (kForm == kStrong) ? 4 : 3; // fields differentiated: x, y, z and, strong form, u
+    constexpr int per_elem = (kForm == kStrong) ? W::strong_doubles : W::weak_doubles;
+    constexpr int nP = (kForm == kWeak) ? M * W::ldp : 1;
+
+    __shared__ double s_D[n * n];
+    __shared__ double s_P[nP], s_Pd[nP], s_w[kForm == kWeak ? M : 1];
+    __shared__ double s_e[C::epb][per_elem];
+
+    constexpr bool kWaveIsElement = (nn == 64);
+    const int tid = threadIdx.x;
+    const int e_loc = kWaveIsElement ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid / nn;
+    const int ij = tid - e_loc * nn;
+    const int j = ij / n;
+    const int i = ij - j * n;
+    const int elem = blockIdx.x * C::epb + e_loc;
+    const bool active = (e_loc < C::epb) && (elem < num_elements);
+    const size_t base = active ? (size_t)elem * n3 : 0;
+    const int el = active ? e_loc : 0;
+    const int lpos = i + j * C::ld;
+    double *const se = s_e[el];
+
+    Column col[nF];
+#pragma unroll
+    for (int f = 0; f < nF; f++) col[f] = (Column)(0.0);
+    double cq[3] = {0.0, 0.0, 0.0};
+    if (active)
+    {
+#pragma unroll
+        for (int f = 0; f < 3; f++)
+        {
+            const double *cp = X.p[f] + base;
+#pragma unroll
+            for (int k = 0; k < n; k++) col[f][k] = __builtin_nontemporal_load(cp + (ij + k * nn));
+        }
+        if constexpr (kForm == kStrong)
+        {
+            const double *up = u + base;
+#pragma unroll
+            for (int k = 0; k < n; k++) col[3][k] = __builtin_nontemporal_load(up + (ij + k * nn));
+        }
+#pragma unroll
+        for (int a = 0; a < 3; a++) cq[a] = __builtin_nontemporal_load(cv.p[a] + base + ij);
+    }
+
+    for (int t = tid; t < n * n; t += kBlock) s_D[t] = D_hat[t];
+    if constexpr (kForm == kWeak)
+    {
+        for (int t = tid; t < M * n; t += kBlock)
+        {
+            const int q = t / n, p = t - q * n;
+            s_P[p + q * W::ldp] = P[t];
+            s_Pd[p + q * W::ldp] = Pd[t];
+        }
+        for (int t = tid; t < M; t += kBlock) s_w[t] = gw[t];
+    }
+    __syncthreads(); // the tables are written across elements
+
+    Column ch[kForm == kWeak ? 3 : 1]; // weak form: chat_r, chat_s, chat_t of this lane's column
+#pragma unroll
+    for (int b = 0; b < (kForm == kWeak ? 3 : 1); b++) ch[b] = (Column)(0.0);
+
+#pragma unroll 1
+    for (int k = 0; k < n; k++)
+    {
+        double *sc = se + (k & 1) * (nF * C::slab);
+        if (active)
+        {
+#pragma unroll
+            for (int f = 0; f < nF; f++) sc[f * C::slab + lpos] = col[f][k];
+        }
+
+        const double c[3] = {cq[0], cq[1], cq[2]};
+        if (active && k + 1 < n)
+        {
+#pragma unroll
+            for (int a = 0; a < 3; a++) cq[a] = __builtin_nontemporal_load(cv.p[a] + base + (ij + (k + 1) * nn));
+        }
+
+        // row k of D_hat: wave-uniform address -> scalar loads
+        double Dk[n];
+#pragma unroll
+        for (int p = 0; p < n; p++) Dk[p] = D_hat[p + k * n];
+
+        element_sync<kWaveLocal>();
+
+        double d[nF][3];
+#pragma unroll
+        for (int f = 0; f < nF; f++) d[f][0] = d[f][1] = d[f][2] = 0.0;
+#pragma unroll
+        for (int p = 0; p < n; p++)
+        {
+            const double di = s_D[p + i * n];
+            const double dj = s_D[p + j * n];
+#pragma unroll
+            for (int f = 0; f < nF; f++)
+            {
+                d[f][0] = __builtin_fma(di, sc[f * C::slab + p + j * C::ld], d[f][0]);
+                d[f][1] = __builtin_fma(dj, sc[f * C::slab + i + p * C::ld], d[f][1]);
+                d[f][2] = __builtin_fma(Dk[p], col[f][p], d[f][2]);
+            }
+        }
+
+        // J[a][b] = d[a][b]; Cf = adj J as in field_kernel
+        double Cf[3][3];
+        Cf[0][0] = d[1][1] * d[2][2] - d[1][2] * d[2][1];
+        Cf[0][1] = d[0][2] * d[2][1] - d[0][1] * d[2][2];
+        Cf[0][2] = d[0][1] * d[1][2] - d[0][2] * d[1][1];
+        Cf[1][0] = d[1][2] * d[2][0] - d[1][0] * d[2][2];
+        Cf[1][1] = d[0][0] * d[2][2] - d[0][2] * d[2][0];
+        Cf[1][2] = d[0][2] * d[1][0] - d[0][0] * d[1][2];
+        Cf[2][0] = d[1][0] * d[2][1] - d[1][1] * d[2][0];
+        Cf[2][1] = d[0][1] * d[2][0] - d[0][0] * d[2][1];
+        Cf[2][2] = d[0][0] * d[1][1] - d[0][1] * d[1][0];
+
+        double chat[3];
+#pragma unroll
+        for (int b = 0; b < 3; b++) chat[b] = Cf[b][0] * c[0] + Cf[b][1] * c[1] + Cf[b][2] * c[2];
+
+        if constexpr (kForm == kStrong)
+        {
+            const double det = d[0][0] * Cf[0][0] + d[0][1] * Cf[1][0] + d[0][2] * Cf[2][0];
+            if (active) __builtin_nontemporal_store((chat[0] * d[3][0] + chat[1] * d[3][1] + chat[2] * d[3][2]) / det, out + base + (ij + k * nn));
+        }
+        else
+        {
+#pragma unroll
+            for (int b = 0; b < 3; b++) ch[b][k] = chat[b];
+        }
+    }
+
+    if constexpr (kForm == kWeak)
+    {
+        Column uc = (Column)(0.0);
+        if (active)
+        {
+            const double *up = u + base;
+#pragma unroll
+            for (int k = 0; k < n; k++) uc[k] = __builtin_nontemporal_load(up + (ij + k * nn));
+        }
+        double *const sS = se, *const sT = se + W::oT, *const sY = se + W::oY, *const sZ = se + W::oZ;
+        Column acc = (Column)(0.0);
+
+        element_sync<kWaveLocal>(); // S lies over the slabs the last k read
+
+#pragma unroll 1
+        for (int qt = 0; qt < M; qt++)
+        {
+            // rows q_t of P and P': wave-uniform address -> scalar loads
+            double Pk[n], Pdk[n];
+#pragma unroll
+            for (int p = 0; p < n; p++)
+            {
+                Pk[p] = P[p + qt * n];
+                Pdk[p] = Pd[p + qt * n];
+            }
+            const double wt = gw[qt];
+
+            // 1. along t
+            double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int k = 0; k < n; k++)
+            {
+#pragma unroll
+                for (int b = 0; b < 3; b++) a[b] = __builtin_fma(Pk[k], ch[b][k], a[b]);
+                a[3] = __builtin_fma(Pk[k], uc[k], a[3]);
+                a[4] = __builtin_fma(Pdk[k], uc[k], a[4]);
+            }
+            if (active)
+            {
+#pragma unroll
+                for (int f = 0; f < 5; f++) sS[f * C::slab + lpos] = a[f];
+            }
+            element_sync<kWaveLocal>();
+
+            // 2. along r: T[0..2] = P chat_b, T[3] = P u, T[4] = P (P'_t u), T[5] = P' u
+#pragma unroll
+            for (int m = 0; m < W::r1; m++)
+            {
+                const int id = ij + m * nn;
+                if (id < M * n)
+                {
+                    const int jj = id / M, qr = id - jj * M;
+                    double t[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                    for (int p = 0; p < n; p++)
+                    {
+                        const double pr = s_P[p + qr * W::ldp], pdr = s_Pd[p + qr * W::ldp];
+                        const double s3 = sS[3 * C::slab + p + jj * C::ld];
+#pragma unroll
+                        for (int b = 0; b < 3; b++) t[b] = __builtin_fma(pr, sS[b * C::slab + p + jj * C::ld], t[b]);
+                        t[3] = __builtin_fma(pr, s3, t[3]);
+                        t[4] = __builtin_fma(pr, sS[4 * C::slab + p + jj * C::ld], t[4]);
+                        t[5] = __builtin_fma(pdr, s3, t[5]);
+                    }
+                    if (active)
+                    {
+#pragma unroll
+                        for (int f = 0; f < 6; f++) sT[f * (M * n) + id] = t[f];
+                    }
+                }
+            }
+            element_sync<kWaveLocal>();
+
+            // 3. along s, and the product on the fine slab
+#pragma unroll
+            for (int m = 0; m < W::r2; m++)
+            {
+                const int id = ij + m * nn;
+                if (id < M * M)
+                {
+                    const int qs = id / M, qr = id - qs * M;
+                    double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}; // chat_r, chat_s, chat_t, u,_s, u,_t, u,_r
+#pragma unroll
+                    for (int p = 0; p < n; p++)
+                    {
+                        const double ps = s_P[p + qs * W::ldp], pds = s_Pd[p + qs * W::ldp];
+#pragma unroll
+                        for (int b = 0; b < 3; b++) v[b] = __builtin_fma(ps, sT[b * (M * n) + qr + p * M], v[b]);
+                        v[3] = __builtin_fma(pds, sT[3 * (M * n) + qr + p * M], v[3]);
+                        v[4] = __builtin_fma(ps, sT[4 * (M * n) + qr + p * M], v[4]);
+                        v[5] = __builtin_fma(ps, sT[5 * (M * n) + qr + p * M], v[5]);
+                    }
+                    if (active) sY[id] = ((s_w[qr] * s_w[qs]) * wt) * (v[0] * v[5] + v[1] * v[3] + v[2] * v[4]);
+                }
+            }
+            element_sync<kWaveLocal>();
+
+            // 4. back along s ...
+#pragma unroll
+            for (int m = 0; m < W::r1; m++)
+            {
+                const int id = ij + m * nn;
+                if (id < M * n)
+                {
+                    const int jj = id / M, qr = id - jj * M;
+                    double z = 0.0;
+#pragma unroll
+                    for (int q = 0; q < M; q++) z = __builtin_fma(s_P[jj + q * W::ldp], sY[qr + q * M], z);
+                    if (active) sZ[id] = z;
+                }
+            }
+            element_sync<kWaveLocal>();
+
+            // ... and along r
+            double val = 0.0;
+#pragma unroll
+            for (int q = 0; q < M; q++) val = __builtin_fma(s_P[i + q * W::ldp], sZ[q + j * M], val);
+
+            // 5. out(i, j, k) += P[q_t][k] v(i, j)
+#pragma unroll
+            for (int k = 0; k < n; k++) acc[k] = __builtin_fma(Pk[k], val, acc[k]);
+        }
+
+        if (active)
+        {
+            double *op = out + base;
+#pragma unroll
+            for (int k = 0; k < n; k++) __builtin_nontemporal_store(acc[k], op + (ij + k * nn));
+        }
+    }
+}
+
 } // namespace
 
 extern "C" {
+
+int fdd_field_convect(double *out, const double *const c[3], const double *u, const double *const xyz[3], const double *D_hat, int num_elements, int poly_degree, void *stream)
+{
+    bool run;
+    if (int rc = field_sizes(num_elements, poly_degree, &run)) return rc;
+    if (!run) return 0;
+    FDD_REQUIRE(out != nullptr && u != nullptr && D_hat != nullptr);
+    Ptrs3 cv, X;
+    if (int rc = three_pointers(cv, c)) return rc;
+    if (int rc = three_pointers(X, xyz)) return rc;
+    const OutPtrs3 o = {{out, nullptr, nullptr}};
+    if (int rc = no_alias(o, 1, cv, 3, X)) return rc;
+    FDD_REQUIRE(out != u && out != D_hat);
+    fdd_for_n<2, 16>(poly_degree + 1, [&](auto nc) {
+        constexpr int nv = decltype(nc)::value;
+        const int grid = (num_elements + FieldCfg<nv>::epb - 1) / FieldCfg<nv>::epb;
+        hipLaunchKernelGGL((convect_kernel<nv, kStrong>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), out, cv, u, X, D_hat, nullptr, nullptr, nullptr, num_elements);
+    });
+    FDD_LAUNCH_CHECK();
+    return 0;
+}
+
+int fdd_field_weak_convect(double *out, const double *const c[3], const double *u, const double *const xyz[3], const double *D_hat, const double *P, const double *Pd, const double *gl_weights, int num_quad, int num_elements, int poly_degree,
+                           void *stream)
+{
+    bool run;
+    if (int rc = field_sizes(num_elements, poly_degree, &run)) return rc;
+    const int n = poly_degree + 1; // every degree has an instance: none needs scratch (DESIGN section 16 has the table)
+    FDD_REQUIRE(num_quad == (3 * n + 1) / 2);
+    if (!run) return 0;
+    FDD_REQUIRE(out != nullptr && u != nullptr && D_hat != nullptr && P != nullptr && Pd != nullptr && gl_weights != nullptr);
+    Ptrs3 cv, X;
+    if (int rc = three_pointers(cv, c)) return rc;
+    if (int rc = three_pointers(X, xyz)) return rc;
+    const OutPtrs3 o = {{out, nullptr, nullptr}};
+    if (int rc = no_alias(o, 1, cv, 3, X)) return rc;
+    FDD_REQUIRE(out != u && out != D_hat && out != P && out != Pd && out != gl_weights);
+    fdd_for_n<2, 16>(n, [&](auto nc) {
+        constexpr int nv = decltype(nc)::value;
+        const int grid = (num_elements + FieldCfg<nv>::epb - 1) / FieldCfg<nv>::epb;
+        hipLaunchKernelGGL((convect_kernel<nv, kWeak>), dim3(grid), dim3(kBlock), 0, fdd_stream(stream), out, cv, u, X, D_hat, P, Pd, gl_weights, num_elements);
+    });
+    FDD_LAUNCH_CHECK();
+    return 0;
+}
 
 int fdd_field_surface(double *area, double *const normal[3], const double *const xyz[3], const double *D_hat, const double *gll_weights, const int *face_elem, const int *face_side, int num_faces, int num_elements, int poly_degree, void *stream)
 {

@@ -100,6 +100,10 @@
 #pragma weak fdd_field_mass
 #pragma weak fdd_field_gradient
 #pragma weak fdd_field_weak_divergence
+// and the convection term on the same mesh: without them fddh_convect and fddh_weak_convect refuse, naming the missing entry
+// (missing_convect_entry)
+#pragma weak fdd_field_convect
+#pragma weak fdd_field_weak_convect
 // and the zeroth-order term of a Helmholtz operator (csrc/fdd_helmholtz.hip): without them fddh_helmholtz_set refuses, naming
 // the missing entry (missing_helmholtz_entry)
 #pragma weak fdd_shift_add
@@ -147,6 +151,14 @@ inline const char *missing_field_entry()
     if (&fdd_field_mass == nullptr) return "fdd_field_mass";
     if (&fdd_field_gradient == nullptr) return "fdd_field_gradient";
     if (&fdd_field_weak_divergence == nullptr) return "fdd_field_weak_divergence";
+    return nullptr;
+}
+
+// the first of the convection entries the loaded kernel library does not export, or nullptr
+inline const char *missing_convect_entry()
+{
+    if (&fdd_field_convect == nullptr) return "fdd_field_convect";
+    if (&fdd_field_weak_convect == nullptr) return "fdd_field_weak_convect";
     return nullptr;
 }
 

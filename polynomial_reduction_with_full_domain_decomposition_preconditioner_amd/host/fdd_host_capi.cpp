@@ -143,6 +143,25 @@ int on_field_ops(fddh_problem *p, bool args_ok, Body &&body)
 
 size_t fine_bytes(const fddh_problem &p) { return (size_t)p.fine().num_local_points * sizeof(double); }
 
+// the two forms of the convection term (fddh_convect, fddh_weak_convect): c and u in through p.a, p.b, p.c and a fourth vector,
+// the result out of a fifth
+template <typename Op>
+int convect_entry(fddh_problem *p, const double *cx, const double *cy, const double *cz, const double *u, double *out, Op &&op)
+{
+    return on_problem(p, cx && cy && cz && u && out, [&](fddh_problem &pr) {
+        if (const char *missing = fdd::missing_convect_entry()) return fail("the convection operators need %s, which the loaded kernel library does not export", missing);
+        const fdd::FieldOps<Domain<SType>> ops(pr.fine());
+        fdd::memory field = fdd::dev().malloc<double>(pr.fine().num_local_points), result = fdd::dev().malloc<double>(pr.fine().num_local_points);
+        pr.a.copyFrom(cx, fine_bytes(pr));
+        pr.b.copyFrom(cy, fine_bytes(pr));
+        pr.c.copyFrom(cz, fine_bytes(pr));
+        field.copyFrom(u, fine_bytes(pr));
+        op(ops, result, pr.a, pr.b, pr.c, field);
+        result.copyTo(out, fine_bytes(pr));
+        return 0;
+    });
+}
+
 // a vector of the fine level's points in through p.a, op, its result out through p.b (out may be null: the result stays in p.b)
 template <typename Op>
 void fine_round_trip(fddh_problem &p, const double *in, double *out, Op &&op)
@@ -1500,6 +1519,34 @@ int fddh_field_weak_divergence(fddh_problem *p, const double *vx, const double *
         pr.c.copyFrom(vz, fine_bytes(pr));
         ops.weak_divergence(result, pr.a, pr.b, pr.c);
         result.copyTo(out, fine_bytes(pr));
+        return 0;
+    });
+}
+
+// ---- the convection term c . grad u on the fine level: pointwise, and as the over-integrated weak form (field_ops.hpp) ----
+int fddh_convect(fddh_problem *p, const double *cx, const double *cy, const double *cz, const double *u, double *out)
+{
+    return convect_entry(p, cx, cy, cz, u, out, [](const fdd::FieldOps<Domain<SType>> &ops, fdd::memory &result, auto &...in) { ops.convect(result, in...); });
+}
+
+int fddh_weak_convect(fddh_problem *p, const double *cx, const double *cy, const double *cz, const double *u, double *out)
+{
+    return convect_entry(p, cx, cy, cz, u, out, [](const fdd::FieldOps<Domain<SType>> &ops, fdd::memory &result, auto &...in) { ops.weak_convect(result, in...); });
+}
+
+// the host tables of the weak form's quadrature; no kernel is needed
+int fddh_convect_quadrature(fddh_problem *p, int *num_quad, double *z, double *w, double *P, double *Pd)
+{
+    return on_problem(p, true, [&](fddh_problem &pr) {
+        Domain<SType> &d = pr.fine();
+        if (d.poly_degree < 1) return fail("the quadrature of the convection term needs poly_degree >= 1, got %d", d.poly_degree);
+        fdd::FieldGeometry &g = d.field_geometry;
+        g.quadrature(d.D_hat_hst, d.poly_degree);
+        if (num_quad) *num_quad = g.num_quad;
+        if (z) memcpy(z, g.quad_z.data(), g.quad_z.size() * sizeof(double));
+        if (w) memcpy(w, g.quad_w.data(), g.quad_w.size() * sizeof(double));
+        if (P) memcpy(P, g.P_hst.data(), g.P_hst.size() * sizeof(double));
+        if (Pd) memcpy(Pd, g.Pd_hst.data(), g.Pd_hst.size() * sizeof(double));
         return 0;
     });
 }

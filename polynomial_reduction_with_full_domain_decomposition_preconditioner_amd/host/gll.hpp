@@ -129,6 +129,60 @@ inline std::vector<double> interpolator(int N_c, int N_f)
     return J;
 }
 
+// M Gauss-Legendre nodes z (ascending in (-1,1)) and weights w: the roots of P_M by Newton from the Chebyshev guess
+// (an option of this build: the quadrature of the over-integrated convection term, field_ops.hpp)
+inline void zwgl(double *z, double *w, int M)
+{
+    for (int k = 0; k < M / 2; k++)
+    {
+        double x = -std::cos(M_PI * (2.0 * k + 1.0) / (2.0 * M));
+        for (int it = 0; it < 100; it++)
+        {
+            double dx = pnleg(x, M) / pndleg(x, M);
+            x -= dx;
+            if (std::fabs(dx) < 1e-16) break;
+        }
+        z[k] = x;
+        z[M - 1 - k] = -x;
+    }
+    if (M % 2 == 1) z[M / 2] = 0.0;
+    for (int k = 0; k < M; k++)
+    {
+        double dp = pndleg(z[k], M);
+        w[k] = 2.0 / ((1.0 - z[k] * z[k]) * dp * dp);
+    }
+}
+
+// P[q*n + i] = l_i(x[q]): the values at the m points x of the Lagrange interpolants through the n points z, by the
+// barycentric formula.  Unlike hgll it has no neighbourhood of a node in which the answer is rounded to 1: a point that
+// IS a node (the centre of an odd Gauss grid on an odd GLL grid) gives that node's unit row, any other point the formula
+inline std::vector<double> interpolation_matrix(const double *z, int n, const double *x, int m)
+{
+    std::vector<double> lambda(n, 1.0), P((size_t)m * n, 0.0);
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < n; j++)
+            if (j != i) lambda[i] = lambda[i] / (z[i] - z[j]);
+    for (int q = 0; q < m; q++)
+    {
+        int at = -1;
+        for (int i = 0; i < n; i++)
+            if (x[q] == z[i]) at = i;
+        if (at >= 0)
+        {
+            P[(size_t)q * n + at] = 1.0;
+            continue;
+        }
+        double sum = 0.0;
+        for (int i = 0; i < n; i++)
+        {
+            P[(size_t)q * n + i] = lambda[i] / (x[q] - z[i]);
+            sum += P[(size_t)q * n + i];
+        }
+        for (int i = 0; i < n; i++) P[(size_t)q * n + i] = P[(size_t)q * n + i] / sum;
+    }
+    return P;
+}
+
 } // namespace gll
 } // namespace fdd
 

@@ -501,6 +501,30 @@ class Problem:
         _H().call("fddh_field_weak_divergence", self.h, _dp(v[0]), _dp(v[1]), _dp(v[2]), _dp(out))
         return out
 
+    def _convect(self, entry, cx, cy, cz, u):
+        out = np.zeros(self.n)
+        v = [np.ascontiguousarray(c, dtype=np.float64) for c in (cx, cy, cz, u)]
+        _H().call(entry, self.h, _dp(v[0]), _dp(v[1]), _dp(v[2]), _dp(v[3]), _dp(out))
+        return out
+
+    def convect(self, cx, cy, cz, u):
+        """c . grad u at every point (collocated), per element"""
+        return self._convect("fddh_convect", cx, cy, cz, u)
+
+    def weak_convect(self, cx, cy, cz, u):
+        """out_i = integral of phi_i (c . grad u) on the (3n+1)/2 Gauss-Legendre points per direction (the 3/2 rule),
+        unassembled like weak_divergence: dssum(p.weak_convect(cx, cy, cz, u)) is the convection term of a weak form"""
+        return self._convect("fddh_weak_convect", cx, cy, cz, u)
+
+    def quadrature(self):
+        """(z, w, P, Pd) of weak_convect's rule: M Gauss-Legendre points and weights, P[q, i] = l_i(z_q) and Pd = P D_hat"""
+        M = ctypes.c_int(0)
+        _H().call("fddh_convect_quadrature", self.h, ctypes.byref(M), None, None, None, None)
+        n = self.level_degree(0) + 1
+        z, w, P, Pd = np.zeros(M.value), np.zeros(M.value), np.zeros((M.value, n)), np.zeros((M.value, n))
+        _H().call("fddh_convect_quadrature", self.h, None, _dp(z), _dp(w), _dp(P), _dp(Pd))
+        return z, w, P, Pd
+
     # --- Helmholtz solves (an addition of this build, include/fdd_host.h) ---
     def helmholtz(self, lam):
         """Solve (-laplace + lam) u = f from here on: lam a constant >= 0 or an array >= 0 over the fine level's points; 0

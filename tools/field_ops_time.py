@@ -1,5 +1,5 @@
-"""Times the three field kernels (fdd_field_mass, _gradient, _weak_divergence; csrc/fdd_field.hip) and, in the same process
-for comparison, the six-array fused stiffness kernel (fdd_dom_stiffness_matrix, 64 B per point) with HIP events:
+"""Times the field kernels (fdd_field_mass, _gradient, _weak_divergence, _convect, _weak_convect; csrc/fdd_field.hip) and, in
+the same process for comparison, the six-array fused stiffness kernel (fdd_dom_stiffness_matrix, 64 B per point) with HIP events:
 
     python tools/field_ops_time.py [--elements 32] [--degrees 7 15] [--launches 20] [--windows 7]
 
@@ -19,7 +19,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-BYTES_PER_POINT = {"mass": 32, "gradient": 56, "weak_divergence": 56, "stiffness": 64}
+BYTES_PER_POINT = {"mass": 32, "gradient": 56, "weak_divergence": 56, "convect": 64, "weak_convect": 64, "stiffness": 64}
 
 
 def gll(N):
@@ -34,6 +34,19 @@ def gll(N):
                 D[i, p] = P(z[i]) / (P(z[p]) * (z[i] - z[p]))
     D[0, 0], D[N, N] = -0.25 * N * (N + 1), 0.25 * N * (N + 1)
     return z, w, D.reshape(-1)
+
+
+def gauss_tables(N, z_gll, D):
+    """weak_convect's rule: M = (3n+1)/2 Gauss-Legendre weights, P[q, i] = l_i(zeta_q) (barycentric) and P' = P D"""
+    n = N + 1
+    zeta, omega = np.polynomial.legendre.leggauss((3 * n + 1) // 2)
+    lam = np.array([1.0 / np.prod([z_gll[i] - z_gll[j] for j in range(n) if j != i]) for i in range(n)])
+    diff = zeta[:, None] - z_gll[None, :]
+    hit = np.abs(diff) < 1e-14  # the centre of an odd rule on an odd grid
+    P = lam[None, :] / np.where(hit, 1.0, diff)
+    P = P / P.sum(axis=1)[:, None]
+    P[hit.any(axis=1)] = hit[hit.any(axis=1)].astype(float)
+    return omega, P, P @ D.reshape(n, n)
 
 
 def kershaw(torch, eps, x, y, z):
@@ -88,6 +101,7 @@ def main():
         E3, n3 = args.elements**3, (N + 1) ** 3
         npts = E3 * n3
         D, w = torch.tensor(Dh, device=gpu), torch.tensor(wg, device=gpu)
+        omega, P, Pd = (torch.tensor(np.ascontiguousarray(t), device=gpu) for t in gauss_tables(N, zg, Dh))
         gen = torch.Generator(device=gpu).manual_seed(1234 + N)
         rand = lambda lo, hi: torch.rand(npts, device=gpu, dtype=torch.float64, generator=gen) * (hi - lo) + lo
         u, v = rand(-1.0, 1.0), [rand(-1.0, 1.0) for _ in range(3)]
@@ -99,6 +113,8 @@ def main():
                 "mass": lambda: k("fdd_field_mass", out[0], xyz, D, w, E3, N),
                 "gradient": lambda: k("fdd_field_gradient", out, u, xyz, D, E3, N),
                 "weak_divergence": lambda: k("fdd_field_weak_divergence", out[0], v, xyz, D, w, E3, N),
+                "convect": lambda: k("fdd_field_convect", out[0], v, u, xyz, D, E3, N),
+                "weak_convect": lambda: k("fdd_field_weak_convect", out[0], v, u, xyz, D, P, Pd, omega, len(omega), E3, N),
                 "stiffness": lambda: k("fdd_dom_stiffness_matrix", out[0], u, D, G, E3, N),
             }
             for fn in launch.values():  # warm-up: code objects loaded, every array touched
@@ -123,7 +139,8 @@ def main():
                 rec["kernels"][name] = {"us_median": med, "us_min": min(t), "us_max": max(t), "bytes_per_point": BYTES_PER_POINT[name], "TB_per_s": BYTES_PER_POINT[name] * npts / med * 1e-6}
                 print("  %-16s %9.1f us  (%.1f .. %.1f)  %2d B/point  %5.2f TB/s" % (name, med, min(t), max(t), BYTES_PER_POINT[name], rec["kernels"][name]["TB_per_s"]))
             rec["gradient_over_stiffness"] = rec["kernels"]["gradient"]["us_median"] / rec["kernels"]["stiffness"]["us_median"]
-            print("  gradient / stiffness = %.2f" % rec["gradient_over_stiffness"])
+            rec["weak_convect_over_gradient"] = rec["kernels"]["weak_convect"]["us_median"] / rec["kernels"]["gradient"]["us_median"]
+            print("  gradient / stiffness = %.2f, weak_convect / gradient = %.2f" % (rec["gradient_over_stiffness"], rec["weak_convect_over_gradient"]))
             records.append(rec)
         del u, v, G, out, box, xyz
         torch.cuda.empty_cache()
