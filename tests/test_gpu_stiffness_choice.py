@@ -48,11 +48,14 @@ def bytes_fit(total, count, candidates):
     return any(bytes_fit(total - n * c[-1], count - n, c[:-1]) for n in range(count + 1))
 
 
-def check_step(p, N, box, precision, flags, affine, seed):
+def check_step(p, N, box, precision, flags, affine, seed, state=None, elements=E, reduction=REDUCTION):
+    """state(d): what was established about the list of degree d (stiffness_choice_rules), for meshes whose lists differ from
+    level to level (test_gpu_partial_lists.py); None: a box or a Kershaw mesh of `elements`, every level alike"""
     f32 = precision == 32
-    n_elems = int(np.prod(E))
-    # the lists: one per Domain level (all of the same eight elements), and the Subdomain's one list of the rank's own elements
-    state = lambda d: (3, d, affine, box, box, box and d == 7, box and d == 7)
+    n_elems = int(np.prod(elements))
+    nodes = lambda d: int(np.prod([e * d + 1 for e in elements]))
+    # the lists: one per Domain level (all of the same elements), and the Subdomain's one list of the rank's own elements
+    state = state or (lambda d: (3, d, affine, box, box, box and d == 7, box and d == 7))
     sub_list, sub_gathered = state(N), p.sub_info()["sub_ext_dofs"]
     assert p.zero_factor_info()["sub_lists"] == 1
     sizes = {}
@@ -64,14 +67,14 @@ def check_step(p, N, box, precision, flags, affine, seed):
             sizes.setdefault(label, []).append(per_point * points + (0 if form == "local" else (4 if single else 8) * gathered))
         return label
 
-    for d in S.level_degrees(N, REDUCTION):
+    for d in S.level_degrees(N, reduction):
         for in_place in (False, True):
             add(state(d), "local", in_place, False, 0)
-        add(state(d), "gather", False, False, (2 * d + 1) ** 3)  # the nodes of 2 x 2 x 2 elements of degree d
+        add(state(d), "gather", False, False, nodes(d))  # the nodes of the box of elements of degree d
     for in_place in (False, True):
         add(sub_list, "local", in_place, False, 0)
     must = {add(state(N), "gather", False, False, p.info["num_local_nodes"]), add(sub_list, "gather", False, f32, sub_gathered)}
-    assert (2 * N + 1) ** 3 == p.info["num_local_nodes"]
+    assert nodes(N) == p.info["num_local_nodes"]
 
     _, record = S.profiled(lambda: short_solve(p, seed), records=True)
     got = {label for label in record if label.startswith(FAMILY_PREFIXES)}
@@ -88,7 +91,7 @@ def check_step(p, N, box, precision, flags, affine, seed):
         answer = name()
         assert (answer["enabled"], answer["fine_domain"], answer[key], answer["sub_lists"]) == (flags[flag], dom[kind], int(sub[kind]), 1), (flag, answer, dom, sub)
     answer = p.affine_info()
-    assert (answer["fine_domain"], answer["sub_lists_affine"], answer["sub_lists"]) == (affine, int(affine), 1), answer
+    assert (answer["fine_domain"], answer["sub_lists_affine"], answer["sub_lists"]) == (state(N)[2], int(sub_list[2]), 1), answer
 
 
 @pytest.mark.parametrize("N,box,precision", [(7, True, 64), (7, True, 32), (11, True, 64), (7, False, 64)])
