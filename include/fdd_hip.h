@@ -384,6 +384,22 @@ int fdd_sub_stiffness_matrix_gather_scaled(double *Au, const double *v, const do
 /* in the multi-vector reductions below w == NULL means unit weights: nothing is read, and x * 1.0 is x bit for bit */
 int fdd_multi_weighted_inner_product_scaled(double *out, double *ws, const double *a, const double *const *b, const double *b_scale_dev, int m, const double *w, int n, void *stream);
 int fdd_multi_axpy_norm2_scaled_dev(double *out, double *ws, double *dst, const double *y, const double *coeffs_dev, double sign, const double *const *x, const double *x_scale_dev, int m, const double *w, int n, void *stream); /* dst == NULL (also in the _f32 form): the updated vector is not stored, only its norm is formed -- the last Arnoldi step of a cycle, whose basis vector nobody reads */
+/* The last Arnoldi step of a cycle, whose vector nobody reads, with its norm taken from the projections where rounding allows
+ * (include/fdd_norm_estimate.h states the function and its bound; double precision only -- a float basis is orthogonal to
+ * about 1e-7 and the float entries keep their pass).  m <= FDD_MULTI_MAX - 1 in all three.
+ *   _self : out[0..m-1] as fdd_multi_weighted_inner_product_scaled gives them, bit for bit, and out[m] = sum a*a*w (no scale),
+ *           from the values the dots load anyway: one launch, one fold
+ *   _gated: fdd_multi_axpy_norm2_scaled_dev behind a gate.  dots_dev: the m + 1 sums of _self.  Where the function says the
+ *           norm may be taken from them, both launches return at once and out, dst and ws are not written; where it does not,
+ *           out and dst have the ungated entry's bits
+ *   step  : fdd_gmres_step_dev with dots_dev[0..j] = <q, v_i>, dots_dev[j+1] = <q, q>, dots_dev[j+2] = what _gated wrote if it
+ *           ran; asks the same function of the same numbers and takes the norm from the estimate or from dots_dev[j+2].
+ *           It counts both outcomes in the state; fdd_gmres_fetch_norm_counters reads the counts and the smallest
+ *           est / <q, q> seen (the owner of the state clears its block once, when allocating it) */
+int fdd_multi_weighted_inner_product_self(double *out, double *ws, const double *a, const double *const *b, const double *b_scale_dev, int m, const double *w, int n, void *stream);
+int fdd_multi_axpy_norm2_scaled_gated_dev(double *out, double *ws, double *dst, const double *y, const double *coeffs_dev, double sign, const double *const *x, const double *x_scale_dev, int m, const double *w, int n, const double *dots_dev, void *stream);
+int fdd_gmres_step_last_dev(void *state, const double *dots_dev, int j, int iterations_before, int max_iterations, double tolerance, int use_relative, void *stream);
+int fdd_gmres_fetch_norm_counters(void *state, long long *estimated, long long *exact, double *min_ratio, void *stream);
 int fdd_multi_axpy_scaled_dev(double *q, const double *coeffs_dev, const double *const *v, const double *v_scale_dev, int m, int n, void *stream);
 int fdd_vector_scaling_dev(double *au, const double *scale_dev, const double *u, int n, void *stream); /* au = (*scale_dev) * u */
 int fdd_multi_lincomb_scaled_dev(double *q, int q_is_zero, const double *coeffs_dev, const double *const *v, const double *v_scale_dev, int m, int n, void *stream); /* fdd_multi_axpy_scaled_dev; q_is_zero: q is taken to be 0 and is not read (it need not have been cleared) */

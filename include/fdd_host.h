@@ -391,6 +391,14 @@ int fddh_convect(fddh_problem *p, const double *cx, const double *cy, const doub
 int fddh_weak_convect(fddh_problem *p, const double *cx, const double *cy, const double *cz, const double *u, double *out);
 int fddh_convect_quadrature(fddh_problem *p, int *num_quad, double *z, double *w, double *P, double *Pd);
 
+/* The inner GMRES's last Arnoldi step of a cycle (flag "last_norm_from_projections", on by default where the kernel library has
+ * the entries and refused at 1 where it lacks them; double inner solves with sub_num_vectors < 8 on the dof-space forms): the
+ * norm of the step's vector, which nobody reads, is taken as <q, q> - sum h_k^2 where that difference keeps at least 2^-10 of
+ * <q, q> (include/fdd_norm_estimate.h), and from the exact pass otherwise.  Counted over the life of the problem's Subdomain:
+ * *estimated steps took the difference, *exact fell back, *min_ratio is the smallest difference / <q, q> among them (0 before
+ * the first).  Any pointer may be NULL.  A problem without a Subdomain is refused.  One blocking read of the device state. */
+int fddh_inner_norm_counters(fddh_problem *p, long long *estimated, long long *exact, double *min_ratio);
+
 /* ---- Helmholtz solves: (-laplace + lambda) u = f (an option of this build; the reference solves the Poisson problem) ----
  * A shift is a constant lambda >= 0 or, lambda_points != NULL, a value >= 0 per point of the fine level (all finite).  It is
  * kept as one node vector, cbar[n] = sum over the copies p of node n of lambda_p * B_p (B: fddh_field_mass; the products in

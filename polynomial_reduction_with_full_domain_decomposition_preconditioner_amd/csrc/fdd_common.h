@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "fdd_hip.h"
+#include "fdd_norm_estimate.h"
 
 #define FDD_WAVE 64
 #define FDD_CU_COUNT 256

@@ -26,6 +26,10 @@ struct GmresState
     double steps;          // steps counted until the stop (the reference's `iter` increment of this cycle)
     double converged;      // the reference's `converged` flag at the end of the cycle
     double inv[kMax + 1];  // 1/gamma_0 and 1/||q_j||: the normalisation of basis vector j, applied by its readers
+    // the last steps of cycles that went through gmres_step_last_kernel, over the life of the state (the owner clears the
+    // block once, when it allocates it): how many took the norm from the projections, how many the exact pass's, and the
+    // smallest est/aa among them
+    double norm_estimated, norm_exact, min_ratio;
 };
 
 __global__ void gmres_begin_kernel(GmresState *st, const double *norm2, int first_cycle)
@@ -44,10 +48,9 @@ __global__ void gmres_begin_kernel(GmresState *st, const double *norm2, int firs
     for (int k = 0; k < kMax; k++) st->y[k] = 0.0;
 }
 
-// column j: dots[0..j] = <q, v_i>, dots[j+1] = ||q - sum h v||^2
-__global__ void gmres_step_kernel(GmresState *st, const double *dots, int j, int iterations_before, int max_iterations, double tolerance, int use_relative)
+// column j: dots[0..j] = <q, v_i>, norm2 = ||q - sum h v||^2
+__device__ __forceinline__ void gmres_step_body(GmresState *st, const double *dots, double norm2, int j, int iterations_before, int max_iterations, double tolerance, int use_relative)
 {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
     if (st->stopped != 0.0) return;
     st->steps += 1.0;
     const int iter = iterations_before + (int)st->steps;
@@ -59,7 +62,7 @@ __global__ void gmres_step_kernel(GmresState *st, const double *dots, int j, int
         st->H[i][j] = st->c[i] * h_ij + st->s[i] * st->H[i + 1][j];
         st->H[i + 1][j] = -st->s[i] * h_ij + st->c[i] * st->H[i + 1][j];
     }
-    const double alpha_j = sqrt(dots[j + 1]);
+    const double alpha_j = sqrt(norm2);
     st->j_last = (double)j;
     if (fabs(alpha_j) == 0.0) // subdomain.tpp:4418-4422
     {
@@ -85,6 +88,31 @@ __global__ void gmres_step_kernel(GmresState *st, const double *dots, int j, int
         st->stopped = 1.0;
         st->converged = 1.0;
     }
+}
+
+// column j: dots[0..j] = <q, v_i>, dots[j+1] = ||q - sum h v||^2
+__global__ void gmres_step_kernel(GmresState *st, const double *dots, int j, int iterations_before, int max_iterations, double tolerance, int use_relative)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    gmres_step_body(st, dots, dots[j + 1], j, iterations_before, max_iterations, tolerance, use_relative);
+}
+
+// The same step where the vector is not read (the last of a cycle): dots[0..j] = <q, v_i>, dots[j+1] = <q, q>, and dots[j+2]
+// the exact ||q - sum h v||^2, written only where the gated pass ran (fdd_multi_axpy_norm2_scaled_gated_dev).  The function
+// the pass was gated on (fdd_norm_estimate.h), asked of the same numbers, says which of the two the step takes.  Double
+// solves only: see the header.
+__global__ void gmres_step_last_kernel(GmresState *st, const double *dots, int j, int iterations_before, int max_iterations, double tolerance, int use_relative)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double est;
+    const int usable = fdd_norm2_from_projections(dots[j + 1], dots, j + 1, &est);
+    const double ratio = est / dots[j + 1];
+    if (ratio == ratio && (st->norm_estimated + st->norm_exact == 0.0 || ratio < st->min_ratio)) st->min_ratio = ratio;
+    if (usable)
+        st->norm_estimated += 1.0;
+    else
+        st->norm_exact += 1.0;
+    gmres_step_body(st, dots, usable ? est : dots[j + 2], j, iterations_before, max_iterations, tolerance, use_relative);
 }
 
 // back-substitution (subdomain.tpp:4462-4468): y[0..j_last]
@@ -121,6 +149,27 @@ int fdd_gmres_step_dev(void *state, const double *dots_dev, int j, int iteration
     FDD_REQUIRE(state != nullptr && dots_dev != nullptr && j >= 0 && j < kMax);
     hipLaunchKernelGGL(gmres_step_kernel, dim3(1), dim3(64), 0, fdd_stream(stream), static_cast<GmresState *>(state), dots_dev, j, iterations_before, max_iterations, tolerance, use_relative);
     FDD_LAUNCH_CHECK();
+    return 0;
+}
+
+int fdd_gmres_step_last_dev(void *state, const double *dots_dev, int j, int iterations_before, int max_iterations, double tolerance, int use_relative, void *stream)
+{
+    FDD_REQUIRE(state != nullptr && dots_dev != nullptr && j >= 0 && j < kMax - 1); // j + 3 doubles of a slot of FDD_GMRES_SLOT
+    hipLaunchKernelGGL(gmres_step_last_kernel, dim3(1), dim3(64), 0, fdd_stream(stream), static_cast<GmresState *>(state), dots_dev, j, iterations_before, max_iterations, tolerance, use_relative);
+    FDD_LAUNCH_CHECK();
+    return 0;
+}
+
+// one blocking copy of the counters of gmres_step_last_kernel (min_ratio: 0 before the first such step)
+int fdd_gmres_fetch_norm_counters(void *state, long long *estimated, long long *exact, double *min_ratio, void *stream)
+{
+    FDD_REQUIRE(state != nullptr);
+    GmresState h;
+    int rc = fdd_fetch_scalars(&h, state, sizeof(GmresState), stream);
+    if (rc) return rc;
+    if (estimated) *estimated = (long long)h.norm_estimated;
+    if (exact) *exact = (long long)h.norm_exact;
+    if (min_ratio) *min_ratio = h.min_ratio;
     return 0;
 }
 

@@ -58,8 +58,9 @@ __device__ __forceinline__ void block_reduce_store(Acc<NV> a, double *ws, int nb
     }
 }
 
+// the three kernels' bodies, stated once for the plain launches and for the gated ones below
 template <typename Op>
-__global__ __launch_bounds__(kBlock) void reduce_vec2_kernel(Op op, double *ws, long long n2, long long n)
+__device__ __forceinline__ void reduce_vec2_body(const Op &op, double *ws, long long n2, long long n)
 {
     Acc<Op::NV> a;
 #pragma unroll
@@ -73,7 +74,7 @@ __global__ __launch_bounds__(kBlock) void reduce_vec2_kernel(Op op, double *ws, 
 }
 
 template <typename Op>
-__global__ __launch_bounds__(kBlock) void reduce_scalar_kernel(Op op, double *ws, long long n)
+__device__ __forceinline__ void reduce_scalar_body(const Op &op, double *ws, long long n)
 {
     Acc<Op::NV> a;
 #pragma unroll
@@ -85,9 +86,60 @@ __global__ __launch_bounds__(kBlock) void reduce_scalar_kernel(Op op, double *ws
     block_reduce_store<Op::NV>(a, ws, FDD_REDUCE_MAX_BLOCKS);
 }
 
+template <typename Op>
+__global__ __launch_bounds__(kBlock) void reduce_vec2_kernel(Op op, double *ws, long long n2, long long n)
+{
+    reduce_vec2_body(op, ws, n2, n);
+}
+
+template <typename Op>
+__global__ __launch_bounds__(kBlock) void reduce_scalar_kernel(Op op, double *ws, long long n)
+{
+    reduce_scalar_body(op, ws, n);
+}
+
+// Gate of the last Arnoldi step's exact norm pass (fdd_norm_estimate.h): dots[0..m-1] are the projections of this step and
+// dots[m] the self product.  Where the norm may be taken from them the launch has nothing to do: every workgroup asks the same
+// question of the same m + 1 numbers (wave-uniform) and returns before it reads a vector or writes anything.
+__device__ __forceinline__ bool norm_pass_needed(const double *dots, int m)
+{
+    double est;
+    return !fdd_norm2_from_projections(dots[m], dots, m, &est);
+}
+
+template <typename Op>
+__global__ __launch_bounds__(kBlock) void reduce_vec2_gated_kernel(Op op, double *ws, long long n2, long long n, const double *dots, int m)
+{
+    if (!norm_pass_needed(dots, m)) return;
+    reduce_vec2_body(op, ws, n2, n);
+}
+
+template <typename Op>
+__global__ __launch_bounds__(kBlock) void reduce_scalar_gated_kernel(Op op, double *ws, long long n, const double *dots, int m)
+{
+    if (!norm_pass_needed(dots, m)) return;
+    reduce_scalar_body(op, ws, n);
+}
+
 // second stage: one workgroup folds `nblocks` partials per value
 template <int NV>
+__device__ __forceinline__ void reduce_final_body(double *out, const double *ws, int nblocks);
+
+template <int NV>
 __global__ __launch_bounds__(kBlock) void reduce_final_kernel(double *out, const double *ws, int nblocks)
+{
+    reduce_final_body<NV>(out, ws, nblocks);
+}
+
+template <int NV>
+__global__ __launch_bounds__(kBlock) void reduce_final_gated_kernel(double *out, const double *ws, int nblocks, const double *dots, int m)
+{
+    if (!norm_pass_needed(dots, m)) return;
+    reduce_final_body<NV>(out, ws, nblocks);
+}
+
+template <int NV>
+__device__ __forceinline__ void reduce_final_body(double *out, const double *ws, int nblocks)
 {
     __shared__ double s[NV][kWaves];
     const int lane = threadIdx.x & (FDD_WAVE - 1);
@@ -153,6 +205,32 @@ int launch_reduce(const Op &op, double *out, double *ws, long long n, void *stre
     }
     FDD_LAUNCH_CHECK();
     hipLaunchKernelGGL(reduce_final_kernel<Op::NV>, dim3(1), dim3(kBlock), 0, s, out, ws, grid);
+    FDD_LAUNCH_CHECK();
+    return 0;
+}
+
+// launch_reduce behind the gate of norm_pass_needed(dots, m): the same path, grid and fold, hence the same bits where the gate
+// is open; where it is closed neither launch writes out, ws or anything the op stores.  An empty sum is the fold over no partials.
+template <typename Op>
+int launch_reduce_gated(const Op &op, double *out, double *ws, long long n, const double *dots, int m, void *stream)
+{
+    hipStream_t s = fdd_stream(stream);
+    int grid = 0;
+    if (n <= 0)
+        ;
+    else if (fdd_lanes_fit<Pair>(op) && n >= 2)
+    {
+        long long n2 = n / 2;
+        grid = fdd_stream_grid(n2, kBlock);
+        hipLaunchKernelGGL(reduce_vec2_gated_kernel<Op>, dim3(grid), dim3(kBlock), 0, s, op, ws, n2, n, dots, m);
+    }
+    else
+    {
+        grid = fdd_stream_grid(n, kBlock);
+        hipLaunchKernelGGL(reduce_scalar_gated_kernel<Op>, dim3(grid), dim3(kBlock), 0, s, op, ws, n, dots, m);
+    }
+    FDD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(reduce_final_gated_kernel<Op::NV>, dim3(1), dim3(kBlock), 0, s, out, ws, grid, dots, m);
     FDD_LAUNCH_CHECK();
     return 0;
 }
@@ -345,6 +423,22 @@ struct FlexWOp // subdomain.okl:229-258
 
 // out[i] = sum a * b_i * w for i < M: `a` and `w` are read once for all M dots
 // (the reference launches weighted_inner_product once per pair, subdomain.tpp:4389-4394)
+// the terms of element i, for MultiDotWOp<M> (NV = M) and MultiDotSelfOp<M> (NV = M + 1: the self product sum a*a*w behind
+// them, from the values already loaded; it takes no scale)
+template <int M, int NV, typename A>
+__device__ __forceinline__ void multi_dot_at(A l, long long i, const double *a, const double *w, const double *const (&b)[M], const double *bs, Acc<NV> &acc)
+{
+    const auto aa = l.ld(a, i), ww = w ? l.ld(w, i) : l.all(1.0); // w == NULL: unit weights, not read (x * 1.0 is x)
+#pragma unroll
+    for (int k = 0; k < M; k++)
+    {
+        auto bb = (b[k] == a) ? aa : l.ld(b[k], i); // <a, a>: one stream, not two
+        if (bs) bb = bs[k] * bb;
+        l.add(acc.v[k], aa * bb * ww);
+    }
+    if constexpr (NV > M) l.add(acc.v[M], aa * aa * ww);
+}
+
 template <int M>
 struct MultiDotWOp
 {
@@ -355,14 +449,7 @@ struct MultiDotWOp
     template <typename A>
     __device__ void at(A l, long long i, Acc<M> &acc) const
     {
-        const auto aa = l.ld(a, i), ww = w ? l.ld(w, i) : l.all(1.0); // w == NULL: unit weights, not read (x * 1.0 is x)
-#pragma unroll
-        for (int k = 0; k < M; k++)
-        {
-            auto bb = (b[k] == a) ? aa : l.ld(b[k], i); // <a, a>: one stream, not two
-            if (bs) bb = bs[k] * bb;
-            l.add(acc.v[k], aa * bb * ww);
-        }
+        multi_dot_at<M>(l, i, a, w, b, bs, acc);
     }
     template <typename F>
     void pointers(F f) const
@@ -372,10 +459,33 @@ struct MultiDotWOp
     }
 };
 
+// MultiDotWOp<M> with out[M] = sum a*a*w: the traversal, and so the bits of the first M sums, are MultiDotWOp<M>'s
+template <int M>
+struct MultiDotSelfOp : MultiDotWOp<M>
+{
+    static constexpr int NV = M + 1;
+    template <typename A>
+    __device__ void at(A l, long long i, Acc<M + 1> &acc) const
+    {
+        multi_dot_at<M>(l, i, this->a, this->w, this->b, this->bs, acc);
+    }
+};
+
 template <int M>
 int launch_multi_dot(double *out, double *ws, const double *a, const double *const *b, const double *b_scale_dev, const double *w, int n, void *stream)
 {
     MultiDotWOp<M> op;
+    op.a = a;
+    op.w = w;
+    op.bs = b_scale_dev;
+    for (int k = 0; k < M; k++) op.b[k] = b[k];
+    return launch_reduce(op, out, ws, n, stream);
+}
+
+template <int M>
+int launch_multi_dot_self(double *out, double *ws, const double *a, const double *const *b, const double *b_scale_dev, const double *w, int n, void *stream)
+{
+    MultiDotSelfOp<M> op;
     op.a = a;
     op.w = w;
     op.bs = b_scale_dev;
@@ -420,8 +530,9 @@ struct MultiAxpyNormOp
     }
 };
 
+// gate_dots: NULL, or the M + 1 dots the launch is gated on (launch_reduce_gated)
 template <int M>
-int launch_multi_axpy_norm(double *out, double *ws, double *dst, const double *y, const double *c, double sign, const double *const *x, const double *x_scale_dev, const double *w, int n, void *stream)
+int launch_multi_axpy_norm(double *out, double *ws, double *dst, const double *y, const double *c, double sign, const double *const *x, const double *x_scale_dev, const double *w, int n, void *stream, const double *gate_dots = nullptr)
 {
     MultiAxpyNormOp<M> op;
     op.dst = dst;
@@ -431,6 +542,7 @@ int launch_multi_axpy_norm(double *out, double *ws, double *dst, const double *y
     op.xs = x_scale_dev;
     op.sign = sign;
     for (int k = 0; k < M; k++) op.x[k] = x[k];
+    if (gate_dots) return launch_reduce_gated(op, out, ws, n, gate_dots, M, stream);
     return launch_reduce(op, out, ws, n, stream);
 }
 
@@ -787,6 +899,30 @@ int fdd_multi_axpy_norm2_scaled_dev(double *out, double *ws, double *dst, const 
     case 7: return launch_multi_axpy_norm<7>(out, ws, dst, y, coeffs_dev, sign, x, x_scale_dev, w, n, stream);
     default: return launch_multi_axpy_norm<8>(out, ws, dst, y, coeffs_dev, sign, x, x_scale_dev, w, n, stream);
     }
+}
+
+// The two entries of an Arnoldi step whose vector is not read (the last of a cycle).  Double only: a float basis is orthogonal
+// to about 1e-7, the identity behind fdd_norm_estimate.h does not hold to double rounding there, and the float inner solve
+// keeps its pass and its bits.
+int fdd_multi_weighted_inner_product_self(double *out, double *ws, const double *a, const double *const *b, const double *b_scale_dev, int m, const double *w, int n, void *stream)
+{
+    // one sum more than the m dots: the workspace and the fold hold FDD_MULTI_MAX of them
+    FDD_REQUIRE(out != nullptr && ws != nullptr && n >= 0 && m >= 1 && m <= FDD_MULTI_MAX - 1 && b != nullptr);
+    FDD_REQUIRE(n == 0 || a != nullptr); // w == NULL: unit weights
+    for (int k = 0; k < m; k++) FDD_REQUIRE(n == 0 || b[k] != nullptr);
+    int rc = 0;
+    fdd_for_n<1, FDD_MULTI_MAX - 1>(m, [&](auto M) { rc = launch_multi_dot_self<M()>(out, ws, a, b, b_scale_dev, w, n, stream); });
+    return rc;
+}
+
+int fdd_multi_axpy_norm2_scaled_gated_dev(double *out, double *ws, double *dst, const double *y, const double *coeffs_dev, double sign, const double *const *x, const double *x_scale_dev, int m, const double *w, int n, const double *dots_dev, void *stream)
+{
+    FDD_REQUIRE(out != nullptr && ws != nullptr && n >= 0 && m >= 1 && m <= FDD_MULTI_MAX - 1 && x != nullptr && coeffs_dev != nullptr && dots_dev != nullptr);
+    FDD_REQUIRE(n == 0 || y != nullptr); // w == NULL: unit weights; dst == NULL: only the norm is formed
+    for (int k = 0; k < m; k++) FDD_REQUIRE(n == 0 || x[k] != nullptr);
+    int rc = 0;
+    fdd_for_n<1, FDD_MULTI_MAX - 1>(m, [&](auto M) { rc = launch_multi_axpy_norm<M()>(out, ws, dst, y, coeffs_dev, sign, x, x_scale_dev, w, n, stream, dots_dev); });
+    return rc;
 }
 
 int fdd_gather_weighted_norm2(double *out, double *ws, const int *Qt_ptr, const int *Qt_col, const double *u, const double *node_weight, int num_nodes, void *stream)

@@ -116,9 +116,25 @@
 // to be set to 1, naming the missing entry (missing_indexed_shift_entry)
 #pragma weak fdd_shift_add_indexed
 #pragma weak fdd_shift_add_indexed_f32
+// and the last Arnoldi step of a cycle with its norm taken from the projections: without them that step keeps the exact pass,
+// and the flag "last_norm_from_projections" refuses to be set to 1, naming the missing entry (missing_norm_estimate_entry)
+#pragma weak fdd_multi_weighted_inner_product_self
+#pragma weak fdd_multi_axpy_norm2_scaled_gated_dev
+#pragma weak fdd_gmres_step_last_dev
+#pragma weak fdd_gmres_fetch_norm_counters
 
 namespace fdd
 {
+
+// the first entry the norm from the projections needs that the loaded kernel library does not export, or nullptr
+inline const char *missing_norm_estimate_entry()
+{
+    if (&fdd_multi_weighted_inner_product_self == nullptr) return "fdd_multi_weighted_inner_product_self";
+    if (&fdd_multi_axpy_norm2_scaled_gated_dev == nullptr) return "fdd_multi_axpy_norm2_scaled_gated_dev";
+    if (&fdd_gmres_step_last_dev == nullptr) return "fdd_gmres_step_last_dev";
+    if (&fdd_gmres_fetch_norm_counters == nullptr) return "fdd_gmres_fetch_norm_counters";
+    return nullptr;
+}
 
 // the first entry a Robin coefficient needs beyond a Helmholtz shift's that the loaded kernel library does not export, or nullptr
 inline const char *missing_boundary_entry()

@@ -1177,6 +1177,16 @@ static int set_indexed_shift(fddh_problem &p, const char *, int value)
     return 0;
 }
 
+// the norm of the inner GMRES's last Arnoldi vector of a cycle from the projections (Subdomain::last_norm_from_projections)
+// or, 0, from the exact pass as before: rounding differs, nothing else
+static int set_last_norm_from_projections(fddh_problem &p, const char *, int value)
+{
+    if (value != 0)
+        if (const char *missing = fdd::missing_norm_estimate_entry()) return fail("last_norm_from_projections needs %s, which the loaded kernel library does not export", missing);
+    if (p.subdomain) p.subdomain->last_norm_from_projections = value != 0;
+    return 0;
+}
+
 // 0: the inner FCG / GMRES(m) (set_options' preconditioner_type); 1: the Chebyshev-Jacobi iteration (an option of this
 // build, Subdomain::chebyshev_dofs), which takes the place of either.  What it cannot run on is refused when a solve starts.
 static int set_inner_solver(fddh_problem &p, const char *, int value)
@@ -1289,6 +1299,7 @@ static const CodedFlagRow *coded_flag_row(const std::string &flag)
         {"affine_geometry", false, set_affine_geometry},
         {"fused_projection", false, set_fused_projection},
         {"indexed_shift", false, set_indexed_shift},
+        {"last_norm_from_projections", false, set_last_norm_from_projections},
         {"inner_solver", true, set_inner_solver},
         {"inner_chebyshev_order", true, set_inner_chebyshev_order},
         {"inner_chebyshev_lower_permille", true, set_inner_chebyshev_lower_permille},
@@ -1547,6 +1558,19 @@ int fddh_convect_quadrature(fddh_problem *p, int *num_quad, double *z, double *w
         if (w) memcpy(w, g.quad_w.data(), g.quad_w.size() * sizeof(double));
         if (P) memcpy(P, g.P_hst.data(), g.P_hst.size() * sizeof(double));
         if (Pd) memcpy(Pd, g.Pd_hst.data(), g.Pd_hst.size() * sizeof(double));
+        return 0;
+    });
+}
+
+int fddh_inner_norm_counters(fddh_problem *p, long long *estimated, long long *exact, double *min_ratio)
+{
+    return on_subdomain(p, true, [&](fddh_problem &, Subdomain<PType> &s) {
+        long long e = 0, x = 0;
+        double r = 0.0;
+        s.norm_counters(e, x, r);
+        if (estimated) *estimated = e;
+        if (exact) *exact = x;
+        if (min_ratio) *min_ratio = r;
         return 0;
     });
 }

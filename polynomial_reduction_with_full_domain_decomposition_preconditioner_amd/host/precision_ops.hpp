@@ -88,6 +88,19 @@ inline void multi_axpy_norm2(double *out, double *ws, float *dst, const float *y
     ProfileScope prof("reduce_vec2_kernel<MultiAxpyNormF32>", 4.0 * n * (m + 2));
     FDD_CALL(fdd_multi_axpy_norm2_scaled_dev_f32(out, ws, dst, y, coeffs_dev, sign, x, x_scale, m, n, s));
 }
+// the last step of a cycle, double only (include/fdd_norm_estimate.h): the dots with out[m] = <a, a> behind them -- the same
+// streams, so the same label and bytes -- and the norm pass gated on those m + 1 sums.  The gated pass is recorded under a
+// label of its own with no bytes: it moves m + 2 vectors where the gate is open and nothing where it is closed.
+inline void multi_dot_self(double *out, double *ws, const double *a, const double *const *b, const double *b_scale, int m, const double *w, int n, void *s)
+{
+    ProfileScope prof("reduce_vec2_kernel<MultiDotW>", 8.0 * n * (m + 1 + (w ? 1 : 0)));
+    FDD_CALL(fdd_multi_weighted_inner_product_self(out, ws, a, b, b_scale, m, w, n, s));
+}
+inline void multi_axpy_norm2_gated(double *out, double *ws, double *dst, const double *y, const double *coeffs_dev, double sign, const double *const *x, const double *x_scale, int m, const double *w, int n, const double *dots_dev, void *s)
+{
+    ProfileScope prof("reduce_vec2_gated_kernel<MultiAxpyNorm>", 0.0);
+    FDD_CALL(fdd_multi_axpy_norm2_scaled_gated_dev(out, ws, dst, y, coeffs_dev, sign, x, x_scale, m, w, n, dots_dev, s));
+}
 
 // ---- the solution update q (+)= sum_k c_k (s_k v_k); q_is_zero: q is not read ----
 // all m vectors (the host knows the column count).  Float has the limited entry only and runs it without a limit.

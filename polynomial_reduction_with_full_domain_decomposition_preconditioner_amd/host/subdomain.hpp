@@ -56,6 +56,7 @@
 #include "csr_matrix.hpp"
 #include "domain.hpp"
 #include "element_operator.hpp"
+#include "fdd_norm_estimate.h"
 #include "gll.hpp"
 #include "gmres.hpp"
 #include "low_order.hpp"
@@ -1522,6 +1523,26 @@ class Subdomain
     bool unit_norm_weight() const { return norm_weight_is_one; }
     bool fold_coarse_exchange = true;     // the coarse level's blocks travel inside the ring pull's group (false: an all-gather of their own)
     bool skip_last_basis_store = true;    // device GMRES: the last Arnoldi step of a cycle forms the norm of its vector without storing it (nobody reads it)
+    // dof-space GMRES in double, m < FDD_MULTI_MAX: the last Arnoldi step of a cycle takes |q - sum h v|^2 from <q, q> and the
+    // projections where include/fdd_norm_estimate.h allows it, and the exact pass runs (gated on the device, no host in between)
+    // only where it does not.  Changes rounding, not more: DESIGN section 4.3.  On where the kernel library has the entries; at 0
+    // every launch is the one it was.  Which norm the step takes depends on this flag alone, not on skip_last_basis_store.
+    bool last_norm_from_projections = fdd::missing_norm_estimate_entry() == nullptr;
+    bool norm_from_projections_at(int j) const { return last_norm_from_projections and precision != 32 and j + 1 == num_vectors and num_vectors < FDD_MULTI_MAX; }
+    long long host_norm_estimated = 0, host_norm_exact = 0; // the host-bookkeeping loop's share of the counters below
+    double host_min_ratio = 0.0;
+    // over the life of this Subdomain: the last steps that took the estimate, those that fell back to the exact pass, and the
+    // smallest est / <q, q> among them (0 before the first); one blocking read of the device state
+    void norm_counters(long long &estimated, long long &exact, double &min_ratio)
+    {
+        estimated = host_norm_estimated, exact = host_norm_exact, min_ratio = host_min_ratio;
+        if (not gmres_state.ptr() or fdd::missing_norm_estimate_entry() != nullptr) return;
+        long long e = 0, x = 0;
+        double r = 0.0;
+        FDD_CALL(fdd_gmres_fetch_norm_counters(gmres_state.ptr(), &e, &x, &r, fdd::dev().stream));
+        if (e + x > 0 and (estimated + exact == 0 or r < min_ratio)) min_ratio = r;
+        estimated += e, exact += x;
+    }
     bool history_pending = false;         // the last solve ran with InnerSolveHints::lazy_history and its history is still on the device
 
     // residual_history of the last lazy solve (one blocking read of the device state)
@@ -2354,7 +2375,12 @@ class Subdomain
             FDD_CALL(fdd_sub_copy_f32_f64(K.fa.template as<float>(), fa_io.as<double>(), nd, stream)); // copy_from_domain_data, subdomain.okl:268-274
         }
         Real *ua = (f32 ? K.ua : ua_io).template as<Real>(), *fa = (f32 ? K.fa : fa_io).template as<Real>(), *qa = K.qa.template as<Real>();
-        if (not gmres_state.ptr()) gmres_state = fdd::dev().malloc<char>(fdd_gmres_state_bytes());
+        if (not gmres_state.ptr())
+        {
+            // cleared once: the counters of fdd_gmres_step_last_dev live as long as the state (every member is a double)
+            gmres_state = fdd::dev().malloc<char>(fdd_gmres_state_bytes());
+            FDD_CALL(fdd_set_to_value(gmres_state.as<double>(), 0.0, (int)(fdd_gmres_state_bytes() / sizeof(double)), 0, fdd::dev().stream));
+        }
         begin_inner_solve();
         double *sc = scalars.as<double>();
         double *ws = reduce_ws.as<double>();
@@ -2433,6 +2459,21 @@ class Subdomain
 
                 double *slot = sc + (j & 1) * FDD_GMRES_SLOT;
                 W[j + 1] = K.VA[j + 1].template as<Real>();
+                if constexpr (not f32)
+                    if (norm_from_projections_at(j))
+                    {
+                        // the cycle's last vector is never read and its norm is <q, q> - sum h^2 up to rounding: the dots carry
+                        // <q, q> along (slot[j + 1]), the exact pass is gated on those numbers on the device (it writes
+                        // slot[j + 2] where it runs), and the step asks the same function which of the two to take.  With the
+                        // vector stored the pass runs ungated for the vector; the norm is chosen the same way.
+                        ops::multi_dot_self(slot, ws, qa, W.data(), inv_dev, j + 1, nw, nd, stream);
+                        if (skip_last_basis_store)
+                            ops::multi_axpy_norm2_gated(slot + (j + 2), ws, nullptr, qa, slot, -1.0, W.data(), inv_dev, j + 1, nw, nd, slot, stream);
+                        else
+                            ops::multi_axpy_norm2(slot + (j + 2), ws, W[j + 1], qa, slot, -1.0, W.data(), inv_dev, j + 1, nw, nd, stream);
+                        FDD_CALL(fdd_gmres_step_last_dev(st, slot, j, iter, max_iterations, tolerance, use_relative ? 1 : 0, stream));
+                        continue;
+                    }
                 ops::multi_dot(slot, ws, qa, W.data(), inv_dev, j + 1, nw, nd, stream);
                 // the cycle's last basis vector is never read: only its norm is formed
                 ops::multi_axpy_norm2(slot + (j + 1), ws, (j + 1 < m or not skip_last_basis_store) ? W[j + 1] : nullptr, qa, slot, -1.0, W.data(), inv_dev, j + 1, nw, nd, stream);
@@ -2677,7 +2718,7 @@ class Subdomain
             fetch_scalars(&norm, 1);
             return std::sqrt(norm);
         };
-        std::vector<double> coeffs(m + 2);
+        std::vector<double> coeffs(m + 3);
         std::vector<const double *> ptrs(m + 1);
         fdd::memory *ra = &fa; // assembled residual of the current cycle
         fdd::GmresSpace<DType> space;
@@ -2713,6 +2754,29 @@ class Subdomain
 
             // H[0..j][j] = <q~, v~_i>, q~ -= sum H v~_i, ||q~||^2: coefficients never leave the device in between
             for (int i = 0; i < j + 1; i++) ptrs[i] = VA[i].template as<double>();
+            if (norm_from_projections_at(j))
+            {
+                // the decision of gmres_dofs_device_t at this step, on the fetched numbers: <q~, q~> rides behind the dots, and
+                // the exact pass with its second fetch runs only where the function says so (the same bits either way)
+                {
+                    fdd::ProfileScope prof("reduce_vec2_kernel<MultiDotW>", 8.0 * nd * (j + 2 + (nw ? 1 : 0)));
+                    FDD_CALL(fdd_multi_weighted_inner_product_self(sc, ws, qa.as<double>(), ptrs.data(), nullptr, j + 1, nw, nd, stream));
+                }
+                fetch_scalars(coeffs.data(), j + 2);
+                for (int i = 0; i < j + 1; i++) H[i][j] = coeffs[i];
+                double est = 0.0;
+                const bool usable = fdd_norm2_from_projections(coeffs[j + 1], coeffs.data(), j + 1, &est) != 0;
+                const double ratio = est / coeffs[j + 1];
+                if (ratio == ratio and (host_norm_estimated + host_norm_exact == 0 or ratio < host_min_ratio)) host_min_ratio = ratio;
+                (usable ? host_norm_estimated : host_norm_exact)++;
+                if (usable) return std::sqrt(est);
+                {
+                    fdd::ProfileScope prof("reduce_vec2_kernel<MultiAxpyNorm>", 8.0 * nd * (j + 3 + (nw ? 1 : 0)));
+                    FDD_CALL(fdd_multi_axpy_norm2_dev(sc + (j + 2), ws, qa.as<double>(), sc, -1.0, ptrs.data(), j + 1, nw, nd, stream));
+                }
+                fetch_scalars(coeffs.data(), j + 3);
+                return std::sqrt(coeffs[j + 2]);
+            }
             dot_dofs(sc, qa, ptrs.data(), j + 1);
             {
                 fdd::ProfileScope prof("reduce_vec2_kernel<MultiAxpyNorm>", 8.0 * nd * (j + 3 + (nw ? 1 : 0)));

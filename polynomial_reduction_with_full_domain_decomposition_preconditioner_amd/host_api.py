@@ -560,6 +560,14 @@ class Problem:
         _H().call("fddh_helmholtz_node_operator", self.h, _dp(v), _dp(q), len(v), ctypes.byref(vq))
         return q, vq.value
 
+    def inner_norm_counters(self):
+        """{"estimated", "exact", "min_ratio"}: over the life of the problem's Subdomain, the last Arnoldi steps of inner GMRES
+        cycles that took their norm from the projections (flag "last_norm_from_projections"), those that ran the exact pass
+        instead, and the smallest (<q, q> - sum h^2) / <q, q> among them (0.0 before the first)"""
+        est, exact, ratio = ctypes.c_longlong(), ctypes.c_longlong(), ctypes.c_double()
+        _H().call("fddh_inner_norm_counters", self.h, ctypes.byref(est), ctypes.byref(exact), ctypes.byref(ratio))
+        return {"estimated": est.value, "exact": exact.value, "min_ratio": ratio.value}
+
     # --- Neumann and Robin faces (an addition of this build, include/fdd_host.h) ---
     def boundary_info(self):
         """{"faces", "num_faces", "robin_active", "alpha_min", "alpha_max", "shift_support", "indexed_shift",
