@@ -348,14 +348,19 @@ def run_csr_case(gpu, ptr, col, val, ncols, expect_kind=None, exact=True):
         k("fdd_csr_plan_multiply", plan, out, dptr, dcol, dval, du, dw)
         same(host(out), refw)
         if len(val) and not np.all(val == 1.0) and expect_kind == 1:
-            # short even rows: the sliced-ELL copy of the matrix (one lane per row, column-major slices of 64 rows);
-            # same products added in the same order as the row-block kernel: same bits
+            # short even rows: the sliced-ELL copy of the matrix (one lane per row, column-major slices of 64 rows)
             attached = ctypes.c_int(0)
             k("fdd_csr_plan_attach_sell", plan, P(ptr), dptr, dcol, dval, ctypes.c_double(1.5), ctypes.byref(attached))
             widths = np.diff(ptr)
             padded = sum(int(widths[i:i + 64].max()) * 64 for i in range(0, rows, 64))
             assert attached.value == int(padded <= 1.5 * len(val) and len(val) <= 16 * rows)  # one lane per row pays up to 16 entries per row (27-entry rows measured faster on the row-block kernel)
             if attached.value:
+                slices, compact = ctypes.c_int(-1), ctypes.c_int(-1)
+                lib.hip().call("fdd_csr_plan_sell_info", plan, ctypes.byref(slices), ctypes.byref(compact))
+                assert slices.value > 0
+                # fdd_csr_plan_multiply does not look at the sliced-ELL copy: attaching one leaves that entry on the
+                # row-block kernel, with the same bits as before.  Of the calls below only fdd_csr_plan_matvec runs
+                # sell_kernel (every entry that does, bit for bit: test_gpu_sell_entries.py)
                 out.fill_(7.0)
                 k("fdd_csr_plan_multiply", plan, out, dptr, dcol, dval, du, None)
                 same(host(out), ref)
