@@ -17,8 +17,13 @@
  * this path, and cannot be built here (OCCA, HYPRE,
  * gslib, MPI, CUDA absent).  What IS pinned by the reference itself: the GLL
  * tables (nodes, weights, D_hat, J_cf) against special_functions.f compiled
- * with flang (oracle/_ref, tests/golden/gll_tables.json).  Kernel and solver
- * arithmetic is "parity unpinned" upstream: this restatement is the contract.
+ * with flang (oracle/_ref, tests/golden/gll_tables.json), and the kernel
+ * restatements of fdd_oracle_kernels.c / fdd_oracle_f32.c against the four OKL
+ * kernel files compiled as their OCCA-Serial loop nests (okl_serial.sed,
+ * oracle/_ref/libokl_*.so, tests/golden/okl_kernels.json,
+ * tests/test_cpu_okl_reference.py).  Host-side setup, solver recurrences,
+ * composite and V-cycle arithmetic are "parity unpinned" upstream: there this
+ * restatement is the contract.
  *
  * Compile with -O2 -ffp-contract=off (x86-64 baseline has no FMA, matching
  * the reference Makefile's plain `-O2` g++ build of the OCCA-Serial path).

@@ -23,6 +23,21 @@ ORACLE_SO = os.path.join(ORACLE_DIR, "_build", "libfdd_oracle.so")
 SPECLIB_REF_SO = os.path.join(ORACLE_DIR, "_ref", "libspeclib_ref.so")
 GOLDEN_DIR = os.path.join(HERE, "golden")
 
+
+def okl_ref_so(tag):
+    """oracle/_ref/libokl_<tag>.so: one instance of a reference OKL kernel file compiled as its OCCA-Serial loop nest
+    (oracle/Makefile, target ref; tags in okl_cases.REF_LIBS).  Present only where the reference was readable at build."""
+    return os.path.join(ORACLE_DIR, "_ref", "libokl_%s.so" % tag)
+
+
+_okl_ref = {}
+
+
+def okl_ref_lib(tag):
+    if tag not in _okl_ref:
+        _okl_ref[tag] = ctypes.CDLL(okl_ref_so(tag))
+    return _okl_ref[tag]
+
 c_int_p = ctypes.POINTER(ctypes.c_int)
 vp = ctypes.c_void_p
 
